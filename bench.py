@@ -29,6 +29,8 @@ roofline (K1 = k_sample_sell, the dominant kernel; the same block for the chain-
   lds          SQ_LDS_IDX_ACTIVE / 256 CUs / kernel cycles
 
   python bench.py --gpus 1 --steps 256 --warmup 16
+  python bench.py --gpus 1 --steps 256 --warmup 16 --dump-outputs DIR     (+ what the last timed step computed, DIR/<name>.npy: the
+         inputs are seeded, so two builds of the project can be compared output for output)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W            (one rank per GPU, RCCL)
 """
@@ -396,6 +398,32 @@ SIDE = [
 ]
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(smp, out_dir):
+    """What a caller of the timed path receives after its last step, as DIR/<name>.npy (float64, one row per chain, the caller's
+    transcript order): mu (the last draw = the last trace row), counts (the last sweep's allocation), sum_log / sum_log2 (the pooled
+    posterior moments).  Above DUMP_MAX_BYTES a fixed, seeded sample of transcripts is kept, its ids in transcript_index.npy."""
+    import numpy as np
+    C, n = smp.n_chains, smp.n
+    names = ("mu", "counts", "sum_log", "sum_log2")
+    idx = None
+    if len(names) * C * n * 8 > DUMP_MAX_BYTES:
+        keep = (DUMP_MAX_BYTES - 4096) // ((len(names) * C + 1) * 8)      # the arrays, the index and the .npy headers
+        idx = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+    rows = {k: [] for k in names}
+    for c in range(C):
+        sl, sl2, _ = smp.moments(c)
+        for k, v in zip(names, (smp.mu(c), smp.counts(c), sl, sl2)):
+            rows[k].append(v.astype(np.float64) if idx is None else v[idx].astype(np.float64))
+    os.makedirs(out_dir, exist_ok=True)
+    for k in names:
+        np.save(os.path.join(out_dir, k + ".npy"), np.stack(rows[k]))
+    if idx is not None:
+        np.save(os.path.join(out_dir, "transcript_index.npy"), idx.astype(np.float64))
+
+
 def compact(d, drop=()):
     """JSON-line diet: floats to 5 significant digits, the given keys dropped (the driver keeps an 8 KB tail of stdout)."""
     out = {}
@@ -432,6 +460,8 @@ def main():
     ap.add_argument("--full-json", default="", help="also write the unabridged record (every field of every measurement) to this file")
     ap.add_argument("--no-live-pmc", action="store_true", help="do not collect FETCH_SIZE / WRITE_SIZE of K1 in child runs under rocprofv3 "
                     "(roofline.traffic then comes from the committed passes of the same kernel build)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last one computed "
+                    "(mu, counts, moments of every chain; at most 64 MB) to DIR/<name>.npy")
     args = ap.parse_args()
 
     import numpy as np
@@ -556,6 +586,9 @@ def main():
         assert int(smp.counts(0).astype(np.int64).sum()) == inf.total_k
     else:
         assert int(smp.counts(0).astype(np.int64).sum()) == total_reads   # the all-reduced counts: every read of every shard
+    assert smp.iteration == args.warmup + args.steps, "the sampler ran %d iterations, not warmup + steps" % smp.iteration
+    if args.dump_outputs and rank == 0:
+        dump_outputs(smp, args.dump_outputs)
     smp.close()
 
     if rank == 0:
