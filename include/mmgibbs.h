@@ -457,6 +457,38 @@ int mmg_selftest_btrs_pretest(int device, uint64_t seed, int64_t n_cases, double
  * allows itself: 1 is what the sampler runs; smaller values show how much room the bound has. */
 int mmg_selftest_binv_pretest(int device, uint64_t seed, int64_t n_cases, double n_lo, double n_hi, double slack, uint64_t *counts);
 
+/* ---- mmcollapse: candidates collapsed by their mean posterior anti-correlation across samples ----------------------------
+ * src/mmcollapse.cpp:483-561 (covariances of the candidates' traces per sample, mean correlations), :713-747 (row maxima for the
+ * threshold), :758-819 with collapse() at :398-441 (the greedy loop).  The device holds the centred traces of every sample and the
+ * C x C matrix V of mean correlations, not the reference's C x C x S cube of covariances.  Every sum runs in a fixed order and
+ * without floating-point atomics: reruns are bit-identical.  Additive in ABI version 8. */
+typedef struct mmg_collapse mmg_collapse;
+/* observed: [n_cand][n_samples], non-zero where candidate c was observed in sample s (the mask S of :688-698).
+ * trace_len: a positive multiple of 16 (the reference: 1024). */
+int mmg_collapse_create(int device, uint32_t n_samples, uint32_t n_cand, uint32_t trace_len, const uint8_t *observed, mmg_collapse **out);
+/* the raw (not logged) traces of sample s, trace[k * n_cand + c] (the layout of the trace files); centred on the device */
+int mmg_collapse_set_sample(mmg_collapse *h, uint32_t sample, const double *trace);
+/* V once every sample is set: V(i, j) = sum over samples observed in both of cov / sqrt(var) / sqrt(var), over their count */
+int mmg_collapse_correlate(mmg_collapse *h);
+/* rows [first, first + count) of V as it stands, out[r * n_cand + j] */
+int mmg_collapse_get_rows(mmg_collapse *h, uint32_t first, uint32_t count, double *out);
+/* per row of the initial V, the maximum over the off-diagonal entries starting from -1, NaN skipped (:719-730) */
+int mmg_collapse_row_max(mmg_collapse *h, double *out);
+/* The greedy loop: while min V < thr (Armadillo's min: NaN skipped, ties to the first entry in column-major order), merge the pair
+ * (a < b) at the minimum into a -- the summed trace, a's observed mask --, b leaves.  pairs[2 m], pairs[2 m + 1] = a, b and values[m]
+ * = the minimum of merge m.  At most max_merges merges per call; a later call continues.  *stopped = 1 once the minimum reached thr. */
+int mmg_collapse_run(mmg_collapse *h, double thr, uint32_t max_merges, uint32_t *pairs, double *values, uint32_t *n_merges, int32_t *stopped);
+/* device memory the handle holds (it allocates everything at creation) */
+int mmg_collapse_device_bytes(mmg_collapse *h, uint64_t *bytes);
+void mmg_collapse_destroy(mmg_collapse *h);
+/* The output stage (:827-1107) on host traces: trace[k * n_cols + c] (trace_len rows), virtual traces v = Gamma(alpha) * virtual_scale[v]
+ * keyed (seed, stream, a tag of their own, virtual_id[v], row), and n_series output series, series g the sum of its members
+ * (series_member[series_ptr[g] .. series_ptr[g + 1]), in that order; member < n_cols a trace column, n_cols + v virtual trace v).  Per
+ * series: mean of the logged trace, Sokal's var and tau of the logged trace and the return code (as mmg_summary_get). */
+int mmg_collapse_summarize(int device, uint32_t trace_len, uint32_t n_cols, const double *trace, uint32_t n_virtual, const uint64_t *virtual_id,
+                           const double *virtual_scale, double alpha, uint64_t seed, uint32_t stream, uint32_t n_series, const uint64_t *series_ptr,
+                           const uint32_t *series_member, double *log_mean, double *var, double *tau, int32_t *sokal_rc);
+
 #ifdef __cplusplus
 }
 #endif

@@ -129,6 +129,17 @@ SYMBOLS = {
     "mmg_summary_get_proportions": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmg_summary_get_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "mmg_summary_destroy": (None, [C.c_void_p]),
+    "mmg_collapse_create": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "mmg_collapse_set_sample": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "mmg_collapse_correlate": (C.c_int, [C.c_void_p]),
+    "mmg_collapse_get_rows": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "mmg_collapse_row_max": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mmg_collapse_run": (C.c_int, [C.c_void_p, C.c_double, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmg_collapse_device_bytes": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mmg_collapse_destroy": (None, [C.c_void_p]),
+    "mmg_collapse_summarize": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_double,
+                                         C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
     "mmg_group_create": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     "mmg_group_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "mmg_group_destroy": (None, [C.c_void_p]),

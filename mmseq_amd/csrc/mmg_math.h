@@ -92,7 +92,7 @@ MMG_HD double u52(uint32_t a, uint32_t b)
 #endif
 }
 
-enum : uint32_t { TAG_ROW = 1, TAG_GAMMA = 2, TAG_SYNTH_ROW = 3, TAG_SYNTH_TX = 4, TAG_SIMU = 5 };
+enum : uint32_t { TAG_ROW = 1, TAG_GAMMA = 2, TAG_SYNTH_ROW = 3, TAG_SYNTH_TX = 4, TAG_SIMU = 5, TAG_COLLAPSE_SIMU = 6 };
 
 // A stream = (key from seed/chain/tag, counter words id_lo,id_hi,iter) + running block index.
 struct Stream {

@@ -93,6 +93,18 @@ static int launch_series(uint32_t count, uint32_t S, const double *X, uint32_t n
     return MMG_OK;
 }
 
+// twiddle factors of host/numerics.hpp:fft_pow2, computed with the host's cos / sin: tw[half + j] = exp(-2 pi i j / (2 half))
+static std::vector<double> twiddles(uint32_t S)
+{
+    std::vector<double> tw(2 * (size_t)(S ? S : 1), 0.0);
+    for (uint32_t len = 2; len <= S; len <<= 1) {
+        const double ang = -2.0 * M_PI / (double)len;
+        const uint32_t half = len / 2;
+        for (uint32_t j = 0; j < half; ++j) { tw[2 * (half + j)] = std::cos(ang * (double)j); tw[2 * (half + j) + 1] = std::sin(ang * (double)j); }
+    }
+    return tw;
+}
+
 // Step 1: the description is checked and uploaded, the buffers exist, the simulated traces of isoforms without hits (which do not
 // depend on the chain, :971-978) are drawn.  The chain may still be running: nothing of its trace is read here.
 extern "C" int mmg_summary_begin(mmg_sampler *smp, const mmg_summary_desc *d, mmg_summary **out)
@@ -153,17 +165,11 @@ extern "C" int mmg_summary_begin(mmg_sampler *smp, const mmg_summary_desc *d, mm
     Q_TRY(upload((void **)&q->d_multi_t, multi_t.data(), (size_t)n));
     Q_TRY(upload((void **)&q->d_multi_v, multi_v.data(), (size_t)nv));
     Q_TRY(upload((void **)&q->d_pind, d->percentile_index, (size_t)np * 4));
-    // twiddle factors of host/numerics.hpp:fft_pow2, computed with the host's cos / sin: tw[half + j] = exp(-2 pi i j / (2 half))
-    std::vector<double> tw(2 * (size_t)(S ? S : 1), 0.0);
-    for (uint32_t len = 2; len <= S; len <<= 1) {
-        const double ang = -2.0 * M_PI / (double)len;
-        const uint32_t half = len / 2;
-        for (uint32_t j = 0; j < half; ++j) { tw[2 * (half + j)] = std::cos(ang * (double)j); tw[2 * (half + j) + 1] = std::sin(ang * (double)j); }
-    }
+    const std::vector<double> tw = twiddles(S);
     Q_TRY(upload((void **)&q->d_tw, tw.data(), tw.size() * 8));
     Q_TRY(dalloc((void **)&q->d_V, (size_t)S * nv * 8));
     Q_TRY(dalloc((void **)&q->d_propV, (size_t)S * nv * 8));
-    if (nv) hipLaunchKernelGGL(k_virtual_traces, dim3(blocks_of((uint64_t)nv * S)), dim3(256), 0, st, v.cfg.seed, v.cfg.alpha, nv, S, d_vid, d_vscale, q->d_V);
+    if (nv) hipLaunchKernelGGL(k_virtual_traces, dim3(blocks_of((uint64_t)nv * S)), dim3(256), 0, st, v.cfg.seed, 0u, (uint32_t)TAG_SIMU, v.cfg.alpha, nv, S, d_vid, d_vscale, q->d_V);
     Q_TRY(hipGetLastError());
     Q_TRY(hipMalloc((void **)&q->d_ident, (size_t)S * (ni ? ni : 1) * 8));
     Q_TRY(hipMalloc((void **)&q->d_gene, (size_t)S * (ng ? ng : 1) * 8));
@@ -339,3 +345,70 @@ extern "C" int mmg_summary_get_rows(mmg_summary *q, int kind, int first_sample, 
 }
 
 extern "C" void mmg_summary_destroy(mmg_summary *q) { summary_free(q); }
+
+// mmcollapse's output stage (src/mmcollapse.cpp:827-1107) on traces from the host, independent of any sampler: simulated traces of the
+// features without one, sums over the output series (:443-481), then per series the mean of the logged trace and Sokal's var / tau
+// (:923-943) -- k_virtual_traces, k_group_sums and k_series_summary, the kernels of the summary above.
+extern "C" int mmg_collapse_summarize(int device, uint32_t trace_len, uint32_t n_cols, const double *trace, uint32_t n_virtual,
+                                      const uint64_t *virtual_id, const double *virtual_scale, double alpha, uint64_t seed, uint32_t stream,
+                                      uint32_t n_series, const uint64_t *series_ptr, const uint32_t *series_member, double *log_mean,
+                                      double *var, double *tau, int32_t *sokal_rc)
+{
+    if ((n_cols && !trace) || (n_virtual && (!virtual_id || !virtual_scale)) || !series_ptr || (n_series && (!series_member || !log_mean || !var || !tau || !sokal_rc)))
+        return fail(MMG_ERR_ARG, "NULL argument");
+    if (trace_len == 0) return fail(MMG_ERR_ARG, "trace_len must be positive");
+    if (stream > 0x00FFFFFFu) return fail(MMG_ERR_ARG, "stream must fit 24 bits");
+    const uint64_t nm = series_ptr[n_series];
+    for (uint32_t g = 0; g < n_series; ++g)
+        if (series_ptr[g + 1] < series_ptr[g]) return fail(MMG_ERR_ARG, "series_ptr must be non-decreasing");
+    if (series_ptr[0] != 0) return fail(MMG_ERR_ARG, "series_ptr[0] must be 0");
+    for (uint64_t j = 0; j < nm; ++j)
+        if (series_member[j] >= (uint64_t)n_cols + n_virtual) return fail(MMG_ERR_ARG, "series member out of range");
+    int rc = require_device(device);
+    if (rc) return rc;
+    if (n_series == 0) return MMG_OK;
+    const uint32_t S = trace_len, n = n_cols, nv = n_virtual, ng = n_series;
+    std::vector<void *> bufs;
+    struct Freer { std::vector<void *> &b; ~Freer() { for (void *x : b) (void)hipFree(x); } } freer{bufs};
+    auto dalloc = [&](void **p, size_t bytes) { hipError_t e = hipMalloc(p, bytes ? bytes : 8); if (e == hipSuccess) bufs.push_back(*p); return e; };
+    auto upload = [&](void **p, const void *src, size_t bytes) {
+        hipError_t e = dalloc(p, bytes);
+        if (e == hipSuccess && bytes) e = hipMemcpy(*p, src, bytes, hipMemcpyHostToDevice);
+        return e;
+    };
+    double *d_tr = nullptr, *d_vs = nullptr, *d_V = nullptr, *d_G = nullptr, *d_T = nullptr, *d_tw = nullptr;
+    uint64_t *d_vid = nullptr, *d_ptr = nullptr, *d_ws = nullptr;
+    uint32_t *d_mem = nullptr;
+    double *d_lm = nullptr, *d_var = nullptr, *d_tau = nullptr;
+    int32_t *d_rc = nullptr;
+    HIP_TRY(upload((void **)&d_tr, trace, (size_t)S * n * 8));
+    HIP_TRY(upload((void **)&d_vid, virtual_id, (size_t)nv * 8));
+    HIP_TRY(upload((void **)&d_vs, virtual_scale, (size_t)nv * 8));
+    HIP_TRY(upload((void **)&d_ptr, series_ptr, ((size_t)ng + 1) * 8));
+    HIP_TRY(upload((void **)&d_mem, series_member, (size_t)nm * 4));
+    const std::vector<double> tw = twiddles(S);
+    HIP_TRY(upload((void **)&d_tw, tw.data(), tw.size() * 8));
+    HIP_TRY(dalloc((void **)&d_V, (size_t)S * nv * 8));
+    HIP_TRY(dalloc((void **)&d_G, (size_t)S * ng * 8));
+    HIP_TRY(dalloc((void **)&d_T, (size_t)S * ng * 8));
+    HIP_TRY(dalloc((void **)&d_lm, (size_t)ng * 8));
+    HIP_TRY(dalloc((void **)&d_var, (size_t)ng * 8));
+    HIP_TRY(dalloc((void **)&d_tau, (size_t)ng * 8));
+    HIP_TRY(dalloc((void **)&d_rc, (size_t)ng * 4));
+    if (series_workspace_bytes(S)) HIP_TRY(dalloc((void **)&d_ws, series_workspace_bytes(S)));
+    hipStream_t st = nullptr;   // the null stream: the uploads above were synchronous
+    if (nv) hipLaunchKernelGGL(k_virtual_traces, dim3(blocks_of((uint64_t)nv * S)), dim3(256), 0, st, seed, stream, (uint32_t)TAG_COLLAPSE_SIMU, alpha, nv, S,
+                               (const uint64_t *)d_vid, (const double *)d_vs, d_V);
+    hipLaunchKernelGGL(k_group_sums, dim3(blocks_of((uint64_t)ng * S)), dim3(256), 0, st, ng, S, n, nv, (const uint64_t *)d_ptr, (const uint32_t *)d_mem,
+                       (const uint32_t *)nullptr, (const double *)d_tr, (const double *)d_V, d_G);
+    HIP_TRY(hipGetLastError());
+    launch_transpose(d_G, d_T, ng, S, nullptr, st);
+    SeriesOut o{d_lm, d_var, d_tau, d_rc, nullptr, nullptr, nullptr, nullptr};
+    rc = launch_series<true>(ng, S, d_T, 0, nullptr, nullptr, d_tw, o, d_ws, st);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(log_mean, d_lm, (size_t)ng * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(var, d_var, (size_t)ng * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(tau, d_tau, (size_t)ng * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(sokal_rc, d_rc, (size_t)ng * 4, hipMemcpyDeviceToHost));
+    return MMG_OK;
+}

@@ -14,14 +14,15 @@
 
 namespace mmg {
 
-// simulated traces of isoforms without hits (:971-978): V[s * nv + v] = Gamma(alpha) * scale[v], keyed (seed, TAG_SIMU, id[v], s)
-__global__ __launch_bounds__(256) void k_virtual_traces(uint64_t seed, double alpha, uint32_t nv, uint32_t S, const uint64_t *__restrict__ id,
-                                                        const double *__restrict__ scale, double *__restrict__ V)
+// simulated traces of isoforms without hits (:971-978): V[s * nv + v] = Gamma(alpha) * scale[v], keyed (seed, chain, tag, id[v], s)
+// (the summary: chain 0, TAG_SIMU; mmcollapse: chain = the sample, TAG_COLLAPSE_SIMU)
+__global__ __launch_bounds__(256) void k_virtual_traces(uint64_t seed, uint32_t chain, uint32_t tag, double alpha, uint32_t nv, uint32_t S,
+                                                        const uint64_t *__restrict__ id, const double *__restrict__ scale, double *__restrict__ V)
 {
     const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= (uint64_t)nv * S) return;
     const uint32_t s = (uint32_t)(gid / nv), v = (uint32_t)(gid % nv);
-    Stream st(seed, 0, TAG_SIMU, id[v], s);
+    Stream st(seed, chain, tag, id[v], s);
     V[gid] = gamma_unit(st, alpha) * scale[v];
 }
 
