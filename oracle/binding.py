@@ -49,6 +49,7 @@ def lib():
     L.orc_binomial_keyed.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_double]
     L.orc_binomial_keyed.restype = C.c_uint32
     L.orc_simu_gamma_trace.argtypes = [C.c_uint64, C.c_uint64, C.c_double, C.c_double, C.c_int, f64p]
+    L.orc_simu_gamma_trace_keyed.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_double, C.c_double, C.c_int, f64p]
     L.orc_sample_counts.argtypes = [C.c_uint64, C.c_uint32, u64p, u32p, C.c_void_p, f64p, C.c_uint64,
                                     C.c_uint32, C.c_uint32, C.c_uint64, i32p]
     L.orc_gamma_update.argtypes = [C.c_uint32, i32p, f64p, C.c_double, C.c_double, C.c_uint64, C.c_uint32,
@@ -135,6 +136,17 @@ def mt19937(seed, n):
 def simu_gamma_trace(seed, sid, shape, scale, n):
     out = np.empty(n, np.float64)
     lib().orc_simu_gamma_trace(seed, sid, shape, scale, n, out)
+    return out
+
+
+TAG_SIMU, TAG_COLLAPSE_SIMU = 5, 6       # the stream tags of mmg_math.h
+
+
+def simu_gamma_trace_keyed(seed, chain, tag, sid, shape, scale, n):
+    """Gamma(shape) * scale keyed (seed, chain, tag, sid, row): (0, TAG_SIMU) is simu_gamma_trace, mmcollapse's simulated traces
+    use (the sample, TAG_COLLAPSE_SIMU)"""
+    out = np.empty(n, np.float64)
+    lib().orc_simu_gamma_trace_keyed(seed, chain, tag, sid, shape, scale, n, out)
     return out
 
 

@@ -114,7 +114,7 @@ static inline double u52(uint32_t a, uint32_t b)
 }
 
 /* stream tags (high byte of key word 1) */
-enum { ORC_TAG_ROW = 1, ORC_TAG_GAMMA = 2, ORC_TAG_SYNTH_ROW = 3, ORC_TAG_SYNTH_TX = 4, ORC_TAG_SIMU = 5 };
+enum { ORC_TAG_ROW = 1, ORC_TAG_GAMMA = 2, ORC_TAG_SYNTH_ROW = 3, ORC_TAG_SYNTH_TX = 4, ORC_TAG_SIMU = 5, ORC_TAG_COLLAPSE_SIMU = 6 };
 
 typedef struct {
     uint32_t k0, k1;
@@ -317,13 +317,20 @@ double orc_gamma_draw(uint64_t seed, uint32_t chain, uint32_t iter, uint64_t t, 
     return keyed_gamma_unit(&s, shape) * scale;
 }
 
+/* a simulated trace keyed by (seed, chain, tag, id, sample): mmseq's isoforms without hits use (0, SIMU), mmcollapse's features
+ * without a trace (chain = the sample, COLLAPSE_SIMU) */
+void orc_simu_gamma_trace_keyed(uint64_t seed, uint32_t chain, uint32_t tag, uint64_t id, double shape, double scale, int n, double *out)
+{
+    for (int i = 0; i < n; ++i) {
+        orc_stream s = stream_make(seed, chain, tag, id, (uint32_t)i);
+        out[i] = keyed_gamma_unit(&s, shape) * scale;
+    }
+}
+
 /* simulated trace of an isoform without hits (src/mmseq.cpp:971-978), keyed by (seed, SIMU, id, sample) */
 void orc_simu_gamma_trace(uint64_t seed, uint64_t id, double shape, double scale, int n, double *out)
 {
-    for (int i = 0; i < n; ++i) {
-        orc_stream s = stream_make(seed, 0, ORC_TAG_SIMU, id, (uint32_t)i);
-        out[i] = keyed_gamma_unit(&s, shape) * scale;
-    }
+    orc_simu_gamma_trace_keyed(seed, 0, ORC_TAG_SIMU, id, shape, scale, n, out);
 }
 
 /* Stirling-series tail log(k!) - [ (k+1/2)log(k+1) - (k+1) + log(2pi)/2 ] */

@@ -17,24 +17,33 @@ def centre(traces):
     return [np.asarray(t, np.float64) - np.asarray(t, np.float64).mean(axis=0) for t in traces]
 
 
-def _corr(Xc_s, a_cols, b_cols=None):
+def _corr(Xc_s, a_cols, b_cols=None, fixed_order=False):
+    """Covariances of the columns a_cols with b_cols (all).  BLAS sums in an order that depends on an entry's position, so a column
+    scaled by 2^k need not give bit-identical correlations; fixed_order sums over the trace rows in ascending order for every entry,
+    which keeps such exact ties (the device's order is fixed too)."""
     N = Xc_s.shape[0]
     A = Xc_s[:, a_cols]
     B = Xc_s if b_cols is None else Xc_s[:, b_cols]
     with np.errstate(all="ignore"):
-        cov = A.T @ B / (N - 1)
+        if fixed_order:
+            cov = np.zeros((A.shape[1], B.shape[1]))
+            for k in range(N):
+                cov += A[k][:, None] * B[k][None, :]
+            cov /= N - 1
+        else:
+            cov = A.T @ B / (N - 1)
         cov[~np.isfinite(cov)] = 0.0
     return cov
 
 
-def mean_corr(Xc, observed):
+def mean_corr(Xc, observed, fixed_order=False):
     """V (C x C): masked mean over samples of cov / sqrt(var_i) / sqrt(var_j); non-finite covariances -> 0."""
     observed = np.asarray(observed, bool)
     C = observed.shape[0]
     num = np.zeros((C, C))
     cnt = np.zeros((C, C))
     for s, X in enumerate(Xc):
-        cov = _corr(X, slice(None))
+        cov = _corr(X, slice(None), fixed_order=fixed_order)
         d = np.sqrt(np.diag(cov).copy())
         with np.errstate(all="ignore"):
             r = cov / d[:, None] / d[None, :]
@@ -73,25 +82,31 @@ def vmin(V):
 
 
 def second_gap(V, a, b):
-    """Distance from the minimum to the smallest entry outside the pair (a, b) / (b, a)."""
+    """Distance from the minimum to the smallest entry outside the pair (a, b) / (b, a) that is not bit-equal to V(a, b) or V(b, a),
+    and the number of entries that are (exact ties, which the column-major rule decides)."""
     W = np.array(V, copy=True)
     W[a, b] = W[b, a] = np.nan
+    same = (W == V[a, b]) | (W == V[b, a])
+    ties = int(np.count_nonzero(same))
+    W[same] = np.nan
     if np.all(np.isnan(W)):
-        return np.inf
-    return np.nanmin(W) - V[a, b]
+        return np.inf, ties
+    return np.nanmin(W) - V[a, b], ties
 
 
 class Greedy:
     """The loop of :758-819 on centred traces: merge the pair at the minimum into the lower index (summed traces, the lower
     member's mask), the higher index NaN, rows / columns of both recomputed (:483-512 with ts = {a, b})."""
 
-    def __init__(self, traces, observed, names=None):
+    def __init__(self, traces, observed, names=None, fixed_order=False):
         self.Xc = centre(traces)
         self.obs = np.array(observed, bool)
         self.C = self.obs.shape[0]
-        self.V = mean_corr(self.Xc, self.obs)
+        self.fixed_order = fixed_order
+        self.V = mean_corr(self.Xc, self.obs, fixed_order)
         self.dead = np.zeros(self.C, bool)
         self.names = list(names) if names is not None else [str(i) for i in range(self.C)]
+        self.exact_ties = 0          # picks of run(tie_tol=...) where another entry equalled the minimum bit for bit
 
     def merge(self, a, b):
         for X in self.Xc:
@@ -100,9 +115,9 @@ class Greedy:
         num = np.zeros(self.C)
         cnt = np.zeros(self.C)
         for s, X in enumerate(self.Xc):
-            cov = _corr(X, [a])[0]
+            cov = _corr(X, [a], fixed_order=self.fixed_order)[0]
             va = cov[a]
-            dj = np.einsum("ij,ij->j", X, X) / (X.shape[0] - 1)
+            dj = ((X * X).sum(axis=0) if self.fixed_order else np.einsum("ij,ij->j", X, X)) / (X.shape[0] - 1)
             dj[~np.isfinite(dj)] = 0.0
             dj[a] = va
             with np.errstate(all="ignore"):
@@ -122,11 +137,12 @@ class Greedy:
         self.names[a] = t[0] + "*" + t[1]
         self.names[b] = "NA"
 
-    def run(self, thr, tie_tol=None):
+    def run(self, thr, tie_tol=None, max_merges=None):
         """Returns the merge list [(a, b, value)]; with tie_tol, asserts no decision lies within tie_tol of a tie (the pick, and
-        the stop against thr)."""
+        the stop against thr).  Entries bit-equal to the minimum are exact ties, not near ones: vmin's column-major rule decides
+        them, and they are counted in self.exact_ties.  With max_merges, returns after that many merges; a later call continues."""
         merges = []
-        while True:
+        while max_merges is None or len(merges) < max_merges:
             m = vmin(self.V)
             if m is None:
                 break
@@ -137,7 +153,9 @@ class Greedy:
                 break
             a, b = min(r, c), max(r, c)
             if tie_tol is not None:
-                assert second_gap(self.V, a, b) > tie_tol, "pick %d is within %g of a tie" % (len(merges), tie_tol)
+                gap, ties = second_gap(self.V, a, b)
+                assert gap > tie_tol, "pick %d is within %g of a tie" % (len(merges), tie_tol)
+                self.exact_ties += ties > 0
             merges.append((a, b, v))
             self.merge(a, b)
         return merges
@@ -278,9 +296,31 @@ def uh(base, series):
     return res
 
 
+SIMU_SEED, ALPHA, BETA = 13837, 0.1, 0.1
+
+
+def simulated(cd, s, ids):
+    """The features of the first sample's list (cd["all_features"]) that sample s's traces (ids) lack, as [(index in that list,
+    name, scale)]: scale = 1 / (0.1 + efflen * mapped / 1e9) with the efflen of sample s's zero rows and its "# Mapped fragments"."""
+    per, have = cd["per"][s], set(ids)
+    return [(f, name, 1.0 / (BETA + per["zero_efflen"][name] * float(per["mapped"]) / 1e9))
+            for f, name in enumerate(cd["all_features"]) if name not in have]
+
+
+def simulate_missing(ids, M, cd, s):
+    """The trace matrix of sample s extended by the simulated traces of its features without one (difference
+    1): Gamma(0.1) * scale keyed (13837, chain s, TAG_COLLAPSE_SIMU, the feature's index in the first sample's list, the row),
+    appended after the real columns in the order of that list."""
+    from oracle import binding as B
+    sim = simulated(cd, s, ids)
+    cols = [B.simu_gamma_trace_keyed(SIMU_SEED, s, B.TAG_COLLAPSE_SIMU, f, ALPHA, sc, M.shape[0]) for f, _, sc in sim]
+    return list(ids) + [n for _, n, _ in sim], np.concatenate([M] + [c[:, None] for c in cols], axis=1)
+
+
 def run(basenames, thres=0.975, tie_tol=None):
     """The whole tool; returns (merges, final candidate names, {base: (comment lines, rows)}) with rows
-    [name, log_mu, sd, mcse, iact, unique_hits] sorted by name.  Features without a trace are not supported here."""
+    [name, log_mu, sd, mcse, iact, unique_hits] sorted by name.  A feature without a trace in a sample gets the simulated trace of
+    simulate_missing."""
     from oracle import binding as B
     cd = candidates(basenames)
     cand = cd["candidates"]
@@ -306,9 +346,7 @@ def run(basenames, thres=0.975, tie_tol=None):
     out = {}
     for s, base in enumerate(basenames):
         ids, M = samp[s]
-        missing = [f for f in cd["all_features"] if f not in set(ids)]
-        assert not missing, "the restatement does not simulate traces"
-        ids = list(ids)
+        ids, M = simulate_missing(ids, M, cd, s)
         tmap = {f: i for i, f in enumerate(ids)}
         shed = set()
         M = M.copy()
