@@ -489,6 +489,33 @@ int mmg_collapse_summarize(int device, uint32_t trace_len, uint32_t n_cols, cons
                            const double *virtual_scale, double alpha, uint64_t seed, uint32_t stream, uint32_t n_series, const uint64_t *series_ptr,
                            const uint32_t *series_member, double *log_mean, double *var, double *tau, int32_t *sokal_rc);
 
+
+/* ---- mmdiff: Bayesian model selection between two linear models per feature -------------------------------------------
+ * src/bms.cpp driven as src/mmdiff.cpp:744-866: per feature an independent MCMC over both models with pseudopriors, the model
+ * indicator gamma and a tuned prior log odds.  One lane per feature, state in device memory; the host drives the phases:
+ * create, burnin once, tune_batch until the untuned count is 0 or the caller's batch limit (none for -notune), sample, get_results.
+ * Keyed streams (seed, 0, TAG_DIFF, feature, iteration): reruns are bit-identical.  Additive in ABI version 8. */
+typedef struct mmg_diff mmg_diff;
+/* y, e: [F][N] estimates and their standard deviations; M: [N][K] covariates; P0: [N][L0], P1: [N][L1] the models' predictors;
+ * C: [N][2] the variance class of sample i under model m, labelled 0 .. n_m - 1.  A single column that varies by less than 1e-5 is
+ * "nil" (no covariate), as in the reference.  Caps: N <= 512, K <= 8, L0, L1 <= 16, 16 classes per model. */
+int mmg_diff_create(int device, uint32_t n_features, uint32_t n_samples, const double *y, const double *e, uint32_t K, const double *M,
+                    uint32_t L0, const double *P0, uint32_t L1, const double *P1, const int32_t *C, double d, double s, double pdash,
+                    int fixalpha, uint64_t seed, mmg_diff **out);
+/* the burn-in (a positive multiple of 1024 iterations, recorded from iteration 102), then the pseudopriors from its record */
+int mmg_diff_burnin(mmg_diff *h, uint32_t iters);
+/* one tuning batch of 128 iterations; *untuned = the features still untuned after the batch's tuning step */
+int mmg_diff_tune_batch(mmg_diff *h, uint32_t *untuned);
+/* iters sampling iterations (may be called again to continue) */
+int mmg_diff_sample(mmg_diff *h, uint32_t iters);
+/* gamma_mean[F], logitp[F], alpha[2][F], beta[2][K][F], eta[L0 + L1][F] (model 0's columns first): posterior means over the
+ * sampling iterations, each as sum / count; any pointer may be NULL */
+int mmg_diff_get_results(mmg_diff *h, double *gamma_mean, double *logitp, double *alpha, double *beta, double *eta);
+/* flags[3] = (M nil, P0 nil, P1 nil), n_classes[2], the tuning batches run so far; any pointer may be NULL */
+int mmg_diff_info(mmg_diff *h, int32_t *flags, uint32_t *n_classes, uint32_t *batches);
+int mmg_diff_device_bytes(mmg_diff *h, uint64_t *bytes);
+void mmg_diff_destroy(mmg_diff *h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -137,6 +137,15 @@ SYMBOLS = {
     "mmg_collapse_run": (C.c_int, [C.c_void_p, C.c_double, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmg_collapse_device_bytes": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mmg_collapse_destroy": (None, [C.c_void_p]),
+    "mmg_diff_create": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
+                                  C.c_uint32, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int, C.c_uint64, C.c_void_p]),
+    "mmg_diff_burnin": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "mmg_diff_tune_batch": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mmg_diff_sample": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "mmg_diff_get_results": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmg_diff_info": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmg_diff_device_bytes": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mmg_diff_destroy": (None, [C.c_void_p]),
     "mmg_collapse_summarize": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_double,
                                          C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),

@@ -1,0 +1,633 @@
+// mmdiff_main.cpp -- drop-in for the reference's mmdiff (src/mmdiff.cpp): Bayesian model selection between two linear models of
+// every feature's expression across samples.  Tables, normalisation, permutation and the design matrices on the host; the
+// per-feature MCMC (src/bms.cpp) on the device through the C ABI (include/mmgibbs.h: mmg_diff_*).  Deliberate differences from the
+// reference are listed in DESIGN.md section 10: keyed streams instead of one MT19937 per thread, a keyed shuffle for -permute, no
+// -tracedir, size caps, dlgamma for gsl_sf_lngamma.
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <fstream>
+#include <iostream>
+#include <string>
+#include <vector>
+
+#include "../../../include/mmgibbs.h"
+#include "../mmg_math.h"
+
+using namespace std;
+
+#define OUTLEN 1024
+#define MAXBATCHES 8192
+
+namespace {
+
+typedef vector<double> Mat;   // row-major, with the shape carried alongside
+
+[[noreturn]] void die(const string &msg)
+{
+    cerr << msg << endl;
+    exit(1);
+}
+
+void tokenise(const string &str, vector<string> &tokens, const string &delimiters = " ")
+{
+    string::size_type lastPos = str.find_first_not_of(delimiters, 0);
+    string::size_type pos = str.find_first_of(delimiters, lastPos);
+    while (string::npos != pos || string::npos != lastPos) {
+        tokens.push_back(str.substr(lastPos, pos - lastPos));
+        lastPos = str.find_first_not_of(delimiters, pos);
+        pos = str.find_first_of(delimiters, lastPos);
+    }
+}
+
+bool endsWith(const string &a, const string &b)
+{
+    if (b.size() > a.size()) return false;
+    return std::equal(a.begin() + a.size() - b.size(), a.end(), b.begin());
+}
+
+// ostream's default formatting of a double (%g, 6 digits); NaN prints as x86-64's 0.0 / 0.0 does in the reference
+string fmt(double x)
+{
+    if (std::isnan(x)) return std::signbit(x) ? "-nan" : "nan";
+    char buf[64];
+    snprintf(buf, sizeof buf, "%g", x);
+    return buf;
+}
+
+void printUsage(ostream &out)
+{
+    out << "Usage: mmdiff [OPTIONS...] [-de n1 n2 ... nC | -m matrices_file] mmseq_file1 mmseq_file2... > out.mmdiff" << endl
+        << "       matrices_file contains M P0 P1 each separated by an empty line" << endl
+        << endl;
+    out << "Mandatory arguments:" << endl
+        << "  ONE OF:" << endl
+        << "  -de INT INT...    simple differential expression between several groups of samples, where" << endl
+        << "                    each INT corresponds to a grouping of MMSEQ files into one condition" << endl
+        << "  -m STRING         path to matrices file specifying the two models to compare" << endl;
+    out << "Optional arguments:" << endl
+        << "  -tracedir STRING  not implemented in this version: MCMC traces are not written (exits with an error)" << endl
+        << "  -useprops         run on isoform/gene proportions instead of expression" << endl
+        << "  -permute          run on permuted dataset (a keyed shuffle per feature); combine with non-permuted results to obtain q-values" << endl
+        << "  -p FLOAT          prior probability of the second model (default: 0.1)" << endl
+        << "  -d FLOAT          d hyperparameter (default: 1.4)" << endl
+        << "  -s FLOAT          s hyperparameter (default: 2.0)" << endl
+        << "  -l INT            length of MCMC trace used to produce the input estimates (default: 1024)" << endl
+        << "  -fixalpha         fix alpha=0 and do not update (default: estimate alpha)" << endl
+        << "  -nonorm           do not normalise the input data" << endl
+        << "  -pdash FLOAT      initial value of pdash for improved mixing of gamma (stays fixed if -notune is set) (default: 0.5)" << endl
+        << "  -notune           do not tune pdash to improve mixing for gamma" << endl
+        << "  -uhfrac FLOAT     if normalising, use features which have at least one unique hit" << endl
+        << "                    in at least uhfrac of the samples (default: max(0.2, (N - floor(N^2/160))/N))" << endl
+        << "  -burnin INT       burnin iterations (default: 8192)" << endl
+        << "  -iter INT         MCMC iterations (default: 16384)" << endl
+        << "  -seed INT         seed for PRNG (default: 1234)" << endl
+        << "  -range INT INT    select features indexed within range (default: all)" << endl
+        << "Size limits: 512 samples, 8 columns of M, 16 columns of P0 and P1, 16 variance classes per model." << endl;
+}
+
+[[noreturn]] void usage_error(const string &msg)
+{
+    cerr << msg << endl;
+    printUsage(cerr);
+    exit(1);
+}
+
+// src/mmdiff.cpp parse_mmseq: y, e, uh as [feature][sample]
+void parse_mmseq(const vector<string> &filenames, vector<string> &features, Mat &y, Mat &e, Mat &uh, int range_start, int range_end,
+                 bool useprops)
+{
+    const size_t S = filenames.size();
+    vector<vector<double>> cy(S), ce(S), cu(S);
+    cerr << "Parsing ";
+    for (size_t i = 0; i < S; ++i) {
+        cerr << filenames[i] << " ";
+        ifstream ifs(filenames[i].c_str());
+        if (!ifs.good()) die("\nError: couldn't open " + filenames[i]);
+        string str;
+        getline(ifs, str);
+        while (!ifs.eof() && !str.empty() && str[0] == '#') getline(ifs, str);
+        vector<string> tokens;
+        tokenise(str, tokens, "\t");
+        int feature_ind = -1, lmg_ind = -1, sd_ind = -1, mp_ind = -1, sp_ind = -1, uh_ind = -1;
+        for (int j = 0; j < (int)tokens.size(); ++j) {
+            if (tokens[j] == "feature_id") feature_ind = j;
+            if (tokens[j] == "log_mu") lmg_ind = j;
+            if (tokens[j] == "sd") sd_ind = j;
+            if (tokens[j] == "mean_probit_proportion") mp_ind = j;
+            if (tokens[j] == "sd_probit_proportion") sp_ind = j;
+            if (tokens[j] == "unique_hits") uh_ind = j;
+        }
+        if (useprops) {
+            if ((feature_ind + 1) * (mp_ind + 1) * (sp_ind + 1) * (uh_ind + 1) == 0)
+                die("\nError: input tables must have feature_id, mean_probit_proportion, sd_probit_proportion and unique_hits columns.");
+        } else {
+            if ((feature_ind + 1) * (lmg_ind + 1) * (sd_ind + 1) * (uh_ind + 1) == 0)
+                die("\nError: input tables must have feature_id, log_mu, sd and unique_hits columns.");
+        }
+        const int yi = useprops ? mp_ind : lmg_ind, ei = useprops ? sp_ind : sd_ind;
+        const int need = max(max(feature_ind, yi), max(ei, uh_ind));
+        size_t k = 0;
+        while (true) {
+            getline(ifs, str);
+            if (ifs.eof()) break;
+            tokens.clear();
+            tokenise(str, tokens, "\t");
+            if ((int)tokens.size() <= need) die("\nError: line " + to_string(k + 2) + " of " + filenames[i] + " has too few columns.");
+            if (k + 1 > features.size()) {
+                if (i > 0) die("\nError: features across files do not match (" + to_string(k) + "," + tokens[feature_ind] + ",)");
+                features.push_back(tokens[feature_ind]);
+            } else if (features[k] != tokens[feature_ind]) {
+                die("\nError: features across files do not match (" + to_string(k) + "," + tokens[feature_ind] + "," + features[k] + ")");
+            }
+            if (tokens[yi] == "NA") die("\nError: encountered NA");
+            cy[i].push_back(atof(tokens[yi].c_str()));
+            ce[i].push_back(atof(tokens[ei].c_str()));
+            cu[i].push_back(atof(tokens[uh_ind].c_str()));
+            ++k;
+        }
+        if (k != features.size())
+            die("\nError: features across files do not match (" + to_string(k) + ",," + (k < features.size() ? features[k] : string()) + ")");
+    }
+    size_t lo = 0, hi = features.size();   // [lo, hi)
+    if (range_start >= 0 && range_end > range_start && (size_t)range_end < features.size()) { lo = range_start; hi = (size_t)range_end + 1; }
+    vector<string> kept;
+    y.clear(); e.clear(); uh.clear();
+    for (size_t f = lo; f < hi; ++f) {
+        if (useprops && std::isinf(cy[0][f])) continue;   // single-isoform genes: infinite probit proportions
+        kept.push_back(features[f]);
+        for (size_t i = 0; i < S; ++i) { y.push_back(cy[i][f]); e.push_back(ce[i][f]); uh.push_back(cu[i][f]); }
+    }
+    features = kept;
+    // the device samplers need finite estimates: "nan" and "inf" entries (atof accepts them) are errors, as "NA" is
+    for (size_t f = 0; f < features.size(); ++f)
+        for (size_t i = 0; i < S; ++i)
+            if (!std::isfinite(y[f * S + i]) || !std::isfinite(e[f * S + i]))
+                die("\nError: encountered a non-finite value (feature " + features[f] + " in " + filenames[i] + ")");
+    if (useprops) cerr << endl << "Kept " << features.size() << " transcripts belonging to multi-isoform genes";
+    else cerr << endl << "Analysing " << features.size() << " features";
+    cerr << endl;
+}
+
+// DESeq style: y[,i] <- y[,i] - median(y[,i] - rowMeans(y)) over the features with unique hits in at least uhfrac of the samples
+void apply_normalisation(const vector<string> &filenames, Mat &y, const Mat &uh, size_t F, size_t S, double uhfrac)
+{
+    vector<size_t> use;
+    for (size_t i = 0; i < F; ++i) {
+        int sum = 0;
+        for (size_t j = 0; j < S; ++j)
+            if (uh[i * S + j] > 0) sum++;
+        if ((double)sum / (double)S >= uhfrac) use.push_back(i);
+    }
+    if (use.size() < 100) {
+        cerr << "Warning: fewer than 100 features found for normalisation. Skipping.\n";
+        return;
+    }
+    cerr << "Using " << use.size() << "/" << F << " features for normalisation.\n";
+    vector<double> rowMeans;
+    for (size_t i = 0; i < use.size(); ++i) {
+        double sum = 0;
+        for (size_t j = 0; j < S; ++j) sum += y[use[i] * S + j];
+        rowMeans.push_back(sum / (double)S);
+    }
+    cerr << "Log scale normalisation factors:\n";
+    for (size_t sample = 0; sample < S; ++sample) {
+        vector<double> ydiff;
+        for (size_t i = 0; i < use.size(); ++i) ydiff.push_back(y[use[i] * S + sample] - rowMeans[i]);
+        sort(ydiff.begin(), ydiff.end());
+        const double m = ydiff[ydiff.size() / 2];
+        cerr << "\t" << filenames[sample] << "\t" << m << endl;
+        for (size_t i = 0; i < F; ++i) y[i * S + sample] = y[i * S + sample] - m;
+    }
+}
+
+// -permute: a Fisher-Yates shuffle of each feature's samples, keyed (seed, 0, TAG_DIFF_PERM, feature, 0) -- the same for every
+// thread count and machine (the reference calls random_shuffle)
+void apply_permutation(Mat &y, Mat &e, size_t F, size_t S, uint64_t seed)
+{
+    cerr << "Permuting input data...";
+    vector<size_t> idx(S);
+    vector<double> ny(S), ne(S);
+    for (size_t f = 0; f < F; ++f) {
+        for (size_t j = 0; j < S; ++j) idx[j] = j;
+        mmg::SeqStream q(mmg::Stream(seed, 0, mmg::TAG_DIFF_PERM, f, 0));
+        for (size_t j = S - 1; j > 0; --j) {
+            size_t k = (size_t)(q.next() * (double)(j + 1));
+            if (k > j) k = j;
+            swap(idx[j], idx[k]);
+        }
+        for (size_t j = 0; j < S; ++j) { ny[j] = y[f * S + idx[j]]; ne[j] = e[f * S + idx[j]]; }
+        for (size_t j = 0; j < S; ++j) { y[f * S + j] = ny[j]; e[f * S + j] = ne[j]; }
+    }
+    cerr << "done\n";
+}
+
+struct Design {
+    size_t N = 0, K = 0, L0 = 0, L1 = 0, CC = 0;
+    Mat M, P0, P1;
+    vector<int> C;   // [N][CC]
+};
+
+void resize_cols(Mat &X, size_t N, size_t &cols, size_t ncols)
+{
+    if (ncols == cols) return;
+    Mat Y(N * ncols, 0.0);
+    for (size_t i = 0; i < N; ++i)
+        for (size_t j = 0; j < min(cols, ncols); ++j) Y[i * ncols + j] = X[i * cols + j];
+    X.swap(Y);
+    cols = ncols;
+}
+
+// src/mmdiff.cpp parse_matrices: blocks M, C, P0, P1 separated by empty lines; "#" starts a comment; P rows are per class
+void parse_matrices(const string &file, Design &D, size_t nrows)
+{
+    ifstream ifs(file.c_str());
+    if (!ifs.good()) die("Error: couldn't open " + file);
+    D.N = nrows;
+    vector<double> Cd;
+    string str;
+    vector<string> tokens;
+    int m = -1;
+    size_t i = 0;
+    int P0reducedcols = 0, P1reducedcols = 0;
+    auto maxC = [&](int col) { int r = INT32_MIN; for (size_t j = 0; j < nrows; ++j) r = max(r, D.C[j * D.CC + col]); return r; };
+    while (true) {
+        bool spacer = false;
+        do {
+            if (!ifs.eof()) getline(ifs, str);
+            else str = "";
+            str = str.substr(0, str.find_first_of("#"));
+            tokens.clear();
+            tokenise(str, tokens, " \t");
+            if (tokens.size() < 1) spacer = true;
+        } while (!ifs.eof() && tokens.size() < 1);
+        if (str.size() == 0 && ifs.eof()) break;
+        if (spacer) { m++; i = 0; }
+        if (m == -1) m = 0;
+        if (m > 3) die("Error: more than four matrices in " + file + ".");
+        if (m == 0) resize_cols(D.M, nrows, D.K, tokens.size());
+        if (m == 1) {
+            if (D.C.size() != nrows * tokens.size()) {
+                vector<int> nc(nrows * tokens.size(), 0);
+                for (size_t r = 0; r < nrows; ++r)
+                    for (size_t c = 0; c < min(D.CC, tokens.size()); ++c) nc[r * tokens.size() + c] = D.C[r * D.CC + c];
+                D.C.swap(nc);
+                D.CC = tokens.size();
+            }
+        }
+        if (m == 2) resize_cols(D.P0, nrows, D.L0, tokens.size());
+        if (m == 3) resize_cols(D.P1, nrows, D.L1, tokens.size());
+        if (i >= nrows) die("Error: number of rows of matrices greater than number of samples.");
+        if ((m == 2 || m == 3) && D.CC < 2) die("Error: the class matrix (the second block) must have two columns.");
+        for (size_t t = 0; t < tokens.size(); ++t) {
+            if (m == 0) D.M[i * D.K + t] = atof(tokens[t].c_str());
+            if (m == 1) D.C[i * D.CC + t] = atoi(tokens[t].c_str());
+            if (m == 2 || m == 3) {
+                const int col = m - 2;
+                const int mc = maxC(col);
+                if ((int)i > mc)
+                    die("Error: more distinct rows of P than classes for model " + to_string(col) + " (" + to_string(i) + " > " + to_string(mc) + ").");
+                Mat &P = col ? D.P1 : D.P0;
+                const size_t L = col ? D.L1 : D.L0;
+                for (size_t j = 0; j < nrows; ++j)
+                    if (D.C[j * D.CC + col] == (int)i) P[j * L + t] = atof(tokens[t].c_str());
+                int &red = col ? P1reducedcols : P0reducedcols;
+                red = max(red, (int)i);
+            }
+        }
+        i++;
+    }
+    if (D.K == 0 || D.CC == 0 || D.L0 == 0 || D.L1 == 0) die("Error: Rows in M, P0, P1 and number of mmseq files must match.");
+    if (D.CC != 2) die("Error: the class matrix (the second block) must have two columns.");
+    int cmin = INT32_MAX;
+    for (int c : D.C) cmin = min(cmin, c);
+    if (cmin != 0) die("Error: need at least one class in each model labelled 0.");
+    if (maxC(0) != P0reducedcols) die("Error: number of classes does not correspond to number of disinct rows of P for model 0.");
+    if (maxC(1) != P1reducedcols) die("Error: number of classes does not correspond to number of disinct rows of P for  model 1.");
+}
+
+// det(Z'Z) == 0 by Gaussian elimination with partial pivoting (what the reference's det() decides for exactly singular products)
+bool singular_gram(const Mat &Z, size_t N, size_t cols)
+{
+    if (cols == 0) return false;
+    vector<double> G(cols * cols, 0.0);
+    for (size_t a = 0; a < cols; ++a)
+        for (size_t b = 0; b < cols; ++b)
+            for (size_t i = 0; i < N; ++i) G[a * cols + b] += Z[i * cols + a] * Z[i * cols + b];
+    for (size_t c = 0; c < cols; ++c) {
+        size_t piv = c;
+        for (size_t r = c + 1; r < cols; ++r)
+            if (fabs(G[r * cols + c]) > fabs(G[piv * cols + c])) piv = r;
+        if (G[piv * cols + c] == 0.0) return true;
+        for (size_t k = 0; k < cols; ++k) swap(G[c * cols + k], G[piv * cols + k]);
+        for (size_t r = c + 1; r < cols; ++r) {
+            const double fct = G[r * cols + c] / G[c * cols + c];
+            for (size_t k = c; k < cols; ++k) G[r * cols + k] -= fct * G[c * cols + k];
+        }
+    }
+    return false;
+}
+
+bool is_nil(const Mat &X, size_t N, size_t cols)
+{
+    if (cols != 1) return false;
+    const double lo = *min_element(X.begin(), X.end()), hi = *max_element(X.begin(), X.end());
+    return hi - lo < 0.00001;
+}
+
+void append_cols(Mat &Z, size_t N, size_t &zc, const Mat &X, size_t xc)
+{
+    Mat Y(N * (zc + xc));
+    for (size_t i = 0; i < N; ++i) {
+        for (size_t j = 0; j < zc; ++j) Y[i * (zc + xc) + j] = Z[i * zc + j];
+        for (size_t j = 0; j < xc; ++j) Y[i * (zc + xc) + zc + j] = X[i * xc + j];
+    }
+    Z.swap(Y);
+    zc += xc;
+}
+
+void check_design(const Design &D, bool fixalpha, bool Mnil, const bool Pnil[2])
+{
+    for (int model = 0; model < 2; ++model) {
+        cerr << "Design matrix for model " << model << " ([";
+        if (!fixalpha) cerr << "1";
+        if (!fixalpha && (!Mnil || !Pnil[model])) cerr << "|";
+        if (!Mnil) cerr << "M";
+        if (!Pnil[model] && (!fixalpha || !Mnil)) cerr << "|";
+        if (!Pnil[model]) cerr << "P0";
+        cerr << "]):\n";
+        size_t zc = fixalpha ? 0 : 1;
+        Mat Z(D.N * zc, 1.0);
+        if (!Mnil) append_cols(Z, D.N, zc, D.M, D.K);
+        if (singular_gram(Z, D.N, zc)) die("Error: collinearity in combined matrix of intercept and covariates for model " + to_string(model));
+        const Mat &P = model ? D.P1 : D.P0;
+        const size_t L = model ? D.L1 : D.L0;
+        if (!Pnil[model]) {
+            append_cols(Z, D.N, zc, P, L);
+            if (singular_gram(P, D.N, L)) die("Error: collinearity in matrix P" + to_string(model));
+        }
+        for (size_t i = 0; i < D.N; ++i) {
+            for (size_t j = 0; j < zc; ++j) {
+                char buf[32];
+                snprintf(buf, sizeof buf, "%10.4f", Z[i * zc + j]);
+                cerr << buf;
+            }
+            cerr << "\n";
+        }
+        if (singular_gram(Z, D.N, zc)) cerr << "Warning: collinearity in full matrix of predictors for model " << model << endl;
+    }
+}
+
+#define MMG_CHECK(call)                                                                                       \
+    do {                                                                                                      \
+        if ((call) != 0) die(string("Error: ") + #call + ": " + mmg_last_error());                           \
+    } while (0)
+
+bool need(const vector<string> &a, size_t n)
+{
+    if (a.size() < n) usage_error("Error: mandatory arguments missing.");
+    return true;
+}
+
+} // namespace
+
+int main(int argc, char **argv)
+{
+    string matrices_file = "";
+    double p = 0.1, d = 1.4, s = 2.0;
+    int burnin = 8192, mcmciters = 16384, seed = 1234, range_start = -1, range_end = -1;
+    bool useprops = false, fixalpha = false, normalise = true, customuhfrac = false, permute = false, tune = true;
+    double uhfrac = -1, pdash = 0.5;
+    vector<int> simple_de;
+    int ss = 0;
+
+    vector<string> arguments;
+    for (int i = 1; i < argc; i++) arguments.push_back(string(argv[i]));
+
+    while (true) {
+        const string a0 = arguments.empty() ? string() : arguments[0];
+        auto take = [&]() { arguments.erase(arguments.begin()); need(arguments, 1); string v = arguments[0]; arguments.erase(arguments.begin()); return v; };
+        if (a0 == "-tracedir") {
+            die("Error: -tracedir is not implemented in this version of mmdiff (MCMC traces are not written).");
+        } else if (a0 == "-m" || a0 == "-de") {
+            arguments.erase(arguments.begin());
+            for (size_t i = 0; i < arguments.size(); i++)
+                if (arguments[i].find("-") == 0) {
+                    cerr << "Error: optional arguments must be specified before -de or -m." << endl << endl;
+                    printUsage(cerr);
+                    exit(1);
+                }
+            if (a0 == "-m") {
+                need(arguments, 1);
+                matrices_file = arguments[0];
+                arguments.erase(arguments.begin());
+            } else {
+                cerr << "Number of samples in each group:";
+                while (ss < (int)arguments.size()) {
+                    simple_de.push_back(atoi(arguments[0].c_str()));
+                    cerr << " " << simple_de.back();
+                    arguments.erase(arguments.begin());
+                    if (simple_de.back() < 1) die("\nError: each grouping must contain at least one sample");
+                    ss += simple_de.back();
+                }
+                cerr << endl;
+                if (ss != (int)arguments.size()) die("Error: total number of samples specified with -de must equal number of MMSEQ files");
+            }
+        } else if (a0 == "-useprops") {
+            arguments.erase(arguments.begin());
+            useprops = true;
+        } else if (a0 == "-p") {
+            p = strtod(take().c_str(), NULL);
+            if (!(p >= 0 && p <= 1)) die("Error: p must be between 0 and 1.");
+        } else if (a0 == "-s") {
+            s = strtod(take().c_str(), NULL);
+            if (!(s > 0) || !std::isfinite(s)) die("Error: s must be positive.");
+        } else if (a0 == "-d") {
+            d = strtod(take().c_str(), NULL);
+            if (!(d > 0) || !std::isfinite(d)) die("Error: d must be positive.");
+        } else if (a0 == "-pdash") {
+            pdash = strtod(take().c_str(), NULL);
+            if (!(pdash >= 0 && pdash <= 1)) die("Error: pdash must be between 0 and 1.");
+        } else if (a0 == "-fixalpha") {
+            arguments.erase(arguments.begin());
+            fixalpha = true;
+        } else if (a0 == "-l") {
+            take();   // accepted for compatibility; the reference does not use it either
+        } else if (a0 == "-burnin") {
+            burnin = atoi(take().c_str());
+        } else if (a0 == "-iter") {
+            mcmciters = atoi(take().c_str());
+        } else if (a0 == "-seed") {
+            seed = atoi(take().c_str());
+        } else if (a0 == "-nonorm") {
+            arguments.erase(arguments.begin());
+            normalise = false;
+        } else if (a0 == "-notune") {
+            arguments.erase(arguments.begin());
+            tune = false;
+        } else if (a0 == "-permute") {
+            arguments.erase(arguments.begin());
+            permute = true;
+        } else if (a0 == "-uhfrac") {
+            customuhfrac = true;
+            uhfrac = atof(take().c_str());
+        } else if (a0 == "-range") {
+            arguments.erase(arguments.begin());
+            need(arguments, 2);
+            range_start = atoi(arguments[0].c_str());
+            range_end = atoi(arguments[1].c_str());
+            arguments.erase(arguments.begin(), arguments.begin() + 2);
+        } else if (a0 == "-h" || a0 == "--help" || a0 == "-help") {
+            cerr << "Bayesian model selection for RNA-seq expression estimates.\n";
+            printUsage(cerr);
+            exit(1);
+        } else if (a0 == "-v" || a0 == "--version" || a0 == "-version") {
+            die("mmdiff-1.0.10-gfx950");
+        } else {
+            if (!a0.empty() && a0[0] == '-') usage_error("Error: unrecognised option " + a0 + ".");
+            else if (arguments.size() <= 2) usage_error("Error: mandatory arguments missing.");
+            else break;
+        }
+    }
+
+    if (burnin <= 0 || mcmciters <= 0) usage_error("Error: negative burnin and iter parameters.");
+    if (burnin % OUTLEN != 0 || mcmciters % OUTLEN != 0) usage_error("Error: burnin and iter parameters must be multiples of " + to_string(OUTLEN));
+    if (useprops) {
+        cerr << "Using proportions, therefore disabling normalisation.\n";
+        normalise = false;
+    }
+    if (matrices_file == "" && simple_de.size() == 0) die("Error: either -de or -m must be specified");
+    if (matrices_file == "" && simple_de.size() == 1) die("Error: -de requires at least two groupings");
+
+    vector<string> filenames(arguments.begin(), arguments.end());
+    const size_t S = filenames.size();
+    if (customuhfrac && (uhfrac > 1 || uhfrac < 1.0 / (double)S)) die("Error: uhfrac must be <= 1 and >= 1/N.");
+    if (!customuhfrac) uhfrac = max(0.2, (double)(S - S * S / 160) / (double)S);
+    if (normalise) cerr << "Min unique hits fraction for normalisation: " << uhfrac << endl;
+    if (S > 512) die("Error: this mmdiff handles at most 512 samples.");
+    const uint64_t useed = (uint64_t)(uint32_t)seed;
+
+    vector<string> features;
+    Mat y, e, uh;
+    parse_mmseq(filenames, features, y, e, uh, range_start, range_end, useprops);
+    const size_t F = features.size();
+    if (F == 0) die("Error: no features to analyse.");
+    if (normalise) apply_normalisation(filenames, y, uh, F, S, uhfrac);
+    if (permute) apply_permutation(y, e, F, S, useed);
+
+    Design D;
+    if (matrices_file == "") {
+        const size_t G = simple_de.size();
+        D.N = S; D.K = 1; D.L0 = 1; D.L1 = G > 2 ? G : 1; D.CC = 2;
+        D.M.assign(S, 0.0); D.P0.assign(S, 0.0); D.P1.assign(S * D.L1, 0.0); D.C.assign(S * 2, 0);
+        size_t k = 0;
+        for (size_t i = 0; i < G; i++)
+            for (int j = 0; j < simple_de[i]; j++) {
+                D.C[k * 2 + 1] = (int)i;
+                D.P0[k] = 1.0;
+                if (G > 2) D.P1[k * D.L1 + i] = 1.0;
+                else D.P1[k] = i == 0 ? .5 : -.5;
+                k++;
+            }
+    } else {
+        parse_matrices(matrices_file, D, S);
+    }
+    if (D.K > 8) die("Error: this mmdiff handles at most 8 columns in M.");
+    if (D.L0 > 16 || D.L1 > 16) die("Error: this mmdiff handles at most 16 columns in P0 and P1.");
+    for (int c : D.C)
+        if (c > 15) die("Error: this mmdiff handles at most 16 variance classes per model.");
+    for (int model = 0; model < 2; ++model) {
+        vector<int> seen(16, 0);
+        int mx = 0;
+        for (size_t i = 0; i < S; ++i) { seen[D.C[i * 2 + model]] = 1; mx = max(mx, D.C[i * 2 + model]); }
+        for (int c = 0; c <= mx; ++c)
+            if (!seen[c]) die("Error: the classes of model " + to_string(model) + " must be labelled 0, 1, ... without gaps.");
+    }
+    for (const Mat *X : {&D.M, &D.P0, &D.P1})
+        for (double v : *X)
+            if (!std::isfinite(v)) die("Error: non-finite value in the design matrices.");
+    const bool Mnil = is_nil(D.M, S, D.K);
+    const bool Pnil[2] = {is_nil(D.P0, S, D.L0), is_nil(D.P1, S, D.L1)};
+    if (fixalpha) cerr << "Fixing alpha=0, so setting v_beta^2=25 instead of 4.\n";
+    check_design(D, fixalpha, Mnil, Pnil);
+    if (Mnil) cerr << "Note: no betas\n";
+    if (Pnil[0]) cerr << "Note: no etas in model 0\n";
+    if (Pnil[1]) cerr << "Note: no etas in model 1\n";
+
+    // every input is checked: now the device
+    int ndev = 0;
+    if (mmg_device_count(&ndev) != 0 || ndev < 1) die("Error: no HIP device available: mmdiff has no CPU fallback");
+    mmg_diff *h = nullptr;
+    MMG_CHECK(mmg_diff_create(0, (uint32_t)F, (uint32_t)S, y.data(), e.data(), (uint32_t)D.K, D.M.data(), (uint32_t)D.L0, D.P0.data(),
+                              (uint32_t)D.L1, D.P1.data(), D.C.data(), d, s, pdash, fixalpha ? 1 : 0, useed, &h));
+    cerr << "BURNIN (" << burnin << " iterations)...";
+    MMG_CHECK(mmg_diff_burnin(h, (uint32_t)burnin));
+    cerr << "\nSetting pseudopriors...done.\n";
+    int numbatches = 0;
+    if (tune) {
+        uint32_t untuned = 0;
+        MMG_CHECK(mmg_diff_tune_batch(h, &untuned));
+        numbatches = 1;
+        while (untuned > 0 && numbatches != MAXBATCHES) {
+            MMG_CHECK(mmg_diff_tune_batch(h, &untuned));
+            numbatches++;
+            if (numbatches % 64 == 0) cerr << "TUNING BATCH " << numbatches << " (" << untuned << " left)\r";
+        }
+    }
+    cerr << "TRACE (" << mcmciters << " iterations, sampling after " << numbatches << " tuning batches)";
+    MMG_CHECK(mmg_diff_sample(h, (uint32_t)mcmciters));
+    cerr << "\nDONE MCMC\n";
+    vector<double> gm(F), logitp(F), alpha(2 * F), beta(2 * D.K * F), eta((D.L0 + D.L1) * F);
+    MMG_CHECK(mmg_diff_get_results(h, gm.data(), logitp.data(), alpha.data(), beta.data(), eta.data()));
+    mmg_diff_destroy(h);
+
+    string out;
+    out += "#prior_probability=" + fmt(p) + "\n";
+    out += "feature_id\tbayes_factor\tposterior_probability\t";
+    for (int model = 0; model < 2; model++) {
+        if (!fixalpha) out += "alpha" + to_string(model) + "\t";
+        if (!Mnil)
+            for (size_t l = 0; l < D.K; l++) out += "beta" + to_string(model) + "_" + to_string(l) + "\t";
+        if (!Pnil[model])
+            for (size_t l = 0; l < (model ? D.L1 : D.L0); l++) out += "eta" + to_string(model) + "_" + to_string(l) + "\t";
+    }
+    vector<string> samplenames = filenames;
+    for (size_t f = 0; f < S; f++) {
+        if (endsWith(filenames[f], ".mmseq")) {
+            const size_t found = filenames[f].find_last_of(".");
+            size_t found2 = filenames[f].find_last_of("/");
+            const long f2 = found2 == string::npos ? -1 : (long)found2;
+            samplenames[f] = filenames[f].substr((size_t)(f2 + 1), (size_t)((long)found - f2 - 1));
+        }
+        out += "mu_" + samplenames[f] + "\t";
+    }
+    for (size_t f = 0; f < S; f++) out += "sd_" + samplenames[f] + (f < S - 1 ? "\t" : "\n");
+    fputs(out.c_str(), stdout);
+    const double logp = log(p), log1mp = log1p(-p);
+    for (size_t feature = 0; feature < F; feature++) {
+        out.clear();
+        const double g = gm[feature];
+        if (g == 0.0 || g == 1.0)
+            cerr << "Warning: gamma did not mix for feature " << feature << "; stuck in model " << (int)g << endl;
+        const double lgp = logitp[feature];
+        const double pp_ = lgp > 0 ? 1.0 / (1.0 + exp(-lgp)) : exp(lgp) / (1.0 + exp(lgp));   // BMS::getp
+        const double BF = g / (1.0 - g) * (1.0 - pp_) / pp_;
+        const double postlogodds = log(BF) + logp - log1mp;
+        double pp = 1.0 / (1.0 + exp(-postlogodds));
+        if (BF >= DBL_MAX) pp = 1.0;
+        out += features[feature] + "\t" + fmt(BF) + "\t" + fmt(pp) + "\t";
+        for (int model = 0; model < 2; model++) {
+            if (!fixalpha) out += fmt(alpha[model * F + feature]) + "\t";
+            if (!Mnil)
+                for (size_t l = 0; l < D.K; l++) out += fmt(beta[(model * D.K + l) * F + feature]) + "\t";
+            if (!Pnil[model])
+                for (size_t l = 0; l < (model ? D.L1 : D.L0); l++) out += fmt(eta[((model ? D.L0 : 0) + l) * F + feature]) + "\t";
+        }
+        for (size_t f = 0; f < S; f++) out += fmt(y[feature * S + f]) + "\t";
+        for (size_t f = 0; f < S; f++) out += fmt(e[feature * S + f]) + (f < S - 1 ? "\t" : "\n");
+        fputs(out.c_str(), stdout);
+    }
+    return 0;
+}

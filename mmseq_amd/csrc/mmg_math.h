@@ -92,7 +92,7 @@ MMG_HD double u52(uint32_t a, uint32_t b)
 #endif
 }
 
-enum : uint32_t { TAG_ROW = 1, TAG_GAMMA = 2, TAG_SYNTH_ROW = 3, TAG_SYNTH_TX = 4, TAG_SIMU = 5, TAG_COLLAPSE_SIMU = 6 };
+enum : uint32_t { TAG_ROW = 1, TAG_GAMMA = 2, TAG_SYNTH_ROW = 3, TAG_SYNTH_TX = 4, TAG_SIMU = 5, TAG_COLLAPSE_SIMU = 6, TAG_DIFF = 7, TAG_DIFF_PERM = 8 };
 
 // A stream = (key from seed/chain/tag, counter words id_lo,id_hi,iter) + running block index.
 struct Stream {
@@ -405,6 +405,23 @@ MMG_HD double gamma_unit(Stream &s, double a_in)
 #endif
     }
     return g;
+}
+
+// log Gamma(x), x > 0, from dlog and IEEE operations only (mmdiff's log densities; gsl_sf_lngamma in the reference):
+// the argument is shifted up to x + n >= 8 through Gamma(x) = Gamma(x + n) / (x (x + 1) ... (x + n - 1)), then Stirling's
+// series to the x^-15 term (its remainder is below 1e-17 there).  Absolute error a few 1e-16 times max(1, |result|): near the
+// zeros at 1 and 2 the subtraction of the shift's logarithm costs the relative accuracy.  Outside (0, inf) -- x <= 0, NaN, +inf --
+// it returns NaN, +inf for +inf, before the shift loop: the loop runs at most 8 times.
+MMG_HD double dlgamma(double x)
+{
+    if (!(x > 0.0)) return __builtin_nan("");
+    if (x == __builtin_huge_val()) return x;
+    double prod = 1.0;
+    while (x < 8.0) { prod = prod * x; x = x + 1.0; }
+    const double z = 1.0 / x, z2 = z * z;
+    const double ser = z * (1.0 / 12.0 + z2 * (-1.0 / 360.0 + z2 * (1.0 / 1260.0 + z2 * (-1.0 / 1680.0 + z2 * (1.0 / 1188.0
+                     + z2 * (-691.0 / 360360.0 + z2 * (1.0 / 156.0 + z2 * (-3617.0 / 122400.0))))))));
+    return ((((x - 0.5) * dlog(x) - x) + 0.91893853320467274178) + ser) - dlog(prod);
 }
 
 // log(k!) Stirling remainder used by the binomial rejection sampler
