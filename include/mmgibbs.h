@@ -418,9 +418,16 @@ enum {
     MMG_OPT_WIRE_CHECK = 9,        /* 0: no verification of a group's first exchanges, 1: verify in groups of one device too, 2: 1 + damage a word behind the exchange (the failure path) */
     MMG_OPT_BIGK_PER_WAVE = 10,    /* list entries per workgroup of k_sample_bigk (the rows on the conditional-binomial chain)                      */
     MMG_OPT_BIGK_SIDE_STREAM = 11, /* 0: k_sample_bigk on the sampler's stream, in front of the tile kernels instead of beside them                    */
-    MMG_OPT_COUNT_ = 12
+    MMG_OPT_FAIL_ALLOC = 12,       /* v >= 0: the v-th acquisition of device memory, a stream or an event after this option is set (counted from 0) fails
+                                      without reaching the runtime (error paths) */
+    MMG_OPT_COUNT_ = 13
 };
 int mmg_selftest_option(int option, int value);
+/* What the library holds: counts[3] = device buffers, streams, events (tests: every call gives back what it acquired). */
+int mmg_selftest_live(int64_t *counts);
+/* A sampler's pool of timing events: *pool events, *free_idx of them on the free list, *pending_idx in pairs not yet harvested
+ * (tests: pool == free_idx + pending_idx between calls). */
+int mmg_selftest_sampler_events(const mmg_sampler *s, int *pool, int *free_idx, int *pending_idx);
 /* The sharded EM of mmg_group_em_create with every shard on ONE device and the exchange done by plain kernels: `sweeps` sweeps from
  * mu0, mu (caller's numbering), the log-likelihood and the number of repeated passes -- the same bits as mmg_problem_em on the
  * unsharded problem. */

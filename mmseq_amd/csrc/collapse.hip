@@ -3,39 +3,30 @@
 #include "collapse_kernels.h"
 #include "mmg_host.h"
 
+#include <memory>
 #include <vector>
 
 using namespace mmg;
 
+// Members are destroyed in reverse declaration order: the destructor waits for `st`, then the buffers go, and the stream last.
 struct mmg_collapse {
+    DevStream st;
     int device = 0;
     uint32_t S = 0, C = 0, Cp = 0, N = 0;
-    double *d_X = nullptr;       // [S][N][Cp] centred traces (merged candidates: the sum of their members')
-    double *d_var = nullptr;     // [S][Cp]
-    double *d_cov = nullptr;     // [S][Cp] the merged row's covariances of one iteration
-    uint8_t *d_obs = nullptr;    // [S][Cp]
-    double *d_V = nullptr;       // [Cp][Cp]
-    double *d_rowmax = nullptr, *d_cmin = nullptr;
-    uint32_t *d_carg = nullptr;
-    uint8_t *d_dead = nullptr, *d_flag = nullptr;
-    ClPick *d_pick = nullptr;
+    DevBuf<double> d_X;          // [S][N][Cp] centred traces (merged candidates: the sum of their members')
+    DevBuf<double> d_var;        // [S][Cp]
+    DevBuf<double> d_cov;        // [S][Cp] the merged row's covariances of one iteration
+    DevBuf<uint8_t> d_obs;       // [S][Cp]
+    DevBuf<double> d_V;          // [Cp][Cp]
+    DevBuf<double> d_rowmax, d_cmin;
+    DevBuf<uint32_t> d_carg;
+    DevBuf<uint8_t> d_dead, d_flag;
+    DevBuf<ClPick> d_pick;
     std::vector<uint8_t> have;   // samples uploaded
     bool correlated = false, stopped = false;
     uint64_t device_bytes = 0;
-    hipStream_t st = nullptr;
+    ~mmg_collapse() { if (st) (void)hipStreamSynchronize(st.get()); }
 };
-
-static void collapse_free(mmg_collapse *h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->st) (void)hipStreamSynchronize(h->st);
-    for (void *x : {(void *)h->d_X, (void *)h->d_var, (void *)h->d_cov, (void *)h->d_obs, (void *)h->d_V, (void *)h->d_rowmax,
-                    (void *)h->d_cmin, (void *)h->d_carg, (void *)h->d_dead, (void *)h->d_flag, (void *)h->d_pick})
-        if (x) (void)hipFree(x);
-    if (h->st) (void)hipStreamDestroy(h->st);
-    delete h;
-}
 
 static inline unsigned cl_blocks(uint64_t n) { return (unsigned)((n + 255) / 256); }
 
@@ -49,39 +40,37 @@ extern "C" int mmg_collapse_create(int device, uint32_t n_samples, uint32_t n_ca
     if (n_cand > 0x7fffff00u) return fail(MMG_ERR_ARG, "too many candidates");
     int rc = require_device(device);
     if (rc) return rc;
-    mmg_collapse *h = new mmg_collapse();
+    std::unique_ptr<mmg_collapse> h(new mmg_collapse());
     h->device = device; h->S = n_samples; h->C = n_cand; h->N = trace_len;
     h->Cp = (uint32_t)(((uint64_t)n_cand + CL_CT - 1) / CL_CT * CL_CT);
     if (h->Cp == 0) h->Cp = CL_CT;
     h->have.assign(n_samples, 0);
     const uint64_t Cp = h->Cp, S = n_samples, N = trace_len;
-    auto bail = [&](int code) { collapse_free(h); return code; };
-#define C_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return bail(fail(MMG_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e))); } while (0)
-    auto dalloc = [&](void **p, uint64_t bytes) {
-        hipError_t e = hipMalloc(p, bytes);
-        if (e == hipSuccess) { h->device_bytes += bytes; e = hipMemsetAsync(*p, 0, bytes, h->st); }
-        return e;
+    auto dalloc = [&](auto &buf, uint64_t count) { // zeroed on the handle's stream
+        HIPE_TRY(buf.alloc(count));
+        const uint64_t bytes = count * sizeof(*buf.get());
+        h->device_bytes += bytes;
+        return hipMemsetAsync(buf.get(), 0, bytes, h->st.get());
     };
-    C_TRY(hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking));
-    C_TRY(dalloc((void **)&h->d_X, S * N * Cp * 8));
-    C_TRY(dalloc((void **)&h->d_var, S * Cp * 8));
-    C_TRY(dalloc((void **)&h->d_cov, S * Cp * 8));
-    C_TRY(dalloc((void **)&h->d_obs, S * Cp));
-    C_TRY(dalloc((void **)&h->d_V, Cp * Cp * 8));
-    C_TRY(dalloc((void **)&h->d_rowmax, Cp * 8));
-    C_TRY(dalloc((void **)&h->d_cmin, Cp * 8));
-    C_TRY(dalloc((void **)&h->d_carg, Cp * 4));
-    C_TRY(dalloc((void **)&h->d_dead, Cp));
-    C_TRY(dalloc((void **)&h->d_flag, Cp));
-    C_TRY(dalloc((void **)&h->d_pick, sizeof(ClPick)));
+    HIP_TRY(h->st.create(hipStreamNonBlocking));
+    HIP_TRY(dalloc(h->d_X, S * N * Cp));
+    HIP_TRY(dalloc(h->d_var, S * Cp));
+    HIP_TRY(dalloc(h->d_cov, S * Cp));
+    HIP_TRY(dalloc(h->d_obs, S * Cp));
+    HIP_TRY(dalloc(h->d_V, Cp * Cp));
+    HIP_TRY(dalloc(h->d_rowmax, Cp));
+    HIP_TRY(dalloc(h->d_cmin, Cp));
+    HIP_TRY(dalloc(h->d_carg, Cp));
+    HIP_TRY(dalloc(h->d_dead, Cp));
+    HIP_TRY(dalloc(h->d_flag, Cp));
+    HIP_TRY(dalloc(h->d_pick, 1));
     // the mask, transposed to [S][Cp] (padding columns unobserved)
     std::vector<uint8_t> obs(S * Cp, 0);
     for (uint64_t c = 0; c < n_cand; ++c)
         for (uint64_t s = 0; s < S; ++s) obs[s * Cp + c] = observed[c * S + s] ? 1 : 0;
-    C_TRY(hipMemcpyAsync(h->d_obs, obs.data(), obs.size(), hipMemcpyHostToDevice, h->st));
-    C_TRY(hipStreamSynchronize(h->st));
-#undef C_TRY
-    *out = h;
+    HIP_TRY(hipMemcpyAsync(h->d_obs.get(), obs.data(), obs.size(), hipMemcpyHostToDevice, h->st.get()));
+    HIP_TRY(hipStreamSynchronize(h->st.get()));
+    *out = h.release();
     return MMG_OK;
 }
 
@@ -91,14 +80,14 @@ extern "C" int mmg_collapse_set_sample(mmg_collapse *h, uint32_t sample, const d
     if (sample >= h->S) return fail(MMG_ERR_ARG, "sample index out of range");
     if (h->correlated) return fail(MMG_ERR_STATE, "the correlations are computed already");
     HIP_TRY(hipSetDevice(h->device));
-    double *X = h->d_X + (uint64_t)sample * h->N * h->Cp;
+    double *X = h->d_X.get() + (uint64_t)sample * h->N * h->Cp;
     if (h->C) {
-        HIP_TRY(hipMemcpy2DAsync(X, (size_t)h->Cp * 8, trace, (size_t)h->C * 8, (size_t)h->C * 8, h->N, hipMemcpyHostToDevice, h->st));
-        hipLaunchKernelGGL(k_cl_center, dim3(cl_blocks(h->C)), dim3(256), 0, h->st, h->N, h->Cp, h->C, X);
+        HIP_TRY(hipMemcpy2DAsync(X, (size_t)h->Cp * 8, trace, (size_t)h->C * 8, (size_t)h->C * 8, h->N, hipMemcpyHostToDevice, h->st.get()));
+        hipLaunchKernelGGL(k_cl_center, dim3(cl_blocks(h->C)), dim3(256), 0, h->st.get(), h->N, h->Cp, h->C, X);
     }
-    hipLaunchKernelGGL(k_cl_var, dim3(cl_blocks(h->Cp)), dim3(256), 0, h->st, h->N, h->Cp, (const double *)X, h->d_var + (uint64_t)sample * h->Cp);
+    hipLaunchKernelGGL(k_cl_var, dim3(cl_blocks(h->Cp)), dim3(256), 0, h->st.get(), h->N, h->Cp, (const double *)X, h->d_var.get() + (uint64_t)sample * h->Cp);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(h->st));   // (the caller's trace was the source of an asynchronous copy)
+    HIP_TRY(hipStreamSynchronize(h->st.get()));   // (the caller's trace was the source of an asynchronous copy)
     h->have[sample] = 1;
     return MMG_OK;
 }
@@ -110,11 +99,11 @@ extern "C" int mmg_collapse_correlate(mmg_collapse *h)
     for (uint8_t x : h->have) if (!x) return fail(MMG_ERR_STATE, "mmg_collapse_correlate before every sample was set");
     HIP_TRY(hipSetDevice(h->device));
     const unsigned nt = h->Cp / CL_CT;
-    hipLaunchKernelGGL(k_cl_corr_tiles, dim3(nt, nt), dim3(256), 0, h->st, h->N, h->Cp, h->S, (const double *)h->d_X,
-                       (const double *)h->d_var, (const uint8_t *)h->d_obs, h->d_V);
-    if (h->C) hipLaunchKernelGGL(k_cl_scan, dim3(h->C), dim3(256), 0, h->st, h->C, h->Cp, (const double *)h->d_V, (uint8_t *)nullptr, h->d_cmin, h->d_carg, h->d_rowmax);
+    hipLaunchKernelGGL(k_cl_corr_tiles, dim3(nt, nt), dim3(256), 0, h->st.get(), h->N, h->Cp, h->S, (const double *)h->d_X.get(),
+                       (const double *)h->d_var.get(), (const uint8_t *)h->d_obs.get(), h->d_V.get());
+    if (h->C) hipLaunchKernelGGL(k_cl_scan, dim3(h->C), dim3(256), 0, h->st.get(), h->C, h->Cp, (const double *)h->d_V.get(), (uint8_t *)nullptr, h->d_cmin.get(), h->d_carg.get(), h->d_rowmax.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(h->st));
+    HIP_TRY(hipStreamSynchronize(h->st.get()));
     h->correlated = true;
     return MMG_OK;
 }
@@ -126,9 +115,9 @@ extern "C" int mmg_collapse_get_rows(mmg_collapse *h, uint32_t first, uint32_t c
     if ((uint64_t)first + count > h->C) return fail(MMG_ERR_ARG, "rows out of range");
     if (!count || !h->C) return MMG_OK;
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMemcpy2DAsync(out, (size_t)h->C * 8, h->d_V + (uint64_t)first * h->Cp, (size_t)h->Cp * 8, (size_t)h->C * 8, count,
-                             hipMemcpyDeviceToHost, h->st));
-    HIP_TRY(hipStreamSynchronize(h->st));
+    HIP_TRY(hipMemcpy2DAsync(out, (size_t)h->C * 8, h->d_V.get() + (uint64_t)first * h->Cp, (size_t)h->Cp * 8, (size_t)h->C * 8, count,
+                             hipMemcpyDeviceToHost, h->st.get()));
+    HIP_TRY(hipStreamSynchronize(h->st.get()));
     return MMG_OK;
 }
 
@@ -138,8 +127,8 @@ extern "C" int mmg_collapse_row_max(mmg_collapse *h, double *out)
     if (!h->correlated) return fail(MMG_ERR_STATE, "mmg_collapse_correlate has not run");
     if (!h->C) return MMG_OK;
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMemcpyAsync(out, h->d_rowmax, (size_t)h->C * 8, hipMemcpyDeviceToHost, h->st));
-    HIP_TRY(hipStreamSynchronize(h->st));
+    HIP_TRY(hipMemcpyAsync(out, h->d_rowmax.get(), (size_t)h->C * 8, hipMemcpyDeviceToHost, h->st.get()));
+    HIP_TRY(hipStreamSynchronize(h->st.get()));
     return MMG_OK;
 }
 
@@ -155,22 +144,22 @@ extern "C" int mmg_collapse_run(mmg_collapse *h, double thr, uint32_t max_merges
     if (stopped) *stopped = h->stopped;
     if (h->stopped || !h->C) { h->stopped = true; if (stopped) *stopped = 1; return MMG_OK; }
     HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = h->st;
+    hipStream_t st = h->st.get();
     uint32_t done = 0;
     while (done < max_merges) {
-        hipLaunchKernelGGL(k_cl_global_min, dim3(1), dim3(1024), 0, st, h->C, (const double *)h->d_cmin, (const uint32_t *)h->d_carg, h->d_pick);
+        hipLaunchKernelGGL(k_cl_global_min, dim3(1), dim3(1024), 0, st, h->C, (const double *)h->d_cmin.get(), (const uint32_t *)h->d_carg.get(), h->d_pick.get());
         HIP_TRY(hipGetLastError());
         ClPick pk;
-        HIP_TRY(hipMemcpyAsync(&pk, h->d_pick, sizeof pk, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&pk, h->d_pick.get(), sizeof pk, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         if (pk.col == CL_NONE || !(pk.value < thr)) { h->stopped = true; break; }
         const uint32_t a = pk.row < pk.col ? pk.row : pk.col, b = pk.row < pk.col ? pk.col : pk.row;
         if (a == b || b >= h->C) return fail(MMG_ERR_STATE, "collapse: the minimum of V sits on the diagonal or out of range");
-        hipLaunchKernelGGL(k_cl_merge, dim3(cl_blocks((uint64_t)h->S * h->N)), dim3(256), 0, st, h->N, h->Cp, h->S, a, b, h->d_X, h->d_dead);
-        hipLaunchKernelGGL(k_cl_row_cov, dim3(cl_blocks(h->Cp), h->S), dim3(256), 0, st, h->N, h->Cp, a, (const double *)h->d_X, h->d_cov);
-        hipLaunchKernelGGL(k_cl_row_update, dim3(cl_blocks(h->C)), dim3(256), 0, st, h->C, h->Cp, h->S, a, b, (const double *)h->d_cov, h->d_var,
-                           (const uint8_t *)h->d_obs, (const uint8_t *)h->d_dead, h->d_V, h->d_cmin, h->d_carg, h->d_flag);
-        hipLaunchKernelGGL(k_cl_scan, dim3(h->C), dim3(256), 0, st, h->C, h->Cp, (const double *)h->d_V, h->d_flag, h->d_cmin, h->d_carg, (double *)nullptr);
+        hipLaunchKernelGGL(k_cl_merge, dim3(cl_blocks((uint64_t)h->S * h->N)), dim3(256), 0, st, h->N, h->Cp, h->S, a, b, h->d_X.get(), h->d_dead.get());
+        hipLaunchKernelGGL(k_cl_row_cov, dim3(cl_blocks(h->Cp), h->S), dim3(256), 0, st, h->N, h->Cp, a, (const double *)h->d_X.get(), h->d_cov.get());
+        hipLaunchKernelGGL(k_cl_row_update, dim3(cl_blocks(h->C)), dim3(256), 0, st, h->C, h->Cp, h->S, a, b, (const double *)h->d_cov.get(), h->d_var.get(),
+                           (const uint8_t *)h->d_obs.get(), (const uint8_t *)h->d_dead.get(), h->d_V.get(), h->d_cmin.get(), h->d_carg.get(), h->d_flag.get());
+        hipLaunchKernelGGL(k_cl_scan, dim3(h->C), dim3(256), 0, st, h->C, h->Cp, (const double *)h->d_V.get(), h->d_flag.get(), h->d_cmin.get(), h->d_carg.get(), (double *)nullptr);
         HIP_TRY(hipGetLastError());
         pairs[2 * done] = a;
         pairs[2 * done + 1] = b;
@@ -190,4 +179,4 @@ extern "C" int mmg_collapse_device_bytes(mmg_collapse *h, uint64_t *bytes)
     return MMG_OK;
 }
 
-extern "C" void mmg_collapse_destroy(mmg_collapse *h) { collapse_free(h); }
+extern "C" void mmg_collapse_destroy(mmg_collapse *h) { delete h; }

@@ -4,6 +4,7 @@
 #include "mmg_host.h"
 
 #include <cmath>
+#include <memory>
 #include <vector>
 
 using namespace mmg;
@@ -13,30 +14,20 @@ constexpr uint32_t DF_CHUNK = 512;    // iterations per launch of burn-in and sa
 constexpr int DF_REC_FROM = 102;      // OUTLEN / 10: burn-in iterations before this one are not recorded
 }
 
+// Members are destroyed in reverse declaration order: the destructor waits for `st`, then the buffers go, and the stream last.
 struct mmg_diff {
+    DevStream st;
     int device = 0;
     DiffParams p{};
     uint32_t F = 0, N = 0, K = 0, L[2] = {0, 0};
     size_t nslot = 0;
-    double *d_y = nullptr, *d_esq = nullptr, *d_st = nullptr, *d_M = nullptr, *d_P0 = nullptr, *d_P1 = nullptr;
-    int *d_C = nullptr, *d_gam = nullptr, *d_tuned = nullptr, *d_cnt = nullptr;
+    DevBuf<double> d_y, d_esq, d_st, d_M, d_P0, d_P1;
+    DevBuf<int> d_C, d_gam, d_tuned, d_cnt;
     uint32_t burnin = 0, batches = 0, sampled = 0;
     bool burnt = false;
     uint64_t device_bytes = 0;
-    hipStream_t st = nullptr;
+    ~mmg_diff() { if (st) (void)hipStreamSynchronize(st.get()); }
 };
-
-static void diff_free(mmg_diff *h)
-{
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->st) (void)hipStreamSynchronize(h->st);
-    for (void *x : {(void *)h->d_y, (void *)h->d_esq, (void *)h->d_st, (void *)h->d_M, (void *)h->d_P0, (void *)h->d_P1, (void *)h->d_C,
-                    (void *)h->d_gam, (void *)h->d_tuned, (void *)h->d_cnt})
-        if (x) (void)hipFree(x);
-    if (h->st) (void)hipStreamDestroy(h->st);
-    delete h;
-}
 
 // the reference's "nil" rule (BMS::BMS): a single column whose entries differ by less than 1e-5 is no covariate at all
 static bool df_nil(const double *X, uint32_t N, uint32_t cols)
@@ -80,7 +71,7 @@ extern "C" int mmg_diff_create(int device, uint32_t F, uint32_t N, const double 
     int rc = require_device(device);
     if (rc) return rc;
 
-    mmg_diff *h = new mmg_diff();
+    std::unique_ptr<mmg_diff> h(new mmg_diff());
     h->device = device; h->F = F; h->N = N; h->K = K; h->L[0] = L0; h->L[1] = L1;
     DiffParams &p = h->p;
     p.F = (int)F; p.N = (int)N; p.K = (int)K;
@@ -105,26 +96,24 @@ extern "C" int mmg_diff_create(int device, uint32_t F, uint32_t N, const double 
     for (int *slot : {&p.wlprop, &p.wsum}) { *slot = o; o += ncmax; }
     h->nslot = (size_t)o;
 
-    auto bail = [&](int code) { diff_free(h); return code; };
-#define D_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return bail(fail(MMG_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e))); } while (0)
-    auto dalloc = [&](void **ptr, uint64_t bytes) {
-        hipError_t err = hipMalloc(ptr, bytes);
-        if (err == hipSuccess) h->device_bytes += bytes;
-        return err;
+    auto dalloc = [&](auto &buf, uint64_t count) {
+        HIPE_TRY(buf.alloc(count));
+        h->device_bytes += count * sizeof(*buf.get());
+        return hipSuccess;
     };
-    D_TRY(hipSetDevice(device));
-    D_TRY(hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking));
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(h->st.create(hipStreamNonBlocking));
     const uint64_t FN = (uint64_t)F * N;
-    D_TRY(dalloc((void **)&h->d_y, FN * 8));
-    D_TRY(dalloc((void **)&h->d_esq, FN * 8));
-    D_TRY(dalloc((void **)&h->d_st, (uint64_t)h->nslot * F * 8));
-    D_TRY(dalloc((void **)&h->d_M, (uint64_t)N * K * 8));
-    D_TRY(dalloc((void **)&h->d_P0, (uint64_t)N * L0 * 8));
-    D_TRY(dalloc((void **)&h->d_P1, (uint64_t)N * L1 * 8));
-    D_TRY(dalloc((void **)&h->d_C, (uint64_t)N * 2 * 4));
-    D_TRY(dalloc((void **)&h->d_gam, (uint64_t)F * 4));
-    D_TRY(dalloc((void **)&h->d_tuned, (uint64_t)F * 4));
-    D_TRY(dalloc((void **)&h->d_cnt, 4));
+    HIP_TRY(dalloc(h->d_y, FN));
+    HIP_TRY(dalloc(h->d_esq, FN));
+    HIP_TRY(dalloc(h->d_st, (uint64_t)h->nslot * F));
+    HIP_TRY(dalloc(h->d_M, (uint64_t)N * K));
+    HIP_TRY(dalloc(h->d_P0, (uint64_t)N * L0));
+    HIP_TRY(dalloc(h->d_P1, (uint64_t)N * L1));
+    HIP_TRY(dalloc(h->d_C, (uint64_t)N * 2));
+    HIP_TRY(dalloc(h->d_gam, (uint64_t)F));
+    HIP_TRY(dalloc(h->d_tuned, (uint64_t)F));
+    HIP_TRY(dalloc(h->d_cnt, 1));
     // y and e^2 transposed to [N][F]: the lanes of a wave read adjacent words
     std::vector<double> ty(FN), te(FN);
     for (uint64_t f = 0; f < F; ++f)
@@ -133,20 +122,19 @@ extern "C" int mmg_diff_create(int device, uint32_t F, uint32_t N, const double 
             const double ei = e[f * N + i];
             te[i * F + f] = ei * ei;
         }
-    D_TRY(hipMemcpyAsync(h->d_y, ty.data(), FN * 8, hipMemcpyHostToDevice, h->st));
-    D_TRY(hipMemcpyAsync(h->d_esq, te.data(), FN * 8, hipMemcpyHostToDevice, h->st));
-    D_TRY(hipMemcpyAsync(h->d_M, M, (size_t)N * K * 8, hipMemcpyHostToDevice, h->st));
-    D_TRY(hipMemcpyAsync(h->d_P0, P0, (size_t)N * L0 * 8, hipMemcpyHostToDevice, h->st));
-    D_TRY(hipMemcpyAsync(h->d_P1, P1, (size_t)N * L1 * 8, hipMemcpyHostToDevice, h->st));
-    D_TRY(hipMemcpyAsync(h->d_C, C, (size_t)N * 2 * 4, hipMemcpyHostToDevice, h->st));
-    p.M = h->d_M; p.m[0].P = h->d_P0; p.m[1].P = h->d_P1; p.Cl = h->d_C;
-    p.y = h->d_y; p.esq = h->d_esq; p.st = h->d_st; p.gam = h->d_gam; p.tuned = h->d_tuned;
+    HIP_TRY(hipMemcpyAsync(h->d_y.get(), ty.data(), FN * 8, hipMemcpyHostToDevice, h->st.get()));
+    HIP_TRY(hipMemcpyAsync(h->d_esq.get(), te.data(), FN * 8, hipMemcpyHostToDevice, h->st.get()));
+    HIP_TRY(hipMemcpyAsync(h->d_M.get(), M, (size_t)N * K * 8, hipMemcpyHostToDevice, h->st.get()));
+    HIP_TRY(hipMemcpyAsync(h->d_P0.get(), P0, (size_t)N * L0 * 8, hipMemcpyHostToDevice, h->st.get()));
+    HIP_TRY(hipMemcpyAsync(h->d_P1.get(), P1, (size_t)N * L1 * 8, hipMemcpyHostToDevice, h->st.get()));
+    HIP_TRY(hipMemcpyAsync(h->d_C.get(), C, (size_t)N * 2 * 4, hipMemcpyHostToDevice, h->st.get()));
+    p.M = h->d_M.get(); p.m[0].P = h->d_P0.get(); p.m[1].P = h->d_P1.get(); p.Cl = h->d_C.get();
+    p.y = h->d_y.get(); p.esq = h->d_esq.get(); p.st = h->d_st.get(); p.gam = h->d_gam.get(); p.tuned = h->d_tuned.get();
     const double logitp0 = std::log(pdash) - std::log(1.0 - pdash);
-    hipLaunchKernelGGL(k_df_init, dim3(df_blocks(F)), dim3(DF_BLOCK), 0, h->st, p, logitp0);
-    D_TRY(hipGetLastError());
-    D_TRY(hipStreamSynchronize(h->st));   // (the host buffers were the sources of asynchronous copies)
-#undef D_TRY
-    *out = h;
+    hipLaunchKernelGGL(k_df_init, dim3(df_blocks(F)), dim3(DF_BLOCK), 0, h->st.get(), p, logitp0);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(h->st.get()));   // (the host buffers were the sources of asynchronous copies)
+    *out = h.release();
     return MMG_OK;
 }
 
@@ -158,11 +146,11 @@ extern "C" int mmg_diff_burnin(mmg_diff *h, uint32_t iters)
     HIP_TRY(hipSetDevice(h->device));
     for (uint32_t t = 0; t < iters; t += DF_CHUNK) {
         const uint32_t n = iters - t < DF_CHUNK ? iters - t : DF_CHUNK;
-        hipLaunchKernelGGL(k_df_run, dim3(df_blocks(h->F)), dim3(DF_BLOCK), 0, h->st, h->p, t, (int)t, (int)n, 0, DF_REC_FROM);
+        hipLaunchKernelGGL(k_df_run, dim3(df_blocks(h->F)), dim3(DF_BLOCK), 0, h->st.get(), h->p, t, (int)t, (int)n, 0, DF_REC_FROM);
     }
-    hipLaunchKernelGGL(k_df_pseudo, dim3(df_blocks(h->F)), dim3(DF_BLOCK), 0, h->st, h->p, (double)(iters - DF_REC_FROM));
+    hipLaunchKernelGGL(k_df_pseudo, dim3(df_blocks(h->F)), dim3(DF_BLOCK), 0, h->st.get(), h->p, (double)(iters - DF_REC_FROM));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(h->st));
+    HIP_TRY(hipStreamSynchronize(h->st.get()));
     h->burnin = iters;
     h->burnt = true;
     return MMG_OK;
@@ -174,13 +162,13 @@ extern "C" int mmg_diff_tune_batch(mmg_diff *h, uint32_t *untuned)
     if (!h->burnt) return fail(MMG_ERR_STATE, "mmg_diff_tune_batch before mmg_diff_burnin");
     if (h->sampled) return fail(MMG_ERR_STATE, "mmg_diff_tune_batch after sampling has started");
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMemsetAsync(h->d_cnt, 0, 4, h->st));
+    HIP_TRY(hipMemsetAsync(h->d_cnt.get(), 0, 4, h->st.get()));
     const uint32_t it0 = h->burnin + h->batches * DF_BATCH;
-    hipLaunchKernelGGL(k_df_tune, dim3(df_blocks(h->F)), dim3(DF_BLOCK), 0, h->st, h->p, it0, (int)h->batches, h->d_cnt);
+    hipLaunchKernelGGL(k_df_tune, dim3(df_blocks(h->F)), dim3(DF_BLOCK), 0, h->st.get(), h->p, it0, (int)h->batches, h->d_cnt.get());
     HIP_TRY(hipGetLastError());
     int cnt = 0;
-    HIP_TRY(hipMemcpyAsync(&cnt, h->d_cnt, 4, hipMemcpyDeviceToHost, h->st));
-    HIP_TRY(hipStreamSynchronize(h->st));
+    HIP_TRY(hipMemcpyAsync(&cnt, h->d_cnt.get(), 4, hipMemcpyDeviceToHost, h->st.get()));
+    HIP_TRY(hipStreamSynchronize(h->st.get()));
     ++h->batches;
     *untuned = (uint32_t)cnt;
     return MMG_OK;
@@ -195,10 +183,10 @@ extern "C" int mmg_diff_sample(mmg_diff *h, uint32_t iters)
     const uint32_t t_first = h->batches * DF_BATCH + h->sampled;
     for (uint32_t j = 0; j < iters; j += DF_CHUNK) {
         const uint32_t n = iters - j < DF_CHUNK ? iters - j : DF_CHUNK;
-        hipLaunchKernelGGL(k_df_run, dim3(df_blocks(h->F)), dim3(DF_BLOCK), 0, h->st, h->p, h->burnin + t_first + j, (int)(t_first + j), (int)n, 2, 0);
+        hipLaunchKernelGGL(k_df_run, dim3(df_blocks(h->F)), dim3(DF_BLOCK), 0, h->st.get(), h->p, h->burnin + t_first + j, (int)(t_first + j), (int)n, 2, 0);
     }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(h->st));
+    HIP_TRY(hipStreamSynchronize(h->st.get()));
     h->sampled += iters;
     return MMG_OK;
 }
@@ -211,7 +199,7 @@ extern "C" int mmg_diff_get_results(mmg_diff *h, double *gamma_mean, double *log
     const size_t F = h->F;
     auto slot = [&](int o, std::vector<double> &v) {
         v.resize(F);
-        return hipMemcpy(v.data(), h->d_st + (size_t)o * F, F * 8, hipMemcpyDeviceToHost);
+        return hipMemcpy(v.data(), h->d_st.get() + (size_t)o * F, F * 8, hipMemcpyDeviceToHost);
     };
     std::vector<double> a, b;
     // the means as BMS::gammamean / alphamean / betamean / etamean form them: sum / count, on the host
@@ -259,4 +247,4 @@ extern "C" int mmg_diff_device_bytes(mmg_diff *h, uint64_t *bytes)
     return MMG_OK;
 }
 
-extern "C" void mmg_diff_destroy(mmg_diff *h) { diff_free(h); }
+extern "C" void mmg_diff_destroy(mmg_diff *h) { delete h; }

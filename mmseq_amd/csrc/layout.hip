@@ -13,6 +13,7 @@
 #include <rocprim/device/device_select.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
+#include "mmg_host.h"
 #include "mmg_launch.h"
 
 namespace mmg {
@@ -202,13 +203,11 @@ hipError_t layout_scan_lens(uint64_t m, const uint32_t *d_len, uint64_t *d_rp, h
     size_t tmp = 0;
     hipError_t e = rocprim::inclusive_scan(nullptr, tmp, it, d_rp + 1, m, rocprim::plus<uint64_t>(), s);
     if (e != hipSuccess) return e;
-    void *d_tmp = nullptr;
-    if ((e = hipMalloc(&d_tmp, tmp ? tmp : 8)) != hipSuccess) return e;
-    e = rocprim::inclusive_scan(d_tmp, tmp, it, d_rp + 1, m, rocprim::plus<uint64_t>(), s);
-    if (e == hipSuccess) e = hipMemsetAsync(d_rp, 0, sizeof(uint64_t), s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(d_tmp);
-    return e;
+    DevBuf<uint8_t> d_tmp;
+    HIPE_TRY(d_tmp.alloc(tmp ? tmp : 8));
+    HIPE_TRY(rocprim::inclusive_scan(d_tmp.get(), tmp, it, d_rp + 1, m, rocprim::plus<uint64_t>(), s));
+    HIPE_TRY(hipMemsetAsync(d_rp, 0, sizeof(uint64_t), s));
+    return hipStreamSynchronize(s);
 }
 
 // ---- step 0 of the canonical layout: rows with a small multiplicity are stored as that many rows of multiplicity 1
@@ -253,65 +252,57 @@ __global__ __launch_bounds__(256) void k_expand_cols(uint64_t m_new, const uint6
     for (uint64_t j = 0; j < L; ++j) col_new[d0 + j] = col_old[s0 + j];
 }
 
-hipError_t layout_expand_rows(uint64_t *m_io, uint64_t *nnz_io, uint64_t **d_rp, uint32_t **d_col, uint32_t **d_k, size_t col_pad, hipStream_t s)
+hipError_t layout_expand_rows(uint64_t *m_io, uint64_t *nnz_io, DevBuf<uint64_t> &d_rp, DevBuf<uint32_t> &d_col, DevBuf<uint32_t> &d_k, size_t col_pad, hipStream_t s)
 {
     const uint64_t m = *m_io;
-    if (m == 0 || !d_k || !*d_k) return hipSuccess;
+    if (m == 0 || !d_k) return hipSuccess;
     if (m >= 0xffffffffull) return hipSuccess;           // (the caller rejects such a problem for the canonical layout anyway)
-    uint32_t *reps = nullptr, *len_new = nullptr, *k_new = nullptr, *src = nullptr, *col_new = nullptr;
-    uint64_t *first = nullptr, *rp_new = nullptr;
-    unsigned long long *d_stats = nullptr, stats[2] = {0, 0};
-    hipError_t e = hipSuccess;
-    auto done = [&](hipError_t rc) {
-        for (void *x : {(void *)reps, (void *)len_new, (void *)k_new, (void *)src, (void *)col_new, (void *)first, (void *)rp_new, (void *)d_stats})
-            if (x) (void)hipFree(x);
-        return rc;
-    };
-#define X_TRY(expr) do { e = (expr); if (e != hipSuccess) return done(e); } while (0)
-    X_TRY(hipMalloc((void **)&reps, m * 4));
-    X_TRY(hipMalloc((void **)&d_stats, 16));
-    X_TRY(hipMemsetAsync(d_stats, 0, 16, s));
+    DevBuf<uint32_t> reps, len_new, k_new, src, col_new;
+    DevBuf<uint64_t> first, rp_new;
+    DevBuf<unsigned long long> d_stats;
+    unsigned long long stats[2] = {0, 0};
+    HIPE_TRY(reps.alloc(m));
+    HIPE_TRY(d_stats.alloc(2));
+    HIPE_TRY(hipMemsetAsync(d_stats.get(), 0, 16, s));
     const unsigned g = blocks_of(m);
-    hipLaunchKernelGGL(k_expand_count, dim3(g), dim3(256), 0, s, m, (const uint64_t *)*d_rp, (const uint32_t *)*d_k, reps, d_stats);
-    X_TRY(hipGetLastError());
-    X_TRY(hipMemcpyAsync(stats, d_stats, 16, hipMemcpyDeviceToHost, s));
-    X_TRY(hipStreamSynchronize(s));
+    hipLaunchKernelGGL(k_expand_count, dim3(g), dim3(256), 0, s, m, (const uint64_t *)d_rp.get(), (const uint32_t *)d_k.get(), reps.get(), d_stats.get());
+    HIPE_TRY(hipGetLastError());
+    HIPE_TRY(hipMemcpyAsync(stats, d_stats.get(), 16, hipMemcpyDeviceToHost, s));
+    HIPE_TRY(hipStreamSynchronize(s));
     if (stats[0] == 0) { // nothing to expand; an array of ones is no array
-        if (stats[1] == 0) { (void)hipFree(*d_k); *d_k = nullptr; }
-        return done(hipSuccess);
+        if (stats[1] == 0) d_k.reset();
+        return hipSuccess;
     }
-    X_TRY(hipMalloc((void **)&first, (m + 1) * 8));
-    X_TRY(layout_scan_lens(m, reps, first, s));
+    HIPE_TRY(first.alloc(m + 1));
+    HIPE_TRY(layout_scan_lens(m, reps.get(), first.get(), s));
     uint64_t m_new = 0;
-    X_TRY(hipMemcpy(&m_new, first + m, 8, hipMemcpyDeviceToHost));
+    HIPE_TRY(hipMemcpy(&m_new, first.get() + m, 8, hipMemcpyDeviceToHost));
     // A heavily collapsed file would be un-collapsed by this step: beyond LAYOUT_EXPAND_MAX_RATIO x the rows (or the row limit of one
     // device) the rows keep their multiplicities and the multiplicity kernel draws for them (k categoricals per row, the same draws).
     // The rule depends on the set of rows only, like everything else of the stored order.
-    if (m_new > LAYOUT_EXPAND_MAX_RATIO * m || m_new >= 0xffffffffull) return done(hipSuccess);
-    X_TRY(hipMalloc((void **)&len_new, m_new * 4));
-    X_TRY(hipMalloc((void **)&k_new, m_new * 4));
-    X_TRY(hipMalloc((void **)&src, m_new * 4));
-    hipLaunchKernelGGL(k_expand_rows, dim3(g), dim3(256), 0, s, m, (const uint64_t *)*d_rp, (const uint32_t *)*d_k, (const uint64_t *)first, len_new, k_new, src);
-    X_TRY(hipGetLastError());
-    X_TRY(hipMalloc((void **)&rp_new, (m_new + 1) * 8));
-    X_TRY(layout_scan_lens(m_new, len_new, rp_new, s));
+    if (m_new > LAYOUT_EXPAND_MAX_RATIO * m || m_new >= 0xffffffffull) return hipSuccess;
+    HIPE_TRY(len_new.alloc(m_new));
+    HIPE_TRY(k_new.alloc(m_new));
+    HIPE_TRY(src.alloc(m_new));
+    hipLaunchKernelGGL(k_expand_rows, dim3(g), dim3(256), 0, s, m, (const uint64_t *)d_rp.get(), (const uint32_t *)d_k.get(), (const uint64_t *)first.get(), len_new.get(), k_new.get(), src.get());
+    HIPE_TRY(hipGetLastError());
+    HIPE_TRY(rp_new.alloc(m_new + 1));
+    HIPE_TRY(layout_scan_lens(m_new, len_new.get(), rp_new.get(), s));
     uint64_t nnz_new = 0;
-    X_TRY(hipMemcpy(&nnz_new, rp_new + m_new, 8, hipMemcpyDeviceToHost));
-    X_TRY(hipMalloc((void **)&col_new, (nnz_new + col_pad) * 4));
-    X_TRY(hipMemsetAsync(col_new + nnz_new, 0, col_pad * 4, s));
-    hipLaunchKernelGGL(k_expand_cols, dim3(blocks_of(m_new)), dim3(256), 0, s, m_new, (const uint64_t *)*d_rp, (const uint32_t *)*d_col, (const uint32_t *)src,
-                       (const uint64_t *)rp_new, col_new);
-    X_TRY(hipGetLastError());
-    X_TRY(hipStreamSynchronize(s));
-    (void)hipFree(*d_rp); *d_rp = rp_new; rp_new = nullptr;
-    (void)hipFree(*d_col); *d_col = col_new; col_new = nullptr;
-    (void)hipFree(*d_k);
-    if (stats[1] == 0) *d_k = nullptr;                     // every multiplicity expanded away
-    else { *d_k = k_new; k_new = nullptr; }
+    HIPE_TRY(hipMemcpy(&nnz_new, rp_new.get() + m_new, 8, hipMemcpyDeviceToHost));
+    HIPE_TRY(col_new.alloc(nnz_new + col_pad));
+    HIPE_TRY(hipMemsetAsync(col_new.get() + nnz_new, 0, col_pad * 4, s));
+    hipLaunchKernelGGL(k_expand_cols, dim3(blocks_of(m_new)), dim3(256), 0, s, m_new, (const uint64_t *)d_rp.get(), (const uint32_t *)d_col.get(), (const uint32_t *)src.get(),
+                       (const uint64_t *)rp_new.get(), col_new.get());
+    HIPE_TRY(hipGetLastError());
+    HIPE_TRY(hipStreamSynchronize(s));
+    d_rp = std::move(rp_new);
+    d_col = std::move(col_new);
+    if (stats[1] == 0) d_k.reset();                        // every multiplicity expanded away
+    else d_k = std::move(k_new);
     *m_io = m_new;
     *nnz_io = nnz_new;
-#undef X_TRY
-    return done(hipSuccess);
+    return hipSuccess;
 }
 
 static hipError_t sort_pairs(uint64_t m, uint64_t *k_in, uint64_t *k_out, uint32_t *v_in, uint32_t *v_out, hipStream_t s)
@@ -319,91 +310,76 @@ static hipError_t sort_pairs(uint64_t m, uint64_t *k_in, uint64_t *k_out, uint32
     size_t tmp = 0;
     hipError_t e = rocprim::radix_sort_pairs(nullptr, tmp, k_in, k_out, v_in, v_out, m, 0, 64, s);
     if (e != hipSuccess) return e;
-    void *d_tmp = nullptr;
-    if ((e = hipMalloc(&d_tmp, tmp ? tmp : 8)) != hipSuccess) return e;
-    e = rocprim::radix_sort_pairs(d_tmp, tmp, k_in, k_out, v_in, v_out, m, 0, 64, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(d_tmp);
-    return e;
+    DevBuf<uint8_t> d_tmp;
+    HIPE_TRY(d_tmp.alloc(tmp ? tmp : 8));
+    HIPE_TRY(rocprim::radix_sort_pairs(d_tmp.get(), tmp, k_in, k_out, v_in, v_out, m, 0, 64, s));
+    return hipStreamSynchronize(s);
 }
 
-hipError_t layout_canonical_sort(uint64_t m, uint64_t nnz, uint64_t **d_rp, uint32_t **d_col, uint32_t **d_k, uint64_t *d_key,
+hipError_t layout_canonical_sort(uint64_t m, uint64_t nnz, DevBuf<uint64_t> &d_rp, DevBuf<uint32_t> &d_col, DevBuf<uint32_t> &d_k, uint64_t *d_key,
                                  size_t col_pad, hipStream_t s)
 {
     if (m == 0) return hipSuccess;
-    uint64_t *hash = nullptr, *k2 = nullptr, *rp_new = nullptr;
-    uint32_t *len = nullptr, *idx = nullptr, *idx2 = nullptr, *col_new = nullptr, *kk_new = nullptr, *len2 = nullptr;
-    hipError_t e = hipSuccess;
-    auto done = [&](hipError_t rc) {
-        for (void *x : {(void *)hash, (void *)k2, (void *)rp_new, (void *)len, (void *)idx, (void *)idx2, (void *)col_new, (void *)kk_new, (void *)len2})
-            if (x) (void)hipFree(x);
-        return rc;
-    };
-#define L_TRY(expr) do { e = (expr); if (e != hipSuccess) return done(e); } while (0)
-    L_TRY(hipMalloc((void **)&hash, m * 8));
-    L_TRY(hipMalloc((void **)&k2, m * 8));
-    L_TRY(hipMalloc((void **)&len, m * 4));
-    L_TRY(hipMalloc((void **)&idx, m * 4));
-    L_TRY(hipMalloc((void **)&idx2, m * 4));
+    DevBuf<uint64_t> hash, k2, rp_new;
+    DevBuf<uint32_t> len, idx, idx2, col_new, kk_new, len2;
+    HIPE_TRY(hash.alloc(m));
+    HIPE_TRY(k2.alloc(m));
+    HIPE_TRY(len.alloc(m));
+    HIPE_TRY(idx.alloc(m));
+    HIPE_TRY(idx2.alloc(m));
     const unsigned g = blocks_of(m);
-    hipLaunchKernelGGL(k_row_keys<true>, dim3(g), dim3(256), 0, s, m, (const uint64_t *)*d_rp, *d_col, d_k ? (const uint32_t *)*d_k : (const uint32_t *)nullptr, d_key, hash, len);
-    hipLaunchKernelGGL(k_iota, dim3(g), dim3(256), 0, s, m, idx);
-    L_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_row_keys<true>, dim3(g), dim3(256), 0, s, m, (const uint64_t *)d_rp.get(), d_col.get(), (const uint32_t *)d_k.get(), d_key, hash.get(), len.get());
+    hipLaunchKernelGGL(k_iota, dim3(g), dim3(256), 0, s, m, idx.get());
+    HIPE_TRY(hipGetLastError());
     // least significant first: content hash, then the key; both sorts are stable, so equal (key, hash) keep the caller's order
-    L_TRY(sort_pairs(m, hash, k2, idx, idx2, s));
-    hipLaunchKernelGGL(k_gather<uint64_t>, dim3(g), dim3(256), 0, s, m, (const uint64_t *)d_key, (const uint32_t *)idx2, hash); // hash buffer reused: keys in hash order
-    L_TRY(hipGetLastError());
-    L_TRY(sort_pairs(m, hash, d_key, idx2, idx, s)); // d_key: sorted keys, idx: stored row -> caller row
-    (void)hipFree(hash); hash = nullptr;
-    (void)hipFree(k2); k2 = nullptr;
-    (void)hipFree(idx2); idx2 = nullptr;
-    L_TRY(hipMalloc((void **)&len2, m * 4));
-    hipLaunchKernelGGL(k_gather<uint32_t>, dim3(g), dim3(256), 0, s, m, (const uint32_t *)len, (const uint32_t *)idx, len2);
-    L_TRY(hipGetLastError());
-    L_TRY(hipMalloc((void **)&rp_new, (m + 1) * 8));
-    L_TRY(layout_scan_lens(m, len2, rp_new, s));
-    (void)hipFree(len); len = nullptr;
-    (void)hipFree(len2); len2 = nullptr;
-    L_TRY(hipMalloc((void **)&col_new, (nnz + col_pad) * 4));
-    L_TRY(hipMemsetAsync(col_new + nnz, 0, col_pad * 4, s));
-    hipLaunchKernelGGL(k_gather_csr, dim3(g), dim3(256), 0, s, m, (const uint64_t *)*d_rp, (const uint32_t *)*d_col, (const uint32_t *)idx,
-                       (const uint64_t *)rp_new, (const uint64_t *)d_key, col_new);
-    if (d_k && *d_k) {
-        L_TRY(hipMalloc((void **)&kk_new, m * 4));
-        hipLaunchKernelGGL(k_gather<uint32_t>, dim3(g), dim3(256), 0, s, m, (const uint32_t *)*d_k, (const uint32_t *)idx, kk_new);
+    HIPE_TRY(sort_pairs(m, hash.get(), k2.get(), idx.get(), idx2.get(), s));
+    hipLaunchKernelGGL(k_gather<uint64_t>, dim3(g), dim3(256), 0, s, m, (const uint64_t *)d_key, (const uint32_t *)idx2.get(), hash.get()); // hash buffer reused: keys in hash order
+    HIPE_TRY(hipGetLastError());
+    HIPE_TRY(sort_pairs(m, hash.get(), d_key, idx2.get(), idx.get(), s)); // d_key: sorted keys, idx: stored row -> caller row
+    hash.reset();
+    k2.reset();
+    idx2.reset();
+    HIPE_TRY(len2.alloc(m));
+    hipLaunchKernelGGL(k_gather<uint32_t>, dim3(g), dim3(256), 0, s, m, (const uint32_t *)len.get(), (const uint32_t *)idx.get(), len2.get());
+    HIPE_TRY(hipGetLastError());
+    HIPE_TRY(rp_new.alloc(m + 1));
+    HIPE_TRY(layout_scan_lens(m, len2.get(), rp_new.get(), s));
+    len.reset();
+    len2.reset();
+    HIPE_TRY(col_new.alloc(nnz + col_pad));
+    HIPE_TRY(hipMemsetAsync(col_new.get() + nnz, 0, col_pad * 4, s));
+    hipLaunchKernelGGL(k_gather_csr, dim3(g), dim3(256), 0, s, m, (const uint64_t *)d_rp.get(), (const uint32_t *)d_col.get(), (const uint32_t *)idx.get(),
+                       (const uint64_t *)rp_new.get(), (const uint64_t *)d_key, col_new.get());
+    if (d_k) {
+        HIPE_TRY(kk_new.alloc(m));
+        hipLaunchKernelGGL(k_gather<uint32_t>, dim3(g), dim3(256), 0, s, m, (const uint32_t *)d_k.get(), (const uint32_t *)idx.get(), kk_new.get());
     }
-    L_TRY(hipGetLastError());
-    L_TRY(hipStreamSynchronize(s));
-    (void)hipFree(*d_rp); *d_rp = rp_new; rp_new = nullptr;
-    (void)hipFree(*d_col); *d_col = col_new; col_new = nullptr;
-    if (kk_new) { (void)hipFree(*d_k); *d_k = kk_new; kk_new = nullptr; }
-#undef L_TRY
-    return done(hipSuccess);
+    HIPE_TRY(hipGetLastError());
+    HIPE_TRY(hipStreamSynchronize(s));
+    d_rp = std::move(rp_new);
+    d_col = std::move(col_new);
+    if (kk_new) d_k = std::move(kk_new);
+    return hipSuccess;
 }
 
 hipError_t layout_segments(uint64_t m, const uint64_t *d_key, uint64_t max_segments, std::vector<uint64_t> &starts, hipStream_t s)
 {
     starts.clear();
     if (m == 0) return hipSuccess;
-    uint64_t *d_out = nullptr;
-    unsigned long long *d_count = nullptr;
-    hipError_t e = hipMalloc((void **)&d_out, (max_segments + 1) * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_count, 8);
-    if (e == hipSuccess) e = hipMemsetAsync(d_count, 0, 8, s);
+    DevBuf<uint64_t> d_out;
+    DevBuf<unsigned long long> d_count;
+    HIPE_TRY(d_out.alloc(max_segments + 1));
+    HIPE_TRY(d_count.alloc(1));
+    HIPE_TRY(hipMemsetAsync(d_count.get(), 0, 8, s));
     unsigned long long count = 0;
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_segment_starts, dim3(blocks_of(m)), dim3(256), 0, s, m, d_key, max_segments, d_out, d_count);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(&count, d_count, 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess && count <= max_segments) {
-        starts.resize(count);
-        e = hipMemcpy(starts.data(), d_out, count * 8, hipMemcpyDeviceToHost);
-        std::sort(starts.begin(), starts.end());
-    }
-    if (d_out) (void)hipFree(d_out);
-    if (d_count) (void)hipFree(d_count);
+    hipLaunchKernelGGL(k_segment_starts, dim3(blocks_of(m)), dim3(256), 0, s, m, d_key, max_segments, d_out.get(), d_count.get());
+    HIPE_TRY(hipGetLastError());
+    HIPE_TRY(hipMemcpyAsync(&count, d_count.get(), 8, hipMemcpyDeviceToHost, s));
+    HIPE_TRY(hipStreamSynchronize(s));
+    if (count > max_segments) return hipSuccess;
+    starts.resize(count);
+    const hipError_t e = hipMemcpy(starts.data(), d_out.get(), count * 8, hipMemcpyDeviceToHost);
+    std::sort(starts.begin(), starts.end());
     return e;
 }
 
@@ -431,14 +407,13 @@ hipError_t layout_max_row_len(uint64_t m, const uint64_t *d_rp, uint32_t *max_le
 {
     *max_len = 0;
     if (m == 0) return hipSuccess;
-    unsigned int *d = nullptr;
-    hipError_t e = hipMalloc((void **)&d, 4);
-    if (e == hipSuccess) e = hipMemsetAsync(d, 0, 4, s);
-    if (e == hipSuccess) { hipLaunchKernelGGL(k_max_len, dim3(blocks_of(m)), dim3(256), 0, s, m, d_rp, d); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipMemcpyAsync(max_len, d, 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (d) (void)hipFree(d);
-    return e;
+    DevBuf<unsigned int> d;
+    HIPE_TRY(d.alloc(1));
+    HIPE_TRY(hipMemsetAsync(d.get(), 0, 4, s));
+    hipLaunchKernelGGL(k_max_len, dim3(blocks_of(m)), dim3(256), 0, s, m, d_rp, d.get());
+    HIPE_TRY(hipGetLastError());
+    HIPE_TRY(hipMemcpyAsync(max_len, d.get(), 4, hipMemcpyDeviceToHost, s));
+    return hipStreamSynchronize(s);
 }
 
 // ---- the list of the rows on the conditional-binomial chain (mmg_types.h: bigk_row; sampled by k_sample_bigk) -------------------
@@ -457,37 +432,34 @@ __global__ __launch_bounds__(256) void k_bigk_count(uint64_t m, const IdxT *__re
     if ((threadIdx.x & 63) == 0 && c) atomicAdd(count, (unsigned long long)c);
 }
 template <typename IdxT>
-static hipError_t bigk_rows(uint64_t m, const IdxT *d_rp, const uint32_t *d_k, uint64_t **d_list, uint64_t *n_list, hipStream_t s)
+static hipError_t bigk_rows(uint64_t m, const IdxT *d_rp, const uint32_t *d_k, DevBuf<uint64_t> &d_list, uint64_t *n_list, hipStream_t s)
 {
-    unsigned long long *d_n = nullptr;
-    void *d_tmp = nullptr;
-    uint64_t *out = nullptr;
-    auto done = [&](hipError_t rc) { if (d_n) (void)hipFree(d_n); if (d_tmp) (void)hipFree(d_tmp); if (rc != hipSuccess && out) (void)hipFree(out); return rc; };
-#define L_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return done(_e); } while (0)
-    L_TRY(hipMalloc((void **)&d_n, 16));
-    L_TRY(hipMemsetAsync(d_n, 0, 16, s));
-    hipLaunchKernelGGL(k_bigk_count<IdxT>, dim3(blocks_of(m)), dim3(256), 0, s, m, d_rp, d_k, d_n);
-    L_TRY(hipGetLastError());
+    DevBuf<unsigned long long> d_n;
+    DevBuf<uint8_t> d_tmp;
+    DevBuf<uint64_t> out;
+    HIPE_TRY(d_n.alloc(2));
+    HIPE_TRY(hipMemsetAsync(d_n.get(), 0, 16, s));
+    hipLaunchKernelGGL(k_bigk_count<IdxT>, dim3(blocks_of(m)), dim3(256), 0, s, m, d_rp, d_k, d_n.get());
+    HIPE_TRY(hipGetLastError());
     unsigned long long n = 0;
-    L_TRY(hipMemcpyAsync(&n, d_n, 8, hipMemcpyDeviceToHost, s));
-    L_TRY(hipStreamSynchronize(s));
-    if (n == 0) return done(hipSuccess);
-    L_TRY(hipMalloc((void **)&out, n * sizeof(uint64_t)));
+    HIPE_TRY(hipMemcpyAsync(&n, d_n.get(), 8, hipMemcpyDeviceToHost, s));
+    HIPE_TRY(hipStreamSynchronize(s));
+    if (n == 0) return hipSuccess;
+    HIPE_TRY(out.alloc(n));
     const BigkRowPred<IdxT> pred{d_rp, d_k};
     rocprim::counting_iterator<uint64_t> rows(0);
     size_t tmp = 0;
-    L_TRY(rocprim::select(nullptr, tmp, rows, out, d_n + 1, (size_t)m, pred, s));
-    L_TRY(hipMalloc(&d_tmp, tmp ? tmp : 8));
-    L_TRY(rocprim::select(d_tmp, tmp, rows, out, d_n + 1, (size_t)m, pred, s));
-    L_TRY(hipStreamSynchronize(s));
-#undef L_TRY
-    *d_list = out;
+    HIPE_TRY(rocprim::select(nullptr, tmp, rows, out.get(), d_n.get() + 1, (size_t)m, pred, s));
+    HIPE_TRY(d_tmp.alloc(tmp ? tmp : 8));
+    HIPE_TRY(rocprim::select(d_tmp.get(), tmp, rows, out.get(), d_n.get() + 1, (size_t)m, pred, s));
+    HIPE_TRY(hipStreamSynchronize(s));
+    d_list = std::move(out);
     *n_list = n;
-    return done(hipSuccess);
+    return hipSuccess;
 }
-hipError_t layout_bigk_rows(bool idx64, uint64_t m, const void *d_rp, const uint32_t *d_k, uint64_t **d_list, uint64_t *n_list, hipStream_t s)
+hipError_t layout_bigk_rows(bool idx64, uint64_t m, const void *d_rp, const uint32_t *d_k, DevBuf<uint64_t> &d_list, uint64_t *n_list, hipStream_t s)
 {
-    *d_list = nullptr;
+    d_list.reset();
     *n_list = 0;
     if (m == 0 || !d_k) return hipSuccess;
     return idx64 ? bigk_rows<uint64_t>(m, (const uint64_t *)d_rp, d_k, d_list, n_list, s) : bigk_rows<uint32_t>(m, (const uint32_t *)d_rp, d_k, d_list, n_list, s);

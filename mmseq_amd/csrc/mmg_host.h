@@ -5,9 +5,124 @@
 #include <cstring>
 #include <functional>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 #include "../../include/mmgibbs.h"
 #include "mmg_types.h"
+
+namespace mmg {
+
+int fail(int code, const std::string &msg);   // records the thread-local message behind mmg_last_error(), returns code
+int opt(int option);                          // mmg_selftest_option value, -1 = default
+bool fail_acquire();                          // MMG_OPT_FAIL_ALLOC: this acquisition of an owner below is the one that fails
+enum { LIVE_BUFFERS = 0, LIVE_STREAMS = 1, LIVE_EVENTS = 2 };
+void count_live(int kind, int delta);         // what the owners below hold, for mmg_selftest_live
+
+// Owners of the library's device memory, streams and events.  Every acquisition goes through them (MMG_OPT_FAIL_ALLOC counts them);
+// a handle's members are owners, so what a failed create built is released by the destructors, in reverse declaration order.
+template <typename T> struct elem_size { static constexpr size_t value = sizeof(T); };
+template <> struct elem_size<void> { static constexpr size_t value = 1; };
+
+// A device buffer and the device it was allocated on: freed there, with the caller's current device restored.
+template <typename T>
+class DevBuf {
+public:
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p_(o.p_), dev_(o.dev_) { o.p_ = nullptr; }
+    template <typename U, typename V = T, typename = std::enable_if_t<std::is_void<V>::value>>
+    DevBuf(DevBuf<U> &&o) noexcept : p_(o.p_), dev_(o.dev_) { o.p_ = nullptr; } // (DevBuf<void>: a typed buffer seen as bytes)
+    DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { reset(); p_ = o.p_; dev_ = o.dev_; o.p_ = nullptr; } return *this; }
+    ~DevBuf() { reset(); }
+    hipError_t alloc(size_t count)
+    {
+        reset();
+        if (fail_acquire()) return hipErrorOutOfMemory;
+        hipError_t e = hipGetDevice(&dev_);
+        if (e == hipSuccess) e = hipMalloc((void **)&p_, count * elem_size<T>::value);
+        if (e != hipSuccess) p_ = nullptr;
+        else count_live(LIVE_BUFFERS, 1);
+        return e;
+    }
+    T *get() const { return p_; }
+    int device() const { return dev_; }
+    explicit operator bool() const { return p_ != nullptr; }
+    T *release() // (the caller frees it: no longer counted)
+    {
+        if (p_) count_live(LIVE_BUFFERS, -1);
+        T *p = p_;
+        p_ = nullptr;
+        return p;
+    }
+    void reset()
+    {
+        if (!p_) return;
+        int cur = dev_;
+        (void)hipGetDevice(&cur);
+        if (cur != dev_) (void)hipSetDevice(dev_);
+        (void)hipFree((void *)p_);
+        if (cur != dev_) (void)hipSetDevice(cur);
+        p_ = nullptr;
+        count_live(LIVE_BUFFERS, -1);
+    }
+
+private:
+    template <typename> friend class DevBuf;
+    T *p_ = nullptr;
+    int dev_ = 0;
+};
+
+// A stream or an event, destroyed with its owner.
+template <typename H, hipError_t (*Create)(H *, unsigned), hipError_t (*Destroy)(H), int Kind>
+class DevHandle {
+public:
+    DevHandle() = default;
+    DevHandle(const DevHandle &) = delete;
+    DevHandle &operator=(const DevHandle &) = delete;
+    DevHandle(DevHandle &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    ~DevHandle() { reset(); }
+    hipError_t create(unsigned flags = 0)
+    {
+        reset();
+        if (fail_acquire()) return hipErrorOutOfMemory; // (what hipStreamCreate* / hipEventCreate* return when the runtime cannot create one)
+        hipError_t e = Create(&h_, flags);
+        if (e != hipSuccess) h_ = nullptr;
+        else count_live(Kind, 1);
+        return e;
+    }
+    H get() const { return h_; }
+    explicit operator bool() const { return h_ != nullptr; }
+    void reset()
+    {
+        if (!h_) return;
+        (void)Destroy(h_);
+        h_ = nullptr;
+        count_live(Kind, -1);
+    }
+
+private:
+    H h_ = nullptr;
+};
+using DevStream = DevHandle<hipStream_t, hipStreamCreateWithFlags, hipStreamDestroy, LIVE_STREAMS>;
+using DevEvent = DevHandle<hipEvent_t, hipEventCreateWithFlags, hipEventDestroy, LIVE_EVENTS>;
+
+// a failed HIP call: record it and return MMG_ERR_HIP (functions that return an MMG_* code) ...
+#define HIP_TRY(expr)                                                                                         \
+    do {                                                                                                      \
+        hipError_t _e = (expr);                                                                               \
+        if (_e != hipSuccess)                                                                                 \
+            return mmg::fail(MMG_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));                 \
+    } while (0)
+// ... or return the error itself (functions that return a hipError_t: layout.hip, order.hip)
+#define HIPE_TRY(expr)                                                                                        \
+    do {                                                                                                      \
+        hipError_t _e = (expr);                                                                               \
+        if (_e != hipSuccess) return _e;                                                                      \
+    } while (0)
+
+} // namespace mmg
 
 struct mmg_problem {
     int device = 0;
@@ -17,29 +132,29 @@ struct mmg_problem {
     bool idx64 = false;
     int cu_count = 256;
     int layout = MMG_LAYOUT_CANONICAL;
-    void *d_row_ptr = nullptr;
-    uint32_t *d_col = nullptr;
-    uint32_t *d_k = nullptr;
-    double *d_l = nullptr;                      // device numbering
+    mmg::DevBuf<void> d_row_ptr;                // uint32_t or (idx64) uint64_t offsets
+    mmg::DevBuf<uint32_t> d_col;
+    mmg::DevBuf<uint32_t> d_k;
+    mmg::DevBuf<double> d_l;                    // device numbering
     std::vector<double> h_l;                    // caller numbering
     // transcript renumbering (tx_order): empty / nullptr = identity
     std::vector<uint32_t> h_int_of_ext, h_ext_of_int;
-    uint32_t *d_int_of_ext = nullptr, *d_ext_of_int = nullptr;
+    mmg::DevBuf<uint32_t> d_int_of_ext, d_ext_of_int;
     // sliced-ELL stream of k_sample_sell / k_em_sell
-    uint8_t *d_sell = nullptr;
+    mmg::DevBuf<uint8_t> d_sell;
     uint64_t sell_bytes = 0, n_sell_tiles = 0, n_fast_tiles = 0, n_far_tiles = 0, padded_slots = 0;
-    mmg::SellTile *d_sell_tiles = nullptr;
-    uint64_t *d_sell_chunk = nullptr;
+    mmg::DevBuf<mmg::SellTile> d_sell_tiles;
+    mmg::DevBuf<uint64_t> d_sell_chunk;
     int grid_sell = 0;
     // problems with multiplicities: the SELL_HASK tiles and the others as two descriptor lists with their own ranges (null / 0: no
     // SELL_HASK tile -- the one launch over d_sell_tiles does everything)
-    mmg::SellTile *d_sell_tiles_1 = nullptr, *d_sell_tiles_k = nullptr;
-    uint64_t *d_sell_chunk_k = nullptr;
+    mmg::DevBuf<mmg::SellTile> d_sell_tiles_1, d_sell_tiles_k;
+    mmg::DevBuf<uint64_t> d_sell_chunk_k;
     int grid_sell_k = 0;
     uint64_t n_hask_tiles = 0;
     // the rows on the conditional-binomial chain (mmg_types.h: bigk_row): their stored positions, ascending -- sampled by k_sample_bigk in
     // pieces of bigk_per_wave list entries per workgroup (the tile kernel skips them); h_bigk_list: the host's copy (the timed shard cut)
-    uint64_t *d_bigk_list = nullptr;
+    mmg::DevBuf<uint64_t> d_bigk_list;
     uint64_t n_bigk = 0;
     uint32_t bigk_per_wave = 0;
     int grid_bigk = 0;
@@ -48,9 +163,9 @@ struct mmg_problem {
     // list when every tile is like that) in its own ranges (2 and 4 chains: fewer resident waves); the other tiles without
     // multiplicities -- far tiles, CSR-walked tiles -- are a third list (d_sell_tiles_x) that k_sample_sell walks for all the
     // chains of the sampler in ONE launch (grid.y = chain), and so are the SELL_HASK tiles
-    mmg::SellTile *d_sell_tiles_f = nullptr, *d_sell_tiles_x = nullptr; // f may alias d_sell_tiles / d_sell_tiles_1 (not owned then)
-    bool owns_tiles_f = false;
-    uint64_t *d_sell_chunk_m[2] = {nullptr, nullptr}, *d_sell_chunk_x = nullptr;
+    mmg::DevBuf<mmg::SellTile> sell_tiles_f, d_sell_tiles_x; // sell_tiles_f: a list of its own, when not every tile is on the register path
+    const mmg::SellTile *d_sell_tiles_f = nullptr;       // sell_tiles_f or d_sell_tiles (not owned)
+    mmg::DevBuf<uint64_t> d_sell_chunk_m[2], d_sell_chunk_x;
     int grid_sell_m[2] = {0, 0}, grid_sell_x = 0;
     uint64_t n_x_tiles = 0;
     bool use_sell = false;
@@ -67,11 +182,11 @@ struct mmg_problem {
     uint32_t cnt_replicas = 1;                  // replicas of a sampler's count vectors (mmg_types.h: CNT_REPLICAS), 1 or CNT_REPLICAS
     bool canonical_rows = false;                // the rows are in canonical order: a canonical problem, or a shard cut from one
     // CSR tiles of the fallback kernel k_sample (built only when the sliced-ELL stream is not used)
-    mmg::TileDesc *d_tiles = nullptr;
+    mmg::DevBuf<mmg::TileDesc> d_tiles;
     uint64_t n_tiles = 0;
-    uint64_t *d_chunk_tile = nullptr;
+    mmg::DevBuf<uint64_t> d_chunk_tile;
     int grid_sample = 1;
-    uint64_t *d_colcnt = nullptr;               // hits per transcript, for the EM scale words (lazy)
+    mmg::DevBuf<uint64_t> d_colcnt;             // hits per transcript, for the EM scale words (lazy)
     bool order_derived = false;                 // the renumbering came from the hit graph (order.hip), not from the caller's tx_order
     bool k1_fixed_walk = false;    // the k = 1 sample kernel's straight-line instantiation (fewer than 5 groups per register-path tile on average)
     bool groups_reordered = false; // tx_order given and the library reordered its groups (spec version 7)
@@ -91,27 +206,27 @@ namespace mmg {
 struct PinnedStage {
     static constexpr size_t CHUNK = 16u << 20;
     void *buf[2] = {nullptr, nullptr};
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    DevEvent ev[2];
     ~PinnedStage()
     {
-        for (int i = 0; i < 2; ++i) { if (buf[i]) (void)hipHostFree(buf[i]); if (ev[i]) (void)hipEventDestroy(ev[i]); }
+        for (int i = 0; i < 2; ++i) if (buf[i]) (void)hipHostFree(buf[i]);
     }
     hipError_t copy_out(void *dst, const void *dsrc, size_t bytes, hipStream_t st)
     {
         for (int i = 0; i < 2; ++i) {
             if (!buf[i]) { hipError_t e = hipHostMalloc(&buf[i], CHUNK, hipHostMallocDefault); if (e != hipSuccess) { buf[i] = nullptr; return e; } }
-            if (!ev[i]) { hipError_t e = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming); if (e != hipSuccess) { ev[i] = nullptr; return e; } }
+            if (!ev[i]) HIPE_TRY(ev[i].create(hipEventDisableTiming));
         }
         const size_t chunks = (bytes + CHUNK - 1) / CHUNK;
         auto issue = [&](size_t c) {
             const size_t off = c * CHUNK, len = bytes - off < CHUNK ? bytes - off : CHUNK;
             hipError_t e = hipMemcpyAsync(buf[c & 1], (const char *)dsrc + off, len, hipMemcpyDeviceToHost, st);
-            return e == hipSuccess ? hipEventRecord(ev[c & 1], st) : e;
+            return e == hipSuccess ? hipEventRecord(ev[c & 1].get(), st) : e;
         };
         if (chunks) { hipError_t e = issue(0); if (e != hipSuccess) return e; }
         for (size_t c = 0; c < chunks; ++c) {
             if (c + 1 < chunks) { hipError_t e = issue(c + 1); if (e != hipSuccess) return e; } // (its buffer was emptied an iteration ago)
-            hipError_t e = hipEventSynchronize(ev[c & 1]);
+            hipError_t e = hipEventSynchronize(ev[c & 1].get());
             if (e != hipSuccess) return e;
             const size_t off = c * CHUNK, len = bytes - off < CHUNK ? bytes - off : CHUNK;
             std::memcpy((char *)dst + off, buf[c & 1], len);
@@ -139,18 +254,9 @@ int em_create_sharded(const mmg_problem *const *shards, int n_shards, const doub
 void em_exchange_buffers(mmg_em *e, int what, void **ptr, size_t *count);
 int em_device(const mmg_em *e);
 
-int fail(int code, const std::string &msg);   // records the thread-local message behind mmg_last_error(), returns code
-int opt(int option);                          // mmg_selftest_option value, -1 = default
 int require_device(int device);
 void weighted_chunks(const std::vector<uint64_t> &cum, uint64_t grid, std::vector<uint64_t> &chunk);
 void weighted_chunks_tapered(const std::vector<uint64_t> &cum, uint64_t grid, uint64_t resident, std::vector<uint64_t> &chunk);
-
-#define HIP_TRY(expr)                                                                                         \
-    do {                                                                                                      \
-        hipError_t _e = (expr);                                                                               \
-        if (_e != hipSuccess)                                                                                 \
-            return mmg::fail(MMG_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));                 \
-    } while (0)
 
 // caller numbering <-> device numbering of per-transcript host arrays
 template <typename T>

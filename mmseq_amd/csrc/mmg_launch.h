@@ -8,6 +8,8 @@
 
 namespace mmg {
 
+template <typename T> class DevBuf; // mmg_host.h
+
 // ---- k1.hip: the sample kernels (src/mmseq.cpp:857-891) and their stream builders
 const void *k1_sell_kernel(bool idx64, bool has_k, bool fixed_walk = false);   // k_sample_sell, 64 threads per workgroup
 const void *k1_sell_far_kernel(bool idx64);            // k_sample_sell for the list of far / CSR-walked tiles (far list prefetched), no multiplicities
@@ -77,13 +79,13 @@ void order_from_edges(uint32_t n, const std::vector<uint64_t> &edges, std::vecto
 // Row keys of the CSR in its current order.  d_key: m u64 (caller frees).
 hipError_t layout_map_cols(uint64_t nnz, uint32_t *d_col, const uint32_t *d_int_of_ext, hipStream_t s);
 hipError_t layout_row_keys(uint64_t m, const uint64_t *d_rp, const uint32_t *d_col, const uint32_t *d_k, uint64_t *d_key, hipStream_t s);
-// Sorts the CSR canonically: on return *d_rp / *d_col / *d_k (k may be nullptr) are NEW device buffers in canonical order (the
+// Sorts the CSR canonically: on return d_rp / d_col / d_k (k may be empty) are NEW device buffers in canonical order (the
 // old ones are freed), d_key holds the sorted keys.  col_pad: extra u32 slots allocated (zeroed) behind col.  m < 2^32.
-hipError_t layout_canonical_sort(uint64_t m, uint64_t nnz, uint64_t **d_rp, uint32_t **d_col, uint32_t **d_k, uint64_t *d_key,
+hipError_t layout_canonical_sort(uint64_t m, uint64_t nnz, DevBuf<uint64_t> &d_rp, DevBuf<uint32_t> &d_col, DevBuf<uint32_t> &d_k, uint64_t *d_key,
                                  size_t col_pad, hipStream_t s);
 // Canonical layout, step 0: a row that draws k >= 2 categoricals becomes k rows with k = 1 (mmg_types.h: draws_categoricals).  *d_rp / *d_col / *d_k are replaced when
-// any row expands; *m, *nnz follow; *d_k is freed and set to nullptr when no multiplicity other than 1 is left.
-hipError_t layout_expand_rows(uint64_t *m, uint64_t *nnz, uint64_t **d_rp, uint32_t **d_col, uint32_t **d_k, size_t col_pad, hipStream_t s);
+// any row expands; *m, *nnz follow; d_k is freed when no multiplicity other than 1 is left.
+hipError_t layout_expand_rows(uint64_t *m, uint64_t *nnz, DevBuf<uint64_t> &d_rp, DevBuf<uint32_t> &d_col, DevBuf<uint32_t> &d_k, size_t col_pad, hipStream_t s);
 // Start rows of the maximal runs of equal (near, band) in d_key (ascending; first entry 0).  Empty if there are more than
 // max_segments runs (rows in no useful order).
 hipError_t layout_segments(uint64_t m, const uint64_t *d_key, uint64_t max_segments, std::vector<uint64_t> &starts, hipStream_t s);
@@ -94,8 +96,8 @@ hipError_t layout_narrow_row_ptr(uint64_t m, const uint64_t *d_rp64, uint32_t *d
 // d_rp[0..m] = running sum of d_len[0..m)
 hipError_t layout_scan_lens(uint64_t m, const uint32_t *d_len, uint64_t *d_rp, hipStream_t s);
 hipError_t layout_max_row_len(uint64_t m, const uint64_t *d_rp, uint32_t *max_len, hipStream_t s);
-// The stored positions (ascending) of the rows on the conditional-binomial chain (mmg_types.h: bigk_row): *d_list is a NEW device buffer
-// of *n_list entries (nullptr / 0 without such rows or without multiplicities).  d_rp: the problem's row offsets (u32 or u64).
-hipError_t layout_bigk_rows(bool idx64, uint64_t m, const void *d_rp, const uint32_t *d_k, uint64_t **d_list, uint64_t *n_list, hipStream_t s);
+// The stored positions (ascending) of the rows on the conditional-binomial chain (mmg_types.h: bigk_row): d_list becomes a NEW device buffer
+// of *n_list entries (empty / 0 without such rows or without multiplicities).  d_rp: the problem's row offsets (u32 or u64).
+hipError_t layout_bigk_rows(bool idx64, uint64_t m, const void *d_rp, const uint32_t *d_k, DevBuf<uint64_t> &d_list, uint64_t *n_list, hipStream_t s);
 
 } // namespace mmg

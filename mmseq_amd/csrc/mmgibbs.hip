@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -28,11 +29,26 @@ extern "C" const char *mmg_last_error(void) { return g_err.c_str(); }
 extern "C" int mmg_abi_version(void) { return MMG_ABI_VERSION; }
 
 // self-test overrides (mmg_selftest_option): -1 = the library decides
-static std::atomic<int> g_opt[MMG_OPT_COUNT_] = {{-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}};
+static std::atomic<int> g_opt[MMG_OPT_COUNT_] = {{-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}};
+static std::atomic<int64_t> g_acquired{0}; // acquisitions through the owners since MMG_OPT_FAIL_ALLOC was last set
+static std::atomic<int64_t> g_live[3] = {{0}, {0}, {0}};
 int mmg::opt(int o) { return g_opt[o].load(std::memory_order_relaxed); }
+void mmg::count_live(int kind, int delta) { g_live[kind].fetch_add(delta, std::memory_order_relaxed); }
+extern "C" int mmg_selftest_live(int64_t *counts)
+{
+    if (!counts) return fail(MMG_ERR_ARG, "NULL argument");
+    for (int k = 0; k < 3; ++k) counts[k] = g_live[k].load(std::memory_order_relaxed);
+    return MMG_OK;
+}
+bool mmg::fail_acquire()
+{
+    const int v = opt(MMG_OPT_FAIL_ALLOC);
+    return v >= 0 && g_acquired.fetch_add(1, std::memory_order_relaxed) == v;
+}
 extern "C" int mmg_selftest_option(int option, int value)
 {
     if (option < 0 || option >= MMG_OPT_COUNT_) return fail(MMG_ERR_ARG, "unknown self-test option");
+    if (option == MMG_OPT_FAIL_ALLOC) g_acquired.store(0, std::memory_order_relaxed);
     g_opt[option].store(value < 0 ? -1 : value, std::memory_order_relaxed);
     return MMG_OK;
 }
@@ -75,17 +91,7 @@ static void parallel_slices(uint64_t n, F f)
 }
 
 // ------------------------------------------------------------------------------ problem
-static void problem_free(mmg_problem *p)
-{
-    if (!p) return;
-    (void)hipSetDevice(p->device);
-    for (void *x : {(void *)p->d_row_ptr, (void *)p->d_col, (void *)p->d_k, (void *)p->d_l, (void *)p->d_int_of_ext, (void *)p->d_ext_of_int,
-                    (void *)p->d_sell, (void *)p->d_sell_tiles, (void *)p->d_sell_chunk, (void *)p->d_sell_chunk_k, (void *)p->d_sell_tiles_1, (void *)p->d_sell_tiles_k, (void *)p->d_sell_chunk_m[0], (void *)p->d_sell_chunk_m[1], (void *)(p->owns_tiles_f ? p->d_sell_tiles_f : nullptr), (void *)p->d_sell_tiles_x, (void *)p->d_sell_chunk_x, (void *)p->d_bigk_list,
-                    (void *)p->d_tiles, (void *)p->d_chunk_tile,
-                    (void *)p->d_colcnt})
-        if (x) (void)hipFree(x);
-    delete p;
-}
+using ProblemPtr = std::unique_ptr<mmg_problem>;
 
 // Contiguous tile ranges of (nearly) equal COST: cum[t] = cost of tiles [0, t).  A tile that cannot run on the register path
 // is walked from the CSR and costs many times more; with equal tile counts a tail of such tiles (far rows are sorted
@@ -139,7 +145,7 @@ void mmg::weighted_chunks_tapered(const std::vector<uint64_t> &cum, uint64_t gri
 // range's first two tiles -- so that ONE scalar load gives a workgroup everything it needs to request its window and its first blocks
 // (with a plain table of boundaries the descriptors are a second dependent memory round trip: 1-2 us per workgroup, which is what a
 // config-2 launch of 29 us is largely made of).
-static hipError_t upload_ranges(const std::vector<uint64_t> &chunk, const std::vector<SellTile> &tiles, uint64_t **d_out)
+static hipError_t upload_ranges(const std::vector<uint64_t> &chunk, const std::vector<SellTile> &tiles, DevBuf<uint64_t> &d_out)
 {
     static_assert(sizeof(SellTile) == 24, "three 64-bit words per descriptor");
     const size_t n = chunk.size() - 1;
@@ -154,9 +160,8 @@ static hipError_t upload_ranges(const std::vector<uint64_t> &chunk, const std::v
             std::memcpy(&h[c * 8 + 2 + 3 * j], &d, sizeof(SellTile));
         }
     }
-    hipError_t e = hipMalloc((void **)d_out, h.size() * sizeof(uint64_t));
-    if (e == hipSuccess) e = hipMemcpy(*d_out, h.data(), h.size() * sizeof(uint64_t), hipMemcpyHostToDevice);
-    return e;
+    HIPE_TRY(d_out.alloc(h.size()));
+    return hipMemcpy(d_out.get(), h.data(), h.size() * sizeof(uint64_t), hipMemcpyHostToDevice);
 }
 
 // List entries per workgroup of k_sample_bigk (one wave): 64 -- a row per lane, no second helping.  Measured (profiles/r06_bigk_ab.md):
@@ -188,17 +193,15 @@ static int problem_build_sell(mmg_problem *p, const std::vector<uint64_t> &seg_s
     tile_row.push_back(p->m);
     const uint64_t nt = tile_row.size() - 1;
     if (nt >= 0x7fffffffull) return MMG_OK; // a 1-D grid cannot describe them; the CSR kernel takes over
-    uint64_t *d_tile_row = nullptr;
-    TileDesc *d_td = nullptr;
-    auto cleanup = [&]() { if (d_tile_row) (void)hipFree(d_tile_row); if (d_td) (void)hipFree(d_td); d_tile_row = nullptr; d_td = nullptr; };
-#define SELL_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { cleanup(); return fail(MMG_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); } } while (0)
-    SELL_TRY(hipMalloc((void **)&d_tile_row, tile_row.size() * sizeof(uint64_t)));
-    SELL_TRY(hipMemcpy(d_tile_row, tile_row.data(), tile_row.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-    SELL_TRY(hipMalloc((void **)&d_td, nt * sizeof(TileDesc)));
-    launch_tile_desc(p->idx64, p->d_row_ptr, p->d_col, p->d_k, d_tile_row, nt, d_td, 0);
-    SELL_TRY(hipGetLastError());
+    DevBuf<uint64_t> d_tile_row;
+    DevBuf<TileDesc> d_td;
+    HIP_TRY(d_tile_row.alloc(tile_row.size()));
+    HIP_TRY(hipMemcpy(d_tile_row.get(), tile_row.data(), tile_row.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIP_TRY(d_td.alloc(nt));
+    launch_tile_desc(p->idx64, p->d_row_ptr.get(), p->d_col.get(), p->d_k.get(), d_tile_row.get(), nt, d_td.get(), 0);
+    HIP_TRY(hipGetLastError());
     std::vector<TileDesc> td(nt);
-    SELL_TRY(hipMemcpy(td.data(), d_td, nt * sizeof(TileDesc), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(td.data(), d_td.get(), nt * sizeof(TileDesc), hipMemcpyDeviceToHost));
     const uint32_t WIN = SELL_WIN, BAND_MASK = ~((1u << LAYOUT_BAND_SHIFT) - 1u);
     // a tile qualifies for the register path iff its hits fit one window whose base is a band start and no row exceeds 255 hits
     auto qualifies = [&](const TileDesc &d) {
@@ -212,26 +215,21 @@ static int problem_build_sell(mmg_problem *p, const std::vector<uint64_t> &seg_s
         for (uint64_t t = 0; t < nt; ++t)
             if (td[t].nnz > 0 && !qualifies(td[t]) && td[t].maxlen <= 255 && td[t].nrows <= 64) cand.push_back((uint32_t)t);
         if (!cand.empty() && d_key) {
-            uint32_t *d_cand = nullptr, *d_out = nullptr;
-            auto cleanup2 = [&]() { if (d_cand) (void)hipFree(d_cand); if (d_out) (void)hipFree(d_out); };
+            DevBuf<uint32_t> d_cand, d_out;
             const size_t nc = cand.size();
-            hipError_t e = hipMalloc((void **)&d_cand, nc * 4);
-            if (e == hipSuccess) e = hipMalloc((void **)&d_out, nc * 12);
-            if (e == hipSuccess) e = hipMemcpy(d_cand, cand.data(), nc * 4, hipMemcpyHostToDevice);
+            HIP_TRY(d_cand.alloc(nc));
+            HIP_TRY(d_out.alloc(nc * 3));
+            HIP_TRY(hipMemcpy(d_cand.get(), cand.data(), nc * 4, hipMemcpyHostToDevice));
             std::vector<uint32_t> out(nc * 3);
-            if (e == hipSuccess) {
-                launch_tile_far(p->idx64, p->d_row_ptr, p->d_col, d_key, d_tile_row, d_cand, nc, d_out, 0);
-                e = hipGetLastError();
-            }
-            if (e == hipSuccess) e = hipMemcpy(out.data(), d_out, out.size() * 4, hipMemcpyDeviceToHost);
-            cleanup2();
-            if (e != hipSuccess) { cleanup(); return fail(MMG_ERR_HIP, std::string("far tiles: ") + hipGetErrorString(e)); }
+            launch_tile_far(p->idx64, p->d_row_ptr.get(), p->d_col.get(), d_key, d_tile_row.get(), d_cand.get(), nc, d_out.get(), 0);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpy(out.data(), d_out.get(), out.size() * 4, hipMemcpyDeviceToHost));
             for (size_t i = 0; i < nc; ++i) { far_wbase[cand[i]] = out[i]; far_nn[cand[i]] = out[nc + i]; far_nf[cand[i]] = out[2 * nc + i]; }
         }
     }
     auto is_far = [&](uint64_t t) { return far_nf[t] <= 255u; };
-    cleanup();
-#undef SELL_TRY
+    d_tile_row.reset();
+    d_td.reset();
     auto resident_raw = [&](bool has_k) { // workgroups of the kernel the device holds at once
         int per_cu = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k1_sell_kernel(p->idx64, has_k, false), 64, 0) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 16; }
@@ -256,7 +254,7 @@ static int problem_build_sell(mmg_problem *p, const std::vector<uint64_t> &seg_s
     // ranges of the two sample launches of a problem with multiplicities -- tiles whose rows all have k = 1, and the others, where a
     // row draws k times (k <= K_SMALL) or runs a binomial per hit.  Identical reads pile up on few hit sets of few abundant
     // transcripts: without their cost in the ranges one workgroup ends up with most of them (20 x the kernel time at config 3).
-    auto has_k_rows = [&](uint64_t t) { return p->d_k != nullptr && td[t].knot1 > 0; };
+    auto has_k_rows = [&](uint64_t t) { return p->d_k.get() != nullptr && td[t].knot1 > 0; };
     p->h_sell_cum.assign(nt + 1, 0);
     std::vector<uint64_t> cum1(nt + 1, 0), cumk(nt + 1, 0);
     uint64_t n_hask = 0;
@@ -343,10 +341,10 @@ static int problem_build_sell(mmg_problem *p, const std::vector<uint64_t> &seg_s
     p->padded_slots = slots;
     p->k1_fixed_walk = n_fast > 0 && slots < 5 * 256 * n_fast; // fewer than 5 groups per register-path tile on average (sell_kernels.h: FIXW)
     const size_t alloc = p->sell_bytes + 64 + 8 * 256; // head room: tiles without a block prefetch the head of the stream
-    HIP_TRY(hipMalloc((void **)&p->d_sell, alloc));
-    HIP_TRY(hipMemset(p->d_sell, 0, alloc));
-    HIP_TRY(hipMalloc((void **)&p->d_sell_tiles, nt * sizeof(SellTile)));
-    HIP_TRY(hipMemcpy(p->d_sell_tiles, st.data(), nt * sizeof(SellTile), hipMemcpyHostToDevice));
+    HIP_TRY(p->d_sell.alloc(alloc));
+    HIP_TRY(hipMemset(p->d_sell.get(), 0, alloc));
+    HIP_TRY(p->d_sell_tiles.alloc(nt));
+    HIP_TRY(hipMemcpy(p->d_sell_tiles.get(), st.data(), nt * sizeof(SellTile), hipMemcpyHostToDevice));
     p->grid_sell = (int)n_ranges;
     p->n_hask_tiles = n_hask;
     // many ranges per band: the flushes of neighbouring workgroups meet at the same addresses (mmg_types.h: CNT_REPLICAS)
@@ -365,12 +363,12 @@ static int problem_build_sell(mmg_problem *p, const std::vector<uint64_t> &seg_s
         weighted_chunks(c1, g1, r1);
         weighted_chunks(ck, gk, rk);
         chunk = r1;
-        HIP_TRY(hipMalloc((void **)&p->d_sell_tiles_1, s1.size() * sizeof(SellTile)));
-        HIP_TRY(hipMemcpy(p->d_sell_tiles_1, s1.data(), s1.size() * sizeof(SellTile), hipMemcpyHostToDevice));
-        HIP_TRY(hipMalloc((void **)&p->d_sell_tiles_k, sk.size() * sizeof(SellTile)));
-        HIP_TRY(hipMemcpy(p->d_sell_tiles_k, sk.data(), sk.size() * sizeof(SellTile), hipMemcpyHostToDevice));
-        HIP_TRY(upload_ranges(rk, sk, &p->d_sell_chunk_k));
-        HIP_TRY(upload_ranges(r1, s1, &p->d_sell_chunk));
+        HIP_TRY(p->d_sell_tiles_1.alloc(s1.size()));
+        HIP_TRY(hipMemcpy(p->d_sell_tiles_1.get(), s1.data(), s1.size() * sizeof(SellTile), hipMemcpyHostToDevice));
+        HIP_TRY(p->d_sell_tiles_k.alloc(sk.size()));
+        HIP_TRY(hipMemcpy(p->d_sell_tiles_k.get(), sk.data(), sk.size() * sizeof(SellTile), hipMemcpyHostToDevice));
+        HIP_TRY(upload_ranges(rk, sk, p->d_sell_chunk_k));
+        HIP_TRY(upload_ranges(r1, s1, p->d_sell_chunk));
         p->h_cum1 = c1; p->h_cumk = ck;
         p->grid_sell_k = (int)gk;
         p->grid_sell = (int)g1;
@@ -378,7 +376,7 @@ static int problem_build_sell(mmg_problem *p, const std::vector<uint64_t> &seg_s
     }
     if (!n_hask) p->h_cum1 = cum1;
     p->resident1 = resident_raw(false); p->residentk = resident_raw(true);
-    if (!n_hask) HIP_TRY(upload_ranges(chunk, st, &p->d_sell_chunk)); // (with SELL_HASK tiles: uploaded above, over the list without them)
+    if (!n_hask) HIP_TRY(upload_ranges(chunk, st, p->d_sell_chunk)); // (with SELL_HASK tiles: uploaded above, over the list without them)
     { // chains in pairs (k_sample_sell_multi): the register-path tiles without multiplicities in their own ranges, the rest apart
         std::vector<SellTile> sf, sx;
         std::vector<uint64_t> cf(1, 0), cx(1, 0);
@@ -391,11 +389,11 @@ static int problem_build_sell(mmg_problem *p, const std::vector<uint64_t> &seg_s
         }
         p->n_x_tiles = sx.size();
         if (!sf.empty()) {
-            if (sf.size() == nt) p->d_sell_tiles_f = p->d_sell_tiles;           // every tile: the list that exists
+            if (sf.size() == nt) p->d_sell_tiles_f = p->d_sell_tiles.get();           // every tile: the list that exists
             else {
-                HIP_TRY(hipMalloc((void **)&p->d_sell_tiles_f, sf.size() * sizeof(SellTile)));
-                HIP_TRY(hipMemcpy(p->d_sell_tiles_f, sf.data(), sf.size() * sizeof(SellTile), hipMemcpyHostToDevice));
-                p->owns_tiles_f = true;
+                HIP_TRY(p->sell_tiles_f.alloc(sf.size()));
+                HIP_TRY(hipMemcpy(p->sell_tiles_f.get(), sf.data(), sf.size() * sizeof(SellTile), hipMemcpyHostToDevice));
+                p->d_sell_tiles_f = p->sell_tiles_f.get();
                 p->device_bytes += sf.size() * sizeof(SellTile);
             }
             const uint64_t nf = sf.size();
@@ -408,31 +406,31 @@ static int problem_build_sell(mmg_problem *p, const std::vector<uint64_t> &seg_s
                 const uint64_t gen = opt(MMG_OPT_SELL_WAVES_PER_CU) >= 1 ? rq : std::min<uint64_t>(nf, rq * std::min<uint64_t>(16, std::max<uint64_t>(1, (nf + rq * (SELL_TILES_PER_RANGE / 2)) / (rq * SELL_TILES_PER_RANGE))));
                 std::vector<uint64_t> cq;
                 weighted_chunks_tapered(cf, gen, opt(MMG_OPT_SELL_WAVES_PER_CU) >= 1 ? 0 : rq, cq);
-                HIP_TRY(upload_ranges(cq, sf, &p->d_sell_chunk_m[q]));
+                HIP_TRY(upload_ranges(cq, sf, p->d_sell_chunk_m[q]));
                 p->grid_sell_m[q] = (int)(cq.size() - 1);
             }
         }
         if (!sx.empty()) {
-            HIP_TRY(hipMalloc((void **)&p->d_sell_tiles_x, sx.size() * sizeof(SellTile)));
-            HIP_TRY(hipMemcpy(p->d_sell_tiles_x, sx.data(), sx.size() * sizeof(SellTile), hipMemcpyHostToDevice));
+            HIP_TRY(p->d_sell_tiles_x.alloc(sx.size()));
+            HIP_TRY(hipMemcpy(p->d_sell_tiles_x.get(), sx.data(), sx.size() * sizeof(SellTile), hipMemcpyHostToDevice));
             std::vector<uint64_t> rx;
             weighted_chunks(cx, std::max<uint64_t>(1, std::min<uint64_t>(sx.size(), resident_grid(false))), rx);
-            HIP_TRY(upload_ranges(rx, sx, &p->d_sell_chunk_x));
+            HIP_TRY(upload_ranges(rx, sx, p->d_sell_chunk_x));
             p->grid_sell_x = (int)(rx.size() - 1);
             p->device_bytes += sx.size() * sizeof(SellTile);
         }
     }
-    if (p->d_k) { // the rows on the conditional-binomial chain: a list of their own (bigk_kernels.h)
-        HIP_TRY(layout_bigk_rows(p->idx64, p->m, p->d_row_ptr, p->d_k, &p->d_bigk_list, &p->n_bigk, 0));
+    if (p->d_k.get()) { // the rows on the conditional-binomial chain: a list of their own (bigk_kernels.h)
+        HIP_TRY(layout_bigk_rows(p->idx64, p->m, p->d_row_ptr.get(), p->d_k.get(), p->d_bigk_list, &p->n_bigk, 0));
         if (p->n_bigk) {
             p->h_bigk_list.resize(p->n_bigk);
-            HIP_TRY(hipMemcpy(p->h_bigk_list.data(), p->d_bigk_list, p->n_bigk * sizeof(uint64_t), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(p->h_bigk_list.data(), p->d_bigk_list.get(), p->n_bigk * sizeof(uint64_t), hipMemcpyDeviceToHost));
             p->bigk_per_wave = bigk_piece(p->n_bigk, p->cu_count);
             p->grid_bigk = (int)((p->n_bigk + p->bigk_per_wave - 1) / p->bigk_per_wave);
             p->device_bytes += p->n_bigk * sizeof(uint64_t);
         }
     }
-    launch_encode_sell(p->idx64, p->d_row_ptr, p->d_col, p->d_sell_tiles, nt, p->d_sell, 0);
+    launch_encode_sell(p->idx64, p->d_row_ptr.get(), p->d_col.get(), p->d_sell_tiles.get(), nt, p->d_sell.get(), 0);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     p->device_bytes += p->sell_bytes + nt * sizeof(SellTile);
@@ -463,53 +461,48 @@ static int problem_build_csr_tiles(mmg_problem *p, const uint64_t *d_rp64)
     std::vector<uint64_t>().swap(rp);
     p->n_tiles = tile_row.size() - 1;
     if (p->n_tiles >= 0x7fffffffull) return fail(MMG_ERR_ARG, "too many tiles for one device");
-    uint64_t *d_tile_row = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_tile_row, tile_row.size() * sizeof(uint64_t)));
-    hipError_t e = hipMemcpy(d_tile_row, tile_row.data(), tile_row.size() * sizeof(uint64_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void **)&p->d_tiles, p->n_tiles * sizeof(TileDesc));
-    if (e == hipSuccess) {
-        launch_tile_desc(p->idx64, p->d_row_ptr, p->d_col, p->d_k, d_tile_row, p->n_tiles, p->d_tiles, 0);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipDeviceSynchronize();
+    {
+        DevBuf<uint64_t> d_tile_row;
+        HIP_TRY(d_tile_row.alloc(tile_row.size()));
+        HIP_TRY(hipMemcpy(d_tile_row.get(), tile_row.data(), tile_row.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+        HIP_TRY(p->d_tiles.alloc(p->n_tiles));
+        launch_tile_desc(p->idx64, p->d_row_ptr.get(), p->d_col.get(), p->d_k.get(), d_tile_row.get(), p->n_tiles, p->d_tiles.get(), 0);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipDeviceSynchronize());
     }
-    (void)hipFree(d_tile_row);
-    if (e != hipSuccess) return fail(MMG_ERR_HIP, std::string("tile descriptors: ") + hipGetErrorString(e));
     p->device_bytes += p->n_tiles * sizeof(TileDesc);
     // persistent grid: every resident workgroup walks one contiguous range of tiles
     int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k1_csr_kernel(p->idx64, p->d_k != nullptr), K1C_BS, 0) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 4; }
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k1_csr_kernel(p->idx64, p->d_k.get() != nullptr), K1C_BS, 0) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 4; }
     if (per_cu > 2048 / K1C_BS) per_cu = 2048 / K1C_BS;
     const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>(p->n_tiles, (uint64_t)p->cu_count * per_cu));
     p->grid_sample = (int)grid;
     std::vector<uint64_t> chunk(grid + 1, 0);
     for (uint64_t c = 0; c <= grid; ++c) chunk[c] = (uint64_t)(((unsigned __int128)p->n_tiles * c) / grid);
-    HIP_TRY(hipMalloc((void **)&p->d_chunk_tile, chunk.size() * sizeof(uint64_t)));
-    HIP_TRY(hipMemcpy(p->d_chunk_tile, chunk.data(), chunk.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIP_TRY(p->d_chunk_tile.alloc(chunk.size()));
+    HIP_TRY(hipMemcpy(p->d_chunk_tile.get(), chunk.data(), chunk.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
     return MMG_OK;
 }
 
 // From a device CSR in the caller's row order (d_rp64: m+1 u64, consumed; p->d_col / p->d_k set) to the finished problem.
-static int problem_build(mmg_problem *p, uint64_t *d_rp64)
+static int problem_build(mmg_problem *p, DevBuf<uint64_t> d_rp64)
 {
     hipDeviceProp_t prop;
-    hipError_t e = hipGetDeviceProperties(&prop, p->device);
-    if (e != hipSuccess) { (void)hipFree(d_rp64); return fail(MMG_ERR_HIP, "hipGetDeviceProperties"); }
+    if (hipGetDeviceProperties(&prop, p->device) != hipSuccess) return fail(MMG_ERR_HIP, "hipGetDeviceProperties");
     p->cu_count = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    uint64_t *d_key = nullptr;
-    auto bail = [&](int code) { if (d_key) (void)hipFree(d_key); if (d_rp64) (void)hipFree(d_rp64); return code; };
-#define B_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return bail(fail(MMG_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e))); } while (0)
+    DevBuf<uint64_t> d_key;
     std::vector<uint64_t> seg;
     if (p->m && p->layout == (int)MMG_LAYOUT_CANONICAL && p->d_k) {
         // a row that draws k >= 2 categoricals (mmg_types.h: draws_categoricals) is stored as k rows with k = 1: identical reads then run on the register path like any
         // other read, instead of through the multiplicity kernel (mmg_types.h)
-        B_TRY(layout_expand_rows(&p->m, &p->nnz, &d_rp64, &p->d_col, &p->d_k, 16, 0));
+        HIP_TRY(layout_expand_rows(&p->m, &p->nnz, d_rp64, p->d_col, p->d_k, 16, 0));
     }
     if (p->m) {
-        B_TRY(hipMalloc((void **)&d_key, p->m * sizeof(uint64_t)));
+        HIP_TRY(d_key.alloc(p->m));
         if (p->layout == (int)MMG_LAYOUT_CANONICAL) {
-            B_TRY(layout_canonical_sort(p->m, p->nnz, &d_rp64, &p->d_col, p->d_k ? &p->d_k : nullptr, d_key, 16, 0));
+            HIP_TRY(layout_canonical_sort(p->m, p->nnz, d_rp64, p->d_col, p->d_k, d_key.get(), 16, 0));
         } else {
-            B_TRY(layout_row_keys(p->m, d_rp64, p->d_col, p->d_k, d_key, 0));
+            HIP_TRY(layout_row_keys(p->m, d_rp64.get(), p->d_col.get(), p->d_k.get(), d_key.get(), 0));
         }
         // kept rows may be in any order: band-aligned tiles only while the runs of equal band stay long
         // (a shard cut from a canonical problem is in canonical order whatever its size: the canonical bound, not the one for rows in any order)
@@ -517,29 +510,30 @@ static int problem_build(mmg_problem *p, uint64_t *d_rp64)
         const uint64_t canon_seg = std::min<uint64_t>(p->m, 2 * ((uint64_t)p->n >> LAYOUT_BAND_SHIFT) + 4);
         const uint64_t max_seg = p->layout == (int)MMG_LAYOUT_CANONICAL ? canon_seg
                                                                           : std::max<uint64_t>(p->canonical_rows ? canon_seg : 0, std::max<uint64_t>(1024, p->m / 32));
-        B_TRY(layout_segments(p->m, d_key, max_seg, seg, 0));
-        B_TRY(layout_max_row_len(p->m, d_rp64, &p->max_row_len, 0));
+        HIP_TRY(layout_segments(p->m, d_key.get(), max_seg, seg, 0));
+        HIP_TRY(layout_max_row_len(p->m, d_rp64.get(), &p->max_row_len, 0));
     }
     p->idx64 = p->nnz >= 0xffffffffull || opt(MMG_OPT_FORCE_IDX64) == 1;
+    const uint64_t *rp64 = d_rp64.get();                // (the CSR-tile build below reads the 64-bit offsets either way)
     if (p->idx64) {
-        p->d_row_ptr = d_rp64;
+        p->d_row_ptr = std::move(d_rp64);
         p->device_bytes += (p->m + 1) * 8;
     } else {
-        B_TRY(hipMalloc(&p->d_row_ptr, (p->m + 1) * sizeof(uint32_t)));
-        B_TRY(layout_narrow_row_ptr(p->m, d_rp64, (uint32_t *)p->d_row_ptr, 0));
-        B_TRY(hipDeviceSynchronize());
+        DevBuf<uint32_t> rp32;
+        HIP_TRY(rp32.alloc(p->m + 1));
+        HIP_TRY(layout_narrow_row_ptr(p->m, rp64, rp32.get(), 0));
+        HIP_TRY(hipDeviceSynchronize());
+        p->d_row_ptr = std::move(rp32);
         p->device_bytes += (p->m + 1) * 4;
     }
-#undef B_TRY
-    int rc = problem_build_sell(p, seg, d_key);
-    if (d_key) { (void)hipFree(d_key); d_key = nullptr; }
-    if (rc == MMG_OK && !p->use_sell) { p->cnt_replicas = 1; rc = problem_build_csr_tiles(p, d_rp64); }
+    int rc = problem_build_sell(p, seg, d_key.get());
+    d_key.reset();
+    if (rc == MMG_OK && !p->use_sell) { p->cnt_replicas = 1; rc = problem_build_csr_tiles(p, rp64); }
     if (opt(MMG_OPT_CNT_REPLICAS) >= 1) p->cnt_replicas = opt(MMG_OPT_CNT_REPLICAS) > 1 ? CNT_REPLICAS : 1u;
-    if (!p->idx64) (void)hipFree(d_rp64);
     return rc;
 }
 
-static int problem_create_checked(const mmg_problem_desc *d, int device, const uint64_t *tx_order, mmg_problem **out);
+static int problem_create_checked(const mmg_problem_desc *d, int device, const uint64_t *tx_order, ProblemPtr &out);
 
 // what a sweep over the problem costs in the units of the tile ranges (2 per register-path tile; the CSR-tile kernel 2.8 per 64 hits)
 static uint64_t modelled_sweep_cost(const mmg_problem *p) { return p->use_sell && !p->h_sell_cum.empty() ? p->h_sell_cum.back() : p->nnz * 7 / 160; }
@@ -564,15 +558,15 @@ extern "C" int mmg_problem_create(const mmg_problem_desc *d, int device, mmg_pro
         if (!(d->l[t] > 0.0)) return fail(MMG_ERR_ARG, "l[t] must be > 0 (src/mmseq.cpp:604)");
     int rc = require_device(device);
     if (rc) return rc;
-    mmg_problem *p = nullptr;
-    rc = problem_create_checked(d, device, d->tx_order, &p);
+    ProblemPtr p;
+    rc = problem_create_checked(d, device, d->tx_order, p);
     if (rc) return rc;
     // No transcript order from the caller, and in the caller's numbering the rows do not fit LDS windows (first-seen numbering,
     // src/mmseq.cpp:399-408: more than a quarter above what register-path tiles alone would cost): derive an order from the hit
     // graph (order.hip) and keep the problem built on it if the model prices it at least a fifth lower.
     if (!d->tx_order && d->layout == MMG_LAYOUT_CANONICAL && p->m > 0 && d->n > 1 && opt(MMG_OPT_DERIVE_ORDER) != 0) {
         const uint64_t floor_cost = SELL_FAST_TILE_COST * (p->use_sell ? p->n_sell_tiles : (p->m + 63) / 64);
-        if (modelled_sweep_cost(p) > floor_cost + floor_cost / 4 || opt(MMG_OPT_DERIVE_ORDER) == 1) {
+        if (modelled_sweep_cost(p.get()) > floor_cost + floor_cost / 4 || opt(MMG_OPT_DERIVE_ORDER) == 1) {
             // The attempt must never cost the caller the problem it already has: p is valid.  The second build needs p's device memory
             // and its build's temporaries once more, plus the edge keys and their sort (16 bytes per sampled hit twice over, at most
             // 4 GB); without that much free, and on any failure below, p stays.
@@ -583,15 +577,15 @@ extern "C" int mmg_problem_create(const mmg_problem_desc *d, int device, mmg_pro
             const bool forced = opt(MMG_OPT_DERIVE_ORDER) == 1;
             if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < need) {
                 (void)hipGetLastError();
-                if (forced) { problem_free(p); return fail(MMG_ERR_HIP, "transcript order from the hit graph: needs " + std::to_string(need >> 20) + " MiB of free device memory, " + std::to_string(free_b >> 20) + " MiB are free"); }
+                if (forced) return fail(MMG_ERR_HIP, "transcript order from the hit graph: needs " + std::to_string(need >> 20) + " MiB of free device memory, " + std::to_string(free_b >> 20) + " MiB are free");
                 p->order_skipped = true;
-                *out = p;
+                *out = p.release();
                 return MMG_OK;
             }
             std::vector<uint64_t> edges;
-            hipError_t e = order_cooccurrence_edges(p->idx64, p->m, p->nnz, p->d_row_ptr, p->d_col, edges, 0); // (no tx_order: device ids are the caller's)
+            hipError_t e = order_cooccurrence_edges(p->idx64, p->m, p->nnz, p->d_row_ptr.get(), p->d_col.get(), edges, 0); // (no tx_order: device ids are the caller's)
             if (e != hipSuccess) {
-                if (forced) { problem_free(p); return fail(MMG_ERR_HIP, std::string("transcript order from the hit graph: ") + hipGetErrorString(e)); }
+                if (forced) return fail(MMG_ERR_HIP, std::string("transcript order from the hit graph: ") + hipGetErrorString(e));
                 (void)hipGetLastError(); edges.clear(); p->order_skipped = true;
             }
             // (a graph in which the average transcript shares rows with more than 1024 others has no band to find: hits drawn all over
@@ -601,12 +595,11 @@ extern "C" int mmg_problem_create(const mmg_problem_desc *d, int device, mmg_pro
                 order_from_edges(d->n, edges, pos);
                 std::vector<uint64_t>().swap(edges);
                 std::vector<uint64_t> keys(pos.begin(), pos.end());
-                mmg_problem *q = nullptr;
-                rc = problem_create_checked(d, device, keys.data(), &q);
-                if (rc && forced) { problem_free(p); return rc; }
-                if (rc) { (void)hipGetLastError(); q = nullptr; rc = MMG_OK; p->order_skipped = true; } // (problem_create_checked frees what it built)
-                if (q && modelled_sweep_cost(q) < modelled_sweep_cost(p) - modelled_sweep_cost(p) / 5) { problem_free(p); p = q; p->order_derived = true; }
-                else if (q) problem_free(q);
+                ProblemPtr q;
+                rc = problem_create_checked(d, device, keys.data(), q);
+                if (rc && forced) return rc;
+                if (rc) { (void)hipGetLastError(); rc = MMG_OK; p->order_skipped = true; } // (problem_create_checked frees what it built)
+                if (q && modelled_sweep_cost(q.get()) < modelled_sweep_cost(p.get()) - modelled_sweep_cost(p.get()) / 5) { p = std::move(q); p->order_derived = true; }
             }
         }
     }
@@ -616,7 +609,7 @@ extern "C" int mmg_problem_create(const mmg_problem_desc *d, int device, mmg_pro
     // together in the caller's order; groups that share no row with another keep their relative order behind the linked ones.
     if (d->tx_order && d->layout == MMG_LAYOUT_CANONICAL && p->m > 0 && d->n > 2 && opt(MMG_OPT_DERIVE_ORDER) != 0) {
         const uint64_t floor_cost = SELL_FAST_TILE_COST * (p->use_sell ? p->n_sell_tiles : (p->m + 63) / 64);
-        if (modelled_sweep_cost(p) > floor_cost + floor_cost / 4 || opt(MMG_OPT_DERIVE_ORDER) == 1) {
+        if (modelled_sweep_cost(p.get()) > floor_cost + floor_cost / 4 || opt(MMG_OPT_DERIVE_ORDER) == 1) {
             std::vector<uint32_t> gkeys(d->n);
             for (uint32_t t = 0; t < d->n; ++t) gkeys[t] = (uint32_t)(d->tx_order[t] >> 32);
             std::vector<uint32_t> uniq(gkeys);
@@ -629,21 +622,21 @@ extern "C" int mmg_problem_create(const mmg_problem_desc *d, int device, mmg_pro
             const bool have_mem = hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b >= need;
             if (nG > 1 && nG < d->n && !have_mem) {
                 (void)hipGetLastError();
-                if (forced) { problem_free(p); return fail(MMG_ERR_HIP, "group order from the hit graph: needs " + std::to_string(need >> 20) + " MiB of free device memory, " + std::to_string(free_b >> 20) + " MiB are free"); }
+                if (forced) return fail(MMG_ERR_HIP, "group order from the hit graph: needs " + std::to_string(need >> 20) + " MiB of free device memory, " + std::to_string(free_b >> 20) + " MiB are free");
                 p->order_skipped = true;
             }
             if (nG > 1 && nG < d->n && have_mem) {
                 std::vector<uint32_t> group_of_ext(d->n), label(d->n);
                 for (uint32_t t = 0; t < d->n; ++t) group_of_ext[t] = (uint32_t)(std::lower_bound(uniq.begin(), uniq.end(), gkeys[t]) - uniq.begin());
                 for (uint32_t i = 0; i < d->n; ++i) label[i] = group_of_ext[p->h_ext_of_int[i]];   // device column id -> group
-                uint32_t *d_label = nullptr;
+                DevBuf<uint32_t> d_label;
                 std::vector<uint64_t> edges;
-                hipError_t e = hipMalloc((void **)&d_label, (size_t)d->n * 4);
-                if (e == hipSuccess) e = hipMemcpy(d_label, label.data(), (size_t)d->n * 4, hipMemcpyHostToDevice);
-                if (e == hipSuccess) e = order_cooccurrence_edges(p->idx64, p->m, p->nnz, p->d_row_ptr, p->d_col, edges, 0, d_label);
-                if (d_label) (void)hipFree(d_label);
+                hipError_t e = d_label.alloc(d->n);
+                if (e == hipSuccess) e = hipMemcpy(d_label.get(), label.data(), (size_t)d->n * 4, hipMemcpyHostToDevice);
+                if (e == hipSuccess) e = order_cooccurrence_edges(p->idx64, p->m, p->nnz, p->d_row_ptr.get(), p->d_col.get(), edges, 0, d_label.get());
+                d_label.reset();
                 if (e != hipSuccess) {
-                    if (forced) { problem_free(p); return fail(MMG_ERR_HIP, std::string("group order from the hit graph: ") + hipGetErrorString(e)); }
+                    if (forced) return fail(MMG_ERR_HIP, std::string("group order from the hit graph: ") + hipGetErrorString(e));
                     (void)hipGetLastError(); edges.clear(); p->order_skipped = true;
                 }
                 if (!edges.empty() && edges.size() <= (uint64_t)nG * 1024) {
@@ -652,26 +645,24 @@ extern "C" int mmg_problem_create(const mmg_problem_desc *d, int device, mmg_pro
                     std::vector<uint64_t>().swap(edges);
                     std::vector<uint64_t> keys(d->n);
                     for (uint32_t t = 0; t < d->n; ++t) keys[t] = ((uint64_t)posg[group_of_ext[t]] << 32) | p->h_int_of_ext[t];
-                    mmg_problem *q = nullptr;
-                    rc = problem_create_checked(d, device, keys.data(), &q);
-                    if (rc && forced) { problem_free(p); return rc; }
-                    if (rc) { (void)hipGetLastError(); q = nullptr; rc = MMG_OK; p->order_skipped = true; }
-                    if (q && modelled_sweep_cost(q) < modelled_sweep_cost(p) - modelled_sweep_cost(p) / 5) { problem_free(p); p = q; p->groups_reordered = true; }
-                    else if (q) problem_free(q);
+                    ProblemPtr q;
+                    rc = problem_create_checked(d, device, keys.data(), q);
+                    if (rc && forced) return rc;
+                    if (rc) { (void)hipGetLastError(); rc = MMG_OK; p->order_skipped = true; }
+                    if (q && modelled_sweep_cost(q.get()) < modelled_sweep_cost(p.get()) - modelled_sweep_cost(p.get()) / 5) { p = std::move(q); p->groups_reordered = true; }
                 }
             }
         }
     }
-    *out = p;
+    *out = p.release();
     return MMG_OK;
 }
 
 // the upload and build behind mmg_problem_create, arguments checked; tx_order: the caller's, a derived one, or NULL
-static int problem_create_checked(const mmg_problem_desc *d, int device, const uint64_t *tx_order, mmg_problem **out)
+static int problem_create_checked(const mmg_problem_desc *d, int device, const uint64_t *tx_order, ProblemPtr &out)
 {
     const uint64_t nnz = d->row_ptr[d->m];
-    int rc = MMG_OK;
-    mmg_problem *p = new mmg_problem();
+    ProblemPtr p(new mmg_problem());
     p->device = device;
     p->m = d->m; p->n = d->n; p->nnz = nnz; p->row_id_base = d->row_id_base; p->layout = (int)d->layout;
     p->h_l.assign(d->l, d->l + d->n);
@@ -680,9 +671,6 @@ static int problem_create_checked(const mmg_problem_desc *d, int device, const u
         p->total_k += kr;
         if (d->row_ptr[r + 1] > d->row_ptr[r]) p->total_k_hit += kr;
     }
-    uint64_t *d_rp64 = nullptr;
-    auto bail = [&](int code) { if (d_rp64) (void)hipFree(d_rp64); problem_free(p); return code; };
-#define C_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return bail(fail(MMG_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e))); } while (0)
     // transcript renumbering: device id = rank of (tx_order[t], t).  The hits are renumbered on the device; the canonical layout then
     // sorts every row's hits (layout.hip), kept rows keep the order they came in (a stored far row: window hits first).
     const uint32_t *col_src = d->col_idx;
@@ -698,34 +686,32 @@ static int problem_create_checked(const mmg_problem_desc *d, int device, const u
         l_int.resize(d->n);
         for (uint32_t i = 0; i < d->n; ++i) l_int[i] = d->l[order[i]];
         l_src = l_int.data();
-        C_TRY(hipMalloc((void **)&p->d_int_of_ext, d->n * 4));
-        C_TRY(hipMalloc((void **)&p->d_ext_of_int, d->n * 4));
-        C_TRY(hipMemcpy(p->d_int_of_ext, p->h_int_of_ext.data(), d->n * 4, hipMemcpyHostToDevice));
-        C_TRY(hipMemcpy(p->d_ext_of_int, p->h_ext_of_int.data(), d->n * 4, hipMemcpyHostToDevice));
+        HIP_TRY(p->d_int_of_ext.alloc(d->n));
+        HIP_TRY(p->d_ext_of_int.alloc(d->n));
+        HIP_TRY(hipMemcpy(p->d_int_of_ext.get(), p->h_int_of_ext.data(), d->n * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(p->d_ext_of_int.get(), p->h_ext_of_int.data(), d->n * 4, hipMemcpyHostToDevice));
         p->device_bytes += d->n * 8;
     }
     const size_t col_bytes = (nnz + 16) * sizeof(uint32_t); // padded: vector loads may over-read
-    C_TRY(hipMalloc((void **)&p->d_col, col_bytes));
-    C_TRY(hipMemset(p->d_col, 0, col_bytes));
-    if (nnz) C_TRY(hipMemcpy(p->d_col, col_src, nnz * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (nnz && p->d_int_of_ext) C_TRY(layout_map_cols(nnz, p->d_col, p->d_int_of_ext, 0));
+    HIP_TRY(p->d_col.alloc(nnz + 16));
+    HIP_TRY(hipMemset(p->d_col.get(), 0, col_bytes));
+    if (nnz) HIP_TRY(hipMemcpy(p->d_col.get(), col_src, nnz * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (nnz && p->d_int_of_ext.get()) HIP_TRY(layout_map_cols(nnz, p->d_col.get(), p->d_int_of_ext.get(), 0));
     p->device_bytes += col_bytes;
     if (d->k && d->m) {
-        C_TRY(hipMalloc((void **)&p->d_k, d->m * sizeof(uint32_t)));
-        C_TRY(hipMemcpy(p->d_k, d->k, d->m * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIP_TRY(p->d_k.alloc(d->m));
+        HIP_TRY(hipMemcpy(p->d_k.get(), d->k, d->m * sizeof(uint32_t), hipMemcpyHostToDevice));
         p->device_bytes += d->m * 4;
     }
-    C_TRY(hipMalloc((void **)&p->d_l, d->n * sizeof(double)));
-    C_TRY(hipMemcpy(p->d_l, l_src, d->n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(p->d_l.alloc(d->n));
+    HIP_TRY(hipMemcpy(p->d_l.get(), l_src, d->n * sizeof(double), hipMemcpyHostToDevice));
     p->device_bytes += d->n * 8;
-    C_TRY(hipMalloc((void **)&d_rp64, (d->m + 1) * sizeof(uint64_t)));
-    C_TRY(hipMemcpy(d_rp64, d->row_ptr, (d->m + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
-#undef C_TRY
-    uint64_t *rp = d_rp64;
-    d_rp64 = nullptr; // consumed by problem_build
-    rc = problem_build(p, rp);
-    if (rc) return bail(rc);
-    *out = p;
+    DevBuf<uint64_t> d_rp64;
+    HIP_TRY(d_rp64.alloc(d->m + 1));
+    HIP_TRY(hipMemcpy(d_rp64.get(), d->row_ptr, (d->m + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+    const int rc = problem_build(p.get(), std::move(d_rp64));
+    if (rc) return rc;
+    out = std::move(p);
     return MMG_OK;
 }
 
@@ -738,83 +724,70 @@ extern "C" int mmg_problem_shard(const mmg_problem *full, uint64_t lo, uint64_t 
     if (lo > hi || hi > full->m) return fail(MMG_ERR_ARG, "row range out of bounds");
     int rc = require_device(device);
     if (rc) return rc;
-    mmg_problem *p = new mmg_problem();
+    ProblemPtr p(new mmg_problem());
     p->device = device;
     p->m = hi - lo; p->n = full->n; p->row_id_base = full->row_id_base + lo; p->layout = (int)MMG_LAYOUT_KEEP_ROWS;
     p->h_l = full->h_l;
     p->h_int_of_ext = full->h_int_of_ext; p->h_ext_of_int = full->h_ext_of_int;
     p->canonical_rows = full->canonical_rows; p->order_derived = full->order_derived;
-    uint64_t *src_rp = nullptr, *d_rp64 = nullptr;
-    auto bail = [&](int code) {
-        if (src_rp) { (void)hipSetDevice(full->device); (void)hipFree(src_rp); }
-        if (d_rp64) { (void)hipSetDevice(device); (void)hipFree(d_rp64); }
-        problem_free(p);
-        return code;
-    };
-#define SH_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return bail(fail(MMG_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e))); } while (0)
+    DevBuf<uint64_t> src_rp, d_rp64;                    // (on the parent's device and on `device`: each is freed on its own)
     // the shard's row offsets, rebased on the parent's device
-    SH_TRY(hipSetDevice(full->device));
-    SH_TRY(hipMalloc((void **)&src_rp, (p->m + 1) * sizeof(uint64_t)));
-    SH_TRY(layout_rebase_row_ptr(full->idx64, full->d_row_ptr, lo, p->m, src_rp, 0));
+    HIP_TRY(hipSetDevice(full->device));
+    HIP_TRY(src_rp.alloc(p->m + 1));
+    HIP_TRY(layout_rebase_row_ptr(full->idx64, full->d_row_ptr.get(), lo, p->m, src_rp.get(), 0));
     uint64_t nz0 = 0, nz1 = 0;
     if (full->idx64) {
-        SH_TRY(hipMemcpy(&nz0, (const uint64_t *)full->d_row_ptr + lo, 8, hipMemcpyDeviceToHost));
-        SH_TRY(hipMemcpy(&nz1, (const uint64_t *)full->d_row_ptr + hi, 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&nz0, (const uint64_t *)full->d_row_ptr.get() + lo, 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&nz1, (const uint64_t *)full->d_row_ptr.get() + hi, 8, hipMemcpyDeviceToHost));
     } else {
         uint32_t a = 0, b = 0;
-        SH_TRY(hipMemcpy(&a, (const uint32_t *)full->d_row_ptr + lo, 4, hipMemcpyDeviceToHost));
-        SH_TRY(hipMemcpy(&b, (const uint32_t *)full->d_row_ptr + hi, 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&a, (const uint32_t *)full->d_row_ptr.get() + lo, 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&b, (const uint32_t *)full->d_row_ptr.get() + hi, 4, hipMemcpyDeviceToHost));
         nz0 = a; nz1 = b;
     }
     p->nnz = nz1 - nz0;
-    SH_TRY(hipSetDevice(device));
-    SH_TRY(hipMalloc((void **)&d_rp64, (p->m + 1) * sizeof(uint64_t)));
-    SH_TRY(hipMemcpyPeer(d_rp64, device, src_rp, full->device, (p->m + 1) * sizeof(uint64_t)));
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(d_rp64.alloc(p->m + 1));
+    HIP_TRY(hipMemcpyPeer(d_rp64.get(), device, src_rp.get(), full->device, (p->m + 1) * sizeof(uint64_t)));
     const size_t col_bytes = (p->nnz + 16) * sizeof(uint32_t);
-    SH_TRY(hipMalloc((void **)&p->d_col, col_bytes));
-    SH_TRY(hipMemset(p->d_col, 0, col_bytes));
-    if (p->nnz) SH_TRY(hipMemcpyPeer(p->d_col, device, full->d_col + nz0, full->device, p->nnz * sizeof(uint32_t)));
+    HIP_TRY(p->d_col.alloc(p->nnz + 16));
+    HIP_TRY(hipMemset(p->d_col.get(), 0, col_bytes));
+    if (p->nnz) HIP_TRY(hipMemcpyPeer(p->d_col.get(), device, full->d_col.get() + nz0, full->device, p->nnz * sizeof(uint32_t)));
     p->device_bytes += col_bytes;
-    if (full->d_k && p->m) {
-        SH_TRY(hipMalloc((void **)&p->d_k, p->m * sizeof(uint32_t)));
-        SH_TRY(hipMemcpyPeer(p->d_k, device, full->d_k + lo, full->device, p->m * sizeof(uint32_t)));
+    if (full->d_k.get() && p->m) {
+        HIP_TRY(p->d_k.alloc(p->m));
+        HIP_TRY(hipMemcpyPeer(p->d_k.get(), device, full->d_k.get() + lo, full->device, p->m * sizeof(uint32_t)));
         p->device_bytes += p->m * 4;
         std::vector<uint32_t> hk(p->m); // total_k of the shard (one pass over its multiplicities)
-        SH_TRY(hipMemcpy(hk.data(), p->d_k, p->m * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(hk.data(), p->d_k.get(), p->m * sizeof(uint32_t), hipMemcpyDeviceToHost));
         for (uint32_t v : hk) p->total_k += v;
         std::vector<uint64_t> hrp(p->m + 1); // ... and of its rows with a hit (the wire check of a group compares a sweep's counts with them)
-        SH_TRY(hipMemcpy(hrp.data(), d_rp64, (p->m + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(hrp.data(), d_rp64.get(), (p->m + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
         for (uint64_t r = 0; r < p->m; ++r) if (hrp[r + 1] > hrp[r]) p->total_k_hit += hk[r];
     } else {
         p->total_k = p->m;
         std::vector<uint64_t> hrp(p->m + 1);
-        if (p->m) SH_TRY(hipMemcpy(hrp.data(), d_rp64, (p->m + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        if (p->m) HIP_TRY(hipMemcpy(hrp.data(), d_rp64.get(), (p->m + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
         for (uint64_t r = 0; r < p->m; ++r) p->total_k_hit += hrp[r + 1] > hrp[r];
     }
-    SH_TRY(hipMalloc((void **)&p->d_l, p->n * sizeof(double)));
+    HIP_TRY(p->d_l.alloc(p->n));
     {
         std::vector<double> l_int;
-        to_int(p, p->h_l.data(), l_int);
-        SH_TRY(hipMemcpy(p->d_l, l_int.data(), p->n * sizeof(double), hipMemcpyHostToDevice));
+        to_int(p.get(), p->h_l.data(), l_int);
+        HIP_TRY(hipMemcpy(p->d_l.get(), l_int.data(), p->n * sizeof(double), hipMemcpyHostToDevice));
     }
     p->device_bytes += p->n * 8;
     if (p->renumbered()) {
-        SH_TRY(hipMalloc((void **)&p->d_int_of_ext, p->n * 4));
-        SH_TRY(hipMalloc((void **)&p->d_ext_of_int, p->n * 4));
-        SH_TRY(hipMemcpy(p->d_int_of_ext, p->h_int_of_ext.data(), p->n * 4, hipMemcpyHostToDevice));
-        SH_TRY(hipMemcpy(p->d_ext_of_int, p->h_ext_of_int.data(), p->n * 4, hipMemcpyHostToDevice));
+        HIP_TRY(p->d_int_of_ext.alloc(p->n));
+        HIP_TRY(p->d_ext_of_int.alloc(p->n));
+        HIP_TRY(hipMemcpy(p->d_int_of_ext.get(), p->h_int_of_ext.data(), p->n * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(p->d_ext_of_int.get(), p->h_ext_of_int.data(), p->n * 4, hipMemcpyHostToDevice));
         p->device_bytes += p->n * 8;
     }
-    SH_TRY(hipSetDevice(full->device));
-    SH_TRY(hipFree(src_rp));
-    src_rp = nullptr;
-    SH_TRY(hipSetDevice(device));
-#undef SH_TRY
-    uint64_t *rp = d_rp64;
-    d_rp64 = nullptr; // consumed by problem_build
-    rc = problem_build(p, rp);
-    if (rc) return bail(rc);
-    *out = p;
+    src_rp.reset();
+    rc = problem_build(p.get(), std::move(d_rp64));
+    if (rc) return rc;
+    *out = p.release();
     return MMG_OK;
 }
 
@@ -845,10 +818,10 @@ extern "C" int mmg_problem_shard_bounds(const mmg_problem *p, int parts, uint64_
     }
     HIP_TRY(hipSetDevice(p->device));
     std::vector<uint64_t> rp(p->m + 1);
-    if (p->idx64) HIP_TRY(hipMemcpy(rp.data(), p->d_row_ptr, (p->m + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (p->idx64) HIP_TRY(hipMemcpy(rp.data(), p->d_row_ptr.get(), (p->m + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
     else {
         std::vector<uint32_t> rp32(p->m + 1);
-        HIP_TRY(hipMemcpy(rp32.data(), p->d_row_ptr, (p->m + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(rp32.data(), p->d_row_ptr.get(), (p->m + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
         for (uint64_t i = 0; i <= p->m; ++i) rp[i] = rp32[i];
     }
     return mmg_shard_bounds(rp.data(), p->m, parts, bounds);
@@ -870,31 +843,24 @@ extern "C" int mmg_problem_shard_bounds_timed(const mmg_problem *p, const double
     const uint64_t nt = p->h_shard_cum.size() - 1;
     const bool split = p->h_cumk.size() > 1;                          // a list of multiplicity tiles with a launch of its own
     const size_t L1 = p->h_cum1.size() - 1, Lk = split ? p->h_cumk.size() - 1 : 0;
-    double *d_mu = nullptr;
-    int32_t *d_cnt = nullptr;
-    std::vector<uint64_t *> d_hdr;                                    // range headers of the round's launches
-    std::vector<hipEvent_t> ev;
-    auto cleanup = [&]() {
-        for (void *x : {(void *)d_mu, (void *)d_cnt}) if (x) (void)hipFree(x);
-        for (uint64_t *h : d_hdr) if (h) (void)hipFree(h);
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-        d_hdr.clear(); ev.clear(); d_mu = nullptr; d_cnt = nullptr;
-    };
-#define T_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { cleanup(); return fail(MMG_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); } } while (0)
+    DevBuf<double> d_mu;
+    DevBuf<int32_t> d_cnt;
+    std::vector<DevBuf<uint64_t>> d_hdr;                              // range headers of the round's launches
+    std::vector<DevEvent> ev;
     std::vector<double> mu_int;
     to_int(p, mu, mu_int);
-    T_TRY(hipMalloc((void **)&d_mu, p->n * sizeof(double)));
-    T_TRY(hipMalloc((void **)&d_cnt, (size_t)CNT_REPLICAS * p->n * sizeof(int32_t)));
-    T_TRY(hipMemcpy(d_mu, mu_int.data(), p->n * sizeof(double), hipMemcpyHostToDevice));
-    T_TRY(hipMemset(d_cnt, 0, (size_t)CNT_REPLICAS * p->n * sizeof(int32_t)));
+    HIP_TRY(d_mu.alloc(p->n));
+    HIP_TRY(d_cnt.alloc((size_t)CNT_REPLICAS * p->n));
+    HIP_TRY(hipMemcpy(d_mu.get(), mu_int.data(), p->n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(d_cnt.get(), 0, (size_t)CNT_REPLICAS * p->n * sizeof(int32_t)));
     // the tile lists as the device holds them (the range headers carry the first two descriptors of a range)
     std::vector<SellTile> t1(std::max<size_t>(L1, 1)), tk(std::max<size_t>(Lk, 1));
-    const SellTile *d_t1 = split ? p->d_sell_tiles_1 : p->d_sell_tiles;
-    T_TRY(hipMemcpy(t1.data(), d_t1, L1 * sizeof(SellTile), hipMemcpyDeviceToHost));
-    if (split) T_TRY(hipMemcpy(tk.data(), p->d_sell_tiles_k, Lk * sizeof(SellTile), hipMemcpyDeviceToHost));
+    const SellTile *d_t1 = split ? p->d_sell_tiles_1.get() : p->d_sell_tiles.get();
+    HIP_TRY(hipMemcpy(t1.data(), d_t1, L1 * sizeof(SellTile), hipMemcpyDeviceToHost));
+    if (split) HIP_TRY(hipMemcpy(tk.data(), p->d_sell_tiles_k.get(), Lk * sizeof(SellTile), hipMemcpyDeviceToHost));
     const int reps = 7;
     ev.resize((size_t)parts * reps * 2);
-    for (auto &e : ev) { e = nullptr; T_TRY(hipEventCreate(&e)); }
+    for (auto &e : ev) HIP_TRY(e.create());
     // entries [lo, hi) of a list as ranges: what problem_build_sell does for a problem of hi - lo tiles
     auto ranges_of = [&](const std::vector<uint64_t> &cum, uint64_t lo, uint64_t hi, bool klist, std::vector<uint64_t> &chunk) {
         const uint64_t n = hi - lo;
@@ -917,11 +883,11 @@ extern "C" int mmg_problem_shard_bounds_timed(const mmg_problem *p, const double
     for (uint64_t t = 0; t < nt; ++t) cost[t] = (double)(p->h_shard_cum[t + 1] - p->h_shard_cum[t]);
     std::vector<uint64_t> tb(parts + 1, 0), best_tb;
     double best_ratio = 1e300;
-    const void *rp = p->d_row_ptr;
-    const uint32_t *ci = p->d_col, *kk = p->d_k;
-    const uint8_t *ss = p->d_sell;
-    const double *mup = d_mu;
-    int32_t *cnt = d_cnt;
+    const void *rp = p->d_row_ptr.get();
+    const uint32_t *ci = p->d_col.get(), *kk = p->d_k.get();
+    const uint8_t *ss = p->d_sell.get();
+    const double *mup = d_mu.get();
+    int32_t *cnt = d_cnt.get();
     SampleArgs a;
     a.seed = 0x5eed; a.row_id_base = p->row_id_base; a.n = p->n; a.chain = 1u << 30; a.iter = 0;
     a.cnt_rep_stride = p->n; a.cnt_rep_mask = CNT_REPLICAS - 1u;     // (shards have many ranges per band: replicated count vectors)
@@ -933,7 +899,7 @@ extern "C" int mmg_problem_shard_bounds_timed(const mmg_problem *p, const double
             e = hipLaunchKernel(k1_sell_kernel(p->idx64, false, p->k1_fixed_walk), dim3(g1), dim3(64), kargs, 0, 0);
         }
         if (e == hipSuccess && gk) {
-            const SellTile *ts = p->d_sell_tiles_k;
+            const SellTile *ts = p->d_sell_tiles_k.get();
             void *kargs[] = {(void *)&rp, (void *)&ci, (void *)&kk, (void *)&ts, (void *)&hdrk, (void *)&mup, (void *)&ss, (void *)&cnt, (void *)&a};
             e = hipLaunchKernel(k1_sell_kernel(p->idx64, true), dim3(gk), dim3(64), kargs, 0, 0);
         }
@@ -945,7 +911,7 @@ extern "C" int mmg_problem_shard_bounds_timed(const mmg_problem *p, const double
         const uint64_t lo = (uint64_t)(std::lower_bound(p->h_bigk_list.begin(), p->h_bigk_list.end(), r_lo) - p->h_bigk_list.begin());
         const uint64_t hi = (uint64_t)(std::lower_bound(p->h_bigk_list.begin(), p->h_bigk_list.end(), r_hi) - p->h_bigk_list.begin());
         if (hi <= lo) return hipSuccess;
-        const uint64_t *list = p->d_bigk_list + lo;
+        const uint64_t *list = p->d_bigk_list.get() + lo;
         uint64_t n_list = hi - lo;
         uint32_t per = bigk_piece(n_list, p->cu_count);
         void *kargs[] = {(void *)&rp, (void *)&ci, (void *)&kk, (void *)&list, (void *)&n_list, (void *)&per, (void *)&mup, (void *)&cnt, (void *)&a};
@@ -967,48 +933,48 @@ extern "C" int mmg_problem_shard_bounds_timed(const mmg_problem *p, const double
             tb[parts] = nt;
         }
         // the launches of every part
-        for (uint64_t *h : d_hdr) if (h) (void)hipFree(h);
-        d_hdr.assign((size_t)parts * 2, nullptr);
+        d_hdr.clear();
+        d_hdr.resize((size_t)parts * 2);
         std::vector<unsigned> g1(parts, 0), gk(parts, 0);
         for (int i = 0; i < parts; ++i) {
             std::vector<uint64_t> chunk;
             const uint64_t lo1 = first_entry(p->h_list1_tile, L1, tb[i]), hi1 = first_entry(p->h_list1_tile, L1, tb[i + 1]);
-            if (hi1 > lo1) { ranges_of(p->h_cum1, lo1, hi1, false, chunk); T_TRY(upload_ranges(chunk, t1, &d_hdr[2 * i])); g1[i] = (unsigned)(chunk.size() - 1); }
+            if (hi1 > lo1) { ranges_of(p->h_cum1, lo1, hi1, false, chunk); HIP_TRY(upload_ranges(chunk, t1, d_hdr[2 * i])); g1[i] = (unsigned)(chunk.size() - 1); }
             if (split) {
                 const uint64_t lok = first_entry(p->h_listk_tile, Lk, tb[i]), hik = first_entry(p->h_listk_tile, Lk, tb[i + 1]);
-                if (hik > lok) { ranges_of(p->h_cumk, lok, hik, true, chunk); T_TRY(upload_ranges(chunk, tk, &d_hdr[2 * i + 1])); gk[i] = (unsigned)(chunk.size() - 1); }
+                if (hik > lok) { ranges_of(p->h_cumk, lok, hik, true, chunk); HIP_TRY(upload_ranges(chunk, tk, d_hdr[2 * i + 1])); gk[i] = (unsigned)(chunk.size() - 1); }
             }
         }
         auto launch_part = [&](int i) -> hipError_t {
-            const hipError_t e = launch_tiles(d_hdr[2 * i], g1[i], d_hdr[2 * i + 1], gk[i]);
+            const hipError_t e = launch_tiles(d_hdr[2 * i].get(), g1[i], d_hdr[2 * i + 1].get(), gk[i]);
             return e == hipSuccess ? launch_bigk(row_of_tile(tb[i]), row_of_tile(tb[i + 1])) : e;
         };
         if (round == 0) { // clocks up: the whole problem for about 50 ms
-            for (int w = 0; w < 4; ++w) for (int i = 0; i < parts; ++i) { a.iter++; T_TRY(launch_part(i)); }
-            T_TRY(hipDeviceSynchronize());
-            hipEvent_t &e0 = ev[0], &e1 = ev[1];
-            T_TRY(hipEventRecord(e0, 0));
-            for (int i = 0; i < parts; ++i) { a.iter++; T_TRY(launch_part(i)); }
-            T_TRY(hipEventRecord(e1, 0));
-            T_TRY(hipEventSynchronize(e1));
+            for (int w = 0; w < 4; ++w) for (int i = 0; i < parts; ++i) { a.iter++; HIP_TRY(launch_part(i)); }
+            HIP_TRY(hipDeviceSynchronize());
+            const hipEvent_t e0 = ev[0].get(), e1 = ev[1].get();
+            HIP_TRY(hipEventRecord(e0, 0));
+            for (int i = 0; i < parts; ++i) { a.iter++; HIP_TRY(launch_part(i)); }
+            HIP_TRY(hipEventRecord(e1, 0));
+            HIP_TRY(hipEventSynchronize(e1));
             float ms = 0.f;
-            T_TRY(hipEventElapsedTime(&ms, e0, e1));
+            HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
             const int more = ms > 0.f ? std::min(2000, (int)(50.0f / ms)) : 0;
-            for (int w = 0; w < more; ++w) for (int i = 0; i < parts; ++i) { a.iter++; T_TRY(launch_part(i)); }
+            for (int w = 0; w < more; ++w) for (int i = 0; i < parts; ++i) { a.iter++; HIP_TRY(launch_part(i)); }
         }
         for (int r = 0; r < reps; ++r)
             for (int i = 0; i < parts; ++i) {
                 a.iter++;
-                T_TRY(hipEventRecord(ev[((size_t)r * parts + i) * 2], 0));
-                T_TRY(launch_part(i));
-                T_TRY(hipEventRecord(ev[((size_t)r * parts + i) * 2 + 1], 0));
+                HIP_TRY(hipEventRecord(ev[((size_t)r * parts + i) * 2].get(), 0));
+                HIP_TRY(launch_part(i));
+                HIP_TRY(hipEventRecord(ev[((size_t)r * parts + i) * 2 + 1].get(), 0));
             }
-        T_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipDeviceSynchronize());
         std::vector<double> T(parts);
         double mean = 0.0, worst = 0.0;
         for (int i = 0; i < parts; ++i) {
             std::vector<float> v(reps);
-            for (int r = 0; r < reps; ++r) T_TRY(hipEventElapsedTime(&v[r], ev[((size_t)r * parts + i) * 2], ev[((size_t)r * parts + i) * 2 + 1]));
+            for (int r = 0; r < reps; ++r) HIP_TRY(hipEventElapsedTime(&v[r], ev[((size_t)r * parts + i) * 2].get(), ev[((size_t)r * parts + i) * 2 + 1].get()));
             std::sort(v.begin(), v.end());
             T[i] = v[reps / 2];
             mean += T[i] / parts;
@@ -1026,8 +992,6 @@ extern "C" int mmg_problem_shard_bounds_timed(const mmg_problem *p, const double
             for (uint64_t t = tb[i]; t < tb[i + 1]; ++t) cost[t] *= f;
         }
     }
-    cleanup();
-#undef T_TRY
     bounds[0] = 0;
     for (int i = 1; i < parts; ++i) {
         uint64_t r = best_tb[i] < nt ? p->h_tile_row[best_tb[i]] : p->m;
@@ -1049,53 +1013,46 @@ extern "C" int mmg_problem_create_synthetic(const mmg_synth_desc *d, int device,
     std::vector<double> efflen, cdf, len_cdf;
     host_synth_tables(d->seed, d->n, d->avg_hits - 1.0, efflen, cdf, len_cdf);
     if (!(cdf[d->n - 1] > 0.0)) return fail(MMG_ERR_ARG, "synthetic abundance table is all zero");
-    mmg_problem *p = new mmg_problem();
+    ProblemPtr p(new mmg_problem());
     p->device = device;
     p->m = d->rows; p->n = d->n; p->row_id_base = d->row0; p->total_k = d->rows; p->total_k_hit = d->rows; // (a generated row has at least one hit)
     p->layout = d->sorted ? (int)MMG_LAYOUT_CANONICAL : (int)MMG_LAYOUT_KEEP_ROWS;
     const double N = (double)(d->mapped_reads ? d->mapped_reads : d->rows);
     p->h_l.resize(d->n);
     for (uint32_t t = 0; t < d->n; ++t) p->h_l[t] = efflen[t] * N / 1000000000.0; // src/mmseq.cpp:603
-    double *d_cdf = nullptr, *d_len_cdf = nullptr;
-    uint32_t *d_lens = nullptr;
-    uint64_t *d_rp64 = nullptr;
-    auto cleanup = [&]() { for (void *x : {(void *)d_cdf, (void *)d_len_cdf, (void *)d_lens, (void *)d_rp64}) if (x) (void)hipFree(x); };
-    auto bail = [&](int code) { cleanup(); problem_free(p); return code; };
-#define SYN_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return bail(fail(MMG_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e))); } while (0)
-    SYN_TRY(hipMalloc((void **)&d_cdf, d->n * sizeof(double)));
-    SYN_TRY(hipMalloc((void **)&d_len_cdf, 99 * sizeof(double)));
-    SYN_TRY(hipMalloc((void **)&d_lens, d->rows * sizeof(uint32_t)));
-    SYN_TRY(hipMalloc((void **)&d_rp64, (d->rows + 1) * sizeof(uint64_t)));
-    SYN_TRY(hipMemcpy(d_cdf, cdf.data(), d->n * sizeof(double), hipMemcpyHostToDevice));
-    SYN_TRY(hipMemcpy(d_len_cdf, len_cdf.data(), 99 * sizeof(double), hipMemcpyHostToDevice));
-    SynthArgs sa{d->seed, d->row0, d->rows, d->n, d->uniform ? 1 : 0, d_cdf, d_len_cdf, 0, 0, 0, 1, 1};
+    DevBuf<double> d_cdf, d_len_cdf;
+    DevBuf<uint32_t> d_lens;
+    DevBuf<uint64_t> d_rp64;
+    HIP_TRY(d_cdf.alloc(d->n));
+    HIP_TRY(d_len_cdf.alloc(99));
+    HIP_TRY(d_lens.alloc(d->rows));
+    HIP_TRY(d_rp64.alloc(d->rows + 1));
+    HIP_TRY(hipMemcpy(d_cdf.get(), cdf.data(), d->n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_len_cdf.get(), len_cdf.data(), 99 * sizeof(double), hipMemcpyHostToDevice));
+    SynthArgs sa{d->seed, d->row0, d->rows, d->n, d->uniform ? 1 : 0, d_cdf.get(), d_len_cdf.get(), 0, 0, 0, 1, 1};
     if (d->gene_size) {
         sa.gene_size = d->gene_size; sa.far_family = d->far_family;
         sa.n_genes = (d->n + d->gene_size - 1) / d->gene_size;
         synth_family_params(d->seed, sa.n_genes, &sa.fam_a, &sa.fam_ainv);
     }
-    launch_synth_len(sa, d->far_fraction, d_lens, 0);
-    SYN_TRY(hipGetLastError());
-    SYN_TRY(layout_scan_lens(d->rows, d_lens, d_rp64, 0));
-    SYN_TRY(hipMemcpy(&p->nnz, d_rp64 + d->rows, sizeof(uint64_t), hipMemcpyDeviceToHost));
-    (void)hipFree(d_lens); d_lens = nullptr;
+    launch_synth_len(sa, d->far_fraction, d_lens.get(), 0);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(layout_scan_lens(d->rows, d_lens.get(), d_rp64.get(), 0));
+    HIP_TRY(hipMemcpy(&p->nnz, d_rp64.get() + d->rows, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    d_lens.reset();
     const size_t col_bytes = (p->nnz + 16) * sizeof(uint32_t);
-    SYN_TRY(hipMalloc((void **)&p->d_col, col_bytes));
-    SYN_TRY(hipMemset(p->d_col, 0, col_bytes));
+    HIP_TRY(p->d_col.alloc(p->nnz + 16));
+    HIP_TRY(hipMemset(p->d_col.get(), 0, col_bytes));
     p->device_bytes += col_bytes;
-    SYN_TRY(hipMalloc((void **)&p->d_l, d->n * sizeof(double)));
-    SYN_TRY(hipMemcpy(p->d_l, p->h_l.data(), d->n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(p->d_l.alloc(d->n));
+    HIP_TRY(hipMemcpy(p->d_l.get(), p->h_l.data(), d->n * sizeof(double), hipMemcpyHostToDevice));
     p->device_bytes += d->n * 8;
-    launch_synth_fill(sa, d->far_fraction, d_rp64, p->d_col, 0);
-    SYN_TRY(hipGetLastError());
-    SYN_TRY(hipDeviceSynchronize());
-#undef SYN_TRY
-    uint64_t *rp = d_rp64;
-    d_rp64 = nullptr; // consumed by problem_build
-    rc = problem_build(p, rp);
-    if (rc) return bail(rc);
-    cleanup();
-    *out = p;
+    launch_synth_fill(sa, d->far_fraction, d_rp64.get(), p->d_col.get(), 0);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    rc = problem_build(p.get(), std::move(d_rp64));
+    if (rc) return rc;
+    *out = p.release();
     return MMG_OK;
 }
 
@@ -1124,22 +1081,22 @@ extern "C" int mmg_problem_download(const mmg_problem *p, uint64_t *row_ptr, uin
     HIP_TRY(hipSetDevice(p->device));
     if (row_ptr) {
         if (p->idx64) {
-            HIP_TRY(hipMemcpy(row_ptr, p->d_row_ptr, (p->m + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(row_ptr, p->d_row_ptr.get(), (p->m + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
         } else {
             std::vector<uint32_t> rp32(p->m + 1);
-            HIP_TRY(hipMemcpy(rp32.data(), p->d_row_ptr, (p->m + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(rp32.data(), p->d_row_ptr.get(), (p->m + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
             for (uint64_t i = 0; i <= p->m; ++i) row_ptr[i] = rp32[i];
         }
     }
     if (col_idx && p->nnz) {
-        HIP_TRY(hipMemcpy(col_idx, p->d_col, p->nnz * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(col_idx, p->d_col.get(), p->nnz * sizeof(uint32_t), hipMemcpyDeviceToHost));
         if (p->renumbered()) {
             const std::vector<uint32_t> &map = p->h_ext_of_int;
             parallel_slices(p->nnz, [&](uint64_t a, uint64_t b) { for (uint64_t j = a; j < b; ++j) col_idx[j] = map[col_idx[j]]; });
         }
     }
     if (k && p->m) {
-        if (p->d_k) HIP_TRY(hipMemcpy(k, p->d_k, p->m * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (p->d_k.get()) HIP_TRY(hipMemcpy(k, p->d_k.get(), p->m * sizeof(uint32_t), hipMemcpyDeviceToHost));
         else for (uint64_t i = 0; i < p->m; ++i) k[i] = 1;
     }
     return MMG_OK;
@@ -1163,32 +1120,28 @@ extern "C" int mmg_problem_start_values(const mmg_problem *p, double *mu0, int32
 {
     if (!p) return fail(MMG_ERR_ARG, "NULL problem");
     HIP_TRY(hipSetDevice(p->device));
-    uint64_t *d_acc = nullptr;
-    int32_t *d_uh = nullptr;
+    DevBuf<uint64_t> d_acc;
+    DevBuf<int32_t> d_uh;
     const size_t n = p->n;
-    HIP_TRY(hipMalloc((void **)&d_acc, 3 * n * sizeof(uint64_t)));
-    if (hipMalloc((void **)&d_uh, n * sizeof(int32_t)) != hipSuccess) { (void)hipFree(d_acc); return fail(MMG_ERR_HIP, "hipMalloc"); }
-    int rc = MMG_OK;
-    do {
-        if (hipMemset(d_acc, 0, 3 * n * sizeof(uint64_t)) != hipSuccess || hipMemset(d_uh, 0, n * sizeof(int32_t)) != hipSuccess) { rc = fail(MMG_ERR_HIP, "hipMemset"); break; }
-        launch_start_values(p->idx64, p->d_row_ptr, p->d_col, p->d_k, p->m, p->n, d_acc, d_uh, 0);
-        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) { rc = fail(MMG_ERR_HIP, "start_values launch"); break; }
-        if (mu0) {
-            std::vector<uint64_t> acc(3 * n);
-            if (hipMemcpy(acc.data(), d_acc, 3 * n * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(MMG_ERR_HIP, "hipMemcpy mu0"); break; }
-            for (uint32_t t = 0; t < p->n; ++t) {
-                const uint32_t i = p->renumbered() ? p->h_int_of_ext[t] : t;
-                mu0[t] = host_start_value(acc[i], acc[n + i], acc[2 * n + i], p->h_l[t]);
-            }
+    HIP_TRY(d_acc.alloc(3 * n));
+    HIP_TRY(d_uh.alloc(n));
+    HIP_TRY(hipMemset(d_acc.get(), 0, 3 * n * sizeof(uint64_t)));
+    HIP_TRY(hipMemset(d_uh.get(), 0, n * sizeof(int32_t)));
+    launch_start_values(p->idx64, p->d_row_ptr.get(), p->d_col.get(), p->d_k.get(), p->m, p->n, d_acc.get(), d_uh.get(), 0);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    if (mu0) {
+        std::vector<uint64_t> acc(3 * n);
+        HIP_TRY(hipMemcpy(acc.data(), d_acc.get(), 3 * n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        for (uint32_t t = 0; t < p->n; ++t) {
+            const uint32_t i = p->renumbered() ? p->h_int_of_ext[t] : t;
+            mu0[t] = host_start_value(acc[i], acc[n + i], acc[2 * n + i], p->h_l[t]);
         }
-        if (unique_hits) rc = download_ext(p, d_uh, unique_hits);
-    } while (0);
-    (void)hipFree(d_acc);
-    (void)hipFree(d_uh);
-    return rc;
+    }
+    return unique_hits ? download_ext(p, d_uh.get(), unique_hits) : MMG_OK;
 }
 
-extern "C" void mmg_problem_destroy(mmg_problem *p) { problem_free(p); }
+extern "C" void mmg_problem_destroy(mmg_problem *p) { delete p; }
 
 // ------------------------------------------------------------------------------ host-side keyed draws, self tests
 extern "C" int mmg_host_gamma_trace(uint64_t seed, uint64_t id, double shape, double scale, int n, double *out)
@@ -1219,15 +1172,15 @@ extern "C" int mmg_selftest_math(int device, int64_t n, const double *x, double 
     if (device < 0) { host_math(n, x, ol, oe, os, orc); return MMG_OK; }
     int rc = require_device(device);
     if (rc) return rc;
-    double *d = nullptr;
-    HIP_TRY(hipMalloc((void **)&d, 5 * (size_t)n * sizeof(double) + 8));
+    DevBuf<double> buf;
+    HIP_TRY(buf.alloc(5 * (size_t)n + 1));
+    double *d = buf.get();
     hipError_t e = hipMemcpy(d, x, n * sizeof(double), hipMemcpyHostToDevice);
     if (e == hipSuccess) { launch_selftest_math(n, d, d + n, d + 2 * n, d + 3 * n, d + 4 * n, 0); e = hipDeviceSynchronize(); }
     if (e == hipSuccess) e = hipMemcpy(ol, d + n, n * sizeof(double), hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(oe, d + 2 * n, n * sizeof(double), hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(os, d + 3 * n, n * sizeof(double), hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(orc, d + 4 * n, n * sizeof(double), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
     if (e != hipSuccess) return fail(MMG_ERR_HIP, std::string("selftest_math: ") + hipGetErrorString(e));
     return MMG_OK;
 }
@@ -1238,13 +1191,13 @@ extern "C" int mmg_selftest_philox(int device, const uint32_t *ctr, const uint32
     if (device < 0) { host_philox(ctr, key, out); return MMG_OK; }
     int rc = require_device(device);
     if (rc) return rc;
-    uint32_t *d = nullptr;
-    HIP_TRY(hipMalloc((void **)&d, 12 * sizeof(uint32_t)));
+    DevBuf<uint32_t> buf;
+    HIP_TRY(buf.alloc(12));
+    uint32_t *d = buf.get();
     hipError_t e = hipMemcpy(d, ctr, 16, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d + 4, key, 8, hipMemcpyHostToDevice);
     if (e == hipSuccess) { launch_selftest_philox(d, d + 4, d + 6, 0); e = hipDeviceSynchronize(); }
     if (e == hipSuccess) e = hipMemcpy(out, d + 6, 24, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
     if (e != hipSuccess) return fail(MMG_ERR_HIP, std::string("selftest_philox: ") + hipGetErrorString(e));
     return MMG_OK;
 }
@@ -1255,12 +1208,12 @@ extern "C" int mmg_selftest_gamma(int device, uint64_t seed, double shape, doubl
     if (device < 0) { host_gamma(seed, 2 /* TAG_GAMMA */, 0, 0, shape, scale, n, out); return MMG_OK; }
     int rc = require_device(device);
     if (rc) return rc;
-    double *d = nullptr;
-    HIP_TRY(hipMalloc((void **)&d, (size_t)n * sizeof(double) + 8));
+    DevBuf<double> buf;
+    HIP_TRY(buf.alloc((size_t)n + 1));
+    double *d = buf.get();
     launch_selftest_gamma(seed, shape, scale, n, d, 0);
     hipError_t e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(out, d, n * sizeof(double), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
     if (e != hipSuccess) return fail(MMG_ERR_HIP, std::string("selftest_gamma: ") + hipGetErrorString(e));
     return MMG_OK;
 }
@@ -1271,12 +1224,12 @@ extern "C" int mmg_selftest_binomial(int device, uint64_t seed, uint32_t nn, dou
     if (device < 0) { host_binomial(seed, nn, p, n, out); return MMG_OK; }
     int rc = require_device(device);
     if (rc) return rc;
-    uint32_t *d = nullptr;
-    HIP_TRY(hipMalloc((void **)&d, (size_t)n * sizeof(uint32_t) + 8));
+    DevBuf<uint32_t> buf;
+    HIP_TRY(buf.alloc((size_t)n + 2));
+    uint32_t *d = buf.get();
     launch_selftest_binomial(seed, nn, p, n, d, 0);
     hipError_t e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(out, d, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
     if (e != hipSuccess) return fail(MMG_ERR_HIP, std::string("selftest_binomial: ") + hipGetErrorString(e));
     return MMG_OK;
 }
@@ -1286,13 +1239,13 @@ extern "C" int mmg_selftest_btrs_pretest(int device, uint64_t seed, int64_t n_ca
     if (n_cases < 0 || !counts || !(n_lo >= 21.0) || !(n_hi >= n_lo) || !(n_hi <= 4294967295.0)) return fail(MMG_ERR_ARG, "bad argument");
     int rc = require_device(device);
     if (rc) return rc;
-    unsigned long long *d = nullptr;
-    HIP_TRY(hipMalloc((void **)&d, 5 * sizeof(unsigned long long)));
+    DevBuf<unsigned long long> buf;
+    HIP_TRY(buf.alloc(5));
+    unsigned long long *d = buf.get();
     hipError_t e = hipMemset(d, 0, 5 * sizeof(unsigned long long));
     if (e == hipSuccess) { launch_selftest_btrs_pretest(seed, n_cases, n_lo, n_hi, d, 0); e = hipGetLastError(); }
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(counts, d, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
     if (e != hipSuccess) return fail(MMG_ERR_HIP, std::string("selftest_btrs_pretest: ") + hipGetErrorString(e));
     return MMG_OK;
 }
@@ -1302,13 +1255,13 @@ extern "C" int mmg_selftest_binv_pretest(int device, uint64_t seed, int64_t n_ca
     if (n_cases < 0 || !counts || !(n_lo >= 1.0) || !(n_hi >= n_lo) || !(n_hi <= 4294967295.0) || !(slack > 0.0)) return fail(MMG_ERR_ARG, "bad argument");
     int rc = require_device(device);
     if (rc) return rc;
-    unsigned long long *d = nullptr;
-    HIP_TRY(hipMalloc((void **)&d, 5 * sizeof(unsigned long long)));
+    DevBuf<unsigned long long> buf;
+    HIP_TRY(buf.alloc(5));
+    unsigned long long *d = buf.get();
     hipError_t e = hipMemset(d, 0, 5 * sizeof(unsigned long long));
     if (e == hipSuccess) { launch_selftest_binv_pretest(seed, n_cases, n_lo, n_hi, (float)slack, d, 0); e = hipGetLastError(); }
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(counts, d, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
     if (e != hipSuccess) return fail(MMG_ERR_HIP, std::string("selftest_binv_pretest: ") + hipGetErrorString(e));
     return MMG_OK;
 }

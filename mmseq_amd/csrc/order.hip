@@ -19,6 +19,7 @@
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_select.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
+#include "mmg_host.h"
 #include "mmg_launch.h"
 
 namespace mmg {
@@ -73,48 +74,40 @@ hipError_t order_cooccurrence_edges(bool idx64, uint64_t m, uint64_t nnz, const 
     if (m == 0 || nnz == 0) return hipSuccess;
     uint64_t mask = 0;
     while ((nnz >> __builtin_popcountll(mask)) > ORDER_SAMPLE_HITS) mask = (mask << 1) | 1;
-    uint32_t *d_cnt = nullptr;
-    uint64_t *d_off = nullptr, *d_keys = nullptr, *d_sorted = nullptr, *d_nuniq = nullptr;
-    void *d_tmp = nullptr;
-    auto done = [&](hipError_t rc) {
-        for (void *x : {(void *)d_cnt, (void *)d_off, (void *)d_keys, (void *)d_sorted, (void *)d_nuniq, d_tmp}) if (x) (void)hipFree(x);
-        return rc;
-    };
-    hipError_t e;
-#define O_TRY(expr) do { e = (expr); if (e != hipSuccess) return done(e); } while (0)
-    O_TRY(hipMalloc((void **)&d_cnt, m * 4));
-    O_TRY(hipMalloc((void **)&d_off, (m + 1) * 8));
+    DevBuf<uint32_t> d_cnt;
+    DevBuf<uint64_t> d_off, d_keys, d_sorted, d_nuniq;
+    DevBuf<uint8_t> d_tmp;
+    HIPE_TRY(d_cnt.alloc(m));
+    HIPE_TRY(d_off.alloc(m + 1));
     const unsigned g = (unsigned)((m + 255) / 256);
-    if (idx64) hipLaunchKernelGGL((k_order_edges<uint64_t, false>), dim3(g), dim3(256), 0, s, m, (const uint64_t *)d_rp, d_col, mask, d_label, d_cnt, (const uint64_t *)nullptr, (uint64_t *)nullptr);
-    else hipLaunchKernelGGL((k_order_edges<uint32_t, false>), dim3(g), dim3(256), 0, s, m, (const uint32_t *)d_rp, d_col, mask, d_label, d_cnt, (const uint64_t *)nullptr, (uint64_t *)nullptr);
-    O_TRY(hipGetLastError());
-    O_TRY(layout_scan_lens(m, d_cnt, d_off, s));
+    if (idx64) hipLaunchKernelGGL((k_order_edges<uint64_t, false>), dim3(g), dim3(256), 0, s, m, (const uint64_t *)d_rp, d_col, mask, d_label, d_cnt.get(), (const uint64_t *)nullptr, (uint64_t *)nullptr);
+    else hipLaunchKernelGGL((k_order_edges<uint32_t, false>), dim3(g), dim3(256), 0, s, m, (const uint32_t *)d_rp, d_col, mask, d_label, d_cnt.get(), (const uint64_t *)nullptr, (uint64_t *)nullptr);
+    HIPE_TRY(hipGetLastError());
+    HIPE_TRY(layout_scan_lens(m, d_cnt.get(), d_off.get(), s));
     uint64_t E = 0;
-    O_TRY(hipMemcpy(&E, d_off + m, 8, hipMemcpyDeviceToHost));
-    if (E == 0) return done(hipSuccess);
-    O_TRY(hipMalloc((void **)&d_keys, E * 8));
-    O_TRY(hipMalloc((void **)&d_sorted, E * 8));
-    if (idx64) hipLaunchKernelGGL((k_order_edges<uint64_t, true>), dim3(g), dim3(256), 0, s, m, (const uint64_t *)d_rp, d_col, mask, d_label, (uint32_t *)nullptr, (const uint64_t *)d_off, d_keys);
-    else hipLaunchKernelGGL((k_order_edges<uint32_t, true>), dim3(g), dim3(256), 0, s, m, (const uint32_t *)d_rp, d_col, mask, d_label, (uint32_t *)nullptr, (const uint64_t *)d_off, d_keys);
-    O_TRY(hipGetLastError());
+    HIPE_TRY(hipMemcpy(&E, d_off.get() + m, 8, hipMemcpyDeviceToHost));
+    if (E == 0) return hipSuccess;
+    HIPE_TRY(d_keys.alloc(E));
+    HIPE_TRY(d_sorted.alloc(E));
+    if (idx64) hipLaunchKernelGGL((k_order_edges<uint64_t, true>), dim3(g), dim3(256), 0, s, m, (const uint64_t *)d_rp, d_col, mask, d_label, (uint32_t *)nullptr, (const uint64_t *)d_off.get(), d_keys.get());
+    else hipLaunchKernelGGL((k_order_edges<uint32_t, true>), dim3(g), dim3(256), 0, s, m, (const uint32_t *)d_rp, d_col, mask, d_label, (uint32_t *)nullptr, (const uint64_t *)d_off.get(), d_keys.get());
+    HIPE_TRY(hipGetLastError());
     size_t tmp = 0;
-    O_TRY(rocprim::radix_sort_keys(nullptr, tmp, d_keys, d_sorted, E, 0, 64, s));
-    O_TRY(hipMalloc(&d_tmp, tmp ? tmp : 8));
-    O_TRY(rocprim::radix_sort_keys(d_tmp, tmp, d_keys, d_sorted, E, 0, 64, s));
-    O_TRY(hipStreamSynchronize(s));
-    (void)hipFree(d_tmp); d_tmp = nullptr;
-    O_TRY(hipMalloc((void **)&d_nuniq, 8));
+    HIPE_TRY(rocprim::radix_sort_keys(nullptr, tmp, d_keys.get(), d_sorted.get(), E, 0, 64, s));
+    HIPE_TRY(d_tmp.alloc(tmp ? tmp : 8));
+    HIPE_TRY(rocprim::radix_sort_keys(d_tmp.get(), tmp, d_keys.get(), d_sorted.get(), E, 0, 64, s));
+    HIPE_TRY(hipStreamSynchronize(s));
+    d_tmp.reset();
+    HIPE_TRY(d_nuniq.alloc(1));
     tmp = 0;
-    O_TRY(rocprim::unique(nullptr, tmp, d_sorted, d_keys, d_nuniq, E, rocprim::equal_to<uint64_t>(), s));
-    O_TRY(hipMalloc(&d_tmp, tmp ? tmp : 8));
-    O_TRY(rocprim::unique(d_tmp, tmp, d_sorted, d_keys, d_nuniq, E, rocprim::equal_to<uint64_t>(), s));
+    HIPE_TRY(rocprim::unique(nullptr, tmp, d_sorted.get(), d_keys.get(), d_nuniq.get(), E, rocprim::equal_to<uint64_t>(), s));
+    HIPE_TRY(d_tmp.alloc(tmp ? tmp : 8));
+    HIPE_TRY(rocprim::unique(d_tmp.get(), tmp, d_sorted.get(), d_keys.get(), d_nuniq.get(), E, rocprim::equal_to<uint64_t>(), s));
     uint64_t nu = 0;
-    O_TRY(hipMemcpyAsync(&nu, d_nuniq, 8, hipMemcpyDeviceToHost, s));
-    O_TRY(hipStreamSynchronize(s));
+    HIPE_TRY(hipMemcpyAsync(&nu, d_nuniq.get(), 8, hipMemcpyDeviceToHost, s));
+    HIPE_TRY(hipStreamSynchronize(s));
     edges.resize(nu);
-    O_TRY(hipMemcpy(edges.data(), d_keys, nu * 8, hipMemcpyDeviceToHost));
-#undef O_TRY
-    return done(hipSuccess);
+    return hipMemcpy(edges.data(), d_keys.get(), nu * 8, hipMemcpyDeviceToHost);
 }
 
 // Position of every transcript in the derived order: pos[t] for t < n (a permutation of 0..n-1).  edges: sorted unique u << 32 | v.

@@ -5,6 +5,7 @@
 #include "mmg_launch.h"
 
 #include <cmath>
+#include <memory>
 #include <mutex>
 #include <vector>
 
@@ -12,53 +13,51 @@ using namespace mmg;
 
 struct SeriesBuf {            // results of one kind of series, on the device
     uint32_t count = 0;
-    double *log_mean = nullptr, *var = nullptr, *tau = nullptr, *pct = nullptr;
-    int32_t *rc = nullptr;
+    DevBuf<double> log_mean, var, tau, pct;
+    DevBuf<int32_t> rc;
 };
 struct PropBuf {
     uint32_t count = 0;
-    double *mean = nullptr, *probit_mean = nullptr, *probit_sd = nullptr, *pct = nullptr;
+    DevBuf<double> mean, probit_mean, probit_sd, pct;
 };
 
+// Members are destroyed in reverse declaration order: the destructor waits for `st`, then the buffers go, and the stream last.
 struct mmg_summary {
+    DevStream st;                  // the summary's own stream: its kernels neither wait for nor delay the chain
     int device = 0;
     uint32_t n = 0, nv = 0, ni = 0, ng = 0, np = 0, S = 0;
     // sample-major derived traces the writers stream row by row
-    double *d_ident = nullptr;   // [S][ni]
-    double *d_gene = nullptr;    // [S][ng]
-    double *d_prop = nullptr;    // [S][n], caller's numbering
+    DevBuf<double> d_ident;      // [S][ni]
+    DevBuf<double> d_gene;       // [S][ng]
+    DevBuf<double> d_prop;       // [S][n], caller's numbering
     SeriesBuf ser[4];            // MMG_SERIES_TRANSCRIPT, _VIRTUAL, _IDENTICAL, _GENE
     PropBuf prop[2];             // MMG_SERIES_TRANSCRIPT, _VIRTUAL
     // the summary is built in steps (mmg_summary_begin / _advance / _finish): what the steps share
     const mmg_problem *p = nullptr;
     const double *trace = nullptr; // the chain's resident trace [S][n], device numbering
-    hipStream_t st = nullptr;      // the summary's own stream: its kernels neither wait for nor delay the chain
     uint32_t done = 0;             // samples whose derived rows exist
     bool finished = false;
-    std::vector<void *> scratch;   // device buffers that live until _finish
+    std::vector<DevBuf<uint8_t>> scratch; // device buffers that live until _finish (the pointers below point into them)
     uint64_t *d_iptr = nullptr, *d_gptr = nullptr;
     uint32_t *d_imem = nullptr, *d_gmem = nullptr, *d_gene_t = nullptr, *d_gene_v = nullptr;
     uint8_t *d_multi_t = nullptr, *d_multi_v = nullptr;
     int32_t *d_pind = nullptr;
     double *d_V = nullptr, *d_propV = nullptr, *d_tw = nullptr;
     // mmg_summary_get_rows: a stream and pinned buffers of its own (the writers of a caller fetch rows while the chain runs)
-    hipStream_t rows_st = nullptr;
+    DevStream rows_st;
     std::mutex rows_mu;
     PinnedStage rows_stage;
+    ~mmg_summary() { if (st) (void)hipStreamSynchronize(st.get()); }
 };
 
-static void summary_free(mmg_summary *q)
+// a device buffer of `bytes` (at least 8) kept in `list`; *ptr points into it
+static hipError_t scratch_alloc(std::vector<DevBuf<uint8_t>> &list, void **ptr, size_t bytes)
 {
-    if (!q) return;
-    (void)hipSetDevice(q->device);
-    if (q->st) (void)hipStreamSynchronize(q->st);
-    for (void *x : q->scratch) if (x) (void)hipFree(x);
-    for (void *x : {(void *)q->d_ident, (void *)q->d_gene, (void *)q->d_prop}) if (x) (void)hipFree(x);
-    for (auto &b : q->ser) for (void *x : {(void *)b.log_mean, (void *)b.var, (void *)b.tau, (void *)b.pct, (void *)b.rc}) if (x) (void)hipFree(x);
-    for (auto &b : q->prop) for (void *x : {(void *)b.mean, (void *)b.probit_mean, (void *)b.probit_sd, (void *)b.pct}) if (x) (void)hipFree(x);
-    if (q->st) (void)hipStreamDestroy(q->st);
-    if (q->rows_st) (void)hipStreamDestroy(q->rows_st);
-    delete q;
+    DevBuf<uint8_t> b;
+    HIPE_TRY(b.alloc(bytes ? bytes : 8));
+    *ptr = b.get();
+    list.push_back(std::move(b));
+    return hipSuccess;
 }
 
 static inline unsigned blocks_of(uint64_t n) { return (unsigned)((n + 255) / 256); }
@@ -138,15 +137,13 @@ extern "C" int mmg_summary_begin(mmg_sampler *smp, const mmg_summary_desc *d, mm
             if (d->identical_member[j] >= n + nv) return fail(MMG_ERR_ARG, "identical-set member out of range");
     }
     HIP_TRY(hipSetDevice(p->device));
-    mmg_summary *q = new mmg_summary();
+    std::unique_ptr<mmg_summary> q(new mmg_summary());
     q->device = p->device; q->n = n; q->nv = nv; q->ni = ni; q->ng = ng; q->np = np; q->S = S;
     q->p = p;
     q->trace = v.d_trace + (size_t)d->chain * S * n;
-    auto bail = [&](int code) { summary_free(q); return code; };
-#define Q_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return bail(fail(MMG_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e))); } while (0)
-    Q_TRY(hipStreamCreateWithFlags(&q->st, hipStreamNonBlocking));
-    hipStream_t st = q->st;
-    auto dalloc = [&](void **ptr, size_t bytes) { hipError_t e = hipMalloc(ptr, bytes ? bytes : 8); if (e == hipSuccess) q->scratch.push_back(*ptr); return e; };
+    HIP_TRY(q->st.create(hipStreamNonBlocking));
+    hipStream_t st = q->st.get();
+    auto dalloc = [&](void **ptr, size_t bytes) { return scratch_alloc(q->scratch, ptr, bytes); };
     auto upload = [&](void **dst, const void *src, size_t bytes) {
         hipError_t e = dalloc(dst, bytes);
         if (e == hipSuccess && bytes) e = hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, st);
@@ -154,29 +151,28 @@ extern "C" int mmg_summary_begin(mmg_sampler *smp, const mmg_summary_desc *d, mm
     };
     uint64_t *d_vid = nullptr;
     double *d_vscale = nullptr;
-    Q_TRY(upload((void **)&d_vid, d->virtual_id, (size_t)nv * 8));
-    Q_TRY(upload((void **)&d_vscale, d->virtual_scale, (size_t)nv * 8));
-    Q_TRY(upload((void **)&q->d_iptr, d->identical_ptr, ((size_t)ni + 1) * 8 * (ni ? 1 : 0)));
-    Q_TRY(upload((void **)&q->d_imem, d->identical_member, ni ? (size_t)d->identical_ptr[ni] * 4 : 0));
-    Q_TRY(upload((void **)&q->d_gptr, d->gene_ptr, ((size_t)ng + 1) * 8 * (ng ? 1 : 0)));
-    Q_TRY(upload((void **)&q->d_gmem, d->gene_member, ng ? (size_t)d->gene_ptr[ng] * 4 : 0));
-    Q_TRY(upload((void **)&q->d_gene_t, gene_of_t.data(), (size_t)n * 4));
-    Q_TRY(upload((void **)&q->d_gene_v, gene_of_v.data(), (size_t)nv * 4));
-    Q_TRY(upload((void **)&q->d_multi_t, multi_t.data(), (size_t)n));
-    Q_TRY(upload((void **)&q->d_multi_v, multi_v.data(), (size_t)nv));
-    Q_TRY(upload((void **)&q->d_pind, d->percentile_index, (size_t)np * 4));
+    HIP_TRY(upload((void **)&d_vid, d->virtual_id, (size_t)nv * 8));
+    HIP_TRY(upload((void **)&d_vscale, d->virtual_scale, (size_t)nv * 8));
+    HIP_TRY(upload((void **)&q->d_iptr, d->identical_ptr, ((size_t)ni + 1) * 8 * (ni ? 1 : 0)));
+    HIP_TRY(upload((void **)&q->d_imem, d->identical_member, ni ? (size_t)d->identical_ptr[ni] * 4 : 0));
+    HIP_TRY(upload((void **)&q->d_gptr, d->gene_ptr, ((size_t)ng + 1) * 8 * (ng ? 1 : 0)));
+    HIP_TRY(upload((void **)&q->d_gmem, d->gene_member, ng ? (size_t)d->gene_ptr[ng] * 4 : 0));
+    HIP_TRY(upload((void **)&q->d_gene_t, gene_of_t.data(), (size_t)n * 4));
+    HIP_TRY(upload((void **)&q->d_gene_v, gene_of_v.data(), (size_t)nv * 4));
+    HIP_TRY(upload((void **)&q->d_multi_t, multi_t.data(), (size_t)n));
+    HIP_TRY(upload((void **)&q->d_multi_v, multi_v.data(), (size_t)nv));
+    HIP_TRY(upload((void **)&q->d_pind, d->percentile_index, (size_t)np * 4));
     const std::vector<double> tw = twiddles(S);
-    Q_TRY(upload((void **)&q->d_tw, tw.data(), tw.size() * 8));
-    Q_TRY(dalloc((void **)&q->d_V, (size_t)S * nv * 8));
-    Q_TRY(dalloc((void **)&q->d_propV, (size_t)S * nv * 8));
+    HIP_TRY(upload((void **)&q->d_tw, tw.data(), tw.size() * 8));
+    HIP_TRY(dalloc((void **)&q->d_V, (size_t)S * nv * 8));
+    HIP_TRY(dalloc((void **)&q->d_propV, (size_t)S * nv * 8));
     if (nv) hipLaunchKernelGGL(k_virtual_traces, dim3(blocks_of((uint64_t)nv * S)), dim3(256), 0, st, v.cfg.seed, 0u, (uint32_t)TAG_SIMU, v.cfg.alpha, nv, S, d_vid, d_vscale, q->d_V);
-    Q_TRY(hipGetLastError());
-    Q_TRY(hipMalloc((void **)&q->d_ident, (size_t)S * (ni ? ni : 1) * 8));
-    Q_TRY(hipMalloc((void **)&q->d_gene, (size_t)S * (ng ? ng : 1) * 8));
-    Q_TRY(hipMalloc((void **)&q->d_prop, (size_t)S * n * 8));
-    Q_TRY(hipStreamSynchronize(st));   // (the host vectors of this call were sources of asynchronous copies)
-#undef Q_TRY
-    *out = q;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(q->d_ident.alloc((size_t)S * (ni ? ni : 1)));
+    HIP_TRY(q->d_gene.alloc((size_t)S * (ng ? ng : 1)));
+    HIP_TRY(q->d_prop.alloc((size_t)S * n));
+    HIP_TRY(hipStreamSynchronize(st));   // (the host vectors of this call were sources of asynchronous copies)
+    *out = q.release();
     return MMG_OK;
 }
 
@@ -191,13 +187,13 @@ extern "C" int mmg_summary_advance(mmg_summary *q, int samples_done)
     if ((uint32_t)samples_done == q->done) return MMG_OK;
     HIP_TRY(hipSetDevice(q->device));
     const uint32_t s0 = q->done, c = (uint32_t)samples_done - s0, n = q->n, nv = q->nv, ni = q->ni, ng = q->ng;
-    hipStream_t st = q->st;
+    hipStream_t st = q->st.get();
     const double *tr = q->trace + (size_t)s0 * n, *V = q->d_V + (size_t)s0 * nv;
-    const uint32_t *ioe = q->p->d_int_of_ext;
-    if (ni) hipLaunchKernelGGL(k_group_sums, dim3(blocks_of((uint64_t)ni * c)), dim3(256), 0, st, ni, c, n, nv, q->d_iptr, q->d_imem, ioe, tr, V, q->d_ident + (size_t)s0 * ni);
-    if (ng) hipLaunchKernelGGL(k_group_sums, dim3(blocks_of((uint64_t)ng * c)), dim3(256), 0, st, ng, c, n, nv, q->d_gptr, q->d_gmem, ioe, tr, V, q->d_gene + (size_t)s0 * ng);
-    hipLaunchKernelGGL(k_proportions, dim3(blocks_of((uint64_t)n * c)), dim3(256), 0, st, n, c, n, tr, ioe, q->d_gene_t, ng, q->d_gene + (size_t)s0 * ng, q->d_prop + (size_t)s0 * n);
-    if (nv) hipLaunchKernelGGL(k_proportions, dim3(blocks_of((uint64_t)nv * c)), dim3(256), 0, st, nv, c, nv, V, (const uint32_t *)nullptr, q->d_gene_v, ng, q->d_gene + (size_t)s0 * ng, q->d_propV + (size_t)s0 * nv);
+    const uint32_t *ioe = q->p->d_int_of_ext.get();
+    if (ni) hipLaunchKernelGGL(k_group_sums, dim3(blocks_of((uint64_t)ni * c)), dim3(256), 0, st, ni, c, n, nv, q->d_iptr, q->d_imem, ioe, tr, V, q->d_ident.get() + (size_t)s0 * ni);
+    if (ng) hipLaunchKernelGGL(k_group_sums, dim3(blocks_of((uint64_t)ng * c)), dim3(256), 0, st, ng, c, n, nv, q->d_gptr, q->d_gmem, ioe, tr, V, q->d_gene.get() + (size_t)s0 * ng);
+    hipLaunchKernelGGL(k_proportions, dim3(blocks_of((uint64_t)n * c)), dim3(256), 0, st, n, c, n, tr, ioe, q->d_gene_t, ng, q->d_gene.get() + (size_t)s0 * ng, q->d_prop.get() + (size_t)s0 * n);
+    if (nv) hipLaunchKernelGGL(k_proportions, dim3(blocks_of((uint64_t)nv * c)), dim3(256), 0, st, nv, c, nv, V, (const uint32_t *)nullptr, q->d_gene_v, ng, q->d_gene.get() + (size_t)s0 * ng, q->d_propV + (size_t)s0 * nv);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
     q->done = (uint32_t)samples_done;
@@ -213,55 +209,50 @@ extern "C" int mmg_summary_finish(mmg_summary *q)
     if (q->done != q->S) return fail(MMG_ERR_STATE, "mmg_summary_finish before every sample was handed to mmg_summary_advance");
     HIP_TRY(hipSetDevice(q->device));
     const uint32_t n = q->n, nv = q->nv, ni = q->ni, ng = q->ng, np = q->np, S = q->S;
-    hipStream_t st = q->st;
+    hipStream_t st = q->st.get();
     // transpose to series-major, one workgroup per series
     size_t maxcnt = n;
     for (size_t c : {(size_t)nv, (size_t)ni, (size_t)ng}) if (c > maxcnt) maxcnt = c;
     double *d_T = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_T, maxcnt * S * 8));
-    q->scratch.push_back(d_T);
+    HIP_TRY(scratch_alloc(q->scratch, (void **)&d_T, maxcnt * S * 8));
     uint64_t *d_ws = nullptr;
-    if (series_workspace_bytes(S)) {
-        HIP_TRY(hipMalloc((void **)&d_ws, series_workspace_bytes(S)));
-        q->scratch.push_back(d_ws);
-    }
+    if (series_workspace_bytes(S)) HIP_TRY(scratch_alloc(q->scratch, (void **)&d_ws, series_workspace_bytes(S)));
     const uint32_t counts[4] = {n, nv, ni, ng};
-    const double *srcs[4] = {q->trace, q->d_V, q->d_ident, q->d_gene};
+    const double *srcs[4] = {q->trace, q->d_V, q->d_ident.get(), q->d_gene.get()};
     for (int k = 0; k < 4; ++k) {
         SeriesBuf &b = q->ser[k];
         b.count = counts[k];
         const size_t c = counts[k] ? counts[k] : 1;
-        HIP_TRY(hipMalloc((void **)&b.log_mean, c * 8));
-        HIP_TRY(hipMalloc((void **)&b.var, c * 8));
-        HIP_TRY(hipMalloc((void **)&b.tau, c * 8));
-        HIP_TRY(hipMalloc((void **)&b.rc, c * 4));
-        HIP_TRY(hipMalloc((void **)&b.pct, c * (np ? np : 1) * 8));
+        HIP_TRY(b.log_mean.alloc(c));
+        HIP_TRY(b.var.alloc(c));
+        HIP_TRY(b.tau.alloc(c));
+        HIP_TRY(b.rc.alloc(c));
+        HIP_TRY(b.pct.alloc(c * (np ? np : 1)));
         if (!counts[k]) continue;
-        launch_transpose(srcs[k], d_T, counts[k], S, k == MMG_SERIES_TRANSCRIPT ? q->p->d_int_of_ext : nullptr, st);
-        SeriesOut o{b.log_mean, b.var, b.tau, b.rc, b.pct, nullptr, nullptr, nullptr};
+        launch_transpose(srcs[k], d_T, counts[k], S, k == MMG_SERIES_TRANSCRIPT ? q->p->d_int_of_ext.get() : nullptr, st);
+        SeriesOut o{b.log_mean.get(), b.var.get(), b.tau.get(), b.rc.get(), b.pct.get(), nullptr, nullptr, nullptr};
         int rc = launch_series<true>(counts[k], S, d_T, np, q->d_pind, nullptr, q->d_tw, o, d_ws, st);
         if (rc) return rc;
     }
-    const double *psrc[2] = {q->d_prop, q->d_propV};
+    const double *psrc[2] = {q->d_prop.get(), q->d_propV};
     const uint8_t *pmulti[2] = {q->d_multi_t, q->d_multi_v};
     for (int k = 0; k < 2; ++k) {
         PropBuf &b = q->prop[k];
         b.count = counts[k];
         const size_t c = counts[k] ? counts[k] : 1;
-        HIP_TRY(hipMalloc((void **)&b.mean, c * 8));
-        HIP_TRY(hipMalloc((void **)&b.probit_mean, c * 8));
-        HIP_TRY(hipMalloc((void **)&b.probit_sd, c * 8));
-        HIP_TRY(hipMalloc((void **)&b.pct, c * (np ? np : 1) * 8));
+        HIP_TRY(b.mean.alloc(c));
+        HIP_TRY(b.probit_mean.alloc(c));
+        HIP_TRY(b.probit_sd.alloc(c));
+        HIP_TRY(b.pct.alloc(c * (np ? np : 1)));
         if (!counts[k]) continue;
         launch_transpose(psrc[k], d_T, counts[k], S, nullptr, st); // d_prop is in the caller's numbering already
-        SeriesOut o{nullptr, nullptr, nullptr, nullptr, b.pct, b.mean, b.probit_mean, b.probit_sd};
+        SeriesOut o{nullptr, nullptr, nullptr, nullptr, b.pct.get(), b.mean.get(), b.probit_mean.get(), b.probit_sd.get()};
         int rc = launch_series<false>(counts[k], S, d_T, np, q->d_pind, pmulti[k], q->d_tw, o, d_ws, st);
         if (rc) return rc;
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
-    for (void *x : q->scratch) if (x) (void)hipFree(x);   // the group tables, the virtual traces: the results no longer need them
-    q->scratch.clear();
+    q->scratch.clear();   // the group tables, the virtual traces: the results no longer need them
     q->d_V = q->d_propV = nullptr;
     q->finished = true;
     return MMG_OK;
@@ -277,7 +268,7 @@ extern "C" int mmg_summary_create(mmg_sampler *smp, const mmg_summary_desc *d, m
     rc = mmg_sampler_sync(smp);                      // every sample is final
     if (rc == MMG_OK) rc = mmg_summary_advance(q, (int)q->S);
     if (rc == MMG_OK) rc = mmg_summary_finish(q);
-    if (rc) { summary_free(q); return rc; }
+    if (rc) { delete q; return rc; }
     *out = q;
     return MMG_OK;
 }
@@ -298,11 +289,11 @@ extern "C" int mmg_summary_get(mmg_summary *q, int kind, double *log_mean, doubl
     const SeriesBuf &b = q->ser[kind];
     const size_t c = b.count;
     if (!c) return MMG_OK;
-    if (log_mean) HIP_TRY(hipMemcpy(log_mean, b.log_mean, c * 8, hipMemcpyDeviceToHost));
-    if (var) HIP_TRY(hipMemcpy(var, b.var, c * 8, hipMemcpyDeviceToHost));
-    if (tau) HIP_TRY(hipMemcpy(tau, b.tau, c * 8, hipMemcpyDeviceToHost));
-    if (sokal_rc) HIP_TRY(hipMemcpy(sokal_rc, b.rc, c * 4, hipMemcpyDeviceToHost));
-    if (percentiles && q->np) HIP_TRY(hipMemcpy(percentiles, b.pct, c * q->np * 8, hipMemcpyDeviceToHost));
+    if (log_mean) HIP_TRY(hipMemcpy(log_mean, b.log_mean.get(), c * 8, hipMemcpyDeviceToHost));
+    if (var) HIP_TRY(hipMemcpy(var, b.var.get(), c * 8, hipMemcpyDeviceToHost));
+    if (tau) HIP_TRY(hipMemcpy(tau, b.tau.get(), c * 8, hipMemcpyDeviceToHost));
+    if (sokal_rc) HIP_TRY(hipMemcpy(sokal_rc, b.rc.get(), c * 4, hipMemcpyDeviceToHost));
+    if (percentiles && q->np) HIP_TRY(hipMemcpy(percentiles, b.pct.get(), c * q->np * 8, hipMemcpyDeviceToHost));
     return MMG_OK;
 }
 
@@ -315,10 +306,10 @@ extern "C" int mmg_summary_get_proportions(mmg_summary *q, int kind, double *mea
     const PropBuf &b = q->prop[kind];
     const size_t c = b.count;
     if (!c) return MMG_OK;
-    if (mean_prop) HIP_TRY(hipMemcpy(mean_prop, b.mean, c * 8, hipMemcpyDeviceToHost));
-    if (mean_probit) HIP_TRY(hipMemcpy(mean_probit, b.probit_mean, c * 8, hipMemcpyDeviceToHost));
-    if (sd_probit) HIP_TRY(hipMemcpy(sd_probit, b.probit_sd, c * 8, hipMemcpyDeviceToHost));
-    if (percentiles && q->np) HIP_TRY(hipMemcpy(percentiles, b.pct, c * q->np * 8, hipMemcpyDeviceToHost));
+    if (mean_prop) HIP_TRY(hipMemcpy(mean_prop, b.mean.get(), c * 8, hipMemcpyDeviceToHost));
+    if (mean_probit) HIP_TRY(hipMemcpy(mean_probit, b.probit_mean.get(), c * 8, hipMemcpyDeviceToHost));
+    if (sd_probit) HIP_TRY(hipMemcpy(sd_probit, b.probit_sd.get(), c * 8, hipMemcpyDeviceToHost));
+    if (percentiles && q->np) HIP_TRY(hipMemcpy(percentiles, b.pct.get(), c * q->np * 8, hipMemcpyDeviceToHost));
     return MMG_OK;
 }
 
@@ -328,9 +319,9 @@ extern "C" int mmg_summary_get_rows(mmg_summary *q, int kind, int first_sample, 
     const double *src = nullptr;
     size_t width = 0;
     switch (kind) {
-    case MMG_SERIES_TRANSCRIPT: src = q->d_prop; width = q->n; break;   // proportions of gene expression, caller's numbering
-    case MMG_SERIES_IDENTICAL: src = q->d_ident; width = q->ni; break;
-    case MMG_SERIES_GENE: src = q->d_gene; width = q->ng; break;
+    case MMG_SERIES_TRANSCRIPT: src = q->d_prop.get(); width = q->n; break;   // proportions of gene expression, caller's numbering
+    case MMG_SERIES_IDENTICAL: src = q->d_ident.get(); width = q->ni; break;
+    case MMG_SERIES_GENE: src = q->d_gene.get(); width = q->ng; break;
     default: return fail(MMG_ERR_ARG, "rows exist for the proportion, identical-set and gene traces");
     }
     if (first_sample < 0 || n_samples < 0 || (int64_t)first_sample + n_samples > (int64_t)q->S) return fail(MMG_ERR_ARG, "bad sample range");
@@ -338,13 +329,13 @@ extern "C" int mmg_summary_get_rows(mmg_summary *q, int kind, int first_sample, 
     HIP_TRY(hipSetDevice(q->device));
     if (width && n_samples) {
         std::lock_guard<std::mutex> lock(q->rows_mu);
-        if (!q->rows_st) HIP_TRY(hipStreamCreateWithFlags(&q->rows_st, hipStreamNonBlocking));
-        HIP_TRY(q->rows_stage.copy_out(out, src + (size_t)first_sample * width, (size_t)n_samples * width * 8, q->rows_st));
+        if (!q->rows_st) HIP_TRY(q->rows_st.create(hipStreamNonBlocking));
+        HIP_TRY(q->rows_stage.copy_out(out, src + (size_t)first_sample * width, (size_t)n_samples * width * 8, q->rows_st.get()));
     }
     return MMG_OK;
 }
 
-extern "C" void mmg_summary_destroy(mmg_summary *q) { summary_free(q); }
+extern "C" void mmg_summary_destroy(mmg_summary *q) { delete q; }
 
 // mmcollapse's output stage (src/mmcollapse.cpp:827-1107) on traces from the host, independent of any sampler: simulated traces of the
 // features without one, sums over the output series (:443-481), then per series the mean of the logged trace and Sokal's var / tau
@@ -368,9 +359,8 @@ extern "C" int mmg_collapse_summarize(int device, uint32_t trace_len, uint32_t n
     if (rc) return rc;
     if (n_series == 0) return MMG_OK;
     const uint32_t S = trace_len, n = n_cols, nv = n_virtual, ng = n_series;
-    std::vector<void *> bufs;
-    struct Freer { std::vector<void *> &b; ~Freer() { for (void *x : b) (void)hipFree(x); } } freer{bufs};
-    auto dalloc = [&](void **p, size_t bytes) { hipError_t e = hipMalloc(p, bytes ? bytes : 8); if (e == hipSuccess) bufs.push_back(*p); return e; };
+    std::vector<DevBuf<uint8_t>> bufs;
+    auto dalloc = [&](void **p, size_t bytes) { return scratch_alloc(bufs, p, bytes); };
     auto upload = [&](void **p, const void *src, size_t bytes) {
         hipError_t e = dalloc(p, bytes);
         if (e == hipSuccess && bytes) e = hipMemcpy(*p, src, bytes, hipMemcpyHostToDevice);

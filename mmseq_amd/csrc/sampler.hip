@@ -7,66 +7,65 @@
 #include <algorithm>
 #include <array>
 #include <deque>
+#include <memory>
 #include <mutex>
 
 using namespace mmg;
 
+// Members are destroyed in reverse declaration order: the destructor waits for `own` and `side`, then the buffers and events go, and the
+// streams they were used on last.
 struct mmg_sampler {
     const mmg_problem *p = nullptr;
     int device = 0;
     mmg_config cfg{};
-    hipStream_t own = nullptr, cur = nullptr;
+    DevStream own;
+    hipStream_t cur = nullptr;
     // the launch of the rows on the conditional-binomial chain (k_sample_bigk: few waves, long chains of arithmetic) runs beside the tile
     // kernels (bound by the stream of hits) on a stream of its own, forked from and joined to `cur` inside every sample()
-    hipStream_t side = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    double *d_mu = nullptr, *d_scale = nullptr, *d_trace = nullptr, *d_mom = nullptr; // mom: [2][C][n]
-    int32_t *d_cnt = nullptr, *d_cnt_last = nullptr;
+    DevStream side;
+    DevEvent ev_fork, ev_join;
+    DevStream reader;                                      // mmg_sampler_get_trace_rows_done: copies that do not queue behind the chain
+    DevBuf<double> d_reader_tmp;                           // its gather buffer, kept (hipFree would wait for the running chain)
+    DevBuf<double> d_mu, d_scale, d_trace, d_mom;          // mom: [2][C][n]
+    DevBuf<int32_t> d_cnt, d_cnt_last;
     int iter = 0;          // completed iterations
     bool sampled = false;  // sample() issued for the current iteration, update() pending
     int64_t n_kept = 0;
     // timing
     // HIP-event pairs around timed launches: a pair is harvested (its time added to the sums, its events back on the free list) as soon
     // as it has completed, so the pool stays as large as the launches in flight however long the chain
-    std::vector<hipEvent_t> ev_pool;
+    std::vector<DevEvent> ev_pool;
     std::vector<int> ev_free;                              // indices into ev_pool
     std::deque<std::array<int, 4>> ev_pending;             // {start, stop, 0 sample | 1 update, stop of the side launch or -1} in enqueue order
-    hipStream_t reader = nullptr;                          // mmg_sampler_get_trace_rows_done: copies that do not queue behind the chain
-    double *d_reader_tmp = nullptr;                        // its gather buffer, kept (hipFree would wait for the running chain)
     size_t reader_cap = 0;
     std::mutex reader_mu;
     PinnedStage reader_stage;
     // marks: an event behind every 16th stored sample, for mmg_sampler_wait_iterations (events without timing, recycled)
-    std::vector<hipEvent_t> mark_pool;
+    std::vector<DevEvent> mark_pool;
     std::vector<int> mark_free;
     std::deque<std::pair<int, int>> marks;                 // {iterations completed when the event fires, index into mark_pool}
     int fired_upto = 0;                                    // iterations known to have completed: the last mark seen fired (recycled or waited for)
     double acc_sample_ms = 0, acc_update_ms = 0;
     uint64_t acc_sample_n = 0, acc_update_n = 0;
+    ~mmg_sampler()
+    {
+        if (own) (void)hipStreamSynchronize(own.get());
+        if (side) (void)hipStreamSynchronize(side.get());
+    }
 };
 
-static void sampler_free(mmg_sampler *s)
-{
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    if (s->own) { (void)hipStreamSynchronize(s->own); }
-    for (auto e : s->ev_pool) (void)hipEventDestroy(e);
-    for (auto e : s->mark_pool) (void)hipEventDestroy(e);
-    for (void *x : {(void *)s->d_mu, (void *)s->d_scale, (void *)s->d_trace, (void *)s->d_mom, (void *)s->d_cnt, (void *)s->d_cnt_last})
-        if (x) (void)hipFree(x);
-    if (s->side) { (void)hipStreamSynchronize(s->side); (void)hipStreamDestroy(s->side); }
-    if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
-    if (s->ev_join) (void)hipEventDestroy(s->ev_join);
-    if (s->own) (void)hipStreamDestroy(s->own);
-    if (s->reader) (void)hipStreamDestroy(s->reader);
-    if (s->d_reader_tmp) (void)hipFree(s->d_reader_tmp);
-    delete s;
-}
+// The pool indices a timed launch holds: back on the free list at scope exit unless the call queued them on ev_pending (keep()).
+struct EvHeld {
+    std::vector<int> &free_list;
+    int idx[3] = {-1, -1, -1};
+    ~EvHeld() { for (int i : idx) if (i >= 0) free_list.push_back(i); }
+    void keep() { idx[0] = idx[1] = idx[2] = -1; }
+};
 
 int mmg::sampler_view(mmg_sampler *s, SamplerView *v)
 {
     if (!s || !v) return fail(MMG_ERR_ARG, "NULL argument");
-    v->p = s->p; v->cfg = s->cfg; v->d_trace = s->d_trace; v->stream = s->cur; v->iter = s->iter; v->n_kept = s->n_kept;
+    v->p = s->p; v->cfg = s->cfg; v->d_trace = s->d_trace.get(); v->stream = s->cur; v->iter = s->iter; v->n_kept = s->n_kept;
     return MMG_OK;
 }
 
@@ -81,47 +80,44 @@ extern "C" int mmg_sampler_create(const mmg_problem *p, const mmg_config *cfg, c
         if (!(mu0[t] >= 0.0)) return fail(MMG_ERR_ARG, "mu0 must be finite and >= 0");
     int rc = require_device(p->device);
     if (rc) return rc;
-    mmg_sampler *s = new mmg_sampler();
+    std::unique_ptr<mmg_sampler> s(new mmg_sampler());
     s->p = p;
     s->device = p->device;
     s->cfg = *cfg;
     const size_t C = (size_t)cfg->n_chains, n = p->n;
-    auto bail = [&](int code) { sampler_free(s); return code; };
-#define S_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return bail(fail(MMG_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e))); } while (0)
-    S_TRY(hipStreamCreateWithFlags(&s->own, hipStreamNonBlocking));
-    s->cur = s->own;
+    HIP_TRY(s->own.create(hipStreamNonBlocking));
+    s->cur = s->own.get();
     if (p->grid_bigk > 0) {
-        S_TRY(hipStreamCreateWithFlags(&s->side, hipStreamNonBlocking));
-        S_TRY(hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming));
-        S_TRY(hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming));
+        HIP_TRY(s->side.create(hipStreamNonBlocking));
+        HIP_TRY(s->ev_fork.create(hipEventDisableTiming));
+        HIP_TRY(s->ev_join.create(hipEventDisableTiming));
     }
-    S_TRY(hipMalloc((void **)&s->d_mu, C * n * sizeof(double)));
-    S_TRY(hipMalloc((void **)&s->d_scale, n * sizeof(double)));
-    S_TRY(hipMalloc((void **)&s->d_mom, 2 * C * n * sizeof(double)));
-    S_TRY(hipMalloc((void **)&s->d_cnt, p->cnt_replicas * C * n * sizeof(int32_t))); // [replicas][C][n]; replica 0 is the public vector
-    S_TRY(hipMalloc((void **)&s->d_cnt_last, C * n * sizeof(int32_t)));
-    if (cfg->keep_trace) S_TRY(hipMalloc((void **)&s->d_trace, C * n * (size_t)cfg->trace_len * sizeof(double)));
+    HIP_TRY(s->d_mu.alloc(C * n));
+    HIP_TRY(s->d_scale.alloc(n));
+    HIP_TRY(s->d_mom.alloc(2 * C * n));
+    HIP_TRY(s->d_cnt.alloc(p->cnt_replicas * C * n)); // [replicas][C][n]; replica 0 is the public vector
+    HIP_TRY(s->d_cnt_last.alloc(C * n));
+    if (cfg->keep_trace) HIP_TRY(s->d_trace.alloc(C * n * (size_t)cfg->trace_len));
     std::vector<double> scale_ext(n), scale, mu_int;
     for (size_t t = 0; t < n; ++t) scale_ext[t] = 1.0 / (cfg->beta + p->h_l[t]); // src/mmseq.cpp:907 second argument
     to_int(p, scale_ext.data(), scale);
     to_int(p, mu0, mu_int);
     // every fill goes to the sampler's own stream (non-blocking: not ordered against the NULL stream) and is waited for here
-    S_TRY(hipMemcpyAsync(s->d_scale, scale.data(), n * sizeof(double), hipMemcpyHostToDevice, s->own));
-    for (size_t c = 0; c < C; ++c) S_TRY(hipMemcpyAsync(s->d_mu + c * n, mu_int.data(), n * sizeof(double), hipMemcpyHostToDevice, s->own));
-    S_TRY(hipMemsetAsync(s->d_mom, 0, 2 * C * n * sizeof(double), s->own));
-    S_TRY(hipMemsetAsync(s->d_cnt, 0, p->cnt_replicas * C * n * sizeof(int32_t), s->own));
-    S_TRY(hipMemsetAsync(s->d_cnt_last, 0, C * n * sizeof(int32_t), s->own));
-    if (s->d_trace) S_TRY(hipMemsetAsync(s->d_trace, 0, C * n * (size_t)cfg->trace_len * sizeof(double), s->own));
-    S_TRY(hipStreamSynchronize(s->own));
-#undef S_TRY
-    *out = s;
+    HIP_TRY(hipMemcpyAsync(s->d_scale.get(), scale.data(), n * sizeof(double), hipMemcpyHostToDevice, s->own.get()));
+    for (size_t c = 0; c < C; ++c) HIP_TRY(hipMemcpyAsync(s->d_mu.get() + c * n, mu_int.data(), n * sizeof(double), hipMemcpyHostToDevice, s->own.get()));
+    HIP_TRY(hipMemsetAsync(s->d_mom.get(), 0, 2 * C * n * sizeof(double), s->own.get()));
+    HIP_TRY(hipMemsetAsync(s->d_cnt.get(), 0, p->cnt_replicas * C * n * sizeof(int32_t), s->own.get()));
+    HIP_TRY(hipMemsetAsync(s->d_cnt_last.get(), 0, C * n * sizeof(int32_t), s->own.get()));
+    if (s->d_trace.get()) HIP_TRY(hipMemsetAsync(s->d_trace.get(), 0, C * n * (size_t)cfg->trace_len * sizeof(double), s->own.get()));
+    HIP_TRY(hipStreamSynchronize(s->own.get()));
+    *out = s.release();
     return MMG_OK;
 }
 
 extern "C" int mmg_sampler_set_stream(mmg_sampler *s, void *hip_stream)
 {
     if (!s) return fail(MMG_ERR_ARG, "NULL sampler");
-    s->cur = hip_stream ? (hipStream_t)hip_stream : s->own;
+    s->cur = hip_stream ? (hipStream_t)hip_stream : s->own.get();
     return MMG_OK;
 }
 
@@ -133,16 +129,16 @@ static int ev_harvest(mmg_sampler *s, bool wait)
         if (!wait) {
             for (int q_i : {1, 3}) {
                 if (pr[q_i] < 0) continue;
-                const hipError_t q = hipEventQuery(s->ev_pool[pr[q_i]]);
+                const hipError_t q = hipEventQuery(s->ev_pool[pr[q_i]].get());
                 if (q == hipErrorNotReady) { (void)hipGetLastError(); return MMG_OK; }
                 if (q != hipSuccess) return fail(MMG_ERR_HIP, std::string("hipEventQuery: ") + hipGetErrorString(q));
             }
         }
         float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, s->ev_pool[pr[0]], s->ev_pool[pr[1]]));
+        HIP_TRY(hipEventElapsedTime(&ms, s->ev_pool[pr[0]].get(), s->ev_pool[pr[1]].get()));
         if (pr[3] >= 0) { // the side launch may end after the last launch of the main stream: K1's time is to the later of the two
             float ms2 = 0;
-            HIP_TRY(hipEventElapsedTime(&ms2, s->ev_pool[pr[0]], s->ev_pool[pr[3]]));
+            HIP_TRY(hipEventElapsedTime(&ms2, s->ev_pool[pr[0]].get(), s->ev_pool[pr[3]].get()));
             ms = std::max(ms, ms2);
             s->ev_free.push_back(pr[3]);
         }
@@ -157,9 +153,9 @@ static int ev_get(mmg_sampler *s, int &idx)
 {
     if (s->ev_free.empty() && s->ev_pending.size() >= 64) { int rc = ev_harvest(s, false); if (rc) return rc; }
     if (s->ev_free.empty()) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreate(&e));
-        s->ev_pool.push_back(e);
+        DevEvent e;
+        HIP_TRY(e.create());
+        s->ev_pool.push_back(std::move(e));
         s->ev_free.push_back((int)s->ev_pool.size() - 1);
     }
     idx = s->ev_free.back();
@@ -175,7 +171,8 @@ static int sampler_sample(mmg_sampler *s, bool fold)
     if (s->sampled) return fail(MMG_ERR_STATE, "sample() already issued for this iteration; call update()");
     const mmg_problem *p = s->p;
     HIP_TRY(hipSetDevice(s->device));
-    int e0 = -1, e1 = -1;
+    EvHeld held{s->ev_free};
+    int &e0 = held.idx[0], &e1 = held.idx[1], &e2 = held.idx[2];
     const bool timed = s->cfg.timing > 0 && s->iter % s->cfg.timing == 0;
     // A timed iteration's events ride on the launches themselves (hipExtLaunchKernel: the dispatch's own start and end time stamps): the
     // first launch of the call carries the start event, every launch the stop event (the last one keeps it).  Recorded into the stream
@@ -184,9 +181,9 @@ static int sampler_sample(mmg_sampler *s, bool fold)
     if (timed) {
         int rc = ev_get(s, e0); if (rc) return rc;
         rc = ev_get(s, e1); if (rc) return rc;
-        ev_start = s->ev_pool[e0]; ev_stop = s->ev_pool[e1];
+        ev_start = s->ev_pool[e0].get(); ev_stop = s->ev_pool[e1].get();
     }
-    int n_launched = 0, e2 = -1;
+    int n_launched = 0;
     bool joined = true;
     auto launch = [&](const void *fn, dim3 grid, dim3 block, void **kargs) -> hipError_t {
         const hipError_t e = timed ? hipExtLaunchKernel(fn, grid, block, kargs, 0, s->cur, n_launched == 0 ? ev_start : nullptr, ev_stop, 0)
@@ -205,15 +202,15 @@ static int sampler_sample(mmg_sampler *s, bool fold)
             a.iter = (uint32_t)s->iter;
             return a;
         };
-        const void *rp = p->d_row_ptr;
-        const uint32_t *ci = p->d_col, *kk = p->d_k;
-        const uint8_t *ss = p->d_sell;
+        const void *rp = p->d_row_ptr.get();
+        const uint32_t *ci = p->d_col.get(), *kk = p->d_k.get();
+        const uint8_t *ss = p->d_sell.get();
         // k_sample_sell over one tile list for chains [c0, c0 + nc): grid.y = chain
         // kind: 0 k_sample_sell, 1 its multiplicity instantiation, 2 its far-list instantiation
         auto launch_single = [&](const SellTile *ts, const uint64_t *cs, int grid, int kind, int c0, int nc) -> int {
             SampleArgs a = args_of(c0);
-            const double *mu = s->d_mu + (size_t)c0 * p->n;
-            int32_t *cnt = s->d_cnt + (size_t)c0 * p->n;
+            const double *mu = s->d_mu.get() + (size_t)c0 * p->n;
+            int32_t *cnt = s->d_cnt.get() + (size_t)c0 * p->n;
             void *kargs[] = {(void *)&rp, (void *)&ci, (void *)&kk, (void *)&ts, (void *)&cs, (void *)&mu, (void *)&ss, (void *)&cnt, (void *)&a};
             const void *fn = kind == 2 ? k1_sell_far_kernel(p->idx64) : k1_sell_kernel(p->idx64, kind == 1, kind == 0 && p->k1_fixed_walk);
             HIP_TRY(launch(fn, dim3(grid, nc), dim3(64), kargs));
@@ -224,21 +221,21 @@ static int sampler_sample(mmg_sampler *s, bool fold)
             // of arithmetic.  They start first, on the side stream (ordered behind everything enqueued on `cur` so far -- the update that
             // wrote mu), and the tile kernels below fill the device around them; sample() ends with `cur` waiting for the side stream.
             SampleArgs a = args_of(0);
-            const double *mu = s->d_mu;
-            int32_t *cnt = s->d_cnt;
-            const uint64_t *list = p->d_bigk_list;
+            const double *mu = s->d_mu.get();
+            int32_t *cnt = s->d_cnt.get();
+            const uint64_t *list = p->d_bigk_list.get();
             uint64_t n_list = p->n_bigk;
             uint32_t per = p->bigk_per_wave;
             void *kargs[] = {(void *)&rp, (void *)&ci, (void *)&kk, (void *)&list, (void *)&n_list, (void *)&per, (void *)&mu, (void *)&cnt, (void *)&a};
             // (not beside the legacy NULL stream or the per-thread stream: special handles, which the event calls below do not take here)
             const bool beside = opt(MMG_OPT_BIGK_SIDE_STREAM) != 0 && s->cur != hipStreamLegacy && s->cur != hipStreamPerThread;
             if (beside) {
-                HIP_TRY(hipEventRecord(s->ev_fork, s->cur));
-                HIP_TRY(hipStreamWaitEvent(s->side, s->ev_fork, 0));
+                HIP_TRY(hipEventRecord(s->ev_fork.get(), s->cur));
+                HIP_TRY(hipStreamWaitEvent(s->side.get(), s->ev_fork.get(), 0));
                 if (timed) { int rc = ev_get(s, e2); if (rc) return rc; }
-                HIP_TRY(timed ? hipExtLaunchKernel(k1_bigk_kernel(p->idx64), dim3(p->grid_bigk, C), dim3(64), kargs, 0, s->side, nullptr, s->ev_pool[e2], 0)
-                              : hipLaunchKernel(k1_bigk_kernel(p->idx64), dim3(p->grid_bigk, C), dim3(64), kargs, 0, s->side));
-                HIP_TRY(hipEventRecord(s->ev_join, s->side));
+                HIP_TRY(timed ? hipExtLaunchKernel(k1_bigk_kernel(p->idx64), dim3(p->grid_bigk, C), dim3(64), kargs, 0, s->side.get(), nullptr, s->ev_pool[e2].get(), 0)
+                              : hipLaunchKernel(k1_bigk_kernel(p->idx64), dim3(p->grid_bigk, C), dim3(64), kargs, 0, s->side.get()));
+                HIP_TRY(hipEventRecord(s->ev_join.get(), s->side.get()));
                 joined = false;
             } else HIP_TRY(launch(k1_bigk_kernel(p->idx64), dim3(p->grid_bigk, C), dim3(64), kargs));
         }
@@ -259,46 +256,47 @@ static int sampler_sample(mmg_sampler *s, bool fold)
                 const int groups = (c < n_fused ? n_fused - c : n_fused + n_rest - c) / f;
                 SampleArgs a = args_of(c);
                 const SellTile *ts = p->d_sell_tiles_f;
-                const uint64_t *cs = p->d_sell_chunk_m[f == 4 ? 1 : 0];
-                const double *mu = s->d_mu + (size_t)c * p->n;
-                int32_t *cnt = s->d_cnt + (size_t)c * p->n;
+                const uint64_t *cs = p->d_sell_chunk_m[f == 4 ? 1 : 0].get();
+                const double *mu = s->d_mu.get() + (size_t)c * p->n;
+                int32_t *cnt = s->d_cnt.get() + (size_t)c * p->n;
                 void *kargs[] = {(void *)&rp, (void *)&ci, (void *)&ts, (void *)&cs, (void *)&mu, (void *)&ss, (void *)&cnt, (void *)&a};
                 HIP_TRY(launch(k1_sell_multi_kernel(p->idx64, f), dim3(p->grid_sell_m[f == 4 ? 1 : 0], groups), dim3(64), kargs));
                 c += f * groups;
             }
             const int n_paired = n_fused + n_rest;
             if (n_paired > 0 && p->grid_sell_x > 0) { // their far / CSR-walked tiles: the far-list instantiation, all paired chains in one launch
-                int rc = launch_single(p->d_sell_tiles_x, p->d_sell_chunk_x, p->grid_sell_x, 2, 0, n_paired);
+                int rc = launch_single(p->d_sell_tiles_x.get(), p->d_sell_chunk_x.get(), p->grid_sell_x, 2, 0, n_paired);
                 if (rc) return rc;
             }
             if (n_paired < C) { // chains without a partner: every tile without multiplicities in ONE launch (a launch of its own for the far
                                 // tiles costs a single chain as much as it saves: 29 us for 17 k far tiles at 2 % far rows)
-                int rc = launch_single(p->grid_sell_k > 0 ? p->d_sell_tiles_1 : p->d_sell_tiles, p->d_sell_chunk, p->grid_sell, 0, n_paired, C - n_paired);
+                int rc = launch_single(p->grid_sell_k > 0 ? p->d_sell_tiles_1.get() : p->d_sell_tiles.get(), p->d_sell_chunk.get(), p->grid_sell, 0, n_paired, C - n_paired);
                 if (rc) return rc;
             }
             if (p->grid_sell_k > 0) { // the tiles that hold collapsed identical reads, in ranges balanced by their cost, for every chain
-                int rc = launch_single(p->d_sell_tiles_k, p->d_sell_chunk_k, p->grid_sell_k, 1, 0, C);
+                int rc = launch_single(p->d_sell_tiles_k.get(), p->d_sell_chunk_k.get(), p->grid_sell_k, 1, 0, C);
                 if (rc) return rc;
             }
         } else {
             for (int c = 0; c < C; ++c) {
                 SampleArgs a = args_of(c);
-                const TileDesc *td = p->d_tiles;
-                const uint64_t *ct = p->d_chunk_tile;
-                const double *mu = s->d_mu + (size_t)c * p->n;
-                int32_t *cnt = s->d_cnt + (size_t)c * p->n;
+                const TileDesc *td = p->d_tiles.get();
+                const uint64_t *ct = p->d_chunk_tile.get();
+                const double *mu = s->d_mu.get() + (size_t)c * p->n;
+                int32_t *cnt = s->d_cnt.get() + (size_t)c * p->n;
                 void *kargs[] = {(void *)&rp, (void *)&ci, (void *)&kk, (void *)&td, (void *)&ct, (void *)&mu, (void *)&cnt, (void *)&a};
-                HIP_TRY(launch(k1_csr_kernel(p->idx64, p->d_k != nullptr), dim3(p->grid_sample), dim3(K1C_BS), kargs));
+                HIP_TRY(launch(k1_csr_kernel(p->idx64, p->d_k.get() != nullptr), dim3(p->grid_sample), dim3(K1C_BS), kargs));
             }
         }
     }
-    if (!joined) HIP_TRY(hipStreamWaitEvent(s->cur, s->ev_join, 0));
+    if (!joined) HIP_TRY(hipStreamWaitEvent(s->cur, s->ev_join.get(), 0));
     if (timed) {
         if (n_launched == 0) { HIP_TRY(hipEventRecord(ev_start, s->cur)); HIP_TRY(hipEventRecord(ev_stop, s->cur)); } // (a problem without rows)
         s->ev_pending.push_back({e0, e1, 0, e2});
+        held.keep();
     }
     if (fold && p->m > 0 && p->cnt_replicas > 1) {
-        launch_fold_counts(s->d_cnt, (uint64_t)s->cfg.n_chains * p->n, (size_t)s->cfg.n_chains * p->n, s->cur);
+        launch_fold_counts(s->d_cnt.get(), (uint64_t)s->cfg.n_chains * p->n, (size_t)s->cfg.n_chains * p->n, s->cur);
         HIP_TRY(hipGetLastError());
     }
     s->sampled = true;
@@ -311,20 +309,20 @@ constexpr int MARK_EVERY = 16;
 static int mark_iteration(mmg_sampler *s)
 {
     while (!s->marks.empty()) {
-        if (hipEventQuery(s->mark_pool[s->marks.front().second]) != hipSuccess) { (void)hipGetLastError(); break; }
+        if (hipEventQuery(s->mark_pool[s->marks.front().second].get()) != hipSuccess) { (void)hipGetLastError(); break; }
         s->fired_upto = std::max(s->fired_upto, s->marks.front().first);
         s->mark_free.push_back(s->marks.front().second);
         s->marks.pop_front();
     }
     if (s->mark_free.empty()) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        s->mark_pool.push_back(e);
+        DevEvent e;
+        HIP_TRY(e.create(hipEventDisableTiming));
+        s->mark_pool.push_back(std::move(e));
         s->mark_free.push_back((int)s->mark_pool.size() - 1);
     }
     const int idx = s->mark_free.back();
     s->mark_free.pop_back();
-    HIP_TRY(hipEventRecord(s->mark_pool[idx], s->cur));
+    HIP_TRY(hipEventRecord(s->mark_pool[idx].get(), s->cur));
     s->marks.push_back({s->iter, idx});
     return MMG_OK;
 }
@@ -342,23 +340,24 @@ extern "C" int mmg_sampler_update(mmg_sampler *s)
     if (s->iter % ss == 0 && s->iter / ss < s->cfg.trace_len) sample_idx = s->iter / ss; // :911, :914
     const size_t C = (size_t)s->cfg.n_chains, n = p->n;
     UpdateArgs a;
-    a.cnt = s->d_cnt; a.cnt_last = s->d_cnt_last; a.scale = s->d_scale; a.mu = s->d_mu; a.trace = s->d_trace;
-    a.sum_log = s->d_mom; a.sum_log2 = s->d_mom + C * n;
-    a.ext_of_int = p->d_ext_of_int;
+    a.cnt = s->d_cnt.get(); a.cnt_last = s->d_cnt_last.get(); a.scale = s->d_scale.get(); a.mu = s->d_mu.get(); a.trace = s->d_trace.get();
+    a.sum_log = s->d_mom.get(); a.sum_log2 = s->d_mom.get() + C * n;
+    a.ext_of_int = p->d_ext_of_int.get();
     a.seed = s->cfg.seed; a.alpha = s->cfg.alpha; a.n = p->n; a.n_chains = (uint32_t)C;
     a.cnt_rep_stride = (uint64_t)C * n;
     a.cnt_replicas = p->cnt_replicas;
     a.chain_base = (uint32_t)s->cfg.chain_base; a.iter = (uint32_t)s->iter; a.sample_idx = sample_idx;
     a.trace_len = (uint32_t)s->cfg.trace_len;
-    int e0 = -1, e1 = -1;
+    EvHeld held{s->ev_free};
+    int &e0 = held.idx[0], &e1 = held.idx[1];
     const bool timed = s->cfg.timing > 0 && s->iter % s->cfg.timing == 0;
     if (timed) {
         int rc = ev_get(s, e0); if (rc) return rc;
         rc = ev_get(s, e1); if (rc) return rc;
     }
-    launch_update(a, s->cur, timed ? s->ev_pool[e0] : nullptr, timed ? s->ev_pool[e1] : nullptr); // (the events ride on the launch: sampler_sample)
+    launch_update(a, s->cur, timed ? s->ev_pool[e0].get() : nullptr, timed ? s->ev_pool[e1].get() : nullptr); // (the events ride on the launch: sampler_sample)
     HIP_TRY(hipGetLastError());
-    if (timed) s->ev_pending.push_back({e0, e1, 1, -1});
+    if (timed) { s->ev_pending.push_back({e0, e1, 1, -1}); held.keep(); }
     if (sample_idx >= 0) s->n_kept++;
     s->iter++;
     s->sampled = false;
@@ -403,11 +402,11 @@ extern "C" int mmg_selftest_gibbs_shards(mmg_sampler *const *samplers, int n_sha
     for (int it = 0; it < n_iter && rc == MMG_OK; ++it) {
         for (int i = 0; i < n_shards && rc == MMG_OK; ++i) rc = mmg_sampler_sample(samplers[i]);             // src/mmseq.cpp:857-891 on the shard's rows
         for (int i = 1; i < n_shards && rc == MMG_OK; ++i) {                                                  // :896-899 across shards
-            launch_add_i32(samplers[0]->d_cnt, samplers[i]->d_cnt, count, st);
+            launch_add_i32(samplers[0]->d_cnt.get(), samplers[i]->d_cnt.get(), count, st);
             if (hipGetLastError() != hipSuccess) rc = fail(MMG_ERR_HIP, "count exchange");
         }
         for (int i = 1; i < n_shards && rc == MMG_OK; ++i)
-            if (hipMemcpyAsync(samplers[i]->d_cnt, samplers[0]->d_cnt, count * sizeof(int32_t), hipMemcpyDeviceToDevice, st) != hipSuccess) rc = fail(MMG_ERR_HIP, "count exchange");
+            if (hipMemcpyAsync(samplers[i]->d_cnt.get(), samplers[0]->d_cnt.get(), count * sizeof(int32_t), hipMemcpyDeviceToDevice, st) != hipSuccess) rc = fail(MMG_ERR_HIP, "count exchange");
         for (int i = 0; i < n_shards && rc == MMG_OK; ++i) rc = mmg_sampler_update(samplers[i]);             // :905-917, identical everywhere
     }
     const hipError_t e = hipStreamSynchronize(st);
@@ -419,7 +418,7 @@ extern "C" int mmg_selftest_gibbs_shards(mmg_sampler *const *samplers, int n_sha
 extern "C" int mmg_sampler_counts_devptr(mmg_sampler *s, void **ptr, uint64_t *count)
 {
     if (!s || !ptr) return fail(MMG_ERR_ARG, "NULL argument");
-    *ptr = s->d_cnt;
+    *ptr = s->d_cnt.get();
     if (count) *count = (uint64_t)s->cfg.n_chains * s->p->n;
     return MMG_OK;
 }
@@ -427,7 +426,7 @@ extern "C" int mmg_sampler_counts_devptr(mmg_sampler *s, void **ptr, uint64_t *c
 extern "C" int mmg_sampler_moments_devptr(mmg_sampler *s, void **ptr, uint64_t *count)
 {
     if (!s || !ptr) return fail(MMG_ERR_ARG, "NULL argument");
-    *ptr = s->d_mom;
+    *ptr = s->d_mom.get();
     if (count) *count = 2ull * (uint64_t)s->cfg.n_chains * s->p->n;
     return MMG_OK;
 }
@@ -457,11 +456,21 @@ extern "C" int mmg_sampler_wait_iterations(mmg_sampler *s, int n_done)
         HIP_TRY(hipStreamSynchronize(s->cur));
         s->fired_upto = s->iter;
     } else {
-        HIP_TRY(hipEventSynchronize(s->mark_pool[s->marks[k].second]));
+        HIP_TRY(hipEventSynchronize(s->mark_pool[s->marks[k].second].get()));
         s->fired_upto = std::max(s->fired_upto, s->marks[k].first);
         ++k;
     }
     for (size_t i = 0; i < k; ++i) { s->mark_free.push_back(s->marks.front().second); s->marks.pop_front(); }
+    return MMG_OK;
+}
+
+extern "C" int mmg_selftest_sampler_events(const mmg_sampler *s, int *pool, int *free_idx, int *pending_idx)
+{
+    if (!s || !pool || !free_idx || !pending_idx) return fail(MMG_ERR_ARG, "NULL argument");
+    *pool = (int)s->ev_pool.size();
+    *free_idx = (int)s->ev_free.size();
+    *pending_idx = 0;
+    for (const auto &pr : s->ev_pending) *pending_idx += 2 + (pr[3] >= 0);
     return MMG_OK;
 }
 
@@ -484,16 +493,14 @@ extern "C" int mmg_sampler_get_trace(mmg_sampler *s, int chain, double *out)
     int rc = check_chain(s, chain);
     if (rc) return rc;
     if (!out) return fail(MMG_ERR_ARG, "NULL out");
-    if (!s->d_trace) return fail(MMG_ERR_STATE, "sampler was created with keep_trace == 0");
+    if (!s->d_trace.get()) return fail(MMG_ERR_STATE, "sampler was created with keep_trace == 0");
     HIP_TRY(hipSetDevice(s->device));
     const size_t n = s->p->n, S = (size_t)s->cfg.trace_len;
-    double *d_tmp = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_tmp, n * S * sizeof(double)));
-    launch_transpose(s->d_trace + (size_t)chain * S * n, d_tmp, (uint32_t)n, (uint32_t)S, s->p->d_int_of_ext, s->cur);
-    hipError_t e = hipStreamSynchronize(s->cur);
-    if (e == hipSuccess) e = hipMemcpy(out, d_tmp, n * S * sizeof(double), hipMemcpyDeviceToHost);
-    (void)hipFree(d_tmp);
-    if (e != hipSuccess) return fail(MMG_ERR_HIP, std::string("get_trace: ") + hipGetErrorString(e));
+    DevBuf<double> d_tmp;
+    HIP_TRY(d_tmp.alloc(n * S));
+    launch_transpose(s->d_trace.get() + (size_t)chain * S * n, d_tmp.get(), (uint32_t)n, (uint32_t)S, s->p->d_int_of_ext.get(), s->cur);
+    HIP_TRY(hipStreamSynchronize(s->cur));
+    HIP_TRY(hipMemcpy(out, d_tmp.get(), n * S * sizeof(double), hipMemcpyDeviceToHost));
     return MMG_OK;
 }
 
@@ -502,22 +509,20 @@ extern "C" int mmg_sampler_get_trace_rows(mmg_sampler *s, int chain, int first, 
     int rc = check_chain(s, chain);
     if (rc) return rc;
     if (!out || first < 0 || count < 0 || (int64_t)first + count > s->cfg.trace_len) return fail(MMG_ERR_ARG, "bad sample range");
-    if (!s->d_trace) return fail(MMG_ERR_STATE, "sampler was created with keep_trace == 0");
+    if (!s->d_trace.get()) return fail(MMG_ERR_STATE, "sampler was created with keep_trace == 0");
     HIP_TRY(hipSetDevice(s->device));
     const size_t n = s->p->n, S = (size_t)s->cfg.trace_len;
-    const double *src = s->d_trace + ((size_t)chain * S + (size_t)first) * n;
+    const double *src = s->d_trace.get() + ((size_t)chain * S + (size_t)first) * n;
     if (!s->p->renumbered() || count == 0) {
         HIP_TRY(hipStreamSynchronize(s->cur));
         HIP_TRY(hipMemcpy(out, src, (size_t)count * n * sizeof(double), hipMemcpyDeviceToHost));
         return MMG_OK;
     }
-    double *d_tmp = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_tmp, (size_t)count * n * sizeof(double)));
-    launch_gather_rows(src, d_tmp, (uint32_t)n, (uint32_t)count, 8, s->p->d_int_of_ext, s->cur);
-    hipError_t e = hipStreamSynchronize(s->cur);
-    if (e == hipSuccess) e = hipMemcpy(out, d_tmp, (size_t)count * n * sizeof(double), hipMemcpyDeviceToHost);
-    (void)hipFree(d_tmp);
-    if (e != hipSuccess) return fail(MMG_ERR_HIP, std::string("get_trace_rows: ") + hipGetErrorString(e));
+    DevBuf<double> d_tmp;
+    HIP_TRY(d_tmp.alloc((size_t)count * n));
+    launch_gather_rows(src, d_tmp.get(), (uint32_t)n, (uint32_t)count, 8, s->p->d_int_of_ext.get(), s->cur);
+    HIP_TRY(hipStreamSynchronize(s->cur));
+    HIP_TRY(hipMemcpy(out, d_tmp.get(), (size_t)count * n * sizeof(double), hipMemcpyDeviceToHost));
     return MMG_OK;
 }
 
@@ -529,24 +534,23 @@ extern "C" int mmg_sampler_get_trace_rows_done(mmg_sampler *s, int chain, int fi
     int rc = check_chain(s, chain);
     if (rc) return rc;
     if (!out || first < 0 || count < 0 || (int64_t)first + count > s->cfg.trace_len) return fail(MMG_ERR_ARG, "bad sample range");
-    if (!s->d_trace) return fail(MMG_ERR_STATE, "sampler was created with keep_trace == 0");
+    if (!s->d_trace.get()) return fail(MMG_ERR_STATE, "sampler was created with keep_trace == 0");
     if (count == 0) return MMG_OK;
     HIP_TRY(hipSetDevice(s->device));
     std::lock_guard<std::mutex> lock(s->reader_mu);
-    if (!s->reader) HIP_TRY(hipStreamCreateWithFlags(&s->reader, hipStreamNonBlocking));
+    if (!s->reader) HIP_TRY(s->reader.create(hipStreamNonBlocking));
     const size_t n = s->p->n, S = (size_t)s->cfg.trace_len;
-    const double *src = s->d_trace + ((size_t)chain * S + (size_t)first) * n;
+    const double *src = s->d_trace.get() + ((size_t)chain * S + (size_t)first) * n;
     if (s->p->renumbered()) {
         if (s->reader_cap < (size_t)count * n) {
-            if (s->d_reader_tmp) (void)hipFree(s->d_reader_tmp);
-            s->d_reader_tmp = nullptr; s->reader_cap = 0;
-            HIP_TRY(hipMalloc((void **)&s->d_reader_tmp, (size_t)count * n * sizeof(double)));
+            s->reader_cap = 0;
+            HIP_TRY(s->d_reader_tmp.alloc((size_t)count * n));
             s->reader_cap = (size_t)count * n;
         }
-        launch_gather_rows(src, s->d_reader_tmp, (uint32_t)n, (uint32_t)count, 8, s->p->d_int_of_ext, s->reader);
-        src = s->d_reader_tmp;
+        launch_gather_rows(src, s->d_reader_tmp.get(), (uint32_t)n, (uint32_t)count, 8, s->p->d_int_of_ext.get(), s->reader.get());
+        src = s->d_reader_tmp.get();
     }
-    const hipError_t e = s->reader_stage.copy_out(out, src, (size_t)count * n * sizeof(double), s->reader);
+    const hipError_t e = s->reader_stage.copy_out(out, src, (size_t)count * n * sizeof(double), s->reader.get());
     if (e != hipSuccess) return fail(MMG_ERR_HIP, std::string("get_trace_rows_done: ") + hipGetErrorString(e));
     return MMG_OK;
 }
@@ -558,7 +562,7 @@ extern "C" int mmg_sampler_get_mu(mmg_sampler *s, int chain, double *mu)
     if (!mu) return fail(MMG_ERR_ARG, "NULL out");
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipStreamSynchronize(s->cur));
-    return download_ext(s->p, s->d_mu + (size_t)chain * s->p->n, mu);
+    return download_ext(s->p, s->d_mu.get() + (size_t)chain * s->p->n, mu);
 }
 
 extern "C" int mmg_sampler_get_counts(mmg_sampler *s, int chain, int32_t *cnt)
@@ -569,7 +573,7 @@ extern "C" int mmg_sampler_get_counts(mmg_sampler *s, int chain, int32_t *cnt)
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipStreamSynchronize(s->cur));
     // between sample() and update() the live counts are the interesting ones
-    const int32_t *src = (s->sampled ? s->d_cnt : s->d_cnt_last) + (size_t)chain * s->p->n;
+    const int32_t *src = (s->sampled ? s->d_cnt.get() : s->d_cnt_last.get()) + (size_t)chain * s->p->n;
     return download_ext(s->p, src, cnt);
 }
 
@@ -580,8 +584,8 @@ extern "C" int mmg_sampler_get_moments(mmg_sampler *s, int chain, double *sum_lo
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipStreamSynchronize(s->cur));
     const size_t C = (size_t)s->cfg.n_chains, n = s->p->n;
-    if (sum_log && (rc = download_ext(s->p, s->d_mom + (size_t)chain * n, sum_log)) != MMG_OK) return rc;
-    if (sum_log2 && (rc = download_ext(s->p, s->d_mom + (C + (size_t)chain) * n, sum_log2)) != MMG_OK) return rc;
+    if (sum_log && (rc = download_ext(s->p, s->d_mom.get() + (size_t)chain * n, sum_log)) != MMG_OK) return rc;
+    if (sum_log2 && (rc = download_ext(s->p, s->d_mom.get() + (C + (size_t)chain) * n, sum_log2)) != MMG_OK) return rc;
     if (n_samples) *n_samples = s->n_kept;
     return MMG_OK;
 }
@@ -612,4 +616,4 @@ extern "C" int mmg_sampler_reset_timing(mmg_sampler *s)
     return MMG_OK;
 }
 
-extern "C" void mmg_sampler_destroy(mmg_sampler *s) { sampler_free(s); }
+extern "C" void mmg_sampler_destroy(mmg_sampler *s) { delete s; }
