@@ -3,9 +3,10 @@
 
 A "step" is one Gibbs sweep: K1 (per-row multinomial allocation + count scatter, the stream of the hit matrix; src/mmseq.cpp:857-891)
 + K2 (Gamma redraw + trace capture, :896-917) over the whole synthetic hit matrix, for every chain on the GPU.
-Headline workload = BASELINE.json's 50M-read / 200k-transcript shape (configs[2]/[3]), 1 chain per GPU; the other shapes the
-round-1 review asked for (config 2, 8 chains, uniform hits, rows kept in generator order, far-hit mixes) are measured in the same
-run and reported in the `extra` block of the same JSON line.
+Headline workload = BASELINE.json's 50M-read / 200k-transcript shape (configs[2]/[3]), 1 chain per GPU.  A plain run does only what
+the headline needs: set-up, warm-up, the timed steps, --dump-outputs, the JSON line.  --full adds everything else in the same run: the
+other shapes the round-1 review asked for (config 2, 8 chains, uniform hits, rows kept in generator order, far-hit mixes) and the EM
+sweeps, reported under `roofline` of the same JSON line; the CPU baseline; K1's HBM traffic measured live (below).
 
 HIP events bracket K1 and K2 on every --time-every-th step INSIDE the timed region, on the stream the kernels are launched on
 (default 4; the library attaches them to the launches -- hipExtLaunchKernel, the dispatch's own time stamps -- so that a timed step costs
@@ -14,10 +15,10 @@ the stream next to nothing); roofline.avg_launch_ms is the mean over those launc
 roofline (K1 = k_sample_sell, the dominant kernel; the same block for the chain-pair kernel and the EM kernel in `roofline_other`):
   bound        "hbm".  K1 is bound by the stream it reads: with the same stream served from the caches it runs 21 % faster
                (DESIGN.md section 4), and the instruction side (VALU issue) sits right behind it
-  traffic      HBM bytes per launch of K1, measured IN THIS RUN at --gpus 1: two short child runs of this script under rocprofv3, one
-               per counter (FETCH_SIZE, WRITE_SIZE; --kernel-trace --pmc only), while this process idles behind its timed region
-               (roofline.traffic_source says so; --no-live-pmc, no rocprofv3 on PATH, or a failed pass: the committed passes of this
-               exact kernel build instead -- profiles/pmc_counters.json, written by tools/pmc_summary.py, stamped with a hash of the
+  traffic      HBM bytes per launch of K1, with --full measured IN THIS RUN at --gpus 1: two short child runs of this script under
+               rocprofv3, one per counter (FETCH_SIZE, WRITE_SIZE; --kernel-trace --pmc only), while this process idles behind its timed
+               region (roofline.traffic_source says so; a plain run, --no-live-pmc, no rocprofv3 on PATH, or a failed pass: the committed
+               passes of this exact kernel build instead -- profiles/pmc_counters.json, written by tools/pmc_summary.py, stamped with a hash of the
                kernel sources and build flags; null if they changed since).  The other counters (VALU, LDS, wave cycles) and the
                chain-pair / EM blocks always come from the committed passes
   achieved     traffic / avg_launch_ms in GB/s;  peak 8000 GB/s (MI355X_MICROARCH.md);  frac = hbm_counter_frac = achieved / peak
@@ -31,6 +32,8 @@ roofline (K1 = k_sample_sell, the dominant kernel; the same block for the chain-
   python bench.py --gpus 1 --steps 256 --warmup 16
   python bench.py --gpus 1 --steps 256 --warmup 16 --dump-outputs DIR     (+ what the last timed step computed, DIR/<name>.npy: the
          inputs are seeded, so two builds of the project can be compared output for output)
+  python bench.py --gpus 1 --steps 256 --warmup 16 --full                 (+ side measurements, EM, CPU baseline, live K1 traffic; each
+         part can be left out with --no-extra / --no-cpu-baseline / --no-live-pmc, --only picks side measurements)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W            (one rank per GPU, RCCL)
 """
@@ -438,7 +441,8 @@ def compact(d, drop=()):
     return out
 
 
-def main():
+def parse_args(argv=None):
+    """The command line; without --full, the parts a plain run leaves out are switched off here."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=256)
@@ -452,17 +456,29 @@ def main():
     ap.add_argument("--time-every", type=int, default=4, help="HIP-event pairs around K1/K2 on every N-th step of the timed region "
                     "(1 = every step)")
     ap.add_argument("--settle-iters", type=int, default=256, help="iterations of a scratch chain before the warm-up steps (GPU clock ramp)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the side measurements")
-    ap.add_argument("--only", default="", help="comma-separated ids of the side measurements to run (default: all)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the side measurements and EM "
+                    "sweeps, the CPU baseline, K1's HBM traffic in child runs under rocprofv3 (at --gpus 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the side measurements")
+    ap.add_argument("--only", default="", help="comma-separated ids of the side measurements of --full to run (default: all)")
     ap.add_argument("--cpu-sample-rows", type=int, default=2_000_000, help="rows of the sample the CPU thread count is picked on")
     ap.add_argument("--cpu-iters", type=int, default=8, help="iterations of the CPU baseline on the full problem")
     ap.add_argument("--full-json", default="", help="also write the unabridged record (every field of every measurement) to this file")
-    ap.add_argument("--no-live-pmc", action="store_true", help="do not collect FETCH_SIZE / WRITE_SIZE of K1 in child runs under rocprofv3 "
-                    "(roofline.traffic then comes from the committed passes of the same kernel build)")
+    ap.add_argument("--no-live-pmc", action="store_true", help="--full without FETCH_SIZE / WRITE_SIZE of K1 in child runs under rocprofv3 "
+                    "(roofline.traffic then comes from the committed passes of the same kernel build, as in a plain run)")
     ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last one computed "
                     "(mu, counts, moments of every chain; at most 64 MB) to DIR/<name>.npy")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.only and not args.full:
+        ap.error("--only picks side measurements of a --full run")
+    if not args.full:
+        # a plain run: set-up, warm-up, the timed steps, the outputs and the line -- nothing the headline does not need
+        args.no_cpu_baseline = args.no_extra = args.no_live_pmc = True
+    return args
+
+
+def main():
+    args = parse_args()
 
     import numpy as np
     import torch
