@@ -78,7 +78,10 @@ extern "C" {
  *      Also version 8: in the GROUP-level hit graph of version 7 a group that shares rows with more than max(32, 8 x the median) other groups
  *      is a hub (version 7: max(256, ...), the transcript-level rule) and stays out of the traversal -- a gene whose repeat-bearing UTR
  *      collects reads of hundreds of genes no longer ties the paralogue families into one component.  Stored order and chain of problems
- *      with such groups differ from version 7. */
+ *      with such groups differ from version 7.
+ *      Additive in version 8, no bump (the chain's specification does not change): mmcollapse (mmg_collapse_*), mmdiff (mmg_diff_*), the
+ *      owners' self tests (MMG_OPT_FAIL_ALLOC, mmg_selftest_live, mmg_selftest_sampler_events) and the convergence diagnostics across
+ *      chains (mmg_convergence_*, MMG_OPT_CONV_SLAB). */
 /* Layout.  The model does not care about the order of rows or the numbering of transcripts (src/mmseq.cpp:399-418 uses
  * first-seen order for both); the kernels do: they keep a window of consecutive transcripts in LDS and want the 64 rows of a
  * wave to have equal lengths.  mmg_problem_create therefore stores the rows in a CANONICAL order of its own (sorted on the
@@ -361,6 +364,26 @@ int mmg_summary_get_proportions(mmg_summary *q, int kind, double *mean_prop, dou
 int mmg_summary_get_rows(mmg_summary *q, int kind, int first_sample, int n_samples, double *out);
 void mmg_summary_destroy(mmg_summary *q);
 
+/* ---- convergence across chains ------------------------------------------------------------------------------------------
+ * Per series the rank-normalized split R-hat and the bulk and tail effective sample sizes (Vehtari et al. 2021, as Stan and ArviZ
+ * report them; DESIGN.md section 11 states the definitions): every chain is cut in two halves (for odd trace lengths the middle draw is
+ * dropped), the pooled draws are ranked (ties: average rank) and mapped to normal scores.  rhat = fmax(R-hat of the scores, R-hat of
+ * the scores of the draws folded about the median); ess_bulk = ESS of the scores; ess_tail = fmin(ESS of I[x <= q05], ESS of
+ * I[x <= q95]).  NaN for a series whose draws are all equal.  Reruns are bit-identical.  Additive in ABI version 8. */
+typedef struct mmg_convergence mmg_convergence;
+/* After the chain (the call synchronises with the sampler, then works on a stream of its own and touches nothing of the sampler):
+ * every chain's trace of the sampler (keep_trace, trace_len >= 4), the series of every kind of mmg_summary_desc -- transcripts,
+ * isoforms without hits (simulated per chain: keyed (seed, chain c, id, sample)), identical sets and genes (sums of the members in the
+ * given order over chain c).  d->chain and the percentiles are ignored.  The results are kept on the host; no device memory is held
+ * after the call. */
+int mmg_convergence_create(mmg_sampler *s, const mmg_summary_desc *d, mmg_convergence **out);
+/* rhat, ess_bulk, ess_tail of the series of `kind` (MMG_SERIES_*), in the numbering of mmg_summary_get; any output may be NULL */
+int mmg_convergence_get(mmg_convergence *h, int kind, double *rhat, double *ess_bulk, double *ess_tail);
+void mmg_convergence_destroy(mmg_convergence *h);
+/* The same diagnostics of `count` series of traces from the host: traces[(c * S + s) * count + i] is draw s of chain c of series i. */
+int mmg_convergence_of_traces(int device, uint32_t n_chains, uint32_t S, uint32_t count, const double *traces, double *rhat, double *ess_bulk,
+                              double *ess_tail);
+
 /* ---- several GPUs of one node, one process (RCCL over xGMI) ----------------------------------------
  * The reference parallelises with OpenMP threads inside one process (src/mmseq.cpp:834-838, :864); here the unit is a device.
  * A group owns one RCCL communicator per device (ncclCommInitAll); sampler i of every call below must live on device i of the
@@ -420,7 +443,8 @@ enum {
     MMG_OPT_BIGK_SIDE_STREAM = 11, /* 0: k_sample_bigk on the sampler's stream, in front of the tile kernels instead of beside them                    */
     MMG_OPT_FAIL_ALLOC = 12,       /* v >= 0: the v-th acquisition of device memory, a stream or an event after this option is set (counted from 0) fails
                                       without reaching the runtime (error paths) */
-    MMG_OPT_COUNT_ = 13
+    MMG_OPT_CONV_SLAB = 13,        /* v >= 1: at most v series per slab of mmg_convergence_create / _of_traces (slab edges on small inputs)     */
+    MMG_OPT_COUNT_ = 14
 };
 int mmg_selftest_option(int option, int value);
 /* What the library holds: counts[3] = device buffers, streams, events (tests: every call gives back what it acquired). */

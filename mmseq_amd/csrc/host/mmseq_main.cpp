@@ -73,6 +73,8 @@ static void printUsage(ostream &out)
         << "                     over them (same results as on one device); with -chains >= gpus every device runs chains/gpus chains" << endl
         << "  -chains INT        independent Gibbs chains (default: 1); log_mu, sd and mcse pool all chains, traces are chain 0's" << endl
         << "  -em_one_device     with -gpus > 1 and one chain: run the EM on the first device alone instead of over the read shards" << endl
+        << "  -convergence       also write output_base.convergence, .identical.convergence and .gene.convergence: rank-normalized" << endl
+        << "                     split R-hat and bulk / tail effective sample sizes across the chains (one device only)" << endl
         << endl;
 }
 
@@ -94,7 +96,7 @@ static bool is_power_of_two(unsigned v) { return v != 0 && (v & (v - 1)) == 0; }
 
 // Command line: a table of options -- name, the variable it sets, how its value is read -- walked once.  Same flags, defaults,
 // messages and exit codes as the reference's loop at src/mmseq.cpp:206-276 (tests/test_cli.py holds them), plus -device / -gpus /
-// -chains / -em_one_device of this build.
+// -chains / -em_one_device / -convergence of this build.
 struct CliOption {
     const char *name;
     enum Kind { REAL, INT, FLAG, LIST, HELP, VERSION } kind;
@@ -363,7 +365,7 @@ int main(int argc, char **argv)
     bool debug = false;
     int device = 0, gpus = 1, chains = 1;
 
-    bool em_one_device = false;
+    bool em_one_device = false, convergence = false;
     vector<string> percentile_fields;
     const CliOption options[] = {
         {"-alpha", CliOption::REAL, &alpha},        {"-beta", CliOption::REAL, &beta},
@@ -373,6 +375,7 @@ int main(int argc, char **argv)
         {"-gpus", CliOption::INT, &gpus},           {"-chains", CliOption::INT, &chains},
         {"-percentiles", CliOption::LIST, &percentile_fields},
         {"-debug", CliOption::FLAG, &debug},        {"-em_one_device", CliOption::FLAG, &em_one_device},
+        {"-convergence", CliOption::FLAG, &convergence},
         {"-h", CliOption::HELP, nullptr},           {"-help", CliOption::HELP, nullptr},       {"--help", CliOption::HELP, nullptr},
         {"-v", CliOption::VERSION, nullptr},        {"-version", CliOption::VERSION, nullptr}, {"--version", CliOption::VERSION, nullptr},
     };
@@ -423,6 +426,11 @@ int main(int argc, char **argv)
     }
     if (gpus < 1 || chains < 1 || (gpus > 1 && chains > 1 && chains % gpus != 0)) {
         cerr << "Error: -gpus and -chains must be positive, and chains a multiple of gpus when both exceed 1.\n";
+        printUsage(cerr);
+        exit(1);
+    }
+    if (convergence && gpus > 1) { // the diagnostic reads every chain's trace on one device
+        cerr << "Error: -convergence needs every chain on one device: it cannot be combined with -gpus > 1.\n";
         printUsage(cerr);
         exit(1);
     }
@@ -1023,6 +1031,10 @@ int main(int argc, char **argv)
     map<string, uint32_t> headerIndexOf;
     for (size_t i = 0; i < nHeader; ++i) headerIndexOf[transcriptList[i]] = (uint32_t)i;
     map<string, uint32_t> simuIndex; // isoform without hits -> its simulated ("virtual") trace
+    // the series of the summary: isoforms without hits, identical sets and genes (their members: caller's transcripts or n + virtual index)
+    vector<uint64_t> vid, iptr(1, 0), gptr(1, 0);
+    vector<double> vscale;
+    vector<uint32_t> imem, gmem;
     {
         mmg_config cfg;
         memset(&cfg, 0, sizeof cfg);
@@ -1047,9 +1059,6 @@ int main(int argc, char **argv)
         smp = smps[0]; // traces and per-feature summaries come from chain 0 (every shard holds the whole chain)
     }
     {
-        vector<uint64_t> vid, iptr(1, 0), gptr(1, 0);
-        vector<double> vscale;
-        vector<uint32_t> imem, gmem;
         for (size_t v = 0; v < nI; ++v) {
             for (auto &name : identical_transcripts[v]) { const int32_t t = obs_of(name); if (t >= 0) imem.push_back((uint32_t)t); }
             iptr.push_back(imem.size());
@@ -1210,6 +1219,28 @@ int main(int argc, char **argv)
     //      are the per-series columns -- percentiles, log means, Sokal -- of which only the columns come back.
     MMG_TRY(mmg_summary_finish(summ));
     stage.mark("device summary");
+    // ---- convergence across the chains (-convergence): per series of the three tables R-hat, bulk and tail ESS, on the device
+    struct Conv { vector<double> rhat, ess_bulk, ess_tail; };
+    Conv cT, cV, cI, cG;
+    if (convergence) {
+        mmg_summary_desc cd;
+        memset(&cd, 0, sizeof cd);
+        cd.n_virtual = (uint32_t)vid.size(); cd.virtual_id = vid.data(); cd.virtual_scale = vscale.data();
+        cd.n_identical = (uint32_t)nI; cd.identical_ptr = iptr.data(); cd.identical_member = imem.data();
+        cd.n_genes = (uint32_t)nG; cd.gene_ptr = gptr.data(); cd.gene_member = gmem.data();
+        mmg_convergence *conv = nullptr;
+        MMG_TRY(mmg_convergence_create(smp, &cd, &conv));
+        auto fetch_conv = [&](int kind, size_t count, Conv &o) {
+            o.rhat.assign(max<size_t>(count, 1), NAN); o.ess_bulk.assign(max<size_t>(count, 1), NAN); o.ess_tail.assign(max<size_t>(count, 1), NAN);
+            MMG_TRY(mmg_convergence_get(conv, kind, o.rhat.data(), o.ess_bulk.data(), o.ess_tail.data()));
+        };
+        fetch_conv(MMG_SERIES_TRANSCRIPT, n, cT);
+        fetch_conv(MMG_SERIES_VIRTUAL, vid.size(), cV);
+        fetch_conv(MMG_SERIES_IDENTICAL, nI, cI);
+        fetch_conv(MMG_SERIES_GENE, nG, cG);
+        mmg_convergence_destroy(conv);
+        stage.mark("convergence diagnostics");
+    }
     // (the trace writer still reads rows of the sampler, the derived-trace writers rows of the summary: both are released once the
     // writers are done, behind the tables)
     auto release_device = [&]() {
@@ -1432,6 +1463,40 @@ int main(int argc, char **argv)
     ofs.close(); ofs.clear();
 
     gene_table.join();
+
+    // ---- the convergence tables: the rows of .mmseq, .identical.mmseq and .gene.mmseq, in their order, with their feature ids
+    if (convergence) {
+        auto conv_head = [&](ostream &o) {
+            o << "# chains " << chains << ", samples per chain " << trace_length << endl;
+            o << "feature_id\trhat\tess_bulk\tess_tail" << endl;
+        };
+        auto conv_row = [&](ostream &o, const Conv &c, size_t i) { o << "\t" << c.rhat[i] << "\t" << c.ess_bulk[i] << "\t" << c.ess_tail[i] << "\n"; };
+        ofs.open((output_base + ".convergence").c_str());
+        conv_head(ofs);
+        for (auto &name : transcriptList) {
+            const int32_t t = obs_of(name);
+            ofs << name;
+            if (t >= 0) conv_row(ofs, cT, (size_t)t);
+            else conv_row(ofs, cV, simu_of(name));
+        }
+        ofs.close(); ofs.clear();
+        ofs.open((output_base + ".identical.convergence").c_str());
+        conv_head(ofs);
+        for (size_t v = 0; v < nI; ++v) {
+            const vector<string> &set = identical_transcripts[v];
+            for (auto &name : set) { ofs << name; if (name.compare(set.back()) != 0) ofs << "+"; } // (the id of .identical.mmseq)
+            conv_row(ofs, cI, v);
+        }
+        ofs.close(); ofs.clear();
+        ofs.open((output_base + ".gene.convergence").c_str());
+        conv_head(ofs);
+        {
+            size_t g = 0;
+            for (auto &gt : gene2transcripts) { ofs << gt.first; conv_row(ofs, cG, g++); }
+        }
+        ofs.close(); ofs.clear();
+        stage.mark("convergence tables");
+    }
 
     cout << "done." << endl;
     cout << "Output files: " << endl

@@ -100,4 +100,17 @@ hipError_t layout_max_row_len(uint64_t m, const uint64_t *d_rp, uint32_t *max_le
 // of *n_list entries (empty / 0 without such rows or without multiplicities).  d_rp: the problem's row offsets (u32 or u64).
 hipError_t layout_bigk_rows(bool idx64, uint64_t m, const void *d_rp, const uint32_t *d_k, DevBuf<uint64_t> &d_list, uint64_t *n_list, hipStream_t s);
 
+// ---- post.hip: the convergence diagnostics across chains (conv_kernels.h) and the summary kernels they reuse (post_kernels.h)
+// k_virtual_traces / k_group_sums of the summary, unchanged (V[s * nv + v], G[s * ng + g])
+void launch_virtual_traces(uint64_t seed, uint32_t chain, uint32_t tag, double alpha, uint32_t nv, uint32_t S, const uint64_t *id, const double *scale,
+                           double *V, hipStream_t s);
+void launch_group_sums(uint32_t ng, uint32_t S, uint32_t n, uint32_t nv, const uint64_t *ptr, const uint32_t *member, const uint32_t *int_of_ext,
+                       const double *trace, const double *V, double *G, hipStream_t s);
+// out[(t * C + c) * S + s] = in[s * ld + col(t0 + t)], t < cnt (col null: the identity)
+void launch_conv_slab(const double *in, uint64_t ld, uint32_t t0, uint32_t cnt, uint32_t S, uint32_t C, uint32_t c, const uint32_t *col, double *out,
+                      hipStream_t s);
+// k_convergence over cnt series X[series][C][S]: in LDS while C S <= 8192, else in ws (2 PP words per workgroup, ws_groups workgroups)
+void launch_convergence(uint32_t cnt, uint32_t C, uint32_t S, const double *X, double inv_log10_p, double *rhat, double *ess_bulk, double *ess_tail,
+                        uint64_t *ws, uint32_t ws_groups, hipStream_t s);
+
 } // namespace mmg

@@ -1,6 +1,7 @@
 // post.hip -- device TU + host side of the mmg_summary_* entry points: the posterior summary of the resident Gibbs trace
 // (src/mmseq.cpp:927-1008, :1110-1227, :1235-1363; src/sokal.cc:33-87).  Kernels in post_kernels.h.
 #include "post_kernels.h"
+#include "conv_kernels.h"
 #include "mmg_host.h"
 #include "mmg_launch.h"
 
@@ -401,4 +402,37 @@ extern "C" int mmg_collapse_summarize(int device, uint32_t trace_len, uint32_t n
     HIP_TRY(hipMemcpy(tau, d_tau, (size_t)ng * 8, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(sokal_rc, d_rc, (size_t)ng * 4, hipMemcpyDeviceToHost));
     return MMG_OK;
+}
+
+// launchers of convergence.hip (mmg_launch.h)
+void mmg::launch_virtual_traces(uint64_t seed, uint32_t chain, uint32_t tag, double alpha, uint32_t nv, uint32_t S, const uint64_t *id, const double *scale,
+                                double *V, hipStream_t st)
+{
+    if (nv && S) hipLaunchKernelGGL(k_virtual_traces, dim3(blocks_of((uint64_t)nv * S)), dim3(256), 0, st, seed, chain, tag, alpha, nv, S, id, scale, V);
+}
+
+void mmg::launch_group_sums(uint32_t ng, uint32_t S, uint32_t n, uint32_t nv, const uint64_t *ptr, const uint32_t *member, const uint32_t *int_of_ext,
+                            const double *trace, const double *V, double *G, hipStream_t st)
+{
+    if (ng && S) hipLaunchKernelGGL(k_group_sums, dim3(blocks_of((uint64_t)ng * S)), dim3(256), 0, st, ng, S, n, nv, ptr, member, int_of_ext, trace, V, G);
+}
+
+void mmg::launch_conv_slab(const double *in, uint64_t ld, uint32_t t0, uint32_t cnt, uint32_t S, uint32_t C, uint32_t c, const uint32_t *col, double *out,
+                           hipStream_t st)
+{
+    if (cnt && S) hipLaunchKernelGGL(k_conv_slab, dim3((cnt + 31) / 32, (S + 31) / 32), dim3(256), 0, st, in, ld, t0, cnt, S, C, c, col, out);
+}
+
+void mmg::launch_convergence(uint32_t cnt, uint32_t C, uint32_t S, const double *X, double inv_log10_p, double *rhat, double *ess_bulk, double *ess_tail,
+                             uint64_t *ws, uint32_t ws_groups, hipStream_t st)
+{
+    if (!cnt) return;
+    const uint64_t cs = (uint64_t)C * S;
+#define CONV_IN_LDS(SMAX) hipLaunchKernelGGL((k_convergence<SMAX>), dim3(cnt), dim3(256), 0, st, cnt, C, S, X, inv_log10_p, rhat, ess_bulk, ess_tail, (uint64_t *)nullptr)
+    if (cs <= 1024) CONV_IN_LDS(1024);
+    else if (cs <= 2048) CONV_IN_LDS(2048);
+    else if (cs <= 4096) CONV_IN_LDS(4096);
+    else if (cs <= 8192) CONV_IN_LDS(8192);
+    else hipLaunchKernelGGL((k_convergence<0>), dim3(cnt < ws_groups ? cnt : ws_groups), dim3(256), 0, st, cnt, C, S, X, inv_log10_p, rhat, ess_bulk, ess_tail, ws);
+#undef CONV_IN_LDS
 }

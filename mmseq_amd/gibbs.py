@@ -443,6 +443,54 @@ class Summary:
             pass
 
 
+class Convergence:
+    """Convergence across the chains of a sampler (mmg_convergence_*): per series the rank-normalized split R-hat and the bulk and tail
+    effective sample sizes.  The series are those of Summary: transcripts, virtual isoforms (simulated per chain), identical sets and
+    genes (member lists as for Summary)."""
+
+    def __init__(self, sampler, virtual_id=(), virtual_scale=(), identical=(), genes=()):
+        from ._lib import SummaryDesc
+        self._lib = _lib.load()
+        vid = np.ascontiguousarray(virtual_id, np.uint64)
+        vsc = np.ascontiguousarray(virtual_scale, np.float64)
+        iptr, imem = _csr(identical)
+        gptr, gmem = _csr(genes)
+        self.counts = [sampler.n, vid.size, len(identical), len(genes)]
+        d = SummaryDesc(0, vid.size, _ptr(vid), _ptr(vsc), len(identical), _ptr(iptr), _ptr(imem), len(genes), _ptr(gptr), _ptr(gmem), 0, None)
+        h = C.c_void_p()
+        check(self._lib.mmg_convergence_create(sampler._h, C.byref(d), C.byref(h)))
+        self._h = h
+
+    def series(self, kind):
+        c = self.counts[kind]
+        r, eb, et = np.empty(c), np.empty(c), np.empty(c)
+        check(self._lib.mmg_convergence_get(self._h, kind, _ptr(r), _ptr(eb), _ptr(et)))
+        return dict(rhat=r, ess_bulk=eb, ess_tail=et)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.mmg_convergence_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def convergence_of_traces(traces, device=0):
+    """mmg_convergence_of_traces: traces[c, s, i] is draw s of chain c of series i (shape (C, S, count)).  Returns a dict of rhat,
+    ess_bulk and ess_tail, one value per series."""
+    tr = np.ascontiguousarray(traces, np.float64)
+    if tr.ndim != 3:
+        raise ValueError("traces must have shape (chains, samples, series)")
+    nc, S, cnt = tr.shape
+    r, eb, et = np.empty(cnt), np.empty(cnt), np.empty(cnt)
+    check(_lib.load().mmg_convergence_of_traces(int(device), nc, S, cnt, _ptr(tr), _ptr(r), _ptr(eb), _ptr(et)))
+    return dict(rhat=r, ess_bulk=eb, ess_tail=et)
+
+
 def em_shards_selftest(shards, mu0, sweeps):
     """mmg_selftest_em_shards: the sharded EM of mmg_group_em_create with all shards on one device (exchange by kernels).
     Returns (mu, loglik, repeated_passes)."""
@@ -471,7 +519,8 @@ def selftest_option(option, value):
 
 OPT = dict(sample_kernel=_lib.OPT_SAMPLE_KERNEL, force_idx64=_lib.OPT_FORCE_IDX64, sell_waves_per_cu=_lib.OPT_SELL_WAVES_PER_CU,
            em_kernel=_lib.OPT_EM_KERNEL, em_grid=_lib.OPT_EM_GRID, fuse_chains=_lib.OPT_FUSE_CHAINS, cnt_replicas=_lib.OPT_CNT_REPLICAS, group_fail=_lib.OPT_GROUP_FAIL, derive_order=_lib.OPT_DERIVE_ORDER,
-           wire_check=_lib.OPT_WIRE_CHECK, bigk_per_wave=_lib.OPT_BIGK_PER_WAVE, bigk_side_stream=_lib.OPT_BIGK_SIDE_STREAM)
+           wire_check=_lib.OPT_WIRE_CHECK, bigk_per_wave=_lib.OPT_BIGK_PER_WAVE, bigk_side_stream=_lib.OPT_BIGK_SIDE_STREAM,
+           conv_slab=_lib.OPT_CONV_SLAB)
 
 
 class options:
