@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../../include/mmgibbs.h"
+#include "stage_timer.hpp"
 
 using namespace std;
 
@@ -70,19 +71,6 @@ static bool readable(const string &path)
     fclose(f);
     return true;
 }
-
-struct StageTimer {
-    bool on = getenv("MMSEQ_TIMING") != nullptr;
-    double t0 = omp_get_wtime(), last = t0;
-    void mark(const char *what)
-    {
-        if (!on) return;
-        const double now = omp_get_wtime();
-        fprintf(stderr, "[timing] %-28s %8.3f s\n", what, now - last);
-        last = now;
-    }
-    void total() { if (on) fprintf(stderr, "[timing] %-28s %8.3f s\n", "total", omp_get_wtime() - t0); }
-};
 
 // what one sample's tables contribute (get_unidentifiable_transcripts, src/mmcollapse.cpp:117-396)
 struct Tables {

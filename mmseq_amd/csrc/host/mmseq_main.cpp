@@ -30,6 +30,7 @@
 #include <iostream>
 #include <limits>
 #include <map>
+#include <memory>
 #include <sstream>
 #include <string>
 #include <unordered_map>
@@ -39,6 +40,7 @@
 #include "hitsio.hpp"
 #include "huffenc.hpp"
 #include "numerics.hpp"
+#include "stage_timer.hpp"
 
 #ifndef MMSEQ_VERSION
 #define MMSEQ_VERSION "1.0.11-mi355x"
@@ -103,47 +105,71 @@ struct CliOption {
     void *target;
 };
 
-// the background writer of .k / .M (if any) finishes its files before the process leaves on a device error: the reference has
-// written both by then (src/mmseq.cpp:682-695), and exit() must not run under a thread that is still formatting
-static std::thread *g_background_writer = nullptr;
-// the thread that brings the HIP runtime up while the file is read: exit() under a thread that is still INSIDE the runtime's
-// initialisation tears the runtime down under its feet (found by tools/hitsio_fuzz.py: 7 of 800 runs on damaged headers ended in the
-// sanitizer's allocator instead of with exit code 1) -- every exit of the main thread waits for it
-static std::thread *g_device_warmup = nullptr;
-[[noreturn]] static void leave(int code)
-{
-    if (g_device_warmup && g_device_warmup->joinable()) g_device_warmup->join();
-    exit(code);
-}
-// Worker threads (the trace writers and their fetchers) never call exit(): exit() runs the atexit handlers and the HIP / RCCL
-// teardown under the main thread's feet, and two workers failing together would both join the background writer.  A worker RECORDS
-// its error (first one wins) and returns; the main thread sees the flag, stops the workers (g_stop_workers: wakes them, joins them)
-// and leaves with the message -- exit() on the main thread only.
-static std::atomic<bool> g_worker_failed{false};
-static std::mutex g_worker_mu;
-static std::string g_worker_msg;
-static std::function<void()> g_stop_workers; // set while worker threads of main() run: makes them return and joins them
-static bool worker_failed(int rc, const char *what)
-{
-    if (rc == 0) return false;
-    std::lock_guard<std::mutex> lk(g_worker_mu);
-    if (!g_worker_failed.load()) g_worker_msg = std::string(mmg_last_error()) + " (" + what + ")";
-    g_worker_failed.store(true);
-    return true;
-}
-[[noreturn]] static void main_thread_exit(const std::string &msg)
-{
-    cerr << "Error: " << msg << endl;
-    if (g_stop_workers) { auto f = g_stop_workers; g_stop_workers = nullptr; f(); }
-    if (g_background_writer && g_background_writer->joinable()) g_background_writer->join();
-    leave(1);
-}
+// The one error path.  A failure on the main thread prints its message where it happens and throws Exit; main() catches it and
+// returns the code.  Unwinding does the cleanup, in the reverse order of run()'s declarations: the trace writers are stopped and
+// joined (TraceWriters), the library handles destroyed, the .k / .M writer joined (the reference has written both by then,
+// src/mmseq.cpp:682-695) and last the device warm-up thread.  Exit never crosses an OpenMP region or leaves a thread's body.
+struct Exit { int code; };
+[[noreturn]] static void leave_with(const string &text) { cerr << text; throw Exit{1}; }
+[[noreturn]] static void fatal(const string &msg) { leave_with("Error: " + msg + "\n"); }
 #define MMG_TRY(expr)                                                                     \
     do {                                                                                  \
-        if ((expr) != 0) main_thread_exit(std::string(mmg_last_error()) + " (" + #expr + ")"); \
+        if ((expr) != 0) fatal(std::string(mmg_last_error()) + " (" + #expr + ")");        \
     } while (0)
-// in a worker thread: record and leave the enclosing function / lambda
-#define MMG_TRY_WORKER(expr) do { if (worker_failed((expr), #expr)) return; } while (0)
+
+// a library handle, destroyed with its *_destroy when its owner goes
+template <class T, void (*Destroy)(T *)> struct Destroyer { void operator()(T *p) const { Destroy(p); } };
+template <class T, void (*Destroy)(T *)> using Owned = unique_ptr<T, Destroyer<T, Destroy>>;
+using Problem = Owned<mmg_problem, mmg_problem_destroy>;
+using Group = Owned<mmg_group, mmg_group_destroy>;
+using Summary = Owned<mmg_summary, mmg_summary_destroy>;
+using Convergence = Owned<mmg_convergence, mmg_convergence_destroy>;
+// handles of one kind, one per device, destroyed together in order; reads as the array of raw handles the calls take
+template <class T, void (*Destroy)(T *)> struct HandleSet {
+    vector<T *> h;
+    explicit HandleSet(size_t count = 0) : h(count, nullptr) {}
+    HandleSet(HandleSet &&o) noexcept : h(std::move(o.h)) { o.h.clear(); }
+    ~HandleSet() { for (T *p : h) if (p) Destroy(p); }
+    T **data() { return h.data(); }
+    T *const *data() const { return h.data(); }
+    T *&operator[](size_t i) { return h[i]; }
+    T *operator[](size_t i) const { return h[i]; }
+    typename vector<T *>::const_iterator begin() const { return h.begin(); }
+    typename vector<T *>::const_iterator end() const { return h.end(); }
+};
+using Problems = HandleSet<mmg_problem, mmg_problem_destroy>;
+using Samplers = HandleSet<mmg_sampler, mmg_sampler_destroy>;
+using Ems = HandleSet<mmg_em, mmg_em_destroy>;
+
+// a thread joined when it goes out of scope: on success, and while an Exit unwinds
+struct JoiningThread {
+    thread t;
+    JoiningThread() = default;
+    template <class F> explicit JoiningThread(F &&f) : t(std::forward<F>(f)) {}
+    JoiningThread(JoiningThread &&) = default;
+    ~JoiningThread() { join(); }
+    void join() { if (t.joinable()) t.join(); }
+};
+
+// The trace writers and what they share with the main thread.  Worker threads (the writers and their fetchers) never throw and never
+// call exit(): exit() runs the atexit handlers and the HIP / RCCL teardown under the main thread's feet.  A worker RECORDS its error
+// (first one wins) and returns; the main thread sees it (check) and leaves with the message.  Going out of scope -- on success after
+// finish(), or while an Exit unwinds -- stops the workers (flag, wake) and joins them, before the summary and samplers they read go.
+struct TraceWriters {
+    mutex mu;
+    condition_variable cv;
+    int samples_ready = 0;        // samples whose rows may be fetched (trace and derived traces)
+    atomic<bool> stop{false};     // a worker failed or the main thread is leaving: every worker returns
+    string failure;               // the first worker's error
+    vector<JoiningThread> threads; // (the last member: joined before the rest goes)
+    ~TraceWriters() { { lock_guard<mutex> lk(mu); stop.store(true); } cv.notify_all(); }
+    void record(const string &msg) { { lock_guard<mutex> lk(mu); if (failure.empty()) failure = msg; stop.store(true); } cv.notify_all(); }
+    bool failed(int rc, const char *what) { if (rc != 0) record(string(mmg_last_error()) + " (" + what + ")"); return rc != 0; }
+    void wait_for(int upto) { unique_lock<mutex> lk(mu); cv.wait(lk, [&] { return samples_ready >= upto || stop.load(); }); }
+    void publish(int ready) { { lock_guard<mutex> lk(mu); samples_ready = ready; } cv.notify_all(); }
+    void check() { string msg; { lock_guard<mutex> lk(mu); msg = failure; } if (!msg.empty()) fatal(msg); } // (main thread)
+    void finish() { for (auto &t : threads) t.join(); check(); }
+};
 
 // gzip text sink: ONE standard gzip member whose deflate stream is produced chunk-wise in parallel.
 // Every chunk is compressed independently as raw deflate and closed with a sync flush (byte-aligned,
@@ -180,14 +206,17 @@ struct GzText {
     uLong crc = 0;
     unsigned long long total = 0;
     string pending; // small writes are gathered here and compressed on flush
-    explicit GzText(const string &path)
+    explicit GzText(const string &path) // (a file that cannot be opened: !ok(), the caller reports it)
     {
         f = fopen(path.c_str(), "wb");
-        if (!f) { cerr << "Error: cannot open " << path << " for writing.\n"; exit(1); }
+        if (!f) return;
         const unsigned char hdr[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 3};
         fwrite(hdr, 1, 10, f);
         crc = crc32(0L, Z_NULL, 0);
     }
+    GzText(const GzText &) = delete;
+    ~GzText() { if (f) fclose(f); }
+    bool ok() const { return f != nullptr; }
     static string deflate_chunk(const string &in, bool last)
     {
         if (!last && gzip_strategy() == Z_HUFFMAN_ONLY) { // the default: host/huffenc.hpp, the same kind of block several times faster
@@ -254,9 +283,8 @@ struct GzText {
 // (device gather + copy), the formatting and compression of this round -- in parallel over pieces of <= 32 k columns of a line
 // (~ 290 KB of text each, deflated independently and joined with sync flushes) -- and the write of the previous round's bytes.
 static void write_trace_rows(GzText &gz, int n_lines, size_t n_cols, const function<void(int, int, double *)> &fetch,
-                             const function<bool(size_t)> &keep, int threads = 0)
+                             const function<bool(size_t)> &keep, const atomic<bool> &stop, int threads)
 {
-    if (threads < 1) threads = max(1, omp_get_max_threads());
     vector<char> mask(n_cols);
     size_t n_keep = 0;
     for (size_t c = 0; c < n_cols; ++c) n_keep += (mask[c] = keep(c) ? 1 : 0);
@@ -272,7 +300,7 @@ static void write_trace_rows(GzText &gz, int n_lines, size_t n_cols, const funct
     fetch(0, (int)min<size_t>(lines_per_round, (size_t)n_lines), buf[0].data());
     thread writer;
     vector<string> comp_prev; // owned by the writer thread while it runs
-    for (int l0 = 0, r = 0; l0 < n_lines && !g_worker_failed.load(); l0 += (int)lines_per_round, ++r) {
+    for (int l0 = 0, r = 0; l0 < n_lines && !stop.load(); l0 += (int)lines_per_round, ++r) {
         const int cnt = (int)min<size_t>(lines_per_round, (size_t)(n_lines - l0));
         const int next0 = l0 + cnt, next_cnt = (int)min<size_t>(lines_per_round, (size_t)max(0, n_lines - next0));
         thread fetcher;
@@ -312,20 +340,6 @@ static void write_trace_rows(GzText &gz, int n_lines, size_t n_cols, const funct
     if (writer.joinable()) writer.join();
 }
 
-// Stage timings on stderr when MMSEQ_TIMING is set (not part of the reference's output)
-struct StageTimer {
-    bool on = getenv("MMSEQ_TIMING") != nullptr;
-    double t0 = omp_get_wtime(), last = t0;
-    void mark(const char *what)
-    {
-        if (!on) return;
-        const double now = omp_get_wtime();
-        fprintf(stderr, "[timing] %-28s %8.3f s\n", what, now - last);
-        last = now;
-    }
-    void total() { if (on) fprintf(stderr, "[timing] %-28s %8.3f s\n", "total", omp_get_wtime() - t0); }
-};
-
 // CPUs this process may actually use: a container's CFS quota (cgroup v2 cpu.max, v1 cpu.cfs_quota_us) is invisible to OpenMP, which
 // then starts one thread per core of the host -- 256 threads throttled to 16 CPUs' worth of time on the GPU boxes here.
 static int cpu_quota()
@@ -344,38 +358,38 @@ static int cpu_quota()
     return (int)max<long long>(1, (quota + period - 1) / period);
 }
 
-int main(int argc, char **argv)
-{
-    StageTimer stage;
-    if (!getenv("OMP_NUM_THREADS")) { // an explicit thread count is the user's (src/mmseq.cpp:323 prints it); otherwise respect the quota
-        const int q = cpu_quota();
-        if (q > 0 && q < omp_get_max_threads()) omp_set_num_threads(q);
-    }
-    const int max_threads = omp_get_max_threads();
+// the sample count of every trace (src/mmseq.cpp:187: gibbs_iter / gibbs_ss)
+constexpr int trace_length = 1024;
 
+struct Options {
     // DEFAULT PARAMETER VALUES (src/mmseq.cpp:183-205)
     double alpha = 0.1, beta = 0.1;
     int max_em_iter = 1000;
     double epsilon = 0.1;
     int gibbs_iter = 16384;
-    const int trace_length = 1024;
     int gibbs_ss = gibbs_iter / trace_length;
     vector<double> percentiles = {5.0, 25.0, 50.0, 75.0, 95.0};
     int seed = 1234;
     bool debug = false;
     int device = 0, gpus = 1, chains = 1;
-
     bool em_one_device = false, convergence = false;
+    string hits_file, output_base;
+};
+
+// the flags and their checks; a bad command line leaves here (no thread runs yet)
+static Options parse_options(int argc, char **argv)
+{
+    Options o;
     vector<string> percentile_fields;
     const CliOption options[] = {
-        {"-alpha", CliOption::REAL, &alpha},        {"-beta", CliOption::REAL, &beta},
-        {"-max_em_iter", CliOption::INT, &max_em_iter}, {"-epsilon", CliOption::REAL, &epsilon},
-        {"-gibbs_iter", CliOption::INT, &gibbs_iter},   {"-gibbs_ss", CliOption::INT, &gibbs_ss},
-        {"-seed", CliOption::INT, &seed},           {"-device", CliOption::INT, &device},
-        {"-gpus", CliOption::INT, &gpus},           {"-chains", CliOption::INT, &chains},
+        {"-alpha", CliOption::REAL, &o.alpha},        {"-beta", CliOption::REAL, &o.beta},
+        {"-max_em_iter", CliOption::INT, &o.max_em_iter}, {"-epsilon", CliOption::REAL, &o.epsilon},
+        {"-gibbs_iter", CliOption::INT, &o.gibbs_iter},   {"-gibbs_ss", CliOption::INT, &o.gibbs_ss},
+        {"-seed", CliOption::INT, &o.seed},           {"-device", CliOption::INT, &o.device},
+        {"-gpus", CliOption::INT, &o.gpus},           {"-chains", CliOption::INT, &o.chains},
         {"-percentiles", CliOption::LIST, &percentile_fields},
-        {"-debug", CliOption::FLAG, &debug},        {"-em_one_device", CliOption::FLAG, &em_one_device},
-        {"-convergence", CliOption::FLAG, &convergence},
+        {"-debug", CliOption::FLAG, &o.debug},        {"-em_one_device", CliOption::FLAG, &o.em_one_device},
+        {"-convergence", CliOption::FLAG, &o.convergence},
         {"-h", CliOption::HELP, nullptr},           {"-help", CliOption::HELP, nullptr},       {"--help", CliOption::HELP, nullptr},
         {"-v", CliOption::VERSION, nullptr},        {"-version", CliOption::VERSION, nullptr}, {"--version", CliOption::VERSION, nullptr},
     };
@@ -383,7 +397,7 @@ int main(int argc, char **argv)
     int pos = 1;                                   // next word of the command line
     for (;;) {
         const CliOption *opt = nullptr;
-        if (pos < argc) for (const CliOption &o : options) if (strcmp(argv[pos], o.name) == 0) opt = &o;
+        if (pos < argc) for (const CliOption &op : options) if (strcmp(argv[pos], op.name) == 0) opt = &op;
         if (!opt) {                                // not an option: exactly the two positional arguments must be left
             if (argc - pos == 2) break;
             if (pos < argc && argv[pos][0] == '-') usage_error(string("Error: unrecognised option ") + argv[pos] + ".");
@@ -400,425 +414,415 @@ int main(int argc, char **argv)
         pos += 2;
     }
     if (!percentile_fields.empty()) {
-        percentiles.resize(percentile_fields.size());
+        o.percentiles.resize(percentile_fields.size());
         for (size_t i = 0; i < percentile_fields.size(); i++) {
             const double v = strtod(percentile_fields[i].c_str(), NULL);
             if (!(v >= 0 && v <= 100)) { cerr << "Percentiles must be in (0,100)\n"; exit(1); }
-            percentiles[i] = v;
+            o.percentiles[i] = v;
         }
     }
-    const vector<string> arguments = {argv[pos], argv[pos + 1]};   // hits_file, output_base
-    if (gibbs_ss == 0 || gibbs_iter % gibbs_ss != 0) { // :278 (gibbs_ss == 0 is a division by zero there)
-        cerr << "Error: gibbs_iter must be divisible by gibbs_ss.\n";
-        printUsage(cerr);
-        exit(1);
-    }
-    gibbs_ss = gibbs_iter / trace_length; // :284 -- the user's -gibbs_ss is overwritten, as in the reference
-    if (gibbs_iter <= 0 || trace_length <= 0) {
-        cerr << "Error: no. of iteratons or trace length <= 0. Possible integer overflow - is gibbs_iter too high?\n";
-        printUsage(cerr);
-        exit(1);
-    }
-    if (gibbs_ss < 1 || gibbs_iter % trace_length != 0) { // the reference overruns its trace / divides by zero here (App. A)
-        cerr << "Error: gibbs_iter must be a positive multiple of " << trace_length << ".\n";
-        printUsage(cerr);
-        exit(1);
-    }
-    if (gpus < 1 || chains < 1 || (gpus > 1 && chains > 1 && chains % gpus != 0)) {
-        cerr << "Error: -gpus and -chains must be positive, and chains a multiple of gpus when both exceed 1.\n";
-        printUsage(cerr);
-        exit(1);
-    }
-    if (convergence && gpus > 1) { // the diagnostic reads every chain's trace on one device
-        cerr << "Error: -convergence needs every chain on one device: it cannot be combined with -gpus > 1.\n";
-        printUsage(cerr);
-        exit(1);
-    }
-    if (!is_power_of_two((unsigned)trace_length)) {
-        cerr << "Error: gibbs_iter/gibbs_ss must be a power of 2.\n";
-        printUsage(cerr);
-        exit(1);
-    }
-    const string hits_file = arguments[0];
-    const string output_base(arguments[1]);
+    o.hits_file = argv[pos];
+    o.output_base = argv[pos + 1];
+    auto check = [](bool ok, const string &msg) { if (!ok) { cerr << msg; printUsage(cerr); exit(1); } };
+    check(o.gibbs_ss != 0 && o.gibbs_iter % o.gibbs_ss == 0, "Error: gibbs_iter must be divisible by gibbs_ss.\n"); // :278 (gibbs_ss == 0 is a division by zero there)
+    o.gibbs_ss = o.gibbs_iter / trace_length; // :284 -- the user's -gibbs_ss is overwritten, as in the reference
+    check(o.gibbs_iter > 0 && trace_length > 0, "Error: no. of iteratons or trace length <= 0. Possible integer overflow - is gibbs_iter too high?\n");
+    // the reference overruns its trace / divides by zero here (App. A)
+    check(o.gibbs_ss >= 1 && o.gibbs_iter % trace_length == 0, "Error: gibbs_iter must be a positive multiple of " + to_string(trace_length) + ".\n");
+    check(o.gpus >= 1 && o.chains >= 1 && !(o.gpus > 1 && o.chains > 1 && o.chains % o.gpus != 0),
+          "Error: -gpus and -chains must be positive, and chains a multiple of gpus when both exceed 1.\n");
+    // the diagnostic reads every chain's trace on one device
+    check(!(o.convergence && o.gpus > 1), "Error: -convergence needs every chain on one device: it cannot be combined with -gpus > 1.\n");
+    check(is_power_of_two((unsigned)trace_length), "Error: gibbs_iter/gibbs_ss must be a power of 2.\n");
+    return o;
+}
 
-    HitsfileReader hitsfileReader(hits_file);
-
-    cout << "Running mmseq with parameters:\n"
-         << "  alpha:         " << alpha << endl
-         << "  beta:          " << beta << endl
-         << "  max_em_iter:   " << max_em_iter << endl
-         << "  epsilon:       " << epsilon << endl
-         << "  gibbs_iter:    " << gibbs_iter << endl
-         << "  gibbs_ss:      " << gibbs_ss << endl
-         << "  seed[0]:       " << seed << endl
-         << "  debug:         " << debug << endl
-         << "  threads:       " << max_threads << endl
-         << "  device:        " << device << " (HIP, libmmgibbs ABI " << mmg_abi_version() << ")" << endl
-         << "  gpus:          " << gpus << endl
-         << "  chains:        " << chains << endl;
-
-    // The HIP runtime, the device context and the library's code object are brought up while the hits file is read (they are first
-    // needed at the device problem build, where they used to cost about two seconds of an otherwise idle GPU): one tiny kernel
-    // launch on a thread of its own.  Its result is ignored -- a device that cannot be used is reported by mmg_problem_create.
-    std::thread device_warmup([device]() {
-        const uint32_t ctr[4] = {0, 0, 0, 0}, key[2] = {0, 0};
-        uint32_t out[6];
-        (void)mmg_selftest_philox(device, ctr, key, out);
-    });
-    g_device_warmup = &device_warmup;
-    struct WarmupJoiner { std::thread &t; ~WarmupJoiner() { if (t.joinable()) t.join(); g_device_warmup = nullptr; } } device_warmup_join{device_warmup};
-
-    // ---- header (src/mmseq.cpp:332-379)
+// ---- header (src/mmseq.cpp:332-379)
+struct Header {
     map<string, double> sidLen;
     map<string, int> sidSeqLen;
     vector<string> transcriptList;
     map<string, vector<string>> gene2transcripts;
     vector<vector<string>> identical_transcripts;
-    hitsfileReader.readHeader(&transcriptList, &sidLen, &sidSeqLen, &gene2transcripts, &identical_transcripts);
-
     map<string, string> transcript2gene;
+    // (lookups that never insert: the table writers run in several threads; a name the header did not describe reads as 0, which
+    // is what the maps' operator[] would have inserted)
+    double len_of(const string &name) const { auto it = sidLen.find(name); return it == sidLen.end() ? 0.0 : it->second; }
+    int seqlen_of(const string &name) const { auto it = sidSeqLen.find(name); return it == sidSeqLen.end() ? 0 : it->second; }
+    size_t gene_size_of(const string &name) const
     {
-        vector<string> transcriptListGI;
-        for (auto &g : gene2transcripts)
-            for (auto &t : g.second) {
-                if (transcript2gene.count(t) > 0) {
-                    cerr << "Error: transcripts must be nested within genes in GeneIsoforms metadata.\n";
-                    leave(1);
-                }
-                transcriptListGI.push_back(t);
-                transcript2gene[t] = g.first;
-            }
-        vector<string> a = transcriptList, b = transcriptListGI;
-        sort(a.begin(), a.end());
-        sort(b.begin(), b.end());
-        if ((size_t)(unique(a.begin(), a.end()) - a.begin()) != transcriptList.size()) {
-            cerr << "Error: duplicate transcripts in @TranscriptMetaData entries.\n";
-            leave(1);
-        }
-        if ((size_t)(unique(b.begin(), b.end()) - b.begin()) != transcriptListGI.size()) {
-            cerr << "Error: duplicate transcripts in @GeneIsoforms entries.\n";
-            leave(1);
-        }
-        for (auto &t : transcriptList)
-            if (transcript2gene.count(t) == 0) {
-                cerr << "Error: " << t << " does not belong to a gene in the @GeneIsoforms header entries.\n";
-                leave(1);
-            }
+        auto tg = transcript2gene.find(name);
+        auto it = gene2transcripts.find(tg == transcript2gene.end() ? string() : tg->second);
+        return it == gene2transcripts.end() ? (size_t)0 : it->second.size();
     }
-    const size_t nHeader = transcriptList.size();
+};
 
-    // ---- READ LOOP (src/mmseq.cpp:395-441): transcript index = first-seen order, row = first-seen hit set
-    vector<int32_t> hdr2obs(nHeader, -1); // header index -> observed index
-    vector<uint32_t> obs2hdr;             // indexSid
+static Header read_header(HitsfileReader &reader)
+{
+    Header h;
+    reader.readHeader(&h.transcriptList, &h.sidLen, &h.sidSeqLen, &h.gene2transcripts, &h.identical_transcripts);
+    vector<string> transcriptListGI;
+    for (auto &g : h.gene2transcripts)
+        for (auto &t : g.second) {
+            if (h.transcript2gene.count(t) > 0) leave_with("Error: transcripts must be nested within genes in GeneIsoforms metadata.\n");
+            transcriptListGI.push_back(t);
+            h.transcript2gene[t] = g.first;
+        }
+    vector<string> a = h.transcriptList, b = transcriptListGI;
+    sort(a.begin(), a.end());
+    sort(b.begin(), b.end());
+    if ((size_t)(unique(a.begin(), a.end()) - a.begin()) != h.transcriptList.size())
+        leave_with("Error: duplicate transcripts in @TranscriptMetaData entries.\n");
+    if ((size_t)(unique(b.begin(), b.end()) - b.begin()) != transcriptListGI.size())
+        leave_with("Error: duplicate transcripts in @GeneIsoforms entries.\n");
+    for (auto &t : h.transcriptList)
+        if (h.transcript2gene.count(t) == 0) leave_with("Error: " + t + " does not belong to a gene in the @GeneIsoforms header entries.\n");
+    return h;
+}
+
+// the collapsed hits: one row per distinct hit set (first-seen order), its columns the observed transcripts it hits
+struct Hits {
+    vector<uint32_t> obs2hdr;             // indexSid: observed index -> header index
     vector<int> doublehits;
     vector<uint32_t> k;                   // multiplicity per hit set
-    vector<uint64_t> row_ptr(1, 0);       // hit sets in first-seen order
+    vector<uint64_t> row_ptr = {0};       // hit sets in first-seen order
     vector<uint32_t> col_idx;
     long long numbermappedreads = 0;
-    {
-        // hit set -> row: open-addressing table keyed by a 64-bit hash of the sorted set; an entry is (upper hash half, row id), a
-        // candidate whose tag matches is confirmed against the stored row itself, so there is no per-set key allocation
-        // (src/mmseq.cpp:395-441 keeps a map<vector<int>,int> and regrows M).  The stage is bound by cache misses (one table line
-        // per read, the stored row for a repeat): the slot of a read a dozen ahead is prefetched, and the table starts at the size
-        // the file suggests (a record is >= 16 compressed bytes) instead of being rebuilt at every doubling.
-        constexpr uint64_t EMPTY = ~0ull;
-        size_t table_size = 1u << 16;
-        {
-            struct stat st_;
-            const uint64_t fsz = stat(hits_file.c_str(), &st_) == 0 ? (uint64_t)st_.st_size : 0;
-            while (table_size < fsz / 16 && table_size < (1ull << 31)) table_size <<= 1;
-        }
-        vector<uint64_t> table(table_size, EMPTY);
-        vector<uint64_t> row_hash;
-        {
-            // The arrays of the hit sets grow to GIGABYTES at 50 M reads (4 GB of column indices): grown by doubling they are copied
-            // 8 GB worth and fault in twice their final pages -- on the thread every other stage waits for.  Address space is
-            // reserved from the file's size instead (a binary record of c hits is >= 16 compressed bytes and inflates about 2.5 x;
-            // untouched pages cost nothing); a reservation the system refuses is simply not made.
-            struct stat st_;
-            const uint64_t fsz = stat(hits_file.c_str(), &st_) == 0 ? (uint64_t)st_.st_size : 0;
-            try {
-                col_idx.reserve((size_t)min<uint64_t>(fsz * 3 / 4, 3ull << 30));
-                const size_t rows = (size_t)min<uint64_t>(fsz / 24, 1ull << 28);
-                row_ptr.reserve(rows + 1); row_hash.reserve(rows); k.reserve(rows);
-                // ... and is advised to come in huge pages: 5 GB first touched on this thread are 1.2 M page faults otherwise
-                auto huge = [](void *p, size_t bytes) {
-                    const uintptr_t a = ((uintptr_t)p + 4095) & ~(uintptr_t)4095, e = ((uintptr_t)p + bytes) & ~(uintptr_t)4095;
-                    if (e > a) (void)madvise((void *)a, e - a, MADV_HUGEPAGE);
-                };
-                huge(col_idx.data(), col_idx.capacity() * 4); huge(row_ptr.data(), row_ptr.capacity() * 8);
-                huge(row_hash.data(), row_hash.capacity() * 8); huge(k.data(), k.capacity() * 4);
-            } catch (const std::bad_alloc &) {}
-        }
-        auto grow = [&]() {
-            vector<uint64_t> bigger(table.size() * 2, EMPTY);
-            const size_t mask = bigger.size() - 1;
-            for (uint32_t r = 0; r < (uint32_t)row_hash.size(); ++r) {
-                size_t s = (size_t)row_hash[r] & mask;
-                while (bigger[s] != EMPTY) s = (s + 1) & mask;
-                bigger[s] = (row_hash[r] & 0xffffffff00000000ull) | r;
-            }
-            table.swap(bigger);
+    uint32_t n() const { return (uint32_t)obs2hdr.size(); }
+    uint64_t m() const { return k.size(); }
+};
+
+// ---- READ LOOP (src/mmseq.cpp:395-441): transcript index = first-seen order, row = first-seen hit set
+static Hits ingest(HitsfileReader &hitsfileReader, const string &hits_file, size_t nHeader, bool timing)
+{
+    Hits H;
+    vector<uint32_t> &obs2hdr = H.obs2hdr, &k = H.k, &col_idx = H.col_idx;
+    vector<uint64_t> &row_ptr = H.row_ptr;
+    vector<int32_t> hdr2obs(nHeader, -1); // header index -> observed index
+    // hit set -> row: open-addressing table keyed by a 64-bit hash of the sorted set; an entry is (upper hash half, row id), a
+    // candidate whose tag matches is confirmed against the stored row itself, so there is no per-set key allocation
+    // (src/mmseq.cpp:395-441 keeps a map<vector<int>,int> and regrows M).  The stage is bound by cache misses (one table line
+    // per read, the stored row for a repeat): the slot of a read a dozen ahead is prefetched, and the table starts at the size
+    // the file suggests (a record is >= 16 compressed bytes) instead of being rebuilt at every doubling.
+    constexpr uint64_t EMPTY = ~0ull;
+    size_t table_size = 1u << 16;
+    struct stat st_;
+    const uint64_t fsz = stat(hits_file.c_str(), &st_) == 0 ? (uint64_t)st_.st_size : 0;
+    while (table_size < fsz / 16 && table_size < (1ull << 31)) table_size <<= 1;
+    vector<uint64_t> table(table_size, EMPTY);
+    vector<uint64_t> row_hash;
+    // The arrays of the hit sets grow to GIGABYTES at 50 M reads (4 GB of column indices): grown by doubling they are copied
+    // 8 GB worth and fault in twice their final pages -- on the thread every other stage waits for.  Address space is
+    // reserved from the file's size instead (a binary record of c hits is >= 16 compressed bytes and inflates about 2.5 x;
+    // untouched pages cost nothing); a reservation the system refuses is simply not made.
+    try {
+        col_idx.reserve((size_t)min<uint64_t>(fsz * 3 / 4, 3ull << 30));
+        const size_t rows = (size_t)min<uint64_t>(fsz / 24, 1ull << 28);
+        row_ptr.reserve(rows + 1); row_hash.reserve(rows); k.reserve(rows);
+        // ... and is advised to come in huge pages: 5 GB first touched on this thread are 1.2 M page faults otherwise
+        auto huge = [](void *p, size_t bytes) {
+            const uintptr_t a = ((uintptr_t)p + 4095) & ~(uintptr_t)4095, e = ((uintptr_t)p + bytes) & ~(uintptr_t)4095;
+            if (e > a) (void)madvise((void *)a, e - a, MADV_HUGEPAGE);
         };
-        // Four stages over a ring of blocks of reads, each stage its own thread(s): (1) the reader -- inflate (a thread of its own inside
-        // hitsio) + record decode, strictly sequential (src/hitsio.hpp:77-79); (2) first-seen transcript numbering (:399-408),
-        // sequential as well; (3) NSORT threads, alternate blocks: every read's hit set sorted and freed of repeats, its hash -- the
-        // longest stage at 50 M reads; (4) this thread: the hit-set table.
-        struct Block { vector<uint32_t> len, idx, dups; vector<uint64_t> hash; bool last = false; };
-        // (round 5: with the file inflated by several threads and the records parsed in place, the two sorters of round 4 became the
-        // pace of the pipeline -- reader and numberer both waited 4.7 s of a 6.3 s read: four, over a ring twice as deep)
-        constexpr int NB = 16, NSORT = 4;
-        Block blocks[NB];
-        int state[NB] = {0}; // 0: free for the reader, 1: decoded, 2: numbered, 3: prepared for the table
-        mutex mtx;
-        condition_variable cv;
-        atomic<uint32_t> n_seen{0}; // transcripts numbered so far (progress line only)
-        double waited[4] = {0.0, 0.0, 0.0, 0.0}; // seconds a stage spent waiting for a block (MMSEQ_TIMING: which stage bounds the pipeline)
-        auto wait_for = [&](int b, int want, int stage_id) {
-            const double t0 = omp_get_wtime();
-            { unique_lock<mutex> lk(mtx); cv.wait(lk, [&] { return state[b] == want; }); }
-            if (stage_id >= 0) waited[stage_id] += omp_get_wtime() - t0;
-        };
-        auto set_state = [&](int b, int v) { { lock_guard<mutex> lk(mtx); state[b] = v; } cv.notify_all(); };
-        thread producer([&]() {
-            bool more = true;
-            for (int b = 0; more; b = (b + 1) % NB) {
-                wait_for(b, 0, 0);
-                Block &B = blocks[b];
-                B.len.clear(); B.idx.clear();
-                more = hitsfileReader.readReadMapRecordsBulk(B.len, B.idx, 65536); // the read names are not used (:395-441)
-                B.last = !more;
-                set_state(b, 1);
-            }
-        });
-        thread numberer([&]() {
-            bool last = false;
-            for (int b = 0; !last; b = (b + 1) % NB) {
-                wait_for(b, 1, 1);
-                Block &B = blocks[b];
-                last = B.last;
-                for (uint32_t &x : B.idx) {
-                    const uint32_t hidx = x;
-                    if (hidx >= nHeader) {
-                        cerr << "Error: a read maps to a transcript that has no @TranscriptMetaData entry (no length).\n";
-                        hits_die(); // (a pipeline thread: no static destructors under the other threads)
-                    }
-                    if (hdr2obs[hidx] < 0) {
-                        hdr2obs[hidx] = (int32_t)obs2hdr.size(); obs2hdr.push_back(hidx);
-                        n_seen.store((uint32_t)obs2hdr.size(), memory_order_relaxed);
-                    }
-                    x = (uint32_t)hdr2obs[hidx];
-                }
-                set_state(b, 2);
-            }
-        });
-        atomic<int> last_block{-1}; // index of the block that ends the file, once known
-        vector<thread> sorters;
-        for (int w = 0; w < NSORT; ++w)
-            sorters.emplace_back([&, w]() {
-                for (int b = w;; b = (b + NSORT) % NB) {
-                    { // this sorter's next block, or the end of the file in the other sorter's hands
-                        unique_lock<mutex> lk(mtx);
-                        cv.wait(lk, [&] { return state[b] == 2 || last_block.load() >= 0; });
-                        if (state[b] != 2) return;
-                    }
-                    Block &B = blocks[b];
-                    B.hash.resize(B.len.size());
-                    B.dups.clear();
-                    size_t at = 0, out = 0;
-                    for (size_t r = 0; r < B.len.size(); ++r) {
-                        uint32_t *c = B.idx.data() + out; // the set is written over the block's own indices (never ahead of the read position)
-                        const uint32_t nin = B.len[r];
-                        for (uint32_t q = 0; q < nin; ++q) c[q] = B.idx[at++];
-                        sort(c, c + nin);
-                        uint32_t nu = 0;
-                        for (uint32_t q = 0; q < nin; ++q) {
-                            if (nu && c[nu - 1] == c[q]) B.dups.push_back(c[q]); // a transcript listed twice for one read (:421-424)
-                            else c[nu++] = c[q];
-                        }
-                        uint64_t h = 0x9E3779B97F4A7C15ull ^ (uint64_t)nu;
-                        for (uint32_t q = 0; q < nu; ++q) { h ^= c[q]; h *= 0xff51afd7ed558ccdull; h ^= h >> 32; }
-                        B.hash[r] = h;
-                        B.len[r] = nu;
-                        out += nu;
-                    }
-                    const bool was_last = B.last;
-                    if (was_last) last_block.store(b);
-                    set_state(b, 3);
-                    if (was_last) return;
-                }
-            });
-        vector<uint32_t> all_dups;
+        huge(col_idx.data(), col_idx.capacity() * 4); huge(row_ptr.data(), row_ptr.capacity() * 8);
+        huge(row_hash.data(), row_hash.capacity() * 8); huge(k.data(), k.capacity() * 4);
+    } catch (const std::bad_alloc &) {}
+    auto grow = [&]() {
+        vector<uint64_t> bigger(table.size() * 2, EMPTY);
+        const size_t mask = bigger.size() - 1;
+        for (uint32_t r = 0; r < (uint32_t)row_hash.size(); ++r) {
+            size_t s = (size_t)row_hash[r] & mask;
+            while (bigger[s] != EMPTY) s = (s + 1) & mask;
+            bigger[s] = (row_hash[r] & 0xffffffff00000000ull) | r;
+        }
+        table.swap(bigger);
+    };
+    // Four stages over a ring of blocks of reads, each stage its own thread(s): (1) the reader -- inflate (a thread of its own inside
+    // hitsio) + record decode, strictly sequential (src/hitsio.hpp:77-79); (2) first-seen transcript numbering (:399-408),
+    // sequential as well; (3) NSORT threads, alternate blocks: every read's hit set sorted and freed of repeats, its hash -- the
+    // longest stage at 50 M reads; (4) this thread: the hit-set table.
+    struct Block { vector<uint32_t> len, idx, dups; vector<uint64_t> hash; bool last = false; };
+    // (round 5: with the file inflated by several threads and the records parsed in place, the two sorters of round 4 became the
+    // pace of the pipeline -- reader and numberer both waited 4.7 s of a 6.3 s read: four, over a ring twice as deep)
+    constexpr int NB = 16, NSORT = 4;
+    Block blocks[NB];
+    int state[NB] = {0}; // 0: free for the reader, 1: decoded, 2: numbered, 3: prepared for the table
+    mutex mtx;
+    condition_variable cv;
+    atomic<uint32_t> n_seen{0}; // transcripts numbered so far (progress line only)
+    double waited[4] = {0.0, 0.0, 0.0, 0.0}; // seconds a stage spent waiting for a block (MMSEQ_TIMING: which stage bounds the pipeline)
+    auto wait_for = [&](int b, int want, int stage_id) {
+        const double t0 = omp_get_wtime();
+        { unique_lock<mutex> lk(mtx); cv.wait(lk, [&] { return state[b] == want; }); }
+        if (stage_id >= 0) waited[stage_id] += omp_get_wtime() - t0;
+    };
+    auto set_state = [&](int b, int v) { { lock_guard<mutex> lk(mtx); state[b] = v; } cv.notify_all(); };
+    thread producer([&]() {
+        bool more = true;
+        for (int b = 0; more; b = (b + 1) % NB) {
+            wait_for(b, 0, 0);
+            Block &B = blocks[b];
+            B.len.clear(); B.idx.clear();
+            more = hitsfileReader.readReadMapRecordsBulk(B.len, B.idx, 65536); // the read names are not used (:395-441)
+            B.last = !more;
+            set_state(b, 1);
+        }
+    });
+    thread numberer([&]() {
         bool last = false;
         for (int b = 0; !last; b = (b + 1) % NB) {
-            wait_for(b, 3, 3);
-            const Block &B = blocks[b];
+            wait_for(b, 1, 1);
+            Block &B = blocks[b];
             last = B.last;
-            all_dups.insert(all_dups.end(), B.dups.begin(), B.dups.end());
-            size_t at = 0;
-            for (size_t r = 0; r < B.len.size(); ++r) {
-                numbermappedreads++;
-                const uint32_t *comb = B.idx.data() + at;
-                const uint32_t nc = B.len[r];
-                at += nc;
-                const uint64_t h = B.hash[r];
-                const size_t mask = table.size() - 1;
-                if (r + 12 < B.len.size()) __builtin_prefetch(&table[(size_t)B.hash[r + 12] & mask]);
-                size_t s = (size_t)h & mask;
-                uint32_t row = 0xffffffffu;
-                for (;; s = (s + 1) & mask) {
-                    const uint64_t e = table[s];
-                    if (e == EMPTY) break;
-                    if ((e ^ h) >> 32) continue; // another set's tag
-                    const uint32_t rr = (uint32_t)e;
-                    if (row_hash[rr] == h && row_ptr[rr + 1] - row_ptr[rr] == nc && equal(comb, comb + nc, col_idx.begin() + (ptrdiff_t)row_ptr[rr])) { row = rr; break; }
+            for (uint32_t &x : B.idx) {
+                const uint32_t hidx = x;
+                if (hidx >= nHeader) {
+                    cerr << "Error: a read maps to a transcript that has no @TranscriptMetaData entry (no length).\n";
+                    hits_die(); // (a pipeline thread: no static destructors under the other threads)
                 }
-                if (row == 0xffffffffu) {
-                    row = (uint32_t)k.size();
-                    if ((row & 0xffff) == 0)
-                        cout << "Found " << n_seen.load(memory_order_relaxed) << " transcripts in " << row << " transcript combinations.\r" << flush;
-                    table[s] = (h & 0xffffffff00000000ull) | row;
-                    row_hash.push_back(h);
-                    k.push_back(0);
-                    col_idx.insert(col_idx.end(), comb, comb + nc);
-                    row_ptr.push_back(col_idx.size());
-                    if ((uint64_t)k.size() * 2 > table.size()) grow();
+                if (hdr2obs[hidx] < 0) {
+                    hdr2obs[hidx] = (int32_t)obs2hdr.size(); obs2hdr.push_back(hidx);
+                    n_seen.store((uint32_t)obs2hdr.size(), memory_order_relaxed);
                 }
-                k[row]++;
+                x = (uint32_t)hdr2obs[hidx];
             }
-            set_state(b, 0);
+            set_state(b, 2);
         }
-        numberer.join();
-        cv.notify_all();
-        for (auto &t : sorters) t.join();
-        doublehits.assign(obs2hdr.size(), 0);
-        for (uint32_t o : all_dups) doublehits[o]++;
-        if (stage.on) fprintf(stderr, "[timing] ingest stages waited: decode %.1f s, numbering %.1f s, table %.1f s (the sort + hash stage is the rest)\n", waited[0], waited[1], waited[3]);
-        producer.join();
-        cout << "Found " << obs2hdr.size() << " transcripts in " << k.size() << " transcript combinations." << endl;
-    }
-    const uint32_t n = (uint32_t)obs2hdr.size();
-    const uint64_t m = k.size();
-    if (n == 0 || m == 0) { cerr << "Error: no reads with transcript hits found in the hits file.\n"; leave(1); }
-    auto sid = [&](uint32_t t) -> const string & { return transcriptList[obs2hdr[t]]; };
-    auto obs_of = [&](const string &name) -> int32_t { // sidIndex lookup by name
-        static map<string, int32_t> cache;
-        if (cache.empty()) for (uint32_t t = 0; t < n; ++t) cache[sid(t)] = (int32_t)t;
-        auto it = cache.find(name);
-        return it == cache.end() ? -1 : it->second;
-    };
-
-    stage.mark("read hits file + collapse");
-    // ---- l[t] (src/mmseq.cpp:593-608)
-    vector<double> l(n);
-    for (uint32_t t = 0; t < n; t++) {
-        if (sidLen.count(sid(t)) == 0) { cerr << "Error: transcript '" << sid(t) << "' has no length.\n"; leave(1); }
-        l[t] = (double)sidLen[sid(t)] * (double)numbermappedreads / 1000000000.0;
-        if (l[t] <= 0) { cerr << "Error: transcript '" << sid(t) << "' has a length of zero.\n"; leave(1); }
-    }
-
-    // ---- start values and unique hits (src/mmseq.cpp:610-638) come from the device once the problem is there
-    //      (mmg_problem_start_values: the shares k_i / |row i| summed EXACTLY in fixed point -- the reference adds them in floating point
-    //      in the order it read the file, so its start value depends on that order in the last bits; this one is a function of the hit
-    //      sets).  The 100-bin histogram of shared counts is only ever written by -debug (.sharedcounts): a host pass, then.
-    vector<vector<int>> counts_shared;
-    vector<double> mu(n, 0.0);
-    vector<int32_t> unique_hits(n, 0);
-    if (debug) {
-        counts_shared.assign(n, vector<int>(100, 0));
-#pragma omp parallel num_threads(max(1, min(8, omp_get_max_threads() / 2))) // every thread reads the whole hit list: more only adds traffic
-        {
-            const uint64_t nth = (uint64_t)omp_get_num_threads(), tid = (uint64_t)omp_get_thread_num();
-            const uint32_t lo = (uint32_t)((uint64_t)n * tid / nth), hi = (uint32_t)((uint64_t)n * (tid + 1) / nth);
-            if (lo < hi)
-                for (uint64_t i = 0; i < m; ++i) {
-                    const uint64_t b = row_ptr[i], e = row_ptr[i + 1];
-                    const int L = (int)(e - b);
-                    for (uint64_t j = b; j < e; ++j) {
-                        const uint32_t c = col_idx[j];
-                        if (c - lo < hi - lo) counts_shared[c][min(L, 100) - 1] += (int)k[i];
-                    }
+    });
+    atomic<int> last_block{-1}; // index of the block that ends the file, once known
+    vector<thread> sorters;
+    for (int w = 0; w < NSORT; ++w)
+        sorters.emplace_back([&, w]() {
+            for (int b = w;; b = (b + NSORT) % NB) {
+                { // this sorter's next block, or the end of the file in the other sorter's hands
+                    unique_lock<mutex> lk(mtx);
+                    cv.wait(lk, [&] { return state[b] == 2 || last_block.load() >= 0; });
+                    if (state[b] != 2) return;
                 }
+                Block &B = blocks[b];
+                B.hash.resize(B.len.size());
+                B.dups.clear();
+                size_t at = 0, out = 0;
+                for (size_t r = 0; r < B.len.size(); ++r) {
+                    uint32_t *c = B.idx.data() + out; // the set is written over the block's own indices (never ahead of the read position)
+                    const uint32_t nin = B.len[r];
+                    for (uint32_t q = 0; q < nin; ++q) c[q] = B.idx[at++];
+                    sort(c, c + nin);
+                    uint32_t nu = 0;
+                    for (uint32_t q = 0; q < nin; ++q) {
+                        if (nu && c[nu - 1] == c[q]) B.dups.push_back(c[q]); // a transcript listed twice for one read (:421-424)
+                        else c[nu++] = c[q];
+                    }
+                    uint64_t h = 0x9E3779B97F4A7C15ull ^ (uint64_t)nu;
+                    for (uint32_t q = 0; q < nu; ++q) { h ^= c[q]; h *= 0xff51afd7ed558ccdull; h ^= h >> 32; }
+                    B.hash[r] = h;
+                    B.len[r] = nu;
+                    out += nu;
+                }
+                const bool was_last = B.last;
+                if (was_last) last_block.store(b);
+                set_state(b, 3);
+                if (was_last) return;
+            }
+        });
+    vector<uint32_t> all_dups;
+    bool last = false;
+    for (int b = 0; !last; b = (b + 1) % NB) {
+        wait_for(b, 3, 3);
+        const Block &B = blocks[b];
+        last = B.last;
+        all_dups.insert(all_dups.end(), B.dups.begin(), B.dups.end());
+        size_t at = 0;
+        for (size_t r = 0; r < B.len.size(); ++r) {
+            H.numbermappedreads++;
+            const uint32_t *comb = B.idx.data() + at;
+            const uint32_t nc = B.len[r];
+            at += nc;
+            const uint64_t h = B.hash[r];
+            const size_t mask = table.size() - 1;
+            if (r + 12 < B.len.size()) __builtin_prefetch(&table[(size_t)B.hash[r + 12] & mask]);
+            size_t s = (size_t)h & mask;
+            uint32_t row = 0xffffffffu;
+            for (;; s = (s + 1) & mask) {
+                const uint64_t e = table[s];
+                if (e == EMPTY) break;
+                if ((e ^ h) >> 32) continue; // another set's tag
+                const uint32_t rr = (uint32_t)e;
+                if (row_hash[rr] == h && row_ptr[rr + 1] - row_ptr[rr] == nc && equal(comb, comb + nc, col_idx.begin() + (ptrdiff_t)row_ptr[rr])) { row = rr; break; }
+            }
+            if (row == 0xffffffffu) {
+                row = (uint32_t)k.size();
+                if ((row & 0xffff) == 0)
+                    cout << "Found " << n_seen.load(memory_order_relaxed) << " transcripts in " << row << " transcript combinations.\r" << flush;
+                table[s] = (h & 0xffffffff00000000ull) | row;
+                row_hash.push_back(h);
+                k.push_back(0);
+                col_idx.insert(col_idx.end(), comb, comb + nc);
+                row_ptr.push_back(col_idx.size());
+                if ((uint64_t)k.size() * 2 > table.size()) grow();
+            }
+            k[row]++;
         }
+        set_state(b, 0);
     }
+    numberer.join();
+    cv.notify_all();
+    for (auto &t : sorters) t.join();
+    H.doublehits.assign(obs2hdr.size(), 0);
+    for (uint32_t o : all_dups) H.doublehits[o]++;
+    if (timing) fprintf(stderr, "[timing] ingest stages waited: decode %.1f s, numbering %.1f s, table %.1f s (the sort + hash stage is the rest)\n", waited[0], waited[1], waited[3]);
+    producer.join();
+    cout << "Found " << obs2hdr.size() << " transcripts in " << k.size() << " transcript combinations." << endl;
+    if (H.n() == 0 || H.m() == 0) leave_with("Error: no reads with transcript hits found in the hits file.\n");
+    return H;
+}
 
-    stage.mark("l");
-    // ---- unique hits to identical sets and genes: O(nnz) form of src/uh.cpp:3-26
-    vector<int> identical_unique_hits(identical_transcripts.size(), 0), gene_unique_hits(gene2transcripts.size(), 0);
+// the observed transcripts by index (sid, indexSid of src/mmseq.cpp) and by name (sidIndex; -1: no hits) -- built once after the
+// read, read by the stages after it (some of them from several threads)
+struct Observed {
+    vector<string> names;
+    unordered_map<string, int32_t> index;
+    Observed(const Header &hdr, const Hits &hits)
     {
-        cerr << "Counting unique hits to sets of identical transcripts...";
-        vector<vector<uint32_t>> t2sets(n);
-        for (size_t v = 0; v < identical_transcripts.size(); ++v)
-            for (auto &name : identical_transcripts[v]) {
-                const int32_t t = obs_of(name);
-                if (t >= 0) t2sets[t].push_back((uint32_t)v);
-            }
-        // rows in parallel, integer counts per thread summed at the end (the sums do not depend on the split)
-        const int uh_threads = max(1, omp_get_max_threads());
-        int64_t empty_rows_k = 0;
-        {
-            vector<vector<int>> part((size_t)uh_threads, vector<int>(identical_unique_hits.size(), 0));
-#pragma omp parallel num_threads(uh_threads) reduction(+ : empty_rows_k)
-            {
-                vector<int> &mine = part[(size_t)omp_get_thread_num()];
-                vector<uint32_t> cand, tmp;
-#pragma omp for schedule(static)
-                for (int64_t i = 0; i < (int64_t)m; ++i) {
-                    const uint64_t b = row_ptr[i], e = row_ptr[i + 1];
-                    if (b == e) { empty_rows_k += (int64_t)k[i]; continue; } // an empty row counts for every group
-                    if (t2sets[col_idx[b]].empty()) continue;
-                    cand = t2sets[col_idx[b]];
-                    for (uint64_t j = b + 1; j < e && !cand.empty(); ++j) {
-                        tmp.clear();
-                        for (uint32_t s : cand)
-                            if (find(t2sets[col_idx[j]].begin(), t2sets[col_idx[j]].end(), s) != t2sets[col_idx[j]].end()) tmp.push_back(s);
-                        cand.swap(tmp);
-                    }
-                    sort(cand.begin(), cand.end());
-                    cand.erase(unique(cand.begin(), cand.end()), cand.end());
-                    for (uint32_t s : cand) mine[s] += (int)k[i];
-                }
-            }
-            for (auto &pt : part) for (size_t v = 0; v < pt.size(); ++v) identical_unique_hits[v] += pt[v];
-            for (auto &x : identical_unique_hits) x += (int)empty_rows_k;
+        names.reserve(hits.n());
+        index.reserve(hits.n());
+        for (uint32_t t = 0; t < hits.n(); ++t) {
+            names.push_back(hdr.transcriptList[hits.obs2hdr[t]]);
+            index[names.back()] = (int32_t)t;
         }
-        cerr << "done." << endl;
-        cerr << "Counting unique hits to genes...";
-        map<string, int> gene2index;
-        { int g = 0; for (auto &gt : gene2transcripts) gene2index[gt.first] = g++; }
-        vector<int> t2g(n);
-        for (uint32_t t = 0; t < n; ++t) t2g[t] = gene2index[transcript2gene[sid(t)]];
-        {
-            vector<vector<int>> part((size_t)uh_threads, vector<int>(gene_unique_hits.size(), 0));
-#pragma omp parallel num_threads(uh_threads)
-            {
-                vector<int> &mine = part[(size_t)omp_get_thread_num()];
-#pragma omp for schedule(static)
-                for (int64_t i = 0; i < (int64_t)m; ++i) {
-                    const uint64_t b = row_ptr[i], e = row_ptr[i + 1];
-                    if (b == e) continue;
-                    const int g = t2g[col_idx[b]];
-                    bool uniq = true;
-                    for (uint64_t j = b + 1; j < e; ++j) if (t2g[col_idx[j]] != g) { uniq = false; break; }
-                    if (uniq) mine[g] += (int)k[i];
-                }
-            }
-            for (auto &pt : part) for (size_t g = 0; g < pt.size(); ++g) gene_unique_hits[g] += pt[g];
-            for (auto &x : gene_unique_hits) x += (int)empty_rows_k;
-        }
-        cerr << "done." << endl;
     }
+    int32_t of(const string &name) const { auto it = index.find(name); return it == index.end() ? -1 : it->second; }
+};
 
-    stage.mark("unique hits (sets, genes)");
-    // ---- .k and .M (src/mmseq.cpp:682-695): 14 GB of text at 50 M reads, written by a thread of its own while the device builds the
-    //      problem and runs EM and Gibbs (the arrays it reads are not touched again; joined before the run ends).  Its formatting
-    //      threads leave three CPUs of the container's quota alone: with all of them busy the quota runs out and the main thread is
-    //      throttled with them -- the upload of the matrix (4 GB of pageable memory through the runtime's staging copies) took 2.8 s
-    //      instead of 0.3 s, and an EM sweep (a kernel and a read-back) 8 ms instead of 1.3.
-    ofstream ofs;
+// ---- l[t] (src/mmseq.cpp:593-608)
+static vector<double> effective_lengths(const Header &hdr, const Hits &hits)
+{
+    vector<double> l(hits.n());
+    for (uint32_t t = 0; t < hits.n(); t++) {
+        const string &sid = hdr.transcriptList[hits.obs2hdr[t]];
+        if (hdr.sidLen.count(sid) == 0) leave_with("Error: transcript '" + sid + "' has no length.\n");
+        l[t] = hdr.sidLen.at(sid) * (double)hits.numbermappedreads / 1000000000.0;
+        if (l[t] <= 0) leave_with("Error: transcript '" + sid + "' has a length of zero.\n");
+    }
+    return l;
+}
+
+// ---- start values and unique hits (src/mmseq.cpp:610-638) come from the device once the problem is there
+//      (mmg_problem_start_values: the shares k_i / |row i| summed EXACTLY in fixed point -- the reference adds them in floating point
+//      in the order it read the file, so its start value depends on that order in the last bits; this one is a function of the hit
+//      sets).  The 100-bin histogram of shared counts is only ever written by -debug (.sharedcounts): a host pass, then.
+static vector<vector<int>> shared_counts(const Hits &hits)
+{
+    const uint32_t n = hits.n();
+    const uint64_t m = hits.m();
+    vector<vector<int>> counts_shared(n, vector<int>(100, 0));
+#pragma omp parallel num_threads(max(1, min(8, omp_get_max_threads() / 2))) // every thread reads the whole hit list: more only adds traffic
+    {
+        const uint64_t nth = (uint64_t)omp_get_num_threads(), tid = (uint64_t)omp_get_thread_num();
+        const uint32_t lo = (uint32_t)((uint64_t)n * tid / nth), hi = (uint32_t)((uint64_t)n * (tid + 1) / nth);
+        if (lo < hi)
+            for (uint64_t i = 0; i < m; ++i) {
+                const uint64_t b = hits.row_ptr[i], e = hits.row_ptr[i + 1];
+                const int L = (int)(e - b);
+                for (uint64_t j = b; j < e; ++j) {
+                    const uint32_t c = hits.col_idx[j];
+                    if (c - lo < hi - lo) counts_shared[c][min(L, 100) - 1] += (int)hits.k[i];
+                }
+            }
+    }
+    return counts_shared;
+}
+
+struct UniqueHits {
+    vector<int> identical, gene;
+    vector<int32_t> transcript;   // (from the device, with the start values)
+};
+
+// ---- unique hits to identical sets and genes: O(nnz) form of src/uh.cpp:3-26
+static UniqueHits count_unique_hits(const Header &hdr, const Hits &hits, const Observed &obs)
+{
+    const uint32_t n = hits.n();
+    const uint64_t m = hits.m();
+    const vector<uint64_t> &row_ptr = hits.row_ptr;
+    const vector<uint32_t> &col_idx = hits.col_idx, &k = hits.k;
+    UniqueHits uh;
+    uh.identical.assign(hdr.identical_transcripts.size(), 0);
+    uh.gene.assign(hdr.gene2transcripts.size(), 0);
+    cerr << "Counting unique hits to sets of identical transcripts...";
+    vector<vector<uint32_t>> t2sets(n);
+    for (size_t v = 0; v < hdr.identical_transcripts.size(); ++v)
+        for (auto &name : hdr.identical_transcripts[v]) {
+            const int32_t t = obs.of(name);
+            if (t >= 0) t2sets[t].push_back((uint32_t)v);
+        }
+    // rows in parallel, integer counts per thread summed at the end (the sums do not depend on the split)
+    const int uh_threads = max(1, omp_get_max_threads());
+    int64_t empty_rows_k = 0;
+    {
+        vector<vector<int>> part((size_t)uh_threads, vector<int>(uh.identical.size(), 0));
+#pragma omp parallel num_threads(uh_threads) reduction(+ : empty_rows_k)
+        {
+            vector<int> &mine = part[(size_t)omp_get_thread_num()];
+            vector<uint32_t> cand, tmp;
+#pragma omp for schedule(static)
+            for (int64_t i = 0; i < (int64_t)m; ++i) {
+                const uint64_t b = row_ptr[i], e = row_ptr[i + 1];
+                if (b == e) { empty_rows_k += (int64_t)k[i]; continue; } // an empty row counts for every group
+                if (t2sets[col_idx[b]].empty()) continue;
+                cand = t2sets[col_idx[b]];
+                for (uint64_t j = b + 1; j < e && !cand.empty(); ++j) {
+                    tmp.clear();
+                    for (uint32_t s : cand)
+                        if (find(t2sets[col_idx[j]].begin(), t2sets[col_idx[j]].end(), s) != t2sets[col_idx[j]].end()) tmp.push_back(s);
+                    cand.swap(tmp);
+                }
+                sort(cand.begin(), cand.end());
+                cand.erase(unique(cand.begin(), cand.end()), cand.end());
+                for (uint32_t s : cand) mine[s] += (int)k[i];
+            }
+        }
+        for (auto &pt : part) for (size_t v = 0; v < pt.size(); ++v) uh.identical[v] += pt[v];
+        for (auto &x : uh.identical) x += (int)empty_rows_k;
+    }
+    cerr << "done." << endl;
+    cerr << "Counting unique hits to genes...";
+    map<string, int> gene2index;
+    { int g = 0; for (auto &gt : hdr.gene2transcripts) gene2index[gt.first] = g++; }
+    vector<int> t2g(n);
+    for (uint32_t t = 0; t < n; ++t) t2g[t] = gene2index[hdr.transcript2gene.at(obs.names[t])];
+    {
+        vector<vector<int>> part((size_t)uh_threads, vector<int>(uh.gene.size(), 0));
+#pragma omp parallel num_threads(uh_threads)
+        {
+            vector<int> &mine = part[(size_t)omp_get_thread_num()];
+#pragma omp for schedule(static)
+            for (int64_t i = 0; i < (int64_t)m; ++i) {
+                const uint64_t b = row_ptr[i], e = row_ptr[i + 1];
+                if (b == e) continue;
+                const int g = t2g[col_idx[b]];
+                bool uniq = true;
+                for (uint64_t j = b + 1; j < e; ++j) if (t2g[col_idx[j]] != g) { uniq = false; break; }
+                if (uniq) mine[g] += (int)k[i];
+            }
+        }
+        for (auto &pt : part) for (size_t g = 0; g < pt.size(); ++g) uh.gene[g] += pt[g];
+        for (auto &x : uh.gene) x += (int)empty_rows_k;
+    }
+    cerr << "done." << endl;
+    return uh;
+}
+
+// ---- .k and .M (src/mmseq.cpp:682-695): 14 GB of text at 50 M reads, written by a thread of its own while the device builds the
+//      problem and runs EM and Gibbs (the arrays it reads are not touched again; joined before the run ends).  Its formatting
+//      threads leave three CPUs of the container's quota alone: with all of them busy the quota runs out and the main thread is
+//      throttled with them -- the upload of the matrix (4 GB of pageable memory through the runtime's staging copies) took 2.8 s
+//      instead of 0.3 s, and an EM sweep (a kernel and a read-back) 8 ms instead of 1.3.
+static JoiningThread start_km_writer(const string &output_base, const Hits &hits, const Observed &obs)
+{
     const int km_threads = max(1, omp_get_max_threads() - 3);
-    std::thread km_writer([&, m, n, km_threads]() {   // integer tables: chunks of rows formatted in parallel (to_chars), written in order
+    return JoiningThread([&hits, &obs, output_base, km_threads]() { // integer tables: chunks of rows formatted in parallel (to_chars), written in order
+        const uint64_t m = hits.m();
+        const uint32_t n = hits.n();
         ofstream ofs;
         auto write_rows = [&](ofstream &o, const function<void(uint64_t, string &)> &fmt) {
             const uint64_t chunk = 1u << 16;
@@ -842,16 +846,16 @@ int main(int argc, char **argv)
             o.push_back(sep);
         };
         ofs.open((output_base + ".k").c_str());
-        write_rows(ofs, [&](uint64_t i, string &o) { put(o, k[i], '\n'); });
+        write_rows(ofs, [&](uint64_t i, string &o) { put(o, hits.k[i], '\n'); });
         ofs.close(); ofs.clear();
         ofs.open((output_base + ".M").c_str());
         ofs << "#";
-        for (uint32_t t = 0; t < n; t++) ofs << "\t" << sid(t);
+        for (uint32_t t = 0; t < n; t++) ofs << "\t" << obs.names[t];
         ofs << "\n";
         // one line "row<TAB>column" per hit (:690-694): 13.7 GB of text at 50 M reads.  The row's digits are formatted once per row,
         // the lines of a chunk go into one buffer sized beforehand (a row index and a column index have at most 10 digits each)
         write_rows(ofs, [&](uint64_t i, string &o) {
-            const uint64_t b = row_ptr[i], e = row_ptr[i + 1];
+            const uint64_t b = hits.row_ptr[i], e = hits.row_ptr[i + 1];
             if (b == e) return;
             char head[24];
             const size_t hl = (size_t)(to_chars(head, head + 22, i).ptr - head);
@@ -861,138 +865,172 @@ int main(int argc, char **argv)
             char *w = &o[at];
             for (uint64_t j = b; j < e; ++j) {
                 memcpy(w, head, hl + 1);
-                w = to_chars(w + hl + 1, w + hl + 12, col_idx[j]).ptr;
+                w = to_chars(w + hl + 1, w + hl + 12, hits.col_idx[j]).ptr;
                 *w++ = '\n';
             }
             o.resize((size_t)(w - o.data()));
         });
         ofs.close(); ofs.clear();
     });
-    struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } km_join{km_writer};
-    g_background_writer = &km_writer;
+}
 
-    if (debug) { // src/mmseq.cpp:697-731
-        ofs.open((output_base + ".sharedcounts").c_str());
-        for (auto &name : transcriptList) {
-            ofs << name << "\t";
-            const int32_t t = obs_of(name);
-            for (int i = 0; i < 100; i++) ofs << (t >= 0 ? counts_shared[t][i] : 0) << "\t";
-            ofs << endl;
-        }
-        ofs.close(); ofs.clear();
-        ofs.open((output_base + ".doublehits").c_str());
-        for (uint32_t i = 0; i < n; i++) ofs << doublehits[i] << endl;
-        ofs.close(); ofs.clear();
-        // transposed matrix without consecutive duplicate rows, and the ids of the duplicates
-        vector<vector<uint32_t>> Mt(n);
-        for (uint64_t i = 0; i < m; ++i)
-            for (uint64_t j = row_ptr[i]; j < row_ptr[i + 1]; ++j) Mt[col_idx[j]].push_back((uint32_t)i);
-        ofs.open((output_base + ".Mt-nodups").c_str());
-        ofstream ofs2((output_base + ".dupIDs").c_str());
-        for (uint32_t t = 0; t < n; ++t) {
-            if (t > 0 && Mt[t] == Mt[t - 1]) ofs2 << sid(t) << endl;
-            else for (uint32_t r : Mt[t]) ofs << t << "\t" << r << endl;
-        }
-        ofs.close(); ofs.clear();
+// src/mmseq.cpp:697-731
+static void write_debug_files(const string &output_base, const Header &hdr, const Hits &hits, const Observed &obs,
+                              const vector<vector<int>> &counts_shared)
+{
+    const uint32_t n = hits.n();
+    ofstream ofs((output_base + ".sharedcounts").c_str());
+    for (auto &name : hdr.transcriptList) {
+        ofs << name << "\t";
+        const int32_t t = obs.of(name);
+        for (int i = 0; i < 100; i++) ofs << (t >= 0 ? counts_shared[t][i] : 0) << "\t";
+        ofs << endl;
     }
+    ofs.close(); ofs.clear();
+    ofs.open((output_base + ".doublehits").c_str());
+    for (uint32_t i = 0; i < n; i++) ofs << hits.doublehits[i] << endl;
+    ofs.close(); ofs.clear();
+    // transposed matrix without consecutive duplicate rows, and the ids of the duplicates
+    vector<vector<uint32_t>> Mt(n);
+    for (uint64_t i = 0; i < hits.m(); ++i)
+        for (uint64_t j = hits.row_ptr[i]; j < hits.row_ptr[i + 1]; ++j) Mt[hits.col_idx[j]].push_back((uint32_t)i);
+    ofs.open((output_base + ".Mt-nodups").c_str());
+    ofstream ofs2((output_base + ".dupIDs").c_str());
+    for (uint32_t t = 0; t < n; ++t) {
+        if (t > 0 && Mt[t] == Mt[t - 1]) ofs2 << obs.names[t] << endl;
+        else for (uint32_t r : Mt[t]) ofs << t << "\t" << r << endl;
+    }
+}
 
-    stage.mark("start the .k .M writer");
-    // ---- device problem.  Rows go up in first-seen order and observed-transcript numbering, exactly as src/mmseq.cpp:399-418 builds
-    //      them; the library stores the rows in its own canonical order and -- given tx_order -- numbers the transcripts gene by gene
-    //      (header order, the isoforms of a gene adjacent: the sample kernel keeps a window of consecutive transcripts in LDS and
-    //      wants a read's hits close together).  Both orders are irrelevant to the model; every array that comes back is in
-    //      observed-transcript numbering.
+// the problem on the device(s).  Declared in this order, released in the reverse one: the problems made for the other devices, the
+// whole problem, the group (as the run has always released them)
+struct Device {
+    Group grp;                  // several devices only
+    Problem prob;               // the whole problem, on the first device (dropped once nothing runs on it any more)
+    Problems copies;            // problems made here for the devices (besides prob)
+    vector<mmg_problem *> part; // problem of device i
+    bool shard = false;         // several devices, one chain: the reads are cut into shards
+};
+
+// ---- device problem.  Rows go up in first-seen order and observed-transcript numbering, exactly as src/mmseq.cpp:399-418 builds
+//      them; the library stores the rows in its own canonical order and -- given tx_order -- numbers the transcripts gene by gene
+//      (header order, the isoforms of a gene adjacent: the sample kernel keeps a window of consecutive transcripts in LDS and
+//      wants a read's hits close together).  Both orders are irrelevant to the model; every array that comes back is in
+//      observed-transcript numbering.
+static Problem build_problem(const Options &opt, const Header &hdr, const Hits &hits, const Observed &obs, const vector<double> &l,
+                             JoiningThread &device_warmup, StageTimer &stage, vector<double> &mu, vector<int32_t> &unique_hits)
+{
+    const uint32_t n = hits.n();
+    const size_t nHeader = hdr.transcriptList.size();
+    // key: (smallest header index of the transcript's gene, own header index)
+    unordered_map<string, uint32_t> hdr_of_name;
+    hdr_of_name.reserve(nHeader * 2);
+    for (size_t i = 0; i < nHeader; ++i) hdr_of_name.emplace(hdr.transcriptList[i], (uint32_t)i);
+    map<string, uint32_t> gene_first;
+    for (auto &gt : hdr.gene2transcripts) {
+        uint32_t f = 0xffffffffu;
+        for (auto &name : gt.second) { auto it = hdr_of_name.find(name); if (it != hdr_of_name.end()) f = min(f, it->second); }
+        gene_first[gt.first] = f;
+    }
+    vector<uint64_t> tx_order(n);
+    for (uint32_t t = 0; t < n; ++t) {
+        auto tg = hdr.transcript2gene.find(obs.names[t]);
+        const uint32_t gf = tg == hdr.transcript2gene.end() ? hits.obs2hdr[t] : min(gene_first[tg->second], hits.obs2hdr[t]);
+        tx_order[t] = ((uint64_t)gf << 32) | hits.obs2hdr[t];
+    }
+    mmg_problem_desc pd;
+    memset(&pd, 0, sizeof pd);
+    pd.m = hits.m(); pd.n = n; pd.row_ptr = hits.row_ptr.data(); pd.col_idx = hits.col_idx.data(); pd.k = hits.k.data(); pd.l = l.data();
+    pd.row_id_base = 0; pd.layout = MMG_LAYOUT_CANONICAL; pd.tx_order = tx_order.data();
+    device_warmup.join();
+    // (the handles keep the names of the calls' text in their error messages: prob, smp, summ, grp, smps, part, ...)
+    const int device = opt.device;
     mmg_problem *prob = nullptr;
-    {
-        // key: (smallest header index of the transcript's gene, own header index)
-        unordered_map<string, uint32_t> hdr_of_name;
-        hdr_of_name.reserve(nHeader * 2);
-        for (size_t i = 0; i < nHeader; ++i) hdr_of_name.emplace(transcriptList[i], (uint32_t)i);
-        map<string, uint32_t> gene_first;
-        for (auto &gt : gene2transcripts) {
-            uint32_t f = 0xffffffffu;
-            for (auto &name : gt.second) { auto it = hdr_of_name.find(name); if (it != hdr_of_name.end()) f = min(f, it->second); }
-            gene_first[gt.first] = f;
-        }
-        vector<uint64_t> tx_order(n);
-        for (uint32_t t = 0; t < n; ++t) {
-            auto tg = transcript2gene.find(sid(t));
-            const uint32_t gf = tg == transcript2gene.end() ? obs2hdr[t] : min(gene_first[tg->second], obs2hdr[t]);
-            tx_order[t] = ((uint64_t)gf << 32) | obs2hdr[t];
-        }
-        mmg_problem_desc pd;
-        memset(&pd, 0, sizeof pd);
-        pd.m = m; pd.n = n; pd.row_ptr = row_ptr.data(); pd.col_idx = col_idx.data(); pd.k = k.data(); pd.l = l.data();
-        pd.row_id_base = 0; pd.layout = MMG_LAYOUT_CANONICAL; pd.tx_order = tx_order.data();
-        if (device_warmup.joinable()) device_warmup.join();
-        MMG_TRY(mmg_problem_create(&pd, device, &prob));
-        {
-            mmg_problem_info inf0;
-            MMG_TRY(mmg_problem_info_get(prob, &inf0));
-            if (inf0.tx_renumbered & MMG_ORDER_SKIPPED)
-                cerr << "Warning: not enough free device memory to try a gene order derived from the hit graph; the run uses the hits file's gene order "
-                        "(slower on reads that hit paralogues, and the traces differ from a run that had the memory)" << endl;
-        }
-        if (stage.on) {
-            mmg_problem_info inf;
-            MMG_TRY(mmg_problem_info_get(prob, &inf));
-            fprintf(stderr, "[timing] sample kernel %d (2 sliced-ELL stream, 0 CSR tiles), %llu of %llu tiles on the register path, %llu with far lists, %.1f MB on the device%s\n",
-                    inf.sample_kernel, (unsigned long long)inf.fast_tiles, (unsigned long long)inf.n_tiles, (unsigned long long)inf.far_tiles, inf.device_bytes / 1e6,
-                    (inf.tx_renumbered & 0xff) == 3 ? "; the genes reordered by the gene-level hit graph (reads that also hit paralogues)" : "");
-        }
+    MMG_TRY(mmg_problem_create(&pd, device, &prob));
+    Problem owned(prob);
+    mmg_problem_info inf0;
+    MMG_TRY(mmg_problem_info_get(prob, &inf0));
+    if (inf0.tx_renumbered & MMG_ORDER_SKIPPED)
+        cerr << "Warning: not enough free device memory to try a gene order derived from the hit graph; the run uses the hits file's gene order "
+                "(slower on reads that hit paralogues, and the traces differ from a run that had the memory)" << endl;
+    if (stage.on) {
+        mmg_problem_info inf;
+        MMG_TRY(mmg_problem_info_get(prob, &inf));
+        fprintf(stderr, "[timing] sample kernel %d (2 sliced-ELL stream, 0 CSR tiles), %llu of %llu tiles on the register path, %llu with far lists, %.1f MB on the device%s\n",
+                inf.sample_kernel, (unsigned long long)inf.fast_tiles, (unsigned long long)inf.n_tiles, (unsigned long long)inf.far_tiles, inf.device_bytes / 1e6,
+                (inf.tx_renumbered & 0xff) == 3 ? "; the genes reordered by the gene-level hit graph (reads that also hit paralogues)" : "");
     }
-
     stage.mark("device problem build");
     MMG_TRY(mmg_problem_start_values(prob, mu.data(), unique_hits.data()));
     stage.mark("start values, unique hits (device)");
-    // ---- several devices: the stored problem (canonical order, device numbering) is cut into contiguous read shards, one per device
-    //      (one chain: EM and Gibbs both run sharded), or replicated (chains >= devices).  Cut on device 0 and copied device to
-    //      device (mmg_problem_shard): nothing comes back to the host.
-    vector<mmg_problem *> dprob;   // problems created here (besides prob)
-    vector<mmg_problem *> part;    // problem of device i
+    return owned;
+}
+
+// ---- several devices: the stored problem (canonical order, device numbering) is cut into contiguous read shards, one per device
+//      (one chain: EM and Gibbs both run sharded), or replicated (chains >= devices).  Cut on device 0 and copied device to
+//      device (mmg_problem_shard): nothing comes back to the host.
+static void spread(const Options &opt, Device &dev, const vector<double> &mu, StageTimer &stage)
+{
+    const int gpus = opt.gpus;
+    const bool shard = dev.shard = gpus > 1 && opt.chains == 1;
+    mmg_problem *prob = dev.prob.get();
+    vector<mmg_problem *> &part = dev.part;
+    if (gpus == 1) { part.assign(1, prob); return; }
+    vector<int> devs(gpus);
+    for (int i = 0; i < gpus; ++i) devs[i] = opt.device + i;
     mmg_group *grp = nullptr;
-    const bool shard = gpus > 1 && chains == 1;
-    if (gpus > 1) {
-        vector<int> devs(gpus);
-        for (int i = 0; i < gpus; ++i) devs[i] = device + i;
-        MMG_TRY(mmg_group_create(devs.data(), gpus, &grp));
-        mmg_problem_info inf;
-        MMG_TRY(mmg_problem_info_get(prob, &inf));
-        vector<uint64_t> bounds(gpus + 1, 0);
-        // cut by measured cost: every candidate shard is timed on device 0 with the start values as weights (0.1 s), so that the devices
-        // finish their sweeps together whatever the mix of near rows, far rows and multiplicities (src/mmseq.cpp:864 splits the rows evenly)
-        if (shard) MMG_TRY(mmg_problem_shard_bounds_timed(prob, mu.data(), gpus, bounds.data()));
-        part.resize(gpus);
-        for (int i = 0; i < gpus; ++i) {
-            if (!shard && i == 0) { part[0] = prob; continue; }
-            MMG_TRY(mmg_problem_shard(prob, shard ? bounds[i] : 0, shard ? bounds[i + 1] : inf.m, devs[i], &part[i]));
-            dprob.push_back(part[i]);
-        }
-        if (stage.on && shard) {
-            fprintf(stderr, "[timing] read shards (rows):");
-            for (int i = 0; i < gpus; ++i) fprintf(stderr, " %llu", (unsigned long long)(bounds[i + 1] - bounds[i]));
-            fprintf(stderr, "\n");
-        }
-        stage.mark(shard ? "read shards" : "replicas");
+    MMG_TRY(mmg_group_create(devs.data(), gpus, &grp));
+    dev.grp.reset(grp);
+    mmg_problem_info inf;
+    MMG_TRY(mmg_problem_info_get(prob, &inf));
+    vector<uint64_t> bounds(gpus + 1, 0);
+    // cut by measured cost: every candidate shard is timed on device 0 with the start values as weights (0.1 s), so that the devices
+    // finish their sweeps together whatever the mix of near rows, far rows and multiplicities (src/mmseq.cpp:864 splits the rows evenly)
+    if (shard) MMG_TRY(mmg_problem_shard_bounds_timed(prob, mu.data(), gpus, bounds.data()));
+    part.assign(gpus, nullptr);
+    for (int i = 0; i < gpus; ++i) {
+        if (!shard && i == 0) { part[0] = prob; continue; }
+        MMG_TRY(mmg_problem_shard(prob, shard ? bounds[i] : 0, shard ? bounds[i + 1] : inf.m, devs[i], &part[i]));
+        dev.copies.h.push_back(part[i]);
     }
-    const bool shard_em = shard && !em_one_device;
+    if (stage.on && shard) {
+        fprintf(stderr, "[timing] read shards (rows):");
+        for (int i = 0; i < gpus; ++i) fprintf(stderr, " %llu", (unsigned long long)(bounds[i + 1] - bounds[i]));
+        fprintf(stderr, "\n");
+    }
+    stage.mark(shard ? "read shards" : "replicas");
+}
+
+// ---- EM on the device(s) (src/mmseq.cpp:741-811): mu stays there; this loop owns the stopping rule and the output
+static vector<double> run_em(const Options &opt, const Observed &obs, Device &dev, vector<double> mu, StageTimer &stage)
+{
+    const uint32_t n = (uint32_t)obs.names.size();
+    const bool shard_em = dev.shard && !opt.em_one_device;
     // the whole problem is needed on device 0 only while something runs on it: with sharded EM and Gibbs, not beyond this point
-    if (shard && shard_em) { mmg_problem_destroy(prob); prob = nullptr; }
-    // ---- EM on the device(s) (src/mmseq.cpp:741-811): mu stays there; this loop owns the stopping rule and the output
-    GzText *gz_em = debug ? new GzText(output_base + ".trace_em.gz") : nullptr;
-    if (gz_em) { for (uint32_t t = 0; t < n; t++) { gz_em->str(sid(t)); gz_em->str(" "); } gz_em->str("\n"); }
+    if (shard_em) dev.prob.reset();
+    unique_ptr<GzText> gz_em;
+    if (opt.debug) {
+        const string path = opt.output_base + ".trace_em.gz";
+        gz_em = make_unique<GzText>(path);
+        if (!gz_em->ok()) fatal("cannot open " + path + " for writing.");
+        for (uint32_t t = 0; t < n; t++) { gz_em->str(obs.names[t]); gz_em->str(" "); }
+        gz_em->str("\n");
+    }
     {
         double loglik = 0.0;
-        vector<mmg_em *> ems(shard_em ? gpus : 1, nullptr);
+        mmg_group *grp = dev.grp.get();
+        mmg_problem *prob = dev.prob.get();
+        const vector<mmg_problem *> &part = dev.part;
+        Ems ems(shard_em ? opt.gpus : 1);
         if (shard_em) MMG_TRY(mmg_group_em_create(grp, part.data(), mu.data(), ems.data(), &loglik)); // exact integer sums: the bits of the unsharded EM
         else MMG_TRY(mmg_em_create(prob, mu.data(), &ems[0], &loglik));
         mmg_em *em = ems[0];
         stage.mark("EM set-up + first pass");
-        double llr = epsilon + 1;
+        double llr = opt.epsilon + 1;
         int iter = 0;
         cout.precision(5);
         cout.setf(ios::fixed, ios::floatfield);
-        while (iter < max_em_iter && llr > epsilon) {
+        while (iter < opt.max_em_iter && llr > opt.epsilon) {
             cout << "EM iteration " << iter << flush;
             if (gz_em) {
                 if (iter) MMG_TRY(mmg_em_get_mu(em, mu.data()));
@@ -1007,260 +1045,258 @@ int main(int argc, char **argv)
             iter++;
         }
         MMG_TRY(mmg_em_get_mu(em, mu.data()));
-        for (auto e : ems) mmg_em_destroy(e);
-        if (shard && prob) { mmg_problem_destroy(prob); prob = nullptr; }   // (-em_one_device: the whole problem has served)
-        cout << endl;
-        cout.unsetf(ios::floatfield);
-        cout.precision(6);
     }
-    if (gz_em) { gz_em->close(); delete gz_em; }
-    const vector<double> mu_em = mu;
+    if (dev.shard) dev.prob.reset();   // (-em_one_device: the whole problem has served)
+    cout << endl;
+    cout.unsetf(ios::floatfield);
+    cout.precision(6);
+    if (gz_em) gz_em->close();
+    return mu;
+}
 
-    stage.mark("EM");
-    // ---- Gibbs on the device(s) (src/mmseq.cpp:833-918); the trace stays there.
-    //      one device: `chains` chains in one sampler.  several devices, one chain: the stored rows are cut into contiguous shards
-    //      (mmg_shard_bounds), one per device, counts all-reduced over RCCL every iteration -- bit-identical to the one-device run.
-    //      several devices, chains >= devices: the stored problem is replicated, every device runs chains / gpus chains.
-    vector<mmg_sampler *> smps;
-    mmg_sampler *smp = nullptr;
-    mmg_summary *summ = nullptr;
-    const size_t nI = identical_transcripts.size(), nG = gene2transcripts.size();
-    const size_t nP = percentiles.size();
-    vector<int> pind(nP);
-    for (size_t i = 0; i < nP; i++) pind[i] = static_cast<int>(round(percentiles[i] / 100.0 * (trace_length - 1)));
-    map<string, uint32_t> headerIndexOf;
-    for (size_t i = 0; i < nHeader; ++i) headerIndexOf[transcriptList[i]] = (uint32_t)i;
-    map<string, uint32_t> simuIndex; // isoform without hits -> its simulated ("virtual") trace
-    // the series of the summary: isoforms without hits, identical sets and genes (their members: caller's transcripts or n + virtual index)
-    vector<uint64_t> vid, iptr(1, 0), gptr(1, 0);
+// the series of the summary: isoforms without hits, identical sets and genes (their members: caller's transcripts or n + virtual index)
+struct SeriesLayout {
+    vector<uint64_t> vid, iptr{0}, gptr{0};
     vector<double> vscale;
     vector<uint32_t> imem, gmem;
+    map<string, uint32_t> simuIndex; // isoform without hits -> its simulated ("virtual") trace
+    vector<int> pind;                // the sample index of each percentile
+    vector<string> identical_ids, gene_ids; // the feature ids of the identical sets ("+"-joined members) and of the genes
+    uint32_t simu_of(const string &name) const { auto it = simuIndex.find(name); return it == simuIndex.end() ? 0u : it->second; }
+    mmg_summary_desc desc() const
     {
-        mmg_config cfg;
-        memset(&cfg, 0, sizeof cfg);
-        cfg.alpha = alpha; cfg.beta = beta; cfg.seed = (uint64_t)(int64_t)seed;
-        cfg.n_chains = gpus > 1 ? max(1, chains / gpus) : chains; cfg.chain_base = 0; cfg.gibbs_iter = gibbs_iter; cfg.trace_len = trace_length;
-        cfg.keep_trace = 1; cfg.timing = 0;
-        if (gpus == 1) {
-            smps.resize(1);
-            MMG_TRY(mmg_sampler_create(prob, &cfg, mu_em.data(), &smps[0]));
-        } else {
-            smps.resize(gpus);
-            for (int i = 0; i < gpus; ++i) {
-                mmg_config ci = cfg;
-                ci.chain_base = shard ? 0 : i * cfg.n_chains;
-                MMG_TRY(mmg_sampler_create(part[i], &ci, mu_em.data(), &smps[i]));
-            }
-        }
-        // ---- the posterior summary is set up BEFORE the loop and fed while it runs (src/mmseq.cpp:911-917 prints sample s inside the
-        //      loop; :927-1108 derives the other traces after it): sample s is final after iteration s * gibbs_ss, so the four trace files
-        //      are formatted, compressed and written by background threads while the device runs on -- rows come off the device on
-        //      streams of their own (mmg_sampler_get_trace_rows_done, mmg_summary_get_rows), nothing waits for the chain.
-        smp = smps[0]; // traces and per-feature summaries come from chain 0 (every shard holds the whole chain)
+        mmg_summary_desc d;
+        memset(&d, 0, sizeof d);
+        d.n_virtual = (uint32_t)vid.size(); d.virtual_id = vid.data(); d.virtual_scale = vscale.data();
+        d.n_identical = (uint32_t)(iptr.size() - 1); d.identical_ptr = iptr.data(); d.identical_member = imem.data();
+        d.n_genes = (uint32_t)(gptr.size() - 1); d.gene_ptr = gptr.data(); d.gene_member = gmem.data();
+        return d;
     }
-    {
-        for (size_t v = 0; v < nI; ++v) {
-            for (auto &name : identical_transcripts[v]) { const int32_t t = obs_of(name); if (t >= 0) imem.push_back((uint32_t)t); }
-            iptr.push_back(imem.size());
+};
+
+static SeriesLayout series_layout(const Options &opt, const Header &hdr, const Hits &hits, const Observed &obs)
+{
+    SeriesLayout s;
+    const uint32_t n = hits.n();
+    const size_t nHeader = hdr.transcriptList.size();
+    map<string, uint32_t> headerIndexOf;
+    for (size_t i = 0; i < nHeader; ++i) headerIndexOf[hdr.transcriptList[i]] = (uint32_t)i;
+    for (auto &set : hdr.identical_transcripts) {
+        string id;
+        for (auto &name : set) {
+            const int32_t t = obs.of(name);
+            if (t >= 0) s.imem.push_back((uint32_t)t);
+            id += name;
+            if (name.compare(set.back()) != 0) id += "+";
         }
-        size_t g = 0;
-        for (auto &gt : gene2transcripts) {
-            for (auto &name : gt.second) {
-                const int32_t t = obs_of(name);
-                if (t >= 0) { gmem.push_back((uint32_t)t); continue; }
-                // no hits: simulate from the prior-only conditional (keyed by the header index, :971-978)
-                simuIndex[name] = (uint32_t)vid.size();
-                gmem.push_back(n + (uint32_t)vid.size());
-                vid.push_back(headerIndexOf.count(name) ? headerIndexOf[name] : (uint64_t)nHeader + g);
-                vscale.push_back(1.0 / (beta + sidLen[name] * (double)numbermappedreads / 1000000000.0));
-            }
-            gptr.push_back(gmem.size());
-            g++;
-        }
-        mmg_summary_desc sd;
-        memset(&sd, 0, sizeof sd);
-        sd.chain = 0;
-        sd.n_virtual = (uint32_t)vid.size(); sd.virtual_id = vid.data(); sd.virtual_scale = vscale.data();
-        sd.n_identical = (uint32_t)nI; sd.identical_ptr = iptr.data(); sd.identical_member = imem.data();
-        sd.n_genes = (uint32_t)nG; sd.gene_ptr = gptr.data(); sd.gene_member = gmem.data();
-        sd.n_percentiles = (uint32_t)nP; sd.percentile_index = pind.data();
-        MMG_TRY(mmg_summary_begin(smp, &sd, &summ));
+        s.iptr.push_back(s.imem.size());
+        s.identical_ids.push_back(id);
     }
-    const size_t nV = simuIndex.size();
-    // (the writers outlive the loop: they are joined after the tables are written -- the tail of their work runs next to the summary
-    // columns and the tables instead of in front of them)
-    std::mutex ready_mu;
-    std::condition_variable ready_cv;
-    int samples_ready = 0;                           // samples whose rows may be fetched (trace and derived traces)
-    auto wait_for = [&](int upto) { std::unique_lock<std::mutex> lk(ready_mu); ready_cv.wait(lk, [&] { return samples_ready >= upto || g_worker_failed.load(); }); };
+    size_t g = 0;
+    for (auto &gt : hdr.gene2transcripts) {
+        s.gene_ids.push_back(gt.first);
+        for (auto &name : gt.second) {
+            const int32_t t = obs.of(name);
+            if (t >= 0) { s.gmem.push_back((uint32_t)t); continue; }
+            // no hits: simulate from the prior-only conditional (keyed by the header index, :971-978)
+            s.simuIndex[name] = (uint32_t)s.vid.size();
+            s.gmem.push_back(n + (uint32_t)s.vid.size());
+            s.vid.push_back(headerIndexOf.count(name) ? headerIndexOf[name] : (uint64_t)nHeader + g);
+            s.vscale.push_back(1.0 / (opt.beta + hdr.len_of(name) * (double)hits.numbermappedreads / 1000000000.0));
+        }
+        s.gptr.push_back(s.gmem.size());
+        g++;
+    }
+    for (double p : opt.percentiles) s.pind.push_back(static_cast<int>(round(p / 100.0 * (trace_length - 1))));
+    return s;
+}
+
+// the chains on the device(s) and the posterior summary that is fed while they run.  Released in the reverse order: summary, samplers
+struct Chains {
+    Samplers smps;              // sampler of device i
+    Summary summ;
+    mmg_sampler *smp() const { return smps.h[0]; } // traces and per-feature summaries come from chain 0 (every shard holds the whole chain)
+};
+
+// ---- Gibbs on the device(s) (src/mmseq.cpp:833-918); the trace stays there.
+//      one device: `chains` chains in one sampler.  several devices, one chain: the stored rows are cut into contiguous shards
+//      (mmg_shard_bounds), one per device, counts all-reduced over RCCL every iteration -- bit-identical to the one-device run.
+//      several devices, chains >= devices: the stored problem is replicated, every device runs chains / gpus chains.
+static Chains start_chains(const Options &opt, const Device &dev, const vector<double> &mu_em, const SeriesLayout &layout)
+{
+    Chains ch;
+    mmg_config cfg;
+    memset(&cfg, 0, sizeof cfg);
+    cfg.alpha = opt.alpha; cfg.beta = opt.beta; cfg.seed = (uint64_t)(int64_t)opt.seed;
+    cfg.n_chains = opt.gpus > 1 ? max(1, opt.chains / opt.gpus) : opt.chains; cfg.chain_base = 0; cfg.gibbs_iter = opt.gibbs_iter; cfg.trace_len = trace_length;
+    cfg.keep_trace = 1; cfg.timing = 0;
+    Samplers &smps = ch.smps;
+    mmg_problem *prob = dev.prob.get();
+    const vector<mmg_problem *> &part = dev.part;
+    smps.h.assign(opt.gpus, nullptr);
+    if (opt.gpus == 1) MMG_TRY(mmg_sampler_create(prob, &cfg, mu_em.data(), &smps[0]));
+    else
+        for (int i = 0; i < opt.gpus; ++i) {
+            mmg_config ci = cfg;
+            ci.chain_base = dev.shard ? 0 : i * cfg.n_chains;
+            MMG_TRY(mmg_sampler_create(part[i], &ci, mu_em.data(), &smps[i]));
+        }
+    // ---- the posterior summary is set up BEFORE the loop and fed while it runs (src/mmseq.cpp:911-917 prints sample s inside the
+    //      loop; :927-1108 derives the other traces after it): sample s is final after iteration s * gibbs_ss, so the four trace files
+    //      are formatted, compressed and written by background threads while the device runs on -- rows come off the device on
+    //      streams of their own (mmg_sampler_get_trace_rows_done, mmg_summary_get_rows), nothing waits for the chain.
+    mmg_summary_desc sd = layout.desc();
+    sd.chain = 0;
+    sd.n_percentiles = (uint32_t)layout.pind.size(); sd.percentile_index = layout.pind.data();
+    mmg_sampler *smp = ch.smp();
+    mmg_summary *summ = nullptr;
+    MMG_TRY(mmg_summary_begin(smp, &sd, &summ));
+    ch.summ.reset(summ);
+    return ch;
+}
+
+// One trace file, written by a worker thread: the ids of the series kept, then trace_length rows fetched as they become final.  With
+// what_first, a series whose first sample has no finite logarithm is left out of the file (:1040 for identical sets, :1068 for genes).
+// (what, what_first: the fetches' call text for an error message; what_first is null for files that keep every series)
+static void start_trace_file(TraceWriters &w, const string &path, const vector<string> &ids, const char *what_first,
+                             const function<int(int, int, double *)> &fetch, const char *what, int threads)
+{
+    w.threads.emplace_back([&w, path, &ids, what_first, fetch, what, threads] {
+        vector<char> keep(ids.size(), 1);
+        if (what_first) {
+            w.wait_for(1);
+            if (w.stop.load()) return;
+            vector<double> first(max<size_t>(ids.size(), 1));
+            if (w.failed(fetch(0, 1, first.data()), what_first)) return;
+            for (size_t i = 0; i < ids.size(); ++i) keep[i] = isfinite(log(first[i])) != 0;
+        }
+        GzText gz(path);
+        if (!gz.ok()) { w.record("cannot open " + path + " for writing."); return; }
+        for (size_t i = 0; i < ids.size(); ++i)
+            if (keep[i]) { gz.str(ids[i]); gz.str(" "); }
+        gz.str("\n");
+        write_trace_rows(gz, trace_length, ids.size(), [&](int first, int count, double *out) { w.wait_for(first + count); if (w.stop.load()) return; (void)w.failed(fetch(first, count, out), what); },
+                         [&](size_t i) { return keep[i] != 0; }, w.stop, threads);
+        gz.close();
+    });
+}
+
+// the Gibbs loop; the four trace files are written alongside by `w` (whose threads outlive it: they are joined after the tables are
+// written -- the tail of their work runs next to the summary columns and the tables instead of in front of them)
+static void run_gibbs(const Options &opt, const Observed &obs, const SeriesLayout &layout, const Device &dev, const Chains &ch,
+                      TraceWriters &w, StageTimer &stage)
+{
     const int writer_threads = max(1, omp_get_max_threads());
     const int t_big = max(1, (writer_threads - 1) * 9 / 20), t_gene = max(1, writer_threads / 10);
-    std::thread w_trace, w_ident, w_gene, w_prop;
-    {
-        w_trace = std::thread([&]() {
-            GzText gz(output_base + ".trace_gibbs.gz");
-            for (uint32_t t = 0; t < n; t++) { gz.str(sid(t)); gz.str(" "); }
-            gz.str("\n");
-            write_trace_rows(gz, trace_length, n, [&](int first, int count, double *out) { wait_for(first + count); if (g_worker_failed.load()) return; MMG_TRY_WORKER(mmg_sampler_get_trace_rows_done(smp, 0, first, count, out)); },
-                             [](size_t) { return true; }, t_big);
-            gz.close();
-        });
-        w_ident = std::thread([&]() {
-            // a set whose first summed sample has no finite logarithm is left out of its trace file (:1040)
-            wait_for(1);
-            if (g_worker_failed.load()) return;
-            vector<double> firstI(max<size_t>(nI, 1));
-            MMG_TRY_WORKER(mmg_summary_get_rows(summ, MMG_SERIES_IDENTICAL, 0, 1, firstI.data()));
-            vector<char> keepI(nI);
-            for (size_t v = 0; v < nI; ++v) keepI[v] = isfinite(log(firstI[v])) != 0;
-            GzText gi(output_base + ".identical.trace_gibbs.gz");
-            for (size_t v = 0; v < nI; ++v)
-                if (keepI[v]) {
-                    for (size_t j = 0; j < identical_transcripts[v].size(); ++j) {
-                        gi.str(identical_transcripts[v][j]);
-                        if (identical_transcripts[v][j].compare(identical_transcripts[v].back()) != 0) gi.str("+");
-                    }
-                    gi.str(" ");
-                }
-            gi.str("\n");
-            write_trace_rows(gi, trace_length, nI, [&](int first, int count, double *out) { wait_for(first + count); if (g_worker_failed.load()) return; MMG_TRY_WORKER(mmg_summary_get_rows(summ, MMG_SERIES_IDENTICAL, first, count, out)); },
-                             [&](size_t v) { return keepI[v] != 0; }, 1);
-            gi.close();
-        });
-        w_gene = std::thread([&]() {
-            wait_for(1);                             // (:1068: the same rule for genes)
-            if (g_worker_failed.load()) return;
-            vector<double> firstG(max<size_t>(nG, 1));
-            MMG_TRY_WORKER(mmg_summary_get_rows(summ, MMG_SERIES_GENE, 0, 1, firstG.data()));
-            vector<char> keepG(nG);
-            for (size_t g = 0; g < nG; ++g) keepG[g] = isfinite(log(firstG[g])) != 0;
-            GzText gg(output_base + ".gene.trace_gibbs.gz");
-            { size_t g = 0; for (auto &gt : gene2transcripts) { if (keepG[g]) { gg.str(gt.first); gg.str(" "); } g++; } }
-            gg.str("\n");
-            write_trace_rows(gg, trace_length, nG, [&](int first, int count, double *out) { wait_for(first + count); if (g_worker_failed.load()) return; MMG_TRY_WORKER(mmg_summary_get_rows(summ, MMG_SERIES_GENE, first, count, out)); },
-                             [&](size_t g) { return keepG[g] != 0; }, t_gene);
-            gg.close();
-        });
-        w_prop = std::thread([&]() {
-            GzText gp(output_base + ".prop.trace_gibbs.gz");
-            for (uint32_t t = 0; t < n; t++) { gp.str(sid(t)); gp.str(" "); }
-            gp.str("\n");
-            write_trace_rows(gp, trace_length, n, [&](int first, int count, double *out) { wait_for(first + count); if (g_worker_failed.load()) return; MMG_TRY_WORKER(mmg_summary_get_rows(summ, MMG_SERIES_TRANSCRIPT, first, count, out)); },
-                             [](size_t) { return true; }, t_big);
-            gp.close();
-        });
-        // how the main thread stops the four writers when it (or one of them) fails: flag, wake, join
-        g_stop_workers = [&]() {
-            { std::lock_guard<std::mutex> lk(ready_mu); g_worker_failed.store(true); }
-            ready_cv.notify_all();
-            for (std::thread *w : {&w_trace, &w_ident, &w_gene, &w_prop}) if (w->joinable()) w->join();
-        };
-        auto check_workers = [&]() {
-            if (!g_worker_failed.load()) return;
-            std::string msg;
-            { std::lock_guard<std::mutex> lk(g_worker_mu); msg = g_worker_msg; }
-            main_thread_exit(msg);
-        };
-        // chunks of 1/64 of the run: the writers start on a chunk's samples when it ends, so what is left of their work after the last
-        // iteration is 1/64 of the files
-        const int chunk = max(1, gibbs_iter / 64);
-        double t_enqueue = 0.0, t_sync = 0.0, t_advance = 0.0;
-        auto enqueue = [&](int it) {
-            const double c0 = omp_get_wtime();
-            if (gpus == 1) MMG_TRY(mmg_sampler_run(smps[0], it));
-            else if (gpus > 1 && chains == 1) MMG_TRY(mmg_group_run_sharded(grp, smps.data(), it));
-            else MMG_TRY(mmg_group_run_chains(grp, smps.data(), it));
-            t_enqueue += omp_get_wtime() - c0;
-        };
-        // one chunk is always enqueued ahead of the one waited for: the device does not idle while this thread hands samples on (or is
-        // held up: the writers use every CPU of the quota)
-        enqueue(min(chunk, gibbs_iter));
-        for (int done = 0; done < gibbs_iter; done += chunk) {
-            cout << "Gibbs iteration " << done << "       \r" << flush;
-            check_workers();
-            const int it = min(chunk, gibbs_iter - done);
-            if (done + it < gibbs_iter) enqueue(min(chunk, gibbs_iter - done - it));
-            // sample s is kept by iteration s * gibbs_ss (:911): the samples of the iterations up to done + it are final once the
-            // iteration that stored the last of them is
-            const int final_samples = min(trace_length, (done + it - 1) / gibbs_ss + 1);
-            const double c1 = omp_get_wtime();
-            for (auto sp : smps) MMG_TRY(mmg_sampler_wait_iterations(sp, done + it < gibbs_iter ? (final_samples - 1) * gibbs_ss + 1 : gibbs_iter));
-            const double c2 = omp_get_wtime();
-            MMG_TRY(mmg_summary_advance(summ, final_samples));
-            { std::lock_guard<std::mutex> lk(ready_mu); samples_ready = final_samples; }
-            ready_cv.notify_all();
-            t_sync += c2 - c1; t_advance += omp_get_wtime() - c2;
-        }
-        for (auto sp : smps) MMG_TRY(mmg_sampler_sync(sp));
-        check_workers();
-        cout << "Gibbs iteration " << gibbs_iter - 1 << "       \r" << endl;
-        if (stage.on) fprintf(stderr, "[timing] Gibbs loop: enqueue %.3f s, wait for the device %.3f s, derived rows %.3f s\n", t_enqueue, t_sync, t_advance);
-        stage.mark("Gibbs (trace files written alongside)");
-    }
-    // moments of log mu pooled over all chains and devices (one fp64 all-reduce): log_mu, sd and mcse of multi-chain runs
-    vector<double> pooled_sl, pooled_sl2;
-    int64_t pooled_ns = 0;
-    if (chains > 1) {
-        pooled_sl.resize(n); pooled_sl2.resize(n);
-        if (grp) MMG_TRY(mmg_group_pool_moments(grp, smps.data(), pooled_sl.data(), pooled_sl2.data(), &pooled_ns));
-        else {
-            vector<double> a_(n), b_(n);
-            for (int c = 0; c < chains; ++c) {
-                int64_t ns = 0;
-                MMG_TRY(mmg_sampler_get_moments(smp, c, a_.data(), b_.data(), &ns));
-                for (uint32_t t = 0; t < n; ++t) { pooled_sl[t] += a_[t]; pooled_sl2[t] += b_[t]; }
-                pooled_ns += ns;
-            }
-        }
-    }
-
-    cout << "Amalgamating transcripts and calculating summary statistics..." << flush;
-    // ---- posterior summary on the device (src/mmseq.cpp:927-1363): the derived traces were computed while the chain ran; what is left
-    //      are the per-series columns -- percentiles, log means, Sokal -- of which only the columns come back.
-    MMG_TRY(mmg_summary_finish(summ));
-    stage.mark("device summary");
-    // ---- convergence across the chains (-convergence): per series of the three tables R-hat, bulk and tail ESS, on the device
-    struct Conv { vector<double> rhat, ess_bulk, ess_tail; };
-    Conv cT, cV, cI, cG;
-    if (convergence) {
-        mmg_summary_desc cd;
-        memset(&cd, 0, sizeof cd);
-        cd.n_virtual = (uint32_t)vid.size(); cd.virtual_id = vid.data(); cd.virtual_scale = vscale.data();
-        cd.n_identical = (uint32_t)nI; cd.identical_ptr = iptr.data(); cd.identical_member = imem.data();
-        cd.n_genes = (uint32_t)nG; cd.gene_ptr = gptr.data(); cd.gene_member = gmem.data();
-        mmg_convergence *conv = nullptr;
-        MMG_TRY(mmg_convergence_create(smp, &cd, &conv));
-        auto fetch_conv = [&](int kind, size_t count, Conv &o) {
-            o.rhat.assign(max<size_t>(count, 1), NAN); o.ess_bulk.assign(max<size_t>(count, 1), NAN); o.ess_tail.assign(max<size_t>(count, 1), NAN);
-            MMG_TRY(mmg_convergence_get(conv, kind, o.rhat.data(), o.ess_bulk.data(), o.ess_tail.data()));
-        };
-        fetch_conv(MMG_SERIES_TRANSCRIPT, n, cT);
-        fetch_conv(MMG_SERIES_VIRTUAL, vid.size(), cV);
-        fetch_conv(MMG_SERIES_IDENTICAL, nI, cI);
-        fetch_conv(MMG_SERIES_GENE, nG, cG);
-        mmg_convergence_destroy(conv);
-        stage.mark("convergence diagnostics");
-    }
-    // (the trace writer still reads rows of the sampler, the derived-trace writers rows of the summary: both are released once the
-    // writers are done, behind the tables)
-    auto release_device = [&]() {
-        w_trace.join(); w_ident.join(); w_gene.join(); w_prop.join();
-        // (the writers fetch the last 1/64 of the rows behind the loop's last check: a failure there -- a HIP error in a row fetch --
-        // would leave a valid but truncated trace file; it ends the run like any other)
-        if (g_worker_failed.load()) {
-            std::string msg;
-            { std::lock_guard<std::mutex> lk(g_worker_mu); msg = g_worker_msg; }
-            g_stop_workers = nullptr; // (joined above)
-            main_thread_exit(msg);
-        }
-        mmg_summary_destroy(summ);
-        for (auto sp : smps) mmg_sampler_destroy(sp);
-        for (auto pp : dprob) mmg_problem_destroy(pp);
-        mmg_problem_destroy(prob);
-        if (grp) mmg_group_destroy(grp);
+    mmg_sampler *smp = ch.smp();
+    mmg_summary *summ = ch.summ.get();
+    mmg_group *grp = dev.grp.get();
+    const Samplers &smps = ch.smps;
+    auto rows = [summ](int kind) { return [summ, kind](int first, int count, double *out) { return mmg_summary_get_rows(summ, kind, first, count, out); }; };
+    const string &base = opt.output_base;
+    w.threads.reserve(4);
+    start_trace_file(w, base + ".trace_gibbs.gz", obs.names, nullptr,
+                     [smp](int first, int count, double *out) { return mmg_sampler_get_trace_rows_done(smp, 0, first, count, out); },
+                     "mmg_sampler_get_trace_rows_done(smp, 0, first, count, out)", t_big);
+    start_trace_file(w, base + ".identical.trace_gibbs.gz", layout.identical_ids,
+                     "mmg_summary_get_rows(summ, MMG_SERIES_IDENTICAL, 0, 1, firstI.data())", rows(MMG_SERIES_IDENTICAL),
+                     "mmg_summary_get_rows(summ, MMG_SERIES_IDENTICAL, first, count, out)", 1);
+    start_trace_file(w, base + ".gene.trace_gibbs.gz", layout.gene_ids, "mmg_summary_get_rows(summ, MMG_SERIES_GENE, 0, 1, firstG.data())",
+                     rows(MMG_SERIES_GENE),
+                     "mmg_summary_get_rows(summ, MMG_SERIES_GENE, first, count, out)", t_gene);
+    start_trace_file(w, base + ".prop.trace_gibbs.gz", obs.names, nullptr, rows(MMG_SERIES_TRANSCRIPT),
+                     "mmg_summary_get_rows(summ, MMG_SERIES_TRANSCRIPT, first, count, out)", t_big);
+    // chunks of 1/64 of the run: the writers start on a chunk's samples when it ends, so what is left of their work after the last
+    // iteration is 1/64 of the files
+    const int gibbs_iter = opt.gibbs_iter, gibbs_ss = opt.gibbs_ss;
+    const int chunk = max(1, gibbs_iter / 64);
+    double t_enqueue = 0.0, t_sync = 0.0, t_advance = 0.0;
+    auto enqueue = [&](int it) {
+        const double c0 = omp_get_wtime();
+        if (opt.gpus == 1) MMG_TRY(mmg_sampler_run(smps[0], it));
+        else if (dev.shard) MMG_TRY(mmg_group_run_sharded(grp, smps.data(), it));
+        else MMG_TRY(mmg_group_run_chains(grp, smps.data(), it));
+        t_enqueue += omp_get_wtime() - c0;
     };
+    // one chunk is always enqueued ahead of the one waited for: the device does not idle while this thread hands samples on (or is
+    // held up: the writers use every CPU of the quota)
+    enqueue(min(chunk, gibbs_iter));
+    for (int done = 0; done < gibbs_iter; done += chunk) {
+        cout << "Gibbs iteration " << done << "       \r" << flush;
+        w.check();
+        const int it = min(chunk, gibbs_iter - done);
+        if (done + it < gibbs_iter) enqueue(min(chunk, gibbs_iter - done - it));
+        // sample s is kept by iteration s * gibbs_ss (:911): the samples of the iterations up to done + it are final once the
+        // iteration that stored the last of them is
+        const int final_samples = min(trace_length, (done + it - 1) / gibbs_ss + 1);
+        const double c1 = omp_get_wtime();
+        for (auto sp : smps) MMG_TRY(mmg_sampler_wait_iterations(sp, done + it < gibbs_iter ? (final_samples - 1) * gibbs_ss + 1 : gibbs_iter));
+        const double c2 = omp_get_wtime();
+        MMG_TRY(mmg_summary_advance(summ, final_samples));
+        w.publish(final_samples);
+        t_sync += c2 - c1; t_advance += omp_get_wtime() - c2;
+    }
+    for (auto sp : smps) MMG_TRY(mmg_sampler_sync(sp));
+    w.check();
+    cout << "Gibbs iteration " << gibbs_iter - 1 << "       \r" << endl;
+    if (stage.on) fprintf(stderr, "[timing] Gibbs loop: enqueue %.3f s, wait for the device %.3f s, derived rows %.3f s\n", t_enqueue, t_sync, t_advance);
+    stage.mark("Gibbs (trace files written alongside)");
+}
 
-    // ---- summary columns (src/mmseq.cpp:1110-1363)
+// moments of log mu pooled over all chains and devices (one fp64 all-reduce): log_mu, sd and mcse of multi-chain runs
+struct Pooled { vector<double> sl, sl2; int64_t ns = 0; };
+static Pooled pool_moments(const Options &opt, const Device &dev, const Chains &ch, uint32_t n)
+{
+    Pooled p;
+    if (opt.chains <= 1) return p;
+    vector<double> &pooled_sl = p.sl, &pooled_sl2 = p.sl2;
+    int64_t &pooled_ns = p.ns;
+    mmg_group *grp = dev.grp.get();
+    mmg_sampler *smp = ch.smp();
+    const Samplers &smps = ch.smps;
+    pooled_sl.resize(n); pooled_sl2.resize(n);
+    if (grp) { MMG_TRY(mmg_group_pool_moments(grp, smps.data(), pooled_sl.data(), pooled_sl2.data(), &pooled_ns)); return p; }
+    vector<double> a_(n), b_(n);
+    for (int c = 0; c < opt.chains; ++c) {
+        int64_t ns = 0;
+        MMG_TRY(mmg_sampler_get_moments(smp, c, a_.data(), b_.data(), &ns));
+        for (uint32_t t = 0; t < n; ++t) { pooled_sl[t] += a_[t]; pooled_sl2[t] += b_[t]; }
+        pooled_ns += ns;
+    }
+    return p;
+}
+
+// ---- convergence across the chains (-convergence): per series of the three tables R-hat, bulk and tail ESS, on the device
+struct Conv { vector<double> rhat, ess_bulk, ess_tail; };
+struct ConvAll { Conv T, V, I, G; };   // transcripts, isoforms without hits, identical sets, genes
+static ConvAll fetch_convergence(const Chains &ch, const SeriesLayout &layout, uint32_t n)
+{
+    ConvAll c;
+    const mmg_summary_desc cd = layout.desc();
+    mmg_sampler *smp = ch.smp();
+    mmg_convergence *conv = nullptr;
+    MMG_TRY(mmg_convergence_create(smp, &cd, &conv));
+    const Convergence owned(conv);
+    auto fetch_conv = [&](int kind, size_t count, Conv &o) {
+        o.rhat.assign(max<size_t>(count, 1), NAN); o.ess_bulk.assign(max<size_t>(count, 1), NAN); o.ess_tail.assign(max<size_t>(count, 1), NAN);
+        MMG_TRY(mmg_convergence_get(conv, kind, o.rhat.data(), o.ess_bulk.data(), o.ess_tail.data()));
+    };
+    fetch_conv(MMG_SERIES_TRANSCRIPT, n, c.T);
+    fetch_conv(MMG_SERIES_VIRTUAL, cd.n_virtual, c.V);
+    fetch_conv(MMG_SERIES_IDENTICAL, cd.n_identical, c.I);
+    fetch_conv(MMG_SERIES_GENE, cd.n_genes, c.G);
+    return c;
+}
+
+// ---- summary columns (src/mmseq.cpp:1110-1363) and the .mmseq, .identical.mmseq and .gene.mmseq tables
+static void write_tables(const Options &opt, const Header &hdr, const Hits &hits, const Observed &obs, const UniqueHits &uh,
+                         const vector<double> &mu_em, const SeriesLayout &layout, const Chains &ch, const Pooled &pooled, StageTimer &stage)
+{
+    const uint32_t n = hits.n();
+    const size_t nI = hdr.identical_transcripts.size(), nG = hdr.gene2transcripts.size(), nV = layout.simuIndex.size();
+    const size_t nP = opt.percentiles.size();
+    const long long numbermappedreads = hits.numbermappedreads;
+    mmg_summary *summ = ch.summ.get();
     struct Series { vector<double> mean, sd, mcse, iact, pct; };
     auto fetch_series = [&](int kind, size_t count, Series &o) {
         o.mean.resize(max<size_t>(count, 1)); o.sd.resize(max<size_t>(count, 1)); o.mcse.resize(max<size_t>(count, 1));
@@ -1276,22 +1312,18 @@ int main(int argc, char **argv)
     };
     Series sT, sV, sI, sG;
     fetch_series(MMG_SERIES_TRANSCRIPT, n, sT);
-    if (chains > 1 && pooled_ns > 1) { // all chains: mean and sd of log mu from the pooled moments, Monte Carlo error of the pooled mean
+    if (opt.chains > 1 && pooled.ns > 1) { // all chains: mean and sd of log mu from the pooled moments, Monte Carlo error of the pooled mean
         for (uint32_t t = 0; t < n; ++t) {
-            const double mean = pooled_sl[t] / (double)pooled_ns;
-            const double var = (pooled_sl2[t] - (double)pooled_ns * mean * mean) / (double)(pooled_ns - 1);
+            const double mean = pooled.sl[t] / (double)pooled.ns;
+            const double var = (pooled.sl2[t] - (double)pooled.ns * mean * mean) / (double)(pooled.ns - 1);
             sT.mean[t] = mean;
             sT.sd[t] = sqrt(var > 0 ? var : 0.0);
-            sT.mcse[t] = sT.mcse[t] / sqrt((double)chains);
+            sT.mcse[t] = sT.mcse[t] / sqrt((double)opt.chains);
         }
     }
     fetch_series(MMG_SERIES_VIRTUAL, nV, sV);
     fetch_series(MMG_SERIES_IDENTICAL, nI, sI);
     fetch_series(MMG_SERIES_GENE, nG, sG);
-    const vector<double> &meanmu = sT.mean, &meanmu_identical = sI.mean, &meanmu_gene = sG.mean;
-    const vector<double> &sd = sT.sd, &mumcse = sT.mcse, &iact = sT.iact;
-    const vector<double> &sd_identical = sI.sd, &mumcse_identical = sI.mcse, &iact_identical = sI.iact;
-    const vector<double> &sd_gene = sG.sd, &mumcse_gene = sG.mcse, &iact_gene = sG.iact;
     struct Props { vector<double> mean, probit_mean, probit_sd, pct; };
     auto fetch_props = [&](int kind, size_t count, Props &o) {
         o.mean.resize(max<size_t>(count, 1)); o.probit_mean.resize(max<size_t>(count, 1)); o.probit_sd.resize(max<size_t>(count, 1));
@@ -1301,34 +1333,23 @@ int main(int argc, char **argv)
     Props pT, pV;
     fetch_props(MMG_SERIES_TRANSCRIPT, n, pT);
     fetch_props(MMG_SERIES_VIRTUAL, nV, pV);
-    const vector<double> &meanprop = pT.mean, &meanprobitprop = pT.probit_mean, &sdprobitprop = pT.probit_sd;
     auto pct_row = [&](const vector<double> &pct, size_t i) { return vector<double>(pct.begin() + (ptrdiff_t)(i * nP), pct.begin() + (ptrdiff_t)((i + 1) * nP)); };
 
-    const double digalpha = mmnum::digamma(alpha);                 // gsl_sf_psi(alpha)        :1372
-    const double sqrtpolygalpha = sqrt(mmnum::trigamma(alpha));    // sqrt(gsl_sf_psi_n(1,.))  :1373
-    // (lookups that never insert: the table writers below run in several threads; a name the header did not describe reads as 0, which
-    // is what the maps' operator[] would have inserted)
-    auto len_of = [&](const string &name) { auto it = sidLen.find(name); return it == sidLen.end() ? 0.0 : it->second; };
-    auto seqlen_of = [&](const string &name) { auto it = sidSeqLen.find(name); return it == sidSeqLen.end() ? 0 : it->second; };
-    auto gene_size_of = [&](const string &name) {
-        auto tg = transcript2gene.find(name);
-        auto it = gene2transcripts.find(tg == transcript2gene.end() ? string() : tg->second);
-        return it == gene2transcripts.end() ? (size_t)0 : it->second.size();
-    };
-    auto simu_of = [&](const string &name) { auto it = simuIndex.find(name); return it == simuIndex.end() ? 0u : it->second; };
-    auto prior_logmu = [&](const string &name) { return digalpha - log(beta + len_of(name) * (double)numbermappedreads / 1000000000.0); };
+    const double digalpha = mmnum::digamma(opt.alpha);                 // gsl_sf_psi(alpha)        :1372
+    const double sqrtpolygalpha = sqrt(mmnum::trigamma(opt.alpha));    // sqrt(gsl_sf_psi_n(1,.))  :1373
+    auto prior_logmu = [&](const string &name) { return digalpha - log(opt.beta + hdr.len_of(name) * (double)numbermappedreads / 1000000000.0); };
 
     // ---- gene-level expression-weighted effective length (src/mmseq.cpp:1375-1395)
     vector<double> gene_lengths(nG, 0.0);
     {
         size_t g = 0;
-        for (auto &gt : gene2transcripts) {
-            if (isfinite(meanmu_gene[g]) != 0) {
+        for (auto &gt : hdr.gene2transcripts) {
+            if (isfinite(sG.mean[g]) != 0) {
                 double sum = 0;
                 for (auto &name : gt.second) {
-                    const int32_t t = obs_of(name);
-                    const double e = t >= 0 ? exp(meanmu[t]) : exp(prior_logmu(name));
-                    gene_lengths[g] += len_of(name) * e;
+                    const int32_t t = obs.of(name);
+                    const double e = t >= 0 ? exp(sT.mean[t]) : exp(prior_logmu(name));
+                    gene_lengths[g] += hdr.len_of(name) * e;
                     sum += e;
                 }
                 gene_lengths[g] /= sum;
@@ -1342,29 +1363,29 @@ int main(int argc, char **argv)
     };
     auto pct_header = [&](ostream &o, const char *label, const char *term) {
         o << label;
-        for (size_t i = 0; i < nP; i++) { o << percentiles[i]; o << (i == nP - 1 ? term : ","); }
+        for (size_t i = 0; i < nP; i++) { o << opt.percentiles[i]; o << (i == nP - 1 ? term : ","); }
     };
 
     // ---- .gene.mmseq (src/mmseq.cpp:1615-1669)
     auto write_gene_table = [&]() {
-    ofstream ofs((output_base + ".gene.mmseq").c_str());
+    ofstream ofs((opt.output_base + ".gene.mmseq").c_str());
     ofs << "# Mapped fragments: " << numbermappedreads << endl;
     ofs << "feature_id\tlog_mu\tsd\tmcse\tiact\teffective_length\ttrue_length\tunique_hits\tntranscripts\tobserved\t";
     pct_header(ofs, "percentiles", "\n");
     {
         size_t g = 0;
-        for (auto &gt : gene2transcripts) {
-            bool obs = false;
-            for (auto &name : gt.second) if (obs_of(name) >= 0) { obs = true; break; }
-            if (obs) {
-                ofs << gt.first << "\t" << meanmu_gene[g] << "\t" << sd_gene[g] << "\t" << mumcse_gene[g] << "\t" << iact_gene[g] << "\t"
+        for (auto &gt : hdr.gene2transcripts) {
+            bool observed = false;
+            for (auto &name : gt.second) if (obs.of(name) >= 0) { observed = true; break; }
+            if (observed) {
+                ofs << gt.first << "\t" << sG.mean[g] << "\t" << sG.sd[g] << "\t" << sG.mcse[g] << "\t" << sG.iact[g] << "\t"
                     << gene_lengths[g] << "\t"
                     << "NA"
-                    << "\t" << gene_unique_hits[g] << "\t" << gt.second.size() << "\t"
+                    << "\t" << uh.gene[g] << "\t" << gt.second.size() << "\t"
                     << "1"
                     << "\t";
             } else {
-                ofs << gt.first << "\t" << meanmu_gene[g] << "\t" << sd_gene[g] << "\t" << sd_gene[g] / sqrt(trace_length) << "\t" << 1 << "\t"
+                ofs << gt.first << "\t" << sG.mean[g] << "\t" << sG.sd[g] << "\t" << sG.sd[g] / sqrt(trace_length) << "\t" << 1 << "\t"
                     << gene_lengths[g] << "\t"
                     << "NA"
                     << "\t"
@@ -1382,7 +1403,7 @@ int main(int argc, char **argv)
 
     stage.mark("summary columns");
     // ---- .mmseq (src/mmseq.cpp:1469-1554)
-    ofs.open((output_base + ".mmseq").c_str());
+    ofstream ofs((opt.output_base + ".mmseq").c_str());
     ofs << "# Mapped fragments: " << numbermappedreads << endl;
     ofs << "feature_id\tlog_mu\tsd\tmcse\tiact\teffective_length\ttrue_length\tunique_hits\tmean_proportion\tmean_probit_proportion\tsd_"
            "probit_proportion\tlog_mu_em\tobserved\tntranscripts\t";
@@ -1390,34 +1411,35 @@ int main(int argc, char **argv)
     pct_header(ofs, "percentiles_proportion", "\n");
     // (the rows are formatted in parallel, a slice of the list per thread into a stream of its own with the default formatting of
     // the file stream, and written in order; the gene table, which shares nothing with this one, is written by a thread of its own)
-    (void)obs_of(string());   // the name table exists before threads read it
     auto mmseq_row = [&](ostream &o, const string &name) {
-        const int32_t t = obs_of(name);
+        const int32_t t = obs.of(name);
         if (t >= 0) {
-            o << name << "\t" << meanmu[t] << "\t" << sd[t] << "\t" << mumcse[t] << "\t" << iact[t] << "\t" << len_of(name) << "\t"
-                << seqlen_of(name) << "\t" << unique_hits[t] << "\t" << meanprop[t] << "\t" << meanprobitprop[t] << "\t"
-                << sdprobitprop[t] << "\t" << log(mu_em[t]) << "\t"
+            o << name << "\t" << sT.mean[t] << "\t" << sT.sd[t] << "\t" << sT.mcse[t] << "\t" << sT.iact[t] << "\t" << hdr.len_of(name) << "\t"
+                << hdr.seqlen_of(name) << "\t" << uh.transcript[t] << "\t" << pT.mean[t] << "\t" << pT.probit_mean[t] << "\t"
+                << pT.probit_sd[t] << "\t" << log(mu_em[t]) << "\t"
                 << "1"
-                << "\t" << gene_size_of(name) << "\t";
+                << "\t" << hdr.gene_size_of(name) << "\t";
             join_pct(o, pct_row(sT.pct, t), "\t");
             join_pct(o, pct_row(pT.pct, t), "\n");
         } else {
+            const uint32_t v = layout.simu_of(name);
             o << name << "\t" << prior_logmu(name) << "\t" << sqrtpolygalpha << "\t"
                 << "0"
                 << "\t"
                 << "1"
-                << "\t" << len_of(name) << "\t" << seqlen_of(name) << "\t" << 0 << "\t" << pV.mean[simu_of(name)] << "\t"
-                << pV.probit_mean[simu_of(name)] << "\t" << pV.probit_sd[simu_of(name)] << "\t"
+                << "\t" << hdr.len_of(name) << "\t" << hdr.seqlen_of(name) << "\t" << 0 << "\t" << pV.mean[v] << "\t"
+                << pV.probit_mean[v] << "\t" << pV.probit_sd[v] << "\t"
                 << "NA"
                 << "\t"
                 << "0"
-                << "\t" << gene_size_of(name) << "\t";
-            join_pct(o, pct_row(sV.pct, simu_of(name)), "\t");
-            join_pct(o, pct_row(pV.pct, simu_of(name)), "\n");
+                << "\t" << hdr.gene_size_of(name) << "\t";
+            join_pct(o, pct_row(sV.pct, v), "\t");
+            join_pct(o, pct_row(pV.pct, v), "\n");
         }
         };
-    std::thread gene_table([&]() { write_gene_table(); });
+    JoiningThread gene_table([&]() { write_gene_table(); });
     {
+        const vector<string> &transcriptList = hdr.transcriptList;
         const int tt = max(1, min(omp_get_max_threads(), (int)(transcriptList.size() / 4096) + 1));
         vector<string> parts((size_t)tt);
 #pragma omp parallel num_threads(tt)
@@ -1433,19 +1455,19 @@ int main(int argc, char **argv)
     ofs.close(); ofs.clear();
 
     // ---- .identical.mmseq (src/mmseq.cpp:1556-1613)
-    ofs.open((output_base + ".identical.mmseq").c_str());
+    ofs.open((opt.output_base + ".identical.mmseq").c_str());
     ofs << "# Mapped fragments: " << numbermappedreads << endl;
     ofs << "feature_id\tlog_mu\tsd\tmcse\tiact\teffective_length\ttrue_length\tunique_hits\tobserved\tntranscripts\t";
     pct_header(ofs, "percentiles", "\n");
     for (size_t v = 0; v < nI; ++v) {
-        const vector<string> &set = identical_transcripts[v];
-        const bool fin = isfinite(meanmu_identical[v]);
+        const vector<string> &set = hdr.identical_transcripts[v];
+        const bool fin = isfinite(sI.mean[v]);
         for (auto &name : set) {
             ofs << name;
             if (name.compare(set.back()) != 0) ofs << "+";
             else if (fin)
-                ofs << "\t" << meanmu_identical[v] << "\t" << sd_identical[v] << "\t" << mumcse_identical[v] << "\t" << iact_identical[v] << "\t"
-                    << sidLen[set.front()] << "\t" << sidSeqLen[set.front()] << "\t" << identical_unique_hits[v] << "\t"
+                ofs << "\t" << sI.mean[v] << "\t" << sI.sd[v] << "\t" << sI.mcse[v] << "\t" << sI.iact[v] << "\t"
+                    << hdr.len_of(set.front()) << "\t" << hdr.seqlen_of(set.front()) << "\t" << uh.identical[v] << "\t"
                     << "1"
                     << "\t" << set.size() << "\t";
             else
@@ -1453,7 +1475,7 @@ int main(int argc, char **argv)
                     << "0"
                     << "\t"
                     << "NA"
-                    << "\t" << sidLen[set.front()] << "\t" << sidSeqLen[set.front()] << "\t" << 0 << "\t"
+                    << "\t" << hdr.len_of(set.front()) << "\t" << hdr.seqlen_of(set.front()) << "\t" << 0 << "\t"
                     << "0"
                     << "\t" << set.size() << "\t";
         }
@@ -1461,67 +1483,162 @@ int main(int argc, char **argv)
         else for (size_t i = 0; i < nP; i++) ofs << "NA" << (i == nP - 1 ? "\n" : ",");
     }
     ofs.close(); ofs.clear();
+}
 
-    gene_table.join();
-
-    // ---- the convergence tables: the rows of .mmseq, .identical.mmseq and .gene.mmseq, in their order, with their feature ids
-    if (convergence) {
-        auto conv_head = [&](ostream &o) {
-            o << "# chains " << chains << ", samples per chain " << trace_length << endl;
-            o << "feature_id\trhat\tess_bulk\tess_tail" << endl;
-        };
-        auto conv_row = [&](ostream &o, const Conv &c, size_t i) { o << "\t" << c.rhat[i] << "\t" << c.ess_bulk[i] << "\t" << c.ess_tail[i] << "\n"; };
-        ofs.open((output_base + ".convergence").c_str());
-        conv_head(ofs);
-        for (auto &name : transcriptList) {
-            const int32_t t = obs_of(name);
-            ofs << name;
-            if (t >= 0) conv_row(ofs, cT, (size_t)t);
-            else conv_row(ofs, cV, simu_of(name));
-        }
-        ofs.close(); ofs.clear();
-        ofs.open((output_base + ".identical.convergence").c_str());
-        conv_head(ofs);
-        for (size_t v = 0; v < nI; ++v) {
-            const vector<string> &set = identical_transcripts[v];
-            for (auto &name : set) { ofs << name; if (name.compare(set.back()) != 0) ofs << "+"; } // (the id of .identical.mmseq)
-            conv_row(ofs, cI, v);
-        }
-        ofs.close(); ofs.clear();
-        ofs.open((output_base + ".gene.convergence").c_str());
-        conv_head(ofs);
-        {
-            size_t g = 0;
-            for (auto &gt : gene2transcripts) { ofs << gt.first; conv_row(ofs, cG, g++); }
-        }
-        ofs.close(); ofs.clear();
-        stage.mark("convergence tables");
+// ---- the convergence tables: the rows of .mmseq, .identical.mmseq and .gene.mmseq, in their order, with their feature ids
+static void write_convergence_tables(const Options &opt, const Header &hdr, const Observed &obs, const SeriesLayout &layout, const ConvAll &c)
+{
+    auto conv_head = [&](ostream &o) {
+        o << "# chains " << opt.chains << ", samples per chain " << trace_length << endl;
+        o << "feature_id\trhat\tess_bulk\tess_tail" << endl;
+    };
+    auto conv_row = [&](ostream &o, const Conv &cv, size_t i) { o << "\t" << cv.rhat[i] << "\t" << cv.ess_bulk[i] << "\t" << cv.ess_tail[i] << "\n"; };
+    ofstream ofs((opt.output_base + ".convergence").c_str());
+    conv_head(ofs);
+    for (auto &name : hdr.transcriptList) {
+        const int32_t t = obs.of(name);
+        ofs << name;
+        if (t >= 0) conv_row(ofs, c.T, (size_t)t);
+        else conv_row(ofs, c.V, layout.simu_of(name));
     }
+    ofs.close(); ofs.clear();
+    ofs.open((opt.output_base + ".identical.convergence").c_str());
+    conv_head(ofs);
+    for (size_t v = 0; v < hdr.identical_transcripts.size(); ++v) {
+        ofs << layout.identical_ids[v]; // (the id of .identical.mmseq)
+        conv_row(ofs, c.I, v);
+    }
+    ofs.close(); ofs.clear();
+    ofs.open((opt.output_base + ".gene.convergence").c_str());
+    conv_head(ofs);
+    size_t g = 0;
+    for (auto &gt : hdr.gene2transcripts) { ofs << gt.first; conv_row(ofs, c.G, g++); }
+}
 
+static void print_parameters(const Options &opt, int max_threads)
+{
+    cout << "Running mmseq with parameters:\n"
+         << "  alpha:         " << opt.alpha << endl
+         << "  beta:          " << opt.beta << endl
+         << "  max_em_iter:   " << opt.max_em_iter << endl
+         << "  epsilon:       " << opt.epsilon << endl
+         << "  gibbs_iter:    " << opt.gibbs_iter << endl
+         << "  gibbs_ss:      " << opt.gibbs_ss << endl
+         << "  seed[0]:       " << opt.seed << endl
+         << "  debug:         " << opt.debug << endl
+         << "  threads:       " << max_threads << endl
+         << "  device:        " << opt.device << " (HIP, libmmgibbs ABI " << mmg_abi_version() << ")" << endl
+         << "  gpus:          " << opt.gpus << endl
+         << "  chains:        " << opt.chains << endl;
+}
+
+static void print_output_files(const Options &opt)
+{
     cout << "done." << endl;
     cout << "Output files: " << endl
-         << "  " << output_base << ".mmseq" << endl
-         << "  " << output_base << ".identical.mmseq" << endl
-         << "  " << output_base << ".gene.mmseq" << endl;
-    cout << "  " << output_base << ".M" << endl << "  " << output_base << ".k" << endl << endl;
-    cout << "  " << output_base << ".trace_gibbs.gz" << endl
-         << "  " << output_base << ".identical.trace_gibbs.gz" << endl
-         << "  " << output_base << ".gene.trace_gibbs.gz" << endl
-         << "  " << output_base << ".prop.trace_gibbs.gz" << endl
+         << "  " << opt.output_base << ".mmseq" << endl
+         << "  " << opt.output_base << ".identical.mmseq" << endl
+         << "  " << opt.output_base << ".gene.mmseq" << endl;
+    cout << "  " << opt.output_base << ".M" << endl << "  " << opt.output_base << ".k" << endl << endl;
+    cout << "  " << opt.output_base << ".trace_gibbs.gz" << endl
+         << "  " << opt.output_base << ".identical.trace_gibbs.gz" << endl
+         << "  " << opt.output_base << ".gene.trace_gibbs.gz" << endl
+         << "  " << opt.output_base << ".prop.trace_gibbs.gz" << endl
          << endl;
-    if (debug) {
+    if (opt.debug) {
         cout << endl
-             << "  " << output_base << ".trace_em.gz" << endl
-             << "  " << output_base << ".sharedcounts" << endl
-             << "  " << output_base << ".Mt-nodups" << endl
-             << "  " << output_base << ".doublehits" << endl
-             << "  " << output_base << ".dupIDs" << endl;
+             << "  " << opt.output_base << ".trace_em.gz" << endl
+             << "  " << opt.output_base << ".sharedcounts" << endl
+             << "  " << opt.output_base << ".Mt-nodups" << endl
+             << "  " << opt.output_base << ".doublehits" << endl
+             << "  " << opt.output_base << ".dupIDs" << endl;
     }
-    stage.mark("write tables");
-    release_device();
+}
+
+// The stages in order.  Declaration order is release order reversed: on an Exit the trace writers stop first, then the library
+// handles go, then the .k / .M writer and the device warm-up thread are joined.
+static int run(int argc, char **argv)
+{
+    StageTimer stage;
+    if (!getenv("OMP_NUM_THREADS")) { // an explicit thread count is the user's (src/mmseq.cpp:323 prints it); otherwise respect the quota
+        const int q = cpu_quota();
+        if (q > 0 && q < omp_get_max_threads()) omp_set_num_threads(q);
+    }
+    const int max_threads = omp_get_max_threads();
+    const Options opt = parse_options(argc, argv);
+    HitsfileReader hitsfileReader(opt.hits_file);
+    print_parameters(opt, max_threads);
+
+    // The HIP runtime, the device context and the library's code object are brought up while the hits file is read (they are first
+    // needed at the device problem build, where they used to cost about two seconds of an otherwise idle GPU): one tiny kernel
+    // launch on a thread of its own.  Its result is ignored -- a device that cannot be used is reported by mmg_problem_create.
+    // Every way out of run() joins it first: exit() under a thread that is still INSIDE the runtime's initialisation tears the
+    // runtime down under its feet (found by tools/hitsio_fuzz.py: 7 of 800 runs on damaged headers ended in the sanitizer's allocator
+    // instead of with exit code 1).
+    JoiningThread device_warmup([device = opt.device]() {
+        const uint32_t ctr[4] = {0, 0, 0, 0}, key[2] = {0, 0};
+        uint32_t out[6];
+        (void)mmg_selftest_philox(device, ctr, key, out);
+    });
+    const Header hdr = read_header(hitsfileReader);
+    const Hits hits = ingest(hitsfileReader, opt.hits_file, hdr.transcriptList.size(), stage.on);
+    stage.mark("read hits file + collapse");
+    const vector<double> l = effective_lengths(hdr, hits);
+    const vector<vector<int>> counts_shared = opt.debug ? shared_counts(hits) : vector<vector<int>>();
+    stage.mark("l");
+    const Observed obs(hdr, hits);
+    UniqueHits uh = count_unique_hits(hdr, hits, obs);
+    stage.mark("unique hits (sets, genes)");
+    JoiningThread km_writer = start_km_writer(opt.output_base, hits, obs);
+    if (opt.debug) write_debug_files(opt.output_base, hdr, hits, obs, counts_shared);
+    stage.mark("start the .k .M writer");
+    {
+        Device dev;
+        vector<double> mu(hits.n(), 0.0);
+        uh.transcript.assign(hits.n(), 0);
+        dev.prob = build_problem(opt, hdr, hits, obs, l, device_warmup, stage, mu, uh.transcript);
+        spread(opt, dev, mu, stage);
+        const vector<double> mu_em = run_em(opt, obs, dev, std::move(mu), stage);
+        stage.mark("EM");
+        const SeriesLayout layout = series_layout(opt, hdr, hits, obs);
+        const Chains ch = start_chains(opt, dev, mu_em, layout);
+        TraceWriters writers;   // (stopped and joined before the summary and samplers they read are released)
+        run_gibbs(opt, obs, layout, dev, ch, writers, stage);
+        const Pooled pooled = pool_moments(opt, dev, ch, hits.n());
+        cout << "Amalgamating transcripts and calculating summary statistics..." << flush;
+        // ---- posterior summary on the device (src/mmseq.cpp:927-1363): the derived traces were computed while the chain ran; what is
+        //      left are the per-series columns -- percentiles, log means, Sokal -- of which only the columns come back.
+        mmg_summary *summ = ch.summ.get();
+        MMG_TRY(mmg_summary_finish(summ));
+        stage.mark("device summary");
+        ConvAll conv;
+        if (opt.convergence) {
+            conv = fetch_convergence(ch, layout, hits.n());
+            stage.mark("convergence diagnostics");
+        }
+        write_tables(opt, hdr, hits, obs, uh, mu_em, layout, ch, pooled, stage);
+        if (opt.convergence) {
+            write_convergence_tables(opt, hdr, obs, layout, conv);
+            stage.mark("convergence tables");
+        }
+        print_output_files(opt);
+        stage.mark("write tables");
+        // (the writers fetch the last 1/64 of the rows behind the loop's last check: a failure there -- a HIP error in a row fetch --
+        // would leave a valid but truncated trace file; it ends the run like any other)
+        writers.finish();
+    }   // the summary, the samplers, the problems and the group are released here, once the trace writers are done
     stage.mark("trace files: the rest");
-    if (km_writer.joinable()) km_writer.join();
+    km_writer.join();
     stage.mark("wait for the .k .M writer");
     stage.total();
     return 0;
+}
+
+int main(int argc, char **argv)
+{
+    try {
+        return run(argc, argv);
+    } catch (const Exit &e) {
+        return e.code;
+    }
 }

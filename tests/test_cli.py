@@ -105,6 +105,8 @@ def test_without_device_fails_loudly_after_writing_k_and_M(tmp_path):
     p.write_bytes(H.write_hits_text(h))
     r = run([str(p), str(tmp_path / "out")])
     assert r.returncode == 1 and b"no HIP device available" in r.stderr
+    # the whole message, the failing call's text included, as the CLI has always printed it
+    assert r.stderr.endswith(b"Error: no HIP device available: libmmgibbs has no CPU fallback (mmg_problem_create(&pd, device, &prob))\n")
     g = H.ingest(h)
     assert (tmp_path / "out.k").read_text().split() == [str(v) for v in g["k"]]     # src/mmseq.cpp:682-684
     lines = (tmp_path / "out.M").read_text().split("\n")
@@ -260,6 +262,29 @@ def test_runs_are_reproducible(tmp_path, gpu):
         assert run([str(p), out, ], timeout=300, env=dict(os.environ, OMP_NUM_THREADS=str(1 + 3 * i))).returncode == 0
         outs.append(open(out + ".mmseq").read() + gzip.open(out + ".trace_gibbs.gz", "rt").read())
     assert outs[0] == outs[1]          # independent of host thread count and of run (cf. src/mmseq.cpp:834-838)
+
+
+@pytest.mark.gpu
+def test_trace_file_that_cannot_be_opened_fails_the_run_after_writing_k_and_M(tmp_path, gpu):
+    """A trace writer runs on a worker thread: when it cannot open its file it records the failure, and the main thread reports it
+    and leaves with exit code 1 -- after the .k / .M writer has finished both files, and before any table is written."""
+    h = dataset(n_reads=1500)
+    p = tmp_path / "in.hits"
+    p.write_bytes(H.write_hits_text(h))
+    blocked = tmp_path / "out.trace_gibbs.gz"
+    blocked.mkdir()                                  # a directory where the trace file goes: fopen fails
+    r = run(["-gibbs_iter", "2048", str(p), str(tmp_path / "out")], timeout=300)
+    assert r.returncode == 1, r.stderr.decode()
+    assert ("Error: cannot open %s for writing." % blocked).encode() in r.stderr
+    g = H.ingest(h)
+    assert (tmp_path / "out.k").read_text().split() == [str(v) for v in g["k"]]
+    lines = (tmp_path / "out.M").read_text().split("\n")
+    assert lines[0] == "#" + "".join("\t" + s for s in g["index_sid"])
+    assert lines[1:-1] == ["%d\t%d" % (i, c) for i, r_ in enumerate(g["rows"]) for c in r_]
+    # (the writer records its failure when it starts, right after the sampler is created; the Gibbs loop checks for worker failures
+    # at each of its 64 chunks and once after it, so the run stops before the tables.  A failure recorded only after that last check
+    # would surface behind the tables instead -- not what happens to a file that cannot be opened at all)
+    assert not (tmp_path / "out.mmseq").exists()
 
 
 def config1_dataset(orc):
