@@ -547,6 +547,31 @@ int mmg_diff_info(mmg_diff *h, int32_t *flags, uint32_t *n_classes, uint32_t *ba
 int mmg_diff_device_bytes(mmg_diff *h, uint64_t *bytes);
 void mmg_diff_destroy(mmg_diff *h);
 
+/* ---- mmdiff, polytomous: J alternatives against one model 0 on one handle ------------------------------------------------
+ * Comparison j (0 <= j < J <= 16) is model 0 against alternative j, and its chain is bit for bit the chain of an mmg_diff handle
+ * created from the same y, e, M, P0, alternative and seed and driven the same way: the stream key holds no comparison index.  y, e,
+ * M and P0 are held once; every launch covers all comparisons.  Additive in ABI version 8. */
+typedef struct mmg_diff_poly mmg_diff_poly;
+/* As mmg_diff_create, with C0: [N] the classes under model 0, L1: [J] the columns of each alternative's P1, P1: the J matrices
+ * [N][L1[j]] one after the other, C1: [J][N] the classes under each alternative. */
+int mmg_diff_poly_create(int device, uint32_t n_features, uint32_t n_samples, const double *y, const double *e, uint32_t K, const double *M,
+                         uint32_t L0, const double *P0, const int32_t *C0, uint32_t J, const uint32_t *L1, const double *P1,
+                         const int32_t *C1, double d, double s, double pdash, int fixalpha, uint64_t seed, mmg_diff_poly **out);
+int mmg_diff_poly_burnin(mmg_diff_poly *h, uint32_t iters);
+/* One tuning batch for every comparison that has not ended tuning.  untuned[J]: the features of comparison j still untuned after the
+ * batch's tuning step (0 for a comparison that had ended before).  A comparison whose count is 0 has ended: it takes no part in later
+ * batches and keeps its batch count.  ended[J] (may be NULL): 1 for the comparisons that have ended, this batch included.  The caller
+ * stops at its batch limit; mmg_diff_poly_sample then starts every comparison at its own index, burnin + 128 * (its batches). */
+int mmg_diff_poly_tune_batch(mmg_diff_poly *h, uint32_t *untuned, int32_t *ended);
+int mmg_diff_poly_sample(mmg_diff_poly *h, uint32_t iters);
+/* comparison j's results, laid out as mmg_diff_get_results lays them out (eta: [L0 + L1[j]][F]) */
+int mmg_diff_poly_get_results(mmg_diff_poly *h, uint32_t j, double *gamma_mean, double *logitp, double *alpha, double *beta, double *eta);
+/* comparison j: flags[3] = (M nil, P0 nil, P1 nil), n_classes[2], its tuning batches, whether it has ended tuning; any pointer may be NULL */
+int mmg_diff_poly_info(mmg_diff_poly *h, uint32_t j, int32_t *flags, uint32_t *n_classes, uint32_t *batches, int32_t *ended);
+/* 8 (2 F N + N K + N L0 + sum_j (F nslot_j + N L1_j)) + 4 sum_j (2 N + 2 F) + 488 J bytes (nslot_j: DESIGN.md section 10) */
+int mmg_diff_poly_device_bytes(mmg_diff_poly *h, uint64_t *bytes);
+void mmg_diff_poly_destroy(mmg_diff_poly *h);
+
 #ifdef __cplusplus
 }
 #endif

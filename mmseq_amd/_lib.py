@@ -148,6 +148,16 @@ SYMBOLS = {
     "mmg_diff_info": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmg_diff_device_bytes": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mmg_diff_destroy": (None, [C.c_void_p]),
+    "mmg_diff_poly_create": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
+                                       C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int,
+                                       C.c_uint64, C.c_void_p]),
+    "mmg_diff_poly_burnin": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "mmg_diff_poly_tune_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmg_diff_poly_sample": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "mmg_diff_poly_get_results": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmg_diff_poly_info": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmg_diff_poly_device_bytes": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mmg_diff_poly_destroy": (None, [C.c_void_p]),
     "mmg_collapse_summarize": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_double,
                                          C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),

@@ -40,6 +40,83 @@ static bool df_nil(const double *X, uint32_t N, uint32_t cols)
 
 static inline unsigned df_blocks(uint32_t F) { return (F + DF_BLOCK - 1) / DF_BLOCK; }
 
+// the classes of one model, C[i * stride]: labels 0 .. *nc - 1, every one of them used
+static int df_classes(const int32_t *C, uint32_t stride, uint32_t N, int *nc)
+{
+    std::vector<int> seen(DF_CMAX, 0);
+    *nc = 0;
+    for (uint32_t i = 0; i < N; ++i) {
+        const int c = C[i * stride];
+        if (c < 0 || c >= DF_CMAX) return fail(MMG_ERR_ARG, "class labels must be between 0 and 15");
+        seen[c] = 1;
+        *nc = c + 1 > *nc ? c + 1 : *nc;
+    }
+    for (int c = 0; c < *nc; ++c)
+        if (!seen[c]) return fail(MMG_ERR_ARG, "the class labels of each model must be 0, 1, ..., n - 1 without gaps");
+    return MMG_OK;
+}
+
+// the slot offsets of one comparison's state and workspace (p.K and p.Mnil set); the number of slots per feature:
+// for each model 11 + 6 K + 11 L + 5 classes, then 3, then (M not nil) 5 K^2 + 2 K, then 2 max(classes)
+static size_t df_layout(DiffParams &p, const uint32_t L[2], const int nc[2])
+{
+    const int K = p.K;
+    int o = 0;
+    for (int mi = 0; mi < 2; ++mi) {
+        DiffModel &m = p.m[mi];
+        const int Lm = (int)L[mi];
+        m.L = Lm; m.nc = nc[mi];
+        for (int *slot : {&m.alpha, &m.A, &m.Va, &m.aS, &m.aSS, &m.aN, &m.rho, &m.Q, &m.R, &m.rS, &m.rlS}) *slot = o++;
+        for (int *slot : {&m.beta, &m.B, &m.Vb, &m.bS, &m.bSS, &m.bN}) { *slot = o; o += K; }
+        for (int *slot : {&m.eta, &m.Fm, &m.Ve, &m.eS, &m.eSS, &m.eN, &m.lam, &m.Dm, &m.Si, &m.lS, &m.llS}) { *slot = o; o += Lm; }
+        for (int *slot : {&m.sig, &m.J, &m.Lm, &m.sS, &m.slS}) { *slot = o; o += m.nc; }
+    }
+    p.gsum = o++; p.logitp = o++; p.LOsum = o++;
+    const int KK = p.Mnil ? 0 : K * K, Kv = p.Mnil ? 0 : K, ncmax = nc[0] > nc[1] ? nc[0] : nc[1];
+    for (int *slot : {&p.wG, &p.wLg, &p.wLi, &p.wV, &p.wLv}) { *slot = o; o += KK; }
+    for (int *slot : {&p.wt, &p.wz}) { *slot = o; o += Kv; }
+    for (int *slot : {&p.wlprop, &p.wsum}) { *slot = o; o += ncmax; }
+    return (size_t)o;
+}
+
+// the posterior means of one comparison from its state block, as mmg_diff_get_results documents them
+static int df_results(const DiffParams &p, const double *d_st, size_t F, uint32_t K, const uint32_t L[2], uint32_t sampled, double *gamma_mean,
+                      double *logitp, double *alpha, double *beta, double *eta)
+{
+    auto slot = [&](int o, std::vector<double> &v) {
+        v.resize(F);
+        return hipMemcpy(v.data(), d_st + (size_t)o * F, F * 8, hipMemcpyDeviceToHost);
+    };
+    std::vector<double> a, b;
+    // the means as BMS::gammamean / alphamean / betamean / etamean form them: sum / count, on the host
+    if (gamma_mean) {
+        HIP_TRY(slot(p.gsum, a));
+        for (size_t f = 0; f < F; ++f) gamma_mean[f] = a[f] / (double)sampled;
+    }
+    if (logitp) {
+        HIP_TRY(slot(p.logitp, a));
+        for (size_t f = 0; f < F; ++f) logitp[f] = a[f];
+    }
+    for (int mi = 0; mi < 2; ++mi) {
+        const DiffModel &m = p.m[mi];
+        if (alpha) {
+            HIP_TRY(slot(m.aS, a)); HIP_TRY(slot(m.aN, b));
+            for (size_t f = 0; f < F; ++f) alpha[mi * F + f] = a[f] / b[f];
+        }
+        if (beta)
+            for (uint32_t k = 0; k < K; ++k) {
+                HIP_TRY(slot(m.bS + (int)k, a)); HIP_TRY(slot(m.bN + (int)k, b));
+                for (size_t f = 0; f < F; ++f) beta[((size_t)mi * K + k) * F + f] = a[f] / b[f];
+            }
+        if (eta)
+            for (uint32_t l = 0; l < L[mi]; ++l) {
+                HIP_TRY(slot(m.eS + (int)l, a)); HIP_TRY(slot(m.eN + (int)l, b));
+                for (size_t f = 0; f < F; ++f) eta[((mi ? L[0] : 0) + l) * F + f] = a[f] / b[f];
+            }
+    }
+    return MMG_OK;
+}
+
 extern "C" int mmg_diff_create(int device, uint32_t F, uint32_t N, const double *y, const double *e, uint32_t K, const double *M,
                                uint32_t L0, const double *P0, uint32_t L1, const double *P1, const int32_t *C, double d, double s,
                                double pdash, int fixalpha, uint64_t seed, mmg_diff **out)
@@ -58,15 +135,8 @@ extern "C" int mmg_diff_create(int device, uint32_t F, uint32_t N, const double 
     if (!finite(M, (uint64_t)N * K) || !finite(P0, (uint64_t)N * L0) || !finite(P1, (uint64_t)N * L1)) return fail(MMG_ERR_ARG, "M, P0 and P1 must be finite");
     int nc[2] = {0, 0};
     for (int mi = 0; mi < 2; ++mi) {
-        std::vector<int> seen(DF_CMAX, 0);
-        for (uint32_t i = 0; i < N; ++i) {
-            const int c = C[i * 2 + mi];
-            if (c < 0 || c >= DF_CMAX) return fail(MMG_ERR_ARG, "class labels must be between 0 and 15");
-            seen[c] = 1;
-            nc[mi] = c + 1 > nc[mi] ? c + 1 : nc[mi];
-        }
-        for (int c = 0; c < nc[mi]; ++c)
-            if (!seen[c]) return fail(MMG_ERR_ARG, "the class labels of each model must be 0, 1, ..., n - 1 without gaps");
+        const int rc = df_classes(C + mi, 2, N, &nc[mi]);
+        if (rc) return rc;
     }
     int rc = require_device(device);
     if (rc) return rc;
@@ -79,22 +149,9 @@ extern "C" int mmg_diff_create(int device, uint32_t F, uint32_t N, const double 
     p.fixalpha = fixalpha ? 1 : 0;
     p.d = d; p.s = s; p.v_beta = fixalpha ? 25.0 : 4.0;
     p.seed = seed;
-    int o = 0;
-    for (int mi = 0; mi < 2; ++mi) {
-        DiffModel &m = p.m[mi];
-        const int Lm = (int)h->L[mi];
-        m.L = Lm; m.nc = nc[mi]; m.Pnil = df_nil(mi ? P1 : P0, N, Lm) ? 1 : 0;
-        for (int *slot : {&m.alpha, &m.A, &m.Va, &m.aS, &m.aSS, &m.aN, &m.rho, &m.Q, &m.R, &m.rS, &m.rlS}) *slot = o++;
-        for (int *slot : {&m.beta, &m.B, &m.Vb, &m.bS, &m.bSS, &m.bN}) { *slot = o; o += (int)K; }
-        for (int *slot : {&m.eta, &m.Fm, &m.Ve, &m.eS, &m.eSS, &m.eN, &m.lam, &m.Dm, &m.Si, &m.lS, &m.llS}) { *slot = o; o += Lm; }
-        for (int *slot : {&m.sig, &m.J, &m.Lm, &m.sS, &m.slS}) { *slot = o; o += m.nc; }
-    }
-    p.gsum = o++; p.logitp = o++; p.LOsum = o++;
-    const int KK = p.Mnil ? 0 : (int)(K * K), Kv = p.Mnil ? 0 : (int)K, ncmax = nc[0] > nc[1] ? nc[0] : nc[1];
-    for (int *slot : {&p.wG, &p.wLg, &p.wLi, &p.wV, &p.wLv}) { *slot = o; o += KK; }
-    for (int *slot : {&p.wt, &p.wz}) { *slot = o; o += Kv; }
-    for (int *slot : {&p.wlprop, &p.wsum}) { *slot = o; o += ncmax; }
-    h->nslot = (size_t)o;
+    p.m[0].Pnil = df_nil(P0, N, L0) ? 1 : 0;
+    p.m[1].Pnil = df_nil(P1, N, L1) ? 1 : 0;
+    h->nslot = df_layout(p, h->L, nc);
 
     auto dalloc = [&](auto &buf, uint64_t count) {
         HIPE_TRY(buf.alloc(count));
@@ -196,39 +253,7 @@ extern "C" int mmg_diff_get_results(mmg_diff *h, double *gamma_mean, double *log
     if (!h) return fail(MMG_ERR_ARG, "NULL argument");
     if (!h->sampled) return fail(MMG_ERR_STATE, "mmg_diff_get_results before mmg_diff_sample");
     HIP_TRY(hipSetDevice(h->device));
-    const size_t F = h->F;
-    auto slot = [&](int o, std::vector<double> &v) {
-        v.resize(F);
-        return hipMemcpy(v.data(), h->d_st.get() + (size_t)o * F, F * 8, hipMemcpyDeviceToHost);
-    };
-    std::vector<double> a, b;
-    // the means as BMS::gammamean / alphamean / betamean / etamean form them: sum / count, on the host
-    if (gamma_mean) {
-        HIP_TRY(slot(h->p.gsum, a));
-        for (size_t f = 0; f < F; ++f) gamma_mean[f] = a[f] / (double)h->sampled;
-    }
-    if (logitp) {
-        HIP_TRY(slot(h->p.logitp, a));
-        for (size_t f = 0; f < F; ++f) logitp[f] = a[f];
-    }
-    for (int mi = 0; mi < 2; ++mi) {
-        const DiffModel &m = h->p.m[mi];
-        if (alpha) {
-            HIP_TRY(slot(m.aS, a)); HIP_TRY(slot(m.aN, b));
-            for (size_t f = 0; f < F; ++f) alpha[mi * F + f] = a[f] / b[f];
-        }
-        if (beta)
-            for (uint32_t k = 0; k < h->K; ++k) {
-                HIP_TRY(slot(m.bS + (int)k, a)); HIP_TRY(slot(m.bN + (int)k, b));
-                for (size_t f = 0; f < F; ++f) beta[((size_t)mi * h->K + k) * F + f] = a[f] / b[f];
-            }
-        if (eta)
-            for (uint32_t l = 0; l < h->L[mi]; ++l) {
-                HIP_TRY(slot(m.eS + (int)l, a)); HIP_TRY(slot(m.eN + (int)l, b));
-                for (size_t f = 0; f < F; ++f) eta[((mi ? h->L[0] : 0) + l) * F + f] = a[f] / b[f];
-            }
-    }
-    return MMG_OK;
+    return df_results(h->p, h->d_st.get(), h->F, h->K, h->L, h->sampled, gamma_mean, logitp, alpha, beta, eta);
 }
 
 extern "C" int mmg_diff_info(mmg_diff *h, int32_t *flags, uint32_t *n_classes, uint32_t *batches)
@@ -248,3 +273,237 @@ extern "C" int mmg_diff_device_bytes(mmg_diff *h, uint64_t *bytes)
 }
 
 extern "C" void mmg_diff_destroy(mmg_diff *h) { delete h; }
+
+// ---- several alternatives against one model 0 on one handle -----------------------------------------------------------------
+// y / e^2 / M / P0 once; per comparison a DiffParams (in h_p and, for the kernels, in d_p), a state block, gam / tuned, P1 and a class
+// table.  The launches cover every comparison (grid.y); a comparison whose untuned count reached 0 leaves the tuning launches.
+static_assert(sizeof(DiffParams) == 480, "mmg_diff_poly_device_bytes is documented with this size (DESIGN.md section 10)");
+
+struct mmg_diff_poly {
+    struct Cmp {
+        uint32_t L1 = 0, batches = 0;
+        bool ended = false;
+        size_t nslot = 0;
+        DevBuf<double> d_st, d_P1;
+        DevBuf<int> d_C, d_gam, d_tuned;
+    };
+    DevStream st;
+    int device = 0;
+    uint32_t F = 0, N = 0, K = 0, L0 = 0, J = 0;
+    DevBuf<double> d_y, d_esq, d_M, d_P0;
+    std::vector<Cmp> cmp;
+    std::vector<DiffParams> h_p;
+    std::vector<uint32_t> h_off;
+    DevBuf<DiffParams> d_p;
+    DevBuf<uint32_t> d_off;   // [J] the iterations comparison c's tuning took (the start of its sampling stream index after burn-in)
+    DevBuf<int> d_cnt;        // [J]
+    uint32_t burnin = 0, batches = 0, sampled = 0;
+    bool burnt = false;
+    uint64_t device_bytes = 0;
+    dim3 grid() const { return dim3(df_blocks(F), J); }
+    ~mmg_diff_poly() { if (st) (void)hipStreamSynchronize(st.get()); }
+};
+
+extern "C" int mmg_diff_poly_create(int device, uint32_t F, uint32_t N, const double *y, const double *e, uint32_t K, const double *M,
+                                    uint32_t L0, const double *P0, const int32_t *C0, uint32_t J, const uint32_t *L1, const double *P1,
+                                    const int32_t *C1, double d, double s, double pdash, int fixalpha, uint64_t seed, mmg_diff_poly **out)
+{
+    if (!out || !y || !e || !M || !P0 || !C0 || !L1 || !P1 || !C1) return fail(MMG_ERR_ARG, "NULL argument");
+    *out = nullptr;
+    if (F == 0 || F > 0x7fffff00u / DF_BLOCK) return fail(MMG_ERR_ARG, "the number of features must be between 1 and 33554428");
+    if (N < 2 || N > (uint32_t)DF_NMAX) return fail(MMG_ERR_ARG, "the number of samples must be between 2 and 512");
+    if (K < 1 || K > (uint32_t)DF_KMAX) return fail(MMG_ERR_ARG, "M must have between 1 and 8 columns");
+    if (J < 1 || J > (uint32_t)DF_JMAX) return fail(MMG_ERR_ARG, "the number of comparisons must be between 1 and 16");
+    if (L0 < 1 || L0 > (uint32_t)DF_LMAX) return fail(MMG_ERR_ARG, "P0 and P1 must have between 1 and 16 columns");
+    uint64_t sumL1 = 0;
+    for (uint32_t c = 0; c < J; ++c) {
+        if (L1[c] < 1 || L1[c] > (uint32_t)DF_LMAX) return fail(MMG_ERR_ARG, "P0 and P1 must have between 1 and 16 columns");
+        sumL1 += L1[c];
+    }
+    if (!(d > 0) || !(s > 0) || !std::isfinite(d) || !std::isfinite(s) || !(pdash >= 0 && pdash <= 1))
+        return fail(MMG_ERR_ARG, "d and s must be positive and finite and pdash in [0, 1]");
+    auto finite = [](const double *x, uint64_t n) { for (uint64_t i = 0; i < n; ++i) if (!std::isfinite(x[i])) return false; return true; };
+    if (!finite(y, (uint64_t)F * N) || !finite(e, (uint64_t)F * N)) return fail(MMG_ERR_ARG, "y and e must be finite");
+    if (!finite(M, (uint64_t)N * K) || !finite(P0, (uint64_t)N * L0) || !finite(P1, (uint64_t)N * sumL1)) return fail(MMG_ERR_ARG, "M, P0 and P1 must be finite");
+    int nc0 = 0;
+    int rc = df_classes(C0, 1, N, &nc0);
+    if (rc) return rc;
+    std::vector<int> nc1(J, 0);
+    for (uint32_t c = 0; c < J; ++c)
+        if ((rc = df_classes(C1 + (size_t)c * N, 1, N, &nc1[c]))) return rc;
+    if ((rc = require_device(device))) return rc;
+
+    std::unique_ptr<mmg_diff_poly> h(new mmg_diff_poly());
+    h->device = device; h->F = F; h->N = N; h->K = K; h->L0 = L0; h->J = J;
+    h->cmp.resize(J);
+    h->h_p.resize(J);
+    h->h_off.assign(J, 0);
+    auto dalloc = [&](auto &buf, uint64_t count) {
+        HIPE_TRY(buf.alloc(count));
+        h->device_bytes += count * sizeof(*buf.get());
+        return hipSuccess;
+    };
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(h->st.create(hipStreamNonBlocking));
+    const hipStream_t st = h->st.get();
+    const uint64_t FN = (uint64_t)F * N;
+    HIP_TRY(dalloc(h->d_y, FN));
+    HIP_TRY(dalloc(h->d_esq, FN));
+    HIP_TRY(dalloc(h->d_M, (uint64_t)N * K));
+    HIP_TRY(dalloc(h->d_P0, (uint64_t)N * L0));
+    HIP_TRY(dalloc(h->d_p, J));
+    HIP_TRY(dalloc(h->d_off, J));
+    HIP_TRY(dalloc(h->d_cnt, J));
+    // y and e^2 transposed to [N][F], as mmg_diff_create holds them
+    std::vector<double> ty(FN), te(FN);
+    for (uint64_t f = 0; f < F; ++f)
+        for (uint64_t i = 0; i < N; ++i) {
+            ty[i * F + f] = y[f * N + i];
+            const double ei = e[f * N + i];
+            te[i * F + f] = ei * ei;
+        }
+    HIP_TRY(hipMemcpyAsync(h->d_y.get(), ty.data(), FN * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->d_esq.get(), te.data(), FN * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->d_M.get(), M, (size_t)N * K * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->d_P0.get(), P0, (size_t)N * L0 * 8, hipMemcpyHostToDevice, st));
+    std::vector<std::vector<int>> hC(J);   // (sources of asynchronous copies: alive until the synchronize below)
+    const double *P1c = P1;
+    for (uint32_t c = 0; c < J; ++c) {
+        mmg_diff_poly::Cmp &q = h->cmp[c];
+        DiffParams &p = h->h_p[c];
+        q.L1 = L1[c];
+        p.F = (int)F; p.N = (int)N; p.K = (int)K;
+        p.Mnil = df_nil(M, N, K) ? 1 : 0;
+        p.fixalpha = fixalpha ? 1 : 0;
+        p.d = d; p.s = s; p.v_beta = fixalpha ? 25.0 : 4.0;
+        p.seed = seed;
+        p.m[0].Pnil = df_nil(P0, N, L0) ? 1 : 0;
+        p.m[1].Pnil = df_nil(P1c, N, q.L1) ? 1 : 0;
+        const uint32_t L[2] = {L0, q.L1};
+        const int nc[2] = {nc0, nc1[c]};
+        q.nslot = df_layout(p, L, nc);
+        HIP_TRY(dalloc(q.d_st, (uint64_t)q.nslot * F));
+        HIP_TRY(dalloc(q.d_P1, (uint64_t)N * q.L1));
+        HIP_TRY(dalloc(q.d_C, (uint64_t)N * 2));
+        HIP_TRY(dalloc(q.d_gam, (uint64_t)F));
+        HIP_TRY(dalloc(q.d_tuned, (uint64_t)F));
+        hC[c].resize((size_t)N * 2);
+        for (uint32_t i = 0; i < N; ++i) { hC[c][i * 2] = C0[i]; hC[c][i * 2 + 1] = C1[(size_t)c * N + i]; }
+        HIP_TRY(hipMemcpyAsync(q.d_P1.get(), P1c, (size_t)N * q.L1 * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(q.d_C.get(), hC[c].data(), (size_t)N * 2 * 4, hipMemcpyHostToDevice, st));
+        p.M = h->d_M.get(); p.m[0].P = h->d_P0.get(); p.m[1].P = q.d_P1.get(); p.Cl = q.d_C.get();
+        p.y = h->d_y.get(); p.esq = h->d_esq.get(); p.st = q.d_st.get(); p.gam = q.d_gam.get(); p.tuned = q.d_tuned.get();
+        P1c += (size_t)N * q.L1;
+    }
+    HIP_TRY(hipMemcpyAsync(h->d_p.get(), h->h_p.data(), (size_t)J * sizeof(DiffParams), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(h->d_off.get(), 0, (size_t)J * 4, st));
+    const double logitp0 = std::log(pdash) - std::log(1.0 - pdash);
+    hipLaunchKernelGGL(k_dfp_init, h->grid(), dim3(DF_BLOCK), 0, st, h->d_p.get(), logitp0);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    *out = h.release();
+    return MMG_OK;
+}
+
+extern "C" int mmg_diff_poly_burnin(mmg_diff_poly *h, uint32_t iters)
+{
+    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
+    if (h->burnt) return fail(MMG_ERR_STATE, "the burn-in has run already");
+    if (iters == 0 || iters % 1024) return fail(MMG_ERR_ARG, "burn-in iterations must be a positive multiple of 1024");
+    HIP_TRY(hipSetDevice(h->device));
+    for (uint32_t t = 0; t < iters; t += DF_CHUNK) {
+        const uint32_t n = iters - t < DF_CHUNK ? iters - t : DF_CHUNK;
+        hipLaunchKernelGGL(k_dfp_run, h->grid(), dim3(DF_BLOCK), 0, h->st.get(), h->d_p.get(), h->d_off.get(), t, (int)t, (int)n, 0, DF_REC_FROM);
+    }
+    hipLaunchKernelGGL(k_dfp_pseudo, h->grid(), dim3(DF_BLOCK), 0, h->st.get(), h->d_p.get(), (double)(iters - DF_REC_FROM));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(h->st.get()));
+    h->burnin = iters;
+    h->burnt = true;
+    return MMG_OK;
+}
+
+extern "C" int mmg_diff_poly_tune_batch(mmg_diff_poly *h, uint32_t *untuned, int32_t *ended)
+{
+    if (!h || !untuned) return fail(MMG_ERR_ARG, "NULL argument");
+    if (!h->burnt) return fail(MMG_ERR_STATE, "mmg_diff_poly_tune_batch before mmg_diff_poly_burnin");
+    if (h->sampled) return fail(MMG_ERR_STATE, "mmg_diff_poly_tune_batch after sampling has started");
+    uint32_t active = 0;
+    for (uint32_t c = 0; c < h->J; ++c)
+        if (!h->cmp[c].ended) active |= 1u << c;
+    if (active) {
+        HIP_TRY(hipSetDevice(h->device));
+        HIP_TRY(hipMemsetAsync(h->d_cnt.get(), 0, (size_t)h->J * 4, h->st.get()));
+        const uint32_t it0 = h->burnin + h->batches * DF_BATCH;
+        hipLaunchKernelGGL(k_dfp_tune, h->grid(), dim3(DF_BLOCK), 0, h->st.get(), h->d_p.get(), active, it0, (int)h->batches, h->d_cnt.get());
+        HIP_TRY(hipGetLastError());
+        int cnt[DF_JMAX] = {0};
+        HIP_TRY(hipMemcpyAsync(cnt, h->d_cnt.get(), (size_t)h->J * 4, hipMemcpyDeviceToHost, h->st.get()));
+        HIP_TRY(hipStreamSynchronize(h->st.get()));
+        ++h->batches;
+        for (uint32_t c = 0; c < h->J; ++c) {
+            mmg_diff_poly::Cmp &q = h->cmp[c];
+            if (q.ended) { untuned[c] = 0; continue; }
+            q.batches = h->batches;
+            untuned[c] = (uint32_t)cnt[c];
+            if (cnt[c] == 0) q.ended = true;
+        }
+    } else {
+        for (uint32_t c = 0; c < h->J; ++c) untuned[c] = 0;
+    }
+    if (ended)
+        for (uint32_t c = 0; c < h->J; ++c) ended[c] = h->cmp[c].ended ? 1 : 0;
+    return MMG_OK;
+}
+
+extern "C" int mmg_diff_poly_sample(mmg_diff_poly *h, uint32_t iters)
+{
+    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
+    if (!h->burnt) return fail(MMG_ERR_STATE, "mmg_diff_poly_sample before mmg_diff_poly_burnin");
+    if (iters == 0) return fail(MMG_ERR_ARG, "iters must be positive");
+    HIP_TRY(hipSetDevice(h->device));
+    if (!h->sampled) {
+        // comparison c's sampling starts at its own running index, burnin + 128 * (its batches)
+        for (uint32_t c = 0; c < h->J; ++c) h->h_off[c] = h->cmp[c].batches * DF_BATCH;
+        HIP_TRY(hipMemcpyAsync(h->d_off.get(), h->h_off.data(), (size_t)h->J * 4, hipMemcpyHostToDevice, h->st.get()));
+    }
+    for (uint32_t j = 0; j < iters; j += DF_CHUNK) {
+        const uint32_t n = iters - j < DF_CHUNK ? iters - j : DF_CHUNK;
+        hipLaunchKernelGGL(k_dfp_run, h->grid(), dim3(DF_BLOCK), 0, h->st.get(), h->d_p.get(), h->d_off.get(), h->burnin + h->sampled + j, 0, (int)n, 2, 0);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(h->st.get()));
+    h->sampled += iters;
+    return MMG_OK;
+}
+
+extern "C" int mmg_diff_poly_get_results(mmg_diff_poly *h, uint32_t j, double *gamma_mean, double *logitp, double *alpha, double *beta, double *eta)
+{
+    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
+    if (j >= h->J) return fail(MMG_ERR_ARG, "no such comparison");
+    if (!h->sampled) return fail(MMG_ERR_STATE, "mmg_diff_poly_get_results before mmg_diff_poly_sample");
+    HIP_TRY(hipSetDevice(h->device));
+    const uint32_t L[2] = {h->L0, h->cmp[j].L1};
+    return df_results(h->h_p[j], h->cmp[j].d_st.get(), h->F, h->K, L, h->sampled, gamma_mean, logitp, alpha, beta, eta);
+}
+
+extern "C" int mmg_diff_poly_info(mmg_diff_poly *h, uint32_t j, int32_t *flags, uint32_t *n_classes, uint32_t *batches, int32_t *ended)
+{
+    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
+    if (j >= h->J) return fail(MMG_ERR_ARG, "no such comparison");
+    const DiffParams &p = h->h_p[j];
+    if (flags) { flags[0] = p.Mnil; flags[1] = p.m[0].Pnil; flags[2] = p.m[1].Pnil; }
+    if (n_classes) { n_classes[0] = (uint32_t)p.m[0].nc; n_classes[1] = (uint32_t)p.m[1].nc; }
+    if (batches) *batches = h->cmp[j].batches;
+    if (ended) *ended = h->cmp[j].ended ? 1 : 0;
+    return MMG_OK;
+}
+
+extern "C" int mmg_diff_poly_device_bytes(mmg_diff_poly *h, uint64_t *bytes)
+{
+    if (!h || !bytes) return fail(MMG_ERR_ARG, "NULL argument");
+    *bytes = h->device_bytes;
+    return MMG_OK;
+}
+
+extern "C" void mmg_diff_poly_destroy(mmg_diff_poly *h) { delete h; }

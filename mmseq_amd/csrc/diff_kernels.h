@@ -542,4 +542,52 @@ __global__ void k_df_pseudo(DiffParams p, double runlen)
 
 #undef DF_S
 
+// ---- several comparisons against one model 0 in one launch (mmg_diff_poly_*) -----------------------------------------------
+// ps[c] is comparison c's DiffParams: its own slot layout, state block, gam / tuned and class table; every one points at the same
+// y / esq / M / P0.  blockIdx.y picks the comparison, so the parameters are read through a wave-uniform address (scalar loads, as
+// the single-comparison kernels read theirs from the kernel arguments), and the grid is (blocks of F) x J.  The per-lane work is
+// df_iteration / df_tune / df_pseudo / df_init unchanged, and the stream key has no comparison in it: comparison c's chain is the
+// chain mmg_diff_* runs for the same inputs.
+constexpr int DF_JMAX = 16;    // comparisons per handle
+
+__global__ void k_dfp_init(const DiffParams *__restrict__ ps, double logitp0)
+{
+    const DiffParams &p = ps[blockIdx.y];
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f < p.F) df_init(p, f, logitp0);
+}
+
+// as k_df_run; comparison c's stream index starts at off[c] + it0 (off: the iterations its own tuning took, 0 in burn-in)
+__global__ void __launch_bounds__(DF_BLOCK) k_dfp_run(const DiffParams *__restrict__ ps, const uint32_t *__restrict__ off, uint32_t it0, int t0,
+                                                      int n, int mode, int rec_from)
+{
+    const DiffParams &p = ps[blockIdx.y];
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= p.F) return;
+    const uint32_t it = off[blockIdx.y] + it0;
+    for (int j = 0; j < n; ++j) {
+        const int t = t0 + j;
+        df_iteration(p, f, it + (uint32_t)j, mode == 0, mode == 2 || t >= rec_from);
+    }
+}
+
+// as k_df_tune, for the comparisons whose bit is set in `active` (the others have ended tuning: their blocks return at once).  Every
+// active comparison is at batch b: all started together and an ended one never resumes.  untuned[c] counts comparison c's features.
+__global__ void __launch_bounds__(DF_BLOCK) k_dfp_tune(const DiffParams *__restrict__ ps, uint32_t active, uint32_t it0, int b,
+                                                       int *__restrict__ untuned)
+{
+    if (!((active >> blockIdx.y) & 1u)) return;
+    const DiffParams &p = ps[blockIdx.y];
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= p.F) return;
+    if (df_tune(p, f, it0, b)) atomicAdd(untuned + blockIdx.y, 1);
+}
+
+__global__ void k_dfp_pseudo(const DiffParams *__restrict__ ps, double runlen)
+{
+    const DiffParams &p = ps[blockIdx.y];
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f < p.F) df_pseudo(p, f, runlen);
+}
+
 } // namespace mmg

@@ -3,6 +3,10 @@
 // per-feature MCMC (src/bms.cpp) on the device through the C ABI (include/mmgibbs.h: mmg_diff_*).  Deliberate differences from the
 // reference are listed in DESIGN.md section 10: keyed streams instead of one MT19937 per thread, a keyed shuffle for -permute, no
 // -tracedir, size caps, dlgamma for gsl_sf_lngamma.
+//
+// Polytomous model selection (the reference's recipe: one mmdiff run per alternative, then polyclass() of src/R/mmseq.R) is built in:
+// repeated -m runs J alternatives against one model 0 on one device handle (mmg_diff_poly_*), and -polyclass combines mmdiff tables on
+// the host alone.
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -10,6 +14,8 @@
 #include <cstdlib>
 #include <fstream>
 #include <iostream>
+#include <limits>
+#include <sstream>
 #include <string>
 #include <vector>
 
@@ -20,6 +26,7 @@ using namespace std;
 
 #define OUTLEN 1024
 #define MAXBATCHES 8192
+#define MAXMODELS 16   // alternatives (-m) in one run
 
 namespace {
 
@@ -61,12 +68,17 @@ void printUsage(ostream &out)
 {
     out << "Usage: mmdiff [OPTIONS...] [-de n1 n2 ... nC | -m matrices_file] mmseq_file1 mmseq_file2... > out.mmdiff" << endl
         << "       matrices_file contains M P0 P1 each separated by an empty line" << endl
+        << "       mmdiff [OPTIONS...] [-prior P0,...,PJ] [-polyout BASE] -m alt1 -m alt2 [-m ...] mmseq_file1 mmseq_file2... > out.polyclass" << endl
+        << "       mmdiff -polyclass [-prior P0,...,PJ] a.mmdiff b.mmdiff [...] > out.polyclass" << endl
         << endl;
     out << "Mandatory arguments:" << endl
         << "  ONE OF:" << endl
         << "  -de INT INT...    simple differential expression between several groups of samples, where" << endl
         << "                    each INT corresponds to a grouping of MMSEQ files into one condition" << endl
-        << "  -m STRING         path to matrices file specifying the two models to compare" << endl;
+        << "  -m STRING         path to matrices file specifying the two models to compare; repeated (-m A -m B ...): one run of" << endl
+        << "                    every alternative against the same model 0, posterior model probabilities on stdout" << endl
+        << "  -polyclass        no MCMC: combine the mmdiff tables of J >= 2 alternatives against the same model 0 into" << endl
+        << "                    posterior probabilities of models 0..J" << endl;
     out << "Optional arguments:" << endl
         << "  -tracedir STRING  not implemented in this version: MCMC traces are not written (exits with an error)" << endl
         << "  -useprops         run on isoform/gene proportions instead of expression" << endl
@@ -85,7 +97,9 @@ void printUsage(ostream &out)
         << "  -iter INT         MCMC iterations (default: 16384)" << endl
         << "  -seed INT         seed for PRNG (default: 1234)" << endl
         << "  -range INT INT    select features indexed within range (default: all)" << endl
-        << "Size limits: 512 samples, 8 columns of M, 16 columns of P0 and P1, 16 variance classes per model." << endl;
+        << "  -prior P0,...,PJ  with repeated -m or -polyclass: prior probabilities of models 0..J, adding up to 1 (default: flat)" << endl
+        << "  -polyout STRING   with repeated -m: write the mmdiff table of alternative j to STRING.model<j>.mmdiff" << endl
+        << "Size limits: 512 samples, 8 columns of M, 16 columns of P0 and P1, 16 variance classes per model, 16 alternatives (-m) per run." << endl;
 }
 
 [[noreturn]] void usage_error(const string &msg)
@@ -380,6 +394,236 @@ void check_design(const Design &D, bool fixalpha, bool Mnil, const bool Pnil[2])
     }
 }
 
+// the size caps, class labels and finiteness of one design, then check_design's collinearity tests; what is nil
+void validate_design(const Design &D, size_t S, bool fixalpha, bool &Mnil, bool Pnil[2])
+{
+    if (D.K > 8) die("Error: this mmdiff handles at most 8 columns in M.");
+    if (D.L0 > 16 || D.L1 > 16) die("Error: this mmdiff handles at most 16 columns in P0 and P1.");
+    for (int c : D.C)
+        if (c > 15) die("Error: this mmdiff handles at most 16 variance classes per model.");
+    for (int model = 0; model < 2; ++model) {
+        vector<int> seen(16, 0);
+        int mx = 0;
+        for (size_t i = 0; i < S; ++i) { seen[D.C[i * 2 + model]] = 1; mx = max(mx, D.C[i * 2 + model]); }
+        for (int c = 0; c <= mx; ++c)
+            if (!seen[c]) die("Error: the classes of model " + to_string(model) + " must be labelled 0, 1, ... without gaps.");
+    }
+    for (const Mat *X : {&D.M, &D.P0, &D.P1})
+        for (double v : *X)
+            if (!std::isfinite(v)) die("Error: non-finite value in the design matrices.");
+    Mnil = is_nil(D.M, S, D.K);
+    Pnil[0] = is_nil(D.P0, S, D.L0);
+    Pnil[1] = is_nil(D.P1, S, D.L1);
+    check_design(D, fixalpha, Mnil, Pnil);
+    if (Mnil) cerr << "Note: no betas\n";
+    if (Pnil[0]) cerr << "Note: no etas in model 0\n";
+    if (Pnil[1]) cerr << "Note: no etas in model 1\n";
+}
+
+struct DiffResults {
+    vector<double> gm, logitp, alpha, beta, eta;
+    DiffResults(size_t F, const Design &D) : gm(F), logitp(F), alpha(2 * F), beta(2 * D.K * F), eta((D.L0 + D.L1) * F) {}
+};
+
+// the table of one comparison: to fp (if any) and appended to *keep (if any)
+void write_table(FILE *fp, string *keep, const vector<string> &features, const vector<string> &filenames, const Design &D, bool fixalpha,
+                 bool Mnil, const bool Pnil[2], double p, const Mat &y, const Mat &e, const DiffResults &r)
+{
+    const size_t F = features.size(), S = filenames.size();
+    const vector<double> &gm = r.gm, &logitp = r.logitp, &alpha = r.alpha, &beta = r.beta, &eta = r.eta;
+    auto emit = [&](const string &t) {
+        if (fp) fputs(t.c_str(), fp);
+        if (keep) *keep += t;
+    };
+    string out;
+    out += "#prior_probability=" + fmt(p) + "\n";
+    out += "feature_id\tbayes_factor\tposterior_probability\t";
+    for (int model = 0; model < 2; model++) {
+        if (!fixalpha) out += "alpha" + to_string(model) + "\t";
+        if (!Mnil)
+            for (size_t l = 0; l < D.K; l++) out += "beta" + to_string(model) + "_" + to_string(l) + "\t";
+        if (!Pnil[model])
+            for (size_t l = 0; l < (model ? D.L1 : D.L0); l++) out += "eta" + to_string(model) + "_" + to_string(l) + "\t";
+    }
+    vector<string> samplenames = filenames;
+    for (size_t f = 0; f < S; f++) {
+        if (endsWith(filenames[f], ".mmseq")) {
+            const size_t found = filenames[f].find_last_of(".");
+            size_t found2 = filenames[f].find_last_of("/");
+            const long f2 = found2 == string::npos ? -1 : (long)found2;
+            samplenames[f] = filenames[f].substr((size_t)(f2 + 1), (size_t)((long)found - f2 - 1));
+        }
+        out += "mu_" + samplenames[f] + "\t";
+    }
+    for (size_t f = 0; f < S; f++) out += "sd_" + samplenames[f] + (f < S - 1 ? "\t" : "\n");
+    emit(out);
+    const double logp = log(p), log1mp = log1p(-p);
+    for (size_t feature = 0; feature < F; feature++) {
+        out.clear();
+        const double g = gm[feature];
+        if (g == 0.0 || g == 1.0)
+            cerr << "Warning: gamma did not mix for feature " << feature << "; stuck in model " << (int)g << endl;
+        const double lgp = logitp[feature];
+        const double pp_ = lgp > 0 ? 1.0 / (1.0 + exp(-lgp)) : exp(lgp) / (1.0 + exp(lgp));   // BMS::getp
+        const double BF = g / (1.0 - g) * (1.0 - pp_) / pp_;
+        const double postlogodds = log(BF) + logp - log1mp;
+        double pp = 1.0 / (1.0 + exp(-postlogodds));
+        if (BF >= DBL_MAX) pp = 1.0;
+        out += features[feature] + "\t" + fmt(BF) + "\t" + fmt(pp) + "\t";
+        for (int model = 0; model < 2; model++) {
+            if (!fixalpha) out += fmt(alpha[model * F + feature]) + "\t";
+            if (!Mnil)
+                for (size_t l = 0; l < D.K; l++) out += fmt(beta[(model * D.K + l) * F + feature]) + "\t";
+            if (!Pnil[model])
+                for (size_t l = 0; l < (model ? D.L1 : D.L0); l++) out += fmt(eta[((model ? D.L0 : 0) + l) * F + feature]) + "\t";
+        }
+        for (size_t f = 0; f < S; f++) out += fmt(y[feature * S + f]) + "\t";
+        for (size_t f = 0; f < S; f++) out += fmt(e[feature * S + f]) + (f < S - 1 ? "\t" : "\n");
+        emit(out);
+    }
+}
+
+// ---- polytomous model selection: polyclass() of the reference's src/R/mmseq.R on mmdiff tables ----------------------------------
+
+// what polyclass needs of one mmdiff table: the features, the Bayes factors as their text parses (strtod), and -- of the first table --
+// the mu_* and sd_* columns as text
+struct PolyTable {
+    vector<string> kept_names, features, kept_cells;   // kept_cells[row]: the kept columns joined by tabs
+    vector<double> bf;
+};
+
+void split_tabs(const string &line, vector<string> &cells)
+{
+    cells.clear();
+    size_t a = 0;
+    while (true) {
+        const size_t b = line.find('\t', a);
+        cells.push_back(line.substr(a, b == string::npos ? string::npos : b - a));
+        if (b == string::npos) break;
+        a = b + 1;
+    }
+}
+
+void parse_poly_table(istream &in, const string &name, bool keep_cells, PolyTable &T)
+{
+    string line;
+    vector<string> cells;
+    bool header = false;
+    int fi = -1, bi = -1;
+    vector<int> kept;
+    size_t lineno = 0;
+    while (getline(in, line)) {
+        ++lineno;
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty() || line[0] == '#') continue;
+        split_tabs(line, cells);
+        if (!header) {
+            header = true;
+            for (int j = 0; j < (int)cells.size(); ++j) {
+                if (cells[j] == "feature_id") fi = j;
+                if (cells[j] == "bayes_factor") bi = j;
+                if (keep_cells && (cells[j].compare(0, 3, "mu_") == 0 || cells[j].compare(0, 3, "sd_") == 0)) {
+                    kept.push_back(j);
+                    T.kept_names.push_back(cells[j]);
+                }
+            }
+            if (fi < 0 || bi < 0) die("Error: " + name + " must have feature_id and bayes_factor columns.");
+            continue;
+        }
+        const int needed = max(max(fi, bi), kept.empty() ? 0 : kept.back());
+        if ((int)cells.size() <= needed) die("Error: line " + to_string(lineno) + " of " + name + " has too few columns.");
+        T.features.push_back(cells[fi]);
+        T.bf.push_back(strtod(cells[bi].c_str(), NULL));
+        if (keep_cells) {
+            string row;
+            for (size_t k = 0; k < kept.size(); ++k) row += (k ? "\t" : "") + cells[kept[k]];
+            T.kept_cells.push_back(row);
+        }
+    }
+    if (!header) die("Error: " + name + " must have feature_id and bayes_factor columns.");
+}
+
+void check_same_features(const PolyTable &A, const string &a, const PolyTable &B, const string &b)
+{
+    if (A.features.size() != B.features.size())
+        die("Error: features across tables do not match (" + to_string(A.features.size()) + " in " + a + ", " + to_string(B.features.size()) + " in " + b + ")");
+    for (size_t i = 0; i < A.features.size(); ++i)
+        if (A.features[i] != B.features[i])
+            die("Error: features across tables do not match (" + to_string(i) + "," + B.features[i] + "," + A.features[i] + ")");
+}
+
+// -prior: n finite values in [0, 1] adding up to 1 within 1.5e-8 (R's all.equal); without it the flat prior and R's warning
+vector<double> parse_prior(bool given, const string &text, size_t n)
+{
+    if (!given) {
+        cerr << "Warning: assuming flat prior across models" << endl;
+        return vector<double>(n, 1.0 / (double)n);
+    }
+    const string msg = "Error: -prior must list " + to_string(n) + " prior probabilities (one per model, model 0 first) in [0, 1] adding up to 1.";
+    vector<double> prior;
+    size_t a = 0;
+    while (true) {
+        const size_t b = text.find(',', a);
+        const string tok = text.substr(a, b == string::npos ? string::npos : b - a);
+        char *end = NULL;
+        const double v = strtod(tok.c_str(), &end);
+        if (tok.empty() || *end != '\0' || !std::isfinite(v) || v < 0 || v > 1) die(msg);
+        prior.push_back(v);
+        if (b == string::npos) break;
+        a = b + 1;
+    }
+    double sum = 0;
+    for (double v : prior) sum += v;
+    if (prior.size() != n || !(fabs(sum - 1.0) <= 1.5e-8)) die(msg);
+    return prior;
+}
+
+// Posterior model probabilities: model 0 has Bayes factor 1, model j table j's; w_j = bf_j * prior_j, postprob_j = w_j / sum(w), the
+// sum in index order.  Where that is undefined (deliberate differences from polyclass()): one infinite Bayes factor
+// -- that model 1, the others 0; several -- those NaN, the others 0; a NaN Bayes factor or a zero sum -- the whole row NaN.
+void polyclass(const vector<PolyTable> &T, const vector<double> &prior, FILE *fp)
+{
+    const size_t J = T.size(), n = J + 1;
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    string out = "#prior_probabilities=";
+    for (size_t j = 0; j < n; ++j) out += (j ? "," : "") + fmt(prior[j]);
+    out += "\nfeature_id";
+    for (const string &c : T[0].kept_names) out += "\t" + c;
+    for (size_t j = 0; j < n; ++j) out += "\tpostprob_model" + to_string(j);
+    out += "\n";
+    fputs(out.c_str(), fp);
+    vector<double> bf(n), post(n);
+    for (size_t i = 0; i < T[0].features.size(); ++i) {
+        bf[0] = 1.0;
+        for (size_t j = 0; j < J; ++j) bf[j + 1] = T[j].bf[i];
+        size_t ninf = 0, nnan = 0;
+        for (double v : bf) { ninf += std::isinf(v) ? 1 : 0; nnan += std::isnan(v) ? 1 : 0; }
+        if (nnan) {
+            cerr << "Warning: NaN Bayes factor for feature " << i << " (" << T[0].features[i] << "): posterior probabilities undefined" << endl;
+            post.assign(n, nan);
+        } else if (ninf == 1) {
+            for (size_t j = 0; j < n; ++j) post[j] = std::isinf(bf[j]) ? 1.0 : 0.0;
+        } else if (ninf > 1) {
+            cerr << "Warning: more than one infinite Bayes factor for feature " << i << " (" << T[0].features[i] << ")" << endl;
+            for (size_t j = 0; j < n; ++j) post[j] = std::isinf(bf[j]) ? nan : 0.0;
+        } else {
+            double sum = 0.0;
+            for (size_t j = 0; j < n; ++j) { post[j] = bf[j] * prior[j]; sum += post[j]; }
+            if (sum == 0.0) {
+                cerr << "Warning: every model of feature " << i << " (" << T[0].features[i] << ") has zero prior times Bayes factor" << endl;
+                post.assign(n, nan);
+            } else {
+                for (size_t j = 0; j < n; ++j) post[j] = post[j] / sum;
+            }
+        }
+        out = T[0].features[i];
+        if (!T[0].kept_names.empty()) out += "\t" + T[0].kept_cells[i];
+        for (size_t j = 0; j < n; ++j) out += "\t" + fmt(post[j]);
+        out += "\n";
+        fputs(out.c_str(), fp);
+    }
+}
+
 #define MMG_CHECK(call)                                                                                       \
     do {                                                                                                      \
         if ((call) != 0) die(string("Error: ") + #call + ": " + mmg_last_error());                           \
@@ -391,11 +635,101 @@ bool need(const vector<string> &a, size_t n)
     return true;
 }
 
+// repeated -m: J alternatives against one model 0 on one device handle.  Table j (what `mmdiff <same options> -m alt_j <same tables>`
+// prints) goes to BASE.model<j>.mmdiff with -polyout; stdout gets polyclass of the tables, from the Bayes factors as the tables print
+// them (%g text parsed back), so that `mmdiff -polyclass` on the written tables reproduces it byte for byte.
+int run_poly(const vector<string> &mats, bool prior_given, const string &prior_text, bool polyout_given, const string &polyout,
+             const vector<string> &features, const vector<string> &filenames, const Mat &y, const Mat &e, double p, double d, double s,
+             double pdash, bool fixalpha, bool tune, int burnin, int mcmciters, uint64_t useed)
+{
+    const size_t J = mats.size(), S = filenames.size(), F = features.size();
+    vector<Design> Ds(J);
+    vector<char> Mnil(J), Pnil0(J), Pnil1(J);
+    for (size_t j = 0; j < J; ++j) {
+        cerr << "Alternative " << j + 1 << " (" << mats[j] << "):\n";
+        parse_matrices(mats[j], Ds[j], S);
+        bool mn = false, pn[2] = {false, false};
+        validate_design(Ds[j], S, fixalpha, mn, pn);
+        Mnil[j] = mn; Pnil0[j] = pn[0]; Pnil1[j] = pn[1];
+        bool same = Ds[j].K == Ds[0].K && Ds[j].L0 == Ds[0].L0 && Ds[j].M == Ds[0].M && Ds[j].P0 == Ds[0].P0;
+        for (size_t i = 0; same && i < S; ++i) same = Ds[j].C[i * 2] == Ds[0].C[i * 2];
+        if (!same) die("Error: model 0 differs between " + mats[0] + " and " + mats[j]);
+    }
+    const vector<double> prior = parse_prior(prior_given, prior_text, J + 1);
+    struct Closer { vector<FILE *> f; ~Closer() { for (FILE *x : f) if (x) fclose(x); } } files;
+    files.f.assign(J, nullptr);
+    if (polyout_given)
+        for (size_t j = 0; j < J; ++j) {
+            const string name = polyout + ".model" + to_string(j + 1) + ".mmdiff";
+            if (!(files.f[j] = fopen(name.c_str(), "w"))) die("Error: couldn't create " + name);
+        }
+
+    // every input is checked: now the device
+    int ndev = 0;
+    if (mmg_device_count(&ndev) != 0 || ndev < 1) die("Error: no HIP device available: mmdiff has no CPU fallback");
+    vector<uint32_t> L1(J);
+    Mat P1;
+    vector<int> C0(S), C1(J * S);
+    for (size_t i = 0; i < S; ++i) C0[i] = Ds[0].C[i * 2];
+    for (size_t j = 0; j < J; ++j) {
+        L1[j] = (uint32_t)Ds[j].L1;
+        P1.insert(P1.end(), Ds[j].P1.begin(), Ds[j].P1.end());
+        for (size_t i = 0; i < S; ++i) C1[j * S + i] = Ds[j].C[i * 2 + 1];
+    }
+    mmg_diff_poly *h = nullptr;
+    MMG_CHECK(mmg_diff_poly_create(0, (uint32_t)F, (uint32_t)S, y.data(), e.data(), (uint32_t)Ds[0].K, Ds[0].M.data(), (uint32_t)Ds[0].L0,
+                                   Ds[0].P0.data(), C0.data(), (uint32_t)J, L1.data(), P1.data(), C1.data(), d, s, pdash, fixalpha ? 1 : 0,
+                                   useed, &h));
+    cerr << "BURNIN (" << burnin << " iterations, " << J << " alternatives)...";
+    MMG_CHECK(mmg_diff_poly_burnin(h, (uint32_t)burnin));
+    cerr << "\nSetting pseudopriors...done.\n";
+    if (tune) {
+        // each comparison stops at the first batch after which none of its features is untuned, or with the others at MAXBATCHES
+        vector<uint32_t> untuned(J);
+        vector<int32_t> ended(J);
+        int numbatches = 0;
+        bool all_ended = false;
+        while (!all_ended && numbatches != MAXBATCHES) {
+            MMG_CHECK(mmg_diff_poly_tune_batch(h, untuned.data(), ended.data()));
+            numbatches++;
+            all_ended = true;
+            uint64_t left = 0;
+            for (size_t j = 0; j < J; ++j) { all_ended = all_ended && ended[j]; left += untuned[j]; }
+            if (numbatches % 64 == 0) cerr << "TUNING BATCH " << numbatches << " (" << left << " left)\r";
+        }
+    }
+    for (size_t j = 0; j < J; ++j) {
+        uint32_t nb = 0;
+        MMG_CHECK(mmg_diff_poly_info(h, (uint32_t)j, NULL, NULL, &nb, NULL));
+        cerr << "model " << j + 1 << ": sampling after " << nb << " tuning batches\n";
+    }
+    cerr << "TRACE (" << mcmciters << " iterations)";
+    MMG_CHECK(mmg_diff_poly_sample(h, (uint32_t)mcmciters));
+    cerr << "\nDONE MCMC\n";
+    vector<PolyTable> T(J);
+    for (size_t j = 0; j < J; ++j) {
+        DiffResults r(F, Ds[j]);
+        MMG_CHECK(mmg_diff_poly_get_results(h, (uint32_t)j, r.gm.data(), r.logitp.data(), r.alpha.data(), r.beta.data(), r.eta.data()));
+        string text;
+        const bool pn[2] = {(bool)Pnil0[j], (bool)Pnil1[j]};
+        write_table(files.f[j], &text, features, filenames, Ds[j], fixalpha, Mnil[j], pn, p, y, e, r);
+        if (files.f[j] && fflush(files.f[j]) != 0) die("Error: couldn't write " + polyout + ".model" + to_string(j + 1) + ".mmdiff");
+        istringstream in(text);
+        parse_poly_table(in, "the table of alternative " + to_string(j + 1), j == 0, T[j]);
+    }
+    mmg_diff_poly_destroy(h);
+    polyclass(T, prior, stdout);
+    return 0;
+}
+
 } // namespace
 
 int main(int argc, char **argv)
 {
     string matrices_file = "";
+    vector<string> matrices_files;   // every -m; more than one: the polytomous run
+    bool polyclass_mode = false, prior_given = false, polyout_given = false;
+    string prior_text, polyout;
     double p = 0.1, d = 1.4, s = 2.0;
     int burnin = 8192, mcmciters = 16384, seed = 1234, range_start = -1, range_end = -1;
     bool useprops = false, fixalpha = false, normalise = true, customuhfrac = false, permute = false, tune = true;
@@ -413,7 +747,19 @@ int main(int argc, char **argv)
             die("Error: -tracedir is not implemented in this version of mmdiff (MCMC traces are not written).");
         } else if (a0 == "-m" || a0 == "-de") {
             arguments.erase(arguments.begin());
-            for (size_t i = 0; i < arguments.size(); i++)
+            // -m FILE -m FILE ...: consecutive pairs are one polytomous run
+            size_t first_other = 0;
+            if (a0 == "-m")
+                for (first_other = arguments.empty() ? 0 : 1; first_other + 1 < arguments.size() && arguments[first_other] == "-m";) first_other += 2;
+            size_t n_m = a0 == "-m" ? 1 : 0;
+            bool de_too = a0 == "-de";
+            for (size_t i = 0; i < arguments.size(); i++) {
+                if (arguments[i] == "-m" && i + 1 < arguments.size()) n_m++;
+                if (arguments[i] == "-de") de_too = true;
+            }
+            if (de_too && n_m > 1) usage_error("Error: -de cannot be combined with more than one -m.");
+            if (polyclass_mode) usage_error("Error: -polyclass takes mmdiff tables, not -de or -m.");
+            for (size_t i = first_other; i < arguments.size(); i++)
                 if (arguments[i].find("-") == 0) {
                     cerr << "Error: optional arguments must be specified before -de or -m." << endl << endl;
                     printUsage(cerr);
@@ -422,7 +768,14 @@ int main(int argc, char **argv)
             if (a0 == "-m") {
                 need(arguments, 1);
                 matrices_file = arguments[0];
+                matrices_files.push_back(arguments[0]);
                 arguments.erase(arguments.begin());
+                while (arguments.size() >= 2 && arguments[0] == "-m") {
+                    matrices_files.push_back(arguments[1]);
+                    arguments.erase(arguments.begin(), arguments.begin() + 2);
+                }
+                if (matrices_files.size() > MAXMODELS)
+                    die("Error: this mmdiff handles at most " + to_string(MAXMODELS) + " alternative models (-m) in one run.");
             } else {
                 cerr << "Number of samples in each group:";
                 while (ss < (int)arguments.size()) {
@@ -479,6 +832,15 @@ int main(int argc, char **argv)
             range_start = atoi(arguments[0].c_str());
             range_end = atoi(arguments[1].c_str());
             arguments.erase(arguments.begin(), arguments.begin() + 2);
+        } else if (a0 == "-polyclass") {
+            arguments.erase(arguments.begin());
+            polyclass_mode = true;
+        } else if (a0 == "-prior") {
+            prior_text = take();
+            prior_given = true;
+        } else if (a0 == "-polyout") {
+            polyout = take();
+            polyout_given = true;
         } else if (a0 == "-h" || a0 == "--help" || a0 == "-help") {
             cerr << "Bayesian model selection for RNA-seq expression estimates.\n";
             printUsage(cerr);
@@ -487,9 +849,30 @@ int main(int argc, char **argv)
             die("mmdiff-1.0.10-gfx950");
         } else {
             if (!a0.empty() && a0[0] == '-') usage_error("Error: unrecognised option " + a0 + ".");
+            else if (polyclass_mode && arguments.size() >= 2) break;
+            else if (polyclass_mode) usage_error("Error: -polyclass needs at least two mmdiff tables.");
             else if (arguments.size() <= 2) usage_error("Error: mandatory arguments missing.");
             else break;
         }
+    }
+
+    const bool poly_run = matrices_files.size() > 1;
+    if ((prior_given || polyout_given) && !poly_run && !polyclass_mode)
+        usage_error("Error: -prior and -polyout need more than one -m (or, -prior, -polyclass).");
+    if (polyout_given && !poly_run) usage_error("Error: -polyout needs more than one -m.");
+    if (polyclass_mode) {
+        // host only: no device is looked for
+        const size_t J = arguments.size();
+        const vector<double> prior = parse_prior(prior_given, prior_text, J + 1);
+        vector<PolyTable> T(J);
+        for (size_t j = 0; j < J; ++j) {
+            ifstream ifs(arguments[j].c_str());
+            if (!ifs.good()) die("Error: couldn't open " + arguments[j]);
+            parse_poly_table(ifs, arguments[j], j == 0, T[j]);
+            if (j > 0) check_same_features(T[0], arguments[0], T[j], arguments[j]);
+        }
+        polyclass(T, prior, stdout);
+        return 0;
     }
 
     if (burnin <= 0 || mcmciters <= 0) usage_error("Error: negative burnin and iter parameters.");
@@ -531,30 +914,14 @@ int main(int argc, char **argv)
                 else D.P1[k] = i == 0 ? .5 : -.5;
                 k++;
             }
-    } else {
+    } else if (!poly_run) {
         parse_matrices(matrices_file, D, S);
     }
-    if (D.K > 8) die("Error: this mmdiff handles at most 8 columns in M.");
-    if (D.L0 > 16 || D.L1 > 16) die("Error: this mmdiff handles at most 16 columns in P0 and P1.");
-    for (int c : D.C)
-        if (c > 15) die("Error: this mmdiff handles at most 16 variance classes per model.");
-    for (int model = 0; model < 2; ++model) {
-        vector<int> seen(16, 0);
-        int mx = 0;
-        for (size_t i = 0; i < S; ++i) { seen[D.C[i * 2 + model]] = 1; mx = max(mx, D.C[i * 2 + model]); }
-        for (int c = 0; c <= mx; ++c)
-            if (!seen[c]) die("Error: the classes of model " + to_string(model) + " must be labelled 0, 1, ... without gaps.");
-    }
-    for (const Mat *X : {&D.M, &D.P0, &D.P1})
-        for (double v : *X)
-            if (!std::isfinite(v)) die("Error: non-finite value in the design matrices.");
-    const bool Mnil = is_nil(D.M, S, D.K);
-    const bool Pnil[2] = {is_nil(D.P0, S, D.L0), is_nil(D.P1, S, D.L1)};
     if (fixalpha) cerr << "Fixing alpha=0, so setting v_beta^2=25 instead of 4.\n";
-    check_design(D, fixalpha, Mnil, Pnil);
-    if (Mnil) cerr << "Note: no betas\n";
-    if (Pnil[0]) cerr << "Note: no etas in model 0\n";
-    if (Pnil[1]) cerr << "Note: no etas in model 1\n";
+    bool Mnil = false, Pnil[2] = {false, false};
+    if (poly_run) return run_poly(matrices_files, prior_given, prior_text, polyout_given, polyout, features, filenames, y, e, p, d, s, pdash,
+                                  fixalpha, tune, burnin, mcmciters, useed);
+    validate_design(D, S, fixalpha, Mnil, Pnil);
 
     // every input is checked: now the device
     int ndev = 0;
@@ -579,55 +946,9 @@ int main(int argc, char **argv)
     cerr << "TRACE (" << mcmciters << " iterations, sampling after " << numbatches << " tuning batches)";
     MMG_CHECK(mmg_diff_sample(h, (uint32_t)mcmciters));
     cerr << "\nDONE MCMC\n";
-    vector<double> gm(F), logitp(F), alpha(2 * F), beta(2 * D.K * F), eta((D.L0 + D.L1) * F);
-    MMG_CHECK(mmg_diff_get_results(h, gm.data(), logitp.data(), alpha.data(), beta.data(), eta.data()));
+    DiffResults r(F, D);
+    MMG_CHECK(mmg_diff_get_results(h, r.gm.data(), r.logitp.data(), r.alpha.data(), r.beta.data(), r.eta.data()));
     mmg_diff_destroy(h);
-
-    string out;
-    out += "#prior_probability=" + fmt(p) + "\n";
-    out += "feature_id\tbayes_factor\tposterior_probability\t";
-    for (int model = 0; model < 2; model++) {
-        if (!fixalpha) out += "alpha" + to_string(model) + "\t";
-        if (!Mnil)
-            for (size_t l = 0; l < D.K; l++) out += "beta" + to_string(model) + "_" + to_string(l) + "\t";
-        if (!Pnil[model])
-            for (size_t l = 0; l < (model ? D.L1 : D.L0); l++) out += "eta" + to_string(model) + "_" + to_string(l) + "\t";
-    }
-    vector<string> samplenames = filenames;
-    for (size_t f = 0; f < S; f++) {
-        if (endsWith(filenames[f], ".mmseq")) {
-            const size_t found = filenames[f].find_last_of(".");
-            size_t found2 = filenames[f].find_last_of("/");
-            const long f2 = found2 == string::npos ? -1 : (long)found2;
-            samplenames[f] = filenames[f].substr((size_t)(f2 + 1), (size_t)((long)found - f2 - 1));
-        }
-        out += "mu_" + samplenames[f] + "\t";
-    }
-    for (size_t f = 0; f < S; f++) out += "sd_" + samplenames[f] + (f < S - 1 ? "\t" : "\n");
-    fputs(out.c_str(), stdout);
-    const double logp = log(p), log1mp = log1p(-p);
-    for (size_t feature = 0; feature < F; feature++) {
-        out.clear();
-        const double g = gm[feature];
-        if (g == 0.0 || g == 1.0)
-            cerr << "Warning: gamma did not mix for feature " << feature << "; stuck in model " << (int)g << endl;
-        const double lgp = logitp[feature];
-        const double pp_ = lgp > 0 ? 1.0 / (1.0 + exp(-lgp)) : exp(lgp) / (1.0 + exp(lgp));   // BMS::getp
-        const double BF = g / (1.0 - g) * (1.0 - pp_) / pp_;
-        const double postlogodds = log(BF) + logp - log1mp;
-        double pp = 1.0 / (1.0 + exp(-postlogodds));
-        if (BF >= DBL_MAX) pp = 1.0;
-        out += features[feature] + "\t" + fmt(BF) + "\t" + fmt(pp) + "\t";
-        for (int model = 0; model < 2; model++) {
-            if (!fixalpha) out += fmt(alpha[model * F + feature]) + "\t";
-            if (!Mnil)
-                for (size_t l = 0; l < D.K; l++) out += fmt(beta[(model * D.K + l) * F + feature]) + "\t";
-            if (!Pnil[model])
-                for (size_t l = 0; l < (model ? D.L1 : D.L0); l++) out += fmt(eta[((model ? D.L0 : 0) + l) * F + feature]) + "\t";
-        }
-        for (size_t f = 0; f < S; f++) out += fmt(y[feature * S + f]) + "\t";
-        for (size_t f = 0; f < S; f++) out += fmt(e[feature * S + f]) + (f < S - 1 ? "\t" : "\n");
-        fputs(out.c_str(), stdout);
-    }
+    write_table(stdout, nullptr, features, filenames, D, fixalpha, Mnil, Pnil, p, y, e, r);
     return 0;
 }

@@ -85,3 +85,87 @@ class Diff:
             self.close()
         except Exception:
             pass
+
+
+class DiffPoly:
+    """J alternatives against one model 0 on one handle (the mmg_diff_poly_* entries): y, e, M and P0 are held once and every launch
+    covers all comparisons.  Comparison j's chain is bit for bit that of `Diff(y, e, M, P0, P1s[j], [classes0, classes1s[j]])` driven
+    the same way; in tuning, a comparison whose untuned count reached 0 has ended and keeps its own batch count."""
+
+    def __init__(self, y, e, M, P0, classes0, P1s, classes1s, d=1.4, s=2.0, pdash=0.5, fixalpha=False, seed=1234, device=0):
+        """y, e: (F, N); M (N, K); P0 (N, L0); classes0 (N,) the variance classes under model 0; P1s: J matrices (N, L1_j);
+        classes1s: J vectors (N,) of classes under each alternative."""
+        self._lib = _lib.load()
+        self._h = None
+        y = np.ascontiguousarray(y, np.float64)
+        e = np.ascontiguousarray(e, np.float64)
+        M = np.ascontiguousarray(M, np.float64)
+        P0 = np.ascontiguousarray(P0, np.float64)
+        C0 = np.ascontiguousarray(classes0, np.int32)
+        P1s = [np.ascontiguousarray(P, np.float64) for P in P1s]
+        C1 = np.ascontiguousarray(np.stack([np.asarray(c, np.int32) for c in classes1s]), np.int32) if len(classes1s) else np.zeros((0, 0), np.int32)
+        F, N = y.shape
+        J = len(P1s)
+        if J < 1 or C1.shape != (J, N) or e.shape != (F, N) or M.shape[0] != N or P0.shape[0] != N or C0.shape != (N,) \
+                or any(P.ndim != 2 or P.shape[0] != N for P in P1s):
+            raise ValueError("inconsistent shapes")
+        self.F, self.N, self.K, self.J = F, N, M.shape[1], J
+        self.L0 = P0.shape[1]
+        self.L1 = tuple(P.shape[1] for P in P1s)
+        L1 = np.array(self.L1, np.uint32)
+        P1 = np.ascontiguousarray(np.concatenate([P.ravel() for P in P1s]))
+        h = C.c_void_p()
+        check(self._lib.mmg_diff_poly_create(device, F, N, _ptr(y), _ptr(e), self.K, _ptr(M), self.L0, _ptr(P0), _ptr(C0), J, _ptr(L1),
+                                             _ptr(P1), _ptr(C1), float(d), float(s), float(pdash), int(bool(fixalpha)),
+                                             int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(h)))
+        self._h = h
+
+    def burnin(self, iters):
+        check(self._lib.mmg_diff_poly_burnin(self._h, int(iters)))
+
+    def tune_batch(self):
+        """One tuning batch for the comparisons that have not ended; (untuned counts, ended flags), one entry per comparison."""
+        n, ended = (C.c_uint32 * self.J)(), (C.c_int32 * self.J)()
+        check(self._lib.mmg_diff_poly_tune_batch(self._h, n, ended))
+        return list(n), [bool(v) for v in ended]
+
+    def tune(self, max_batches=MAXBATCHES):
+        """Batches until every comparison has ended or max_batches have run; the batch count of each comparison."""
+        nb = 0
+        while nb != max_batches:
+            _, ended = self.tune_batch()
+            nb += 1
+            if all(ended):
+                break
+        return [self.info(j)["batches"] for j in range(self.J)]
+
+    def sample(self, iters):
+        check(self._lib.mmg_diff_poly_sample(self._h, int(iters)))
+
+    def results(self, j):
+        F, K, L = self.F, self.K, self.L0 + self.L1[j]
+        out = dict(gamma_mean=np.empty(F), logitp=np.empty(F), alpha=np.empty((2, F)), beta=np.empty((2, K, F)), eta=np.empty((L, F)))
+        check(self._lib.mmg_diff_poly_get_results(self._h, int(j), *(_ptr(out[k]) for k in ("gamma_mean", "logitp", "alpha", "beta", "eta"))))
+        return out
+
+    def info(self, j):
+        flags, nc, nb, ended = (C.c_int32 * 3)(), (C.c_uint32 * 2)(), C.c_uint32(), C.c_int32()
+        check(self._lib.mmg_diff_poly_info(self._h, int(j), flags, nc, C.byref(nb), C.byref(ended)))
+        return dict(Mnil=bool(flags[0]), Pnil=(bool(flags[1]), bool(flags[2])), n_classes=(nc[0], nc[1]), batches=nb.value,
+                    ended=bool(ended.value))
+
+    def device_bytes(self):
+        b = C.c_uint64()
+        check(self._lib.mmg_diff_poly_device_bytes(self._h, C.byref(b)))
+        return b.value
+
+    def close(self):
+        if self._h:
+            self._lib.mmg_diff_poly_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
