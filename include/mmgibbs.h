@@ -80,8 +80,8 @@ extern "C" {
  *      collects reads of hundreds of genes no longer ties the paralogue families into one component.  Stored order and chain of problems
  *      with such groups differ from version 7.
  *      Additive in version 8, no bump (the chain's specification does not change): mmcollapse (mmg_collapse_*), mmdiff (mmg_diff_*), the
- *      owners' self tests (MMG_OPT_FAIL_ALLOC, mmg_selftest_live, mmg_selftest_sampler_events) and the convergence diagnostics across
- *      chains (mmg_convergence_*, MMG_OPT_CONV_SLAB). */
+ *      owners' self tests (MMG_OPT_FAIL_ALLOC, mmg_selftest_live, mmg_selftest_sampler_events), the convergence diagnostics across
+ *      chains (mmg_convergence_*, MMG_OPT_CONV_SLAB) and mmdiff's chains (mmg_diff_chains_*). */
 /* Layout.  The model does not care about the order of rows or the numbering of transcripts (src/mmseq.cpp:399-418 uses
  * first-seen order for both); the kernels do: they keep a window of consecutive transcripts in LDS and want the 64 rows of a
  * wave to have equal lengths.  mmg_problem_create therefore stores the rows in a CANONICAL order of its own (sorted on the
@@ -571,6 +571,41 @@ int mmg_diff_poly_info(mmg_diff_poly *h, uint32_t j, int32_t *flags, uint32_t *n
 /* 8 (2 F N + N K + N L0 + sum_j (F nslot_j + N L1_j)) + 4 sum_j (2 N + 2 F) + 488 J bytes (nslot_j: DESIGN.md section 10) */
 int mmg_diff_poly_device_bytes(mmg_diff_poly *h, uint64_t *bytes);
 void mmg_diff_poly_destroy(mmg_diff_poly *h);
+
+/* ---- mmdiff, several chains: C independent chains of one comparison on one handle, pooled ------------------------------------
+ * Chain c (0 <= c < C <= 16) draws from the streams (seed, c, TAG_DIFF, feature, iteration).  The stream key is
+ * (seed >> 32) ^ chain ^ (tag << 24), so chain c is bit for bit the chain of an mmg_diff handle created from the same inputs with
+ * seed ^ ((uint64_t)c << 32) and driven the same way; chain 0 is the chain of mmg_diff_create.  y, e, M, P0, P1 and the classes are
+ * held once; every launch covers all chains; each chain tunes on its own, as a comparison of mmg_diff_poly_* does.  Additive in ABI
+ * version 8. */
+typedef struct mmg_diff_chains mmg_diff_chains;
+/* As mmg_diff_create, with the number of chains and the total number of sampling iterations (a positive multiple of 16): the
+ * sampling run is cut into 16 batches of sample_total / 16 iterations whose sums of gamma are kept per chain and feature. */
+int mmg_diff_chains_create(int device, uint32_t n_features, uint32_t n_samples, const double *y, const double *e, uint32_t K, const double *M,
+                           uint32_t L0, const double *P0, uint32_t L1, const double *P1, const int32_t *C, double d, double s, double pdash,
+                           int fixalpha, uint64_t seed, uint32_t n_chains, uint32_t sample_total, mmg_diff_chains **out);
+int mmg_diff_chains_burnin(mmg_diff_chains *h, uint32_t iters);
+/* One tuning batch for every chain that has not ended tuning: untuned[C], ended[C] (may be NULL) as mmg_diff_poly_tune_batch fills
+ * them per comparison.  mmg_diff_chains_sample starts chain c at its own index, burnin + 128 * (its batches). */
+int mmg_diff_chains_tune_batch(mmg_diff_chains *h, uint32_t *untuned, int32_t *ended);
+/* iters more sampling iterations of every chain; MMG_ERR_ARG if that would pass sample_total in all */
+int mmg_diff_chains_sample(mmg_diff_chains *h, uint32_t iters);
+/* the pooled estimates, once sample_total iterations have been sampled */
+int mmg_diff_chains_pool(mmg_diff_chains *h);
+/* chain c's results, laid out as mmg_diff_get_results lays them out */
+int mmg_diff_chains_get_results(mmg_diff_chains *h, uint32_t c, double *gamma_mean, double *logitp, double *alpha, double *beta, double *eta);
+/* sums[16][F]: chain c's sum of gamma over each sixteenth of the sampling run (integers; their sum is gamma_mean * iterations sampled) */
+int mmg_diff_chains_get_batch_sums(mmg_diff_chains *h, uint32_t c, double *sums);
+/* log_bf[F], log_bf_sd[F], log_bf_mcse[F], chains_mixed[F]; alpha, beta, eta laid out as mmg_diff_get_results lays them out, each the
+ * chains' summed sums over their summed counts; any pointer may be NULL.  After mmg_diff_chains_pool. */
+int mmg_diff_chains_get_pooled(mmg_diff_chains *h, double *log_bf, double *log_bf_sd, double *log_bf_mcse, uint32_t *chains_mixed,
+                               double *alpha, double *beta, double *eta);
+/* chain c: flags[3] = (M nil, P0 nil, P1 nil), n_classes[2], its tuning batches, whether it has ended tuning; any pointer may be NULL */
+int mmg_diff_chains_info(mmg_diff_chains *h, uint32_t c, int32_t *flags, uint32_t *n_classes, uint32_t *batches, int32_t *ended);
+/* 8 (2 F N + N K + N L0 + N L1 + C F (nslot + 16) + F (8 + 4 K + 2 L0 + 2 L1)) + 4 (2 N + 2 C F) + 488 C bytes (nslot: DESIGN.md
+ * section 10) */
+int mmg_diff_chains_device_bytes(mmg_diff_chains *h, uint64_t *bytes);
+void mmg_diff_chains_destroy(mmg_diff_chains *h);
 
 #ifdef __cplusplus
 }

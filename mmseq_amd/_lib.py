@@ -158,6 +158,19 @@ SYMBOLS = {
     "mmg_diff_poly_info": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmg_diff_poly_device_bytes": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mmg_diff_poly_destroy": (None, [C.c_void_p]),
+    "mmg_diff_chains_create": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
+                                         C.c_uint32, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int, C.c_uint64, C.c_uint32,
+                                         C.c_uint32, C.c_void_p]),
+    "mmg_diff_chains_burnin": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "mmg_diff_chains_tune_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmg_diff_chains_sample": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "mmg_diff_chains_pool": (C.c_int, [C.c_void_p]),
+    "mmg_diff_chains_get_results": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmg_diff_chains_get_batch_sums": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "mmg_diff_chains_get_pooled": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmg_diff_chains_info": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmg_diff_chains_device_bytes": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mmg_diff_chains_destroy": (None, [C.c_void_p]),
     "mmg_collapse_summarize": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_double,
                                          C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),

@@ -507,3 +507,280 @@ extern "C" int mmg_diff_poly_device_bytes(mmg_diff_poly *h, uint64_t *bytes)
 }
 
 extern "C" void mmg_diff_poly_destroy(mmg_diff_poly *h) { delete h; }
+
+// ---- several chains of one comparison on one handle ---------------------------------------------------------------------------
+// y / e^2 / M / P0 / P1 and the class table once; per chain a DiffParams (chain c in the stream key), a state block of nslot + DF_NB slots
+// (the last DF_NB: the batch sums of gamma), gam / tuned.  The launches cover every chain (grid.y); a chain whose untuned count reached 0
+// leaves the tuning launches, as a comparison of mmg_diff_poly_* does.
+struct mmg_diff_chains {
+    DevStream st;
+    int device = 0;
+    uint32_t F = 0, N = 0, K = 0, L[2] = {0, 0}, C = 0, T = 0;
+    size_t nslot = 0, npool = 0;   // slots per feature of one chain (without the batch slots) and of the pooled output
+    DevBuf<double> d_y, d_esq, d_M, d_P0, d_P1, d_st, d_pool;
+    DevBuf<int> d_C, d_gam, d_tuned;
+    std::vector<DiffParams> h_p;
+    std::vector<uint32_t> h_off, nb;   // per chain: 128 * (its batches); its batches
+    std::vector<char> ended;
+    DevBuf<DiffParams> d_p;
+    DevBuf<uint32_t> d_off;
+    DevBuf<int> d_cnt;
+    uint32_t burnin = 0, batches = 0, sampled = 0;
+    bool burnt = false, pooled = false;
+    uint64_t device_bytes = 0;
+    dim3 grid() const { return dim3(df_blocks(F), C); }
+    int gb() const { return (int)nslot; }
+    ~mmg_diff_chains() { if (st) (void)hipStreamSynchronize(st.get()); }
+};
+
+extern "C" int mmg_diff_chains_create(int device, uint32_t F, uint32_t N, const double *y, const double *e, uint32_t K, const double *M,
+                                      uint32_t L0, const double *P0, uint32_t L1, const double *P1, const int32_t *C, double d, double s,
+                                      double pdash, int fixalpha, uint64_t seed, uint32_t n_chains, uint32_t sample_total, mmg_diff_chains **out)
+{
+    if (!out || !y || !e || !M || !P0 || !P1 || !C) return fail(MMG_ERR_ARG, "NULL argument");
+    *out = nullptr;
+    if (F == 0 || F > 0x7fffff00u / DF_BLOCK) return fail(MMG_ERR_ARG, "the number of features must be between 1 and 33554428");
+    if (N < 2 || N > (uint32_t)DF_NMAX) return fail(MMG_ERR_ARG, "the number of samples must be between 2 and 512");
+    if (K < 1 || K > (uint32_t)DF_KMAX) return fail(MMG_ERR_ARG, "M must have between 1 and 8 columns");
+    if (L0 < 1 || L0 > (uint32_t)DF_LMAX || L1 < 1 || L1 > (uint32_t)DF_LMAX) return fail(MMG_ERR_ARG, "P0 and P1 must have between 1 and 16 columns");
+    if (n_chains < 1 || n_chains > (uint32_t)DF_CHAINS_MAX) return fail(MMG_ERR_ARG, "the number of chains must be between 1 and 16");
+    if (sample_total == 0 || sample_total % DF_NB || sample_total > 0x7fffffffu)
+        return fail(MMG_ERR_ARG, "the total sampling length must be a positive multiple of 16");
+    if (!(d > 0) || !(s > 0) || !std::isfinite(d) || !std::isfinite(s) || !(pdash >= 0 && pdash <= 1))
+        return fail(MMG_ERR_ARG, "d and s must be positive and finite and pdash in [0, 1]");
+    auto finite = [](const double *x, uint64_t n) { for (uint64_t i = 0; i < n; ++i) if (!std::isfinite(x[i])) return false; return true; };
+    if (!finite(y, (uint64_t)F * N) || !finite(e, (uint64_t)F * N)) return fail(MMG_ERR_ARG, "y and e must be finite");
+    if (!finite(M, (uint64_t)N * K) || !finite(P0, (uint64_t)N * L0) || !finite(P1, (uint64_t)N * L1)) return fail(MMG_ERR_ARG, "M, P0 and P1 must be finite");
+    int nc[2] = {0, 0};
+    int rc;
+    for (int mi = 0; mi < 2; ++mi)
+        if ((rc = df_classes(C + mi, 2, N, &nc[mi]))) return rc;
+    if ((rc = require_device(device))) return rc;
+
+    std::unique_ptr<mmg_diff_chains> h(new mmg_diff_chains());
+    h->device = device; h->F = F; h->N = N; h->K = K; h->L[0] = L0; h->L[1] = L1; h->C = n_chains; h->T = sample_total;
+    h->h_off.assign(n_chains, 0);
+    h->nb.assign(n_chains, 0);
+    h->ended.assign(n_chains, 0);
+    DiffParams p{};
+    p.F = (int)F; p.N = (int)N; p.K = (int)K;
+    p.Mnil = df_nil(M, N, K) ? 1 : 0;
+    p.fixalpha = fixalpha ? 1 : 0;
+    p.d = d; p.s = s; p.v_beta = fixalpha ? 25.0 : 4.0;
+    p.seed = seed;
+    p.m[0].Pnil = df_nil(P0, N, L0) ? 1 : 0;
+    p.m[1].Pnil = df_nil(P1, N, L1) ? 1 : 0;
+    h->nslot = df_layout(p, h->L, nc);
+    h->npool = (size_t)DF_POOL_STATS + 2 * (size_t)(2 + 2 * K + L0 + L1);
+    const uint64_t per_chain = (uint64_t)(h->nslot + DF_NB) * F;   // doubles of one chain's state block
+
+    auto dalloc = [&](auto &buf, uint64_t count) {
+        HIPE_TRY(buf.alloc(count));
+        h->device_bytes += count * sizeof(*buf.get());
+        return hipSuccess;
+    };
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(h->st.create(hipStreamNonBlocking));
+    const hipStream_t st = h->st.get();
+    const uint64_t FN = (uint64_t)F * N;
+    HIP_TRY(dalloc(h->d_y, FN));
+    HIP_TRY(dalloc(h->d_esq, FN));
+    HIP_TRY(dalloc(h->d_M, (uint64_t)N * K));
+    HIP_TRY(dalloc(h->d_P0, (uint64_t)N * L0));
+    HIP_TRY(dalloc(h->d_P1, (uint64_t)N * L1));
+    HIP_TRY(dalloc(h->d_C, (uint64_t)N * 2));
+    HIP_TRY(dalloc(h->d_st, per_chain * n_chains));
+    HIP_TRY(dalloc(h->d_gam, (uint64_t)F * n_chains));
+    HIP_TRY(dalloc(h->d_tuned, (uint64_t)F * n_chains));
+    HIP_TRY(dalloc(h->d_pool, (uint64_t)h->npool * F));
+    HIP_TRY(dalloc(h->d_p, n_chains));
+    HIP_TRY(dalloc(h->d_off, n_chains));
+    HIP_TRY(dalloc(h->d_cnt, n_chains));
+    // y and e^2 transposed to [N][F], as mmg_diff_create holds them
+    std::vector<double> ty(FN), te(FN);
+    for (uint64_t f = 0; f < F; ++f)
+        for (uint64_t i = 0; i < N; ++i) {
+            ty[i * F + f] = y[f * N + i];
+            const double ei = e[f * N + i];
+            te[i * F + f] = ei * ei;
+        }
+    HIP_TRY(hipMemcpyAsync(h->d_y.get(), ty.data(), FN * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->d_esq.get(), te.data(), FN * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->d_M.get(), M, (size_t)N * K * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->d_P0.get(), P0, (size_t)N * L0 * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->d_P1.get(), P1, (size_t)N * L1 * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->d_C.get(), C, (size_t)N * 2 * 4, hipMemcpyHostToDevice, st));
+    p.M = h->d_M.get(); p.m[0].P = h->d_P0.get(); p.m[1].P = h->d_P1.get(); p.Cl = h->d_C.get();
+    p.y = h->d_y.get(); p.esq = h->d_esq.get();
+    h->h_p.assign(n_chains, p);
+    for (uint32_t c = 0; c < n_chains; ++c) {
+        DiffParams &q = h->h_p[c];
+        q.chain = (int)c;
+        q.st = h->d_st.get() + per_chain * c;
+        q.gam = h->d_gam.get() + (size_t)F * c;
+        q.tuned = h->d_tuned.get() + (size_t)F * c;
+    }
+    HIP_TRY(hipMemcpyAsync(h->d_p.get(), h->h_p.data(), (size_t)n_chains * sizeof(DiffParams), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(h->d_off.get(), 0, (size_t)n_chains * 4, st));
+    const double logitp0 = std::log(pdash) - std::log(1.0 - pdash);
+    hipLaunchKernelGGL(k_dfc_init, h->grid(), dim3(DF_BLOCK), 0, st, h->d_p.get(), logitp0, h->gb());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    *out = h.release();
+    return MMG_OK;
+}
+
+extern "C" int mmg_diff_chains_burnin(mmg_diff_chains *h, uint32_t iters)
+{
+    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
+    if (h->burnt) return fail(MMG_ERR_STATE, "the burn-in has run already");
+    if (iters == 0 || iters % 1024) return fail(MMG_ERR_ARG, "burn-in iterations must be a positive multiple of 1024");
+    HIP_TRY(hipSetDevice(h->device));
+    for (uint32_t t = 0; t < iters; t += DF_CHUNK) {
+        const uint32_t n = iters - t < DF_CHUNK ? iters - t : DF_CHUNK;
+        hipLaunchKernelGGL(k_dfc_run, h->grid(), dim3(DF_BLOCK), 0, h->st.get(), h->d_p.get(), h->d_off.get(), t, (int)t, (int)n, 0, DF_REC_FROM,
+                           h->gb(), (int)(h->T / DF_NB));
+    }
+    hipLaunchKernelGGL(k_dfc_pseudo, h->grid(), dim3(DF_BLOCK), 0, h->st.get(), h->d_p.get(), (double)(iters - DF_REC_FROM));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(h->st.get()));
+    h->burnin = iters;
+    h->burnt = true;
+    return MMG_OK;
+}
+
+extern "C" int mmg_diff_chains_tune_batch(mmg_diff_chains *h, uint32_t *untuned, int32_t *ended)
+{
+    if (!h || !untuned) return fail(MMG_ERR_ARG, "NULL argument");
+    if (!h->burnt) return fail(MMG_ERR_STATE, "mmg_diff_chains_tune_batch before mmg_diff_chains_burnin");
+    if (h->sampled) return fail(MMG_ERR_STATE, "mmg_diff_chains_tune_batch after sampling has started");
+    uint32_t active = 0;
+    for (uint32_t c = 0; c < h->C; ++c)
+        if (!h->ended[c]) active |= 1u << c;
+    for (uint32_t c = 0; c < h->C; ++c) untuned[c] = 0;
+    if (active) {
+        HIP_TRY(hipSetDevice(h->device));
+        HIP_TRY(hipMemsetAsync(h->d_cnt.get(), 0, (size_t)h->C * 4, h->st.get()));
+        const uint32_t it0 = h->burnin + h->batches * DF_BATCH;
+        hipLaunchKernelGGL(k_dfc_tune, h->grid(), dim3(DF_BLOCK), 0, h->st.get(), h->d_p.get(), active, it0, (int)h->batches, h->d_cnt.get());
+        HIP_TRY(hipGetLastError());
+        int cnt[DF_CHAINS_MAX] = {0};
+        HIP_TRY(hipMemcpyAsync(cnt, h->d_cnt.get(), (size_t)h->C * 4, hipMemcpyDeviceToHost, h->st.get()));
+        HIP_TRY(hipStreamSynchronize(h->st.get()));
+        ++h->batches;
+        for (uint32_t c = 0; c < h->C; ++c) {
+            if (h->ended[c]) continue;
+            h->nb[c] = h->batches;
+            untuned[c] = (uint32_t)cnt[c];
+            if (cnt[c] == 0) h->ended[c] = 1;
+        }
+    }
+    if (ended)
+        for (uint32_t c = 0; c < h->C; ++c) ended[c] = h->ended[c] ? 1 : 0;
+    return MMG_OK;
+}
+
+extern "C" int mmg_diff_chains_sample(mmg_diff_chains *h, uint32_t iters)
+{
+    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
+    if (!h->burnt) return fail(MMG_ERR_STATE, "mmg_diff_chains_sample before mmg_diff_chains_burnin");
+    if (iters == 0) return fail(MMG_ERR_ARG, "iters must be positive");
+    // the batch slot of sampling index t is t / (T / 16) < 16 only while t < T
+    if (iters > h->T - h->sampled) return fail(MMG_ERR_ARG, "sampling beyond the total sampling length the handle was created with");
+    HIP_TRY(hipSetDevice(h->device));
+    if (!h->sampled) {
+        // chain c's sampling starts at its own running index, burnin + 128 * (its batches)
+        for (uint32_t c = 0; c < h->C; ++c) h->h_off[c] = h->nb[c] * DF_BATCH;
+        HIP_TRY(hipMemcpyAsync(h->d_off.get(), h->h_off.data(), (size_t)h->C * 4, hipMemcpyHostToDevice, h->st.get()));
+    }
+    for (uint32_t j = 0; j < iters; j += DF_CHUNK) {
+        const uint32_t n = iters - j < DF_CHUNK ? iters - j : DF_CHUNK;
+        hipLaunchKernelGGL(k_dfc_run, h->grid(), dim3(DF_BLOCK), 0, h->st.get(), h->d_p.get(), h->d_off.get(), h->burnin + h->sampled + j,
+                           (int)(h->sampled + j), (int)n, 2, 0, h->gb(), (int)(h->T / DF_NB));
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(h->st.get()));
+    h->sampled += iters;
+    h->pooled = false;
+    return MMG_OK;
+}
+
+extern "C" int mmg_diff_chains_pool(mmg_diff_chains *h)
+{
+    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
+    if (h->sampled != h->T) return fail(MMG_ERR_STATE, "mmg_diff_chains_pool before the total sampling length has been sampled");
+    HIP_TRY(hipSetDevice(h->device));
+    hipLaunchKernelGGL(k_dfc_pool, dim3(df_blocks(h->F)), dim3(DF_BLOCK), 0, h->st.get(), h->d_p.get(), (int)h->C, (int)h->T, h->gb(), h->d_pool.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(h->st.get()));
+    h->pooled = true;
+    return MMG_OK;
+}
+
+extern "C" int mmg_diff_chains_get_results(mmg_diff_chains *h, uint32_t c, double *gamma_mean, double *logitp, double *alpha, double *beta, double *eta)
+{
+    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
+    if (c >= h->C) return fail(MMG_ERR_ARG, "no such chain");
+    if (!h->sampled) return fail(MMG_ERR_STATE, "mmg_diff_chains_get_results before mmg_diff_chains_sample");
+    HIP_TRY(hipSetDevice(h->device));
+    return df_results(h->h_p[c], h->h_p[c].st, h->F, h->K, h->L, h->sampled, gamma_mean, logitp, alpha, beta, eta);
+}
+
+extern "C" int mmg_diff_chains_get_batch_sums(mmg_diff_chains *h, uint32_t c, double *sums)
+{
+    if (!h || !sums) return fail(MMG_ERR_ARG, "NULL argument");
+    if (c >= h->C) return fail(MMG_ERR_ARG, "no such chain");
+    if (!h->sampled) return fail(MMG_ERR_STATE, "mmg_diff_chains_get_batch_sums before mmg_diff_chains_sample");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipMemcpy(sums, h->h_p[c].st + h->nslot * h->F, (size_t)DF_NB * h->F * 8, hipMemcpyDeviceToHost));
+    return MMG_OK;
+}
+
+extern "C" int mmg_diff_chains_get_pooled(mmg_diff_chains *h, double *log_bf, double *log_bf_sd, double *log_bf_mcse, uint32_t *chains_mixed,
+                                          double *alpha, double *beta, double *eta)
+{
+    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
+    if (!h->pooled) return fail(MMG_ERR_STATE, "mmg_diff_chains_get_pooled before mmg_diff_chains_pool");
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t F = h->F;
+    std::vector<double> v(h->npool * F);
+    HIP_TRY(hipMemcpy(v.data(), h->d_pool.get(), v.size() * 8, hipMemcpyDeviceToHost));
+    for (size_t f = 0; f < F; ++f) {
+        if (log_bf) log_bf[f] = v[f];
+        if (log_bf_sd) log_bf_sd[f] = v[F + f];
+        if (log_bf_mcse) log_bf_mcse[f] = v[2 * F + f];
+        if (chains_mixed) chains_mixed[f] = (uint32_t)v[3 * F + f];
+    }
+    // the means: summed sums / summed counts, the quotient on the host as df_results takes it
+    const size_t nq[3] = {2, 2 * (size_t)h->K, (size_t)h->L[0] + h->L[1]};
+    double *dst[3] = {alpha, beta, eta};
+    size_t q = 0;
+    for (int a = 0; a < 3; ++a)
+        for (size_t i = 0; i < nq[a]; ++i, ++q) {
+            if (!dst[a]) continue;
+            const double *S = &v[(DF_POOL_STATS + 2 * q) * F], *Nn = &v[(DF_POOL_STATS + 2 * q + 1) * F];
+            for (size_t f = 0; f < F; ++f) dst[a][i * F + f] = S[f] / Nn[f];
+        }
+    return MMG_OK;
+}
+
+extern "C" int mmg_diff_chains_info(mmg_diff_chains *h, uint32_t c, int32_t *flags, uint32_t *n_classes, uint32_t *batches, int32_t *ended)
+{
+    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
+    if (c >= h->C) return fail(MMG_ERR_ARG, "no such chain");
+    const DiffParams &p = h->h_p[c];
+    if (flags) { flags[0] = p.Mnil; flags[1] = p.m[0].Pnil; flags[2] = p.m[1].Pnil; }
+    if (n_classes) { n_classes[0] = (uint32_t)p.m[0].nc; n_classes[1] = (uint32_t)p.m[1].nc; }
+    if (batches) *batches = h->nb[c];
+    if (ended) *ended = h->ended[c] ? 1 : 0;
+    return MMG_OK;
+}
+
+extern "C" int mmg_diff_chains_device_bytes(mmg_diff_chains *h, uint64_t *bytes)
+{
+    if (!h || !bytes) return fail(MMG_ERR_ARG, "NULL argument");
+    *bytes = h->device_bytes;
+    return MMG_OK;
+}
+
+extern "C" void mmg_diff_chains_destroy(mmg_diff_chains *h) { delete h; }

@@ -5,8 +5,8 @@
 // interact, so a launch covers many iterations; the host drives the phases (burn-in, pseudopriors, tuning batches, sampling).
 // The state is SoA in global memory, slot j of feature f at st[j * F + f]: adjacent lanes touch adjacent words.
 //
-// Randomness: Stream(seed, 0, TAG_DIFF, feature, it), `it` one running iteration index over burn-in, tuning and sampling; the
-// block counter runs on through the updates of the iteration.  Every sum runs in a fixed order, no floating-point atomics:
+// Randomness: Stream(seed, chain, TAG_DIFF, feature, it), `it` one running iteration index over burn-in, tuning and sampling; the
+// block counter runs on through the updates of the iteration.  The chain is 0 except in the handles of mmg_diff_chains_*.  Every sum runs in a fixed order, no floating-point atomics:
 // reruns are bit-identical and tests/mmdiff_ref.py restates every operation in numpy.
 #pragma once
 #include "mmg_math.h"
@@ -35,6 +35,7 @@ struct DiffModel {
 
 struct DiffParams {
     int F, N, K, Mnil, fixalpha;
+    int chain;            // the chain of the stream key (in what was padding: the size stays 480); 0 but for mmg_diff_chains_*
     double d, s, v_beta;
     uint64_t seed;
     const double *M;      // [N][K]
@@ -394,7 +395,7 @@ MMG_HD double df_log_pseudo(const DiffParams &p, int f, int mi)
 // one iteration of one feature (src/mmdiff.cpp:786-846): fit = burn-in, or the model gamma currently selects
 MMG_HD void df_iteration(const DiffParams &p, int f, uint32_t it, bool inburnin, bool rec)
 {
-    Stream rs(p.seed, 0, TAG_DIFF, (uint64_t)f, it);
+    Stream rs(p.seed, (uint32_t)p.chain, TAG_DIFF, (uint64_t)f, it);
     const int g = p.gam[f];
     for (int mi = 0; mi < 2; ++mi) df_update_alpha(p, f, mi, inburnin || g == mi, rec, rs);
     for (int mi = 0; mi < 2; ++mi) df_update_beta(p, f, mi, inburnin || g == mi, rec, rs);
@@ -588,6 +589,161 @@ __global__ void k_dfp_pseudo(const DiffParams *__restrict__ ps, double runlen)
     const DiffParams &p = ps[blockIdx.y];
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f < p.F) df_pseudo(p, f, runlen);
+}
+
+// ---- several chains of one comparison in one launch (mmg_diff_chains_*) ------------------------------------------------------
+// ps[c] is chain c's DiffParams: the slot layout, y / esq / M / P0 / P1 and class table of every chain are the same; the state block,
+// gam / tuned and `chain` are its own.  blockIdx.y picks the chain as it picks the comparison above, and the per-lane work is the same
+// df_iteration / df_tune / df_pseudo / df_init: chain c is the chain of a single handle whose seed is seed ^ (c << 32).
+// After the slots of df_layout every chain has DF_NB batch slots gb .. gb + DF_NB - 1: during sampling the lane adds its new gamma to
+// slot t / blen, t the chain's sampling index and blen = (total sampling length) / DF_NB.  The sums are integers in doubles.
+constexpr int DF_CHAINS_MAX = 16;   // chains per handle
+constexpr int DF_NB = 16;           // batches of the sampling run (batch means for the Monte Carlo standard error)
+
+__global__ void k_dfc_init(const DiffParams *__restrict__ ps, double logitp0, int gb)
+{
+    const DiffParams &p = ps[blockIdx.y];
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= p.F) return;
+    df_init(p, f, logitp0);
+    for (int b = 0; b < DF_NB; ++b) p.st[(size_t)(gb + b) * (size_t)p.F + (size_t)f] = 0.0;
+}
+
+// as k_dfp_run; in sampling (mode 2) t0 is the sampling index of the launch's first iteration, the same for every chain
+__global__ void __launch_bounds__(DF_BLOCK) k_dfc_run(const DiffParams *__restrict__ ps, const uint32_t *__restrict__ off, uint32_t it0, int t0,
+                                                      int n, int mode, int rec_from, int gb, int blen)
+{
+    const DiffParams &p = ps[blockIdx.y];
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= p.F) return;
+    const uint32_t it = off[blockIdx.y] + it0;
+    for (int j = 0; j < n; ++j) {
+        const int t = t0 + j;
+        df_iteration(p, f, it + (uint32_t)j, mode == 0, mode == 2 || t >= rec_from);
+        if (mode == 2) p.st[(size_t)(gb + t / blen) * (size_t)p.F + (size_t)f] += (double)p.gam[f];
+    }
+}
+
+// as k_dfp_tune, `active` the chains still tuning
+__global__ void __launch_bounds__(DF_BLOCK) k_dfc_tune(const DiffParams *__restrict__ ps, uint32_t active, uint32_t it0, int b,
+                                                       int *__restrict__ untuned)
+{
+    if (!((active >> blockIdx.y) & 1u)) return;
+    const DiffParams &p = ps[blockIdx.y];
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= p.F) return;
+    if (df_tune(p, f, it0, b)) atomicAdd(untuned + blockIdx.y, 1);
+}
+
+__global__ void k_dfc_pseudo(const DiffParams *__restrict__ ps, double runlen)
+{
+    const DiffParams &p = ps[blockIdx.y];
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f < p.F) df_pseudo(p, f, runlen);
+}
+
+MMG_HD double df_sigmoid(double x) { return x > 0 ? 1.0 / (1.0 + dexp(-x)) : dexp(x) / (1.0 + dexp(x)); }
+
+// The chains' estimates pooled, one lane per feature, after T sampling iterations.  Every sum runs over the
+// chains in ascending order.  out is SoA [DF_POOL_STATS + 2 Q][F], Q = 2 + 2 K + L0 + L1:
+//   0 log_bf       the root b of sum_c sigmoid(b + logitp_c) = sum_c gsum_c / T by 64 halvings of [-1024, 1024]; -inf / +inf when no / every
+//                  draw of any chain chose model 1
+//   1 log_bf_sd    the sd (divisor n - 1, two passes) of logit(gsum_c / T) - logitp_c over the mixed chains (0 < gsum_c < T); NaN below two
+//   2 log_bf_mcse  sqrt(sum_c v_c) / sum_c w_c, v_c the variance of chain c's mean gamma from its DF_NB batch means, w_c = s (1 - s) at
+//                  s = sigmoid(log_bf + logitp_c); NaN when log_bf is infinite
+//   3 chains_mixed
+//   then for q = 0 .. Q - 1 (alpha of models 0, 1; beta [2][K]; eta [L0 + L1], the order of mmg_diff_get_results) the chains' summed
+//   sums and summed counts: the host divides, as it does for a single handle.
+// A chain whose logit p' is not finite (pdash 0 or 1 without tuning) makes 0 .. 2 NaN.
+constexpr int DF_POOL_STATS = 4;
+
+MMG_HD void df_pool(const DiffParams *__restrict__ ps, int C, int T, int gb, double *__restrict__ out, int f)
+{
+    const DiffParams &p = ps[0];
+    const size_t F = (size_t)p.F;
+#define DFC_S(c, o) ps[c].st[(size_t)(o) * F + (size_t)f]
+    const double Td = (double)T, bl = (double)(T / DF_NB);
+    const double nan = __builtin_nan(""), inf = __builtin_inf();
+    double sumG = 0.0;
+    int mixed = 0;
+    bool finite = true;
+    for (int c = 0; c < C; ++c) {
+        const double G = DFC_S(c, p.gsum), o = DFC_S(c, p.logitp);
+        sumG += G;
+        if (G > 0.0 && G < Td) ++mixed;
+        if (!(o - o == 0.0)) finite = false;
+    }
+    double b = nan, sd = nan, mcse = nan;
+    if (finite) {
+        if (sumG == 0.0) b = -inf;
+        else if (sumG == (double)C * Td) b = inf;
+        else {
+            const double target = sumG / Td;
+            double lo = -1024.0, hi = 1024.0;
+            for (int k = 0; k < 64; ++k) {
+                const double mid = 0.5 * (lo + hi);
+                double s = 0.0;
+                for (int c = 0; c < C; ++c) s += df_sigmoid(mid + DFC_S(c, p.logitp));
+                if (s - target < 0.0) lo = mid;
+                else hi = mid;
+            }
+            b = 0.5 * (lo + hi);
+        }
+        if (mixed >= 2) {
+            double sum = 0.0, ss = 0.0;
+            for (int pass = 0; pass < 2; ++pass) {
+                const double mean = sum / (double)mixed;
+                for (int c = 0; c < C; ++c) {
+                    const double G = DFC_S(c, p.gsum);
+                    if (!(G > 0.0 && G < Td)) continue;
+                    const double g = G / Td;
+                    const double l = (dlog(g) - dlog(1.0 - g)) - DFC_S(c, p.logitp);
+                    if (pass == 0) sum += l;
+                    else ss += (l - mean) * (l - mean);
+                }
+            }
+            sd = dsqrt(ss / (double)(mixed - 1));
+        }
+        if (b - b == 0.0) {
+            double sv = 0.0, sw = 0.0;
+            for (int c = 0; c < C; ++c) {
+                const double g = DFC_S(c, p.gsum) / Td;
+                double acc = 0.0;
+                for (int k = 0; k < DF_NB; ++k) {
+                    const double dv = DFC_S(c, gb + k) / bl - g;
+                    acc += dv * dv;
+                }
+                sv += acc / (double)(DF_NB - 1) / (double)DF_NB;
+                const double s = df_sigmoid(b + DFC_S(c, p.logitp));
+                sw += s * (1.0 - s);
+            }
+            mcse = dsqrt(sv) / sw;
+        }
+    }
+    out[0 * F + f] = b;
+    out[1 * F + f] = sd;
+    out[2 * F + f] = mcse;
+    out[3 * F + f] = (double)mixed;
+    int q = 0;
+    auto pooled = [&](int oS, int oN) {
+        double S = 0.0, N = 0.0;
+        for (int c = 0; c < C; ++c) { S += DFC_S(c, oS); N += DFC_S(c, oN); }
+        out[(size_t)(DF_POOL_STATS + 2 * q) * F + f] = S;
+        out[(size_t)(DF_POOL_STATS + 2 * q + 1) * F + f] = N;
+        ++q;
+    };
+    for (int mi = 0; mi < 2; ++mi) pooled(p.m[mi].aS, p.m[mi].aN);
+    for (int mi = 0; mi < 2; ++mi)
+        for (int k = 0; k < p.K; ++k) pooled(p.m[mi].bS + k, p.m[mi].bN + k);
+    for (int mi = 0; mi < 2; ++mi)
+        for (int l = 0; l < p.m[mi].L; ++l) pooled(p.m[mi].eS + l, p.m[mi].eN + l);
+#undef DFC_S
+}
+
+__global__ void k_dfc_pool(const DiffParams *__restrict__ ps, int C, int T, int gb, double *__restrict__ out)
+{
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f < ps[0].F) df_pool(ps, C, T, gb, out, f);
 }
 
 } // namespace mmg

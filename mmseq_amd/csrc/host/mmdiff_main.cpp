@@ -7,6 +7,9 @@
 // Polytomous model selection (the reference's recipe: one mmdiff run per alternative, then polyclass() of src/R/mmseq.R) is built in:
 // repeated -m runs J alternatives against one model 0 on one device handle (mmg_diff_poly_*), and -polyclass combines mmdiff tables on
 // the host alone.
+//
+// -chains C runs C independent chains of one comparison on one device handle (mmg_diff_chains_*) and prints their pooled table:
+// run_chains and DESIGN.md section 10.2.
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -27,6 +30,7 @@ using namespace std;
 #define OUTLEN 1024
 #define MAXBATCHES 8192
 #define MAXMODELS 16   // alternatives (-m) in one run
+#define MAXCHAINS 16   // chains (-chains) in one run
 
 namespace {
 
@@ -70,6 +74,7 @@ void printUsage(ostream &out)
         << "       matrices_file contains M P0 P1 each separated by an empty line" << endl
         << "       mmdiff [OPTIONS...] [-prior P0,...,PJ] [-polyout BASE] -m alt1 -m alt2 [-m ...] mmseq_file1 mmseq_file2... > out.polyclass" << endl
         << "       mmdiff -polyclass [-prior P0,...,PJ] a.mmdiff b.mmdiff [...] > out.polyclass" << endl
+        << "       mmdiff [OPTIONS...] -chains C [-chainout BASE] [-de n1 n2 ... nC | -m matrices_file] mmseq_file1 mmseq_file2... > out.mmdiff" << endl
         << endl;
     out << "Mandatory arguments:" << endl
         << "  ONE OF:" << endl
@@ -99,7 +104,11 @@ void printUsage(ostream &out)
         << "  -range INT INT    select features indexed within range (default: all)" << endl
         << "  -prior P0,...,PJ  with repeated -m or -polyclass: prior probabilities of models 0..J, adding up to 1 (default: flat)" << endl
         << "  -polyout STRING   with repeated -m: write the mmdiff table of alternative j to STRING.model<j>.mmdiff" << endl
-        << "Size limits: 512 samples, 8 columns of M, 16 columns of P0 and P1, 16 variance classes per model, 16 alternatives (-m) per run." << endl;
+        << "  -chains INT       run INT (1 to 16) independent chains, seeded (seed, chain), and print their pooled table: the Bayes factor" << endl
+        << "                    from all chains and the columns log_bf, log_bf_sd, log_bf_mcse, chains_mixed appended (default: 1, the" << endl
+        << "                    plain table); not with repeated -m or -polyclass (chains of several alternatives are left for later)" << endl
+        << "  -chainout STRING  with -chains: write the mmdiff table of chain c to STRING.chain<c>.mmdiff" << endl
+        << "Size limits: 512 samples, 8 columns of M, 16 columns of P0 and P1, 16 variance classes per model, 16 alternatives (-m) per run, 16 chains." << endl;
 }
 
 [[noreturn]] void usage_error(const string &msg)
@@ -425,9 +434,19 @@ struct DiffResults {
     DiffResults(size_t F, const Design &D) : gm(F), logitp(F), alpha(2 * F), beta(2 * D.K * F), eta((D.L0 + D.L1) * F) {}
 };
 
-// the table of one comparison: to fp (if any) and appended to *keep (if any)
+// what the pooled table of several chains has besides a chain's: the logarithm of its Bayes factor and three more columns, [F] each
+struct PooledCols {
+    vector<double> log_bf, log_bf_sd, log_bf_mcse;
+    vector<uint32_t> chains_mixed;
+    PooledCols(size_t F) : log_bf(F), log_bf_sd(F), log_bf_mcse(F), chains_mixed(F) {}
+};
+
+// The table of one comparison: to fp (if any) and appended to *keep (if any).  The Bayes factor is the chain's own, with the warning for
+// a gamma that did not mix -- or, with `pool` (the pooled table of several chains: its columns are appended), exp(log_bf).  warn_stuck:
+// off for the tables of a run of several chains, which reports mixing per feature itself.
 void write_table(FILE *fp, string *keep, const vector<string> &features, const vector<string> &filenames, const Design &D, bool fixalpha,
-                 bool Mnil, const bool Pnil[2], double p, const Mat &y, const Mat &e, const DiffResults &r)
+                 bool Mnil, const bool Pnil[2], double p, const Mat &y, const Mat &e, const DiffResults &r, bool warn_stuck = true,
+                 const PooledCols *pool = nullptr)
 {
     const size_t F = features.size(), S = filenames.size();
     const vector<double> &gm = r.gm, &logitp = r.logitp, &alpha = r.alpha, &beta = r.beta, &eta = r.eta;
@@ -455,17 +474,22 @@ void write_table(FILE *fp, string *keep, const vector<string> &features, const v
         }
         out += "mu_" + samplenames[f] + "\t";
     }
-    for (size_t f = 0; f < S; f++) out += "sd_" + samplenames[f] + (f < S - 1 ? "\t" : "\n");
+    for (size_t f = 0; f < S; f++) out += "sd_" + samplenames[f] + (f < S - 1 ? "\t" : "");
+    out += pool ? "\tlog_bf\tlog_bf_sd\tlog_bf_mcse\tchains_mixed\n" : "\n";
     emit(out);
     const double logp = log(p), log1mp = log1p(-p);
     for (size_t feature = 0; feature < F; feature++) {
         out.clear();
         const double g = gm[feature];
-        if (g == 0.0 || g == 1.0)
+        if (warn_stuck && (g == 0.0 || g == 1.0))
             cerr << "Warning: gamma did not mix for feature " << feature << "; stuck in model " << (int)g << endl;
         const double lgp = logitp[feature];
         const double pp_ = lgp > 0 ? 1.0 / (1.0 + exp(-lgp)) : exp(lgp) / (1.0 + exp(lgp));   // BMS::getp
-        const double BF = g / (1.0 - g) * (1.0 - pp_) / pp_;
+        double BF = g / (1.0 - g) * (1.0 - pp_) / pp_;
+        if (pool) {
+            const double b = pool->log_bf[feature];
+            BF = std::isnan(b) ? b : (std::isinf(b) ? (b < 0 ? 0.0 : b) : mmg::dexp(b));
+        }
         const double postlogodds = log(BF) + logp - log1mp;
         double pp = 1.0 / (1.0 + exp(-postlogodds));
         if (BF >= DBL_MAX) pp = 1.0;
@@ -478,7 +502,11 @@ void write_table(FILE *fp, string *keep, const vector<string> &features, const v
                 for (size_t l = 0; l < (model ? D.L1 : D.L0); l++) out += fmt(eta[((model ? D.L0 : 0) + l) * F + feature]) + "\t";
         }
         for (size_t f = 0; f < S; f++) out += fmt(y[feature * S + f]) + "\t";
-        for (size_t f = 0; f < S; f++) out += fmt(e[feature * S + f]) + (f < S - 1 ? "\t" : "\n");
+        for (size_t f = 0; f < S; f++) out += fmt(e[feature * S + f]) + (f < S - 1 ? "\t" : "");
+        if (pool)
+            out += "\t" + fmt(pool->log_bf[feature]) + "\t" + fmt(pool->log_bf_sd[feature]) + "\t" + fmt(pool->log_bf_mcse[feature]) + "\t"
+                   + to_string(pool->chains_mixed[feature]);
+        out += "\n";
         emit(out);
     }
 }
@@ -722,14 +750,82 @@ int run_poly(const vector<string> &mats, bool prior_given, const string &prior_t
     return 0;
 }
 
+// -chains C, C >= 2: C chains of one comparison on one device handle, chain c keyed (seed, c).  Table c (what a single run prints for
+// that chain) goes to BASE.chain<c>.mmdiff with -chainout; stdout gets the pooled table.
+int run_chains(int C, bool chainout_given, const string &chainout, const Design &D, bool Mnil, const bool Pnil[2],
+               const vector<string> &features, const vector<string> &filenames, const Mat &y, const Mat &e, double p, double d, double s,
+               double pdash, bool fixalpha, bool tune, int burnin, int mcmciters, uint64_t useed)
+{
+    const size_t S = filenames.size(), F = features.size();
+    struct Closer { vector<FILE *> f; ~Closer() { for (FILE *x : f) if (x) fclose(x); } } files;
+    files.f.assign(C, nullptr);
+    auto name = [&](int c) { return chainout + ".chain" + to_string(c) + ".mmdiff"; };
+    if (chainout_given)
+        for (int c = 0; c < C; ++c)
+            if (!(files.f[c] = fopen(name(c).c_str(), "w"))) die("Error: couldn't create " + name(c));
+
+    // every input is checked: now the device
+    int ndev = 0;
+    if (mmg_device_count(&ndev) != 0 || ndev < 1) die("Error: no HIP device available: mmdiff has no CPU fallback");
+    mmg_diff_chains *h = nullptr;
+    MMG_CHECK(mmg_diff_chains_create(0, (uint32_t)F, (uint32_t)S, y.data(), e.data(), (uint32_t)D.K, D.M.data(), (uint32_t)D.L0, D.P0.data(),
+                                     (uint32_t)D.L1, D.P1.data(), D.C.data(), d, s, pdash, fixalpha ? 1 : 0, useed, (uint32_t)C,
+                                     (uint32_t)mcmciters, &h));
+    cerr << "BURNIN (" << burnin << " iterations, " << C << " chains)...";
+    MMG_CHECK(mmg_diff_chains_burnin(h, (uint32_t)burnin));
+    cerr << "\nSetting pseudopriors...done.\n";
+    if (tune) {
+        // each chain stops at the first batch after which none of its features is untuned, or with the others at MAXBATCHES
+        vector<uint32_t> untuned(C);
+        vector<int32_t> ended(C);
+        int numbatches = 0;
+        bool all_ended = false;
+        while (!all_ended && numbatches != MAXBATCHES) {
+            MMG_CHECK(mmg_diff_chains_tune_batch(h, untuned.data(), ended.data()));
+            numbatches++;
+            all_ended = true;
+            uint64_t left = 0;
+            for (int c = 0; c < C; ++c) { all_ended = all_ended && ended[c]; left += untuned[c]; }
+            if (numbatches % 64 == 0) cerr << "TUNING BATCH " << numbatches << " (" << left << " left)\r";
+        }
+    }
+    for (int c = 0; c < C; ++c) {
+        uint32_t nb = 0;
+        MMG_CHECK(mmg_diff_chains_info(h, (uint32_t)c, NULL, NULL, &nb, NULL));
+        cerr << "chain " << c << ": sampling after " << nb << " tuning batches\n";
+    }
+    cerr << "TRACE (" << mcmciters << " iterations)";
+    MMG_CHECK(mmg_diff_chains_sample(h, (uint32_t)mcmciters));
+    MMG_CHECK(mmg_diff_chains_pool(h));
+    cerr << "\nDONE MCMC\n";
+    DiffResults r(F, D);
+    for (int c = 0; c < C && chainout_given; ++c) {
+        MMG_CHECK(mmg_diff_chains_get_results(h, (uint32_t)c, r.gm.data(), r.logitp.data(), r.alpha.data(), r.beta.data(), r.eta.data()));
+        write_table(files.f[c], nullptr, features, filenames, D, fixalpha, Mnil, Pnil, p, y, e, r, false);
+        if (fflush(files.f[c]) != 0) die("Error: couldn't write " + name(c));
+    }
+    // the pooled table: chain 0's gamma mean and logit p' are not printed (the Bayes factor is exp(log_bf)), the means are the pooled ones
+    PooledCols pool(F);
+    MMG_CHECK(mmg_diff_chains_get_results(h, 0, r.gm.data(), r.logitp.data(), NULL, NULL, NULL));
+    MMG_CHECK(mmg_diff_chains_get_pooled(h, pool.log_bf.data(), pool.log_bf_sd.data(), pool.log_bf_mcse.data(), pool.chains_mixed.data(),
+                                         r.alpha.data(), r.beta.data(), r.eta.data()));
+    mmg_diff_chains_destroy(h);
+    for (size_t f = 0; f < F; ++f)
+        if (pool.chains_mixed[f] < (uint32_t)C)
+            cerr << "Warning: gamma mixed in " << pool.chains_mixed[f] << " of " << C << " chains for feature " << f << endl;
+    write_table(stdout, nullptr, features, filenames, D, fixalpha, Mnil, Pnil, p, y, e, r, false, &pool);
+    return 0;
+}
+
 } // namespace
 
 int main(int argc, char **argv)
 {
     string matrices_file = "";
     vector<string> matrices_files;   // every -m; more than one: the polytomous run
-    bool polyclass_mode = false, prior_given = false, polyout_given = false;
-    string prior_text, polyout;
+    bool polyclass_mode = false, prior_given = false, polyout_given = false, chains_given = false, chainout_given = false;
+    string prior_text, polyout, chainout;
+    int chains = 1;
     double p = 0.1, d = 1.4, s = 2.0;
     int burnin = 8192, mcmciters = 16384, seed = 1234, range_start = -1, range_end = -1;
     bool useprops = false, fixalpha = false, normalise = true, customuhfrac = false, permute = false, tune = true;
@@ -841,6 +937,16 @@ int main(int argc, char **argv)
         } else if (a0 == "-polyout") {
             polyout = take();
             polyout_given = true;
+        } else if (a0 == "-chains") {
+            const string v = take();
+            char *end = NULL;
+            const long n = strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end != '\0' || n < 1 || n > MAXCHAINS) die("Error: -chains takes an integer between 1 and " + to_string(MAXCHAINS) + ".");
+            chains = (int)n;
+            chains_given = true;
+        } else if (a0 == "-chainout") {
+            chainout = take();
+            chainout_given = true;
         } else if (a0 == "-h" || a0 == "--help" || a0 == "-help") {
             cerr << "Bayesian model selection for RNA-seq expression estimates.\n";
             printUsage(cerr);
@@ -860,6 +966,9 @@ int main(int argc, char **argv)
     if ((prior_given || polyout_given) && !poly_run && !polyclass_mode)
         usage_error("Error: -prior and -polyout need more than one -m (or, -prior, -polyclass).");
     if (polyout_given && !poly_run) usage_error("Error: -polyout needs more than one -m.");
+    if (chainout_given && !chains_given) usage_error("Error: -chainout needs -chains.");
+    if (chains_given && (poly_run || polyclass_mode))
+        usage_error("Error: -chains cannot be combined with more than one -m or with -polyclass (chains of several alternatives are left for later).");
     if (polyclass_mode) {
         // host only: no device is looked for
         const size_t J = arguments.size();
@@ -922,6 +1031,13 @@ int main(int argc, char **argv)
     if (poly_run) return run_poly(matrices_files, prior_given, prior_text, polyout_given, polyout, features, filenames, y, e, p, d, s, pdash,
                                   fixalpha, tune, burnin, mcmciters, useed);
     validate_design(D, S, fixalpha, Mnil, Pnil);
+    if (chains > 1)
+        return run_chains(chains, chainout_given, chainout, D, Mnil, Pnil, features, filenames, y, e, p, d, s, pdash, fixalpha, tune, burnin,
+                          mcmciters, useed);
+    // -chains 1 -chainout BASE: the plain run, its table to BASE.chain0.mmdiff as well
+    struct Closer { FILE *f = nullptr; ~Closer() { if (f) fclose(f); } } chain0;
+    const string chain0_name = chainout + ".chain0.mmdiff";
+    if (chainout_given && !(chain0.f = fopen(chain0_name.c_str(), "w"))) die("Error: couldn't create " + chain0_name);
 
     // every input is checked: now the device
     int ndev = 0;
@@ -949,6 +1065,8 @@ int main(int argc, char **argv)
     DiffResults r(F, D);
     MMG_CHECK(mmg_diff_get_results(h, r.gm.data(), r.logitp.data(), r.alpha.data(), r.beta.data(), r.eta.data()));
     mmg_diff_destroy(h);
-    write_table(stdout, nullptr, features, filenames, D, fixalpha, Mnil, Pnil, p, y, e, r);
+    string text;
+    write_table(stdout, chain0.f ? &text : nullptr, features, filenames, D, fixalpha, Mnil, Pnil, p, y, e, r);
+    if (chain0.f && (fputs(text.c_str(), chain0.f) < 0 || fflush(chain0.f) != 0)) die("Error: couldn't write " + chain0_name);
     return 0;
 }

@@ -2,7 +2,8 @@
 
 `Diff` holds every feature's MCMC state on the device (src/bms.cpp driven as src/mmdiff.cpp:744-866): `burnin` runs the burn-in and
 sets the pseudopriors, `tune_batch` one tuning batch of 128 iterations, `sample` the sampling iterations, `results` the posterior
-means.  No CPU path exists: without a device every call raises.
+means.  `DiffPoly` runs several alternatives against one model 0 on one handle, `DiffChains` several chains of one comparison.  No
+CPU path exists: without a device every call raises.
 """
 import ctypes as C
 
@@ -162,6 +163,101 @@ class DiffPoly:
     def close(self):
         if self._h:
             self._lib.mmg_diff_poly_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DiffChains:
+    """C independent chains of one comparison on one handle (the mmg_diff_chains_* entries).  Chain c draws from the streams
+    (seed, c, ...) and is bit for bit `Diff(..., seed=seed ^ (c << 32))` driven the same way; each chain tunes on its own and keeps
+    its batch count.  `sample_total` (a positive multiple of 16) is the whole sampling length: `sample` may be called in pieces that
+    add up to it, and `pool` then forms the pooled estimates."""
+
+    NB = 16
+
+    def __init__(self, y, e, M, P0, P1, classes, n_chains, sample_total, d=1.4, s=2.0, pdash=0.5, fixalpha=False, seed=1234, device=0):
+        self._lib = _lib.load()
+        self._h = None
+        y = np.ascontiguousarray(y, np.float64)
+        e = np.ascontiguousarray(e, np.float64)
+        M = np.ascontiguousarray(M, np.float64)
+        P = [np.ascontiguousarray(P0, np.float64), np.ascontiguousarray(P1, np.float64)]
+        Cl = np.ascontiguousarray(classes, np.int32)
+        F, N = y.shape
+        if e.shape != (F, N) or M.shape[0] != N or P[0].shape[0] != N or P[1].shape[0] != N or Cl.shape != (N, 2):
+            raise ValueError("inconsistent shapes")
+        self.F, self.N, self.K = F, N, M.shape[1]
+        self.L = (P[0].shape[1], P[1].shape[1])
+        self.C, self.T = int(n_chains), int(sample_total)
+        h = C.c_void_p()
+        check(self._lib.mmg_diff_chains_create(device, F, N, _ptr(y), _ptr(e), self.K, _ptr(M), self.L[0], _ptr(P[0]), self.L[1], _ptr(P[1]),
+                                               _ptr(Cl), float(d), float(s), float(pdash), int(bool(fixalpha)),
+                                               int(seed) & 0xFFFFFFFFFFFFFFFF, self.C, self.T, C.byref(h)))
+        self._h = h
+
+    def burnin(self, iters):
+        check(self._lib.mmg_diff_chains_burnin(self._h, int(iters)))
+
+    def tune_batch(self):
+        """One tuning batch for the chains that have not ended; (untuned counts, ended flags), one entry per chain."""
+        n, ended = (C.c_uint32 * self.C)(), (C.c_int32 * self.C)()
+        check(self._lib.mmg_diff_chains_tune_batch(self._h, n, ended))
+        return list(n), [bool(v) for v in ended]
+
+    def tune(self, max_batches=MAXBATCHES):
+        """Batches until every chain has ended or max_batches have run; the batch count of each chain."""
+        nb = 0
+        while nb != max_batches:
+            _, ended = self.tune_batch()
+            nb += 1
+            if all(ended):
+                break
+        return [self.info(c)["batches"] for c in range(self.C)]
+
+    def sample(self, iters):
+        check(self._lib.mmg_diff_chains_sample(self._h, int(iters)))
+
+    def pool(self):
+        check(self._lib.mmg_diff_chains_pool(self._h))
+
+    def results(self, c):
+        F, K, L = self.F, self.K, self.L
+        out = dict(gamma_mean=np.empty(F), logitp=np.empty(F), alpha=np.empty((2, F)), beta=np.empty((2, K, F)), eta=np.empty((L[0] + L[1], F)))
+        check(self._lib.mmg_diff_chains_get_results(self._h, int(c), *(_ptr(out[k]) for k in ("gamma_mean", "logitp", "alpha", "beta", "eta"))))
+        return out
+
+    def batch_sums(self, c):
+        out = np.empty((self.NB, self.F))
+        check(self._lib.mmg_diff_chains_get_batch_sums(self._h, int(c), _ptr(out)))
+        return out
+
+    def pooled(self):
+        F, K, L = self.F, self.K, self.L
+        out = dict(log_bf=np.empty(F), log_bf_sd=np.empty(F), log_bf_mcse=np.empty(F), chains_mixed=np.empty(F, np.uint32),
+                   alpha=np.empty((2, F)), beta=np.empty((2, K, F)), eta=np.empty((L[0] + L[1], F)))
+        check(self._lib.mmg_diff_chains_get_pooled(self._h, *(_ptr(out[k]) for k in ("log_bf", "log_bf_sd", "log_bf_mcse", "chains_mixed",
+                                                                                      "alpha", "beta", "eta"))))
+        return out
+
+    def info(self, c):
+        flags, nc, nb, ended = (C.c_int32 * 3)(), (C.c_uint32 * 2)(), C.c_uint32(), C.c_int32()
+        check(self._lib.mmg_diff_chains_info(self._h, int(c), flags, nc, C.byref(nb), C.byref(ended)))
+        return dict(Mnil=bool(flags[0]), Pnil=(bool(flags[1]), bool(flags[2])), n_classes=(nc[0], nc[1]), batches=nb.value,
+                    ended=bool(ended.value))
+
+    def device_bytes(self):
+        b = C.c_uint64()
+        check(self._lib.mmg_diff_chains_device_bytes(self._h, C.byref(b)))
+        return b.value
+
+    def close(self):
+        if self._h:
+            self._lib.mmg_diff_chains_destroy(self._h)
             self._h = None
 
     def __del__(self):
