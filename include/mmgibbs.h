@@ -444,7 +444,8 @@ enum {
     MMG_OPT_FAIL_ALLOC = 12,       /* v >= 0: the v-th acquisition of device memory, a stream or an event after this option is set (counted from 0) fails
                                       without reaching the runtime (error paths) */
     MMG_OPT_CONV_SLAB = 13,        /* v >= 1: at most v series per slab of mmg_convergence_create / _of_traces (slab edges on small inputs)     */
-    MMG_OPT_COUNT_ = 14
+    MMG_OPT_DIFF_TRACE_ROWS = 14,  /* v >= 1: at most v rows per row buffer of mmg_diff_trace_open (shortened traced launches on small inputs)    */
+    MMG_OPT_COUNT_ = 15
 };
 int mmg_selftest_option(int option, int value);
 /* What the library holds: counts[3] = device buffers, streams, events (tests: every call gives back what it acquired). */
@@ -533,7 +534,8 @@ typedef struct mmg_diff mmg_diff;
 int mmg_diff_create(int device, uint32_t n_features, uint32_t n_samples, const double *y, const double *e, uint32_t K, const double *M,
                     uint32_t L0, const double *P0, uint32_t L1, const double *P1, const int32_t *C, double d, double s, double pdash,
                     int fixalpha, uint64_t seed, mmg_diff **out);
-/* the burn-in (a positive multiple of 1024 iterations, recorded from iteration 102), then the pseudopriors from its record */
+/* the burn-in (at least 104 iterations, recorded from iteration 102; the CLI takes multiples of 1024, as the reference does), then
+ * the pseudopriors from its record */
 int mmg_diff_burnin(mmg_diff *h, uint32_t iters);
 /* one tuning batch of 128 iterations; *untuned = the features still untuned after the batch's tuning step */
 int mmg_diff_tune_batch(mmg_diff *h, uint32_t *untuned);
@@ -546,6 +548,38 @@ int mmg_diff_get_results(mmg_diff *h, double *gamma_mean, double *logitp, double
 int mmg_diff_info(mmg_diff *h, int32_t *flags, uint32_t *n_classes, uint32_t *batches);
 int mmg_diff_device_bytes(mmg_diff *h, uint64_t *bytes);
 void mmg_diff_destroy(mmg_diff *h);
+
+/* ---- mmdiff: traces (what the reference writes under -tracedir).  Additive in ABI version 8. ----
+ * The traced parameters, in the order of BMS::initialise_streams and named as its files are: alpha0, alpha1; beta0_i, beta1_i per
+ * column of M; eta0_l, eta1_l; lambda0_l, lambda1_l per column of P0 / P1; sigmasq0_c, sigmasq1_c per class; rho0, rho1; gamma (as
+ * 0.0 / 1.0).  A nil M or P keeps its columns, at their starting values.  *n_params counts gamma, the last one; *n_pseudo is the
+ * number of columns of mmg_diff_get_pseudo.  Either pointer may be NULL. */
+int mmg_diff_trace_layout(mmg_diff *h, uint32_t *n_params, uint32_t *n_pseudo);
+/* the name of traced parameter `param` into name[len] */
+int mmg_diff_trace_name(mmg_diff *h, uint32_t param, char *name, uint32_t len);
+/* The sink of recorded rows: phase 0 is the burn-in, 1 sampling; rows [first_row, first_row + n_rows) of that phase, row r the state
+ * after the iteration r * every of the phase (sampling iterations count from the first one), as rows[(r - first_row) * P + s][F]
+ * with P = n_params in sampling and n_params - 1 (no gamma) in burn-in.  `rows` is valid during the call.  A non-zero return stops
+ * the run: the entry that was running returns MMG_ERR_IO, and every later burnin / tune_batch / sample MMG_ERR_STATE. */
+typedef int (*mmg_diff_trace_sink)(void *user, int phase, uint32_t first_row, uint32_t n_rows, const double *rows);
+/* Before mmg_diff_burnin: record every every_burnin-th burn-in and every every_sample-th sampling iteration (both >= 1) and hand
+ * the rows to `sink` on the calling thread while the next launch runs.  Recording draws nothing: the chain is the one of an untraced
+ * handle, bit for bit.  The handle then holds two row buffers on the device (counted by mmg_diff_device_bytes: together
+ * 2 * R * n_params * F * 8 bytes, R = min(ceil(512 / min(every_burnin, every_sample)), max(1, 64 MiB / (n_params * F * 8))) rows (at most MMG_OPT_DIFF_TRACE_ROWS, if set), and
+ * 2 * 496 bytes of launch descriptors) and two of each in pinned host memory.  MMG_ERR_ARG for an interval of 0 or above
+ * 2^30 = 1073741824, or once the burn-in has run. */
+int mmg_diff_trace_open(mmg_diff *h, uint32_t every_burnin, uint32_t every_sample, mmg_diff_trace_sink sink, void *user);
+/* After the burn-in: mean_lo[F] = (the sum of the log odds since the feature's last tuning step) / 128 and logitp[F] = logit p' as
+ * they stand -- before tuning batch b >= 1 what BMS::printtune prints at its start, for tuned (frozen) features too.  Either may be NULL. */
+int mmg_diff_get_tune_state(mmg_diff *h, double *mean_lo, double *logitp);
+/* After the burn-in: the pseudopriors as out[n_pseudo][F], in the column order of BMS::print_pseudo -- per model A, Valpha; B, Vbeta
+ * per column of M; F, Veta, S = 1 / S_inv per column of P; J, L per class; Q, R. */
+int mmg_diff_get_pseudo(mmg_diff *h, double *out);
+/* Self test, no device: the row buffer and one launch of a traced run as mmg_diff_trace_open and the traced phases plan them.  *cap = the
+ * rows a buffer holds for n_params x n_features at the denser interval every_min (max_rows: MMG_OPT_DIFF_TRACE_ROWS, 0 = none); the
+ * launch at phase index tt with `left` iterations to go at interval `every` covers *n iterations and rows [*first_row, *first_row + *rows). */
+int mmg_selftest_diff_trace_plan(uint32_t n_params, uint32_t n_features, uint32_t every_min, uint32_t max_rows, uint32_t tt, uint32_t left,
+                                 uint32_t every, uint32_t *cap, uint32_t *first_row, uint32_t *rows, uint32_t *n);
 
 /* ---- mmdiff, polytomous: J alternatives against one model 0 on one handle ------------------------------------------------
  * Comparison j (0 <= j < J <= 16) is model 0 against alternative j, and its chain is bit for bit the chain of an mmg_diff handle

@@ -39,7 +39,7 @@ class MMGError(RuntimeError):
 
 LAYOUT_CANONICAL, LAYOUT_KEEP_ROWS = 0, 1
 # mmg_selftest_option ids
-OPT_SAMPLE_KERNEL, OPT_FORCE_IDX64, OPT_SELL_WAVES_PER_CU, OPT_EM_KERNEL, OPT_EM_GRID, OPT_FUSE_CHAINS, OPT_CNT_REPLICAS, OPT_GROUP_FAIL, OPT_DERIVE_ORDER, OPT_WIRE_CHECK, OPT_BIGK_PER_WAVE, OPT_BIGK_SIDE_STREAM, OPT_FAIL_ALLOC, OPT_CONV_SLAB = range(14)
+OPT_SAMPLE_KERNEL, OPT_FORCE_IDX64, OPT_SELL_WAVES_PER_CU, OPT_EM_KERNEL, OPT_EM_GRID, OPT_FUSE_CHAINS, OPT_CNT_REPLICAS, OPT_GROUP_FAIL, OPT_DERIVE_ORDER, OPT_WIRE_CHECK, OPT_BIGK_PER_WAVE, OPT_BIGK_SIDE_STREAM, OPT_FAIL_ALLOC, OPT_CONV_SLAB, OPT_DIFF_TRACE_ROWS = range(15)
 
 
 class ProblemDesc(C.Structure):
@@ -148,6 +148,12 @@ SYMBOLS = {
     "mmg_diff_info": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmg_diff_device_bytes": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mmg_diff_destroy": (None, [C.c_void_p]),
+    "mmg_diff_trace_layout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmg_diff_trace_name": (C.c_int, [C.c_void_p, C.c_uint32, C.c_char_p, C.c_uint32]),
+    "mmg_diff_trace_open": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "mmg_diff_get_tune_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmg_diff_get_pseudo": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mmg_selftest_diff_trace_plan": (C.c_int, [C.c_uint32] * 7 + [C.c_void_p] * 4),
     "mmg_diff_poly_create": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
                                        C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int,
                                        C.c_uint64, C.c_void_p]),

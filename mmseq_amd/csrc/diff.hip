@@ -4,7 +4,9 @@
 #include "mmg_host.h"
 
 #include <cmath>
+#include <cstdio>
 #include <memory>
+#include <string>
 #include <vector>
 
 using namespace mmg;
@@ -14,7 +16,26 @@ constexpr uint32_t DF_CHUNK = 512;    // iterations per launch of burn-in and sa
 constexpr int DF_REC_FROM = 102;      // OUTLEN / 10: burn-in iterations before this one are not recorded
 }
 
-// Members are destroyed in reverse declaration order: the destructor waits for `st`, then the buffers go, and the stream last.
+// What mmg_diff_trace_open adds to a handle: the copy stream, two row buffers on the device and two in pinned host memory, and the
+// events between them.  Launch i records into d_rows[i & 1]; the copy stream waits for it and copies to h_rows[i & 1]; the host hands
+// launch i - 1's rows to the sink while launch i runs.
+struct DiffTracing {
+    DevStream copy;
+    DevEvent ran[2], copied[2];
+    DevBuf<double> d_rows[2];
+    PinnedBuf<double> h_rows[2];
+    DevBuf<DiffTrace> d_q;         // [2] the descriptor of the launch that records into d_rows[b], copied from h_q[b] ahead of it
+    PinnedBuf<DiffTrace> h_q;      // [2]
+    DiffTrace q{};                 // the slot table; tr, P, every, tt0 are set per launch
+    int P = 0;                     // traced parameters, gamma (the last one, sampling only) included
+    uint32_t every[2] = {1, 1};    // burn-in, sampling
+    uint32_t cap = 0;              // rows a buffer holds
+    mmg_diff_trace_sink sink = nullptr;
+    void *user = nullptr;
+    bool stopped = false;          // the sink returned non-zero: the chain is part way through a phase
+};
+
+// Members are destroyed in reverse declaration order: the destructor waits for the streams, then the buffers go, and `st` last.
 struct mmg_diff {
     DevStream st;
     int device = 0;
@@ -26,7 +47,12 @@ struct mmg_diff {
     uint32_t burnin = 0, batches = 0, sampled = 0;
     bool burnt = false;
     uint64_t device_bytes = 0;
-    ~mmg_diff() { if (st) (void)hipStreamSynchronize(st.get()); }
+    std::unique_ptr<DiffTracing> tr;
+    ~mmg_diff()
+    {
+        if (st) (void)hipStreamSynchronize(st.get());
+        if (tr && tr->copy) (void)hipStreamSynchronize(tr->copy.get());
+    }
 };
 
 // the reference's "nil" rule (BMS::BMS): a single column whose entries differ by less than 1e-5 is no covariate at all
@@ -195,15 +221,207 @@ extern "C" int mmg_diff_create(int device, uint32_t F, uint32_t N, const double 
     return MMG_OK;
 }
 
+// ---- traces ------------------------------------------------------------------------------------------------------------------
+static_assert(sizeof(DiffTrace) == 496, "mmg_diff_device_bytes with tracing open is documented with this size (include/mmgibbs.h)");
+constexpr uint64_t DF_TRACE_BUF_BYTES = 64u << 20;   // the most one row buffer takes (Traces), one row at least
+
+// the traced parameters in the order of BMS::initialise_streams: their names (if asked for) and state slots; the count
+static int df_trace_table(const mmg_diff *h, std::vector<std::string> *names, int *slot)
+{
+    const DiffParams &p = h->p;
+    int n = 0;
+    auto add = [&](const char *stem, int mi, int idx, int o) {
+        if (names) names->push_back(std::string(stem) + std::to_string(mi) + (idx < 0 ? std::string() : "_" + std::to_string(idx)));
+        if (slot) slot[n] = o;
+        ++n;
+    };
+    for (int mi = 0; mi < 2; ++mi) add("alpha", mi, -1, p.m[mi].alpha);
+    for (int mi = 0; mi < 2; ++mi)
+        for (int k = 0; k < p.K; ++k) add("beta", mi, k, p.m[mi].beta + k);
+    for (int mi = 0; mi < 2; ++mi)
+        for (int l = 0; l < p.m[mi].L; ++l) add("eta", mi, l, p.m[mi].eta + l);
+    for (int mi = 0; mi < 2; ++mi)
+        for (int l = 0; l < p.m[mi].L; ++l) add("lambda", mi, l, p.m[mi].lam + l);
+    for (int mi = 0; mi < 2; ++mi)
+        for (int c = 0; c < p.m[mi].nc; ++c) add("sigmasq", mi, c, p.m[mi].sig + c);
+    for (int mi = 0; mi < 2; ++mi) add("rho", mi, -1, p.m[mi].rho);
+    if (names) names->push_back("gamma");
+    if (slot) slot[n] = -1;
+    return n + 1;
+}
+
+// the columns of BMS::print_pseudo per model: A, Valpha; B, Vbeta per column of M; F, Veta, S per column of P; J, L per class; Q, R
+static uint32_t df_pseudo_cols(const mmg_diff *h)
+{
+    uint32_t n = 0;
+    for (int mi = 0; mi < 2; ++mi) n += 2 + 2 * h->K + 3 * h->L[mi] + 2 * (uint32_t)h->p.m[mi].nc + 2;
+    return n;
+}
+
+extern "C" int mmg_diff_trace_layout(mmg_diff *h, uint32_t *n_params, uint32_t *n_pseudo)
+{
+    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
+    if (n_params) *n_params = (uint32_t)df_trace_table(h, nullptr, nullptr);
+    if (n_pseudo) *n_pseudo = df_pseudo_cols(h);
+    return MMG_OK;
+}
+
+extern "C" int mmg_diff_trace_name(mmg_diff *h, uint32_t param, char *name, uint32_t len)
+{
+    if (!h || !name || len == 0) return fail(MMG_ERR_ARG, "NULL argument");
+    std::vector<std::string> names;
+    df_trace_table(h, &names, nullptr);
+    if (param >= names.size()) return fail(MMG_ERR_ARG, "no such traced parameter");
+    if (names[param].size() + 1 > len) return fail(MMG_ERR_ARG, "the name buffer is too short");
+    std::snprintf(name, len, "%s", names[param].c_str());
+    return MMG_OK;
+}
+
+extern "C" int mmg_diff_trace_open(mmg_diff *h, uint32_t every_burnin, uint32_t every_sample, mmg_diff_trace_sink sink, void *user)
+{
+    // (the intervals first: the row arithmetic of the launcher and the kernel is written for this range)
+    if (every_burnin == 0 || every_sample == 0 || every_burnin > DF_TRACE_EVERY_MAX || every_sample > DF_TRACE_EVERY_MAX)
+        return fail(MMG_ERR_ARG, "the thinning intervals must be at least 1 and at most 1073741824");
+    if (!h || !sink) return fail(MMG_ERR_ARG, "NULL argument");
+    if (h->burnt) return fail(MMG_ERR_ARG, "mmg_diff_trace_open after the burn-in has started");
+    if (h->tr) return fail(MMG_ERR_STATE, "tracing is open already");
+    std::unique_ptr<DiffTracing> T(new DiffTracing());
+    T->P = df_trace_table(h, nullptr, T->q.slot);
+    T->every[0] = every_burnin; T->every[1] = every_sample;
+    T->sink = sink; T->user = user;
+    const int max_rows = opt(MMG_OPT_DIFF_TRACE_ROWS);
+    T->cap = df_trace_cap((uint32_t)T->P, h->F, every_burnin < every_sample ? every_burnin : every_sample, DF_CHUNK, DF_TRACE_BUF_BYTES,
+                          max_rows > 0 ? (uint32_t)max_rows : 0);
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(T->copy.create(hipStreamNonBlocking));
+    const uint64_t count = (uint64_t)T->cap * T->P * h->F;
+    for (int b = 0; b < 2; ++b) {
+        HIP_TRY(T->ran[b].create(hipEventDisableTiming));
+        HIP_TRY(T->copied[b].create(hipEventDisableTiming));
+        HIP_TRY(T->d_rows[b].alloc(count));
+        HIP_TRY(T->h_rows[b].alloc(count));
+    }
+    HIP_TRY(T->d_q.alloc(2));
+    HIP_TRY(T->h_q.alloc(2));
+    h->device_bytes += 2 * count * 8 + 2 * sizeof(DiffTrace);
+    h->tr = std::move(T);
+    return MMG_OK;
+}
+
+// iters iterations of one phase (0 burn-in, 1 sampling) with rows recorded: the launches of the untraced loop, shortened where a
+// buffer would not hold their rows.  it_first: the stream index; t_first: the index k_df_run takes as t0; tt_first: the phase index.
+static int df_run_traced(mmg_diff *h, int phase, uint32_t it_first, uint32_t t_first, uint32_t tt_first, uint32_t iters)
+{
+    DiffTracing &T = *h->tr;
+    // (phase indices below 2^30 and intervals up to 2^30: the kernel's tt + every - 1 stays inside int)
+    if ((uint64_t)tt_first + iters > (1u << 30)) return fail(MMG_ERR_ARG, "a traced phase takes at most 1073741824 iterations");
+    const uint32_t every = T.every[phase];
+    const int P = phase ? T.P : T.P - 1;
+    const size_t rowlen = (size_t)P * h->F;
+    uint32_t first[2] = {0, 0}, rows[2] = {0, 0};
+    // launch b's rows, once its copy has ended, to the sink
+    auto hand = [&](int b) {
+        HIP_TRY(hipEventSynchronize(T.copied[b].get()));
+        if (!rows[b]) return (int)MMG_OK;
+        const int rc = T.sink(T.user, phase, first[b], rows[b], T.h_rows[b].get());
+        if (rc) {
+            T.stopped = true;
+            (void)hipStreamSynchronize(h->st.get());
+            (void)hipStreamSynchronize(T.copy.get());
+            return fail(MMG_ERR_IO, "the trace sink returned " + std::to_string(rc));
+        }
+        return (int)MMG_OK;
+    };
+    uint32_t i = 0;
+    for (uint32_t j = 0; j < iters; ++i) {
+        const int b = (int)(i & 1);
+        const uint32_t tt = tt_first + j;
+        const uint32_t n = df_trace_plan(tt, iters - j, every, T.cap, DF_CHUNK, &first[b], &rows[b]);
+        // (buffer b and its descriptor are free: the host waited for launch i - 2's copy before it handed those rows on)
+        DiffTrace &q = T.h_q.get()[b];
+        q = T.q;
+        q.tr = T.d_rows[b].get(); q.P = P; q.every = (int)every; q.tt0 = (int)tt; q.cap = (int)T.cap;
+        HIP_TRY(hipMemcpyAsync(T.d_q.get() + b, &q, sizeof(DiffTrace), hipMemcpyHostToDevice, h->st.get()));
+        hipLaunchKernelGGL(k_df_run_traced, dim3(df_blocks(h->F)), dim3(DF_BLOCK), 0, h->st.get(), h->p, it_first + j, (int)(t_first + j), (int)n,
+                           phase ? 2 : 0, phase ? 0 : DF_REC_FROM, (const DiffTrace *)(T.d_q.get() + b));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(T.ran[b].get(), h->st.get()));
+        HIP_TRY(hipStreamWaitEvent(T.copy.get(), T.ran[b].get(), 0));
+        if (rows[b]) HIP_TRY(hipMemcpyAsync(T.h_rows[b].get(), T.d_rows[b].get(), rows[b] * rowlen * 8, hipMemcpyDeviceToHost, T.copy.get()));
+        HIP_TRY(hipEventRecord(T.copied[b].get(), T.copy.get()));
+        if (i >= 1) {
+            const int rc = hand(b ^ 1);
+            if (rc) return rc;
+        }
+        j += n;
+    }
+    return i ? hand((int)((i - 1) & 1)) : (int)MMG_OK;
+}
+
+extern "C" int mmg_selftest_diff_trace_plan(uint32_t n_params, uint32_t n_features, uint32_t every_min, uint32_t max_rows, uint32_t tt, uint32_t left,
+                                            uint32_t every, uint32_t *cap, uint32_t *first_row, uint32_t *rows, uint32_t *n)
+{
+    if (!cap || !first_row || !rows || !n) return fail(MMG_ERR_ARG, "NULL argument");
+    if (!n_params || !n_features || !every_min || !every || !left || every_min > DF_TRACE_EVERY_MAX || every > DF_TRACE_EVERY_MAX)
+        return fail(MMG_ERR_ARG, "counts and intervals must be positive, the intervals at most 1073741824");
+    *cap = df_trace_cap(n_params, n_features, every_min, DF_CHUNK, DF_TRACE_BUF_BYTES, max_rows);
+    *n = df_trace_plan(tt, left, every, *cap, DF_CHUNK, first_row, rows);
+    return MMG_OK;
+}
+
+extern "C" int mmg_diff_get_tune_state(mmg_diff *h, double *mean_lo, double *logitp)
+{
+    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
+    if (!h->burnt) return fail(MMG_ERR_STATE, "mmg_diff_get_tune_state before mmg_diff_burnin");
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t F = h->F;
+    if (mean_lo) {
+        HIP_TRY(hipMemcpy(mean_lo, h->d_st.get() + (size_t)h->p.LOsum * F, F * 8, hipMemcpyDeviceToHost));
+        for (size_t f = 0; f < F; ++f) mean_lo[f] = mean_lo[f] / (double)DF_BATCH;
+    }
+    if (logitp) HIP_TRY(hipMemcpy(logitp, h->d_st.get() + (size_t)h->p.logitp * F, F * 8, hipMemcpyDeviceToHost));
+    return MMG_OK;
+}
+
+extern "C" int mmg_diff_get_pseudo(mmg_diff *h, double *out)
+{
+    if (!h || !out) return fail(MMG_ERR_ARG, "NULL argument");
+    if (!h->burnt) return fail(MMG_ERR_STATE, "mmg_diff_get_pseudo before mmg_diff_burnin");
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t F = h->F;
+    size_t col = 0;
+    auto slot = [&](int o) { return hipMemcpy(out + col++ * F, h->d_st.get() + (size_t)o * F, F * 8, hipMemcpyDeviceToHost); };
+    for (int mi = 0; mi < 2; ++mi) {
+        const DiffModel &m = h->p.m[mi];
+        HIP_TRY(slot(m.A)); HIP_TRY(slot(m.Va));
+        for (int k = 0; k < h->p.K; ++k) { HIP_TRY(slot(m.B + k)); HIP_TRY(slot(m.Vb + k)); }
+        for (int l = 0; l < m.L; ++l) {
+            HIP_TRY(slot(m.Fm + l)); HIP_TRY(slot(m.Ve + l)); HIP_TRY(slot(m.Si + l));
+            double *S = out + (col - 1) * F;   // the file's S is 1 / S_inv
+            for (size_t f = 0; f < F; ++f) S[f] = 1.0 / S[f];
+        }
+        for (int c = 0; c < m.nc; ++c) { HIP_TRY(slot(m.J + c)); HIP_TRY(slot(m.Lm + c)); }
+        HIP_TRY(slot(m.Q)); HIP_TRY(slot(m.R));
+    }
+    return MMG_OK;
+}
+
 extern "C" int mmg_diff_burnin(mmg_diff *h, uint32_t iters)
 {
     if (!h) return fail(MMG_ERR_ARG, "NULL argument");
     if (h->burnt) return fail(MMG_ERR_STATE, "the burn-in has run already");
-    if (iters == 0 || iters % 1024) return fail(MMG_ERR_ARG, "burn-in iterations must be a positive multiple of 1024");
+    if (h->tr && h->tr->stopped) return fail(MMG_ERR_STATE, "the trace sink stopped this run");
+    // (the pseudopriors are the variances of iters - 102 recorded iterations: two of them at least)
+    if (iters < (uint32_t)DF_REC_FROM + 2) return fail(MMG_ERR_ARG, "burn-in iterations must be at least 104");
     HIP_TRY(hipSetDevice(h->device));
-    for (uint32_t t = 0; t < iters; t += DF_CHUNK) {
-        const uint32_t n = iters - t < DF_CHUNK ? iters - t : DF_CHUNK;
-        hipLaunchKernelGGL(k_df_run, dim3(df_blocks(h->F)), dim3(DF_BLOCK), 0, h->st.get(), h->p, t, (int)t, (int)n, 0, DF_REC_FROM);
+    if (h->tr) {
+        const int rc = df_run_traced(h, 0, 0, 0, 0, iters);
+        if (rc) return rc;
+    } else {
+        for (uint32_t t = 0; t < iters; t += DF_CHUNK) {
+            const uint32_t n = iters - t < DF_CHUNK ? iters - t : DF_CHUNK;
+            hipLaunchKernelGGL(k_df_run, dim3(df_blocks(h->F)), dim3(DF_BLOCK), 0, h->st.get(), h->p, t, (int)t, (int)n, 0, DF_REC_FROM);
+        }
     }
     hipLaunchKernelGGL(k_df_pseudo, dim3(df_blocks(h->F)), dim3(DF_BLOCK), 0, h->st.get(), h->p, (double)(iters - DF_REC_FROM));
     HIP_TRY(hipGetLastError());
@@ -218,6 +436,7 @@ extern "C" int mmg_diff_tune_batch(mmg_diff *h, uint32_t *untuned)
     if (!h || !untuned) return fail(MMG_ERR_ARG, "NULL argument");
     if (!h->burnt) return fail(MMG_ERR_STATE, "mmg_diff_tune_batch before mmg_diff_burnin");
     if (h->sampled) return fail(MMG_ERR_STATE, "mmg_diff_tune_batch after sampling has started");
+    if (h->tr && h->tr->stopped) return fail(MMG_ERR_STATE, "the trace sink stopped this run");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipMemsetAsync(h->d_cnt.get(), 0, 4, h->st.get()));
     const uint32_t it0 = h->burnin + h->batches * DF_BATCH;
@@ -236,11 +455,17 @@ extern "C" int mmg_diff_sample(mmg_diff *h, uint32_t iters)
     if (!h) return fail(MMG_ERR_ARG, "NULL argument");
     if (!h->burnt) return fail(MMG_ERR_STATE, "mmg_diff_sample before mmg_diff_burnin");
     if (iters == 0) return fail(MMG_ERR_ARG, "iters must be positive");
+    if (h->tr && h->tr->stopped) return fail(MMG_ERR_STATE, "the trace sink stopped this run");
     HIP_TRY(hipSetDevice(h->device));
     const uint32_t t_first = h->batches * DF_BATCH + h->sampled;
-    for (uint32_t j = 0; j < iters; j += DF_CHUNK) {
-        const uint32_t n = iters - j < DF_CHUNK ? iters - j : DF_CHUNK;
-        hipLaunchKernelGGL(k_df_run, dim3(df_blocks(h->F)), dim3(DF_BLOCK), 0, h->st.get(), h->p, h->burnin + t_first + j, (int)(t_first + j), (int)n, 2, 0);
+    if (h->tr) {
+        const int rc = df_run_traced(h, 1, h->burnin + t_first, t_first, h->sampled, iters);
+        if (rc) return rc;
+    } else {
+        for (uint32_t j = 0; j < iters; j += DF_CHUNK) {
+            const uint32_t n = iters - j < DF_CHUNK ? iters - j : DF_CHUNK;
+            hipLaunchKernelGGL(k_df_run, dim3(df_blocks(h->F)), dim3(DF_BLOCK), 0, h->st.get(), h->p, h->burnin + t_first + j, (int)(t_first + j), (int)n, 2, 0);
+        }
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(h->st.get()));

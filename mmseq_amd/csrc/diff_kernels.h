@@ -455,6 +455,73 @@ __global__ void __launch_bounds__(DF_BLOCK) k_df_run(DiffParams p, uint32_t it0,
     }
 }
 
+// ---- traces (mmg_diff_trace_open): thinned rows of the parameters recorded by the run kernel itself ---------------------------------
+// The parameters of BMS::initialise_streams in its order (alpha, beta, eta, lambda, sigma^2, rho of model 0 then 1 within each kind;
+// gamma last, in sampling only): slot[s] is the state slot of traced parameter s, -1 for gamma.  A row is the state after an iteration
+// whose phase index tt (the burn-in's t, or the sampling iteration counted from the first one) is a multiple of `every`; the rows of
+// a launch start at row0 = ceil(tt0 / every) and go to tr[((row - row0) * P + s) * F + f]: a wave stores adjacent words, like every
+// other state access.  cap is the number of rows the buffer holds; the launcher sizes its launches to it, and the kernel never
+// stores beyond it.
+constexpr int DF_TRACE_PMAX = 2 + 2 * DF_KMAX + 4 * DF_LMAX + 2 * DF_CMAX + 2 + 1;
+
+struct DiffTrace {
+    double *tr;       // [cap][P][F]
+    int P, every, tt0, cap;
+    int slot[DF_TRACE_PMAX];
+};
+
+// rows with index in [ceil(a / every), ceil(b / every)): those of the iterations a .. b - 1 (t < 2^31 and every <= DF_TRACE_EVERY_MAX, so
+// the sum stays inside int)
+constexpr uint32_t DF_TRACE_EVERY_MAX = 1u << 30;
+MMG_HD int df_trace_row_ceil(int t, int every) { return (t + every - 1) / every; }
+
+// rows a trace buffer holds: those of a full launch of `chunk` iterations at the denser thinning, cut to what `limit` bytes hold (one
+// row at least) and to `max_rows` if that is not 0
+MMG_HD uint32_t df_trace_cap(uint32_t P, uint32_t F, uint32_t every_min, uint32_t chunk, uint64_t limit, uint32_t max_rows)
+{
+    uint64_t cap = ((uint64_t)chunk + every_min - 1) / every_min;
+    const uint64_t fit = limit / ((uint64_t)P * F * 8);
+    if (cap > fit) cap = fit ? fit : 1;
+    if (max_rows && cap > max_rows) cap = max_rows;
+    return (uint32_t)cap;
+}
+
+// the launch that starts at phase index tt with `left` iterations to go: it ends after `chunk` iterations, or before the iteration of
+// the row after the buffer's last.  Returns its length (>= 1 for left >= 1); *first_row = ceil(tt / every), *rows <= cap.
+MMG_HD uint32_t df_trace_plan(uint32_t tt, uint32_t left, uint32_t every, uint32_t cap, uint32_t chunk, uint32_t *first_row, uint32_t *rows)
+{
+    const uint64_t r0 = ((uint64_t)tt + every - 1) / every;
+    const uint64_t room = (r0 + cap) * every - tt;
+    uint64_t n = left < chunk ? left : chunk;
+    if (n > room) n = room;
+    *first_row = (uint32_t)r0;
+    *rows = (uint32_t)(((uint64_t)tt + n + every - 1) / every - r0);
+    return (uint32_t)n;
+}
+
+// k_df_run recording rows: the same df_iteration calls in the same order, and reads of the state after them -- it draws nothing.
+// The descriptor is read from device memory where a row is stored, not held in registers across the iterations: as kernel arguments
+// its fields cost two more VGPRs (169) and with them the third wave per SIMD.
+__global__ void __launch_bounds__(DF_BLOCK) k_df_run_traced(DiffParams p, uint32_t it0, int t0, int n, int mode, int rec_from, const DiffTrace *q)
+{
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= p.F) return;
+    for (int j = 0; j < n; ++j) {
+        const int t = t0 + j;
+        df_iteration(p, f, it0 + (uint32_t)j, mode == 0, mode == 2 || t >= rec_from);
+        const int tt = q->tt0 + j, every = q->every;
+        if (tt % every) continue;
+        const int row = tt / every - df_trace_row_ceil(q->tt0, every);
+        if (row >= q->cap) continue;
+        const int P = q->P;
+        double *dst = q->tr + (size_t)row * (size_t)P * (size_t)p.F + (size_t)f;
+        for (int s = 0; s < P; ++s) {
+            const int o = q->slot[s];
+            dst[(size_t)s * (size_t)p.F] = o >= 0 ? DF_S(o) : (double)p.gam[f];
+        }
+    }
+}
+
 // tuning batch b (src/mmdiff.cpp:781-790, BMS::tunep): iterations 128 b .. 128 b + 127.  A feature tuned before the batch is frozen;
 // from the second batch on, its first iteration tunes logit p' from the mean log odds of the previous batch.  untuned counts the
 // features still untuned after that step (an integer atomic: the count is order-free).

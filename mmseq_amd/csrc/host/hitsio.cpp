@@ -2,6 +2,7 @@
 // behaviour notes cite the reference lines they reproduce.
 #include "hitsio.hpp"
 #include "pinflate.hpp"
+#include "cpu_quota.hpp"
 
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -130,12 +131,7 @@ private:
     static int default_inflate_threads()
     {
         long cpus = (long)std::thread::hardware_concurrency();
-        if (FILE *q = std::fopen("/sys/fs/cgroup/cpu.max", "r")) { // cgroup v2 quota: "max" or "<quota> <period>"
-            char a[32];
-            long per = 0;
-            if (std::fscanf(q, "%31s %ld", a, &per) == 2 && std::strcmp(a, "max") != 0 && per > 0) cpus = std::min(cpus, (std::atol(a) + per - 1) / per);
-            std::fclose(q);
-        }
+        if (const int q = cpu_quota()) cpus = std::min(cpus, (long)q);
         return (int)std::max(1L, std::min(8L, cpus / 2));
     }
     void open_parallel(const std::string &fileName)

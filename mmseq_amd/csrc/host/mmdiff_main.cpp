@@ -1,8 +1,8 @@
 // mmdiff_main.cpp -- drop-in for the reference's mmdiff (src/mmdiff.cpp): Bayesian model selection between two linear models of
 // every feature's expression across samples.  Tables, normalisation, permutation and the design matrices on the host; the
 // per-feature MCMC (src/bms.cpp) on the device through the C ABI (include/mmgibbs.h: mmg_diff_*).  Deliberate differences from the
-// reference are listed in DESIGN.md section 10: keyed streams instead of one MT19937 per thread, a keyed shuffle for -permute, no
-// -tracedir, size caps, dlgamma for gsl_sf_lngamma.
+// reference are listed in DESIGN.md section 10: keyed streams instead of one MT19937 per thread, a keyed shuffle for -permute,
+// -traces for -tracedir (without sigar<model>.txt), size caps, dlgamma for gsl_sf_lngamma.
 //
 // Polytomous model selection (the reference's recipe: one mmdiff run per alternative, then polyclass() of src/R/mmseq.R) is built in:
 // repeated -m runs J alternatives against one model 0 on one device handle (mmg_diff_poly_*), and -polyclass combines mmdiff tables on
@@ -10,20 +10,34 @@
 //
 // -chains C runs C independent chains of one comparison on one device handle (mmg_diff_chains_*) and prints their pooled table:
 // run_chains and DESIGN.md section 10.2.
+//
+// -traces DIR writes the reference's MCMC trace files (its -tracedir): TraceWriter below.
 #include <algorithm>
+#include <atomic>
 #include <cfloat>
+#include <charconv>
 #include <cmath>
+#include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <deque>
 #include <fstream>
 #include <iostream>
 #include <limits>
+#include <memory>
+#include <mutex>
 #include <sstream>
 #include <string>
+#include <thread>
 #include <vector>
+
+#include <sys/stat.h>
+#include <unistd.h>
 
 #include "../../../include/mmgibbs.h"
 #include "../mmg_math.h"
+#include "cpu_quota.hpp"
 
 using namespace std;
 
@@ -85,7 +99,10 @@ void printUsage(ostream &out)
         << "  -polyclass        no MCMC: combine the mmdiff tables of J >= 2 alternatives against the same model 0 into" << endl
         << "                    posterior probabilities of models 0..J" << endl;
     out << "Optional arguments:" << endl
-        << "  -tracedir STRING  not implemented in this version: MCMC traces are not written (exits with an error)" << endl
+        << "  -tracedir STRING  not implemented in this version: MCMC traces are not written (exits with an error); use -traces" << endl
+        << "  -traces STRING    directory in which to save MCMC traces, as the reference's -tracedir writes them: <param>-burnin and" << endl
+        << "                    <param> (1024 lines each, one value per feature), logitp, meanLO, pseudo; sigar<model>.txt is not" << endl
+        << "                    written; not with -chains or repeated -m (default: \"\" (do not write traces))" << endl
         << "  -useprops         run on isoform/gene proportions instead of expression" << endl
         << "  -permute          run on permuted dataset (a keyed shuffle per feature); combine with non-permuted results to obtain q-values" << endl
         << "  -p FLOAT          prior probability of the second model (default: 0.1)" << endl
@@ -817,6 +834,197 @@ int run_chains(int C, bool chainout_given, const string &chainout, const Design 
     return 0;
 }
 
+// ---- -traces DIR: the files of the reference's -tracedir (BMS::initialise_streams, print, printtune, print_pseudo) ------------------
+// The library hands the recorded rows of a launch to sink() on the main thread, which copies them and returns; writer threads format
+// them while the chain goes on.  File s belongs to thread s % T and every thread takes the chunks in order, so a file's lines are in
+// order without a lock per file.  At most PENDING chunks wait: beyond that sink() waits for the writers, and the chain with it.
+
+// fmt() into a buffer (at least 32 bytes): std::to_chars in the general format with 6 digits is printf's %g
+char *fmt_to(char *out, double x)
+{
+    if (std::isnan(x)) {
+        const char *t = std::signbit(x) ? "-nan" : "nan";
+        const size_t n = strlen(t);
+        memcpy(out, t, n);
+        return out + n;
+    }
+    return std::to_chars(out, out + 32, x, std::chars_format::general, 6).ptr;
+}
+
+class TraceWriter {
+public:
+    static constexpr size_t PENDING = 4;
+    atomic<uint64_t> bytes{0};   // written to the trace directory
+
+    TraceWriter(const string &dir, const vector<string> &names, size_t F) : dir_(dir), F_(F), P_(names.size())
+    {
+        // burn-in files of every parameter but gamma, then the sampling files; gamma-burnin and logitp-burnin stay empty
+        for (int phase = 0; phase < 2; ++phase)
+            for (size_t s = 0; s + (phase ? 0 : 1) < P_; ++s) files_.push_back(open(names[s] + (phase ? "" : "-burnin")));
+        fclose(open("gamma-burnin"));
+        fclose(open("logitp-burnin"));
+        meanLO_[0] = open("meanLO-burnin");
+        meanLO_[1] = open("meanLO");
+        logitp_ = open("logitp");
+        // as many writers as the container's CPU quota (or, without one, the hardware) allows, 16 at most
+        const int quota = cpu_quota();
+        const size_t cpus = quota ? (size_t)quota : max<size_t>(1, thread::hardware_concurrency());
+        const size_t T = max<size_t>(1, min<size_t>(min<size_t>(P_, 16), cpus));
+        for (size_t t = 0; t < T; ++t) threads_.emplace_back([this, t, T] { work(t, T); });
+    }
+    ~TraceWriter() { finish(); }
+
+    static int sink(void *user, int phase, uint32_t first_row, uint32_t n_rows, const double *rows)
+    {
+        return ((TraceWriter *)user)->push(phase, n_rows, rows);
+    }
+
+    // BMS::printtune: one line of each of meanLO and logitp
+    void tune_line(const vector<double> &mean_lo, const vector<double> &logitp)
+    {
+        line(meanLO_[1], mean_lo);
+        line(logitp_, logitp);
+    }
+
+    // BMS::print_pseudo; cols[c * F + f]
+    void pseudo(size_t K, const size_t L[2], const uint32_t nc[2], const vector<double> &cols)
+    {
+        FILE *fp = open("pseudo");
+        string out;
+        for (int m = 0; m < 2; ++m) {
+            const string M = to_string(m);
+            out += "A" + M + "\tValpha" + M + "\t";
+            for (size_t l = 0; l < K; ++l) out += "B" + M + "_" + to_string(l) + "\tVbeta" + M + "_" + to_string(l) + "\t";
+            for (size_t l = 0; l < L[m]; ++l) out += "F" + M + "_" + to_string(l) + "\tVeta" + M + "_" + to_string(l) + "\tS" + M + "_" + to_string(l) + "\t";
+            for (uint32_t c = 0; c < nc[m]; ++c) out += "J" + M + "_" + to_string(c) + "\tL" + M + "_" + to_string(c) + "\t";
+            out += "Q" + M + "\tR" + M + "\t";
+        }
+        out += "\n";
+        const size_t Q = cols.size() / F_;
+        for (size_t f = 0; f < F_; ++f) {
+            for (size_t c = 0; c < Q; ++c) out += fmt(cols[c * F_ + f]) + "\t";
+            out += "\n";
+        }
+        put(fp, out.data(), out.size());
+        if (fclose(fp) != 0) failed_ = true;
+    }
+
+    // waits for the writers and closes every file; false if anything could not be written
+    bool finish()
+    {
+        {
+            lock_guard<mutex> g(mu_);
+            done_ = true;
+        }
+        cv_.notify_all();
+        for (thread &t : threads_) t.join();
+        threads_.clear();
+        for (FILE **f : {&meanLO_[0], &meanLO_[1], &logitp_})
+            if (*f) { if (fclose(*f) != 0) failed_ = true; *f = nullptr; }
+        for (FILE *&f : files_)
+            if (f) { if (fclose(f) != 0) failed_ = true; f = nullptr; }
+        return !failed_;
+    }
+
+private:
+    struct Chunk {
+        int phase;
+        uint32_t rows;
+        vector<double> v;   // [rows][P of the phase][F]
+        size_t left;        // threads that have not written it yet
+    };
+
+    FILE *open(const string &name)
+    {
+        const string path = dir_ + "/" + name;
+        FILE *f = fopen(path.c_str(), "w");
+        if (!f) die("Error: couldn't create " + path);
+        return f;
+    }
+    void put(FILE *f, const char *data, size_t n)
+    {
+        if (fwrite(data, 1, n, f) != n) fail();
+        bytes += n;
+    }
+    void line(FILE *f, const vector<double> &v)
+    {
+        string out(v.size() * 32 + 1, '\0');
+        char *q = &out[0];
+        for (double x : v) { q = fmt_to(q, x); *q++ = ' '; }
+        *q++ = '\n';
+        put(f, out.data(), (size_t)(q - out.data()));
+    }
+    int push(int phase, uint32_t rows, const double *data)
+    {
+        // the reference's print() ends a line in meanLO for every recorded iteration, though printtune alone writes values there
+        const string nl(rows, '\n');
+        put(meanLO_[phase], nl.data(), nl.size());
+        auto c = make_shared<Chunk>();
+        c->phase = phase; c->rows = rows; c->left = threads_.size();
+        c->v.assign(data, data + (size_t)rows * (P_ - (phase ? 0 : 1)) * F_);
+        unique_lock<mutex> g(mu_);
+        cv_.wait(g, [&] { return pushed_ - retired_ < PENDING || failed_; });
+        if (failed_) return 1;
+        chunks_.push_back(c);
+        ++pushed_;
+        g.unlock();
+        cv_.notify_all();
+        return 0;
+    }
+    void work(size_t t, size_t T)
+    {
+        string out;
+        for (size_t next = 0;; ++next) {
+            shared_ptr<Chunk> c;
+            {
+                unique_lock<mutex> g(mu_);
+                cv_.wait(g, [&] { return next < pushed_ || done_; });
+                if (next >= pushed_) return;
+                c = chunks_[next - retired_];
+            }
+            const size_t P = P_ - (c->phase ? 0 : 1), base = c->phase ? P_ - 1 : 0;
+            for (size_t s = t; s < P; s += T) {
+                out.resize((size_t)c->rows * (F_ * 32 + 1));
+                char *q = &out[0];
+                const bool gamma = c->phase && s + 1 == P_;   // printed as the int it is
+                for (uint32_t r = 0; r < c->rows; ++r) {
+                    const double *v = &c->v[((size_t)r * P + s) * F_];
+                    for (size_t f = 0; f < F_; ++f) {
+                        if (gamma) *q++ = v[f] != 0.0 ? '1' : '0';
+                        else q = fmt_to(q, v[f]);
+                        *q++ = ' ';
+                    }
+                    *q++ = '\n';
+                }
+                put(files_[base + s], out.data(), (size_t)(q - out.data()));
+            }
+            {
+                lock_guard<mutex> g(mu_);
+                // chunks retire in order: every thread takes them in order, so the oldest is the first to be written by all
+                if (--c->left == 0) { chunks_.pop_front(); ++retired_; }
+            }
+            cv_.notify_all();
+        }
+    }
+
+    string dir_;
+    size_t F_, P_;
+    vector<FILE *> files_;   // [P - 1] burn-in, then [P] sampling
+    FILE *meanLO_[2] = {nullptr, nullptr}, *logitp_ = nullptr;
+    vector<thread> threads_;
+    mutex mu_;
+    condition_variable cv_;
+    deque<shared_ptr<Chunk>> chunks_;   // chunks retired_ .. pushed_ - 1
+    size_t pushed_ = 0, retired_ = 0;
+    bool done_ = false;
+    atomic<bool> failed_{false};   // set by any thread; push() waits on it too
+    void fail()
+    {
+        { lock_guard<mutex> g(mu_); failed_ = true; }   // (under the lock: push() must not miss the wake-up)
+        cv_.notify_all();
+    }
+};
+
 } // namespace
 
 int main(int argc, char **argv)
@@ -824,7 +1032,7 @@ int main(int argc, char **argv)
     string matrices_file = "";
     vector<string> matrices_files;   // every -m; more than one: the polytomous run
     bool polyclass_mode = false, prior_given = false, polyout_given = false, chains_given = false, chainout_given = false;
-    string prior_text, polyout, chainout;
+    string prior_text, polyout, chainout, traces;
     int chains = 1;
     double p = 0.1, d = 1.4, s = 2.0;
     int burnin = 8192, mcmciters = 16384, seed = 1234, range_start = -1, range_end = -1;
@@ -840,7 +1048,10 @@ int main(int argc, char **argv)
         const string a0 = arguments.empty() ? string() : arguments[0];
         auto take = [&]() { arguments.erase(arguments.begin()); need(arguments, 1); string v = arguments[0]; arguments.erase(arguments.begin()); return v; };
         if (a0 == "-tracedir") {
-            die("Error: -tracedir is not implemented in this version of mmdiff (MCMC traces are not written).");
+            die("Error: -tracedir is not implemented in this version of mmdiff (MCMC traces are not written); use -traces DIR.");
+        } else if (a0 == "-traces") {
+            traces = take();
+            if (traces.empty()) die("Error: -traces needs a directory.");
         } else if (a0 == "-m" || a0 == "-de") {
             arguments.erase(arguments.begin());
             // -m FILE -m FILE ...: consecutive pairs are one polytomous run
@@ -969,6 +1180,8 @@ int main(int argc, char **argv)
     if (chainout_given && !chains_given) usage_error("Error: -chainout needs -chains.");
     if (chains_given && (poly_run || polyclass_mode))
         usage_error("Error: -chains cannot be combined with more than one -m or with -polyclass (chains of several alternatives are left for later).");
+    if (!traces.empty() && (chains_given || poly_run || polyclass_mode))
+        usage_error("Error: -traces cannot be combined with -chains, more than one -m or -polyclass (traces of several chains or alternatives are left for later).");
     if (polyclass_mode) {
         // host only: no device is looked for
         const size_t J = arguments.size();
@@ -992,6 +1205,10 @@ int main(int argc, char **argv)
     }
     if (matrices_file == "" && simple_de.size() == 0) die("Error: either -de or -m must be specified");
     if (matrices_file == "" && simple_de.size() == 1) die("Error: -de requires at least two groupings");
+    if (!traces.empty()) {   // src/mmdiff.cpp:594-603
+        mkdir(traces.c_str(), 0755);
+        if (::access(traces.c_str(), F_OK | R_OK | W_OK | X_OK) == -1) die("Error: can't write to trace directory " + traces + ".");
+    }
 
     vector<string> filenames(arguments.begin(), arguments.end());
     const size_t S = filenames.size();
@@ -1045,15 +1262,45 @@ int main(int argc, char **argv)
     mmg_diff *h = nullptr;
     MMG_CHECK(mmg_diff_create(0, (uint32_t)F, (uint32_t)S, y.data(), e.data(), (uint32_t)D.K, D.M.data(), (uint32_t)D.L0, D.P0.data(),
                               (uint32_t)D.L1, D.P1.data(), D.C.data(), d, s, pdash, fixalpha ? 1 : 0, useed, &h));
+    unique_ptr<TraceWriter> tw;
+    if (!traces.empty()) {
+        uint32_t np = 0;
+        MMG_CHECK(mmg_diff_trace_layout(h, &np, NULL));
+        vector<string> names(np);
+        for (uint32_t i = 0; i < np; ++i) {
+            char name[32];
+            MMG_CHECK(mmg_diff_trace_name(h, i, name, sizeof name));
+            names[i] = name;
+        }
+        tw.reset(new TraceWriter(traces, names, F));
+        // a line per burnin / OUTLEN burn-in and per mcmciters / OUTLEN sampling iterations (src/mmdiff.cpp:733-734, 837)
+        MMG_CHECK(mmg_diff_trace_open(h, (uint32_t)(burnin / OUTLEN), (uint32_t)(mcmciters / OUTLEN), TraceWriter::sink, tw.get()));
+    }
     cerr << "BURNIN (" << burnin << " iterations)...";
     MMG_CHECK(mmg_diff_burnin(h, (uint32_t)burnin));
     cerr << "\nSetting pseudopriors...done.\n";
+    vector<double> mean_lo, tune_logitp;
+    if (tw) {
+        uint32_t nq = 0, nc[2] = {0, 0};
+        MMG_CHECK(mmg_diff_trace_layout(h, NULL, &nq));
+        MMG_CHECK(mmg_diff_info(h, NULL, nc, NULL));
+        vector<double> cols((size_t)nq * F);
+        MMG_CHECK(mmg_diff_get_pseudo(h, cols.data()));
+        const size_t L[2] = {D.L0, D.L1};
+        tw->pseudo(D.K, L, nc, cols);
+        mean_lo.resize(F);
+        tune_logitp.resize(F);
+    }
     int numbatches = 0;
     if (tune) {
         uint32_t untuned = 0;
         MMG_CHECK(mmg_diff_tune_batch(h, &untuned));
         numbatches = 1;
         while (untuned > 0 && numbatches != MAXBATCHES) {
+            if (tw) {   // BMS::printtune at the start of a batch, before its tuning step
+                MMG_CHECK(mmg_diff_get_tune_state(h, mean_lo.data(), tune_logitp.data()));
+                tw->tune_line(mean_lo, tune_logitp);
+            }
             MMG_CHECK(mmg_diff_tune_batch(h, &untuned));
             numbatches++;
             if (numbatches % 64 == 0) cerr << "TUNING BATCH " << numbatches << " (" << untuned << " left)\r";
@@ -1065,6 +1312,10 @@ int main(int argc, char **argv)
     DiffResults r(F, D);
     MMG_CHECK(mmg_diff_get_results(h, r.gm.data(), r.logitp.data(), r.alpha.data(), r.beta.data(), r.eta.data()));
     mmg_diff_destroy(h);
+    if (tw) {
+        if (!tw->finish()) die("Error: couldn't write the trace files in " + traces);
+        cerr << "Wrote " << tw->bytes << " bytes of traces to " << traces << "\n";
+    }
     string text;
     write_table(stdout, chain0.f ? &text : nullptr, features, filenames, D, fixalpha, Mnil, Pnil, p, y, e, r);
     if (chain0.f && (fputs(text.c_str(), chain0.f) < 0 || fflush(chain0.f) != 0)) die("Error: couldn't write " + chain0_name);

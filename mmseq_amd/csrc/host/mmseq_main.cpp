@@ -11,6 +11,7 @@
 // are written after the loop from the device-resident trace, VLAs are heap vectors (:1308-1348).
 // There is no CPU sampler here: without a HIP device the program stops with an error.
 #include <omp.h>
+#include "cpu_quota.hpp"
 #include <atomic>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -338,24 +339,6 @@ static void write_trace_rows(GzText &gz, int n_lines, size_t n_cols, const funct
         if (fetcher.joinable()) fetcher.join();
     }
     if (writer.joinable()) writer.join();
-}
-
-// CPUs this process may actually use: a container's CFS quota (cgroup v2 cpu.max, v1 cpu.cfs_quota_us) is invisible to OpenMP, which
-// then starts one thread per core of the host -- 256 threads throttled to 16 CPUs' worth of time on the GPU boxes here.
-static int cpu_quota()
-{
-    long long quota = -1, period = 100000;
-    if (FILE *f = fopen("/sys/fs/cgroup/cpu.max", "r")) {
-        char q[64];
-        if (fscanf(f, "%63s %lld", q, &period) == 2 && strcmp(q, "max") != 0) quota = atoll(q);
-        fclose(f);
-    } else if (FILE *g = fopen("/sys/fs/cgroup/cpu/cpu.cfs_quota_us", "r")) {
-        if (fscanf(g, "%lld", &quota) != 1) quota = -1;
-        fclose(g);
-        if (FILE *h = fopen("/sys/fs/cgroup/cpu/cpu.cfs_period_us", "r")) { if (fscanf(h, "%lld", &period) != 1) period = 100000; fclose(h); }
-    }
-    if (quota <= 0 || period <= 0) return 0;
-    return (int)max<long long>(1, (quota + period - 1) / period);
 }
 
 // the sample count of every trace (src/mmseq.cpp:187: gibbs_iter / gibbs_ss)

@@ -74,6 +74,36 @@ private:
     int dev_ = 0;
 };
 
+// Pinned host memory, freed with its owner (counted with the buffers).
+template <typename T>
+class PinnedBuf {
+public:
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+    ~PinnedBuf() { reset(); }
+    hipError_t alloc(size_t count)
+    {
+        reset();
+        if (fail_acquire()) return hipErrorOutOfMemory;
+        hipError_t e = hipHostMalloc((void **)&p_, count * sizeof(T), hipHostMallocDefault);
+        if (e != hipSuccess) p_ = nullptr;
+        else count_live(LIVE_BUFFERS, 1);
+        return e;
+    }
+    T *get() const { return p_; }
+    void reset()
+    {
+        if (!p_) return;
+        (void)hipHostFree((void *)p_);
+        p_ = nullptr;
+        count_live(LIVE_BUFFERS, -1);
+    }
+
+private:
+    T *p_ = nullptr;
+};
+
 // A stream or an event, destroyed with its owner.
 template <typename H, hipError_t (*Create)(H *, unsigned), hipError_t (*Destroy)(H), int Kind>
 class DevHandle {

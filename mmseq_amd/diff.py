@@ -13,6 +13,7 @@ from . import _lib
 from ._lib import check
 
 MAXBATCHES = 8192
+TRACE_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_double))
 
 
 def _ptr(a):
@@ -42,7 +43,7 @@ class Diff:
         self._h = h
 
     def burnin(self, iters):
-        check(self._lib.mmg_diff_burnin(self._h, int(iters)))
+        self._run(self._lib.mmg_diff_burnin(self._h, int(iters)))
 
     def tune_batch(self):
         """One tuning batch; the number of features still untuned."""
@@ -58,7 +59,7 @@ class Diff:
         return nb
 
     def sample(self, iters):
-        check(self._lib.mmg_diff_sample(self._h, int(iters)))
+        self._run(self._lib.mmg_diff_sample(self._h, int(iters)))
 
     def results(self):
         F, K, L = self.F, self.K, self.L
@@ -75,6 +76,71 @@ class Diff:
         b = C.c_uint64()
         check(self._lib.mmg_diff_device_bytes(self._h, C.byref(b)))
         return b.value
+
+    def trace_names(self):
+        """The traced parameters as the reference's trace files are named, in row order; `gamma`, the last, is in sampling rows only."""
+        n = C.c_uint32()
+        check(self._lib.mmg_diff_trace_layout(self._h, C.byref(n), None))
+        buf = C.create_string_buffer(32)
+        names = []
+        for i in range(n.value):
+            check(self._lib.mmg_diff_trace_name(self._h, i, buf, 32))
+            names.append(buf.value.decode())
+        return names
+
+    def open_traces(self, every_burnin, every_sample, sink=None):
+        """Before `burnin`: record every every_burnin-th burn-in and every every_sample-th sampling iteration.  sink(phase, first_row,
+        rows) gets the rows of one launch as an array (n, P, F) that is valid during the call (phase 0 burn-in, P without gamma; 1
+        sampling) and returns 0, or non-zero to stop the run.  Without a sink the rows are kept: `traces`."""
+        P, F = len(self.trace_names()), self.F
+        rows_kept = ([], [])
+
+        def keep(phase, first, rows):
+            rows_kept[phase].append(rows.copy())
+            return 0
+
+        fn = sink or keep
+
+        def cb(user, phase, first, n, ptr):
+            try:
+                rows = np.ctypeslib.as_array(ptr, shape=(n, P if phase else P - 1, F))
+                return int(fn(phase, first, rows) or 0)
+            except BaseException as ex:     # an exception cannot cross the C frames: stop the run, raise it from the entry that ran
+                self._sink_error = ex
+                return -1
+
+        cfn = TRACE_SINK(cb)
+        check(self._lib.mmg_diff_trace_open(self._h, int(every_burnin), int(every_sample), C.cast(cfn, C.c_void_p), None))
+        self._sink = cfn                # (kept alive with the handle)
+        self._rows = None if sink else rows_kept
+
+    def traces(self):
+        """The rows kept so far: (burn-in (rows, P - 1, F), sampling (rows, P, F)).  Only after `open_traces` without a sink."""
+        if getattr(self, "_rows", None) is None:
+            raise RuntimeError("no rows are kept: traces() needs open_traces() without a sink")
+        P, F = len(self.trace_names()), self.F
+        return tuple(np.concatenate(r) if r else np.empty((0, P - 1 + ph, F)) for ph, r in enumerate(self._rows))
+
+    def _run(self, rc):
+        """check(rc); an exception of the caller's sink, which stopped the run, is raised in place of the library's error."""
+        ex, self._sink_error = getattr(self, "_sink_error", None), None
+        if rc != 0 and ex is not None:
+            raise ex
+        check(rc)
+
+    def tune_state(self):
+        """(mean log odds of the last batch, logit p') per feature, as they stand: what BMS::printtune prints before a batch's tuning."""
+        lo, lp = np.empty(self.F), np.empty(self.F)
+        check(self._lib.mmg_diff_get_tune_state(self._h, _ptr(lo), _ptr(lp)))
+        return lo, lp
+
+    def pseudo(self):
+        """The pseudopriors after the burn-in, (columns of BMS::print_pseudo, F)."""
+        n = C.c_uint32()
+        check(self._lib.mmg_diff_trace_layout(self._h, None, C.byref(n)))
+        out = np.empty((n.value, self.F))
+        check(self._lib.mmg_diff_get_pseudo(self._h, _ptr(out)))
+        return out
 
     def close(self):
         if self._h:
