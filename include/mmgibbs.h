@@ -81,7 +81,8 @@ extern "C" {
  *      with such groups differ from version 7.
  *      Additive in version 8, no bump (the chain's specification does not change): mmcollapse (mmg_collapse_*), mmdiff (mmg_diff_*), the
  *      owners' self tests (MMG_OPT_FAIL_ALLOC, mmg_selftest_live, mmg_selftest_sampler_events), the convergence diagnostics across
- *      chains (mmg_convergence_*, MMG_OPT_CONV_SLAB) and mmdiff's chains (mmg_diff_chains_*). */
+ *      chains (mmg_convergence_*, MMG_OPT_CONV_SLAB), mmdiff's chains (mmg_diff_chains_*) and the posterior assignment probabilities
+ *      of the hits (mmg_assign_*, MMG_OPT_ASSIGN_WAVES). */
 /* Layout.  The model does not care about the order of rows or the numbering of transcripts (src/mmseq.cpp:399-418 uses
  * first-seen order for both); the kernels do: they keep a window of consecutive transcripts in LDS and want the 64 rows of a
  * wave to have equal lengths.  mmg_problem_create therefore stores the rows in a CANONICAL order of its own (sorted on the
@@ -445,7 +446,8 @@ enum {
                                       without reaching the runtime (error paths) */
     MMG_OPT_CONV_SLAB = 13,        /* v >= 1: at most v series per slab of mmg_convergence_create / _of_traces (slab edges on small inputs)     */
     MMG_OPT_DIFF_TRACE_ROWS = 14,  /* v >= 1: at most v rows per row buffer of mmg_diff_trace_open (shortened traced launches on small inputs)    */
-    MMG_OPT_COUNT_ = 15
+    MMG_OPT_ASSIGN_WAVES = 15,     /* v >= 1: at most v waves per launch of mmg_assign_run_* (several scratch chunks on small inputs)             */
+    MMG_OPT_COUNT_ = 16
 };
 int mmg_selftest_option(int option, int value);
 /* What the library holds: counts[3] = device buffers, streams, events (tests: every call gives back what it acquired). */
@@ -521,6 +523,30 @@ int mmg_collapse_summarize(int device, uint32_t trace_len, uint32_t n_cols, cons
                            const double *virtual_scale, double alpha, uint64_t seed, uint32_t stream, uint32_t n_series, const uint64_t *series_ptr,
                            const uint32_t *series_member, double *log_mean, double *var, double *tau, int32_t *sokal_rc);
 
+
+/* ---- posterior assignment probability of every hit ----------------------------------------------------------------------
+ * What the sample kernel draws and discards (src/mmseq.cpp:857-891), Rao-Blackwellised: for a hit (i, t) the mean over the samples s
+ * of a range of mu_s[t] / sum_{t' in row i} mu_s[t'] (1 / hits of the row where that sum is 0 or not finite, the oracle's degenerate
+ * case; exactly 1 for the hit of a row of one).  Every sum runs in a fixed order (tests/assign_ref.py) without floating-point atomics: reruns are
+ * bit-identical.  The handle has its own copy of the rows, in the CALLER's order and numbering -- hit j of the results is entry j of
+ * col_idx; no mmg_problem is needed.  Additive in ABI version 8. */
+typedef struct mmg_assign mmg_assign;
+/* row_ptr: n_rows + 1 offsets from 0, not decreasing (empty rows are allowed and produce nothing); col_idx: row_ptr[n_rows] columns
+ * below n_tx.  Checked before any device work. */
+int mmg_assign_create(int device, uint64_t n_rows, uint32_t n_tx, const uint64_t *row_ptr, const uint32_t *col_idx, mmg_assign **out);
+/* The samples [first_sample, first_sample + n_samples) of chain `chain` of a sampler with keep_trace on the same device whose problem
+ * has n_tx transcripts.  The call waits for the chain; the sampler's trace (sample-major, device numbering) is transposed on the
+ * device into the handle's copy and never touches the host.  MMG_ERR_STATE for samples the chain has not kept yet. */
+int mmg_assign_run_sampler(mmg_assign *h, mmg_sampler *s, int chain, int first_sample, int n_samples);
+/* The same over a host trace laid out as mmg_sampler_get_trace returns it: trace[t * trace_len + s]. */
+int mmg_assign_run_host(mmg_assign *h, const double *trace, int trace_len, int first_sample, int n_samples);
+/* P of the hits [first_hit, first_hit + n_hits) of the last run; MMG_ERR_STATE before the first one */
+int mmg_assign_get(mmg_assign *h, uint64_t first_hit, uint64_t n_hits, double *P);
+/* 8 (n_rows + 1) + 12 max(hits, 1) bytes from creation; after a run over n_samples of a trace of T samples also 8 n_tx T (the
+ * trace copy) + 8 W ceil64(n_samples) (the scratch slices), W = max(1, min(ceil(hits / 256), 64 MiB / (8 ceil64(n_samples)),
+ * MMG_OPT_ASSIGN_WAVES if set)), ceil64 rounding up to a multiple of 64.  Both are kept until a run of another shape. */
+int mmg_assign_device_bytes(mmg_assign *h, uint64_t *bytes);
+void mmg_assign_destroy(mmg_assign *h);
 
 /* ---- mmdiff: Bayesian model selection between two linear models per feature -------------------------------------------
  * src/bms.cpp driven as src/mmdiff.cpp:744-866: per feature an independent MCMC over both models with pseudopriors, the model

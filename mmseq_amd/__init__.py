@@ -2,5 +2,7 @@
 
 csrc/      HIP kernels (gfx950), the C ABI (include/mmgibbs.h) and the C++ host code
 gibbs.py   numpy-facing mirror of the C ABI (Problem, Sampler)
+assign.py  posterior assignment probability of every hit from a chain's trace (Assign)
 """
+from .assign import Assign  # noqa: F401
 from .gibbs import Problem, Sampler, device_count  # noqa: F401

@@ -39,7 +39,7 @@ class MMGError(RuntimeError):
 
 LAYOUT_CANONICAL, LAYOUT_KEEP_ROWS = 0, 1
 # mmg_selftest_option ids
-OPT_SAMPLE_KERNEL, OPT_FORCE_IDX64, OPT_SELL_WAVES_PER_CU, OPT_EM_KERNEL, OPT_EM_GRID, OPT_FUSE_CHAINS, OPT_CNT_REPLICAS, OPT_GROUP_FAIL, OPT_DERIVE_ORDER, OPT_WIRE_CHECK, OPT_BIGK_PER_WAVE, OPT_BIGK_SIDE_STREAM, OPT_FAIL_ALLOC, OPT_CONV_SLAB, OPT_DIFF_TRACE_ROWS = range(15)
+OPT_SAMPLE_KERNEL, OPT_FORCE_IDX64, OPT_SELL_WAVES_PER_CU, OPT_EM_KERNEL, OPT_EM_GRID, OPT_FUSE_CHAINS, OPT_CNT_REPLICAS, OPT_GROUP_FAIL, OPT_DERIVE_ORDER, OPT_WIRE_CHECK, OPT_BIGK_PER_WAVE, OPT_BIGK_SIDE_STREAM, OPT_FAIL_ALLOC, OPT_CONV_SLAB, OPT_DIFF_TRACE_ROWS, OPT_ASSIGN_WAVES = range(16)
 
 
 class ProblemDesc(C.Structure):
@@ -180,6 +180,12 @@ SYMBOLS = {
     "mmg_collapse_summarize": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_double,
                                          C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),
+    "mmg_assign_create": (C.c_int, [C.c_int, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "mmg_assign_run_sampler": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "mmg_assign_run_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "mmg_assign_get": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "mmg_assign_device_bytes": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mmg_assign_destroy": (None, [C.c_void_p]),
     "mmg_convergence_create": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "mmg_convergence_get": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmg_convergence_destroy": (None, [C.c_void_p]),

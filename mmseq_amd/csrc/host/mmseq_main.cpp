@@ -78,6 +78,8 @@ static void printUsage(ostream &out)
         << "  -em_one_device     with -gpus > 1 and one chain: run the EM on the first device alone instead of over the read shards" << endl
         << "  -convergence       also write output_base.convergence, .identical.convergence and .gene.convergence: rank-normalized" << endl
         << "                     split R-hat and bulk / tail effective sample sizes across the chains (one device only)" << endl
+        << "  -assign            also write output_base.assign (the lines of output_base.M with the posterior probability that the hit set's" << endl
+        << "                     reads come from that transcript), .counts and .gene.counts (expected hits per feature; one device only)" << endl
         << endl;
 }
 
@@ -99,7 +101,7 @@ static bool is_power_of_two(unsigned v) { return v != 0 && (v & (v - 1)) == 0; }
 
 // Command line: a table of options -- name, the variable it sets, how its value is read -- walked once.  Same flags, defaults,
 // messages and exit codes as the reference's loop at src/mmseq.cpp:206-276 (tests/test_cli.py holds them), plus -device / -gpus /
-// -chains / -em_one_device / -convergence of this build.
+// -chains / -em_one_device / -convergence / -assign of this build.
 struct CliOption {
     const char *name;
     enum Kind { REAL, INT, FLAG, LIST, HELP, VERSION } kind;
@@ -125,6 +127,7 @@ using Problem = Owned<mmg_problem, mmg_problem_destroy>;
 using Group = Owned<mmg_group, mmg_group_destroy>;
 using Summary = Owned<mmg_summary, mmg_summary_destroy>;
 using Convergence = Owned<mmg_convergence, mmg_convergence_destroy>;
+using Assign = Owned<mmg_assign, mmg_assign_destroy>;
 // handles of one kind, one per device, destroyed together in order; reads as the array of raw handles the calls take
 template <class T, void (*Destroy)(T *)> struct HandleSet {
     vector<T *> h;
@@ -355,7 +358,7 @@ struct Options {
     int seed = 1234;
     bool debug = false;
     int device = 0, gpus = 1, chains = 1;
-    bool em_one_device = false, convergence = false;
+    bool em_one_device = false, convergence = false, assign = false;
     string hits_file, output_base;
 };
 
@@ -372,7 +375,7 @@ static Options parse_options(int argc, char **argv)
         {"-gpus", CliOption::INT, &o.gpus},           {"-chains", CliOption::INT, &o.chains},
         {"-percentiles", CliOption::LIST, &percentile_fields},
         {"-debug", CliOption::FLAG, &o.debug},        {"-em_one_device", CliOption::FLAG, &o.em_one_device},
-        {"-convergence", CliOption::FLAG, &o.convergence},
+        {"-convergence", CliOption::FLAG, &o.convergence}, {"-assign", CliOption::FLAG, &o.assign},
         {"-h", CliOption::HELP, nullptr},           {"-help", CliOption::HELP, nullptr},       {"--help", CliOption::HELP, nullptr},
         {"-v", CliOption::VERSION, nullptr},        {"-version", CliOption::VERSION, nullptr}, {"--version", CliOption::VERSION, nullptr},
     };
@@ -416,6 +419,8 @@ static Options parse_options(int argc, char **argv)
           "Error: -gpus and -chains must be positive, and chains a multiple of gpus when both exceed 1.\n");
     // the diagnostic reads every chain's trace on one device
     check(!(o.convergence && o.gpus > 1), "Error: -convergence needs every chain on one device: it cannot be combined with -gpus > 1.\n");
+    // the pass reads the chain's trace where one sampler holds it
+    check(!(o.assign && o.gpus > 1), "Error: -assign reads the chain's trace on one device: it cannot be combined with -gpus > 1.\n");
     check(is_power_of_two((unsigned)trace_length), "Error: gibbs_iter/gibbs_ss must be a power of 2.\n");
     return o;
 }
@@ -1498,6 +1503,71 @@ static void write_convergence_tables(const Options &opt, const Header &hdr, cons
     for (auto &gt : hdr.gene2transcripts) { ofs << gt.first; conv_row(ofs, c.G, g++); }
 }
 
+// ---- -assign: the posterior assignment probability of every hit, and the expected hits per transcript and gene that follow from it.
+//      The device pass (mmg_assign_*) runs over chain 0's trace_length kept samples -- the samples the .mmseq summaries are taken over
+//      (mmg_summary_begin with chain 0 in start_chains; post.hip reads all cfg.trace_len samples of that chain) -- on the rows as the
+//      .M file lists them: first-seen order, observed-transcript numbering.  The sums over hits are the host's, in ascending hit index.
+static void write_assignments(const Options &opt, const Header &hdr, const Hits &hits, const Observed &obs, const Chains &ch)
+{
+    const uint64_t m = hits.m(), H = hits.col_idx.size();
+    const uint32_t n = hits.n();
+    vector<double> P(max<uint64_t>(H, 1));
+    {
+        mmg_assign *raw = nullptr;
+        MMG_TRY(mmg_assign_create(opt.device, m, n, hits.row_ptr.data(), hits.col_idx.data(), &raw));
+        Assign as(raw);
+        MMG_TRY(mmg_assign_run_sampler(raw, ch.smp(), 0, 0, trace_length));
+        MMG_TRY(mmg_assign_get(raw, 0, H, P.data()));
+    }
+    // .assign: the lines of .M (start_km_writer) with a third column; chunks of rows formatted in parallel, written in order
+    {
+        ofstream ofs((opt.output_base + ".assign").c_str());
+        const int threads = max(1, omp_get_max_threads());
+        const uint64_t chunk = 1u << 14;
+        const int64_t nchunks = (int64_t)((m + chunk - 1) / chunk), batch = max<int64_t>(1, threads * 2);
+        for (int64_t c0 = 0; c0 < nchunks; c0 += batch) {
+            const int64_t nb = min(batch, nchunks - c0);
+            vector<string> out(nb);
+#pragma omp parallel for schedule(dynamic, 1) num_threads(threads)
+            for (int64_t c = 0; c < nb; ++c) {
+                const uint64_t r0 = (uint64_t)(c0 + c) * chunk, r1 = min<uint64_t>(m, r0 + chunk);
+                string &o = out[c];
+                char tmp[96];
+                for (uint64_t i = r0; i < r1; ++i)
+                    for (uint64_t j = hits.row_ptr[i]; j < hits.row_ptr[i + 1]; ++j)
+                        o.append(tmp, (size_t)snprintf(tmp, sizeof tmp, "%llu\t%u\t%.9g\n", (unsigned long long)i, hits.col_idx[j], P[j]));
+            }
+            for (auto &x : out) ofs.write(x.data(), (streamsize)x.size());
+        }
+        ofs.close();
+        if (!ofs) fatal("cannot write " + opt.output_base + ".assign");
+    }
+    vector<double> expected(n, 0.0);
+    for (uint64_t i = 0; i < m; ++i)
+        for (uint64_t j = hits.row_ptr[i]; j < hits.row_ptr[i + 1]; ++j) expected[hits.col_idx[j]] += (double)hits.k[i] * P[j];
+    auto of_name = [&](const string &name) { const int32_t t = obs.of(name); return t >= 0 ? expected[t] : 0.0; };
+    auto line = [](ostream &o, const string &id, double v) {
+        char tmp[40];
+        snprintf(tmp, sizeof tmp, "%.9g", v);
+        o << id << "\t" << tmp << "\n";
+    };
+    ofstream ofs((opt.output_base + ".counts").c_str());          // the rows of .mmseq, in its order
+    ofs << "feature_id\texpected_hits\n";
+    for (auto &name : hdr.transcriptList) line(ofs, name, of_name(name));
+    ofs.close();
+    if (!ofs) fatal("cannot write " + opt.output_base + ".counts");
+    ofs.clear();
+    ofs.open((opt.output_base + ".gene.counts").c_str());         // the rows of .gene.mmseq; a gene's isoforms added in @GeneIsoforms order
+    ofs << "feature_id\texpected_hits\n";
+    for (auto &gt : hdr.gene2transcripts) {
+        double sum = 0.0;
+        for (auto &name : gt.second) sum += of_name(name);
+        line(ofs, gt.first, sum);
+    }
+    ofs.close();
+    if (!ofs) fatal("cannot write " + opt.output_base + ".gene.counts");
+}
+
 static void print_parameters(const Options &opt, int max_threads)
 {
     cout << "Running mmseq with parameters:\n"
@@ -1528,6 +1598,11 @@ static void print_output_files(const Options &opt)
          << "  " << opt.output_base << ".gene.trace_gibbs.gz" << endl
          << "  " << opt.output_base << ".prop.trace_gibbs.gz" << endl
          << endl;
+    if (opt.assign)
+        cout << "  " << opt.output_base << ".assign" << endl
+             << "  " << opt.output_base << ".counts" << endl
+             << "  " << opt.output_base << ".gene.counts" << endl
+             << endl;
     if (opt.debug) {
         cout << endl
              << "  " << opt.output_base << ".trace_em.gz" << endl
@@ -1604,8 +1679,12 @@ static int run(int argc, char **argv)
             write_convergence_tables(opt, hdr, obs, layout, conv);
             stage.mark("convergence tables");
         }
+        if (opt.assign) {
+            stage.mark("write tables");
+            write_assignments(opt, hdr, hits, obs, ch);
+        }
         print_output_files(opt);
-        stage.mark("write tables");
+        stage.mark(opt.assign ? "assignment probabilities" : "write tables");
         // (the writers fetch the last 1/64 of the rows behind the loop's last check: a failure there -- a HIP error in a row fetch --
         // would leave a valid but truncated trace file; it ends the run like any other)
         writers.finish();
