@@ -447,7 +447,8 @@ enum {
     MMG_OPT_CONV_SLAB = 13,        /* v >= 1: at most v series per slab of mmg_convergence_create / _of_traces (slab edges on small inputs)     */
     MMG_OPT_DIFF_TRACE_ROWS = 14,  /* v >= 1: at most v rows per row buffer of mmg_diff_trace_open (shortened traced launches on small inputs)    */
     MMG_OPT_ASSIGN_WAVES = 15,     /* v >= 1: at most v waves per launch of mmg_assign_run_* (several scratch chunks on small inputs)             */
-    MMG_OPT_COUNT_ = 16
+    MMG_OPT_CONTRAST_SLAB = 16,    /* v >= 1: at most v contrasts per slab of mmg_contrast_create / _of_traces (slab edges on small inputs)      */
+    MMG_OPT_COUNT_ = 17
 };
 int mmg_selftest_option(int option, int value);
 /* What the library holds: counts[3] = device buffers, streams, events (tests: every call gives back what it acquired). */
@@ -547,6 +548,44 @@ int mmg_assign_get(mmg_assign *h, uint64_t first_hit, uint64_t n_hits, double *P
  * MMG_OPT_ASSIGN_WAVES if set)), ceil64 rounding up to a multiple of 64.  Both are kept until a run of another shape. */
 int mmg_assign_device_bytes(mmg_assign *h, uint64_t *bytes);
 void mmg_assign_destroy(mmg_assign *h);
+
+/* ---- contrasts: posterior log-ratios between sets of transcripts of one sample ------------------------------------------
+ * The kept samples of a chain are draws from the joint posterior, so they carry the posterior of any comparison between features of
+ * the same sample: an allele against the other, an isoform against its gene, a gene against its family.  Contrast c has an ordered
+ * numerator list num_member[num_ptr[c] .. num_ptr[c + 1]) and a denominator list alike; a member < n is the caller's transcript,
+ * n + v isoform without hits v (the members of mmg_summary_desc's groups).  Both lists are non-empty; a member may be on both sides
+ * (a proportion), not twice on one.  Per kept sample s: N_s, D_s = the members' traces added in list order from 0, r_s = log N_s -
+ * log D_s (the library's log; never the logarithm of the quotient, which underflows where the difference does not; non-finite values
+ * propagate), gt_s = N_s > D_s.  Per contrast: log_ratio = the mean of r (samples added in order); var, tau and the return code of
+ * Sokal's estimator on r, as mmg_summary_get gives them for log mu; the order statistics of r at percentile_index; p_gt = the share
+ * of samples with gt_s.  Every sum runs in a fixed order (tests/contrast_ref.py) without floating-point
+ * atomics: reruns are bit-identical.  Additive in ABI version 8. */
+typedef struct mmg_contrast mmg_contrast;
+typedef struct mmg_contrast_desc {
+    uint32_t n_contrasts;                                  /* at least 1 */
+    const uint64_t *num_ptr; const uint32_t *num_member;   /* n_contrasts + 1 offsets from 0, not decreasing */
+    const uint64_t *den_ptr; const uint32_t *den_member;
+    uint32_t n_percentiles; const int32_t *percentile_index;   /* sample indices of the sorted series; outside [0, S): NaN */
+} mmg_contrast_desc;
+/* After mmg_summary_finish (or _create) of a summary q of sampler s: the chain is the summary's, and so are the isoforms without hits
+ * (their simulated traces are drawn again, the same bits).  Checked before any device work.  The sampler must outlive the handle. */
+int mmg_contrast_create(mmg_sampler *s, mmg_summary *q, const mmg_contrast_desc *d, mmg_contrast **out);
+/* The same from host traces, series-major traces[member * S + s]; members < n_series only. */
+int mmg_contrast_of_traces(int device, uint32_t S, uint32_t n_series, const double *traces, const mmg_contrast_desc *d, mmg_contrast **out);
+/* log_ratio, var, tau, sokal_rc, p_gt: [n_contrasts]; percentiles: [n_contrasts][n_percentiles]; any output may be NULL.  The results
+ * are on the host from creation: no device work. */
+int mmg_contrast_get(mmg_contrast *h, double *log_ratio, double *var, double *tau, int32_t *sokal_rc, double *p_gt, double *percentiles);
+/* r of the contrasts [first, first + count), R[(c - first) * S + s]: computed again on the device, the same bits as at creation */
+int mmg_contrast_get_rows(mmg_contrast *h, uint32_t first, uint32_t count, double *R);
+/* What the handle holds between calls: 16 (n_contrasts + 1) + 4 (numerator members + denominator members) bytes of lists; from a
+ * sampler also 4 bytes per distinct member of each slab (summed over the slabs) and 16 bytes per isoform without hits of the summary;
+ * from host traces also 8 n_series S.  A slab is cap = max(1, min(n_contrasts, 256 MiB / (8 S), MMG_OPT_CONTRAST_SLAB if set))
+ * contrasts.  While creation or mmg_contrast_get_rows runs, on top of that: 8 S cap of series (get_rows: 8 S min(cap, count)),
+ * from a sampler 8 S times the largest number of distinct members of a slab, and at creation 16 max(S, 1) + 4 n_percentiles +
+ * cap (32 + 8 n_percentiles) bytes of tables and results, plus 24 SP min(cap, 1024) of workspace when S > 8192 (SP = S rounded up to
+ * a power of two). */
+int mmg_contrast_device_bytes(mmg_contrast *h, uint64_t *bytes);
+void mmg_contrast_destroy(mmg_contrast *h);
 
 /* ---- mmdiff: Bayesian model selection between two linear models per feature -------------------------------------------
  * src/bms.cpp driven as src/mmdiff.cpp:744-866: per feature an independent MCMC over both models with pseudopriors, the model

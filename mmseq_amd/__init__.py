@@ -3,6 +3,8 @@
 csrc/      HIP kernels (gfx950), the C ABI (include/mmgibbs.h) and the C++ host code
 gibbs.py   numpy-facing mirror of the C ABI (Problem, Sampler)
 assign.py  posterior assignment probability of every hit from a chain's trace (Assign)
+contrast.py posterior log-ratios between sets of transcripts of one sample from a chain's trace (Contrast)
 """
 from .assign import Assign  # noqa: F401
+from .contrast import Contrast  # noqa: F401
 from .gibbs import Problem, Sampler, device_count  # noqa: F401

@@ -39,7 +39,7 @@ class MMGError(RuntimeError):
 
 LAYOUT_CANONICAL, LAYOUT_KEEP_ROWS = 0, 1
 # mmg_selftest_option ids
-OPT_SAMPLE_KERNEL, OPT_FORCE_IDX64, OPT_SELL_WAVES_PER_CU, OPT_EM_KERNEL, OPT_EM_GRID, OPT_FUSE_CHAINS, OPT_CNT_REPLICAS, OPT_GROUP_FAIL, OPT_DERIVE_ORDER, OPT_WIRE_CHECK, OPT_BIGK_PER_WAVE, OPT_BIGK_SIDE_STREAM, OPT_FAIL_ALLOC, OPT_CONV_SLAB, OPT_DIFF_TRACE_ROWS, OPT_ASSIGN_WAVES = range(16)
+OPT_SAMPLE_KERNEL, OPT_FORCE_IDX64, OPT_SELL_WAVES_PER_CU, OPT_EM_KERNEL, OPT_EM_GRID, OPT_FUSE_CHAINS, OPT_CNT_REPLICAS, OPT_GROUP_FAIL, OPT_DERIVE_ORDER, OPT_WIRE_CHECK, OPT_BIGK_PER_WAVE, OPT_BIGK_SIDE_STREAM, OPT_FAIL_ALLOC, OPT_CONV_SLAB, OPT_DIFF_TRACE_ROWS, OPT_ASSIGN_WAVES, OPT_CONTRAST_SLAB = range(17)
 
 
 class ProblemDesc(C.Structure):
@@ -67,6 +67,11 @@ class SummaryDesc(C.Structure):
                 ("n_identical", C.c_uint32), ("identical_ptr", C.c_void_p), ("identical_member", C.c_void_p),
                 ("n_genes", C.c_uint32), ("gene_ptr", C.c_void_p), ("gene_member", C.c_void_p),
                 ("n_percentiles", C.c_uint32), ("percentile_index", C.c_void_p)]
+
+
+class ContrastDesc(C.Structure):
+    _fields_ = [("n_contrasts", C.c_uint32), ("num_ptr", C.c_void_p), ("num_member", C.c_void_p), ("den_ptr", C.c_void_p),
+                ("den_member", C.c_void_p), ("n_percentiles", C.c_uint32), ("percentile_index", C.c_void_p)]
 
 
 class Config(C.Structure):
@@ -186,6 +191,12 @@ SYMBOLS = {
     "mmg_assign_get": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
     "mmg_assign_device_bytes": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mmg_assign_destroy": (None, [C.c_void_p]),
+    "mmg_contrast_create": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ContrastDesc), C.POINTER(C.c_void_p)]),
+    "mmg_contrast_of_traces": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(ContrastDesc), C.POINTER(C.c_void_p)]),
+    "mmg_contrast_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmg_contrast_get_rows": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "mmg_contrast_device_bytes": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mmg_contrast_destroy": (None, [C.c_void_p]),
     "mmg_convergence_create": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "mmg_convergence_get": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmg_convergence_destroy": (None, [C.c_void_p]),

@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "../../../include/mmgibbs.h"
+#include "contrasts_file.hpp"
 #include "hitsio.hpp"
 #include "huffenc.hpp"
 #include "numerics.hpp"
@@ -80,6 +81,8 @@ static void printUsage(ostream &out)
         << "                     split R-hat and bulk / tail effective sample sizes across the chains (one device only)" << endl
         << "  -assign            also write output_base.assign (the lines of output_base.M with the posterior probability that the hit set's" << endl
         << "                     reads come from that transcript), .counts and .gene.counts (expected hits per feature; one device only)" << endl
+        << "  -contrasts FILE    also write output_base.contrasts.mmseq: per line `name<TAB>id,id,...<TAB>id,id,...` of FILE the posterior of" << endl
+        << "                     log(sum of mu over the first ids / sum over the second) from chain 0's samples (one device only)" << endl
         << endl;
 }
 
@@ -101,10 +104,10 @@ static bool is_power_of_two(unsigned v) { return v != 0 && (v & (v - 1)) == 0; }
 
 // Command line: a table of options -- name, the variable it sets, how its value is read -- walked once.  Same flags, defaults,
 // messages and exit codes as the reference's loop at src/mmseq.cpp:206-276 (tests/test_cli.py holds them), plus -device / -gpus /
-// -chains / -em_one_device / -convergence / -assign of this build.
+// -chains / -em_one_device / -convergence / -assign / -contrasts of this build.
 struct CliOption {
     const char *name;
-    enum Kind { REAL, INT, FLAG, LIST, HELP, VERSION } kind;
+    enum Kind { REAL, INT, FLAG, LIST, TEXT, HELP, VERSION } kind;
     void *target;
 };
 
@@ -128,6 +131,7 @@ using Group = Owned<mmg_group, mmg_group_destroy>;
 using Summary = Owned<mmg_summary, mmg_summary_destroy>;
 using Convergence = Owned<mmg_convergence, mmg_convergence_destroy>;
 using Assign = Owned<mmg_assign, mmg_assign_destroy>;
+using Contrast = Owned<mmg_contrast, mmg_contrast_destroy>;
 // handles of one kind, one per device, destroyed together in order; reads as the array of raw handles the calls take
 template <class T, void (*Destroy)(T *)> struct HandleSet {
     vector<T *> h;
@@ -359,6 +363,7 @@ struct Options {
     bool debug = false;
     int device = 0, gpus = 1, chains = 1;
     bool em_one_device = false, convergence = false, assign = false;
+    string contrasts_file;
     string hits_file, output_base;
 };
 
@@ -376,6 +381,7 @@ static Options parse_options(int argc, char **argv)
         {"-percentiles", CliOption::LIST, &percentile_fields},
         {"-debug", CliOption::FLAG, &o.debug},        {"-em_one_device", CliOption::FLAG, &o.em_one_device},
         {"-convergence", CliOption::FLAG, &o.convergence}, {"-assign", CliOption::FLAG, &o.assign},
+        {"-contrasts", CliOption::TEXT, &o.contrasts_file},
         {"-h", CliOption::HELP, nullptr},           {"-help", CliOption::HELP, nullptr},       {"--help", CliOption::HELP, nullptr},
         {"-v", CliOption::VERSION, nullptr},        {"-version", CliOption::VERSION, nullptr}, {"--version", CliOption::VERSION, nullptr},
     };
@@ -396,6 +402,7 @@ static Options parse_options(int argc, char **argv)
         const char *value = argv[pos + 1];
         if (opt->kind == CliOption::REAL) *(double *)opt->target = strtod(value, NULL);
         else if (opt->kind == CliOption::INT) *(int *)opt->target = atoi(value);
+        else if (opt->kind == CliOption::TEXT) *(string *)opt->target = value;
         else *(vector<string> *)opt->target = split_fields(value, ',');
         pos += 2;
     }
@@ -421,6 +428,8 @@ static Options parse_options(int argc, char **argv)
     check(!(o.convergence && o.gpus > 1), "Error: -convergence needs every chain on one device: it cannot be combined with -gpus > 1.\n");
     // the pass reads the chain's trace where one sampler holds it
     check(!(o.assign && o.gpus > 1), "Error: -assign reads the chain's trace on one device: it cannot be combined with -gpus > 1.\n");
+    // the pass reads chain 0's trace where one sampler holds it
+    check(!(!o.contrasts_file.empty() && o.gpus > 1), "Error: -contrasts reads the chain's trace on one device: it cannot be combined with -gpus > 1.\n");
     check(is_power_of_two((unsigned)trace_length), "Error: gibbs_iter/gibbs_ss must be a power of 2.\n");
     return o;
 }
@@ -1568,6 +1577,77 @@ static void write_assignments(const Options &opt, const Header &hdr, const Hits 
     if (!ofs) fatal("cannot write " + opt.output_base + ".gene.counts");
 }
 
+// ---- -contrasts: the file is read against the header's ids right after the header, before the reads and any device work
+static ContrastsFile read_contrasts(const Options &opt, const Header &hdr)
+{
+    ContrastsFile cf;
+    if (opt.contrasts_file.empty()) return cf;
+    unordered_map<string, uint32_t> header_index;
+    header_index.reserve(hdr.transcriptList.size());
+    for (size_t i = 0; i < hdr.transcriptList.size(); ++i) header_index[hdr.transcriptList[i]] = (uint32_t)i;
+    string error;
+    if (!read_contrasts_file(opt.contrasts_file, header_index, cf, error)) fatal(error);
+    return cf;
+}
+
+// ---- .contrasts.mmseq: per contrast the posterior of log(sum of mu over the numerator / sum over the denominator) over chain 0's
+//      trace_length kept samples -- the samples the .mmseq summaries are taken over -- on the device (mmg_contrast_*).  The columns
+//      mmdiff reads are there under its names: log_mu is the mean log-ratio, sd its posterior standard deviation.
+static void write_contrasts(const Options &opt, const Header &hdr, const Hits &hits, const Observed &obs, const UniqueHits &uh,
+                            const SeriesLayout &layout, const Chains &ch, const ContrastsFile &cf)
+{
+    const uint32_t n = hits.n();
+    const size_t C = cf.size(), nP = opt.percentiles.size();
+    vector<uint64_t> ptr[2] = {{0}, {0}};
+    vector<uint32_t> mem[2];
+    vector<long long> side_hits[2];
+    vector<char> side_observed[2];
+    for (size_t c = 0; c < C; ++c)
+        for (int k = 0; k < 2; ++k) {
+            long long hits_sum = 0;
+            bool any = false;
+            for (uint32_t hidx : (k == 0 ? cf.num[c] : cf.den[c])) {
+                const string &name = hdr.transcriptList[hidx];
+                const int32_t t = obs.of(name);
+                if (t >= 0) { mem[k].push_back((uint32_t)t); hits_sum += uh.transcript[t]; any = true; }
+                else mem[k].push_back(n + layout.simu_of(name));   // no hits: its simulated trace
+            }
+            ptr[k].push_back(mem[k].size());
+            side_hits[k].push_back(hits_sum);
+            side_observed[k].push_back(any);
+        }
+    mmg_contrast_desc cd;
+    memset(&cd, 0, sizeof cd);
+    cd.n_contrasts = (uint32_t)C;
+    cd.num_ptr = ptr[0].data(); cd.num_member = mem[0].data();
+    cd.den_ptr = ptr[1].data(); cd.den_member = mem[1].data();
+    cd.n_percentiles = (uint32_t)layout.pind.size(); cd.percentile_index = layout.pind.data();
+    vector<double> mean(C), var(C), tau(C), p_gt(C), pct(max<size_t>(C * nP, 1));
+    vector<int32_t> rc(C);
+    {
+        mmg_contrast *raw = nullptr;
+        MMG_TRY(mmg_contrast_create(ch.smp(), ch.summ.get(), &cd, &raw));
+        Contrast owned(raw);
+        MMG_TRY(mmg_contrast_get(raw, mean.data(), var.data(), tau.data(), rc.data(), p_gt.data(), pct.data()));
+    }
+    ofstream ofs((opt.output_base + ".contrasts.mmseq").c_str());
+    ofs << "# Log-ratios between transcript sets of this sample: log_mu is the posterior mean of log(numerator / denominator); mmdiff needs -nonorm on this table" << endl;
+    ofs << "feature_id\tlog_mu\tsd\tmcse\tiact\tunique_hits\tp_gt\tn_num\tn_den\tobserved\t";
+    ofs << "percentiles";
+    for (size_t i = 0; i < nP; i++) { ofs << opt.percentiles[i]; ofs << (i == nP - 1 ? "\n" : ","); }
+    for (size_t c = 0; c < C; ++c) {
+        // sd, mcse, iact as write_tables' fetch_series derives them (:1311-1324)
+        const double sd = sqrt(var[c]);
+        const double mcse = rc[c] != 0 ? (double)trace_length : sqrt(tau[c] * var[c] / trace_length);
+        const double iact = rc[c] != 0 ? NAN : tau[c];
+        ofs << cf.names[c] << "\t" << mean[c] << "\t" << sd << "\t" << mcse << "\t" << iact << "\t" << min(side_hits[0][c], side_hits[1][c]) << "\t"
+            << p_gt[c] << "\t" << cf.num[c].size() << "\t" << cf.den[c].size() << "\t" << (side_observed[0][c] && side_observed[1][c] ? "1" : "0") << "\t";
+        for (size_t i = 0; i < nP; i++) { ofs << pct[c * nP + i]; ofs << (i == nP - 1 ? "\n" : ","); }
+    }
+    ofs.close();
+    if (!ofs) fatal("cannot write " + opt.output_base + ".contrasts.mmseq");
+}
+
 static void print_parameters(const Options &opt, int max_threads)
 {
     cout << "Running mmseq with parameters:\n"
@@ -1603,6 +1683,7 @@ static void print_output_files(const Options &opt)
              << "  " << opt.output_base << ".counts" << endl
              << "  " << opt.output_base << ".gene.counts" << endl
              << endl;
+    if (!opt.contrasts_file.empty()) cout << "  " << opt.output_base << ".contrasts.mmseq" << endl << endl;
     if (opt.debug) {
         cout << endl
              << "  " << opt.output_base << ".trace_em.gz" << endl
@@ -1639,6 +1720,7 @@ static int run(int argc, char **argv)
         (void)mmg_selftest_philox(device, ctr, key, out);
     });
     const Header hdr = read_header(hitsfileReader);
+    const ContrastsFile contrasts = read_contrasts(opt, hdr);
     const Hits hits = ingest(hitsfileReader, opt.hits_file, hdr.transcriptList.size(), stage.on);
     stage.mark("read hits file + collapse");
     const vector<double> l = effective_lengths(hdr, hits);
@@ -1683,8 +1765,12 @@ static int run(int argc, char **argv)
             stage.mark("write tables");
             write_assignments(opt, hdr, hits, obs, ch);
         }
+        if (!opt.contrasts_file.empty()) {
+            stage.mark(opt.assign ? "assignment probabilities" : "write tables");
+            write_contrasts(opt, hdr, hits, obs, uh, layout, ch, contrasts);
+        }
         print_output_files(opt);
-        stage.mark(opt.assign ? "assignment probabilities" : "write tables");
+        stage.mark(!opt.contrasts_file.empty() ? "contrasts" : opt.assign ? "assignment probabilities" : "write tables");
         // (the writers fetch the last 1/64 of the rows behind the loop's last check: a failure there -- a HIP error in a row fetch --
         // would leave a valid but truncated trace file; it ends the run like any other)
         writers.finish();

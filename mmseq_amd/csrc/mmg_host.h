@@ -276,6 +276,21 @@ struct SamplerView {
 };
 int sampler_view(mmg_sampler *s, SamplerView *v);
 
+// what the contrast code needs to see of a summary (post.hip)
+struct SummaryView {
+    const mmg_problem *p;
+    int device;
+    uint32_t n, nv, S;
+    const double *trace;     // the summary's chain: [S][n] sample-major, device numbering (the sampler's memory)
+    bool finished;
+    uint64_t seed;           // the simulated traces: Gamma(alpha) * vscale[v] keyed (seed, chain 0, TAG_SIMU, vid[v], sample)
+    double alpha;
+    const uint64_t *vid;     // [nv], host (the summary's)
+    const double *vscale;
+};
+int summary_view(mmg_summary *q, SummaryView *v);
+std::vector<double> series_twiddles(uint32_t S);   // the twiddle table of k_series_summary (post.hip)
+
 // read shards of one problem as one EM (em_host.hip): make_reduce(members, ctx) returns the exchange called between the phases with
 // what = 0 (xe: max, int32), 1 (accumulators + log-likelihood limbs: sum, uint64), 2 (column counts: sum, uint64); the buffers of a
 // member come from em_exchange_buffers

@@ -113,4 +113,15 @@ void launch_conv_slab(const double *in, uint64_t ld, uint32_t t0, uint32_t cnt, 
 void launch_convergence(uint32_t cnt, uint32_t C, uint32_t S, const double *X, double inv_log10_p, double *rhat, double *ess_bulk, double *ess_tail,
                         uint64_t *ws, uint32_t ws_groups, hipStream_t s);
 
+// ---- post.hip: the contrasts (contrast_kernels.h)
+// M[j * S + s] = the trace of member col[j] < n (trace[s * n + int_of_ext[col[j]]]) or the simulated trace of isoform col[j] - n, j < nm
+void launch_contrast_gather(uint32_t nm, uint32_t S, uint32_t n, const uint32_t *col, const uint32_t *int_of_ext, const double *trace, uint64_t seed,
+                            double alpha, const uint64_t *vid, const double *vscale, double *M, hipStream_t s);
+// R[w * S + s] = log N_s - log D_s of contrast c0 + w, w < cnt, its lists slots of M[slot][S]; gt[w] = samples with N_s > D_s (gt may be null)
+void launch_contrast_series(uint32_t c0, uint32_t cnt, uint32_t S, const uint64_t *num_ptr, const uint32_t *num_slot, const uint64_t *den_ptr,
+                            const uint32_t *den_slot, const double *M, double *R, uint32_t *gt, hipStream_t s);
+// k_contrast_summary over cnt series R[series][S]: in LDS while S <= 8192, else in ws (3 SP words per workgroup, ws_groups workgroups)
+void launch_contrast_summary(uint32_t cnt, uint32_t S, const double *R, uint32_t np, const int32_t *pind, const double *tw, double *log_ratio,
+                             double *var, double *tau, int32_t *rc, double *pct, uint64_t *ws, uint32_t ws_groups, hipStream_t s);
+
 } // namespace mmg

@@ -2,6 +2,7 @@
 // (src/mmseq.cpp:927-1008, :1110-1227, :1235-1363; src/sokal.cc:33-87).  Kernels in post_kernels.h.
 #include "post_kernels.h"
 #include "conv_kernels.h"
+#include "contrast_kernels.h"
 #include "mmg_host.h"
 #include "mmg_launch.h"
 
@@ -36,6 +37,11 @@ struct mmg_summary {
     // the summary is built in steps (mmg_summary_begin / _advance / _finish): what the steps share
     const mmg_problem *p = nullptr;
     const double *trace = nullptr; // the chain's resident trace [S][n], device numbering
+    // what keys the simulated traces (the device's copy goes at _finish; mmg_contrast_create draws the ones it needs again)
+    uint64_t seed = 0;
+    double alpha = 0.0;
+    std::vector<uint64_t> h_vid;
+    std::vector<double> h_vscale;
     uint32_t done = 0;             // samples whose derived rows exist
     bool finished = false;
     std::vector<DevBuf<uint8_t>> scratch; // device buffers that live until _finish (the pointers below point into them)
@@ -142,6 +148,8 @@ extern "C" int mmg_summary_begin(mmg_sampler *smp, const mmg_summary_desc *d, mm
     q->device = p->device; q->n = n; q->nv = nv; q->ni = ni; q->ng = ng; q->np = np; q->S = S;
     q->p = p;
     q->trace = v.d_trace + (size_t)d->chain * S * n;
+    q->seed = v.cfg.seed; q->alpha = v.cfg.alpha;
+    if (nv) { q->h_vid.assign(d->virtual_id, d->virtual_id + nv); q->h_vscale.assign(d->virtual_scale, d->virtual_scale + nv); }
     HIP_TRY(q->st.create(hipStreamNonBlocking));
     hipStream_t st = q->st.get();
     auto dalloc = [&](void **ptr, size_t bytes) { return scratch_alloc(q->scratch, ptr, bytes); };
@@ -338,6 +346,17 @@ extern "C" int mmg_summary_get_rows(mmg_summary *q, int kind, int first_sample, 
 
 extern "C" void mmg_summary_destroy(mmg_summary *q) { delete q; }
 
+// what contrast.hip sees of a summary (mmg_host.h)
+int mmg::summary_view(mmg_summary *q, SummaryView *v)
+{
+    if (!q || !v) return fail(MMG_ERR_ARG, "NULL summary");
+    v->p = q->p; v->device = q->device; v->n = q->n; v->nv = q->nv; v->S = q->S; v->trace = q->trace; v->finished = q->finished;
+    v->seed = q->seed; v->alpha = q->alpha; v->vid = q->h_vid.data(); v->vscale = q->h_vscale.data();
+    return MMG_OK;
+}
+
+std::vector<double> mmg::series_twiddles(uint32_t S) { return twiddles(S); }
+
 // mmcollapse's output stage (src/mmcollapse.cpp:827-1107) on traces from the host, independent of any sampler: simulated traces of the
 // features without one, sums over the output series (:443-481), then per series the mean of the logged trace and Sokal's var / tau
 // (:923-943) -- k_virtual_traces, k_group_sums and k_series_summary, the kernels of the summary above.
@@ -435,4 +454,32 @@ void mmg::launch_convergence(uint32_t cnt, uint32_t C, uint32_t S, const double 
     else if (cs <= 8192) CONV_IN_LDS(8192);
     else hipLaunchKernelGGL((k_convergence<0>), dim3(cnt < ws_groups ? cnt : ws_groups), dim3(256), 0, st, cnt, C, S, X, inv_log10_p, rhat, ess_bulk, ess_tail, ws);
 #undef CONV_IN_LDS
+}
+
+// launchers of contrast.hip (mmg_launch.h)
+void mmg::launch_contrast_gather(uint32_t nm, uint32_t S, uint32_t n, const uint32_t *col, const uint32_t *int_of_ext, const double *trace, uint64_t seed,
+                                 double alpha, const uint64_t *vid, const double *vscale, double *M, hipStream_t st)
+{
+    if (nm && S) hipLaunchKernelGGL(k_contrast_gather, dim3((nm + 31) / 32, (S + 31) / 32), dim3(256), 0, st, nm, S, n, col, int_of_ext, trace, seed, alpha, vid, vscale, M);
+}
+
+void mmg::launch_contrast_series(uint32_t c0, uint32_t cnt, uint32_t S, const uint64_t *num_ptr, const uint32_t *num_slot, const uint64_t *den_ptr,
+                                 const uint32_t *den_slot, const double *M, double *R, uint32_t *gt, hipStream_t st)
+{
+    constexpr unsigned per = CTR_BLOCK / CTR_LANES;
+    if (cnt && S) hipLaunchKernelGGL(k_contrast_series, dim3((cnt + per - 1) / per), dim3(CTR_BLOCK), 0, st, c0, cnt, S, num_ptr, num_slot, den_ptr, den_slot, M, R, gt);
+}
+
+void mmg::launch_contrast_summary(uint32_t cnt, uint32_t S, const double *R, uint32_t np, const int32_t *pind, const double *tw, double *log_ratio,
+                                  double *var, double *tau, int32_t *rc, double *pct, uint64_t *ws, uint32_t ws_groups, hipStream_t st)
+{
+    if (!cnt) return;
+    ContrastOut o{log_ratio, var, tau, rc, pct};
+#define CONTRAST_IN_LDS(SMAX) hipLaunchKernelGGL((k_contrast_summary<SMAX>), dim3(cnt), dim3(256), 0, st, cnt, S, R, np, pind, tw, o, (uint64_t *)nullptr)
+    if (S <= 1024) CONTRAST_IN_LDS(1024);
+    else if (S <= 2048) CONTRAST_IN_LDS(2048);
+    else if (S <= 4096) CONTRAST_IN_LDS(4096);
+    else if (S <= 8192) CONTRAST_IN_LDS(8192);
+    else hipLaunchKernelGGL((k_contrast_summary<0>), dim3(cnt < ws_groups ? cnt : ws_groups), dim3(256), 0, st, cnt, S, R, np, pind, tw, o, ws);
+#undef CONTRAST_IN_LDS
 }
