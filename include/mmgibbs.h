@@ -82,7 +82,8 @@ extern "C" {
  *      Additive in version 8, no bump (the chain's specification does not change): mmcollapse (mmg_collapse_*), mmdiff (mmg_diff_*), the
  *      owners' self tests (MMG_OPT_FAIL_ALLOC, mmg_selftest_live, mmg_selftest_sampler_events), the convergence diagnostics across
  *      chains (mmg_convergence_*, MMG_OPT_CONV_SLAB), mmdiff's chains (mmg_diff_chains_*) and the posterior assignment probabilities
- *      of the hits (mmg_assign_*, MMG_OPT_ASSIGN_WAVES). */
+ *      of the hits (mmg_assign_*, MMG_OPT_ASSIGN_WAVES), and the posterior summary over the draws of all chains (mmg_pooled_*,
+ *      MMG_OPT_POOL_SLAB). */
 /* Layout.  The model does not care about the order of rows or the numbering of transcripts (src/mmseq.cpp:399-418 uses
  * first-seen order for both); the kernels do: they keep a window of consecutive transcripts in LDS and want the 64 rows of a
  * wave to have equal lengths.  mmg_problem_create therefore stores the rows in a CANONICAL order of its own (sorted on the
@@ -385,6 +386,46 @@ void mmg_convergence_destroy(mmg_convergence *h);
 int mmg_convergence_of_traces(int device, uint32_t n_chains, uint32_t S, uint32_t count, const double *traces, double *rhat, double *ess_bulk,
                               double *ess_tail);
 
+/* ---- the posterior summary over all chains ----------------------------------------------------------------------------------
+ * What mmg_summary_* computes from one chain, from the N = n_chains * trace_len draws of every chain of a sampler (DESIGN.md section 14
+ * states the definitions, tests/pooled_ref.py restates them).  With m_c, var_c, tau_c, rc_c the columns mmg_summary_get returns for
+ * chain c alone (S = trace_len, sums over the chains in ascending order, every operation rounded once):
+ *   log_mean = (sum m_c) / C;   var = ((S - 1) sum var_c + S sum (m_c - log_mean)^2) / (N - 1), the sample variance of the N logged draws;
+ *   mcse2 = (sum tau_c var_c) / S / (C C), the variance of the mean of C independent chain means;   tau = (sum tau_c var_c) / (sum var_c);
+ *   rc = the first non-zero rc_c, else 0; with rc != 0, tau = mcse2 = 0.  One chain: its own columns, copied, mcse2 = tau_0 var_0 / S.
+ *   percentiles: the order statistics of the N pooled draws at positions in [0, N) (NaN outside), NaNs last.
+ * Proportions: mean = (sum over all N draws) / N, the probit mean and sd over the N draws, each chain's sums taken in sample order and
+ * added over the chains; percentiles of the pooled proportions.  Reruns are bit-identical.  Additive in ABI version 8. */
+typedef struct mmg_pooled mmg_pooled;
+/* After the chain (the call synchronises with the sampler, then works on a stream of its own and touches nothing of the sampler): every
+ * chain's trace of the sampler (keep_trace; MMG_ERR_ARG without), the series of every kind of mmg_summary_desc as mmg_convergence_create
+ * builds them (isoforms without hits simulated per chain, keyed (seed, chain c, id, sample)).  d->chain is ignored; d->percentile_index
+ * are positions in [0, n_chains * trace_len).  The results are kept on the host; no device memory is held after the call. */
+int mmg_pooled_create(mmg_sampler *s, const mmg_summary_desc *d, mmg_pooled **out);
+/* The pooled columns of the series of `kind` (MMG_SERIES_*), in the numbering of mmg_summary_get; percentiles [series][percentile];
+ * any output may be NULL */
+int mmg_pooled_get(mmg_pooled *h, int kind, double *log_mean, double *var, double *tau, double *mcse2, int32_t *rc, double *percentiles);
+/* The columns of chain `chain` alone: what mmg_summary_get returns for a summary of that chain (for the isoforms without hits and the
+ * groups that contain them: of the traces simulated for that chain) */
+int mmg_pooled_get_chain(mmg_pooled *h, int kind, int chain, double *log_mean, double *var, double *tau, int32_t *rc);
+/* kind MMG_SERIES_TRANSCRIPT or MMG_SERIES_VIRTUAL, as mmg_summary_get_proportions */
+int mmg_pooled_get_proportions(mmg_pooled *h, int kind, double *mean_prop, double *mean_probit, double *sd_probit, double *percentiles);
+void mmg_pooled_destroy(mmg_pooled *h);
+/* The pooled log columns of `count` series of traces from the host: traces[(c * S + s) * count + i] is draw s of chain c of series i;
+ * pind: np positions in [0, n_chains * S); percentiles [series][np]; any output may be NULL.  MMG_ERR_ARG for n_chains == 0 or S == 0. */
+int mmg_pooled_of_traces(int device, uint32_t n_chains, uint32_t S, uint32_t count, const double *traces, uint32_t np, const int32_t *pind,
+                         double *log_mean, double *var, double *tau, double *mcse2, int32_t *rc, double *percentiles);
+/* Device memory mmg_pooled_create held while it ran (all of it from the first launch to the last).  With C chains of S samples, the counts
+ * n, nv, ni, ng of the four kinds, np percentiles, cap = max(1, min(max count, 256 MiB / (8 C S), MMG_OPT_POOL_SLAB if set)) series per
+ * slab and L the largest number of gene members the genes of one slab of transcripts (or of isoforms without hits) list:
+ *   16 max(nv, 1) + 8 (ni + 1 | 1) + 4 max(members of the sets, 1) + 8 (ng + 1 | 1) + 4 max(members of the genes, 1)    the description
+ *   + 8 C S max(nv, 1)                                                                                              the simulated traces
+ *   + 8 cap C S + 16 cap S                                                                  a slab, its group sums and its proportions
+ *   + 8 (cap + 1) + 4 max(L, 1) + 5 cap                                                                      the slab's genes and flags
+ *   + 28 cap C + 36 cap + 8 cap max(np, 1) + 4 max(np, 1) + 16 max(S, 1)            the chains' columns, the results, the twiddle table
+ *   + (S > 8192: 24 * 1024 SP, SP = S rounded up to a power of two) + (C S > 8192: 8 PP min(1024, cap, max(1, 256 MiB / (8 PP)))). */
+int mmg_pooled_device_bytes(mmg_pooled *h, uint64_t *bytes);
+
 /* ---- several GPUs of one node, one process (RCCL over xGMI) ----------------------------------------
  * The reference parallelises with OpenMP threads inside one process (src/mmseq.cpp:834-838, :864); here the unit is a device.
  * A group owns one RCCL communicator per device (ncclCommInitAll); sampler i of every call below must live on device i of the
@@ -448,7 +489,8 @@ enum {
     MMG_OPT_DIFF_TRACE_ROWS = 14,  /* v >= 1: at most v rows per row buffer of mmg_diff_trace_open (shortened traced launches on small inputs)    */
     MMG_OPT_ASSIGN_WAVES = 15,     /* v >= 1: at most v waves per launch of mmg_assign_run_* (several scratch chunks on small inputs)             */
     MMG_OPT_CONTRAST_SLAB = 16,    /* v >= 1: at most v contrasts per slab of mmg_contrast_create / _of_traces (slab edges on small inputs)      */
-    MMG_OPT_COUNT_ = 17
+    MMG_OPT_POOL_SLAB = 17,        /* v >= 1: at most v series per slab of mmg_pooled_create / _of_traces (slab edges on small inputs)          */
+    MMG_OPT_COUNT_ = 18
 };
 int mmg_selftest_option(int option, int value);
 /* What the library holds: counts[3] = device buffers, streams, events (tests: every call gives back what it acquired). */

@@ -79,6 +79,10 @@ static void printUsage(ostream &out)
         << "  -em_one_device     with -gpus > 1 and one chain: run the EM on the first device alone instead of over the read shards" << endl
         << "  -convergence       also write output_base.convergence, .identical.convergence and .gene.convergence: rank-normalized" << endl
         << "                     split R-hat and bulk / tail effective sample sizes across the chains (one device only)" << endl
+        << "  -pool              with -chains: every column of .mmseq, .identical.mmseq and .gene.mmseq -- log_mu, sd, mcse, iact, the percentiles," << endl
+        << "                     the proportion columns -- from the kept samples of all chains instead of chain 0's.  log_mu is then the mean of" << endl
+        << "                     log mu over the kept samples (without -pool, -chains takes it from the sampler's running moments over every" << endl
+        << "                     iteration).  Trace files, -assign and -contrasts stay chain 0's (one device only)" << endl
         << "  -assign            also write output_base.assign (the lines of output_base.M with the posterior probability that the hit set's" << endl
         << "                     reads come from that transcript), .counts and .gene.counts (expected hits per feature; one device only)" << endl
         << "  -contrasts FILE    also write output_base.contrasts.mmseq: per line `name<TAB>id,id,...<TAB>id,id,...` of FILE the posterior of" << endl
@@ -104,7 +108,7 @@ static bool is_power_of_two(unsigned v) { return v != 0 && (v & (v - 1)) == 0; }
 
 // Command line: a table of options -- name, the variable it sets, how its value is read -- walked once.  Same flags, defaults,
 // messages and exit codes as the reference's loop at src/mmseq.cpp:206-276 (tests/test_cli.py holds them), plus -device / -gpus /
-// -chains / -em_one_device / -convergence / -assign / -contrasts of this build.
+// -chains / -em_one_device / -convergence / -pool / -assign / -contrasts of this build.
 struct CliOption {
     const char *name;
     enum Kind { REAL, INT, FLAG, LIST, TEXT, HELP, VERSION } kind;
@@ -130,6 +134,7 @@ using Problem = Owned<mmg_problem, mmg_problem_destroy>;
 using Group = Owned<mmg_group, mmg_group_destroy>;
 using Summary = Owned<mmg_summary, mmg_summary_destroy>;
 using Convergence = Owned<mmg_convergence, mmg_convergence_destroy>;
+using PooledSummary = Owned<mmg_pooled, mmg_pooled_destroy>;
 using Assign = Owned<mmg_assign, mmg_assign_destroy>;
 using Contrast = Owned<mmg_contrast, mmg_contrast_destroy>;
 // handles of one kind, one per device, destroyed together in order; reads as the array of raw handles the calls take
@@ -362,7 +367,7 @@ struct Options {
     int seed = 1234;
     bool debug = false;
     int device = 0, gpus = 1, chains = 1;
-    bool em_one_device = false, convergence = false, assign = false;
+    bool em_one_device = false, convergence = false, assign = false, pool = false;
     string contrasts_file;
     string hits_file, output_base;
 };
@@ -381,7 +386,7 @@ static Options parse_options(int argc, char **argv)
         {"-percentiles", CliOption::LIST, &percentile_fields},
         {"-debug", CliOption::FLAG, &o.debug},        {"-em_one_device", CliOption::FLAG, &o.em_one_device},
         {"-convergence", CliOption::FLAG, &o.convergence}, {"-assign", CliOption::FLAG, &o.assign},
-        {"-contrasts", CliOption::TEXT, &o.contrasts_file},
+        {"-contrasts", CliOption::TEXT, &o.contrasts_file}, {"-pool", CliOption::FLAG, &o.pool},
         {"-h", CliOption::HELP, nullptr},           {"-help", CliOption::HELP, nullptr},       {"--help", CliOption::HELP, nullptr},
         {"-v", CliOption::VERSION, nullptr},        {"-version", CliOption::VERSION, nullptr}, {"--version", CliOption::VERSION, nullptr},
     };
@@ -426,6 +431,8 @@ static Options parse_options(int argc, char **argv)
           "Error: -gpus and -chains must be positive, and chains a multiple of gpus when both exceed 1.\n");
     // the diagnostic reads every chain's trace on one device
     check(!(o.convergence && o.gpus > 1), "Error: -convergence needs every chain on one device: it cannot be combined with -gpus > 1.\n");
+    // the pooled summary reads every chain's trace on one device
+    check(!(o.pool && o.gpus > 1), "Error: -pool needs every chain on one device: it cannot be combined with -gpus > 1.\n");
     // the pass reads the chain's trace where one sampler holds it
     check(!(o.assign && o.gpus > 1), "Error: -assign reads the chain's trace on one device: it cannot be combined with -gpus > 1.\n");
     // the pass reads chain 0's trace where one sampler holds it
@@ -1285,9 +1292,42 @@ static ConvAll fetch_convergence(const Chains &ch, const SeriesLayout &layout, u
     return c;
 }
 
+// ---- the summary over all chains (-pool): the columns of the three tables from the kept samples of every chain, on the device
+struct PooledSeries { vector<double> log_mean, var, tau, mcse2, pct; vector<int32_t> rc; };
+struct PooledProps { vector<double> mean, probit_mean, probit_sd, pct; };
+struct PooledAll { bool on = false; PooledSeries ser[4]; PooledProps prop[2]; };   // indexed by MMG_SERIES_*
+static PooledAll fetch_pooled(const Options &opt, const Chains &ch, const SeriesLayout &layout, uint32_t n)
+{
+    PooledAll a;
+    a.on = true;
+    mmg_summary_desc pd = layout.desc();
+    vector<int> pind;   // positions among the chains * trace_length pooled draws
+    for (double p : opt.percentiles) pind.push_back(static_cast<int>(round(p / 100.0 * ((double)opt.chains * trace_length - 1))));
+    pd.n_percentiles = (uint32_t)pind.size(); pd.percentile_index = pind.data();
+    mmg_pooled *pooled = nullptr;
+    MMG_TRY(mmg_pooled_create(ch.smp(), &pd, &pooled));
+    const PooledSummary owned(pooled);
+    const size_t nP = pind.size();
+    const size_t counts[4] = {n, pd.n_virtual, pd.n_identical, pd.n_genes};
+    for (int kind = 0; kind < 4; ++kind) {
+        PooledSeries &o = a.ser[kind];
+        const size_t c = max<size_t>(counts[kind], 1);
+        o.log_mean.resize(c); o.var.resize(c); o.tau.resize(c); o.mcse2.resize(c); o.rc.resize(c); o.pct.resize(max<size_t>(counts[kind] * nP, 1));
+        MMG_TRY(mmg_pooled_get(pooled, kind, o.log_mean.data(), o.var.data(), o.tau.data(), o.mcse2.data(), o.rc.data(), o.pct.data()));
+    }
+    for (int kind = 0; kind < 2; ++kind) {
+        PooledProps &o = a.prop[kind];
+        const size_t c = max<size_t>(counts[kind], 1);
+        o.mean.resize(c); o.probit_mean.resize(c); o.probit_sd.resize(c); o.pct.resize(max<size_t>(counts[kind] * nP, 1));
+        MMG_TRY(mmg_pooled_get_proportions(pooled, kind, o.mean.data(), o.probit_mean.data(), o.probit_sd.data(), o.pct.data()));
+    }
+    return a;
+}
+
 // ---- summary columns (src/mmseq.cpp:1110-1363) and the .mmseq, .identical.mmseq and .gene.mmseq tables
 static void write_tables(const Options &opt, const Header &hdr, const Hits &hits, const Observed &obs, const UniqueHits &uh,
-                         const vector<double> &mu_em, const SeriesLayout &layout, const Chains &ch, const Pooled &pooled, StageTimer &stage)
+                         const vector<double> &mu_em, const SeriesLayout &layout, const Chains &ch, const Pooled &pooled, const PooledAll &all_chains,
+                         StageTimer &stage)
 {
     const uint32_t n = hits.n();
     const size_t nI = hdr.identical_transcripts.size(), nG = hdr.gene2transcripts.size(), nV = layout.simuIndex.size();
@@ -1300,6 +1340,16 @@ static void write_tables(const Options &opt, const Header &hdr, const Hits &hits
         o.iact.resize(max<size_t>(count, 1)); o.pct.resize(max<size_t>(count * nP, 1));
         vector<double> var(max<size_t>(count, 1)), tau(max<size_t>(count, 1));
         vector<int32_t> rc(max<size_t>(count, 1));
+        if (all_chains.on) { // -pool: the same columns from the draws of every chain; the Monte Carlo error is that of the mean of the chains' means
+            const PooledSeries &ps = all_chains.ser[kind];
+            o.mean = ps.log_mean; o.pct = ps.pct;
+            for (size_t t = 0; t < count; ++t) {
+                if (ps.rc[t] != 0) { o.mcse[t] = (double)opt.chains * trace_length; o.iact[t] = NAN; }
+                else { o.mcse[t] = sqrt(ps.mcse2[t]); o.iact[t] = ps.tau[t]; }
+                o.sd[t] = sqrt(ps.var[t]);
+            }
+            return;
+        }
         MMG_TRY(mmg_summary_get(summ, kind, o.mean.data(), var.data(), tau.data(), rc.data(), o.pct.data()));
         for (size_t t = 0; t < count; ++t) { // :1311-1324
             if (rc[t] != 0) { o.mcse[t] = trace_length; o.iact[t] = NAN; }
@@ -1309,7 +1359,7 @@ static void write_tables(const Options &opt, const Header &hdr, const Hits &hits
     };
     Series sT, sV, sI, sG;
     fetch_series(MMG_SERIES_TRANSCRIPT, n, sT);
-    if (opt.chains > 1 && pooled.ns > 1) { // all chains: mean and sd of log mu from the pooled moments, Monte Carlo error of the pooled mean
+    if (!all_chains.on && opt.chains > 1 && pooled.ns > 1) { // all chains: mean and sd of log mu from the pooled moments, Monte Carlo error of the pooled mean
         for (uint32_t t = 0; t < n; ++t) {
             const double mean = pooled.sl[t] / (double)pooled.ns;
             const double var = (pooled.sl2[t] - (double)pooled.ns * mean * mean) / (double)(pooled.ns - 1);
@@ -1325,6 +1375,11 @@ static void write_tables(const Options &opt, const Header &hdr, const Hits &hits
     auto fetch_props = [&](int kind, size_t count, Props &o) {
         o.mean.resize(max<size_t>(count, 1)); o.probit_mean.resize(max<size_t>(count, 1)); o.probit_sd.resize(max<size_t>(count, 1));
         o.pct.resize(max<size_t>(count * nP, 1));
+        if (all_chains.on) {
+            const PooledProps &pp = all_chains.prop[kind];
+            o.mean = pp.mean; o.probit_mean = pp.probit_mean; o.probit_sd = pp.probit_sd; o.pct = pp.pct;
+            return;
+        }
         MMG_TRY(mmg_summary_get_proportions(summ, kind, o.mean.data(), o.probit_mean.data(), o.probit_sd.data(), o.pct.data()));
     };
     Props pT, pV;
@@ -1332,6 +1387,8 @@ static void write_tables(const Options &opt, const Header &hdr, const Hits &hits
     fetch_props(MMG_SERIES_VIRTUAL, nV, pV);
     auto pct_row = [&](const vector<double> &pct, size_t i) { return vector<double>(pct.begin() + (ptrdiff_t)(i * nP), pct.begin() + (ptrdiff_t)((i + 1) * nP)); };
 
+    // the draws behind a row: a gene without observed transcripts has independent simulated draws, its mcse is sd / sqrt(draws)
+    const double row_draws = all_chains.on ? (double)opt.chains * trace_length : (double)trace_length;
     const double digalpha = mmnum::digamma(opt.alpha);                 // gsl_sf_psi(alpha)        :1372
     const double sqrtpolygalpha = sqrt(mmnum::trigamma(opt.alpha));    // sqrt(gsl_sf_psi_n(1,.))  :1373
     auto prior_logmu = [&](const string &name) { return digalpha - log(opt.beta + hdr.len_of(name) * (double)numbermappedreads / 1000000000.0); };
@@ -1382,7 +1439,7 @@ static void write_tables(const Options &opt, const Header &hdr, const Hits &hits
                     << "1"
                     << "\t";
             } else {
-                ofs << gt.first << "\t" << sG.mean[g] << "\t" << sG.sd[g] << "\t" << sG.sd[g] / sqrt(trace_length) << "\t" << 1 << "\t"
+                ofs << gt.first << "\t" << sG.mean[g] << "\t" << sG.sd[g] << "\t" << sG.sd[g] / sqrt(row_draws) << "\t" << 1 << "\t"
                     << gene_lengths[g] << "\t"
                     << "NA"
                     << "\t"
@@ -1756,7 +1813,12 @@ static int run(int argc, char **argv)
             conv = fetch_convergence(ch, layout, hits.n());
             stage.mark("convergence diagnostics");
         }
-        write_tables(opt, hdr, hits, obs, uh, mu_em, layout, ch, pooled, stage);
+        PooledAll all_chains;
+        if (opt.pool) {
+            all_chains = fetch_pooled(opt, ch, layout, hits.n());
+            stage.mark("summary over all chains");
+        }
+        write_tables(opt, hdr, hits, obs, uh, mu_em, layout, ch, pooled, all_chains, stage);
         if (opt.convergence) {
             write_convergence_tables(opt, hdr, obs, layout, conv);
             stage.mark("convergence tables");

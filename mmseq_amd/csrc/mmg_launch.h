@@ -124,4 +124,20 @@ void launch_contrast_series(uint32_t c0, uint32_t cnt, uint32_t S, const uint64_
 void launch_contrast_summary(uint32_t cnt, uint32_t S, const double *R, uint32_t np, const int32_t *pind, const double *tw, double *log_ratio,
                              double *var, double *tau, int32_t *rc, double *pct, uint64_t *ws, uint32_t ws_groups, hipStream_t s);
 
+// ---- post.hip: the summary over all chains (pool_kernels.h) and the summary kernels it reuses (post_kernels.h)
+// k_proportions of the summary, unchanged: P[s * cnt + i] = X[s * stride + col_of(i)] / G[s * ng + gene_of[i]] (col_of null: the identity)
+void launch_proportions(uint32_t cnt, uint32_t S, uint32_t stride, const double *X, const uint32_t *col_of, const uint32_t *gene_of, uint32_t ng,
+                        const double *G, double *P, hipStream_t s);
+// k_series_summary<., true> of the summary, unchanged, without percentiles, over count series X[series][S]: the per-chain columns of a
+// slab X[series][chain][S] with count = series * chains.  ws: chain_columns_workspace_bytes(S) bytes (0: none needed)
+int launch_chain_columns(uint32_t count, uint32_t S, const double *X, const double *tw, double *log_mean, double *var, double *tau, int32_t *rc,
+                         uint64_t *ws, hipStream_t s);
+size_t chain_columns_workspace_bytes(uint32_t S);
+// k_pooled_summary over cnt series X[series][C][S]: in LDS while C S <= 8192, else in ws (PP words per workgroup, ws_groups workgroups).
+// log mode: cm / cv / ct / crc [cnt][C] are the per-chain columns, results a = log_mean, b = var, c = tau, mcse2, rc;
+// proportion mode: cm / cv / ct are scratch, multi [cnt], results a = mean, b = probit_mean, c = probit_sd
+void launch_pooled_summary(bool log_mode, uint32_t cnt, uint32_t C, uint32_t S, const double *X, uint32_t np, const int32_t *pind, double *cm,
+                           double *cv, double *ct, const int32_t *crc, const uint8_t *multi, double *a, double *b, double *c, double *mcse2,
+                           int32_t *rc, double *pct, uint64_t *ws, uint32_t ws_groups, hipStream_t s);
+
 } // namespace mmg

@@ -3,6 +3,7 @@
 #include "post_kernels.h"
 #include "conv_kernels.h"
 #include "contrast_kernels.h"
+#include "pool_kernels.h"
 #include "mmg_host.h"
 #include "mmg_launch.h"
 
@@ -482,4 +483,41 @@ void mmg::launch_contrast_summary(uint32_t cnt, uint32_t S, const double *R, uin
     else if (S <= 8192) CONTRAST_IN_LDS(8192);
     else hipLaunchKernelGGL((k_contrast_summary<0>), dim3(cnt < ws_groups ? cnt : ws_groups), dim3(256), 0, st, cnt, S, R, np, pind, tw, o, ws);
 #undef CONTRAST_IN_LDS
+}
+
+// launchers of pooled.hip (mmg_launch.h)
+void mmg::launch_proportions(uint32_t cnt, uint32_t S, uint32_t stride, const double *X, const uint32_t *col_of, const uint32_t *gene_of, uint32_t ng,
+                             const double *G, double *P, hipStream_t st)
+{
+    if (cnt && S) hipLaunchKernelGGL(k_proportions, dim3(blocks_of((uint64_t)cnt * S)), dim3(256), 0, st, cnt, S, stride, X, col_of, gene_of, ng, G, P);
+}
+
+int mmg::launch_chain_columns(uint32_t count, uint32_t S, const double *X, const double *tw, double *log_mean, double *var, double *tau, int32_t *rc,
+                              uint64_t *ws, hipStream_t st)
+{
+    SeriesOut o{log_mean, var, tau, rc, nullptr, nullptr, nullptr, nullptr};
+    return launch_series<true>(count, S, X, 0, nullptr, nullptr, tw, o, ws, st);
+}
+
+size_t mmg::chain_columns_workspace_bytes(uint32_t S) { return series_workspace_bytes(S); }
+
+void mmg::launch_pooled_summary(bool log_mode, uint32_t cnt, uint32_t C, uint32_t S, const double *X, uint32_t np, const int32_t *pind, double *cm,
+                                double *cv, double *ct, const int32_t *crc, const uint8_t *multi, double *a, double *b, double *c, double *mcse2,
+                                int32_t *rc, double *pct, uint64_t *ws, uint32_t ws_groups, hipStream_t st)
+{
+    if (!cnt) return;
+    PoolOut o{a, b, c, mcse2, rc, pct};
+    const uint64_t cs = (uint64_t)C * S;
+#define POOLED_IN_LDS(PMAX)                                                                                                                                      \
+    do {                                                                                                                                                         \
+        if (log_mode) hipLaunchKernelGGL((k_pooled_summary<PMAX, true>), dim3(cnt), dim3(256), 0, st, cnt, C, S, X, np, pind, cm, cv, ct, crc, multi, o, (uint64_t *)nullptr); \
+        else hipLaunchKernelGGL((k_pooled_summary<PMAX, false>), dim3(cnt), dim3(256), 0, st, cnt, C, S, X, np, pind, cm, cv, ct, crc, multi, o, (uint64_t *)nullptr);       \
+    } while (0)
+    if (cs <= 1024) POOLED_IN_LDS(1024);
+    else if (cs <= 2048) POOLED_IN_LDS(2048);
+    else if (cs <= 4096) POOLED_IN_LDS(4096);
+    else if (cs <= 8192) POOLED_IN_LDS(8192);
+    else if (log_mode) hipLaunchKernelGGL((k_pooled_summary<0, true>), dim3(cnt < ws_groups ? cnt : ws_groups), dim3(256), 0, st, cnt, C, S, X, np, pind, cm, cv, ct, crc, multi, o, ws);
+    else hipLaunchKernelGGL((k_pooled_summary<0, false>), dim3(cnt < ws_groups ? cnt : ws_groups), dim3(256), 0, st, cnt, C, S, X, np, pind, cm, cv, ct, crc, multi, o, ws);
+#undef POOLED_IN_LDS
 }

@@ -491,6 +491,85 @@ def convergence_of_traces(traces, device=0):
     return dict(rhat=r, ess_bulk=eb, ess_tail=et)
 
 
+class PooledSummary:
+    """Posterior summary over the draws of ALL chains of a sampler (mmg_pooled_*): what Summary computes from one chain, from the
+    n_chains * trace_len pooled draws.  The series are those of Convergence (virtual isoforms simulated per chain); percentile_index are
+    positions in [0, n_chains * trace_len)."""
+
+    def __init__(self, sampler, virtual_id=(), virtual_scale=(), identical=(), genes=(), percentile_index=()):
+        from ._lib import SummaryDesc
+        self._lib = _lib.load()
+        vid = np.ascontiguousarray(virtual_id, np.uint64)
+        vsc = np.ascontiguousarray(virtual_scale, np.float64)
+        iptr, imem = _csr(identical)
+        gptr, gmem = _csr(genes)
+        pidx = np.ascontiguousarray(percentile_index, np.int32)
+        self.counts = [sampler.n, vid.size, len(identical), len(genes)]
+        self.np_ = pidx.size
+        self.n_chains = sampler.n_chains
+        d = SummaryDesc(0, vid.size, _ptr(vid), _ptr(vsc), len(identical), _ptr(iptr), _ptr(imem), len(genes), _ptr(gptr), _ptr(gmem),
+                        pidx.size, _ptr(pidx))
+        h = C.c_void_p()
+        check(self._lib.mmg_pooled_create(sampler._h, C.byref(d), C.byref(h)))
+        self._h = h
+
+    def series(self, kind):
+        """log_mean, var, tau, mcse2, rc and percentiles [series, percentile] of the pooled draws"""
+        c = self.counts[kind]
+        lm, var, tau, m2 = np.empty(c), np.empty(c), np.empty(c), np.empty(c)
+        rc = np.empty(c, np.int32)
+        pct = np.empty((c, self.np_))
+        check(self._lib.mmg_pooled_get(self._h, kind, _ptr(lm), _ptr(var), _ptr(tau), _ptr(m2), _ptr(rc), _ptr(pct)))
+        return dict(log_mean=lm, var=var, tau=tau, mcse2=m2, rc=rc, percentiles=pct)
+
+    def chain_series(self, kind, c):
+        """log_mean, var, tau and rc of chain c alone: the columns of Summary(sampler, chain=c)"""
+        cnt = self.counts[kind]
+        lm, var, tau = np.empty(cnt), np.empty(cnt), np.empty(cnt)
+        rc = np.empty(cnt, np.int32)
+        check(self._lib.mmg_pooled_get_chain(self._h, kind, int(c), _ptr(lm), _ptr(var), _ptr(tau), _ptr(rc)))
+        return dict(log_mean=lm, var=var, tau=tau, rc=rc)
+
+    def proportions(self, kind):
+        c = self.counts[kind]
+        mp, pm, ps = np.empty(c), np.empty(c), np.empty(c)
+        pct = np.empty((c, self.np_))
+        check(self._lib.mmg_pooled_get_proportions(self._h, kind, _ptr(mp), _ptr(pm), _ptr(ps), _ptr(pct)))
+        return dict(mean=mp, probit_mean=pm, probit_sd=ps, percentiles=pct)
+
+    def device_bytes(self):
+        b = C.c_uint64(0)
+        check(self._lib.mmg_pooled_device_bytes(self._h, C.byref(b)))
+        return b.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.mmg_pooled_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def pooled_of_traces(traces, percentile_index=(), device=0):
+    """mmg_pooled_of_traces: traces[c, s, i] is draw s of chain c of series i (shape (C, S, count)).  Returns a dict of log_mean, var, tau,
+    mcse2, rc and percentiles [series, percentile], the columns of PooledSummary.series."""
+    tr = np.ascontiguousarray(traces, np.float64)
+    if tr.ndim != 3:
+        raise ValueError("traces must have shape (chains, samples, series)")
+    nc, S, cnt = tr.shape
+    pidx = np.ascontiguousarray(percentile_index, np.int32)
+    lm, var, tau, m2 = np.empty(cnt), np.empty(cnt), np.empty(cnt), np.empty(cnt)
+    rc = np.empty(cnt, np.int32)
+    pct = np.empty((cnt, pidx.size))
+    check(_lib.load().mmg_pooled_of_traces(int(device), nc, S, cnt, _ptr(tr), pidx.size, _ptr(pidx), _ptr(lm), _ptr(var), _ptr(tau), _ptr(m2),
+                                           _ptr(rc), _ptr(pct)))
+    return dict(log_mean=lm, var=var, tau=tau, mcse2=m2, rc=rc, percentiles=pct)
+
+
 def em_shards_selftest(shards, mu0, sweeps):
     """mmg_selftest_em_shards: the sharded EM of mmg_group_em_create with all shards on one device (exchange by kernels).
     Returns (mu, loglik, repeated_passes)."""
@@ -520,7 +599,7 @@ def selftest_option(option, value):
 OPT = dict(sample_kernel=_lib.OPT_SAMPLE_KERNEL, force_idx64=_lib.OPT_FORCE_IDX64, sell_waves_per_cu=_lib.OPT_SELL_WAVES_PER_CU,
            em_kernel=_lib.OPT_EM_KERNEL, em_grid=_lib.OPT_EM_GRID, fuse_chains=_lib.OPT_FUSE_CHAINS, cnt_replicas=_lib.OPT_CNT_REPLICAS, group_fail=_lib.OPT_GROUP_FAIL, derive_order=_lib.OPT_DERIVE_ORDER,
            wire_check=_lib.OPT_WIRE_CHECK, bigk_per_wave=_lib.OPT_BIGK_PER_WAVE, bigk_side_stream=_lib.OPT_BIGK_SIDE_STREAM,
-           conv_slab=_lib.OPT_CONV_SLAB, contrast_slab=_lib.OPT_CONTRAST_SLAB)
+           conv_slab=_lib.OPT_CONV_SLAB, contrast_slab=_lib.OPT_CONTRAST_SLAB, pool_slab=_lib.OPT_POOL_SLAB)
 
 
 class options:
