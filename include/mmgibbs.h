@@ -83,7 +83,7 @@ extern "C" {
  *      owners' self tests (MMG_OPT_FAIL_ALLOC, mmg_selftest_live, mmg_selftest_sampler_events), the convergence diagnostics across
  *      chains (mmg_convergence_*, MMG_OPT_CONV_SLAB), mmdiff's chains (mmg_diff_chains_*) and the posterior assignment probabilities
  *      of the hits (mmg_assign_*, MMG_OPT_ASSIGN_WAVES), and the posterior summary over the draws of all chains (mmg_pooled_*,
- *      MMG_OPT_POOL_SLAB). */
+ *      MMG_OPT_POOL_SLAB), and the posterior correlation of pairs of transcripts (mmg_pairs_*, MMG_OPT_PAIRS_SLAB). */
 /* Layout.  The model does not care about the order of rows or the numbering of transcripts (src/mmseq.cpp:399-418 uses
  * first-seen order for both); the kernels do: they keep a window of consecutive transcripts in LDS and want the 64 rows of a
  * wave to have equal lengths.  mmg_problem_create therefore stores the rows in a CANONICAL order of its own (sorted on the
@@ -490,7 +490,8 @@ enum {
     MMG_OPT_ASSIGN_WAVES = 15,     /* v >= 1: at most v waves per launch of mmg_assign_run_* (several scratch chunks on small inputs)             */
     MMG_OPT_CONTRAST_SLAB = 16,    /* v >= 1: at most v contrasts per slab of mmg_contrast_create / _of_traces (slab edges on small inputs)      */
     MMG_OPT_POOL_SLAB = 17,        /* v >= 1: at most v series per slab of mmg_pooled_create / _of_traces (slab edges on small inputs)          */
-    MMG_OPT_COUNT_ = 18
+    MMG_OPT_PAIRS_SLAB = 18,       /* v >= 1: at most v pairs per slab of mmg_pairs_create / _of_traces (slab edges on small inputs)             */
+    MMG_OPT_COUNT_ = 19
 };
 int mmg_selftest_option(int option, int value);
 /* What the library holds: counts[3] = device buffers, streams, events (tests: every call gives back what it acquired). */
@@ -628,6 +629,34 @@ int mmg_contrast_get_rows(mmg_contrast *h, uint32_t first, uint32_t count, doubl
  * a power of two). */
 int mmg_contrast_device_bytes(mmg_contrast *h, uint64_t *bytes);
 void mmg_contrast_destroy(mmg_contrast *h);
+
+/* ---- the posterior correlation of transcripts that share reads -----------------------------------------------------------
+ * Which transcripts of a sample are confounded with which: for ordered pairs (a, b) of transcripts, a != b, from the S kept samples
+ * of one chain.  Per sample u = log x_a, v = log x_b, w = log(x_a + x_b) (the library's log).  Every sum over the samples runs in
+ * the order of a wave with one lane per sample (lane l adds its samples l, l + 64, ... ascending from 0.0, the 64 partial sums are
+ * folded by halving).  mean_a, mean_b, mean_sum = the sums of u, v, w over S; then with du = u - mean_a, dv = v - mean_b,
+ * dw = w - mean_sum: saa, sbb, sab, sss = the sums of du du, dv dv, du dv, dw dw (each product rounded, then added); n_gt = the
+ * number of samples with x_a > x_b.  Non-finite values propagate.  mean_a and saa depend on a alone: the same bits in every pair a is
+ * in, whatever the slab.  The caller derives cor = sab / (sqrt(saa) sqrt(sbb)), sd_a = sqrt(saa / (S - 1)), p_gt = n_gt / S.
+ * The same pair may occur twice, and a member may be in any number of pairs; the output order is the caller's pair order.
+ * tests/pairs_ref.py; no floating-point atomics: reruns are bit-identical.  Additive in ABI version 8. */
+typedef struct mmg_pairs mmg_pairs;
+/* Over the trace_len kept samples of `chain` of sampler s, a and b in the caller's numbering.  The sampler must hold a trace and be
+ * past its last kept sample (MMG_ERR_STATE otherwise).  MMG_ERR_ARG, with a message that names the pair: n_pairs == 0, a NULL array or
+ * output, a == b, a member >= n, a chain out of range.  Checked before any device work. */
+int mmg_pairs_create(mmg_sampler *s, int chain, uint64_t n_pairs, const uint32_t *a, const uint32_t *b, mmg_pairs **out);
+/* The same from host traces, series-major traces[member * S + s]. */
+int mmg_pairs_of_traces(int device, uint32_t S, uint32_t n_series, const double *traces, uint64_t n_pairs, const uint32_t *a, const uint32_t *b,
+                        mmg_pairs **out);
+/* Every output [n_pairs]; any pointer may be NULL.  The results are on the host from creation: no device work. */
+int mmg_pairs_get(mmg_pairs *h, double *mean_a, double *mean_b, double *mean_sum, double *saa, double *sbb, double *sab, double *sss, uint32_t *n_gt);
+/* The handle holds nothing on the device once it exists; this is what its creation held at its peak.  The pairs are cut into slabs
+ * of consecutive pairs: a slab ends in front of the pair that would bring its distinct members over max(2, 256 MiB / (16 S)) or its
+ * pairs over min(2^22, MMG_OPT_PAIRS_SLAB if set).  With Mx the largest number of distinct members of a slab and Px the largest
+ * number of pairs of one: 4 Mx of member list + 8 S Mx of centred logarithms + 16 Mx of member means and squares + 8 Px of slots +
+ * 60 Px of results; from a sampler also 8 S Mx of gathered traces, from host traces also 8 n_series S. */
+int mmg_pairs_device_bytes(mmg_pairs *h, uint64_t *bytes);
+void mmg_pairs_destroy(mmg_pairs *h);
 
 /* ---- mmdiff: Bayesian model selection between two linear models per feature -------------------------------------------
  * src/bms.cpp driven as src/mmdiff.cpp:744-866: per feature an independent MCMC over both models with pseudopriors, the model

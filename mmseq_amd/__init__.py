@@ -4,7 +4,9 @@ csrc/      HIP kernels (gfx950), the C ABI (include/mmgibbs.h) and the C++ host 
 gibbs.py   numpy-facing mirror of the C ABI (Problem, Sampler)
 assign.py  posterior assignment probability of every hit from a chain's trace (Assign)
 contrast.py posterior log-ratios between sets of transcripts of one sample from a chain's trace (Contrast)
+pairs.py   posterior correlation of pairs of transcripts that share reads from a chain's trace (Pairs)
 """
 from .assign import Assign  # noqa: F401
 from .contrast import Contrast  # noqa: F401
+from .pairs import Pairs  # noqa: F401
 from .gibbs import Problem, Sampler, device_count  # noqa: F401

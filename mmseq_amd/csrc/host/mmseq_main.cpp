@@ -42,6 +42,7 @@
 #include "hitsio.hpp"
 #include "huffenc.hpp"
 #include "numerics.hpp"
+#include "pairs_gen.hpp"
 #include "stage_timer.hpp"
 
 #ifndef MMSEQ_VERSION
@@ -87,6 +88,9 @@ static void printUsage(ostream &out)
         << "                     reads come from that transcript), .counts and .gene.counts (expected hits per feature; one device only)" << endl
         << "  -contrasts FILE    also write output_base.contrasts.mmseq: per line `name<TAB>id,id,...<TAB>id,id,...` of FILE the posterior of" << endl
         << "                     log(sum of mu over the first ids / sum over the second) from chain 0's samples (one device only)" << endl
+        << "  -pairs             also write output_base.pairs: for every two transcripts that share a hit set the posterior correlation of" << endl
+        << "                     their log mu, the sd of each and of the log of their sum, from chain 0's samples (one device only)" << endl
+        << "  -pairs_maxset INT  with -pairs: hit sets of more transcripts than this contribute no pairs (default: 16)" << endl
         << endl;
 }
 
@@ -108,7 +112,7 @@ static bool is_power_of_two(unsigned v) { return v != 0 && (v & (v - 1)) == 0; }
 
 // Command line: a table of options -- name, the variable it sets, how its value is read -- walked once.  Same flags, defaults,
 // messages and exit codes as the reference's loop at src/mmseq.cpp:206-276 (tests/test_cli.py holds them), plus -device / -gpus /
-// -chains / -em_one_device / -convergence / -pool / -assign / -contrasts of this build.
+// -chains / -em_one_device / -convergence / -pool / -assign / -contrasts / -pairs / -pairs_maxset of this build.
 struct CliOption {
     const char *name;
     enum Kind { REAL, INT, FLAG, LIST, TEXT, HELP, VERSION } kind;
@@ -137,6 +141,7 @@ using Convergence = Owned<mmg_convergence, mmg_convergence_destroy>;
 using PooledSummary = Owned<mmg_pooled, mmg_pooled_destroy>;
 using Assign = Owned<mmg_assign, mmg_assign_destroy>;
 using Contrast = Owned<mmg_contrast, mmg_contrast_destroy>;
+using Pairs = Owned<mmg_pairs, mmg_pairs_destroy>;
 // handles of one kind, one per device, destroyed together in order; reads as the array of raw handles the calls take
 template <class T, void (*Destroy)(T *)> struct HandleSet {
     vector<T *> h;
@@ -369,6 +374,8 @@ struct Options {
     int device = 0, gpus = 1, chains = 1;
     bool em_one_device = false, convergence = false, assign = false, pool = false;
     string contrasts_file;
+    bool pairs = false;
+    int pairs_maxset = 16;
     string hits_file, output_base;
 };
 
@@ -387,6 +394,7 @@ static Options parse_options(int argc, char **argv)
         {"-debug", CliOption::FLAG, &o.debug},        {"-em_one_device", CliOption::FLAG, &o.em_one_device},
         {"-convergence", CliOption::FLAG, &o.convergence}, {"-assign", CliOption::FLAG, &o.assign},
         {"-contrasts", CliOption::TEXT, &o.contrasts_file}, {"-pool", CliOption::FLAG, &o.pool},
+        {"-pairs", CliOption::FLAG, &o.pairs},        {"-pairs_maxset", CliOption::INT, &o.pairs_maxset},
         {"-h", CliOption::HELP, nullptr},           {"-help", CliOption::HELP, nullptr},       {"--help", CliOption::HELP, nullptr},
         {"-v", CliOption::VERSION, nullptr},        {"-version", CliOption::VERSION, nullptr}, {"--version", CliOption::VERSION, nullptr},
     };
@@ -437,6 +445,8 @@ static Options parse_options(int argc, char **argv)
     check(!(o.assign && o.gpus > 1), "Error: -assign reads the chain's trace on one device: it cannot be combined with -gpus > 1.\n");
     // the pass reads chain 0's trace where one sampler holds it
     check(!(!o.contrasts_file.empty() && o.gpus > 1), "Error: -contrasts reads the chain's trace on one device: it cannot be combined with -gpus > 1.\n");
+    check(!(o.pairs && o.gpus > 1), "Error: -pairs reads the chain's trace on one device: it cannot be combined with -gpus > 1.\n");
+    check(o.pairs_maxset >= 2, "Error: -pairs_maxset must be at least 2.\n");
     check(is_power_of_two((unsigned)trace_length), "Error: gibbs_iter/gibbs_ss must be a power of 2.\n");
     return o;
 }
@@ -1705,6 +1715,50 @@ static void write_contrasts(const Options &opt, const Header &hdr, const Hits &h
     if (!ofs) fatal("cannot write " + opt.output_base + ".contrasts.mmseq");
 }
 
+// ---- -pairs: every two transcripts that share a hit set of at most -pairs_maxset transcripts, in the header's transcript order
+//      (pairs_gen.hpp); generated before any device work, so that a refusal costs nothing
+static pairsgen::Result generate_pairs(const Options &opt, const Hits &hits)
+{
+    pairsgen::Result r;
+    if (!opt.pairs) return r;
+    string error;
+    if (!pairsgen::generate(hits.m(), hits.row_ptr.data(), hits.col_idx.data(), hits.k.data(), hits.obs2hdr.data(), opt.pairs_maxset, r, error)) fatal(error);
+    return r;
+}
+
+// ---- .pairs: per pair the posterior correlation of log mu_a and log mu_b, their sd, the sd and mean of log(mu_a + mu_b) and the
+//      share of samples with mu_a > mu_b over chain 0's trace_length kept samples -- the samples the .mmseq summaries are taken
+//      over -- on the device (mmg_pairs_*); cor, the sd and the share are derived here from the sums the device returns
+static void write_pairs(const Options &opt, const Header &hdr, const Hits &hits, const Chains &ch, const pairsgen::Result &gen)
+{
+    const size_t P = gen.pairs.size();
+    vector<double> mean_sum(P), saa(P), sbb(P), sab(P), sss(P);
+    vector<uint32_t> n_gt(P);
+    if (P) {
+        vector<int32_t> hdr2obs(hdr.transcriptList.size(), -1);
+        for (uint32_t t = 0; t < hits.n(); ++t) hdr2obs[hits.obs2hdr[t]] = (int32_t)t;
+        vector<uint32_t> a(P), b(P);
+        for (size_t p = 0; p < P; ++p) { a[p] = (uint32_t)hdr2obs[gen.pairs[p].a]; b[p] = (uint32_t)hdr2obs[gen.pairs[p].b]; }
+        mmg_pairs *raw = nullptr;
+        MMG_TRY(mmg_pairs_create(ch.smp(), 0, P, a.data(), b.data(), &raw));
+        Pairs owned(raw);
+        MMG_TRY(mmg_pairs_get(raw, nullptr, nullptr, mean_sum.data(), saa.data(), sbb.data(), sab.data(), sss.data(), n_gt.data()));
+    }
+    ofstream ofs((opt.output_base + ".pairs").c_str());
+    ofs << "# " << P << " pairs of transcripts that share a hit set of at most " << opt.pairs_maxset << " transcripts (-pairs_maxset); "
+        << gen.skipped_sets << " larger sets skipped with " << gen.skipped_hits << " hits" << endl;
+    ofs << "feature_a\tfeature_b\tshared_hits\tshared_sets\tcor\tsd_a\tsd_b\tsd_sum\tlog_mu_sum\tp_a_gt_b\n";
+    const double d = (double)trace_length - 1.0;
+    for (size_t p = 0; p < P; ++p) {
+        const pairsgen::Pair &g = gen.pairs[p];
+        ofs << hdr.transcriptList[g.a] << "\t" << hdr.transcriptList[g.b] << "\t" << g.shared_hits << "\t" << g.shared_sets << "\t"
+            << sab[p] / (sqrt(saa[p]) * sqrt(sbb[p])) << "\t" << sqrt(saa[p] / d) << "\t" << sqrt(sbb[p] / d) << "\t" << sqrt(sss[p] / d) << "\t"
+            << mean_sum[p] << "\t" << (double)n_gt[p] / (double)trace_length << "\n";
+    }
+    ofs.close();
+    if (!ofs) fatal("cannot write " + opt.output_base + ".pairs");
+}
+
 static void print_parameters(const Options &opt, int max_threads)
 {
     cout << "Running mmseq with parameters:\n"
@@ -1741,6 +1795,7 @@ static void print_output_files(const Options &opt)
              << "  " << opt.output_base << ".gene.counts" << endl
              << endl;
     if (!opt.contrasts_file.empty()) cout << "  " << opt.output_base << ".contrasts.mmseq" << endl << endl;
+    if (opt.pairs) cout << "  " << opt.output_base << ".pairs" << endl << endl;
     if (opt.debug) {
         cout << endl
              << "  " << opt.output_base << ".trace_em.gz" << endl
@@ -1783,6 +1838,7 @@ static int run(int argc, char **argv)
     const vector<double> l = effective_lengths(hdr, hits);
     const vector<vector<int>> counts_shared = opt.debug ? shared_counts(hits) : vector<vector<int>>();
     stage.mark("l");
+    const pairsgen::Result pair_list = generate_pairs(opt, hits);
     const Observed obs(hdr, hits);
     UniqueHits uh = count_unique_hits(hdr, hits, obs);
     stage.mark("unique hits (sets, genes)");
@@ -1831,8 +1887,13 @@ static int run(int argc, char **argv)
             stage.mark(opt.assign ? "assignment probabilities" : "write tables");
             write_contrasts(opt, hdr, hits, obs, uh, layout, ch, contrasts);
         }
+        const char *before_pairs = !opt.contrasts_file.empty() ? "contrasts" : opt.assign ? "assignment probabilities" : "write tables";
+        if (opt.pairs) {
+            stage.mark(before_pairs);
+            write_pairs(opt, hdr, hits, ch, pair_list);
+        }
         print_output_files(opt);
-        stage.mark(!opt.contrasts_file.empty() ? "contrasts" : opt.assign ? "assignment probabilities" : "write tables");
+        stage.mark(opt.pairs ? "pairs" : before_pairs);
         // (the writers fetch the last 1/64 of the rows behind the loop's last check: a failure there -- a HIP error in a row fetch --
         // would leave a valid but truncated trace file; it ends the run like any other)
         writers.finish();
