@@ -525,7 +525,9 @@ def test_sliced_ell_kernel_edge_rows(gpu, orc, with_k, keep_rows):
     mu0[::5] = 1e-300
     mu0[2000:2200] = 0.0                                       # rows whose every weight is zero: uniform pick
     mu0[3000:3100] = np.inf                                    # total not finite: uniform pick as well
-    with gpu.options(sample_kernel=2, sell_waves_per_cu=1):  # few workgroups: long tile ranges, several window slides each
+    # one wave per CU: the fewest workgroups the library allows -- still min(tiles, CUs) of them, 2 to 3 tiles each on a 256-CU
+    # device, a window slide in most (long ranges: tests/test_gpu_stream_ranges.py)
+    with gpu.options(sample_kernel=2, sell_waves_per_cu=1):
         prob, p = _dev(gpu, orc, p, keep_rows=keep_rows)
     # canonical order: nearly every tile runs from the register stream, the 300-hit row and the far row sit in slow tiles; kept
     # as given, the bands change from row to row and (almost) every 64-row tile is walked from the CSR by the same kernel
@@ -546,7 +548,8 @@ def test_sliced_ell_kernel_edge_rows(gpu, orc, with_k, keep_rows):
 def test_far_tiles_bit_exact(gpu, orc, with_k):
     """Rows with hits outside their window (reads that also hit a paralogue elsewhere in the transcriptome) sort by their HOME band
     and are walked from far tiles: window bytes, escapes, a far list per lane.  Far hits below and above the window, rows that are
-    mostly far, multiplicities up to the binomial chain, EM and fused chains (which still walk these rows from the CSR)."""
+    mostly far, multiplicities up to the binomial chain, EM and fused chains (the fused kernel gets the register-path tiles only:
+    the pair's far tiles go through the far-list instantiation of the single-chain kernel, one launch for both chains)."""
     rng = np.random.default_rng(21)
     p, _ = orc.synth_problem(R=60000, T=20000, avg_hits=9, seed=77, sort=False, far_fraction=0.3)
     rp, ci = p.row_ptr.astype(np.int64), p.col_idx.copy()
@@ -579,7 +582,7 @@ def test_far_tiles_bit_exact(gpu, orc, with_k):
         m2 = gpu.Sampler(prob, mu0, seed=5, n_chains=2, gibbs_iter=4, trace_len=4)
         m2.run(2)                                     # left alone, chains of a problem with far tiles run one per launch
         with gpu.options(fuse_chains=2):
-            m2.run(2)                                 # forced pairs: the fused kernel walks far tiles from the CSR
+            m2.run(2)                                 # forced pairs: the far tiles in the far-list launch beside the fused kernel
         for c in range(2):
             assert np.array_equal(m2.trace(c), orc.gibbs_keyed(qs, mu0, seed=5, chain=c, n_iter=4, trace_len=4)["trace"])
 
@@ -1161,7 +1164,9 @@ def _64bit_body(gpu, orc):
 @pytest.mark.parametrize("n_chains", [2, 4, 8, 11])
 def test_chains_of_one_sampler_equal_independent_single_chains(gpu, orc, n_chains, fuse):
     """Chains advanced together by the fused walk (k_sample_sell_multi: groups of 4 / 2 / 1 chains per launch) are bit-identical
-    to single-chain runs keyed with the same global chain index -- also across window slides, a far row and a 40-hit row."""
+    to single-chain runs keyed with the same global chain index -- also across a window slide, a far row and a 40-hit row.  (About 650
+    tiles in 2 x CUs ranges: a workgroup walks 1 or 2 tiles here, one trip of the pair kernel's loop; ranges of 24 tiles and more
+    are tests/test_gpu_stream_ranges.py.)"""
     p, mu0, _ = _mk(orc, 40000, 1500, 9, far_fraction=0.01)
     with gpu.options(fuse_chains=fuse, sell_waves_per_cu=2):
         prob, p = _dev(gpu, orc, p)

@@ -60,7 +60,7 @@ def one_case(seed, gpu, orc, verbose=True):
         mu0, uh = orc.start_values(pk)
         if rng.integers(0, 3) == 0: mu0[rng.integers(0, T, size=max(1, T // 20))] = 0.0
         if rng.integers(0, 4) == 0: mu0 *= 10.0 ** rng.uniform(-120, 120, size=T)
-        rid0 = int(rng.choice([0, 0, 12345, (1 << 32) - 100, (1 << 40) + 7]))    # shard offset: crosses 2^32 in the middle of a problem
+        rid0 = int(rng.choice([0, 0, 12345, (1 << 32) - 100, (1 << 33) - 40, (1 << 40) + 7]))    # shard offset: crosses 2^32 / 2^33 (the row stream's key changes) in the middle of a problem
         prob = gpu.Problem.from_csr(pk.row_ptr, pk.col_idx, pk.l, k=pk.k, row_id_base=rid0, keep_rows=keep_rows, tx_order=tx_order)
         d_rp, d_ci, d_k = prob.download(with_k=True)     # stored order: what the oracle replays
         pk = orc.Problem(d_rp, d_ci, pk.l, k=(d_k if k is not None else None))
