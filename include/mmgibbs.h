@@ -83,7 +83,8 @@ extern "C" {
  *      owners' self tests (MMG_OPT_FAIL_ALLOC, mmg_selftest_live, mmg_selftest_sampler_events), the convergence diagnostics across
  *      chains (mmg_convergence_*, MMG_OPT_CONV_SLAB), mmdiff's chains (mmg_diff_chains_*) and the posterior assignment probabilities
  *      of the hits (mmg_assign_*, MMG_OPT_ASSIGN_WAVES), and the posterior summary over the draws of all chains (mmg_pooled_*,
- *      MMG_OPT_POOL_SLAB), and the posterior correlation of pairs of transcripts (mmg_pairs_*, MMG_OPT_PAIRS_SLAB). */
+ *      MMG_OPT_POOL_SLAB), and the posterior correlation of pairs of transcripts (mmg_pairs_*, MMG_OPT_PAIRS_SLAB), and mmdiff's
+ *      effect summaries (mmg_diff_effects_*, mmg_effects_*). */
 /* Layout.  The model does not care about the order of rows or the numbering of transcripts (src/mmseq.cpp:399-418 uses
  * first-seen order for both); the kernels do: they keep a window of consecutive transcripts in LDS and want the 64 rows of a
  * wave to have equal lengths.  mmg_problem_create therefore stores the rows in a CANONICAL order of its own (sorted on the
@@ -716,6 +717,37 @@ int mmg_diff_get_pseudo(mmg_diff *h, double *out);
  * launch at phase index tt with `left` iterations to go at interval `every` covers *n iterations and rows [*first_row, *first_row + *rows). */
 int mmg_selftest_diff_trace_plan(uint32_t n_params, uint32_t n_features, uint32_t every_min, uint32_t max_rows, uint32_t tt, uint32_t left,
                                  uint32_t every, uint32_t *cap, uint32_t *first_row, uint32_t *rows, uint32_t *n);
+
+/* ---- mmdiff: effects (credible intervals of alpha, beta, eta, ... from the chain's own rows, on the device).  Additive in ABI
+ * version 8.  DESIGN.md section 10.3. ----
+ * Before mmg_diff_burnin: keep row r = the state after sampling iteration r * every (counted from the first sampling iteration, the
+ * rule of mmg_diff_trace_open) of every traced parameter and gamma in one buffer [max_rows][n_params][F] on the device.  Burn-in and
+ * tuning run as on a plain handle and the chain is the plain handle's, bit for bit; mmg_diff_sample may be called again and recording
+ * continues, and a call that would need a row beyond max_rows returns MMG_ERR_ARG before it launches anything.  mmg_diff_device_bytes
+ * grows by max_rows * n_params * F * 8 + 496 bytes (the launch descriptor): 2.3 GB at 20 000 features, 14 parameters and 1024 rows.
+ * MMG_ERR_ARG for every outside [1, 2^30], max_rows outside [1, 4096], or once the burn-in has run; MMG_ERR_STATE while
+ * mmg_diff_trace_open is open on the handle (and mmg_diff_trace_open returns it after this call) or when called twice. */
+int mmg_diff_effects_open(mmg_diff *h, uint32_t every, uint32_t max_rows);
+typedef struct mmg_effects mmg_effects;
+/* The summary of the rows recorded so far (MMG_ERR_STATE before the first sampling call, or without mmg_diff_effects_open); the
+ * handle's rows stay and sampling may go on.  Parameter s belongs to model m(s), the digit after its name's stem (alpha1: 1), and its
+ * draws for a feature are the rows whose own gamma equals m(s), in row order; n of them:
+ *   n[m][F]          the rows with gamma == m
+ *   mean, sd         [n_params - 1][F]: the sequential sum over n, and sqrt(sum (x - mean)^2 / (n - 1)), summed sequentially in a second pass
+ *   n_gt             [n_params - 1][F]: the draws with x > 0 (neither zero counts)
+ *   q                [n_params - 1][np][F]: the sorted draw at index floor(percentiles[j] / 100 * (n - 1) + 0.5)
+ * mean, sd and q are NaN for n == 0, sd for n == 1.  MMG_ERR_ARG, before any device work: a percentile outside [0, 100], np > 32, a
+ * NULL array, more than 4096 rows. */
+int mmg_diff_effects_summarize(mmg_diff *h, uint32_t np, const double *percentiles, mmg_effects **out);
+/* The same summary of host rows[S][P][F] (gamma = parameter P - 1, every value 0.0 or 1.0: MMG_ERR_ARG otherwise) with model_of[P - 1]
+ * (0 or 1) the model of each parameter.  MMG_ERR_ARG also for S == 0, S > 4096, P < 2, F == 0. */
+int mmg_effects_of_rows(int device, uint32_t S, uint32_t P, uint32_t F, const double *rows, const uint8_t *model_of, uint32_t np,
+                        const double *percentiles, mmg_effects **out);
+/* The results, which stay on the device until here; any pointer may be NULL. */
+int mmg_effects_get(mmg_effects *e, uint32_t *n, double *mean, double *sd, uint32_t *n_gt, double *q);
+/* what the results hold: 8 F + (P - 1) F (20 + 8 np) + 8 np + (P - 1) bytes */
+int mmg_effects_device_bytes(mmg_effects *e, uint64_t *bytes);
+void mmg_effects_destroy(mmg_effects *e);
 
 /* ---- mmdiff, polytomous: J alternatives against one model 0 on one handle ------------------------------------------------
  * Comparison j (0 <= j < J <= 16) is model 0 against alternative j, and its chain is bit for bit the chain of an mmg_diff handle

@@ -159,6 +159,13 @@ SYMBOLS = {
     "mmg_diff_get_tune_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmg_diff_get_pseudo": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mmg_selftest_diff_trace_plan": (C.c_int, [C.c_uint32] * 7 + [C.c_void_p] * 4),
+    "mmg_diff_effects_open": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    "mmg_diff_effects_summarize": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "mmg_effects_of_rows": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                      C.POINTER(C.c_void_p)]),
+    "mmg_effects_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmg_effects_device_bytes": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mmg_effects_destroy": (None, [C.c_void_p]),
     "mmg_diff_poly_create": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
                                        C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int,
                                        C.c_uint64, C.c_void_p]),

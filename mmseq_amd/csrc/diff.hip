@@ -35,6 +35,17 @@ struct DiffTracing {
     bool stopped = false;          // the sink returned non-zero: the chain is part way through a phase
 };
 
+// What mmg_diff_effects_open adds to a handle: one resident buffer of sampling rows and the descriptor of the launch that records
+// into it.  Nothing is copied out: mmg_diff_effects_summarize reads the rows where they are.
+struct DiffEffectsRows {
+    DevBuf<double> d_rows;         // [max_rows][P][F]
+    DevBuf<DiffTrace> d_q;         // [1] written ahead of every sampling launch, in stream order
+    DiffTrace q{};                 // the slot table; tr, tt0, cap are set per launch
+    int P = 0;                     // traced parameters, gamma (the last one) included
+    uint32_t every = 1, max_rows = 0;
+    std::vector<uint8_t> model_of; // [P - 1] the model of each traced parameter
+};
+
 // Members are destroyed in reverse declaration order: the destructor waits for the streams, then the buffers go, and `st` last.
 struct mmg_diff {
     DevStream st;
@@ -48,6 +59,7 @@ struct mmg_diff {
     bool burnt = false;
     uint64_t device_bytes = 0;
     std::unique_ptr<DiffTracing> tr;
+    std::unique_ptr<DiffEffectsRows> fx;
     ~mmg_diff()
     {
         if (st) (void)hipStreamSynchronize(st.get());
@@ -225,14 +237,15 @@ extern "C" int mmg_diff_create(int device, uint32_t F, uint32_t N, const double 
 static_assert(sizeof(DiffTrace) == 496, "mmg_diff_device_bytes with tracing open is documented with this size (include/mmgibbs.h)");
 constexpr uint64_t DF_TRACE_BUF_BYTES = 64u << 20;   // the most one row buffer takes (Traces), one row at least
 
-// the traced parameters in the order of BMS::initialise_streams: their names (if asked for) and state slots; the count
-static int df_trace_table(const mmg_diff *h, std::vector<std::string> *names, int *slot)
+// the traced parameters in the order of BMS::initialise_streams: their names, state slots and models (each if asked for); the count
+static int df_trace_table(const mmg_diff *h, std::vector<std::string> *names, int *slot, std::vector<uint8_t> *model = nullptr)
 {
     const DiffParams &p = h->p;
     int n = 0;
     auto add = [&](const char *stem, int mi, int idx, int o) {
         if (names) names->push_back(std::string(stem) + std::to_string(mi) + (idx < 0 ? std::string() : "_" + std::to_string(idx)));
         if (slot) slot[n] = o;
+        if (model) model->push_back((uint8_t)mi);
         ++n;
     };
     for (int mi = 0; mi < 2; ++mi) add("alpha", mi, -1, p.m[mi].alpha);
@@ -285,6 +298,7 @@ extern "C" int mmg_diff_trace_open(mmg_diff *h, uint32_t every_burnin, uint32_t 
     if (!h || !sink) return fail(MMG_ERR_ARG, "NULL argument");
     if (h->burnt) return fail(MMG_ERR_ARG, "mmg_diff_trace_open after the burn-in has started");
     if (h->tr) return fail(MMG_ERR_STATE, "tracing is open already");
+    if (h->fx) return fail(MMG_ERR_STATE, "mmg_diff_effects_open was called on this handle: traces and effects exclude each other");
     std::unique_ptr<DiffTracing> T(new DiffTracing());
     T->P = df_trace_table(h, nullptr, T->q.slot);
     T->every[0] = every_burnin; T->every[1] = every_sample;
@@ -367,6 +381,68 @@ extern "C" int mmg_selftest_diff_trace_plan(uint32_t n_params, uint32_t n_featur
     *cap = df_trace_cap(n_params, n_features, every_min, DF_CHUNK, DF_TRACE_BUF_BYTES, max_rows);
     *n = df_trace_plan(tt, left, every, *cap, DF_CHUNK, first_row, rows);
     return MMG_OK;
+}
+
+// ---- effects: sampling rows kept on the device ---------------------------------------------------------
+extern "C" int mmg_diff_effects_open(mmg_diff *h, uint32_t every, uint32_t max_rows)
+{
+    if (every == 0 || every > DF_TRACE_EVERY_MAX) return fail(MMG_ERR_ARG, "the thinning interval must be at least 1 and at most 1073741824");
+    if (max_rows == 0 || max_rows > 4096) return fail(MMG_ERR_ARG, "max_rows must be between 1 and 4096");
+    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
+    if (h->burnt) return fail(MMG_ERR_ARG, "mmg_diff_effects_open after the burn-in has started");
+    if (h->tr) return fail(MMG_ERR_STATE, "tracing is open on this handle: traces and effects exclude each other");
+    if (h->fx) return fail(MMG_ERR_STATE, "effects are open already");
+    std::unique_ptr<DiffEffectsRows> X(new DiffEffectsRows());
+    X->P = df_trace_table(h, nullptr, X->q.slot, &X->model_of);
+    X->every = every; X->max_rows = max_rows;
+    X->q.P = X->P; X->q.every = (int)every;
+    HIP_TRY(hipSetDevice(h->device));
+    const uint64_t count = (uint64_t)max_rows * X->P * h->F;
+    HIP_TRY(X->d_rows.alloc(count));
+    HIP_TRY(X->d_q.alloc(1));
+    h->device_bytes += count * 8 + sizeof(DiffTrace);
+    h->fx = std::move(X);
+    return MMG_OK;
+}
+
+// iters sampling iterations from sampling index tt_first with rows recorded into the resident buffer: the launches of the untraced
+// loop, k_df_run_traced in place of k_df_run.  The launch at index tt starts at row ceil(tt / every) and may fill the rest of the buffer.
+static int df_sample_effects(mmg_diff *h, uint32_t it_first, uint32_t t_first, uint32_t tt_first, uint32_t iters)
+{
+    DiffEffectsRows &X = *h->fx;
+    // (indices below 2^30 and intervals up to 2^30: the kernel's tt + every - 1 stays inside int)
+    if ((uint64_t)tt_first + iters > (1u << 30)) return fail(MMG_ERR_ARG, "a recorded sampling phase takes at most 1073741824 iterations");
+    if (((uint64_t)tt_first + iters + X.every - 1) / X.every > X.max_rows)
+        return fail(MMG_ERR_ARG, "these iterations need more rows than mmg_diff_effects_open reserved (max_rows)");
+    const size_t rowlen = (size_t)X.P * h->F;
+    // the descriptors of this call's launches: sources of asynchronous copies, alive until the caller has synchronised
+    std::vector<DiffTrace> q((iters + DF_CHUNK - 1) / DF_CHUNK, X.q);
+    size_t i = 0;
+    for (uint32_t j = 0; j < iters; j += DF_CHUNK, ++i) {
+        const uint32_t n = iters - j < DF_CHUNK ? iters - j : DF_CHUNK, tt = tt_first + j;
+        const uint32_t row0 = (uint32_t)(((uint64_t)tt + X.every - 1) / X.every);   // <= max_rows
+        q[i].tr = X.d_rows.get() + (size_t)row0 * rowlen;
+        q[i].tt0 = (int)tt; q[i].cap = (int)(X.max_rows - row0);
+        HIP_TRY(hipMemcpyAsync(X.d_q.get(), &q[i], sizeof(DiffTrace), hipMemcpyHostToDevice, h->st.get()));
+        hipLaunchKernelGGL(k_df_run_traced, dim3(df_blocks(h->F)), dim3(DF_BLOCK), 0, h->st.get(), h->p, it_first + j, (int)(t_first + j), (int)n, 2, 0,
+                           (const DiffTrace *)X.d_q.get());
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(h->st.get()));
+    return MMG_OK;
+}
+
+extern "C" int mmg_diff_effects_summarize(mmg_diff *h, uint32_t np, const double *percentiles, mmg_effects **out)
+{
+    if (!h || !out) return fail(MMG_ERR_ARG, "NULL argument");
+    *out = nullptr;
+    if (!h->fx) return fail(MMG_ERR_STATE, "mmg_diff_effects_summarize without mmg_diff_effects_open");
+    if (!h->sampled) return fail(MMG_ERR_STATE, "mmg_diff_effects_summarize before a sampling row exists");
+    const DiffEffectsRows &X = *h->fx;
+    const uint32_t S = (uint32_t)(((uint64_t)h->sampled + X.every - 1) / X.every);
+    const int rc = effects_check(S, (uint32_t)X.P, np, percentiles);
+    if (rc) return rc;
+    return effects_of_device_rows(h->device, S, (uint32_t)X.P, h->F, X.d_rows.get(), X.model_of.data(), np, percentiles, out);
 }
 
 extern "C" int mmg_diff_get_tune_state(mmg_diff *h, double *mean_lo, double *logitp)
@@ -460,6 +536,9 @@ extern "C" int mmg_diff_sample(mmg_diff *h, uint32_t iters)
     const uint32_t t_first = h->batches * DF_BATCH + h->sampled;
     if (h->tr) {
         const int rc = df_run_traced(h, 1, h->burnin + t_first, t_first, h->sampled, iters);
+        if (rc) return rc;
+    } else if (h->fx) {
+        const int rc = df_sample_effects(h, h->burnin + t_first, t_first, h->sampled, iters);
         if (rc) return rc;
     } else {
         for (uint32_t j = 0; j < iters; j += DF_CHUNK) {

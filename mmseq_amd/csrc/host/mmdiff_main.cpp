@@ -12,6 +12,9 @@
 // run_chains and DESIGN.md section 10.2.
 //
 // -traces DIR writes the reference's MCMC trace files (its -tracedir): TraceWriter below.
+//
+// -effects FILE keeps thinned sampling rows on the device and writes their per-feature summaries (mean, sd, P(> 0), percentiles of
+// every parameter under its own model): write_effects below and DESIGN.md section 10.3.
 #include <algorithm>
 #include <atomic>
 #include <cfloat>
@@ -103,6 +106,13 @@ void printUsage(ostream &out)
         << "  -traces STRING    directory in which to save MCMC traces, as the reference's -tracedir writes them: <param>-burnin and" << endl
         << "                    <param> (1024 lines each, one value per feature), logitp, meanLO, pseudo; sigar<model>.txt is not" << endl
         << "                    written; not with -chains or repeated -m (default: \"\" (do not write traces))" << endl
+        << "  -effects STRING   file for the effects: per feature n0, n1 (the kept sampling rows under each model) and, for every parameter" << endl
+        << "                    its model has, <name>_mean, <name>_sd, <name>_p_gt0 and <name>_q<p> per percentile, over the rows" << endl
+        << "                    whose own gamma is the parameter's model; the rows stay on the device (8 bytes x rows x parameters" << endl
+        << "                    x features); not with -traces, -chains, repeated -m or -polyclass (default: \"\" (no effects))" << endl
+        << "  -effects_every INT  with -effects: keep every INT-th sampling iteration; iter / INT rows, rounded up, at most 4096" << endl
+        << "                    (default: max(1, iter / 1024))" << endl
+        << "  -effects_percentiles P1,P2,...  with -effects: up to 32 percentiles in [0, 100] (default: 2.5,50,97.5)" << endl
         << "  -useprops         run on isoform/gene proportions instead of expression" << endl
         << "  -permute          run on permuted dataset (a keyed shuffle per feature); combine with non-permuted results to obtain q-values" << endl
         << "  -p FLOAT          prior probability of the second model (default: 0.1)" << endl
@@ -1025,6 +1035,83 @@ private:
     }
 };
 
+// ---- -effects FILE ---------------------------------------------------------------------------------------------------------------
+#define MAXEFFECTROWS 4096
+#define MAXPERCENTILES 32
+
+// -effects_percentiles: a comma-separated list of 1 to 32 finite values in [0, 100]
+vector<double> parse_percentiles(const string &text)
+{
+    const string msg = "Error: -effects_percentiles takes a comma-separated list of 1 to " + to_string(MAXPERCENTILES) + " percentiles in [0, 100].";
+    vector<double> pct;
+    size_t a = 0;
+    while (true) {
+        const size_t b = text.find(',', a);
+        const string tok = text.substr(a, b == string::npos ? string::npos : b - a);
+        char *end = NULL;
+        const double v = strtod(tok.c_str(), &end);
+        if (tok.empty() || *end != '\0' || !std::isfinite(v) || v < 0 || v > 100) die(msg);
+        pct.push_back(v);
+        if (b == string::npos) break;
+        a = b + 1;
+    }
+    if (pct.size() > MAXPERCENTILES) die(msg);
+    return pct;
+}
+
+// %.9g, NaN as "nan"
+string fmt9(double x)
+{
+    if (std::isnan(x)) return "nan";
+    char buf[64];
+    snprintf(buf, sizeof buf, "%.9g", x);
+    return buf;
+}
+
+// whether the model of traced parameter `name` (alpha<m>, beta<m>_k, eta<m>_l, lambda<m>_l, sigmasq<m>_c, rho<m>) has it
+bool model_has(const string &name, bool fixalpha, bool Mnil, const bool Pnil[2])
+{
+    const string stem = name.substr(0, name.find('_'));
+    const int m = stem.back() - '0';
+    const string kind = stem.substr(0, stem.size() - 1);
+    if (kind == "alpha") return !fixalpha;
+    if (kind == "beta") return !Mnil;
+    if (kind == "eta" || kind == "lambda") return !Pnil[m];
+    return true;
+}
+
+// The effects table: a line per feature, in the order of the stdout table.  names: the traced parameters without gamma.
+void write_effects(const string &file, const vector<string> &features, const vector<string> &names, const vector<double> &pct, bool fixalpha,
+                   bool Mnil, const bool Pnil[2], const vector<uint32_t> &n, const vector<double> &mean, const vector<double> &sd,
+                   const vector<uint32_t> &n_gt, const vector<double> &q)
+{
+    FILE *fp = fopen(file.c_str(), "w");
+    if (!fp) die("Error: couldn't create " + file);
+    const size_t F = features.size(), np = pct.size();
+    vector<size_t> cols;
+    for (size_t s = 0; s < names.size(); ++s)
+        if (model_has(names[s], fixalpha, Mnil, Pnil)) cols.push_back(s);
+    string out = "feature_id\tn0\tn1";
+    for (size_t s : cols) {
+        out += "\t" + names[s] + "_mean\t" + names[s] + "_sd\t" + names[s] + "_p_gt0";
+        for (double p : pct) out += "\t" + names[s] + "_q" + fmt9(p);
+    }
+    out += "\n";
+    bool ok = fputs(out.c_str(), fp) >= 0;
+    for (size_t f = 0; f < F && ok; ++f) {
+        out = features[f] + "\t" + to_string(n[f]) + "\t" + to_string(n[F + f]);
+        for (size_t s : cols) {
+            const int m = names[s].substr(0, names[s].find('_')).back() - '0';
+            const double nm = (double)n[(size_t)m * F + f];
+            out += "\t" + fmt9(mean[s * F + f]) + "\t" + fmt9(sd[s * F + f]) + "\t" + fmt9((double)n_gt[s * F + f] / nm);
+            for (size_t j = 0; j < np; ++j) out += "\t" + fmt9(q[(s * np + j) * F + f]);
+        }
+        out += "\n";
+        ok = fputs(out.c_str(), fp) >= 0;
+    }
+    if (fclose(fp) != 0 || !ok) die("Error: couldn't write " + file);
+}
+
 } // namespace
 
 int main(int argc, char **argv)
@@ -1032,7 +1119,9 @@ int main(int argc, char **argv)
     string matrices_file = "";
     vector<string> matrices_files;   // every -m; more than one: the polytomous run
     bool polyclass_mode = false, prior_given = false, polyout_given = false, chains_given = false, chainout_given = false;
-    string prior_text, polyout, chainout, traces;
+    string prior_text, polyout, chainout, traces, effects, effects_pct_text = "2.5,50,97.5";
+    bool effects_every_given = false, effects_pct_given = false;
+    long effects_every = 0;
     int chains = 1;
     double p = 0.1, d = 1.4, s = 2.0;
     int burnin = 8192, mcmciters = 16384, seed = 1234, range_start = -1, range_end = -1;
@@ -1052,6 +1141,19 @@ int main(int argc, char **argv)
         } else if (a0 == "-traces") {
             traces = take();
             if (traces.empty()) die("Error: -traces needs a directory.");
+        } else if (a0 == "-effects") {
+            effects = take();
+            if (effects.empty()) die("Error: -effects needs a file name.");
+        } else if (a0 == "-effects_every") {
+            const string v = take();
+            char *end = NULL;
+            effects_every = strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end != '\0' || effects_every < 1 || effects_every > (1L << 30))
+                die("Error: -effects_every takes an integer between 1 and 1073741824.");
+            effects_every_given = true;
+        } else if (a0 == "-effects_percentiles") {
+            effects_pct_text = take();
+            effects_pct_given = true;
         } else if (a0 == "-m" || a0 == "-de") {
             arguments.erase(arguments.begin());
             // -m FILE -m FILE ...: consecutive pairs are one polytomous run
@@ -1182,6 +1284,14 @@ int main(int argc, char **argv)
         usage_error("Error: -chains cannot be combined with more than one -m or with -polyclass (chains of several alternatives are left for later).");
     if (!traces.empty() && (chains_given || poly_run || polyclass_mode))
         usage_error("Error: -traces cannot be combined with -chains, more than one -m or -polyclass (traces of several chains or alternatives are left for later).");
+    if ((effects_every_given || effects_pct_given) && effects.empty())
+        usage_error("Error: -effects_every and -effects_percentiles need -effects.");
+    if (!effects.empty() && !traces.empty())
+        usage_error("Error: -effects cannot be combined with -traces (the handle records rows for one of them).");
+    if (!effects.empty() && (chains_given || poly_run || polyclass_mode))
+        usage_error("Error: -effects cannot be combined with -chains, more than one -m or -polyclass (effects of several chains or alternatives are left for later).");
+    vector<double> effects_pct;
+    if (!effects.empty()) effects_pct = parse_percentiles(effects_pct_text);
     if (polyclass_mode) {
         // host only: no device is looked for
         const size_t J = arguments.size();
@@ -1202,6 +1312,15 @@ int main(int argc, char **argv)
     if (useprops) {
         cerr << "Using proportions, therefore disabling normalisation.\n";
         normalise = false;
+    }
+    uint32_t effects_rows = 0;
+    if (!effects.empty()) {
+        if (!effects_every_given) effects_every = max(1, mcmciters / 1024);
+        const long rows = ((long)mcmciters + effects_every - 1) / effects_every;
+        if (rows > MAXEFFECTROWS)
+            die("Error: -effects keeps at most " + to_string(MAXEFFECTROWS) + " rows: -iter " + to_string(mcmciters) + " with -effects_every "
+                + to_string(effects_every) + " needs " + to_string(rows) + ".");
+        effects_rows = (uint32_t)rows;
     }
     if (matrices_file == "" && simple_de.size() == 0) die("Error: either -de or -m must be specified");
     if (matrices_file == "" && simple_de.size() == 1) die("Error: -de requires at least two groupings");
@@ -1276,6 +1395,7 @@ int main(int argc, char **argv)
         // a line per burnin / OUTLEN burn-in and per mcmciters / OUTLEN sampling iterations (src/mmdiff.cpp:733-734, 837)
         MMG_CHECK(mmg_diff_trace_open(h, (uint32_t)(burnin / OUTLEN), (uint32_t)(mcmciters / OUTLEN), TraceWriter::sink, tw.get()));
     }
+    if (!effects.empty()) MMG_CHECK(mmg_diff_effects_open(h, (uint32_t)effects_every, effects_rows));
     cerr << "BURNIN (" << burnin << " iterations)...";
     MMG_CHECK(mmg_diff_burnin(h, (uint32_t)burnin));
     cerr << "\nSetting pseudopriors...done.\n";
@@ -1311,6 +1431,25 @@ int main(int argc, char **argv)
     cerr << "\nDONE MCMC\n";
     DiffResults r(F, D);
     MMG_CHECK(mmg_diff_get_results(h, r.gm.data(), r.logitp.data(), r.alpha.data(), r.beta.data(), r.eta.data()));
+    if (!effects.empty()) {
+        uint32_t P = 0;
+        MMG_CHECK(mmg_diff_trace_layout(h, &P, NULL));
+        vector<string> names(P - 1);   // gamma, the last one, has no effects of its own
+        for (uint32_t i = 0; i + 1 < P; ++i) {
+            char name[32];
+            MMG_CHECK(mmg_diff_trace_name(h, i, name, sizeof name));
+            names[i] = name;
+        }
+        const size_t Q = P - 1, np = effects_pct.size();
+        mmg_effects *fx = nullptr;
+        MMG_CHECK(mmg_diff_effects_summarize(h, (uint32_t)np, effects_pct.data(), &fx));
+        vector<uint32_t> n(2 * F), n_gt(Q * F);
+        vector<double> mean(Q * F), sd(Q * F), q(Q * np * F);
+        MMG_CHECK(mmg_effects_get(fx, n.data(), mean.data(), sd.data(), n_gt.data(), q.data()));
+        mmg_effects_destroy(fx);
+        write_effects(effects, features, names, effects_pct, fixalpha, Mnil, Pnil, n, mean, sd, n_gt, q);
+        cerr << "Wrote the effects of " << effects_rows << " rows to " << effects << "\n";
+    }
     mmg_diff_destroy(h);
     if (tw) {
         if (!tw->finish()) die("Error: couldn't write the trace files in " + traces);

@@ -299,6 +299,13 @@ int em_create_sharded(const mmg_problem *const *shards, int n_shards, const doub
 void em_exchange_buffers(mmg_em *e, int what, void **ptr, size_t *count);
 int em_device(const mmg_em *e);
 
+// mmdiff's effect summaries (diff_effects.hip).  effects_check: the argument rules that mmg_effects_of_rows and
+// mmg_diff_effects_summarize share, before any device work.  effects_of_device_rows: the summary of rows[S][P][F] that are on `device`
+// already (checked, gamma 0.0 / 1.0, model_of[P - 1] on the host); the rows are free again when it returns.
+int effects_check(uint32_t S, uint32_t P, uint32_t np, const double *percentiles);
+int effects_of_device_rows(int device, uint32_t S, uint32_t P, uint32_t F, const double *d_rows, const uint8_t *model_of, uint32_t np,
+                           const double *percentiles, mmg_effects **out);
+
 int require_device(int device);
 void weighted_chunks(const std::vector<uint64_t> &cum, uint64_t grid, std::vector<uint64_t> &chunk);
 void weighted_chunks_tapered(const std::vector<uint64_t> &cum, uint64_t grid, uint64_t resident, std::vector<uint64_t> &chunk);

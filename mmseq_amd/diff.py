@@ -121,6 +121,19 @@ class Diff:
         P, F = len(self.trace_names()), self.F
         return tuple(np.concatenate(r) if r else np.empty((0, P - 1 + ph, F)) for ph, r in enumerate(self._rows))
 
+    def open_effects(self, every, max_rows):
+        """Before `burnin`: keep every every-th sampling iteration's row (max_rows at most, up to 4096) on the device for `effects`.
+        Not together with `open_traces`."""
+        check(self._lib.mmg_diff_effects_open(self._h, int(every), int(max_rows)))
+
+    def effects(self, percentiles=(2.5, 50.0, 97.5)):
+        """The summary of the rows recorded so far: `effects_of_rows` of them with the models of `trace_names()`."""
+        pct = np.ascontiguousarray(percentiles, np.float64).ravel()
+        e = C.c_void_p()
+        check(self._lib.mmg_diff_effects_summarize(self._h, len(pct), _ptr(pct), C.byref(e)))
+        names = self.trace_names()[:-1]
+        return _effects_out(self._lib, e, names, self.F, pct)
+
     def _run(self, rc):
         """check(rc); an exception of the caller's sink, which stopped the run, is raised in place of the library's error."""
         ex, self._sink_error = getattr(self, "_sink_error", None), None
@@ -152,6 +165,39 @@ class Diff:
             self.close()
         except Exception:
             pass
+
+
+def _effects_out(lib, e, names, F, pct):
+    """The results of an mmg_effects handle as a dict of arrays, and the handle destroyed."""
+    Q, npct = len(names), len(pct)
+    out = dict(names=list(names), percentiles=pct.copy(), n=np.empty((2, F), np.uint32), mean=np.empty((Q, F)), sd=np.empty((Q, F)),
+               n_gt=np.empty((Q, F), np.uint32), q=np.empty((Q, npct, F)))
+    try:
+        check(lib.mmg_effects_get(e, *(_ptr(out[k]) for k in ("n", "mean", "sd", "n_gt", "q"))))
+        b = C.c_uint64()
+        check(lib.mmg_effects_device_bytes(e, C.byref(b)))
+        out["device_bytes"] = b.value
+    finally:
+        lib.mmg_effects_destroy(e)
+    return out
+
+
+def effects_of_rows(rows, model_of, percentiles=(2.5, 50.0, 97.5), names=None, device=0):
+    """Effect summaries of rows (S, P, F), gamma (0.0 / 1.0) as parameter P - 1, model_of (P - 1,) the model of each parameter: per
+    parameter and feature, over the rows whose own gamma equals the parameter's model, `n` (2, F), `mean`, `sd`, `n_gt` (P - 1, F)
+    and `q` (P - 1, len(percentiles), F), the sorted draw at floor(p / 100 * (n - 1) + 0.5).  tests/mmdiff_effects_ref.py restates it."""
+    lib = _lib.load()
+    rows = np.ascontiguousarray(rows, np.float64)
+    if rows.ndim != 3:
+        raise ValueError("rows must be (S, P, F)")
+    S, P, F = rows.shape
+    model_of = np.ascontiguousarray(model_of, np.uint8).ravel()
+    if len(model_of) != max(P - 1, 0):
+        raise ValueError("model_of must have P - 1 entries")
+    pct = np.ascontiguousarray(percentiles, np.float64).ravel()
+    e = C.c_void_p()
+    check(lib.mmg_effects_of_rows(device, S, P, F, _ptr(rows), _ptr(model_of), len(pct), _ptr(pct), C.byref(e)))
+    return _effects_out(lib, e, names if names is not None else ["param%d" % s for s in range(P - 1)], F, pct)
 
 
 class DiffPoly:
