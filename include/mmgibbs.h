@@ -84,7 +84,8 @@ extern "C" {
  *      chains (mmg_convergence_*, MMG_OPT_CONV_SLAB), mmdiff's chains (mmg_diff_chains_*) and the posterior assignment probabilities
  *      of the hits (mmg_assign_*, MMG_OPT_ASSIGN_WAVES), and the posterior summary over the draws of all chains (mmg_pooled_*,
  *      MMG_OPT_POOL_SLAB), and the posterior correlation of pairs of transcripts (mmg_pairs_*, MMG_OPT_PAIRS_SLAB), and mmdiff's
- *      effect summaries (mmg_diff_effects_*, mmg_effects_*). */
+ *      effect summaries (mmg_diff_effects_*, mmg_effects_*), and mmdiff's permutation null with its q-values (mmg_diff_perm_*,
+ *      mmg_qvalues). */
 /* Layout.  The model does not care about the order of rows or the numbering of transcripts (src/mmseq.cpp:399-418 uses
  * first-seen order for both); the kernels do: they keep a window of consecutive transcripts in LDS and want the 64 rows of a
  * wave to have equal lengths.  mmg_problem_create therefore stores the rows in a CANONICAL order of its own (sorted on the
@@ -808,6 +809,49 @@ int mmg_diff_chains_info(mmg_diff_chains *h, uint32_t c, int32_t *flags, uint32_
  * section 10) */
 int mmg_diff_chains_device_bytes(mmg_diff_chains *h, uint64_t *bytes);
 void mmg_diff_chains_destroy(mmg_diff_chains *h);
+
+/* ---- mmdiff, a permutation null: the data and B shuffled copies of it on one handle, q-values --------------------------------
+ * The handle holds R = n_perm + 1 replicas (1 <= n_perm <= 31: the tuning launch takes a 32-bit mask of replicas).  Replica 0 is
+ * the data as given; replica b >= 1 is the data with every feature's samples shuffled on the device: a Fisher-Yates on the
+ * replica's own column, for j = N - 1 .. 1: k = min((size_t)(u (j + 1)), j), entries j and k of y and e^2 swapped, u the next
+ * uniform of SeqStream(Stream(seed, b, TAG_DIFF_PERM, feature, 0)).  The stream key is (seed >> 32) ^ chain ^ (tag << 24), so that
+ * is the shuffle mmdiff -permute applies with the seed seed ^ ((uint64_t)b << 32), and replica b draws its chain from the streams
+ * (seed, b, TAG_DIFF, ...): replica b is bit for bit the mmg_diff handle created from that -permute data with the seed
+ * seed ^ ((uint64_t)b << 32) and driven the same way; replica 0 is the handle of mmg_diff_create.  Every replica has its own y, e^2,
+ * state block and tuning state; M, P0, P1 and the classes are held once; every launch covers all replicas, and each replica tunes on
+ * its own, as a chain of mmg_diff_chains_* does.  Additive in ABI version 8. */
+typedef struct mmg_diff_perm mmg_diff_perm;
+int mmg_diff_perm_create(int device, uint32_t n_features, uint32_t n_samples, const double *y, const double *e, uint32_t K, const double *M,
+                         uint32_t L0, const double *P0, uint32_t L1, const double *P1, const int32_t *C, double d, double s, double pdash,
+                         int fixalpha, uint64_t seed, uint32_t n_perm, mmg_diff_perm **out);
+/* iters: a positive multiple of 1024, as for mmg_diff_chains_burnin */
+int mmg_diff_perm_burnin(mmg_diff_perm *h, uint32_t iters);
+/* One tuning batch for every replica that has not ended tuning: untuned[R], ended[R] (may be NULL) as mmg_diff_poly_tune_batch fills
+ * them per comparison.  mmg_diff_perm_sample starts replica b at its own index, burnin + 128 * (its batches). */
+int mmg_diff_perm_tune_batch(mmg_diff_perm *h, uint32_t *untuned, int32_t *ended);
+int mmg_diff_perm_sample(mmg_diff_perm *h, uint32_t iters);
+/* replica b's results, laid out as mmg_diff_get_results lays them out; MMG_ERR_ARG for b >= R */
+int mmg_diff_perm_get_results(mmg_diff_perm *h, uint32_t b, double *gamma_mean, double *logitp, double *alpha, double *beta, double *eta);
+/* replica b: flags[3] = (M nil, P0 nil, P1 nil), n_classes[2], its tuning batches, whether it has ended tuning; any pointer may be NULL */
+int mmg_diff_perm_info(mmg_diff_perm *h, uint32_t b, int32_t *flags, uint32_t *n_classes, uint32_t *batches, int32_t *ended);
+/* After sampling (MMG_ERR_STATE before): per replica and feature the log Bayes factor T = log(g) - log(1 - g) - logit p', g the mean
+ * of gamma (the library's own log; -inf for g == 0, +inf for g == 1, NaN for a logit p' that is not finite), and mmg_qvalues of
+ * replica 0's T against the pooled T of replicas 1 .. B.  Everything stays on the device; sampling further makes it stale. */
+int mmg_diff_perm_qvalues(mmg_diff_perm *h);
+/* stat[R][F], null_ge[F], q[F] of the last mmg_diff_perm_qvalues (MMG_ERR_STATE without one); any pointer may be NULL */
+int mmg_diff_perm_get_qvalues(mmg_diff_perm *h, double *stat, uint64_t *null_ge, double *q);
+/* 8 (2 R F N + N K + N L0 + N L1 + R F (nslot + 1) + 2 F) + 4 (2 N + 2 R F) + 488 R bytes (nslot: DESIGN.md section 10); the working
+ * memory of mmg_diff_perm_qvalues is taken and given back inside the call and not counted */
+int mmg_diff_perm_device_bytes(mmg_diff_perm *h, uint64_t *bytes);
+void mmg_diff_perm_destroy(mmg_diff_perm *h);
+
+/* q-values of F observed statistics against n_null null statistics (host arrays; computed on `device`).  With m and m0 the observed
+ * and null values that are not NaN, -0.0 equal to 0.0, R(t) the observed values >= t and V(t) the null values >= t:
+ *   fdr(t) = min(1, ((double)V(t) * (double)m) / ((double)m0 * (double)R(t))),
+ *   q[f] = min { fdr(t') : t' an observed value, t' <= obs[f] },   null_ge[f] = V(obs[f]).
+ * An observed NaN gets q = NaN and null_ge = 0 and counts in no R; with m0 == 0 every q is NaN.
+ * MMG_ERR_ARG for F == 0, n_null == 0, n_null > 2^31 - 1 or a NULL pointer. */
+int mmg_qvalues(int device, uint32_t F, const double *obs, uint64_t n_null, const double *null, uint64_t *null_ge, double *q);
 
 #ifdef __cplusplus
 }

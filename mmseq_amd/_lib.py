@@ -189,6 +189,19 @@ SYMBOLS = {
     "mmg_diff_chains_info": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmg_diff_chains_device_bytes": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mmg_diff_chains_destroy": (None, [C.c_void_p]),
+    "mmg_diff_perm_create": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
+                                       C.c_uint32, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int, C.c_uint64, C.c_uint32,
+                                       C.c_void_p]),
+    "mmg_diff_perm_burnin": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "mmg_diff_perm_tune_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmg_diff_perm_sample": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "mmg_diff_perm_get_results": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmg_diff_perm_info": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmg_diff_perm_qvalues": (C.c_int, [C.c_void_p]),
+    "mmg_diff_perm_get_qvalues": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmg_diff_perm_device_bytes": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mmg_diff_perm_destroy": (None, [C.c_void_p]),
+    "mmg_qvalues": (C.c_int, [C.c_int, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmg_collapse_summarize": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_double,
                                          C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),

@@ -1,6 +1,7 @@
 // diff.hip -- device TU + host side of the mmg_diff_* entry points: mmdiff's per-feature MCMC (src/bms.cpp driven as
 // src/mmdiff.cpp:744-866).  Kernels in diff_kernels.h.
 #include "diff_kernels.h"
+#include "diff_perm_kernels.h"
 #include "mmg_host.h"
 
 #include <cmath>
@@ -1088,3 +1089,262 @@ extern "C" int mmg_diff_chains_device_bytes(mmg_diff_chains *h, uint64_t *bytes)
 }
 
 extern "C" void mmg_diff_chains_destroy(mmg_diff_chains *h) { delete h; }
+
+// ---- a permutation null: the data and B shuffled copies of it on one handle ----------------------------------------------------
+// M / P0 / P1 and the class table once; per replica its y / e^2 ([R][N][F]: replica 0 as given, replica b >= 1 shuffled by
+// k_dfq_shuffle), a DiffParams (replica b in the stream key), a state block, gam / tuned.  The launches are those of mmg_diff_poly_*,
+// grid.y the replica; a replica whose untuned count reached 0 leaves the tuning launches.  stat / null_ge / q: what
+// mmg_diff_perm_qvalues leaves on the device.
+constexpr uint32_t DF_PERM_MAX = 31;   // k_dfp_tune's `active` mask has 32 bits: the data and 31 shuffles
+
+struct mmg_diff_perm {
+    DevStream st;
+    int device = 0;
+    uint32_t F = 0, N = 0, K = 0, L[2] = {0, 0}, R = 0;
+    size_t nslot = 0;
+    DevBuf<double> d_y, d_esq, d_M, d_P0, d_P1, d_st, d_stat, d_q;
+    DevBuf<uint64_t> d_null_ge;
+    DevBuf<int> d_C, d_gam, d_tuned;
+    std::vector<DiffParams> h_p;
+    std::vector<uint32_t> h_off, nb;   // per replica: 128 * (its batches); its batches
+    std::vector<char> ended;
+    DevBuf<DiffParams> d_p;
+    DevBuf<uint32_t> d_off;
+    DevBuf<int> d_cnt;
+    uint32_t burnin = 0, batches = 0, sampled = 0;
+    bool burnt = false, have_q = false;
+    uint64_t device_bytes = 0;
+    dim3 grid() const { return dim3(df_blocks(F), R); }
+    ~mmg_diff_perm() { if (st) (void)hipStreamSynchronize(st.get()); }
+};
+
+extern "C" int mmg_diff_perm_create(int device, uint32_t F, uint32_t N, const double *y, const double *e, uint32_t K, const double *M,
+                                    uint32_t L0, const double *P0, uint32_t L1, const double *P1, const int32_t *C, double d, double s,
+                                    double pdash, int fixalpha, uint64_t seed, uint32_t n_perm, mmg_diff_perm **out)
+{
+    if (!out || !y || !e || !M || !P0 || !P1 || !C) return fail(MMG_ERR_ARG, "NULL argument");
+    *out = nullptr;
+    if (F == 0 || F > 0x7fffff00u / DF_BLOCK) return fail(MMG_ERR_ARG, "the number of features must be between 1 and 33554428");
+    if (N < 2 || N > (uint32_t)DF_NMAX) return fail(MMG_ERR_ARG, "the number of samples must be between 2 and 512");
+    if (K < 1 || K > (uint32_t)DF_KMAX) return fail(MMG_ERR_ARG, "M must have between 1 and 8 columns");
+    if (L0 < 1 || L0 > (uint32_t)DF_LMAX || L1 < 1 || L1 > (uint32_t)DF_LMAX) return fail(MMG_ERR_ARG, "P0 and P1 must have between 1 and 16 columns");
+    if (n_perm < 1 || n_perm > DF_PERM_MAX) return fail(MMG_ERR_ARG, "the number of permutations must be between 1 and 31");
+    if (!(d > 0) || !(s > 0) || !std::isfinite(d) || !std::isfinite(s) || !(pdash >= 0 && pdash <= 1))
+        return fail(MMG_ERR_ARG, "d and s must be positive and finite and pdash in [0, 1]");
+    auto finite = [](const double *x, uint64_t n) { for (uint64_t i = 0; i < n; ++i) if (!std::isfinite(x[i])) return false; return true; };
+    if (!finite(y, (uint64_t)F * N) || !finite(e, (uint64_t)F * N)) return fail(MMG_ERR_ARG, "y and e must be finite");
+    if (!finite(M, (uint64_t)N * K) || !finite(P0, (uint64_t)N * L0) || !finite(P1, (uint64_t)N * L1)) return fail(MMG_ERR_ARG, "M, P0 and P1 must be finite");
+    int nc[2] = {0, 0};
+    int rc;
+    for (int mi = 0; mi < 2; ++mi)
+        if ((rc = df_classes(C + mi, 2, N, &nc[mi]))) return rc;
+    if ((rc = require_device(device))) return rc;
+
+    const uint32_t R = n_perm + 1;
+    std::unique_ptr<mmg_diff_perm> h(new mmg_diff_perm());
+    h->device = device; h->F = F; h->N = N; h->K = K; h->L[0] = L0; h->L[1] = L1; h->R = R;
+    h->h_off.assign(R, 0);
+    h->nb.assign(R, 0);
+    h->ended.assign(R, 0);
+    DiffParams p{};
+    p.F = (int)F; p.N = (int)N; p.K = (int)K;
+    p.Mnil = df_nil(M, N, K) ? 1 : 0;
+    p.fixalpha = fixalpha ? 1 : 0;
+    p.d = d; p.s = s; p.v_beta = fixalpha ? 25.0 : 4.0;
+    p.seed = seed;
+    p.m[0].Pnil = df_nil(P0, N, L0) ? 1 : 0;
+    p.m[1].Pnil = df_nil(P1, N, L1) ? 1 : 0;
+    h->nslot = df_layout(p, h->L, nc);
+    const uint64_t FN = (uint64_t)F * N, per_replica = (uint64_t)h->nslot * F;
+
+    auto dalloc = [&](auto &buf, uint64_t count) {
+        HIPE_TRY(buf.alloc(count));
+        h->device_bytes += count * sizeof(*buf.get());
+        return hipSuccess;
+    };
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(h->st.create(hipStreamNonBlocking));
+    const hipStream_t st = h->st.get();
+    HIP_TRY(dalloc(h->d_y, FN * R));
+    HIP_TRY(dalloc(h->d_esq, FN * R));
+    HIP_TRY(dalloc(h->d_M, (uint64_t)N * K));
+    HIP_TRY(dalloc(h->d_P0, (uint64_t)N * L0));
+    HIP_TRY(dalloc(h->d_P1, (uint64_t)N * L1));
+    HIP_TRY(dalloc(h->d_C, (uint64_t)N * 2));
+    HIP_TRY(dalloc(h->d_st, per_replica * R));
+    HIP_TRY(dalloc(h->d_gam, (uint64_t)F * R));
+    HIP_TRY(dalloc(h->d_tuned, (uint64_t)F * R));
+    HIP_TRY(dalloc(h->d_stat, (uint64_t)F * R));
+    HIP_TRY(dalloc(h->d_q, (uint64_t)F));
+    HIP_TRY(dalloc(h->d_null_ge, (uint64_t)F));
+    HIP_TRY(dalloc(h->d_p, R));
+    HIP_TRY(dalloc(h->d_off, R));
+    HIP_TRY(dalloc(h->d_cnt, R));
+    // y and e^2 transposed to [N][F], as mmg_diff_create holds them: replica 0, copied on the device to every other replica and shuffled there
+    std::vector<double> ty(FN), te(FN);
+    for (uint64_t f = 0; f < F; ++f)
+        for (uint64_t i = 0; i < N; ++i) {
+            ty[i * F + f] = y[f * N + i];
+            const double ei = e[f * N + i];
+            te[i * F + f] = ei * ei;
+        }
+    HIP_TRY(hipMemcpyAsync(h->d_y.get(), ty.data(), FN * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->d_esq.get(), te.data(), FN * 8, hipMemcpyHostToDevice, st));
+    for (uint32_t b = 1; b < R; ++b) {
+        HIP_TRY(hipMemcpyAsync(h->d_y.get() + FN * b, h->d_y.get(), FN * 8, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(h->d_esq.get() + FN * b, h->d_esq.get(), FN * 8, hipMemcpyDeviceToDevice, st));
+    }
+    hipLaunchKernelGGL(k_dfq_shuffle, dim3(df_blocks(F), n_perm), dim3(DF_BLOCK), 0, st, h->d_y.get(), h->d_esq.get(), (int)F, (int)N, seed);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h->d_M.get(), M, (size_t)N * K * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->d_P0.get(), P0, (size_t)N * L0 * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->d_P1.get(), P1, (size_t)N * L1 * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(h->d_C.get(), C, (size_t)N * 2 * 4, hipMemcpyHostToDevice, st));
+    p.M = h->d_M.get(); p.m[0].P = h->d_P0.get(); p.m[1].P = h->d_P1.get(); p.Cl = h->d_C.get();
+    h->h_p.assign(R, p);
+    for (uint32_t b = 0; b < R; ++b) {
+        DiffParams &q = h->h_p[b];
+        q.chain = (int)b;
+        q.y = h->d_y.get() + FN * b;
+        q.esq = h->d_esq.get() + FN * b;
+        q.st = h->d_st.get() + per_replica * b;
+        q.gam = h->d_gam.get() + (size_t)F * b;
+        q.tuned = h->d_tuned.get() + (size_t)F * b;
+    }
+    HIP_TRY(hipMemcpyAsync(h->d_p.get(), h->h_p.data(), (size_t)R * sizeof(DiffParams), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(h->d_off.get(), 0, (size_t)R * 4, st));
+    const double logitp0 = std::log(pdash) - std::log(1.0 - pdash);
+    hipLaunchKernelGGL(k_dfp_init, h->grid(), dim3(DF_BLOCK), 0, st, h->d_p.get(), logitp0);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));   // (the host buffers were the sources of asynchronous copies)
+    *out = h.release();
+    return MMG_OK;
+}
+
+extern "C" int mmg_diff_perm_burnin(mmg_diff_perm *h, uint32_t iters)
+{
+    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
+    if (h->burnt) return fail(MMG_ERR_STATE, "the burn-in has run already");
+    if (iters == 0 || iters % 1024) return fail(MMG_ERR_ARG, "burn-in iterations must be a positive multiple of 1024");
+    HIP_TRY(hipSetDevice(h->device));
+    for (uint32_t t = 0; t < iters; t += DF_CHUNK) {
+        const uint32_t n = iters - t < DF_CHUNK ? iters - t : DF_CHUNK;
+        hipLaunchKernelGGL(k_dfp_run, h->grid(), dim3(DF_BLOCK), 0, h->st.get(), h->d_p.get(), h->d_off.get(), t, (int)t, (int)n, 0, DF_REC_FROM);
+    }
+    hipLaunchKernelGGL(k_dfp_pseudo, h->grid(), dim3(DF_BLOCK), 0, h->st.get(), h->d_p.get(), (double)(iters - DF_REC_FROM));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(h->st.get()));
+    h->burnin = iters;
+    h->burnt = true;
+    return MMG_OK;
+}
+
+extern "C" int mmg_diff_perm_tune_batch(mmg_diff_perm *h, uint32_t *untuned, int32_t *ended)
+{
+    if (!h || !untuned) return fail(MMG_ERR_ARG, "NULL argument");
+    if (!h->burnt) return fail(MMG_ERR_STATE, "mmg_diff_perm_tune_batch before mmg_diff_perm_burnin");
+    if (h->sampled) return fail(MMG_ERR_STATE, "mmg_diff_perm_tune_batch after sampling has started");
+    uint32_t active = 0;
+    for (uint32_t b = 0; b < h->R; ++b)
+        if (!h->ended[b]) active |= 1u << b;
+    for (uint32_t b = 0; b < h->R; ++b) untuned[b] = 0;
+    if (active) {
+        HIP_TRY(hipSetDevice(h->device));
+        HIP_TRY(hipMemsetAsync(h->d_cnt.get(), 0, (size_t)h->R * 4, h->st.get()));
+        const uint32_t it0 = h->burnin + h->batches * DF_BATCH;
+        hipLaunchKernelGGL(k_dfp_tune, h->grid(), dim3(DF_BLOCK), 0, h->st.get(), h->d_p.get(), active, it0, (int)h->batches, h->d_cnt.get());
+        HIP_TRY(hipGetLastError());
+        int cnt[DF_PERM_MAX + 1] = {0};
+        HIP_TRY(hipMemcpyAsync(cnt, h->d_cnt.get(), (size_t)h->R * 4, hipMemcpyDeviceToHost, h->st.get()));
+        HIP_TRY(hipStreamSynchronize(h->st.get()));
+        ++h->batches;
+        for (uint32_t b = 0; b < h->R; ++b) {
+            if (h->ended[b]) continue;
+            h->nb[b] = h->batches;
+            untuned[b] = (uint32_t)cnt[b];
+            if (cnt[b] == 0) h->ended[b] = 1;
+        }
+    }
+    if (ended)
+        for (uint32_t b = 0; b < h->R; ++b) ended[b] = h->ended[b] ? 1 : 0;
+    return MMG_OK;
+}
+
+extern "C" int mmg_diff_perm_sample(mmg_diff_perm *h, uint32_t iters)
+{
+    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
+    if (!h->burnt) return fail(MMG_ERR_STATE, "mmg_diff_perm_sample before mmg_diff_perm_burnin");
+    if (iters == 0) return fail(MMG_ERR_ARG, "iters must be positive");
+    HIP_TRY(hipSetDevice(h->device));
+    if (!h->sampled) {
+        // replica b's sampling starts at its own running index, burnin + 128 * (its batches)
+        for (uint32_t b = 0; b < h->R; ++b) h->h_off[b] = h->nb[b] * DF_BATCH;
+        HIP_TRY(hipMemcpyAsync(h->d_off.get(), h->h_off.data(), (size_t)h->R * 4, hipMemcpyHostToDevice, h->st.get()));
+    }
+    for (uint32_t j = 0; j < iters; j += DF_CHUNK) {
+        const uint32_t n = iters - j < DF_CHUNK ? iters - j : DF_CHUNK;
+        hipLaunchKernelGGL(k_dfp_run, h->grid(), dim3(DF_BLOCK), 0, h->st.get(), h->d_p.get(), h->d_off.get(), h->burnin + h->sampled + j, 0, (int)n, 2, 0);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(h->st.get()));
+    h->sampled += iters;
+    h->have_q = false;
+    return MMG_OK;
+}
+
+extern "C" int mmg_diff_perm_get_results(mmg_diff_perm *h, uint32_t b, double *gamma_mean, double *logitp, double *alpha, double *beta, double *eta)
+{
+    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
+    if (b >= h->R) return fail(MMG_ERR_ARG, "no such replica");
+    if (!h->sampled) return fail(MMG_ERR_STATE, "mmg_diff_perm_get_results before mmg_diff_perm_sample");
+    HIP_TRY(hipSetDevice(h->device));
+    return df_results(h->h_p[b], h->h_p[b].st, h->F, h->K, h->L, h->sampled, gamma_mean, logitp, alpha, beta, eta);
+}
+
+extern "C" int mmg_diff_perm_info(mmg_diff_perm *h, uint32_t b, int32_t *flags, uint32_t *n_classes, uint32_t *batches, int32_t *ended)
+{
+    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
+    if (b >= h->R) return fail(MMG_ERR_ARG, "no such replica");
+    const DiffParams &p = h->h_p[b];
+    if (flags) { flags[0] = p.Mnil; flags[1] = p.m[0].Pnil; flags[2] = p.m[1].Pnil; }
+    if (n_classes) { n_classes[0] = (uint32_t)p.m[0].nc; n_classes[1] = (uint32_t)p.m[1].nc; }
+    if (batches) *batches = h->nb[b];
+    if (ended) *ended = h->ended[b] ? 1 : 0;
+    return MMG_OK;
+}
+
+extern "C" int mmg_diff_perm_qvalues(mmg_diff_perm *h)
+{
+    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
+    if (!h->sampled) return fail(MMG_ERR_STATE, "mmg_diff_perm_qvalues before mmg_diff_perm_sample");
+    HIP_TRY(hipSetDevice(h->device));
+    const DiffParams &p = h->h_p[0];
+    int rc = qvalue_stat_on_device(h->st.get(), h->d_st.get(), h->nslot * (size_t)h->F, p.gsum, p.logitp, h->F, h->R, h->sampled, h->d_stat.get());
+    if (rc) return rc;
+    // replica 0's statistics against those of replicas 1 .. B, which follow them in d_stat
+    rc = qvalues_on_device(h->st.get(), h->F, h->d_stat.get(), (uint64_t)(h->R - 1) * h->F, h->d_stat.get() + h->F, h->d_null_ge.get(), h->d_q.get());
+    if (rc) { (void)hipStreamSynchronize(h->st.get()); return rc; }
+    h->have_q = true;
+    return MMG_OK;
+}
+
+extern "C" int mmg_diff_perm_get_qvalues(mmg_diff_perm *h, double *stat, uint64_t *null_ge, double *q)
+{
+    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
+    if (!h->have_q) return fail(MMG_ERR_STATE, "mmg_diff_perm_get_qvalues before mmg_diff_perm_qvalues");
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t F = h->F;
+    if (stat) HIP_TRY(hipMemcpy(stat, h->d_stat.get(), (size_t)h->R * F * 8, hipMemcpyDeviceToHost));
+    if (null_ge) HIP_TRY(hipMemcpy(null_ge, h->d_null_ge.get(), F * 8, hipMemcpyDeviceToHost));
+    if (q) HIP_TRY(hipMemcpy(q, h->d_q.get(), F * 8, hipMemcpyDeviceToHost));
+    return MMG_OK;
+}
+
+extern "C" int mmg_diff_perm_device_bytes(mmg_diff_perm *h, uint64_t *bytes)
+{
+    if (!h || !bytes) return fail(MMG_ERR_ARG, "NULL argument");
+    *bytes = h->device_bytes;
+    return MMG_OK;
+}
+
+extern "C" void mmg_diff_perm_destroy(mmg_diff_perm *h) { delete h; }

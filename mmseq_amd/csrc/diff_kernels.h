@@ -6,7 +6,7 @@
 // The state is SoA in global memory, slot j of feature f at st[j * F + f]: adjacent lanes touch adjacent words.
 //
 // Randomness: Stream(seed, chain, TAG_DIFF, feature, it), `it` one running iteration index over burn-in, tuning and sampling; the
-// block counter runs on through the updates of the iteration.  The chain is 0 except in the handles of mmg_diff_chains_*.  Every sum runs in a fixed order, no floating-point atomics:
+// block counter runs on through the updates of the iteration.  The chain is 0 except in the handles of mmg_diff_chains_* and mmg_diff_perm_*.  Every sum runs in a fixed order, no floating-point atomics:
 // reruns are bit-identical and tests/mmdiff_ref.py restates every operation in numpy.
 #pragma once
 #include "mmg_math.h"
@@ -35,7 +35,7 @@ struct DiffModel {
 
 struct DiffParams {
     int F, N, K, Mnil, fixalpha;
-    int chain;            // the chain of the stream key (in what was padding: the size stays 480); 0 but for mmg_diff_chains_*
+    int chain;            // the chain of the stream key (in what was padding: the size stays 480); 0 but for mmg_diff_chains_* and mmg_diff_perm_*
     double d, s, v_beta;
     uint64_t seed;
     const double *M;      // [N][K]

@@ -48,6 +48,7 @@ using namespace std;
 #define MAXBATCHES 8192
 #define MAXMODELS 16   // alternatives (-m) in one run
 #define MAXCHAINS 16   // chains (-chains) in one run
+#define MAXPERMS 31    // shuffled replicas (-permutations) in one run
 
 namespace {
 
@@ -92,6 +93,7 @@ void printUsage(ostream &out)
         << "       mmdiff [OPTIONS...] [-prior P0,...,PJ] [-polyout BASE] -m alt1 -m alt2 [-m ...] mmseq_file1 mmseq_file2... > out.polyclass" << endl
         << "       mmdiff -polyclass [-prior P0,...,PJ] a.mmdiff b.mmdiff [...] > out.polyclass" << endl
         << "       mmdiff [OPTIONS...] -chains C [-chainout BASE] [-de n1 n2 ... nC | -m matrices_file] mmseq_file1 mmseq_file2... > out.mmdiff" << endl
+        << "       mmdiff [OPTIONS...] -permutations B [-permout BASE] [-de n1 n2 ... nC | -m matrices_file] mmseq_file1 mmseq_file2... > out.mmdiff" << endl
         << endl;
     out << "Mandatory arguments:" << endl
         << "  ONE OF:" << endl
@@ -135,7 +137,14 @@ void printUsage(ostream &out)
         << "                    from all chains and the columns log_bf, log_bf_sd, log_bf_mcse, chains_mixed appended (default: 1, the" << endl
         << "                    plain table); not with repeated -m or -polyclass (chains of several alternatives are left for later)" << endl
         << "  -chainout STRING  with -chains: write the mmdiff table of chain c to STRING.chain<c>.mmdiff" << endl
-        << "Size limits: 512 samples, 8 columns of M, 16 columns of P0 and P1, 16 variance classes per model, 16 alternatives (-m) per run, 16 chains." << endl;
+        << "  -permutations INT run the data and INT (1 to 31) copies of it whose samples are shuffled per feature (as -permute shuffles" << endl
+        << "                    them, copy b with the seed seed ^ (b << 32)) in one run, and append to the plain table perm_ge (the" << endl
+        << "                    shuffled log Bayes factors, over all copies and features, not below the feature's own) and q_value (the" << endl
+        << "                    smallest estimated false discovery rate at which the feature is called); not with -permute, -chains," << endl
+        << "                    repeated -m, -traces, -effects or -polyclass.  A shuffle only relabels samples: with few samples many" << endl
+        << "                    shuffles reproduce the original grouping (a third of them for 2 vs 2), and the q-values are conservative" << endl
+        << "  -permout STRING   with -permutations: write the mmdiff table of shuffled copy b to STRING.perm<b>.mmdiff" << endl
+        << "Size limits: 512 samples, 8 columns of M, 16 columns of P0 and P1, 16 variance classes per model, 16 alternatives (-m) per run, 16 chains. At most 31 permutations." << endl;
 }
 
 [[noreturn]] void usage_error(const string &msg)
@@ -255,9 +264,9 @@ void apply_normalisation(const vector<string> &filenames, Mat &y, const Mat &uh,
 
 // -permute: a Fisher-Yates shuffle of each feature's samples, keyed (seed, 0, TAG_DIFF_PERM, feature, 0) -- the same for every
 // thread count and machine (the reference calls random_shuffle)
-void apply_permutation(Mat &y, Mat &e, size_t F, size_t S, uint64_t seed)
+void apply_permutation(Mat &y, Mat &e, size_t F, size_t S, uint64_t seed, bool quiet = false)
 {
-    cerr << "Permuting input data...";
+    if (!quiet) cerr << "Permuting input data...";
     vector<size_t> idx(S);
     vector<double> ny(S), ne(S);
     for (size_t f = 0; f < F; ++f) {
@@ -271,7 +280,7 @@ void apply_permutation(Mat &y, Mat &e, size_t F, size_t S, uint64_t seed)
         for (size_t j = 0; j < S; ++j) { ny[j] = y[f * S + idx[j]]; ne[j] = e[f * S + idx[j]]; }
         for (size_t j = 0; j < S; ++j) { y[f * S + j] = ny[j]; e[f * S + j] = ne[j]; }
     }
-    cerr << "done\n";
+    if (!quiet) cerr << "done\n";
 }
 
 struct Design {
@@ -468,12 +477,19 @@ struct PooledCols {
     PooledCols(size_t F) : log_bf(F), log_bf_sd(F), log_bf_mcse(F), chains_mixed(F) {}
 };
 
+// what the table of a -permutations run has besides the plain one's: the null statistics not below the feature's own and its q-value
+struct PermCols {
+    vector<uint64_t> null_ge;
+    vector<double> q;
+    PermCols(size_t F) : null_ge(F), q(F) {}
+};
+
 // The table of one comparison: to fp (if any) and appended to *keep (if any).  The Bayes factor is the chain's own, with the warning for
 // a gamma that did not mix -- or, with `pool` (the pooled table of several chains: its columns are appended), exp(log_bf).  warn_stuck:
-// off for the tables of a run of several chains, which reports mixing per feature itself.
+// off for the tables of a run of several chains, which reports mixing per feature itself.  With `perm` its two columns are appended.
 void write_table(FILE *fp, string *keep, const vector<string> &features, const vector<string> &filenames, const Design &D, bool fixalpha,
                  bool Mnil, const bool Pnil[2], double p, const Mat &y, const Mat &e, const DiffResults &r, bool warn_stuck = true,
-                 const PooledCols *pool = nullptr)
+                 const PooledCols *pool = nullptr, const PermCols *perm = nullptr)
 {
     const size_t F = features.size(), S = filenames.size();
     const vector<double> &gm = r.gm, &logitp = r.logitp, &alpha = r.alpha, &beta = r.beta, &eta = r.eta;
@@ -502,7 +518,9 @@ void write_table(FILE *fp, string *keep, const vector<string> &features, const v
         out += "mu_" + samplenames[f] + "\t";
     }
     for (size_t f = 0; f < S; f++) out += "sd_" + samplenames[f] + (f < S - 1 ? "\t" : "");
-    out += pool ? "\tlog_bf\tlog_bf_sd\tlog_bf_mcse\tchains_mixed\n" : "\n";
+    if (pool) out += "\tlog_bf\tlog_bf_sd\tlog_bf_mcse\tchains_mixed";
+    if (perm) out += "\tperm_ge\tq_value";
+    out += "\n";
     emit(out);
     const double logp = log(p), log1mp = log1p(-p);
     for (size_t feature = 0; feature < F; feature++) {
@@ -533,6 +551,7 @@ void write_table(FILE *fp, string *keep, const vector<string> &features, const v
         if (pool)
             out += "\t" + fmt(pool->log_bf[feature]) + "\t" + fmt(pool->log_bf_sd[feature]) + "\t" + fmt(pool->log_bf_mcse[feature]) + "\t"
                    + to_string(pool->chains_mixed[feature]);
+        if (perm) out += "\t" + to_string(perm->null_ge[feature]) + "\t" + fmt(perm->q[feature]);
         out += "\n";
         emit(out);
     }
@@ -844,6 +863,72 @@ int run_chains(int C, bool chainout_given, const string &chainout, const Design 
     return 0;
 }
 
+// -permutations B: the data and B shuffled copies of it on one device handle.  stdout gets the plain run's
+// table with perm_ge and q_value appended; the table of shuffled copy b (what -permute prints with the seed seed ^ (b << 32)) goes to
+// BASE.perm<b>.mmdiff with -permout.
+int run_perm(int B, bool permout_given, const string &permout, const Design &D, bool Mnil, const bool Pnil[2], const vector<string> &features,
+             const vector<string> &filenames, const Mat &y, const Mat &e, double p, double d, double s, double pdash, bool fixalpha, bool tune,
+             int burnin, int mcmciters, uint64_t useed)
+{
+    const size_t S = filenames.size(), F = features.size();
+    const int R = B + 1;
+    struct Closer { vector<FILE *> f; ~Closer() { for (FILE *x : f) if (x) fclose(x); } } files;
+    files.f.assign(R, nullptr);
+    auto name = [&](int b) { return permout + ".perm" + to_string(b) + ".mmdiff"; };
+    if (permout_given)
+        for (int b = 1; b < R; ++b)
+            if (!(files.f[b] = fopen(name(b).c_str(), "w"))) die("Error: couldn't create " + name(b));
+
+    // every input is checked: now the device
+    int ndev = 0;
+    if (mmg_device_count(&ndev) != 0 || ndev < 1) die("Error: no HIP device available: mmdiff has no CPU fallback");
+    mmg_diff_perm *h = nullptr;
+    MMG_CHECK(mmg_diff_perm_create(0, (uint32_t)F, (uint32_t)S, y.data(), e.data(), (uint32_t)D.K, D.M.data(), (uint32_t)D.L0, D.P0.data(),
+                                   (uint32_t)D.L1, D.P1.data(), D.C.data(), d, s, pdash, fixalpha ? 1 : 0, useed, (uint32_t)B, &h));
+    cerr << "BURNIN (" << burnin << " iterations, the data and " << B << " permutations)...";
+    MMG_CHECK(mmg_diff_perm_burnin(h, (uint32_t)burnin));
+    cerr << "\nSetting pseudopriors...done.\n";
+    if (tune) {
+        // each replica stops at the first batch after which none of its features is untuned, or with the others at MAXBATCHES
+        vector<uint32_t> untuned(R);
+        vector<int32_t> ended(R);
+        int numbatches = 0;
+        bool all_ended = false;
+        while (!all_ended && numbatches != MAXBATCHES) {
+            MMG_CHECK(mmg_diff_perm_tune_batch(h, untuned.data(), ended.data()));
+            numbatches++;
+            all_ended = true;
+            uint64_t left = 0;
+            for (int b = 0; b < R; ++b) { all_ended = all_ended && ended[b]; left += untuned[b]; }
+            if (numbatches % 64 == 0) cerr << "TUNING BATCH " << numbatches << " (" << left << " left)\r";
+        }
+    }
+    for (int b = 0; b < R; ++b) {
+        uint32_t nb = 0;
+        MMG_CHECK(mmg_diff_perm_info(h, (uint32_t)b, NULL, NULL, &nb, NULL));
+        cerr << "replica " << b << ": sampling after " << nb << " tuning batches\n";
+    }
+    cerr << "TRACE (" << mcmciters << " iterations)";
+    MMG_CHECK(mmg_diff_perm_sample(h, (uint32_t)mcmciters));
+    MMG_CHECK(mmg_diff_perm_qvalues(h));
+    cerr << "\nDONE MCMC\n";
+    DiffResults r(F, D);
+    for (int b = 1; b < R && permout_given; ++b) {
+        // the table's mu_ / sd_ columns: the shuffle the device applied to replica b, on the host
+        Mat yb = y, eb = e;
+        apply_permutation(yb, eb, F, S, useed ^ ((uint64_t)b << 32), true);
+        MMG_CHECK(mmg_diff_perm_get_results(h, (uint32_t)b, r.gm.data(), r.logitp.data(), r.alpha.data(), r.beta.data(), r.eta.data()));
+        write_table(files.f[b], nullptr, features, filenames, D, fixalpha, Mnil, Pnil, p, yb, eb, r, false);
+        if (fflush(files.f[b]) != 0) die("Error: couldn't write " + name(b));
+    }
+    PermCols cols(F);
+    MMG_CHECK(mmg_diff_perm_get_results(h, 0, r.gm.data(), r.logitp.data(), r.alpha.data(), r.beta.data(), r.eta.data()));
+    MMG_CHECK(mmg_diff_perm_get_qvalues(h, NULL, cols.null_ge.data(), cols.q.data()));
+    mmg_diff_perm_destroy(h);
+    write_table(stdout, nullptr, features, filenames, D, fixalpha, Mnil, Pnil, p, y, e, r, true, nullptr, &cols);
+    return 0;
+}
+
 // ---- -traces DIR: the files of the reference's -tracedir (BMS::initialise_streams, print, printtune, print_pseudo) ------------------
 // The library hands the recorded rows of a launch to sink() on the main thread, which copies them and returns; writer threads format
 // them while the chain goes on.  File s belongs to thread s % T and every thread takes the chunks in order, so a file's lines are in
@@ -1118,11 +1203,11 @@ int main(int argc, char **argv)
 {
     string matrices_file = "";
     vector<string> matrices_files;   // every -m; more than one: the polytomous run
-    bool polyclass_mode = false, prior_given = false, polyout_given = false, chains_given = false, chainout_given = false;
-    string prior_text, polyout, chainout, traces, effects, effects_pct_text = "2.5,50,97.5";
+    bool polyclass_mode = false, prior_given = false, polyout_given = false, chains_given = false, chainout_given = false, perms_given = false, permout_given = false;
+    string prior_text, polyout, chainout, permout, traces, effects, effects_pct_text = "2.5,50,97.5";
     bool effects_every_given = false, effects_pct_given = false;
     long effects_every = 0;
-    int chains = 1;
+    int chains = 1, perms = 0;
     double p = 0.1, d = 1.4, s = 2.0;
     int burnin = 8192, mcmciters = 16384, seed = 1234, range_start = -1, range_end = -1;
     bool useprops = false, fixalpha = false, normalise = true, customuhfrac = false, permute = false, tune = true;
@@ -1260,6 +1345,16 @@ int main(int argc, char **argv)
         } else if (a0 == "-chainout") {
             chainout = take();
             chainout_given = true;
+        } else if (a0 == "-permutations") {
+            const string v = take();
+            char *end = NULL;
+            const long n = strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end != '\0' || n < 1 || n > MAXPERMS) die("Error: -permutations takes an integer between 1 and " + to_string(MAXPERMS) + ".");
+            perms = (int)n;
+            perms_given = true;
+        } else if (a0 == "-permout") {
+            permout = take();
+            permout_given = true;
         } else if (a0 == "-h" || a0 == "--help" || a0 == "-help") {
             cerr << "Bayesian model selection for RNA-seq expression estimates.\n";
             printUsage(cerr);
@@ -1290,6 +1385,9 @@ int main(int argc, char **argv)
         usage_error("Error: -effects cannot be combined with -traces (the handle records rows for one of them).");
     if (!effects.empty() && (chains_given || poly_run || polyclass_mode))
         usage_error("Error: -effects cannot be combined with -chains, more than one -m or -polyclass (effects of several chains or alternatives are left for later).");
+    if (permout_given && !perms_given) usage_error("Error: -permout needs -permutations.");
+    if (perms_given && (permute || chains > 1 || chainout_given || poly_run || polyclass_mode || !traces.empty() || !effects.empty()))
+        usage_error("Error: -permutations cannot be combined with -permute, -chains above 1 (or -chainout), more than one -m, -traces, -effects or -polyclass.");
     vector<double> effects_pct;
     if (!effects.empty()) effects_pct = parse_percentiles(effects_pct_text);
     if (polyclass_mode) {
@@ -1370,6 +1468,9 @@ int main(int argc, char **argv)
     if (chains > 1)
         return run_chains(chains, chainout_given, chainout, D, Mnil, Pnil, features, filenames, y, e, p, d, s, pdash, fixalpha, tune, burnin,
                           mcmciters, useed);
+    if (perms_given)
+        return run_perm(perms, permout_given, permout, D, Mnil, Pnil, features, filenames, y, e, p, d, s, pdash, fixalpha, tune, burnin, mcmciters,
+                        useed);
     // -chains 1 -chainout BASE: the plain run, its table to BASE.chain0.mmdiff as well
     struct Closer { FILE *f = nullptr; ~Closer() { if (f) fclose(f); } } chain0;
     const string chain0_name = chainout + ".chain0.mmdiff";

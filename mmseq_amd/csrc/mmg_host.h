@@ -306,6 +306,13 @@ int effects_check(uint32_t S, uint32_t P, uint32_t np, const double *percentiles
 int effects_of_device_rows(int device, uint32_t S, uint32_t P, uint32_t F, const double *d_rows, const uint8_t *model_of, uint32_t np,
                            const double *percentiles, mmg_effects **out);
 
+// mmdiff's permutation null (qvalue.hip), both on stream st of the current device.  qvalue_stat_on_device: stat[R][F], the log Bayes
+// factor of every replica and feature from R state blocks `stride` doubles apart (slots gsum and logitp); in stream order, not
+// synchronised.  qvalues_on_device: mmg_qvalues of device arrays into device arrays; the stream has been waited for when it returns.
+int qvalue_stat_on_device(hipStream_t st, const double *d_st, size_t stride, int gsum, int logitp, uint32_t F, uint32_t R, uint32_t sampled,
+                          double *d_stat);
+int qvalues_on_device(hipStream_t st, uint32_t F, const double *d_obs, uint64_t n_null, const double *d_null, uint64_t *d_null_ge, double *d_q);
+
 int require_device(int device);
 void weighted_chunks(const std::vector<uint64_t> &cum, uint64_t grid, std::vector<uint64_t> &chunk);
 void weighted_chunks_tapered(const std::vector<uint64_t> &cum, uint64_t grid, uint64_t resident, std::vector<uint64_t> &chunk);

@@ -2,8 +2,8 @@
 
 `Diff` holds every feature's MCMC state on the device (src/bms.cpp driven as src/mmdiff.cpp:744-866): `burnin` runs the burn-in and
 sets the pseudopriors, `tune_batch` one tuning batch of 128 iterations, `sample` the sampling iterations, `results` the posterior
-means.  `DiffPoly` runs several alternatives against one model 0 on one handle, `DiffChains` several chains of one comparison.  No
-CPU path exists: without a device every call raises.
+means.  `DiffPoly` runs several alternatives against one model 0 on one handle, `DiffChains` several chains of one comparison, `DiffPerm` the data and
+its shuffled copies with q-values (`qvalues` computes them for any two arrays of statistics).  No CPU path exists: without a device every call raises.
 """
 import ctypes as C
 
@@ -377,3 +377,102 @@ class DiffChains:
             self.close()
         except Exception:
             pass
+
+
+class DiffPerm:
+    """The data and B shuffled copies of it on one handle (the mmg_diff_perm_* entries): R = n_perm + 1 replicas, 1 <= n_perm <= 31.
+    Replica 0 is the data as given; replica b >= 1 is the data with every feature's samples shuffled on the device, the shuffle
+    `mmdiff -permute` applies with the seed seed ^ (b << 32).  Replica b is bit for bit `Diff(y_b, e_b, ..., seed=seed ^ (b << 32))`
+    driven the same way; each replica tunes on its own and keeps its batch count.  After sampling, `qvalues` gives the log Bayes
+    factors of every replica and the q-values of replica 0 against the pooled replicas 1 .. B."""
+
+    def __init__(self, y, e, M, P0, P1, classes, n_perm, d=1.4, s=2.0, pdash=0.5, fixalpha=False, seed=1234, device=0):
+        self._lib = _lib.load()
+        self._h = None
+        y = np.ascontiguousarray(y, np.float64)
+        e = np.ascontiguousarray(e, np.float64)
+        M = np.ascontiguousarray(M, np.float64)
+        P = [np.ascontiguousarray(P0, np.float64), np.ascontiguousarray(P1, np.float64)]
+        Cl = np.ascontiguousarray(classes, np.int32)
+        F, N = y.shape
+        if e.shape != (F, N) or M.shape[0] != N or P[0].shape[0] != N or P[1].shape[0] != N or Cl.shape != (N, 2):
+            raise ValueError("inconsistent shapes")
+        self.F, self.N, self.K = F, N, M.shape[1]
+        self.L = (P[0].shape[1], P[1].shape[1])
+        self.B = int(n_perm)
+        self.R = self.B + 1
+        h = C.c_void_p()
+        check(self._lib.mmg_diff_perm_create(device, F, N, _ptr(y), _ptr(e), self.K, _ptr(M), self.L[0], _ptr(P[0]), self.L[1], _ptr(P[1]),
+                                             _ptr(Cl), float(d), float(s), float(pdash), int(bool(fixalpha)),
+                                             int(seed) & 0xFFFFFFFFFFFFFFFF, self.B & 0xFFFFFFFF, C.byref(h)))
+        self._h = h
+
+    def burnin(self, iters):
+        check(self._lib.mmg_diff_perm_burnin(self._h, int(iters)))
+
+    def tune_batch(self):
+        """One tuning batch for the replicas that have not ended; (untuned counts, ended flags), one entry per replica."""
+        n, ended = (C.c_uint32 * self.R)(), (C.c_int32 * self.R)()
+        check(self._lib.mmg_diff_perm_tune_batch(self._h, n, ended))
+        return list(n), [bool(v) for v in ended]
+
+    def tune(self, max_batches=MAXBATCHES):
+        """Batches until every replica has ended or max_batches have run; the batch count of each replica."""
+        nb = 0
+        while nb != max_batches:
+            _, ended = self.tune_batch()
+            nb += 1
+            if all(ended):
+                break
+        return [self.info(b)["batches"] for b in range(self.R)]
+
+    def sample(self, iters):
+        check(self._lib.mmg_diff_perm_sample(self._h, int(iters)))
+
+    def results(self, b):
+        F, K, L = self.F, self.K, self.L
+        out = dict(gamma_mean=np.empty(F), logitp=np.empty(F), alpha=np.empty((2, F)), beta=np.empty((2, K, F)), eta=np.empty((L[0] + L[1], F)))
+        check(self._lib.mmg_diff_perm_get_results(self._h, int(b), *(_ptr(out[k]) for k in ("gamma_mean", "logitp", "alpha", "beta", "eta"))))
+        return out
+
+    def info(self, b):
+        flags, nc, nb, ended = (C.c_int32 * 3)(), (C.c_uint32 * 2)(), C.c_uint32(), C.c_int32()
+        check(self._lib.mmg_diff_perm_info(self._h, int(b), flags, nc, C.byref(nb), C.byref(ended)))
+        return dict(Mnil=bool(flags[0]), Pnil=(bool(flags[1]), bool(flags[2])), n_classes=(nc[0], nc[1]), batches=nb.value,
+                    ended=bool(ended.value))
+
+    def qvalues(self):
+        """After sampling: `stat` (R, F) the log Bayes factor of every replica and feature, and of replica 0 against the pooled
+        replicas 1 .. B `null_ge` (F,) the null statistics not below the feature's own and `q` (F,) the q-values."""
+        out = dict(stat=np.empty((self.R, self.F)), null_ge=np.empty(self.F, np.uint64), q=np.empty(self.F))
+        check(self._lib.mmg_diff_perm_qvalues(self._h))
+        check(self._lib.mmg_diff_perm_get_qvalues(self._h, _ptr(out["stat"]), _ptr(out["null_ge"]), _ptr(out["q"])))
+        return out
+
+    def device_bytes(self):
+        b = C.c_uint64()
+        check(self._lib.mmg_diff_perm_device_bytes(self._h, C.byref(b)))
+        return b.value
+
+    def close(self):
+        if self._h:
+            self._lib.mmg_diff_perm_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def qvalues(obs, null, device=0):
+    """q-values of the observed statistics against the null statistics (any shapes, taken flat), on the device: (null_ge, q), per
+    observed value the null values not below it and min over the observed t' <= it of min(1, V(t') m / (m0 R(t'))), with R and V the
+    observed and null values >= t', m and m0 the observed and null values that are not NaN.  tests/qvalue_ref.py restates it."""
+    lib = _lib.load()
+    obs = np.ascontiguousarray(obs, np.float64).ravel()
+    null = np.ascontiguousarray(null, np.float64).ravel()
+    null_ge, q = np.empty(obs.size, np.uint64), np.empty(obs.size)
+    check(lib.mmg_qvalues(device, obs.size, _ptr(obs), null.size, _ptr(null), _ptr(null_ge), _ptr(q)))
+    return null_ge, q
