@@ -189,7 +189,7 @@ class _Model:
 
     def log_terms(self):
         """log of every grid point's contribution to the marginal likelihood, in batches.  log N(y; 0, D + X V0 X'), D the diagonal
-        e^2 + sigma^2, through the determinant lemma and the Woodbury identity on A = V0^-1 + X' D^-1 X (p x p, p <= 3):
+        e^2 + sigma^2, through the determinant lemma and the Woodbury identity on A = V0^-1 + X' D^-1 X (p x p, p the number of coefficients, 5 at the most in the designs tested):
         log det = sum log D + sum log V0 + log det A, y' Sigma^-1 y = y' D^-1 y - t' A^-1 t with t = X' D^-1 y.  The N x N covariance
         itself has a condition number of 1e17 at lambda = e^30 and loses its sign to rounding at e^35; the p x p form stays exact
         there.  test_gaussian_only_model holds it to scipy's density of the N x N covariance."""

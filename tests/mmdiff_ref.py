@@ -462,7 +462,9 @@ class BMS:
             lss = float(dlog(np.array([self.s]))[0])
             for l in range(self.L[m]):
                 e, lam = S["eta"][:, l], S["lam"][:, l]
-                sm = sm + (((((-0.5 * e) * e) / lam - (1.5 + self.d) * dlog(lam)) + self.d * lss) - lgd) - self.s / lam
+                # src/bms.cpp:948-949 adds the column's whole term to the sum: `sum += a - b + c - d - e`, so s / lambda is taken from
+                # the term, not from the running sum (the two differ in the last bits from the second column on)
+                sm = sm + ((((((-0.5 * e) * e) / lam - (1.5 + self.d) * dlog(lam)) + self.d * lss) - lgd) - self.s / lam)
         for c in range(self.nc[m]):
             sg = S["sig"][:, c]
             sm = sm + (((k / 2.0) * dlog(rho) - (k * rho) / (2.0 * sg)) - (1.0 + k / 2.0) * dlog(sg))

@@ -244,6 +244,26 @@ def test_effects_of_the_device_chain_match_the_exact_posterior(gpu):
     X.check_effects_against_exact(got, "device")
 
 
+@pytest.mark.gpu
+def test_effects_of_the_device_chain_match_the_exact_posterior_with_three_covariates(gpu):
+    """The same on design f_cov3 (test_mmdiff_effects_exact.COV3): three covariate columns, so the summaries of six beta columns go
+    through the rule beside alpha and eta.  Measured on an MI355X (and the same, bit for bit, with the restatement on the CPU): n under
+    model 0 from 29 to 75 of 128 rows, under model 1 from 53 to 99; the 86 deviations lie between -1.60 s.e. (q 2.5 of beta0_2, fixture
+    row 2) and +2.17 s.e. (P(> 0) of beta0_0, fixture row 2), two of them beyond 2."""
+    import test_mmdiff_effects_exact as X
+    from mmseq_amd.diff import Diff
+    cfg = X.COV3
+    y, e, M, P0, P1, classes, kw = X.stat_inputs(cfg["case"])
+    d = Diff(y, e, M, P0, P1, classes, pdash=cfg["pdash"], seed=cfg["seed"], **kw)
+    d.open_effects(X.THIN, X.ITERS // X.THIN)
+    d.burnin(X.BURNIN)
+    d.sample(X.ITERS)
+    got = d.effects(X.PCT)
+    d.close()
+    assert [n for n in got["names"] if n.startswith("beta")] == ["beta%d_%d" % (m, j) for m in range(2) for j in range(3)]
+    X.check_effects_against_exact(got, "device f_cov3", cfg)
+
+
 # ---- the CLI ---------------------------------------------------------------------------------------------------------------
 def format_effects(features, fx, fixalpha, Mnil, Pnil):
     """The file `mmdiff -effects` writes, from the dict of Diff.effects()."""

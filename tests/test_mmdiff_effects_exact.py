@@ -49,6 +49,14 @@ PCT = (2.5, 50.0, 97.5)
 QUANTITIES = (("alpha0", 0, "alpha"), ("alpha1", 1, "alpha"), ("eta1_0", 1, "eta_0"))   # traced name, model, name in the exact module
 P_GT0_OF = ("eta1_0",)
 N_MIN, LEFT_OUT_MAX = 8, 0.05
+# The same rule on design f_cov3 (three covariate columns, 12 samples; rows 1 and 2 again): every beta column of both models joins
+# (a) and (c), and (b) takes the betas too, whose exact P(> 0) lies between 0.2 and 0.9.  p' = 0.5, at which these rows spend
+# 0.55 and 0.65 of their time in model 1 (n from 29 to 75 rows under model 0, from 53 to 99 under model 1; none left out).
+COV3 = dict(case="f_cov3", pdash=0.5, seed=22,
+            quantities=(("alpha0", 0, "alpha"), ("alpha1", 1, "alpha"))
+            + tuple(("beta%d_%d" % (m, j), m, "beta_%d" % j) for m in range(2) for j in range(3)) + (("eta1_0", 1, "eta_0"),),
+            p_gt0_of=tuple("beta%d_%d" % (m, j) for m in range(2) for j in range(3)) + ("eta1_0",))
+BASE = dict(case=CASE, pdash=PDASH, seed=SEED, quantities=QUANTITIES, p_gt0_of=P_GT0_OF)
 
 
 # ----------------------------------------------------------------------------- the exact marginals against closed forms
@@ -116,9 +124,9 @@ def test_grid_refinement_moves_sd_and_cdf_by_less_than_1e_6():
 
 
 # ----------------------------------------------------------------------------- the statistical rule
-def stat_inputs():
+def stat_inputs(case=CASE):
     """y (2 R, N), e (2 R, N), M, P0, P1, classes and the keyword arguments of the design: row ROWS[i] is features i R .. i R + R - 1."""
-    y, e, M, P0, P1, classes, kw = design(CASE)
+    y, e, M, P0, P1, classes, kw = design(case)
     return replicate(y[list(ROWS)], R), np.tile(e, (len(ROWS) * R, 1)), M, P0, P1, classes, kw
 
 
@@ -126,33 +134,45 @@ STAT_GRID = X.DEFAULT_GRID.coarsened(0.5)
 
 
 @functools.lru_cache(maxsize=None)
-def exact_mixtures():
+def exact_mixtures(case=CASE):
     """The exact marginals of the statistical rule, on half the default grid's points per axis: a second for both rows instead of
-    eleven, so that the device test stays short.  test_half_the_grid_points_move_nothing_the_rule_can_see bounds what that costs."""
-    y, e, M, P0, P1, classes, kw = design(CASE)
+    eleven, so that the device test stays short.  test_half_the_grid_points_move_nothing_the_rule_can_see bounds what that costs.
+    (f_cov3: model 1's grid has three dimensions, 250 880 nodes of which 24 000 carry the weight; six seconds for both rows.)"""
+    y, e, M, P0, P1, classes, kw = design(case)
     return [[XE.mixture(y[r], e, M, P, classes[:, m], grid=STAT_GRID, **kw) for m, P in ((0, P0), (1, P1))] for r in ROWS]
 
 
-def test_half_the_grid_points_move_nothing_the_rule_can_see():
-    """STAT_GRID against the default grid, both fixture rows and models: mean, sd (relative) and F at mean, mean +- sd, mean +- 2 sd.
-    Measured for model 1: mean 6.5e-08, sd 1.1e-07, F 9.3e-08; the rule's standard errors are 1e-3.  (0.35 of the points: 3.8e-05.)"""
-    y, e, M, P0, P1, classes, kw = design(CASE)
-    for r in ROWS:
+def _half_grid_moves(case, rows):
+    y, e, M, P0, P1, classes, kw = design(case)
+    for r in rows:
         for m, P in ((0, P0), (1, P1)):
             base = XE.moments(y[r], e, M, P, classes[:, m], **kw)
             at = np.concatenate([[mu + k * sd for k in (-2, -1, 0, 1, 2)] for mu, sd in zip(base["mean"], base["sd"])])
             base = XE.moments(y[r], e, M, P, classes[:, m], at=at, **kw)
             half = XE.moments(y[r], e, M, P, classes[:, m], at=at, grid=STAT_GRID, **kw)
             moved = (np.abs(half["mean"] - base["mean"]).max(), np.abs(half["sd"] / base["sd"] - 1.0).max(), np.abs(half["cdf"] - base["cdf"]).max())
-            print("half grid, row %d model %d: mean %.1e sd %.1e F %.1e" % ((r, m) + moved))
-            assert max(moved) < 1e-6, (r, m, moved)
+            print("half grid, %s row %d model %d: mean %.1e sd %.1e F %.1e" % ((case, r, m) + moved))
+            assert max(moved) < 1e-6, (case, r, m, moved)
 
 
-def check_effects_against_exact(fx, what):
+def test_half_the_grid_points_move_nothing_the_rule_can_see():
+    """STAT_GRID against the default grid, both fixture rows and models: mean, sd (relative) and F at mean, mean +- sd, mean +- 2 sd.
+    Measured for model 1: mean 6.5e-08, sd 1.1e-07, F 9.3e-08; the rule's standard errors are 1e-3.  (0.35 of the points: 3.8e-05.)"""
+    _half_grid_moves(CASE, ROWS)
+
+
+def test_half_the_grid_points_move_nothing_the_rule_can_see_with_three_covariates():
+    """The same for f_cov3, one row (the default grid of its model 1 has two million nodes and takes a minute).  Measured for model 1:
+    mean 1.8e-08, sd 8.5e-08, F 5.5e-08."""
+    _half_grid_moves(COV3["case"], ROWS[:1])
+
+
+def check_effects_against_exact(fx, what, cfg=None):
     """fx: the dict of mmdiff_effects_ref.effects / Diff.effects over the features of stat_inputs() with percentiles PCT.  Prints every
-    figure, then asserts (a), (b) and (c) of the module's docstring."""
+    figure, then asserts (a), (b) and (c) of the module's docstring.  cfg: BASE (the default) or COV3."""
+    cfg = cfg or BASE
     names = list(fx["names"])
-    mix = exact_mixtures()
+    mix = exact_mixtures(cfg["case"])
     failures = []
 
     def rule(est, exact, label):
@@ -161,7 +181,7 @@ def check_effects_against_exact(fx, what):
         except AssertionError as ex:
             failures.append((label, str(ex)))
 
-    for name, m, cname in QUANTITIES:
+    for name, m, cname in cfg["quantities"]:
         s = names.index(name)
         n = fx["n"][m].astype(np.float64).reshape(len(ROWS), R)
         ok = n >= N_MIN
@@ -171,7 +191,7 @@ def check_effects_against_exact(fx, what):
         for i in range(len(ROWS)):
             k = ok[i]
             ni = n[i][k]
-            if name in P_GT0_OF:
+            if name in cfg["p_gt0_of"]:
                 p_gt = fx["n_gt"][s].reshape(len(ROWS), R)[i][k] / ni
                 rule(p_gt[None, :], [mix[i][m].p_gt0(cname)], "%s row %d P(> 0)" % (name, ROWS[i]))
             # (c)
@@ -195,3 +215,20 @@ def test_restated_effects_match_the_exact_posterior(orc):
     fx = E.effects(rows, E.model_of_names(names[:-1]), PCT)
     fx["names"] = names[:-1]
     check_effects_against_exact(fx, "restatement")
+
+
+def test_restated_effects_match_the_exact_posterior_with_three_covariates(orc):
+    """As above on design f_cov3 (COV3): 21 traced parameters, the summaries of six beta columns among them.  Measured: the 86
+    deviations lie between -1.60 and +2.17 standard errors; the device's own rows give the same figures
+    (tests/test_gpu_mmdiff_effects.py).  The restatement of the chain takes about a minute and a half here."""
+    import mmdiff_trace_ref as TR
+    y, e, M, P0, P1, classes, kw = stat_inputs(COV3["case"])
+    b = TR.TracedBMS(y, e, M, P0, P1, classes, pdash=COV3["pdash"], seed=COV3["seed"], every_burnin=BURNIN, every_sample=THIN, **kw)
+    b.burnin(BURNIN)
+    b.sample(ITERS)
+    rows = b.stacked(1)
+    names = b.names()
+    assert rows.shape == (ITERS // THIN, len(names), len(ROWS) * R)
+    fx = E.effects(rows, E.model_of_names(names[:-1]), PCT)
+    fx["names"] = names[:-1]
+    check_effects_against_exact(fx, "restatement f_cov3", COV3)
