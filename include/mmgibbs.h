@@ -85,7 +85,9 @@ extern "C" {
  *      of the hits (mmg_assign_*, MMG_OPT_ASSIGN_WAVES), and the posterior summary over the draws of all chains (mmg_pooled_*,
  *      MMG_OPT_POOL_SLAB), and the posterior correlation of pairs of transcripts (mmg_pairs_*, MMG_OPT_PAIRS_SLAB), and mmdiff's
  *      effect summaries (mmg_diff_effects_*, mmg_effects_*), and mmdiff's permutation null with its q-values (mmg_diff_perm_*,
- *      mmg_qvalues). */
+ *      mmg_qvalues), and the self test of the streams' key space and of the scalar functions (mmg_selftest_keyed).
+ *      mmg_sampler_create refuses chains beyond 2^24: the Gamma stream's key holds 24 bits of the chain index (the row stream all 32), so
+ *      chain 2^24 + c would redraw mu from chain c's uniforms.  No chain that ran before is changed by the check. */
 /* Layout.  The model does not care about the order of rows or the numbering of transcripts (src/mmseq.cpp:399-418 uses
  * first-seen order for both); the kernels do: they keep a window of consecutive transcripts in LDS and want the 64 rows of a
  * wave to have equal lengths.  mmg_problem_create therefore stores the rows in a CANONICAL order of its own (sorted on the
@@ -110,6 +112,8 @@ enum {
  * draw k >= 2 categoricals are stored k times by the canonical layout. */
 #define MMG_K_SMALL 64u
 #define MMG_K_DRAWS_PER_HIT 16u
+/* chain indices (mmg_config.chain_base + the chain) fit 24 bits: that many enter the key of the Gamma stream */
+#define MMG_MAX_CHAINS 16777216
 
 typedef struct mmg_problem mmg_problem; /* device-resident CSR hit-set matrix M + k + l */
 typedef struct mmg_sampler mmg_sampler; /* chains' state: mu, counts, trace, moments     */
@@ -199,7 +203,8 @@ typedef struct mmg_config {
     double alpha, beta;
     uint64_t seed;
     int32_t n_chains;   /* independent chains advanced per sweep on this device (>= 1)   */
-    int32_t chain_base; /* global index of chain 0 here (multi-device chains mode)        */
+    int32_t chain_base; /* global index of chain 0 here (multi-device chains mode); >= 0,
+                           chain_base + n_chains <= MMG_MAX_CHAINS                        */
     int32_t gibbs_iter; /* planned chain length; sample s kept when iter % (gibbs_iter/trace_len) == 0 (:911) */
     int32_t trace_len;  /* samples per chain: 1024 in the reference (:191)                */
     int32_t keep_trace; /* !=0: store the samples (n*trace_len doubles per chain); 0: moments only */
@@ -536,6 +541,43 @@ int mmg_selftest_btrs_pretest(int device, uint64_t seed, int64_t n_cases, double
  * the end (the sequential code draws again), [4] the sum of the outcomes (counts: 5 words).  slack scales the error bound the fp32 search
  * allows itself: 1 is what the sampler runs; smaller values show how much room the bound has. */
 int mmg_selftest_binv_pretest(int device, uint64_t seed, int64_t n_cases, double n_lo, double n_hi, double slack, uint64_t *counts);
+
+/* The keyed streams over their whole key space, and the scalar functions behind them pointwise (device >= 0: in kernels on that device;
+ * device == -1: the host instantiation of the same inline code).  Three independent parts; a part with count 0 is skipped, its pointers
+ * may be NULL.
+ *   streams, element i keyed (seed[i], chain[i], tag[i], id[i], iter[i]) -- the chain as the kernels pass it, all 32 bits:
+ *     out_uniforms[4 i ..]  the first two pairs of uniforms of the Philox4x32 stream (K2's Gamma stream, the simulated traces)
+ *     out_words[3 i ..]     the first three words of the Philox2x32 row stream
+ *     out_gamma[i]          the Gamma(shape[i]) draw of the Philox4x32 stream times scale (NaN unless shape[i] > 0)
+ *   math, element i at x[i]:
+ *     out_probit, out_lgamma   the inverse normal CDF of the proportion summaries (AS 241), log Gamma of mmdiff's densities
+ *     out_normal[i]            the N(0,1) draw of stream (normal_seed, chain 0, the Gamma tag, id i, iteration 0): x is not used
+ *     out_stirling[i]          the binomial sampler's Stirling remainder of log(x!), 0 <= x < 2^32 (NaN elsewhere)
+ *     out_ilogb[i]             the exponent of x, 0 < x < inf, subnormals included (INT32_MIN elsewhere)
+ *   words, element i:
+ *     out_u32[i], out_u52[i]   the uniforms made of the word w0[i] and of the pair (w0[i], w1[i])
+ *     out_target[i]            the categorical draw's target of word w0[i] over weights of total t[i]
+ * Additive in version 8. */
+typedef struct mmg_keyed_io {
+    int64_t n_streams;
+    const uint64_t *seed, *id;
+    const uint32_t *chain, *tag, *iter;
+    const double *shape;
+    double scale;
+    double *out_uniforms;
+    uint32_t *out_words;
+    double *out_gamma;
+    int64_t n_math;
+    const double *x;
+    uint64_t normal_seed;
+    double *out_probit, *out_lgamma, *out_normal, *out_stirling;
+    int32_t *out_ilogb;
+    int64_t n_words;
+    const uint32_t *w0, *w1;
+    const double *t;
+    double *out_u32, *out_u52, *out_target;
+} mmg_keyed_io;
+int mmg_selftest_keyed(int device, const mmg_keyed_io *io);
 
 /* ---- mmcollapse: candidates collapsed by their mean posterior anti-correlation across samples ----------------------------
  * src/mmcollapse.cpp:483-561 (covariances of the candidates' traces per sample, mean correlations), :713-747 (row maxima for the

@@ -80,6 +80,16 @@ class Config(C.Structure):
                 ("keep_trace", C.c_int32), ("timing", C.c_int32)]
 
 
+class KeyedIO(C.Structure):
+    _fields_ = [("n_streams", C.c_int64), ("seed", C.c_void_p), ("id", C.c_void_p), ("chain", C.c_void_p), ("tag", C.c_void_p),
+                ("iter", C.c_void_p), ("shape", C.c_void_p), ("scale", C.c_double), ("out_uniforms", C.c_void_p),
+                ("out_words", C.c_void_p), ("out_gamma", C.c_void_p),
+                ("n_math", C.c_int64), ("x", C.c_void_p), ("normal_seed", C.c_uint64), ("out_probit", C.c_void_p),
+                ("out_lgamma", C.c_void_p), ("out_normal", C.c_void_p), ("out_stirling", C.c_void_p), ("out_ilogb", C.c_void_p),
+                ("n_words", C.c_int64), ("w0", C.c_void_p), ("w1", C.c_void_p), ("t", C.c_void_p), ("out_u32", C.c_void_p),
+                ("out_u52", C.c_void_p), ("out_target", C.c_void_p)]
+
+
 class Timing(C.Structure):
     _fields_ = [("sample_ms", C.c_double), ("update_ms", C.c_double), ("sample_launches", C.c_uint64),
                 ("update_launches", C.c_uint64)]
@@ -255,6 +265,7 @@ SYMBOLS = {
     "mmg_selftest_binomial": (C.c_int, [C.c_int, C.c_uint64, C.c_uint32, C.c_double, C.c_int64, C.c_void_p]),
     "mmg_selftest_btrs_pretest": (C.c_int, [C.c_int, C.c_uint64, C.c_int64, C.c_double, C.c_double, C.c_void_p]),
     "mmg_selftest_binv_pretest": (C.c_int, [C.c_int, C.c_uint64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_void_p]),
+    "mmg_selftest_keyed": (C.c_int, [C.c_int, C.POINTER(KeyedIO)]),
 }
 
 

@@ -66,7 +66,8 @@ static void printUsage(ostream &out)
         << "  -epsilon FLOAT     minimum loglik ratio between successive EM iterations (default: 0.1)" << endl
         << "  -gibbs_iter INT    number of Gibbs iterations (default: 16384)" << endl
         << "  -gibbs_ss INT      subsampling interval for Gibbs output (default: gibbs_iter/1024)" << endl
-        << "  -seed INT          seed for the PRNG in thread 0 (default: 1234)" << endl
+        << "  -seed INT          seed for the PRNG in thread 0 (default: 1234).  A 32-bit signed integer, sign-extended to the 64-bit key" << endl
+        << "                     of the random streams: -seed -7 is the library's seed 2^64 - 7, not 7" << endl
         << "  -percentiles STR   comma-separated list of real-scale marginal posterior percentiles to output (default: "
            "\"5,25,50,75,95\")"
         << endl
@@ -1152,7 +1153,7 @@ static Chains start_chains(const Options &opt, const Device &dev, const vector<d
     else
         for (int i = 0; i < opt.gpus; ++i) {
             mmg_config ci = cfg;
-            ci.chain_base = dev.shard ? 0 : i * cfg.n_chains;
+            ci.chain_base = dev.shard ? 0 : i * cfg.n_chains; // (far below MMG_MAX_CHAINS: at most 4096 chains per sampler, and mmg_sampler_create checks)
             MMG_TRY(mmg_sampler_create(part[i], &ci, mu_em.data(), &smps[i]));
         }
     // ---- the posterior summary is set up BEFORE the loop and fed while it runs (src/mmseq.cpp:911-917 prints sample s inside the

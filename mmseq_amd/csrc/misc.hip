@@ -116,6 +116,20 @@ void host_binomial(uint64_t seed, uint32_t nn, double p, int64_t n, uint32_t *ou
     for (int64_t i = 0; i < n; ++i) { Stream2 q(seed, 0, TAG_ROW, (uint64_t)i, 0); out[i] = binomial(q, nn, p); }
 }
 
+// mmg_selftest_keyed: io's pointers are device memory for the launcher, host memory for host_keyed
+void launch_selftest_keyed(const mmg_keyed_io &io, hipStream_t s)
+{
+    if (io.n_streams) hipLaunchKernelGGL(k_selftest_keyed_streams, dim3((unsigned)((io.n_streams + 255) / 256)), dim3(256), 0, s, io);
+    if (io.n_math) hipLaunchKernelGGL(k_selftest_keyed_math, dim3((unsigned)((io.n_math + 255) / 256)), dim3(256), 0, s, io);
+    if (io.n_words) hipLaunchKernelGGL(k_selftest_keyed_words, dim3((unsigned)((io.n_words + 255) / 256)), dim3(256), 0, s, io);
+}
+void host_keyed(const mmg_keyed_io &io)
+{
+    for (int64_t i = 0; i < io.n_streams; ++i) keyed_streams_one(io, i);
+    for (int64_t i = 0; i < io.n_math; ++i) keyed_math_one(io, i);
+    for (int64_t i = 0; i < io.n_words; ++i) keyed_words_one(io, i);
+}
+
 // transcript tables of the synthetic generator
 void host_synth_tables(uint64_t seed, uint32_t T, double lambda, std::vector<double> &efflen, std::vector<double> &cdf,
                        std::vector<double> &len_cdf)

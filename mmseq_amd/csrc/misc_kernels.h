@@ -324,6 +324,53 @@ __global__ void k_selftest_binomial(uint64_t seed, uint32_t nn, double p, int64_
     out[i] = binomial(q, nn, p);
 }
 
+// mmg_selftest_keyed: the keyed streams at caller-given keys, the scalar functions and the word-to-uniform maps pointwise.  One element
+// each is host-and-device inline code (misc.hip's host_keyed runs the same three functions), one lane per element in the kernels.
+// The kernels take the ABI's own descriptor by value, its pointers replaced by device copies.
+MMG_HD void keyed_streams_one(const mmg_keyed_io &a, int64_t i)
+{
+    Stream s(a.seed[i], a.chain[i], a.tag[i], a.id[i], a.iter[i]);
+    s.pair(a.out_uniforms[4 * i], a.out_uniforms[4 * i + 1]);
+    s.pair(a.out_uniforms[4 * i + 2], a.out_uniforms[4 * i + 3]);
+    Stream2 q(a.seed[i], a.chain[i], a.tag[i], a.id[i], a.iter[i]);
+    for (int b = 0; b < 3; ++b) a.out_words[3 * i + b] = q.next_word();
+    Stream g(a.seed[i], a.chain[i], a.tag[i], a.id[i], a.iter[i]);
+    a.out_gamma[i] = a.shape[i] > 0.0 ? gamma_unit(g, a.shape[i]) * a.scale : __builtin_nan("");
+}
+MMG_HD void keyed_math_one(const mmg_keyed_io &a, int64_t i)
+{
+    const double x = a.x[i];
+    a.out_probit[i] = dprobit(x);
+    a.out_lgamma[i] = dlgamma(x);
+    Stream s(a.normal_seed, 0, TAG_GAMMA, (uint64_t)i, 0);
+    a.out_normal[i] = normal(s);
+    // (both are defined on what the binomial sampler passes: counts up to 2^32 - 1, positive finite weights)
+    a.out_stirling[i] = (x >= 0.0 && x <= 4294967295.0) ? stirling_tail(x) : __builtin_nan("");
+    a.out_ilogb[i] = (x > 0.0 && x < __builtin_huge_val()) ? dilogb(x) : INT32_MIN;
+}
+MMG_HD void keyed_words_one(const mmg_keyed_io &a, int64_t i)
+{
+    a.out_u32[i] = u32_unit(a.w0[i]);
+    a.out_u52[i] = u52(a.w0[i], a.w1[i]);
+    const double ts = a.t[i] * 0x1p-32, hs = ts * 0.5; // as the sample kernels form them
+    a.out_target[i] = draw_target(a.w0[i], ts, hs);
+}
+__global__ __launch_bounds__(256) void k_selftest_keyed_streams(mmg_keyed_io a)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < a.n_streams) keyed_streams_one(a, i);
+}
+__global__ __launch_bounds__(256) void k_selftest_keyed_math(mmg_keyed_io a)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < a.n_math) keyed_math_one(a, i);
+}
+__global__ __launch_bounds__(256) void k_selftest_keyed_words(mmg_keyed_io a)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < a.n_words) keyed_words_one(a, i);
+}
+
 // BTRS candidates over (n, p) drawn from the case index: n log-uniform in [n_lo, n_hi], p log-uniform in [10 / n, 1/2] (where binomial() takes
 // BTRS), one attempt each from the case's keyed stream.  counts[0] attempts that reach the exact test, [1] of them decided by btrs_pretest,
 // [2] decided AND different from the fp64 test (must stay 0), [3] accepted by the fp64 test, [4] max |estimate - fp64 difference| / bound, in millionths.

@@ -1265,3 +1265,57 @@ extern "C" int mmg_selftest_binv_pretest(int device, uint64_t seed, int64_t n_ca
     if (e != hipSuccess) return fail(MMG_ERR_HIP, std::string("selftest_binv_pretest: ") + hipGetErrorString(e));
     return MMG_OK;
 }
+
+extern "C" int mmg_selftest_keyed(int device, const mmg_keyed_io *io)
+{
+    if (!io || io->n_streams < 0 || io->n_math < 0 || io->n_words < 0) return fail(MMG_ERR_ARG, "bad argument");
+    if (io->n_streams && (!io->seed || !io->id || !io->chain || !io->tag || !io->iter || !io->shape || !io->out_uniforms || !io->out_words || !io->out_gamma))
+        return fail(MMG_ERR_ARG, "selftest_keyed: NULL stream argument");
+    if (io->n_math && (!io->x || !io->out_probit || !io->out_lgamma || !io->out_normal || !io->out_stirling || !io->out_ilogb))
+        return fail(MMG_ERR_ARG, "selftest_keyed: NULL math argument");
+    if (io->n_words && (!io->w0 || !io->w1 || !io->t || !io->out_u32 || !io->out_u52 || !io->out_target))
+        return fail(MMG_ERR_ARG, "selftest_keyed: NULL word argument");
+    if (device < 0) { host_keyed(*io); return MMG_OK; }
+    int rc = require_device(device);
+    if (rc) return rc;
+    // the descriptor again with every pointer replaced by a device buffer of the same extent
+    mmg_keyed_io d = *io;
+    struct Back { void *host; const void *dev; size_t bytes; };
+    std::vector<DevBuf<uint8_t>> bufs;
+    std::vector<Back> back;
+    bufs.reserve(24);
+    hipError_t e = hipSuccess;
+    auto in = [&](auto *&f, int64_t count) {
+        if (e != hipSuccess) return;
+        const void *h = f;
+        bufs.emplace_back();
+        e = bufs.back().alloc((size_t)count * sizeof(*f));
+        if (e == hipSuccess) e = hipMemcpy(bufs.back().get(), h, (size_t)count * sizeof(*f), hipMemcpyHostToDevice);
+        f = reinterpret_cast<std::remove_reference_t<decltype(f)>>(bufs.back().get());
+    };
+    auto out = [&](auto *&f, int64_t count) {
+        if (e != hipSuccess) return;
+        bufs.emplace_back();
+        e = bufs.back().alloc((size_t)count * sizeof(*f));
+        back.push_back(Back{f, bufs.back().get(), (size_t)count * sizeof(*f)});
+        f = reinterpret_cast<std::remove_reference_t<decltype(f)>>(bufs.back().get());
+    };
+    if (const int64_t n = d.n_streams) {
+        in(d.seed, n); in(d.id, n); in(d.chain, n); in(d.tag, n); in(d.iter, n); in(d.shape, n);
+        out(d.out_uniforms, 4 * n); out(d.out_words, 3 * n); out(d.out_gamma, n);
+    }
+    if (const int64_t n = d.n_math) {
+        in(d.x, n);
+        out(d.out_probit, n); out(d.out_lgamma, n); out(d.out_normal, n); out(d.out_stirling, n); out(d.out_ilogb, n);
+    }
+    if (const int64_t n = d.n_words) {
+        in(d.w0, n); in(d.w1, n); in(d.t, n);
+        out(d.out_u32, n); out(d.out_u52, n); out(d.out_target, n);
+    }
+    if (e == hipSuccess) { launch_selftest_keyed(d, 0); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    for (const Back &b : back)
+        if (e == hipSuccess) e = hipMemcpy(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(MMG_ERR_HIP, std::string("selftest_keyed: ") + hipGetErrorString(e));
+    return MMG_OK;
+}

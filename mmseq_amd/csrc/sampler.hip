@@ -73,6 +73,10 @@ extern "C" int mmg_sampler_create(const mmg_problem *p, const mmg_config *cfg, c
 {
     if (!p || !cfg || !mu0 || !out) return fail(MMG_ERR_ARG, "NULL argument");
     if (cfg->n_chains < 1 || cfg->n_chains > 4096) return fail(MMG_ERR_ARG, "n_chains out of range");
+    // the Gamma stream's key holds 24 bits of the chain index (mmg_math.h: Stream; the row stream all 32): chain 2^24 + c would redraw mu
+    // from the uniforms of chain c
+    if (cfg->chain_base < 0 || (int64_t)cfg->chain_base + cfg->n_chains > (int64_t)MMG_MAX_CHAINS)
+        return fail(MMG_ERR_ARG, "chain_base >= 0 and chain_base + n_chains <= 16777216: chain indices must fit 24 bits");
     if (!(cfg->alpha > 0.0) || !(cfg->beta > 0.0)) return fail(MMG_ERR_ARG, "alpha, beta must be > 0");
     if (cfg->trace_len < 1 || cfg->gibbs_iter < 1) return fail(MMG_ERR_ARG, "gibbs_iter and trace_len must be >= 1 (src/mmseq.cpp:286)");
     if (cfg->gibbs_iter % cfg->trace_len != 0) return fail(MMG_ERR_ARG, "gibbs_iter must be a multiple of trace_len (src/mmseq.cpp:278-284)");

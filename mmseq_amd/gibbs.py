@@ -661,3 +661,46 @@ def selftest_binv_pretest(seed, n_cases, n_lo, n_hi, slack=1.0, device=0):
     out = np.zeros(5, np.uint64)
     check(_lib.load().mmg_selftest_binv_pretest(device, seed, n_cases, float(n_lo), float(n_hi), float(slack), _ptr(out)))
     return tuple(int(v) for v in out)
+
+
+def _keyed(device, io):
+    check(_lib.load().mmg_selftest_keyed(int(device), C.byref(io)))
+
+
+def selftest_keyed_streams(seed, chain, tag, ident, it, shape=1.0, scale=1.0, device=-1):
+    """mmg_selftest_keyed, streams: element i is keyed (seed[i], chain[i], tag[i], ident[i], it[i]) (scalars broadcast).  Returns
+    dict(uniforms [n, 4]: the first two pairs of the Philox4x32 stream; words [n, 3]: the first three words of the row stream;
+    gamma [n]: the stream's Gamma(shape[i]) draw times scale).  device -1: the host instantiation."""
+    seed, ident, chain, tag, it, shape = np.broadcast_arrays(np.asarray(seed, np.uint64), np.asarray(ident, np.uint64), np.asarray(chain, np.uint32),
+                                                            np.asarray(tag, np.uint32), np.asarray(it, np.uint32), np.asarray(shape, np.float64))
+    seed, ident, chain, tag, it, shape = [np.ascontiguousarray(a).ravel() for a in (seed, ident, chain, tag, it, shape)]
+    n = seed.size
+    out = dict(uniforms=np.empty((n, 4)), words=np.empty((n, 3), np.uint32), gamma=np.empty(n))
+    io = _lib.KeyedIO(n_streams=n, seed=_ptr(seed), id=_ptr(ident), chain=_ptr(chain), tag=_ptr(tag), iter=_ptr(it), shape=_ptr(shape),
+                      scale=float(scale), out_uniforms=_ptr(out["uniforms"]), out_words=_ptr(out["words"]), out_gamma=_ptr(out["gamma"]))
+    _keyed(device, io)                                    # (the arrays io points into are locals: alive until here)
+    return out
+
+
+def selftest_keyed_math(x, normal_seed=0, device=-1):
+    """mmg_selftest_keyed, math: dict(probit, lgamma, stirling, ilogb) of x[i], and normal[i]: the N(0,1) draw of the stream
+    (normal_seed, id i) (include/mmgibbs.h)."""
+    x = np.ascontiguousarray(x, np.float64).ravel()
+    out = {k: np.empty(x.size) for k in ("probit", "lgamma", "normal", "stirling")}
+    out["ilogb"] = np.empty(x.size, np.int32)
+    io = _lib.KeyedIO(n_math=x.size, x=_ptr(x), normal_seed=int(normal_seed), out_probit=_ptr(out["probit"]), out_lgamma=_ptr(out["lgamma"]),
+                      out_normal=_ptr(out["normal"]), out_stirling=_ptr(out["stirling"]), out_ilogb=_ptr(out["ilogb"]))
+    _keyed(device, io)
+    return out
+
+
+def selftest_keyed_words(w0, w1, t, device=-1):
+    """mmg_selftest_keyed, words: dict(u32: the uniform of word w0[i]; u52: of the pair (w0[i], w1[i]); target: the categorical draw's
+    target of word w0[i] over weights of total t[i])."""
+    w0, w1, t = np.broadcast_arrays(np.asarray(w0, np.uint32), np.asarray(w1, np.uint32), np.asarray(t, np.float64))
+    w0, w1, t = [np.ascontiguousarray(a).ravel() for a in (w0, w1, t)]
+    out = {k: np.empty(w0.size) for k in ("u32", "u52", "target")}
+    io = _lib.KeyedIO(n_words=w0.size, w0=_ptr(w0), w1=_ptr(w1), t=_ptr(t), out_u32=_ptr(out["u32"]), out_u52=_ptr(out["u52"]),
+                      out_target=_ptr(out["target"]))
+    _keyed(device, io)
+    return out

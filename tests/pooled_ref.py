@@ -23,7 +23,9 @@ Proportion mode (transcripts, isoforms without hits), p[c][s] = x / (the gene's 
   percentiles the order statistics of the pooled proportions
 
 `log` is np.log by default; the device tests pass the library's own logarithm (mmg_selftest_math) for bit identity.  `probit` is
-scipy's ndtri: the library evaluates AS 241 itself, so the two probit columns agree to that algorithm's accuracy, not bit for bit.
+scipy's ndtri by default: the library evaluates AS 241 itself, so against ndtri the two probit columns agree to that algorithm's
+accuracy; the device tests pass the transcription of AS 241 on the library's logarithm (tests/key_space_checks.py: probit_as241),
+against which they are bit-identical (the sums run in sample order on both sides).
 """
 import numpy as np
 

@@ -35,6 +35,7 @@ def test_struct_layouts_match_header():
     assert C.sizeof(_lib.Config) == 48
     assert C.sizeof(_lib.Timing) == 32
     assert C.sizeof(_lib.ProblemInfo) == 112
+    assert C.sizeof(_lib.KeyedIO) == 208
 
 
 def test_no_cpu_fallback_without_device():
@@ -52,7 +53,7 @@ def test_no_cpu_fallback_without_device():
 
 
 def test_argument_validation_happens_before_device_use():
-    from mmseq_amd import gibbs
+    from mmseq_amd import _lib, gibbs
     from mmseq_amd._lib import MMGError
     with pytest.raises(MMGError) as e:
         gibbs.Problem.from_csr(np.array([0, 2], np.uint64), np.array([0, 7], np.uint32), np.ones(3))
@@ -63,6 +64,14 @@ def test_argument_validation_happens_before_device_use():
     with pytest.raises(MMGError) as e:
         gibbs.Problem.from_csr(np.array([1, 1], np.uint64), np.array([0], np.uint32), np.ones(1))
     assert e.value.code == 1
+    # mmg_selftest_keyed: a part with a count needs every one of its arrays, also on a device that does not exist
+    lib = _lib.load()
+    x = np.ones(3)
+    for device in (-1, 0, 99):
+        assert lib.mmg_selftest_keyed(device, None) == 1
+        for io in (_lib.KeyedIO(n_math=3, x=x.ctypes.data), _lib.KeyedIO(n_streams=1), _lib.KeyedIO(n_words=-1)):
+            assert lib.mmg_selftest_keyed(device, C.byref(io)) == 1, device
+    assert lib.mmg_selftest_keyed(-1, C.byref(_lib.KeyedIO())) == 0          # nothing asked, nothing done
 
 
 def test_host_instantiation_of_library_math_equals_oracle(orc):

@@ -395,3 +395,27 @@ def test_timed_sampler_event_pool_failure(env, entries, fail_at):
         assert live() == base_live
     finally:
         lib.mmg_problem_destroy(p)
+
+
+@pytest.mark.gpu
+def test_chain_indices_beyond_the_gamma_streams_24_bits_are_refused(env, gpu):
+    """mmg_sampler_create: chain_base >= 0 and chain_base + n_chains <= 2^24 (MMG_MAX_CHAINS).  The key of K2's Gamma stream holds 24 bits of
+    the chain index, the row stream's all 32: chain 2^24 would redraw mu from chain 0's uniforms while drawing rows of its own
+    (tests/test_key_space.py::test_gamma_stream_sees_24_bits_of_the_chain).  The refusal comes before anything is acquired."""
+    from mmseq_amd._lib import MMGError
+    lib, free_mem, live = env
+    prob = gpu.Problem.synthetic(2000, 100, 4, seed=3)
+    mu0, _ = prob.start_values()
+    base_live = live()
+    for base, chains in ((-1, 1), (-2 ** 31, 1), (1 << 24, 1), ((1 << 24) - 2, 3), ((1 << 24) - 1, 2), (2 ** 31 - 1, 2)):
+        with pytest.raises(MMGError) as e:
+            gpu.Sampler(prob, mu0, n_chains=chains, chain_base=base, gibbs_iter=4, trace_len=4)
+        assert e.value.code == 1 and "16777216" in str(e.value) and "24 bits" in str(e.value), (base, chains)
+        assert live() == base_live
+    for base, chains in (((1 << 24) - 3, 3), ((1 << 24) - 1, 1), (0, 3)):
+        s = gpu.Sampler(prob, mu0, n_chains=chains, chain_base=base, gibbs_iter=4, trace_len=4)
+        s.run(4)
+        assert np.isfinite(s.mu(chains - 1)).all()
+        s.close()
+    assert live() == base_live
+    prob.close()

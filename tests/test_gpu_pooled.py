@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import pooled_ref as R
+from key_space_checks import probit_as241
 from oracle import host_oracle as H
 from test_cli import dataset
 from test_gpu_convergence import _ids, _mixed, _run, _same6, _sampler_case
@@ -147,7 +148,11 @@ def test_pooled_proportions_match_the_reference(gpu, case):
         ref = R.pooled_proportions(prop[:, sl].transpose(0, 2, 1), multi[sl], PIDX)
         _same(got, ref, ("mean", "percentiles"), "kind %d" % kind)
         mu, out = multi[sl], gene_of[sl] < 0
-        # the probit columns: the tolerance of tests/test_gpu_summary.py for the same columns of one chain (AS 241 against scipy's ndtri)
+        # the probit columns: bit for bit against AS 241 transcribed on the device's own logarithm, sums in sample order ...
+        exact = R.pooled_proportions(prop[:, sl].transpose(0, 2, 1), multi[sl], PIDX, probit=lambda p: probit_as241(p, _dlog(gpu)))
+        assert np.array_equal(got["probit_mean"][mu], exact["probit_mean"][mu]) and np.array_equal(got["probit_sd"][mu], exact["probit_sd"][mu])
+        assert mu.sum() > 30
+        # ... and to the accuracy of that algorithm against scipy's ndtri, as before
         np.testing.assert_allclose(got["probit_mean"][mu], ref["probit_mean"][mu], rtol=1e-9, atol=1e-12)
         np.testing.assert_allclose(got["probit_sd"][mu], ref["probit_sd"][mu], rtol=1e-7)
         assert np.isinf(got["probit_mean"][~mu]).all() and (got["probit_mean"][~mu] > 0).all() and np.isnan(got["probit_sd"][~mu]).all()

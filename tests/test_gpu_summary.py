@@ -1,9 +1,11 @@
 """The posterior summary computed on the device (mmg_summary_*, src/mmseq.cpp:927-1363) against numpy and the oracle's Sokal
 (which is pinned to the reference's own sokal.cc): trace sums, proportions, simulated traces and percentiles bit for bit (they
 are sums / quotients in the reference's order and order statistics of the trace itself), log means and Sokal to the rounding of
-log(), probit summaries to the accuracy of AS 241."""
+log(), probit summaries bit for bit against AS 241 transcribed on the device's logarithm (and to that algorithm's accuracy against scipy)."""
 import numpy as np
 import pytest
+
+from key_space_checks import probit_as241
 
 pytestmark = pytest.mark.gpu
 
@@ -85,6 +87,14 @@ def test_device_summary_matches_numpy_and_the_pinned_sokal(gpu, orc, tx_order):
         r = q.proportions(kind)
         assert np.array_equal(r["percentiles"], np.sort(pr, axis=1)[:, pidx])
         np.testing.assert_allclose(r["mean"], pr.mean(axis=1), rtol=1e-12)
+        # bit for bit: AS 241 transcribed on the device's own logarithm, the sums one addition after the other in sample order (:1237-1262)
+        z = probit_as241(np.clip(pr, 1e-9, 1 - 1e-9), lambda x: gpu.selftest_math(x, 0)["log"])
+        s1, s2 = np.add.accumulate(z, axis=1)[:, -1], np.add.accumulate(z * z, axis=1)[:, -1]
+        assert mu.sum() > 20
+        assert np.array_equal(r["probit_mean"][mu], (s1 / S)[mu])
+        with np.errstate(invalid="ignore"):                        # (genes of one transcript, not compared: a constant series whose variance may round below 0)
+            assert np.array_equal(r["probit_sd"][mu], np.sqrt((s2 - s1 * s1 / S) / (S - 1.0))[mu])
+        # ... and to the accuracy of AS 241 against scipy's ndtri, as before
         z = ndtri(np.clip(pr, 1e-9, 1 - 1e-9))
         s1, s2 = z.sum(axis=1), (z * z).sum(axis=1)
         np.testing.assert_allclose(r["probit_mean"][mu], (s1 / S)[mu], rtol=1e-9, atol=1e-12)
