@@ -85,7 +85,8 @@ extern "C" {
  *      of the hits (mmg_assign_*, MMG_OPT_ASSIGN_WAVES), and the posterior summary over the draws of all chains (mmg_pooled_*,
  *      MMG_OPT_POOL_SLAB), and the posterior correlation of pairs of transcripts (mmg_pairs_*, MMG_OPT_PAIRS_SLAB), and mmdiff's
  *      effect summaries (mmg_diff_effects_*, mmg_effects_*), and mmdiff's permutation null with its q-values (mmg_diff_perm_*,
- *      mmg_qvalues), and the self test of the streams' key space and of the scalar functions (mmg_selftest_keyed).
+ *      mmg_qvalues), and the self test of the streams' key space and of the scalar functions (mmg_selftest_keyed), and mmdiff's
+ *      likelihood-ratio test (mmg_diff_lrt_*).
  *      mmg_sampler_create refuses chains beyond 2^24: the Gamma stream's key holds 24 bits of the chain index (the row stream all 32), so
  *      chain 2^24 + c would redraw mu from chain c's uniforms.  No chain that ran before is changed by the check. */
 /* Layout.  The model does not care about the order of rows or the numbering of transcripts (src/mmseq.cpp:399-418 uses
@@ -894,6 +895,34 @@ void mmg_diff_perm_destroy(mmg_diff_perm *h);
  * An observed NaN gets q = NaN and null_ge = 0 and counts in no R; with m0 == 0 every q is NaN.
  * MMG_ERR_ARG for F == 0, n_null == 0, n_null > 2^31 - 1 or a NULL pointer. */
 int mmg_qvalues(int device, uint32_t F, const double *obs, uint64_t n_null, const double *null, uint64_t *null_ge, double *q);
+
+/* ---- mmdiff -lrt: the per-feature likelihood-ratio test ---------------------------------------------
+ * Both models of mmg_diff_create fitted by maximum likelihood, without priors: y_i ~ N((X_m theta_m)_i, e_i^2 + sigma^2_{C_m(i)}),
+ * X_m = [1 unless fixalpha | M unless nil | P_m unless nil] with p_m columns, theta_m free, sigma^2_c >= 0 per variance class;
+ * l_m = -1/2 sum_i [log 2 pi + log v_i + r_i^2 / v_i].  One lane per feature profiles theta by weighted least squares and moves
+ * sigma^2 by projected Fisher scoring with step halving, from sigma^2_c = the class mean of e_i^2, for at most max_iters scoring
+ * iterations per model (0: the default, 200).  No sampler, no stream: reruns are bit-identical.  The model sets are not checked for
+ * nesting.  Additive in ABI version 8. */
+typedef struct mmg_diff_lrt mmg_diff_lrt;
+/* Arguments, caps and refusals as mmg_diff_create (MMG_ERR_ARG with the same messages, before any device work).  The call computes
+ * everything, keeps the results on the host and holds no device memory when it returns. */
+int mmg_diff_lrt_create(int device, uint32_t n_features, uint32_t n_samples, const double *y, const double *e, uint32_t K, const double *M,
+                        uint32_t L0, const double *P0, uint32_t L1, const double *P1, const int32_t *C, int fixalpha, uint32_t max_iters,
+                        mmg_diff_lrt **out);
+/* loglik[2][F]; stat[F] = 2 (l_1 - l_0); df = (p_1 + classes_1) - (p_0 + classes_0); p_value[F] = Q(df / 2, max(stat, 0) / 2), NaN for
+ * df <= 0 or a NaN stat; q_value[F]: Benjamini-Hochberg over the p that are not NaN, ties in input order; theta0[p_0][F], theta1[p_1][F]
+ * in the column order of X_m; sigmasq0[classes_0][F], sigmasq1[classes_1][F]; iters[2][F] the scoring iterations used; status[2][F]
+ * bits: 1 the cap was reached before the stopping rule held, 2 X'WX is not positive definite or a weight is not finite (l, theta
+ * and sigma^2 of that model are NaN, iters 0; the bit stands alone), 4 some sigma^2_c is 0 (the estimate is on the boundary, where
+ * the chi-squared reference is conservative).  Any pointer may be NULL. */
+int mmg_diff_lrt_get(mmg_diff_lrt *h, double *loglik, double *stat, double *p_value, double *q_value, int32_t *df, double *theta0,
+                     double *theta1, double *sigmasq0, double *sigmasq1, uint32_t *iters, uint32_t *status);
+/* flags[3] as mmg_diff_info (M, P0, P1 nil), n_classes[2], n_cols[2] = p_0, p_1; any pointer may be NULL */
+int mmg_diff_lrt_info(mmg_diff_lrt *h, int32_t *flags, uint32_t *n_classes, uint32_t *n_cols);
+/* The peak during creation: 8 (2 F N + (N + F) (p_0 + p_1) + F (classes_0 + classes_1) + 2 F + F W) + 4 (2 N + 4 F) bytes, with
+ * W = 2 max(classes_0, classes_1) + (pm <= 4 ? 0 : pm (pm + 1) / 2) workspace slots per feature, pm = max(p_0, p_1). */
+int mmg_diff_lrt_device_bytes(mmg_diff_lrt *h, uint64_t *bytes);
+void mmg_diff_lrt_destroy(mmg_diff_lrt *h);
 
 #ifdef __cplusplus
 }

@@ -163,6 +163,12 @@ SYMBOLS = {
     "mmg_diff_info": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmg_diff_device_bytes": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mmg_diff_destroy": (None, [C.c_void_p]),
+    "mmg_diff_lrt_create": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
+                                      C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p]),
+    "mmg_diff_lrt_get": (C.c_int, [C.c_void_p] * 12),
+    "mmg_diff_lrt_info": (C.c_int, [C.c_void_p] * 4),
+    "mmg_diff_lrt_device_bytes": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mmg_diff_lrt_destroy": (None, [C.c_void_p]),
     "mmg_diff_trace_layout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmg_diff_trace_name": (C.c_int, [C.c_void_p, C.c_uint32, C.c_char_p, C.c_uint32]),
     "mmg_diff_trace_open": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),

@@ -2,6 +2,7 @@
 // src/mmdiff.cpp:744-866).  Kernels in diff_kernels.h.
 #include "diff_kernels.h"
 #include "diff_perm_kernels.h"
+#include "diff_lrt_kernels.h"
 #include "mmg_host.h"
 
 #include <cmath>
@@ -16,6 +17,8 @@ namespace {
 constexpr uint32_t DF_CHUNK = 512;    // iterations per launch of burn-in and sampling
 constexpr int DF_REC_FROM = 102;      // OUTLEN / 10: burn-in iterations before this one are not recorded
 }
+static_assert(LRT_KMAX == DF_KMAX && LRT_LMAX == DF_LMAX && LRT_CMAX == DF_CMAX && LRT_NMAX == DF_NMAX && LRT_BLOCK == DF_BLOCK,
+              "the likelihood-ratio test (diff_lrt_kernels.h) takes the designs mmg_diff_create takes");
 
 // What mmg_diff_trace_open adds to a handle: the copy stream, two row buffers on the device and two in pinned host memory, and the
 // events between them.  Launch i records into d_rows[i & 1]; the copy stream waits for it and copies to h_rows[i & 1]; the host hands
@@ -69,7 +72,7 @@ struct mmg_diff {
 };
 
 // the reference's "nil" rule (BMS::BMS): a single column whose entries differ by less than 1e-5 is no covariate at all
-static bool df_nil(const double *X, uint32_t N, uint32_t cols)
+bool mmg::df_nil(const double *X, uint32_t N, uint32_t cols)
 {
     if (cols != 1 || N == 0) return false;
     double lo = X[0], hi = X[0];
@@ -80,7 +83,7 @@ static bool df_nil(const double *X, uint32_t N, uint32_t cols)
 static inline unsigned df_blocks(uint32_t F) { return (F + DF_BLOCK - 1) / DF_BLOCK; }
 
 // the classes of one model, C[i * stride]: labels 0 .. *nc - 1, every one of them used
-static int df_classes(const int32_t *C, uint32_t stride, uint32_t N, int *nc)
+int mmg::df_classes(const int32_t *C, uint32_t stride, uint32_t N, int *nc)
 {
     std::vector<int> seen(DF_CMAX, 0);
     *nc = 0;

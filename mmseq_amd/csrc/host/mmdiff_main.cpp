@@ -144,6 +144,12 @@ void printUsage(ostream &out)
         << "                    repeated -m, -traces, -effects or -polyclass.  A shuffle only relabels samples: with few samples many" << endl
         << "                    shuffles reproduce the original grouping (a third of them for 2 vs 2), and the q-values are conservative" << endl
         << "  -permout STRING   with -permutations: write the mmdiff table of shuffled copy b to STRING.perm<b>.mmdiff" << endl
+        << "  -lrt STRING       file for the per-feature likelihood-ratio test of the two models (maximum likelihood, no priors, no MCMC):" << endl
+        << "                    loglik0, loglik1, lrt_stat, df, p_value (chi-squared with df degrees of freedom), q_value (Benjamini-" << endl
+        << "                    Hochberg), the estimates alpha, beta, eta, sigmasq of both models (NA for a term a model lacks), iters and" << endl
+        << "                    status per model (bits: 1 iteration cap reached, 2 singular design or weights: NaN, 4 some sigmasq is 0);" << endl
+        << "                    stdout is what it is without the flag; not with -chains, repeated -m, -permutations or -polyclass" << endl
+        << "  -lrtonly          with -lrt: skip the MCMC and leave stdout empty" << endl
         << "Size limits: 512 samples, 8 columns of M, 16 columns of P0 and P1, 16 variance classes per model, 16 alternatives (-m) per run, 16 chains. At most 31 permutations." << endl;
 }
 
@@ -1197,6 +1203,46 @@ void write_effects(const string &file, const vector<string> &features, const vec
     if (fclose(fp) != 0 || !ok) die("Error: couldn't write " + file);
 }
 
+// The likelihood-ratio table: a line per feature, in the order of the stdout table; the estimates are named as the trace files are,
+// NA where a model has no such term.
+void write_lrt(FILE *fp, const string &file, const vector<string> &features, const Design &D, bool fixalpha, mmg_diff_lrt *h)
+{
+    const size_t F = features.size();
+    int32_t flags[3] = {0, 0, 0}, df = 0;
+    uint32_t nc[2] = {0, 0}, pc[2] = {0, 0};
+    MMG_CHECK(mmg_diff_lrt_info(h, flags, nc, pc));
+    const bool Mnil = flags[0] != 0, Pnil[2] = {flags[1] != 0, flags[2] != 0};
+    const size_t L[2] = {D.L0, D.L1};
+    vector<double> ll(2 * F), stat(F), pv(F), qv(F), theta[2], sig[2];
+    vector<uint32_t> iters(2 * F), status(2 * F);
+    for (int m = 0; m < 2; ++m) { theta[m].resize((size_t)pc[m] * F); sig[m].resize((size_t)nc[m] * F); }
+    MMG_CHECK(mmg_diff_lrt_get(h, ll.data(), stat.data(), pv.data(), qv.data(), &df, theta[0].data(), theta[1].data(), sig[0].data(), sig[1].data(),
+                               iters.data(), status.data()));
+    string out = "feature_id\tloglik0\tloglik1\tlrt_stat\tdf\tp_value\tq_value\talpha0\talpha1";
+    for (int m = 0; m < 2; ++m)
+        for (size_t k = 0; k < D.K; ++k) out += "\tbeta" + to_string(m) + "_" + to_string(k);
+    for (int m = 0; m < 2; ++m)
+        for (size_t l = 0; l < L[m]; ++l) out += "\teta" + to_string(m) + "_" + to_string(l);
+    for (int m = 0; m < 2; ++m)
+        for (uint32_t c = 0; c < nc[m]; ++c) out += "\tsigmasq" + to_string(m) + "_" + to_string(c);
+    out += "\titers0\titers1\tstatus0\tstatus1\n";
+    bool ok = fputs(out.c_str(), fp) >= 0;
+    const size_t a_cols = fixalpha ? 0 : 1, b_cols = Mnil ? 0 : D.K;
+    for (size_t f = 0; f < F && ok; ++f) {
+        out = features[f] + "\t" + fmt(ll[f]) + "\t" + fmt(ll[F + f]) + "\t" + fmt(stat[f]) + "\t" + to_string(df) + "\t" + fmt(pv[f]) + "\t" + fmt(qv[f]);
+        for (int m = 0; m < 2; ++m) out += "\t" + (fixalpha ? string("NA") : fmt(theta[m][f]));
+        for (int m = 0; m < 2; ++m)
+            for (size_t k = 0; k < D.K; ++k) out += "\t" + (Mnil ? string("NA") : fmt(theta[m][(a_cols + k) * F + f]));
+        for (int m = 0; m < 2; ++m)
+            for (size_t l = 0; l < L[m]; ++l) out += "\t" + (Pnil[m] ? string("NA") : fmt(theta[m][(a_cols + b_cols + l) * F + f]));
+        for (int m = 0; m < 2; ++m)
+            for (uint32_t c = 0; c < nc[m]; ++c) out += "\t" + fmt(sig[m][(size_t)c * F + f]);
+        out += "\t" + to_string(iters[f]) + "\t" + to_string(iters[F + f]) + "\t" + to_string(status[f]) + "\t" + to_string(status[F + f]) + "\n";
+        ok = fputs(out.c_str(), fp) >= 0;
+    }
+    if (fflush(fp) != 0 || !ok) die("Error: couldn't write " + file);
+}
+
 } // namespace
 
 int main(int argc, char **argv)
@@ -1204,7 +1250,8 @@ int main(int argc, char **argv)
     string matrices_file = "";
     vector<string> matrices_files;   // every -m; more than one: the polytomous run
     bool polyclass_mode = false, prior_given = false, polyout_given = false, chains_given = false, chainout_given = false, perms_given = false, permout_given = false;
-    string prior_text, polyout, chainout, permout, traces, effects, effects_pct_text = "2.5,50,97.5";
+    string prior_text, polyout, chainout, permout, traces, effects, effects_pct_text = "2.5,50,97.5", lrt_file;
+    bool lrt_given = false, lrt_only = false;
     bool effects_every_given = false, effects_pct_given = false;
     long effects_every = 0;
     int chains = 1, perms = 0;
@@ -1229,6 +1276,13 @@ int main(int argc, char **argv)
         } else if (a0 == "-effects") {
             effects = take();
             if (effects.empty()) die("Error: -effects needs a file name.");
+        } else if (a0 == "-lrt") {
+            lrt_file = take();
+            if (lrt_file.empty()) die("Error: -lrt needs a file name.");
+            lrt_given = true;
+        } else if (a0 == "-lrtonly") {
+            arguments.erase(arguments.begin());
+            lrt_only = true;
         } else if (a0 == "-effects_every") {
             const string v = take();
             char *end = NULL;
@@ -1388,6 +1442,9 @@ int main(int argc, char **argv)
     if (permout_given && !perms_given) usage_error("Error: -permout needs -permutations.");
     if (perms_given && (permute || chains > 1 || chainout_given || poly_run || polyclass_mode || !traces.empty() || !effects.empty()))
         usage_error("Error: -permutations cannot be combined with -permute, -chains above 1 (or -chainout), more than one -m, -traces, -effects or -polyclass.");
+    if (lrt_only && !lrt_given) usage_error("Error: -lrtonly needs -lrt.");
+    if ((lrt_given || lrt_only) && (chains_given || poly_run || perms_given || polyclass_mode))
+        usage_error("Error: -lrt and -lrtonly cannot be combined with -chains, more than one -m, -permutations or -polyclass.");
     vector<double> effects_pct;
     if (!effects.empty()) effects_pct = parse_percentiles(effects_pct_text);
     if (polyclass_mode) {
@@ -1475,10 +1532,22 @@ int main(int argc, char **argv)
     struct Closer { FILE *f = nullptr; ~Closer() { if (f) fclose(f); } } chain0;
     const string chain0_name = chainout + ".chain0.mmdiff";
     if (chainout_given && !(chain0.f = fopen(chain0_name.c_str(), "w"))) die("Error: couldn't create " + chain0_name);
+    Closer lrt_out;
+    if (lrt_given && !(lrt_out.f = fopen(lrt_file.c_str(), "w"))) die("Error: couldn't create " + lrt_file);
 
     // every input is checked: now the device
     int ndev = 0;
     if (mmg_device_count(&ndev) != 0 || ndev < 1) die("Error: no HIP device available: mmdiff has no CPU fallback");
+    if (lrt_given) {
+        // the same y, e and design the chain gets
+        mmg_diff_lrt *lh = nullptr;
+        MMG_CHECK(mmg_diff_lrt_create(0, (uint32_t)F, (uint32_t)S, y.data(), e.data(), (uint32_t)D.K, D.M.data(), (uint32_t)D.L0, D.P0.data(),
+                                      (uint32_t)D.L1, D.P1.data(), D.C.data(), fixalpha ? 1 : 0, 0, &lh));
+        write_lrt(lrt_out.f, lrt_file, features, D, fixalpha, lh);
+        mmg_diff_lrt_destroy(lh);
+        cerr << "Wrote the likelihood-ratio tests of " << F << " features to " << lrt_file << "\n";
+        if (lrt_only) return 0;
+    }
     mmg_diff *h = nullptr;
     MMG_CHECK(mmg_diff_create(0, (uint32_t)F, (uint32_t)S, y.data(), e.data(), (uint32_t)D.K, D.M.data(), (uint32_t)D.L0, D.P0.data(),
                               (uint32_t)D.L1, D.P1.data(), D.C.data(), d, s, pdash, fixalpha ? 1 : 0, useed, &h));

@@ -313,6 +313,11 @@ int qvalue_stat_on_device(hipStream_t st, const double *d_st, size_t stride, int
                           double *d_stat);
 int qvalues_on_device(hipStream_t st, uint32_t F, const double *d_obs, uint64_t n_null, const double *d_null, uint64_t *d_null_ge, double *d_q);
 
+// mmdiff's design rules (diff.hip), shared with the likelihood-ratio test (diff_lrt.hip).  df_nil: the reference's "nil" rule.
+// df_classes: the classes of one model, C[i * stride]: labels 0 .. *nc - 1, every one of them used (MMG_ERR_ARG otherwise).
+bool df_nil(const double *X, uint32_t N, uint32_t cols);
+int df_classes(const int32_t *C, uint32_t stride, uint32_t N, int *nc);
+
 int require_device(int device);
 void weighted_chunks(const std::vector<uint64_t> &cum, uint64_t grid, std::vector<uint64_t> &chunk);
 void weighted_chunks_tapered(const std::vector<uint64_t> &cum, uint64_t grid, uint64_t resident, std::vector<uint64_t> &chunk);

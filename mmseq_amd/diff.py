@@ -3,7 +3,8 @@
 `Diff` holds every feature's MCMC state on the device (src/bms.cpp driven as src/mmdiff.cpp:744-866): `burnin` runs the burn-in and
 sets the pseudopriors, `tune_batch` one tuning batch of 128 iterations, `sample` the sampling iterations, `results` the posterior
 means.  `DiffPoly` runs several alternatives against one model 0 on one handle, `DiffChains` several chains of one comparison, `DiffPerm` the data and
-its shuffled copies with q-values (`qvalues` computes them for any two arrays of statistics).  No CPU path exists: without a device every call raises.
+its shuffled copies with q-values (`qvalues` computes them for any two arrays of statistics), `DiffLrt` fits both models by maximum
+likelihood and gives the likelihood-ratio test of every feature.  No CPU path exists: without a device every call raises.
 """
 import ctypes as C
 
@@ -457,6 +458,66 @@ class DiffPerm:
     def close(self):
         if self._h:
             self._lib.mmg_diff_perm_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DiffLrt:
+    """The per-feature likelihood-ratio test of `Diff`'s two models (the mmg_diff_lrt_* entries): both fitted by maximum likelihood,
+    without priors, on the device; no sampler and no stream.  The constructor computes everything and the handle keeps the results
+    on the host.  tests/mmdiff_lrt_ref.py restates it."""
+
+    def __init__(self, y, e, M, P0, P1, classes, fixalpha=False, max_iters=0, device=0):
+        """y, e, M, P0, P1, classes as for `Diff`; max_iters: the cap on scoring iterations per model (0: the default, 200)."""
+        self._lib = _lib.load()
+        self._h = None
+        y = np.ascontiguousarray(y, np.float64)
+        e = np.ascontiguousarray(e, np.float64)
+        M = np.ascontiguousarray(M, np.float64)
+        P = [np.ascontiguousarray(P0, np.float64), np.ascontiguousarray(P1, np.float64)]
+        Cl = np.ascontiguousarray(classes, np.int32)
+        F, N = y.shape
+        if e.shape != (F, N) or M.shape[0] != N or P[0].shape[0] != N or P[1].shape[0] != N or Cl.shape != (N, 2):
+            raise ValueError("inconsistent shapes")
+        self.F, self.N, self.K = F, N, M.shape[1]
+        self.L = (P[0].shape[1], P[1].shape[1])
+        h = C.c_void_p()
+        check(self._lib.mmg_diff_lrt_create(device, F, N, _ptr(y), _ptr(e), self.K, _ptr(M), self.L[0], _ptr(P[0]), self.L[1], _ptr(P[1]),
+                                            _ptr(Cl), int(bool(fixalpha)), int(max_iters), C.byref(h)))
+        self._h = h
+
+    def info(self):
+        flags, nc, p = (C.c_int32 * 3)(), (C.c_uint32 * 2)(), (C.c_uint32 * 2)()
+        check(self._lib.mmg_diff_lrt_info(self._h, flags, nc, p))
+        return dict(Mnil=bool(flags[0]), Pnil=(bool(flags[1]), bool(flags[2])), n_classes=(nc[0], nc[1]), n_cols=(p[0], p[1]))
+
+    def results(self):
+        """dict: loglik (2, F), stat, p_value, q_value (F,), df, theta0 (p0, F), theta1 (p1, F) in the column order
+        [alpha | beta | eta] of the terms the model has, sigmasq0 (classes0, F), sigmasq1, iters and status (2, F)."""
+        F, i = self.F, self.info()
+        out = dict(loglik=np.empty((2, F)), stat=np.empty(F), p_value=np.empty(F), q_value=np.empty(F), theta0=np.empty((i["n_cols"][0], F)),
+                   theta1=np.empty((i["n_cols"][1], F)), sigmasq0=np.empty((i["n_classes"][0], F)), sigmasq1=np.empty((i["n_classes"][1], F)),
+                   iters=np.empty((2, F), np.uint32), status=np.empty((2, F), np.uint32))
+        df = C.c_int32()
+        check(self._lib.mmg_diff_lrt_get(self._h, _ptr(out["loglik"]), _ptr(out["stat"]), _ptr(out["p_value"]), _ptr(out["q_value"]), C.byref(df),
+                                         *(_ptr(out[k]) for k in ("theta0", "theta1", "sigmasq0", "sigmasq1", "iters", "status"))))
+        out["df"] = df.value
+        out["n_cols"], out["n_classes"] = i["n_cols"], i["n_classes"]
+        return out
+
+    def device_bytes(self):
+        b = C.c_uint64()
+        check(self._lib.mmg_diff_lrt_device_bytes(self._h, C.byref(b)))
+        return b.value
+
+    def close(self):
+        if self._h:
+            self._lib.mmg_diff_lrt_destroy(self._h)
             self._h = None
 
     def __del__(self):
