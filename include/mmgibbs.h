@@ -86,7 +86,7 @@ extern "C" {
  *      MMG_OPT_POOL_SLAB), and the posterior correlation of pairs of transcripts (mmg_pairs_*, MMG_OPT_PAIRS_SLAB), and mmdiff's
  *      effect summaries (mmg_diff_effects_*, mmg_effects_*), and mmdiff's permutation null with its q-values (mmg_diff_perm_*,
  *      mmg_qvalues), and the self test of the streams' key space and of the scalar functions (mmg_selftest_keyed), and mmdiff's
- *      likelihood-ratio test (mmg_diff_lrt_*).
+ *      likelihood-ratio test (mmg_diff_lrt_*) with its permutation null (mmg_diff_lrt_perm_*).
  *      mmg_sampler_create refuses chains beyond 2^24: the Gamma stream's key holds 24 bits of the chain index (the row stream all 32), so
  *      chain 2^24 + c would redraw mu from chain c's uniforms.  No chain that ran before is changed by the check. */
 /* Layout.  The model does not care about the order of rows or the numbering of transcripts (src/mmseq.cpp:399-418 uses
@@ -923,6 +923,38 @@ int mmg_diff_lrt_info(mmg_diff_lrt *h, int32_t *flags, uint32_t *n_classes, uint
  * W = 2 max(classes_0, classes_1) + (pm <= 4 ? 0 : pm (pm + 1) / 2) workspace slots per feature, pm = max(p_0, p_1). */
 int mmg_diff_lrt_device_bytes(mmg_diff_lrt *h, uint64_t *bytes);
 void mmg_diff_lrt_destroy(mmg_diff_lrt *h);
+
+/* ---- mmdiff -lrt FILE -lrtperm B: a permutation null for the likelihood-ratio test ------------------
+ * The test of mmg_diff_lrt_create on the data (copy 0) and on B shuffled copies of it.  Copy b = 1 .. B is the data with every
+ * feature's samples shuffled as replica b of mmg_diff_perm_create shuffles them (a Fisher-Yates keyed (seed, b, feature), y and e moved
+ * together); its statistic T[b][f] = 2 (l_1 - l_0) is, bit for bit, the stat of mmg_diff_lrt_create on that copy, NaN where a fit has
+ * status 2.  The copies are fitted slab_copies at a time (0: as many as keep the slab and its workspace under 1 GiB, at least 1);
+ * no result depends on it.  Additive in ABI version 8. */
+typedef struct mmg_diff_lrt_perm mmg_diff_lrt_perm;
+/* Arguments, caps, refusals and messages as mmg_diff_lrt_create; also MMG_ERR_ARG, before any device work, for n_perm outside
+ * 1 .. 65535 and for n_perm * n_features > 2^31 - 1 (mmg_qvalues' cap on the null).  The call computes everything, keeps the results
+ * on the host and holds no device memory when it returns. */
+int mmg_diff_lrt_perm_create(int device, uint32_t n_features, uint32_t n_samples, const double *y, const double *e, uint32_t K, const double *M,
+                             uint32_t L0, const double *P0, uint32_t L1, const double *P1, const int32_t *C, int fixalpha, uint32_t max_iters,
+                             uint32_t n_perm, uint64_t seed, uint32_t slab_copies, mmg_diff_lrt_perm **out);
+/* The test on the data: every output bit-identical to mmg_diff_lrt_create on the same arguments.  Borrowed: read it with
+ * mmg_diff_lrt_get / _info / _device_bytes, do not destroy it; it goes with h. */
+mmg_diff_lrt *mmg_diff_lrt_perm_observed(mmg_diff_lrt_perm *h);
+/* Per feature against its own copies: perm_ge[F] = #{b : T[b][f] >= T[0][f]}, perm_n[F] = #{b : T[b][f] is not NaN},
+ * perm_p[F] = (double)(1 + perm_ge) / (double)(1 + perm_n); a NaN copy counts in neither, -0.0 equals 0.0, an observed NaN gives
+ * perm_p NaN and perm_ge 0.  Pooled: null_ge[F], q_perm[F] = mmg_qvalues(obs = T[0][.], null = T[1 .. B][.]).  Any pointer may be NULL. */
+int mmg_diff_lrt_perm_get(mmg_diff_lrt_perm *h, uint64_t *perm_ge, uint64_t *perm_n, double *perm_p, uint64_t *null_ge, double *q_perm);
+/* Copies b0 + 1 .. b0 + nb: stat[nb][F] and status[nb][F] = status0 | status1 << 4 (the bits of mmg_diff_lrt_get).  MMG_ERR_ARG for
+ * b0 + nb > B; either pointer may be NULL. */
+int mmg_diff_lrt_perm_get_null(mmg_diff_lrt_perm *h, uint32_t b0, uint32_t nb, double *stat, uint8_t *status);
+/* The peak of the handle's own device memory during creation: mmg_diff_lrt_device_bytes of the observed test
+ *   + 8 Sc F (2 N + W') + 9 B F + 48 F bytes,
+ * with Sc the copies of one slab (y and e^2 of each, [Sc][N][F]), W' = 3 max(classes_0, classes_1) + (pm <= 4 ? 0 : pm (pm + 1) / 2 + pm)
+ * workspace slots per copy and feature, 9 B F the statistics and status bytes of the copies, 48 F the six per-feature results.  The
+ * slab and its workspace are released before the q-values; mmg_qvalues' working memory (40 F + 16 B F + 16 bytes and the sorts') is
+ * taken and given back inside the call and not counted. */
+int mmg_diff_lrt_perm_device_bytes(mmg_diff_lrt_perm *h, uint64_t *bytes);
+void mmg_diff_lrt_perm_destroy(mmg_diff_lrt_perm *h);
 
 #ifdef __cplusplus
 }

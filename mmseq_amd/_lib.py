@@ -169,6 +169,13 @@ SYMBOLS = {
     "mmg_diff_lrt_info": (C.c_int, [C.c_void_p] * 4),
     "mmg_diff_lrt_device_bytes": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mmg_diff_lrt_destroy": (None, [C.c_void_p]),
+    "mmg_diff_lrt_perm_create": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
+                                           C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p]),
+    "mmg_diff_lrt_perm_observed": (C.c_void_p, [C.c_void_p]),
+    "mmg_diff_lrt_perm_get": (C.c_int, [C.c_void_p] * 6),
+    "mmg_diff_lrt_perm_get_null": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "mmg_diff_lrt_perm_device_bytes": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mmg_diff_lrt_perm_destroy": (None, [C.c_void_p]),
     "mmg_diff_trace_layout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmg_diff_trace_name": (C.c_int, [C.c_void_p, C.c_uint32, C.c_char_p, C.c_uint32]),
     "mmg_diff_trace_open": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),

@@ -1,25 +1,13 @@
 // diff_lrt.hip -- device TU + host side of the mmg_diff_lrt_* entry points: mmdiff's per-feature likelihood-ratio test
 // (DESIGN.md section 10.5).  Kernels in diff_lrt_kernels.h; the p- and q-values in host/lrt_stats.hpp.
-#include "diff_lrt_kernels.h"
+#include "diff_lrt_host.h"
 #include "host/lrt_stats.hpp"
-#include "mmg_host.h"
 
 #include <cmath>
 #include <memory>
 #include <vector>
 
 using namespace mmg;
-
-// Creation computes everything; the handle keeps the results on the host and no device memory.
-struct mmg_diff_lrt {
-    uint32_t F = 0;
-    int32_t flags[3] = {0, 0, 0};
-    uint32_t nc[2] = {0, 0}, p[2] = {0, 0};
-    int32_t df = 0;
-    uint64_t device_bytes = 0;
-    std::vector<double> ll, stat, pv, qv, theta[2], sig[2];
-    std::vector<uint32_t> iters, status;
-};
 
 // X_m = [1 unless fixalpha | M unless nil | P_m unless nil], [N][p]
 static std::vector<double> lrt_design(uint32_t N, bool fixalpha, bool Mnil, uint32_t K, const double *M, bool Pnil, uint32_t L, const double *P,
@@ -37,12 +25,11 @@ static std::vector<double> lrt_design(uint32_t N, bool fixalpha, bool Mnil, uint
     return X;
 }
 
-extern "C" int mmg_diff_lrt_create(int device, uint32_t F, uint32_t N, const double *y, const double *e, uint32_t K, const double *M,
-                                   uint32_t L0, const double *P0, uint32_t L1, const double *P1, const int32_t *C, int fixalpha,
-                                   uint32_t max_iters, mmg_diff_lrt **out)
+namespace mmg {
+
+int lrt_check_args(int device, uint32_t F, uint32_t N, const double *y, const double *e, uint32_t K, const double *M, uint32_t L0, const double *P0,
+                   uint32_t L1, const double *P1, const int32_t *C, int nc[2])
 {
-    if (!out || !y || !e || !M || !P0 || !P1 || !C) return fail(MMG_ERR_ARG, "NULL argument");
-    *out = nullptr;
     if (F == 0 || F > 0x7fffff00u / LRT_BLOCK) return fail(MMG_ERR_ARG, "the number of features must be between 1 and 33554428");
     if (N < 2 || N > (uint32_t)LRT_NMAX) return fail(MMG_ERR_ARG, "the number of samples must be between 2 and 512");
     if (K < 1 || K > (uint32_t)LRT_KMAX) return fail(MMG_ERR_ARG, "M must have between 1 and 8 columns");
@@ -50,15 +37,17 @@ extern "C" int mmg_diff_lrt_create(int device, uint32_t F, uint32_t N, const dou
     auto finite = [](const double *x, uint64_t n) { for (uint64_t i = 0; i < n; ++i) if (!std::isfinite(x[i])) return false; return true; };
     if (!finite(y, (uint64_t)F * N) || !finite(e, (uint64_t)F * N)) return fail(MMG_ERR_ARG, "y and e must be finite");
     if (!finite(M, (uint64_t)N * K) || !finite(P0, (uint64_t)N * L0) || !finite(P1, (uint64_t)N * L1)) return fail(MMG_ERR_ARG, "M, P0 and P1 must be finite");
-    int nc[2] = {0, 0};
+    nc[0] = nc[1] = 0;
     for (int mi = 0; mi < 2; ++mi) {
         const int rc = df_classes(C + mi, 2, N, &nc[mi]);
         if (rc) return rc;
     }
-    int rc = require_device(device);
-    if (rc) return rc;
+    return require_device(device);
+}
 
-    std::unique_ptr<mmg_diff_lrt> h(new mmg_diff_lrt());
+int lrt_observed(int device, uint32_t F, uint32_t N, const double *y, const double *e, uint32_t K, const double *M, uint32_t L0, const double *P0,
+                 uint32_t L1, const double *P1, const int32_t *C, const int nc[2], int fixalpha, uint32_t max_iters, mmg_diff_lrt *h, LrtDevice &D)
+{
     h->F = F;
     const bool Mnil = df_nil(M, N, K), Pnil[2] = {df_nil(P0, N, L0), df_nil(P1, N, L1)};
     h->flags[0] = Mnil; h->flags[1] = Pnil[0]; h->flags[2] = Pnil[1];
@@ -71,15 +60,15 @@ extern "C" int mmg_diff_lrt_create(int device, uint32_t F, uint32_t N, const dou
     const bool small = pm <= (uint32_t)LRT_PSMALL;
     const uint64_t wslots = 2ull * ncmax + (small ? 0 : (uint64_t)pm * (pm + 1) / 2);
 
-    // everything below is released when this function returns: the owners are locals (the host sources of the asynchronous copies
-    // first, so they outlive the stream's work; `drain`, the last local, waits for the stream before anything goes)
+    // the device arrays are the caller's (D) and go when it lets them; the host sources of the asynchronous copies are locals, and
+    // `drain`, the last local, waits for the stream before they go
     const uint64_t FN = (uint64_t)F * N;
     std::vector<double> ty(FN), te(FN);
     std::vector<int> cls(2 * (size_t)N);
-    DevStream st;
-    DevBuf<double> d_y, d_esq, d_X[2], d_theta[2], d_sig[2], d_ll, d_ws;
-    DevBuf<int> d_cls;
-    DevBuf<uint32_t> d_iters, d_status;
+    DevStream &st = D.st;
+    DevBuf<double> &d_y = D.d_y, &d_esq = D.d_esq, (&d_X)[2] = D.d_X, (&d_theta)[2] = D.d_theta, (&d_sig)[2] = D.d_sig, &d_ll = D.d_ll, &d_ws = D.d_ws;
+    DevBuf<int> &d_cls = D.d_cls;
+    DevBuf<uint32_t> &d_iters = D.d_iters, &d_status = D.d_status;
     auto dalloc = [&](auto &buf, uint64_t count) {
         if (count == 0) return hipSuccess;   // (a model without columns: the pointer is never read)
         HIPE_TRY(buf.alloc(count));
@@ -115,7 +104,8 @@ extern "C" int mmg_diff_lrt_create(int device, uint32_t F, uint32_t N, const dou
         if (h->p[mi]) HIP_TRY(hipMemcpyAsync(d_X[mi].get(), X[mi].data(), X[mi].size() * 8, hipMemcpyHostToDevice, st.get()));
     HIP_TRY(hipMemcpyAsync(d_cls.get(), cls.data(), cls.size() * 4, hipMemcpyHostToDevice, st.get()));
 
-    LrtParams q{};
+    LrtParams &q = D.q;
+    D.small = small; D.pm = pm;
     q.F = (int)F; q.N = (int)N;
     q.p[0] = (int)h->p[0]; q.p[1] = (int)h->p[1];
     q.nc[0] = nc[0]; q.nc[1] = nc[1];
@@ -149,6 +139,24 @@ extern "C" int mmg_diff_lrt_create(int device, uint32_t F, uint32_t N, const dou
         h->pv[f] = lrt::chi2_sf(h->df, h->stat[f]);
     }
     lrt::bh_qvalues(F, h->pv.data(), h->qv.data());
+    return MMG_OK;
+}
+
+} // namespace mmg
+
+extern "C" int mmg_diff_lrt_create(int device, uint32_t F, uint32_t N, const double *y, const double *e, uint32_t K, const double *M,
+                                   uint32_t L0, const double *P0, uint32_t L1, const double *P1, const int32_t *C, int fixalpha,
+                                   uint32_t max_iters, mmg_diff_lrt **out)
+{
+    if (!out || !y || !e || !M || !P0 || !P1 || !C) return fail(MMG_ERR_ARG, "NULL argument");
+    *out = nullptr;
+    int nc[2] = {0, 0};
+    int rc = lrt_check_args(device, F, N, y, e, K, M, L0, P0, L1, P1, C, nc);
+    if (rc) return rc;
+    std::unique_ptr<mmg_diff_lrt> h(new mmg_diff_lrt());
+    LrtDevice D;   // released when this function returns
+    rc = lrt_observed(device, F, N, y, e, K, M, L0, P0, L1, P1, C, nc, fixalpha, max_iters, h.get(), D);
+    if (rc) return rc;
     *out = h.release();
     return MMG_OK;
 }

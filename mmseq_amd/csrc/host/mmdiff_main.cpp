@@ -49,6 +49,7 @@ using namespace std;
 #define MAXMODELS 16   // alternatives (-m) in one run
 #define MAXCHAINS 16   // chains (-chains) in one run
 #define MAXPERMS 31    // shuffled replicas (-permutations) in one run
+#define MAXLRTPERMS 65535   // shuffled copies of the likelihood-ratio test (-lrtperm)
 
 namespace {
 
@@ -150,6 +151,12 @@ void printUsage(ostream &out)
         << "                    status per model (bits: 1 iteration cap reached, 2 singular design or weights: NaN, 4 some sigmasq is 0);" << endl
         << "                    stdout is what it is without the flag; not with -chains, repeated -m, -permutations or -polyclass" << endl
         << "  -lrtonly          with -lrt: skip the MCMC and leave stdout empty" << endl
+        << "  -lrtperm INT      with -lrt: repeat the test on INT (1 to 65535, INT x features at most 2147483647) copies of the data whose" << endl
+        << "                    samples are shuffled per feature (copy b as -permutations shuffles its copy b) and append to the file" << endl
+        << "                    perm_ge (the feature's own shuffled lrt_stat not below its lrt_stat), perm_p ((1 + perm_ge) / (1 + the" << endl
+        << "                    copies whose lrt_stat is not NaN)), null_ge (the shuffled lrt_stat of all copies and features not below it)" << endl
+        << "                    and q_perm (as -permutations forms q_value); not with -permute.  With few samples many shuffles" << endl
+        << "                    reproduce the original grouping, and this null is conservative too" << endl
         << "Size limits: 512 samples, 8 columns of M, 16 columns of P0 and P1, 16 variance classes per model, 16 alternatives (-m) per run, 16 chains. At most 31 permutations." << endl;
 }
 
@@ -1205,7 +1212,8 @@ void write_effects(const string &file, const vector<string> &features, const vec
 
 // The likelihood-ratio table: a line per feature, in the order of the stdout table; the estimates are named as the trace files are,
 // NA where a model has no such term.
-void write_lrt(FILE *fp, const string &file, const vector<string> &features, const Design &D, bool fixalpha, mmg_diff_lrt *h)
+void write_lrt(FILE *fp, const string &file, const vector<string> &features, const Design &D, bool fixalpha, mmg_diff_lrt *h,
+               mmg_diff_lrt_perm *perm = nullptr)
 {
     const size_t F = features.size();
     int32_t flags[3] = {0, 0, 0}, df = 0;
@@ -1218,6 +1226,10 @@ void write_lrt(FILE *fp, const string &file, const vector<string> &features, con
     for (int m = 0; m < 2; ++m) { theta[m].resize((size_t)pc[m] * F); sig[m].resize((size_t)nc[m] * F); }
     MMG_CHECK(mmg_diff_lrt_get(h, ll.data(), stat.data(), pv.data(), qv.data(), &df, theta[0].data(), theta[1].data(), sig[0].data(), sig[1].data(),
                                iters.data(), status.data()));
+    // -lrtperm: four columns after the plain line
+    vector<uint64_t> perm_ge(perm ? F : 0), null_ge(perm ? F : 0);
+    vector<double> perm_p(perm ? F : 0), q_perm(perm ? F : 0);
+    if (perm) MMG_CHECK(mmg_diff_lrt_perm_get(perm, perm_ge.data(), NULL, perm_p.data(), null_ge.data(), q_perm.data()));
     string out = "feature_id\tloglik0\tloglik1\tlrt_stat\tdf\tp_value\tq_value\talpha0\talpha1";
     for (int m = 0; m < 2; ++m)
         for (size_t k = 0; k < D.K; ++k) out += "\tbeta" + to_string(m) + "_" + to_string(k);
@@ -1225,7 +1237,9 @@ void write_lrt(FILE *fp, const string &file, const vector<string> &features, con
         for (size_t l = 0; l < L[m]; ++l) out += "\teta" + to_string(m) + "_" + to_string(l);
     for (int m = 0; m < 2; ++m)
         for (uint32_t c = 0; c < nc[m]; ++c) out += "\tsigmasq" + to_string(m) + "_" + to_string(c);
-    out += "\titers0\titers1\tstatus0\tstatus1\n";
+    out += "\titers0\titers1\tstatus0\tstatus1";
+    if (perm) out += "\tperm_ge\tperm_p\tnull_ge\tq_perm";
+    out += "\n";
     bool ok = fputs(out.c_str(), fp) >= 0;
     const size_t a_cols = fixalpha ? 0 : 1, b_cols = Mnil ? 0 : D.K;
     for (size_t f = 0; f < F && ok; ++f) {
@@ -1237,7 +1251,9 @@ void write_lrt(FILE *fp, const string &file, const vector<string> &features, con
             for (size_t l = 0; l < L[m]; ++l) out += "\t" + (Pnil[m] ? string("NA") : fmt(theta[m][(a_cols + b_cols + l) * F + f]));
         for (int m = 0; m < 2; ++m)
             for (uint32_t c = 0; c < nc[m]; ++c) out += "\t" + fmt(sig[m][(size_t)c * F + f]);
-        out += "\t" + to_string(iters[f]) + "\t" + to_string(iters[F + f]) + "\t" + to_string(status[f]) + "\t" + to_string(status[F + f]) + "\n";
+        out += "\t" + to_string(iters[f]) + "\t" + to_string(iters[F + f]) + "\t" + to_string(status[f]) + "\t" + to_string(status[F + f]);
+        if (perm) out += "\t" + to_string(perm_ge[f]) + "\t" + fmt(perm_p[f]) + "\t" + to_string(null_ge[f]) + "\t" + fmt(q_perm[f]);
+        out += "\n";
         ok = fputs(out.c_str(), fp) >= 0;
     }
     if (fflush(fp) != 0 || !ok) die("Error: couldn't write " + file);
@@ -1251,7 +1267,8 @@ int main(int argc, char **argv)
     vector<string> matrices_files;   // every -m; more than one: the polytomous run
     bool polyclass_mode = false, prior_given = false, polyout_given = false, chains_given = false, chainout_given = false, perms_given = false, permout_given = false;
     string prior_text, polyout, chainout, permout, traces, effects, effects_pct_text = "2.5,50,97.5", lrt_file;
-    bool lrt_given = false, lrt_only = false;
+    bool lrt_given = false, lrt_only = false, lrtperm_given = false;
+    long lrt_perms = 0;
     bool effects_every_given = false, effects_pct_given = false;
     long effects_every = 0;
     int chains = 1, perms = 0;
@@ -1283,6 +1300,13 @@ int main(int argc, char **argv)
         } else if (a0 == "-lrtonly") {
             arguments.erase(arguments.begin());
             lrt_only = true;
+        } else if (a0 == "-lrtperm") {
+            const string v = take();
+            char *end = NULL;
+            lrt_perms = strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end != '\0' || lrt_perms < 1 || lrt_perms > MAXLRTPERMS)
+                usage_error("Error: -lrtperm takes an integer between 1 and " + to_string(MAXLRTPERMS) + ".");
+            lrtperm_given = true;
         } else if (a0 == "-effects_every") {
             const string v = take();
             char *end = NULL;
@@ -1445,6 +1469,8 @@ int main(int argc, char **argv)
     if (lrt_only && !lrt_given) usage_error("Error: -lrtonly needs -lrt.");
     if ((lrt_given || lrt_only) && (chains_given || poly_run || perms_given || polyclass_mode))
         usage_error("Error: -lrt and -lrtonly cannot be combined with -chains, more than one -m, -permutations or -polyclass.");
+    if (lrtperm_given && !lrt_given) usage_error("Error: -lrtperm needs -lrt.");
+    if (lrtperm_given && permute) usage_error("Error: -lrtperm cannot be combined with -permute.");
     vector<double> effects_pct;
     if (!effects.empty()) effects_pct = parse_percentiles(effects_pct_text);
     if (polyclass_mode) {
@@ -1541,10 +1567,30 @@ int main(int argc, char **argv)
     if (lrt_given) {
         // the same y, e and design the chain gets
         mmg_diff_lrt *lh = nullptr;
-        MMG_CHECK(mmg_diff_lrt_create(0, (uint32_t)F, (uint32_t)S, y.data(), e.data(), (uint32_t)D.K, D.M.data(), (uint32_t)D.L0, D.P0.data(),
-                                      (uint32_t)D.L1, D.P1.data(), D.C.data(), fixalpha ? 1 : 0, 0, &lh));
-        write_lrt(lrt_out.f, lrt_file, features, D, fixalpha, lh);
-        mmg_diff_lrt_destroy(lh);
+        mmg_diff_lrt_perm *ph = nullptr;
+        if (lrtperm_given) {
+            // copy b: the data of BASE.perm<b>.mmdiff of this command line with -permutations (the seed run_perm hands on)
+            MMG_CHECK(mmg_diff_lrt_perm_create(0, (uint32_t)F, (uint32_t)S, y.data(), e.data(), (uint32_t)D.K, D.M.data(), (uint32_t)D.L0,
+                                               D.P0.data(), (uint32_t)D.L1, D.P1.data(), D.C.data(), fixalpha ? 1 : 0, 0, (uint32_t)lrt_perms, useed,
+                                               0, &ph));
+            lh = mmg_diff_lrt_perm_observed(ph);
+        } else {
+            MMG_CHECK(mmg_diff_lrt_create(0, (uint32_t)F, (uint32_t)S, y.data(), e.data(), (uint32_t)D.K, D.M.data(), (uint32_t)D.L0, D.P0.data(),
+                                          (uint32_t)D.L1, D.P1.data(), D.C.data(), fixalpha ? 1 : 0, 0, &lh));
+        }
+        write_lrt(lrt_out.f, lrt_file, features, D, fixalpha, lh, ph);
+        if (ph) {
+            vector<uint8_t> st((size_t)lrt_perms * F);
+            MMG_CHECK(mmg_diff_lrt_perm_get_null(ph, 0, (uint32_t)lrt_perms, NULL, st.data()));
+            uint64_t bits[3] = {0, 0, 0};
+            for (uint8_t v : st)
+                for (int k = 0; k < 3; ++k) bits[k] += ((v >> k) & 1) + ((v >> (4 + k)) & 1);
+            cerr << "Null of the likelihood-ratio test: " << 2 * st.size() << " fits on " << lrt_perms << " shuffled copies; status bit 1 (cap) on "
+                 << bits[0] << ", bit 2 (singular) on " << bits[1] << ", bit 4 (boundary) on " << bits[2] << "\n";
+            mmg_diff_lrt_perm_destroy(ph);
+        } else {
+            mmg_diff_lrt_destroy(lh);
+        }
         cerr << "Wrote the likelihood-ratio tests of " << F << " features to " << lrt_file << "\n";
         if (lrt_only) return 0;
     }

@@ -527,6 +527,59 @@ class DiffLrt:
             pass
 
 
+class DiffLrtPerm(DiffLrt):
+    """`DiffLrt` with a permutation null (the mmg_diff_lrt_perm_* entries): the test on the data and on n_perm copies of it whose
+    samples are shuffled per feature as replica b of `DiffPerm` shuffles them, one device lane per (copy, feature).  The constructor
+    computes everything and the handle keeps the results on the host.  tests/mmdiff_lrt_perm_ref.py restates it."""
+
+    def __init__(self, y, e, M, P0, P1, classes, n_perm, fixalpha=False, max_iters=0, seed=1234, slab_copies=0, device=0):
+        """y, e, M, P0, P1, classes, fixalpha, max_iters as for `DiffLrt`; n_perm: the copies B, 1 to 65535 with B x features at most
+        2^31 - 1; seed: the shuffles' key; slab_copies: the copies fitted by one launch (0: as many as keep their data and
+        workspace under 1 GiB) -- no result depends on it."""
+        self._lib = _lib.load()
+        self._h = self._perm = None
+        y = np.ascontiguousarray(y, np.float64)
+        e = np.ascontiguousarray(e, np.float64)
+        M = np.ascontiguousarray(M, np.float64)
+        P = [np.ascontiguousarray(P0, np.float64), np.ascontiguousarray(P1, np.float64)]
+        Cl = np.ascontiguousarray(classes, np.int32)
+        F, N = y.shape
+        if e.shape != (F, N) or M.shape[0] != N or P[0].shape[0] != N or P[1].shape[0] != N or Cl.shape != (N, 2):
+            raise ValueError("inconsistent shapes")
+        if not 0 <= int(n_perm) < 2 ** 32 or not 0 <= int(slab_copies) < 2 ** 32:
+            raise ValueError("n_perm and slab_copies must fit 32 bits")
+        self.F, self.N, self.K, self.B = F, N, M.shape[1], int(n_perm)
+        self.L = (P[0].shape[1], P[1].shape[1])
+        h = C.c_void_p()
+        check(self._lib.mmg_diff_lrt_perm_create(device, F, N, _ptr(y), _ptr(e), self.K, _ptr(M), self.L[0], _ptr(P[0]), self.L[1], _ptr(P[1]),
+                                                 _ptr(Cl), int(bool(fixalpha)), int(max_iters), self.B, int(seed) & (2 ** 64 - 1), int(slab_copies),
+                                                 C.byref(h)))
+        self._perm = h
+        self._h = C.c_void_p(self._lib.mmg_diff_lrt_perm_observed(h))      # borrowed: DiffLrt's info() and results() read it
+
+    def results(self):
+        """What `DiffLrt.results()` returns for the data, and null_stat (B, F), null_status (B, F) uint8 = status0 | status1 << 4,
+        perm_ge, perm_n (F,) uint64, perm_p, null_ge (uint64) and q_perm (F,)."""
+        F, B = self.F, self.B
+        out = DiffLrt.results(self)
+        out.update(null_stat=np.empty((B, F)), null_status=np.empty((B, F), np.uint8), perm_ge=np.empty(F, np.uint64), perm_n=np.empty(F, np.uint64),
+                   perm_p=np.empty(F), null_ge=np.empty(F, np.uint64), q_perm=np.empty(F))
+        check(self._lib.mmg_diff_lrt_perm_get_null(self._perm, 0, B, _ptr(out["null_stat"]), _ptr(out["null_status"])))
+        check(self._lib.mmg_diff_lrt_perm_get(self._perm, *(_ptr(out[k]) for k in ("perm_ge", "perm_n", "perm_p", "null_ge", "q_perm"))))
+        return out
+
+    def device_bytes(self):
+        """The peak of the handle's own device memory during creation (the formula of include/mmgibbs.h)."""
+        b = C.c_uint64()
+        check(self._lib.mmg_diff_lrt_perm_device_bytes(self._perm, C.byref(b)))
+        return b.value
+
+    def close(self):
+        if self._perm:
+            self._lib.mmg_diff_lrt_perm_destroy(self._perm)
+        self._perm = self._h = None
+
+
 def qvalues(obs, null, device=0):
     """q-values of the observed statistics against the null statistics (any shapes, taken flat), on the device: (null_ge, q), per
     observed value the null values not below it and min over the observed t' <= it of min(1, V(t') m / (m0 R(t'))), with R and V the
