@@ -98,6 +98,81 @@ int mmg::df_classes(const int32_t *C, uint32_t stride, uint32_t N, int *nc)
     return MMG_OK;
 }
 
+// ---- the argument checks every create entry of mmdiff makes, in the order it makes them (mmg_host.h) ---------------------------------
+int mmg::df_check_shape(uint32_t F, uint32_t N, uint32_t K)
+{
+    if (F == 0 || F > 0x7fffff00u / DF_BLOCK) return fail(MMG_ERR_ARG, "the number of features must be between 1 and 33554428");
+    if (N < 2 || N > (uint32_t)DF_NMAX) return fail(MMG_ERR_ARG, "the number of samples must be between 2 and 512");
+    if (K < 1 || K > (uint32_t)DF_KMAX) return fail(MMG_ERR_ARG, "M must have between 1 and 8 columns");
+    return MMG_OK;
+}
+
+int mmg::df_check_cols(uint32_t L0, uint32_t J, const uint32_t *L1)
+{
+    bool ok = L0 >= 1 && L0 <= (uint32_t)DF_LMAX;
+    for (uint32_t j = 0; j < J; ++j) ok = ok && L1[j] >= 1 && L1[j] <= (uint32_t)DF_LMAX;
+    return ok ? (int)MMG_OK : fail(MMG_ERR_ARG, "P0 and P1 must have between 1 and 16 columns");
+}
+
+int mmg::df_check_prior(double d, double s, double pdash)
+{
+    if (!(d > 0) || !(s > 0) || !std::isfinite(d) || !std::isfinite(s) || !(pdash >= 0 && pdash <= 1))
+        return fail(MMG_ERR_ARG, "d and s must be positive and finite and pdash in [0, 1]");
+    return MMG_OK;
+}
+
+// every input value finite: a NaN or an infinity would reach the log densities and the samplers on the device
+int mmg::df_check_finite(uint32_t F, uint32_t N, const double *y, const double *e, uint32_t K, const double *M, uint32_t L0, const double *P0,
+                         uint64_t L1, const double *P1)
+{
+    auto finite = [](const double *x, uint64_t n) { for (uint64_t i = 0; i < n; ++i) if (!std::isfinite(x[i])) return false; return true; };
+    if (!finite(y, (uint64_t)F * N) || !finite(e, (uint64_t)F * N)) return fail(MMG_ERR_ARG, "y and e must be finite");
+    if (!finite(M, (uint64_t)N * K) || !finite(P0, (uint64_t)N * L0) || !finite(P1, (uint64_t)N * L1)) return fail(MMG_ERR_ARG, "M, P0 and P1 must be finite");
+    return MMG_OK;
+}
+
+int mmg::df_check_classes(const int32_t *C, uint32_t N, int nc[2])
+{
+    nc[0] = nc[1] = 0;
+    for (int mi = 0; mi < 2; ++mi) {
+        const int rc = df_classes(C + mi, 2, N, &nc[mi]);
+        if (rc) return rc;
+    }
+    return MMG_OK;
+}
+
+int mmg::df_upload_transposed(hipStream_t st, uint32_t F, uint32_t N, const double *y, const double *e, double *d_y, double *d_esq, DiffStaged &staged)
+{
+    const uint64_t FN = (uint64_t)F * N;
+    std::vector<double> &ty = staged.ty, &te = staged.te;
+    ty.resize(FN); te.resize(FN);
+    for (uint64_t f = 0; f < F; ++f)
+        for (uint64_t i = 0; i < N; ++i) {
+            ty[i * F + f] = y[f * N + i];
+            const double ei = e[f * N + i];
+            te[i * F + f] = ei * ei;
+        }
+    HIP_TRY(hipMemcpyAsync(d_y, ty.data(), FN * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_esq, te.data(), FN * 8, hipMemcpyHostToDevice, st));
+    return MMG_OK;
+}
+
+// what every handle's DiffParams start from: the sizes, the nil flags, the hyperparameters and the seed (the pointers, `chain` and
+// the slot layout are the caller's)
+static DiffParams df_params(uint32_t F, uint32_t N, uint32_t K, const double *M, uint32_t L0, const double *P0, uint32_t L1, const double *P1,
+                            double d, double s, int fixalpha, uint64_t seed)
+{
+    DiffParams p{};
+    p.F = (int)F; p.N = (int)N; p.K = (int)K;
+    p.Mnil = df_nil(M, N, K) ? 1 : 0;
+    p.fixalpha = fixalpha ? 1 : 0;
+    p.d = d; p.s = s; p.v_beta = fixalpha ? 25.0 : 4.0;
+    p.seed = seed;
+    p.m[0].Pnil = df_nil(P0, N, L0) ? 1 : 0;
+    p.m[1].Pnil = df_nil(P1, N, L1) ? 1 : 0;
+    return p;
+}
+
 // the slot offsets of one comparison's state and workspace (p.K and p.Mnil set); the number of slots per feature:
 // for each model 11 + 6 K + 11 L + 5 classes, then 3, then (M not nil) 5 K^2 + 2 K, then 2 max(classes)
 static size_t df_layout(DiffParams &p, const uint32_t L[2], const int nc[2])
@@ -165,34 +240,15 @@ extern "C" int mmg_diff_create(int device, uint32_t F, uint32_t N, const double 
 {
     if (!out || !y || !e || !M || !P0 || !P1 || !C) return fail(MMG_ERR_ARG, "NULL argument");
     *out = nullptr;
-    if (F == 0 || F > 0x7fffff00u / DF_BLOCK) return fail(MMG_ERR_ARG, "the number of features must be between 1 and 33554428");
-    if (N < 2 || N > (uint32_t)DF_NMAX) return fail(MMG_ERR_ARG, "the number of samples must be between 2 and 512");
-    if (K < 1 || K > (uint32_t)DF_KMAX) return fail(MMG_ERR_ARG, "M must have between 1 and 8 columns");
-    if (L0 < 1 || L0 > (uint32_t)DF_LMAX || L1 < 1 || L1 > (uint32_t)DF_LMAX) return fail(MMG_ERR_ARG, "P0 and P1 must have between 1 and 16 columns");
-    if (!(d > 0) || !(s > 0) || !std::isfinite(d) || !std::isfinite(s) || !(pdash >= 0 && pdash <= 1))
-        return fail(MMG_ERR_ARG, "d and s must be positive and finite and pdash in [0, 1]");
-    // every input value finite: a NaN or an infinity would reach the log densities and the samplers on the device
-    auto finite = [](const double *x, uint64_t n) { for (uint64_t i = 0; i < n; ++i) if (!std::isfinite(x[i])) return false; return true; };
-    if (!finite(y, (uint64_t)F * N) || !finite(e, (uint64_t)F * N)) return fail(MMG_ERR_ARG, "y and e must be finite");
-    if (!finite(M, (uint64_t)N * K) || !finite(P0, (uint64_t)N * L0) || !finite(P1, (uint64_t)N * L1)) return fail(MMG_ERR_ARG, "M, P0 and P1 must be finite");
-    int nc[2] = {0, 0};
-    for (int mi = 0; mi < 2; ++mi) {
-        const int rc = df_classes(C + mi, 2, N, &nc[mi]);
-        if (rc) return rc;
-    }
-    int rc = require_device(device);
-    if (rc) return rc;
+    int nc[2] = {0, 0}, rc;
+    if ((rc = df_check_shape(F, N, K)) || (rc = df_check_cols(L0, 1, &L1)) || (rc = df_check_prior(d, s, pdash))
+        || (rc = df_check_finite(F, N, y, e, K, M, L0, P0, L1, P1)) || (rc = df_check_classes(C, N, nc)) || (rc = require_device(device)))
+        return rc;
 
     std::unique_ptr<mmg_diff> h(new mmg_diff());
     h->device = device; h->F = F; h->N = N; h->K = K; h->L[0] = L0; h->L[1] = L1;
     DiffParams &p = h->p;
-    p.F = (int)F; p.N = (int)N; p.K = (int)K;
-    p.Mnil = df_nil(M, N, K) ? 1 : 0;
-    p.fixalpha = fixalpha ? 1 : 0;
-    p.d = d; p.s = s; p.v_beta = fixalpha ? 25.0 : 4.0;
-    p.seed = seed;
-    p.m[0].Pnil = df_nil(P0, N, L0) ? 1 : 0;
-    p.m[1].Pnil = df_nil(P1, N, L1) ? 1 : 0;
+    p = df_params(F, N, K, M, L0, P0, L1, P1, d, s, fixalpha, seed);
     h->nslot = df_layout(p, h->L, nc);
 
     auto dalloc = [&](auto &buf, uint64_t count) {
@@ -213,16 +269,8 @@ extern "C" int mmg_diff_create(int device, uint32_t F, uint32_t N, const double 
     HIP_TRY(dalloc(h->d_gam, (uint64_t)F));
     HIP_TRY(dalloc(h->d_tuned, (uint64_t)F));
     HIP_TRY(dalloc(h->d_cnt, 1));
-    // y and e^2 transposed to [N][F]: the lanes of a wave read adjacent words
-    std::vector<double> ty(FN), te(FN);
-    for (uint64_t f = 0; f < F; ++f)
-        for (uint64_t i = 0; i < N; ++i) {
-            ty[i * F + f] = y[f * N + i];
-            const double ei = e[f * N + i];
-            te[i * F + f] = ei * ei;
-        }
-    HIP_TRY(hipMemcpyAsync(h->d_y.get(), ty.data(), FN * 8, hipMemcpyHostToDevice, h->st.get()));
-    HIP_TRY(hipMemcpyAsync(h->d_esq.get(), te.data(), FN * 8, hipMemcpyHostToDevice, h->st.get()));
+    DiffStaged staged;
+    if ((rc = df_upload_transposed(h->st.get(), F, N, y, e, h->d_y.get(), h->d_esq.get(), staged))) return rc;
     HIP_TRY(hipMemcpyAsync(h->d_M.get(), M, (size_t)N * K * 8, hipMemcpyHostToDevice, h->st.get()));
     HIP_TRY(hipMemcpyAsync(h->d_P0.get(), P0, (size_t)N * L0 * 8, hipMemcpyHostToDevice, h->st.get()));
     HIP_TRY(hipMemcpyAsync(h->d_P1.get(), P1, (size_t)N * L1 * 8, hipMemcpyHostToDevice, h->st.get()));
@@ -582,129 +630,245 @@ extern "C" int mmg_diff_device_bytes(mmg_diff *h, uint64_t *bytes)
 
 extern "C" void mmg_diff_destroy(mmg_diff *h) { delete h; }
 
-// ---- several alternatives against one model 0 on one handle -----------------------------------------------------------------
-// y / e^2 / M / P0 once; per comparison a DiffParams (in h_p and, for the kernels, in d_p), a state block, gam / tuned, P1 and a class
-// table.  The launches cover every comparison (grid.y); a comparison whose untuned count reached 0 leaves the tuning launches.
+// ---- what the handles of several replicas share on the host ---------------------------------------------------------------------
+// A replica is a comparison of mmg_diff_poly_*, a chain of mmg_diff_chains_* or a data set of mmg_diff_perm_*.  Per replica a DiffParams
+// (in h_p and, for the kernels, in d_p) with its own state block and gam / tuned; what else is its own is the handle's business.  The
+// launches cover every replica (grid.y); each replica tunes on its own: one whose untuned count reached 0 has ended, leaves the tuning
+// launches and keeps its batch count nb, and its sampling stream index starts at burnin + 128 * nb (h_off / d_off).
+// `entry` and `unit` are the handle's words in the messages: "mmg_diff_poly" and "comparison".
 static_assert(sizeof(DiffParams) == 480, "mmg_diff_poly_device_bytes is documented with this size (DESIGN.md section 10)");
+constexpr uint32_t DF_RMAX = 32;   // k_dfp_tune's `active` mask has 32 bits
 
-struct mmg_diff_poly {
-    struct Cmp {
-        uint32_t L1 = 0, batches = 0;
-        bool ended = false;
-        size_t nslot = 0;
-        DevBuf<double> d_st, d_P1;
-        DevBuf<int> d_C, d_gam, d_tuned;
-    };
+struct DiffReplicas {
+    const std::string entry, unit;
     DevStream st;
     int device = 0;
-    uint32_t F = 0, N = 0, K = 0, L0 = 0, J = 0;
-    DevBuf<double> d_y, d_esq, d_M, d_P0;
-    std::vector<Cmp> cmp;
+    uint32_t F = 0, R = 0;
+    uint32_t sample_total = 0;         // chains: the whole sampling length, which sample() may not pass (0: no such length)
     std::vector<DiffParams> h_p;
-    std::vector<uint32_t> h_off;
+    std::vector<uint32_t> h_off, nb;   // per replica: 128 * (its batches); its batches
+    std::vector<char> ended;
     DevBuf<DiffParams> d_p;
-    DevBuf<uint32_t> d_off;   // [J] the iterations comparison c's tuning took (the start of its sampling stream index after burn-in)
-    DevBuf<int> d_cnt;        // [J]
+    DevBuf<uint32_t> d_off;
+    DevBuf<int> d_cnt;                 // [R]
     uint32_t burnin = 0, batches = 0, sampled = 0;
     bool burnt = false;
     uint64_t device_bytes = 0;
-    dim3 grid() const { return dim3(df_blocks(F), J); }
-    ~mmg_diff_poly() { if (st) (void)hipStreamSynchronize(st.get()); }
+
+    DiffReplicas(const char *entry_, const char *unit_) : entry(entry_), unit(unit_) {}
+    virtual ~DiffReplicas() = default;
+    // (a handle's destructor calls this first: its own buffers go before the members above, and none while the stream still runs)
+    void drain() { if (st) (void)hipStreamSynchronize(st.get()); }
+    dim3 grid() const { return dim3(df_blocks(F), R); }
+
+    template <typename B> hipError_t dalloc(B &buf, uint64_t count)
+    {
+        HIPE_TRY(buf.alloc(count));
+        device_bytes += count * sizeof(*buf.get());
+        return hipSuccess;
+    }
+
+    // the stream and the per-replica arrays of a new handle
+    int start(int device_, uint32_t F_, uint32_t R_)
+    {
+        device = device_; F = F_; R = R_;
+        h_p.resize(R);
+        h_off.assign(R, 0);
+        nb.assign(R, 0);
+        ended.assign(R, 0);
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(st.create(hipStreamNonBlocking));
+        HIP_TRY(dalloc(d_p, R));
+        HIP_TRY(dalloc(d_off, R));
+        HIP_TRY(dalloc(d_cnt, R));
+        return MMG_OK;
+    }
+
+    // h_p, complete, to the device and every offset 0: in stream order, ahead of the handle's init launch
+    int upload_params()
+    {
+        HIP_TRY(hipMemcpyAsync(d_p.get(), h_p.data(), (size_t)R * sizeof(DiffParams), hipMemcpyHostToDevice, st.get()));
+        HIP_TRY(hipMemsetAsync(d_off.get(), 0, (size_t)R * 4, st.get()));
+        return MMG_OK;
+    }
+
+    // One launch of n iterations of every replica.  t: the burn-in or sampling index of the first one; k_dfp_run needs none in sampling.
+    virtual void launch_run(uint32_t it0, int t, int n, int mode, int rec_from)
+    {
+        hipLaunchKernelGGL(k_dfp_run, grid(), dim3(DF_BLOCK), 0, st.get(), d_p.get(), d_off.get(), it0, mode == 2 ? 0 : t, n, mode, rec_from);
+    }
+
+    int run_burnin(uint32_t iters)
+    {
+        if (burnt) return fail(MMG_ERR_STATE, "the burn-in has run already");
+        if (iters == 0 || iters % 1024) return fail(MMG_ERR_ARG, "burn-in iterations must be a positive multiple of 1024");
+        HIP_TRY(hipSetDevice(device));
+        for (uint32_t t = 0; t < iters; t += DF_CHUNK) {
+            const uint32_t n = iters - t < DF_CHUNK ? iters - t : DF_CHUNK;
+            launch_run(t, (int)t, (int)n, 0, DF_REC_FROM);
+        }
+        hipLaunchKernelGGL(k_dfp_pseudo, grid(), dim3(DF_BLOCK), 0, st.get(), d_p.get(), (double)(iters - DF_REC_FROM));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(st.get()));
+        burnin = iters;
+        burnt = true;
+        return MMG_OK;
+    }
+
+    int tune_batch(uint32_t *untuned, int32_t *ended_out)
+    {
+        if (!untuned) return fail(MMG_ERR_ARG, "NULL argument");
+        if (!burnt) return fail(MMG_ERR_STATE, entry + "_tune_batch before " + entry + "_burnin");
+        if (sampled) return fail(MMG_ERR_STATE, entry + "_tune_batch after sampling has started");
+        uint32_t active = 0;
+        for (uint32_t r = 0; r < R; ++r)
+            if (!ended[r]) active |= 1u << r;
+        for (uint32_t r = 0; r < R; ++r) untuned[r] = 0;
+        if (active) {
+            HIP_TRY(hipSetDevice(device));
+            HIP_TRY(hipMemsetAsync(d_cnt.get(), 0, (size_t)R * 4, st.get()));
+            const uint32_t it0 = burnin + batches * DF_BATCH;
+            hipLaunchKernelGGL(k_dfp_tune, grid(), dim3(DF_BLOCK), 0, st.get(), d_p.get(), active, it0, (int)batches, d_cnt.get());
+            HIP_TRY(hipGetLastError());
+            int cnt[DF_RMAX] = {0};
+            HIP_TRY(hipMemcpyAsync(cnt, d_cnt.get(), (size_t)R * 4, hipMemcpyDeviceToHost, st.get()));
+            HIP_TRY(hipStreamSynchronize(st.get()));
+            ++batches;
+            for (uint32_t r = 0; r < R; ++r) {
+                if (ended[r]) continue;
+                nb[r] = batches;
+                untuned[r] = (uint32_t)cnt[r];
+                if (cnt[r] == 0) ended[r] = 1;
+            }
+        }
+        if (ended_out)
+            for (uint32_t r = 0; r < R; ++r) ended_out[r] = ended[r] ? 1 : 0;
+        return MMG_OK;
+    }
+
+    int sample(uint32_t iters)
+    {
+        if (!burnt) return fail(MMG_ERR_STATE, entry + "_sample before " + entry + "_burnin");
+        if (iters == 0) return fail(MMG_ERR_ARG, "iters must be positive");
+        // (chains: the batch slot of sampling index t is t / (T / 16) < 16 only while t < T)
+        if (sample_total && iters > sample_total - sampled)
+            return fail(MMG_ERR_ARG, "sampling beyond the total sampling length the handle was created with");
+        HIP_TRY(hipSetDevice(device));
+        if (!sampled) {
+            // replica r's sampling starts at its own running index, burnin + 128 * (its batches)
+            for (uint32_t r = 0; r < R; ++r) h_off[r] = nb[r] * DF_BATCH;
+            HIP_TRY(hipMemcpyAsync(d_off.get(), h_off.data(), (size_t)R * 4, hipMemcpyHostToDevice, st.get()));
+        }
+        for (uint32_t j = 0; j < iters; j += DF_CHUNK) {
+            const uint32_t n = iters - j < DF_CHUNK ? iters - j : DF_CHUNK;
+            launch_run(burnin + sampled + j, (int)(sampled + j), (int)n, 2, 0);
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(st.get()));
+        sampled += iters;
+        return MMG_OK;
+    }
+
+    int results(uint32_t r, double *gamma_mean, double *logitp, double *alpha, double *beta, double *eta)
+    {
+        if (r >= R) return fail(MMG_ERR_ARG, "no such " + unit);
+        if (!sampled) return fail(MMG_ERR_STATE, entry + "_get_results before " + entry + "_sample");
+        HIP_TRY(hipSetDevice(device));
+        const DiffParams &p = h_p[r];
+        const uint32_t L[2] = {(uint32_t)p.m[0].L, (uint32_t)p.m[1].L};
+        return df_results(p, p.st, F, (uint32_t)p.K, L, sampled, gamma_mean, logitp, alpha, beta, eta);
+    }
+
+    int info(uint32_t r, int32_t *flags, uint32_t *n_classes, uint32_t *batches_out, int32_t *ended_out) const
+    {
+        if (r >= R) return fail(MMG_ERR_ARG, "no such " + unit);
+        const DiffParams &p = h_p[r];
+        if (flags) { flags[0] = p.Mnil; flags[1] = p.m[0].Pnil; flags[2] = p.m[1].Pnil; }
+        if (n_classes) { n_classes[0] = (uint32_t)p.m[0].nc; n_classes[1] = (uint32_t)p.m[1].nc; }
+        if (batches_out) *batches_out = nb[r];
+        if (ended_out) *ended_out = ended[r] ? 1 : 0;
+        return MMG_OK;
+    }
+};
+
+static int df_null() { return fail(MMG_ERR_ARG, "NULL argument"); }
+
+static int df_device_bytes(const DiffReplicas *h, uint64_t *bytes)
+{
+    if (!h || !bytes) return df_null();
+    *bytes = h->device_bytes;
+    return MMG_OK;
+}
+
+// ---- several alternatives against one model 0 on one handle -----------------------------------------------------------------
+// y / e^2 / M / P0 once; per comparison its own slot layout, state block, gam / tuned, P1 and class table.
+struct mmg_diff_poly : DiffReplicas {
+    struct Cmp {
+        DevBuf<double> d_st, d_P1;
+        DevBuf<int> d_C, d_gam, d_tuned;
+    };
+    DevBuf<double> d_y, d_esq, d_M, d_P0;
+    std::vector<Cmp> cmp;
+    mmg_diff_poly() : DiffReplicas("mmg_diff_poly", "comparison") {}
+    ~mmg_diff_poly() { drain(); }
 };
 
 extern "C" int mmg_diff_poly_create(int device, uint32_t F, uint32_t N, const double *y, const double *e, uint32_t K, const double *M,
                                     uint32_t L0, const double *P0, const int32_t *C0, uint32_t J, const uint32_t *L1, const double *P1,
                                     const int32_t *C1, double d, double s, double pdash, int fixalpha, uint64_t seed, mmg_diff_poly **out)
 {
-    if (!out || !y || !e || !M || !P0 || !C0 || !L1 || !P1 || !C1) return fail(MMG_ERR_ARG, "NULL argument");
+    if (!out || !y || !e || !M || !P0 || !C0 || !L1 || !P1 || !C1) return df_null();
     *out = nullptr;
-    if (F == 0 || F > 0x7fffff00u / DF_BLOCK) return fail(MMG_ERR_ARG, "the number of features must be between 1 and 33554428");
-    if (N < 2 || N > (uint32_t)DF_NMAX) return fail(MMG_ERR_ARG, "the number of samples must be between 2 and 512");
-    if (K < 1 || K > (uint32_t)DF_KMAX) return fail(MMG_ERR_ARG, "M must have between 1 and 8 columns");
+    int rc;
+    if ((rc = df_check_shape(F, N, K))) return rc;
     if (J < 1 || J > (uint32_t)DF_JMAX) return fail(MMG_ERR_ARG, "the number of comparisons must be between 1 and 16");
-    if (L0 < 1 || L0 > (uint32_t)DF_LMAX) return fail(MMG_ERR_ARG, "P0 and P1 must have between 1 and 16 columns");
+    if ((rc = df_check_cols(L0, J, L1))) return rc;
     uint64_t sumL1 = 0;
-    for (uint32_t c = 0; c < J; ++c) {
-        if (L1[c] < 1 || L1[c] > (uint32_t)DF_LMAX) return fail(MMG_ERR_ARG, "P0 and P1 must have between 1 and 16 columns");
-        sumL1 += L1[c];
-    }
-    if (!(d > 0) || !(s > 0) || !std::isfinite(d) || !std::isfinite(s) || !(pdash >= 0 && pdash <= 1))
-        return fail(MMG_ERR_ARG, "d and s must be positive and finite and pdash in [0, 1]");
-    auto finite = [](const double *x, uint64_t n) { for (uint64_t i = 0; i < n; ++i) if (!std::isfinite(x[i])) return false; return true; };
-    if (!finite(y, (uint64_t)F * N) || !finite(e, (uint64_t)F * N)) return fail(MMG_ERR_ARG, "y and e must be finite");
-    if (!finite(M, (uint64_t)N * K) || !finite(P0, (uint64_t)N * L0) || !finite(P1, (uint64_t)N * sumL1)) return fail(MMG_ERR_ARG, "M, P0 and P1 must be finite");
+    for (uint32_t c = 0; c < J; ++c) sumL1 += L1[c];
+    if ((rc = df_check_prior(d, s, pdash)) || (rc = df_check_finite(F, N, y, e, K, M, L0, P0, sumL1, P1))) return rc;
     int nc0 = 0;
-    int rc = df_classes(C0, 1, N, &nc0);
-    if (rc) return rc;
+    if ((rc = df_classes(C0, 1, N, &nc0))) return rc;
     std::vector<int> nc1(J, 0);
     for (uint32_t c = 0; c < J; ++c)
         if ((rc = df_classes(C1 + (size_t)c * N, 1, N, &nc1[c]))) return rc;
     if ((rc = require_device(device))) return rc;
 
     std::unique_ptr<mmg_diff_poly> h(new mmg_diff_poly());
-    h->device = device; h->F = F; h->N = N; h->K = K; h->L0 = L0; h->J = J;
     h->cmp.resize(J);
-    h->h_p.resize(J);
-    h->h_off.assign(J, 0);
-    auto dalloc = [&](auto &buf, uint64_t count) {
-        HIPE_TRY(buf.alloc(count));
-        h->device_bytes += count * sizeof(*buf.get());
-        return hipSuccess;
-    };
-    HIP_TRY(hipSetDevice(device));
-    HIP_TRY(h->st.create(hipStreamNonBlocking));
+    if ((rc = h->start(device, F, J))) return rc;
     const hipStream_t st = h->st.get();
     const uint64_t FN = (uint64_t)F * N;
-    HIP_TRY(dalloc(h->d_y, FN));
-    HIP_TRY(dalloc(h->d_esq, FN));
-    HIP_TRY(dalloc(h->d_M, (uint64_t)N * K));
-    HIP_TRY(dalloc(h->d_P0, (uint64_t)N * L0));
-    HIP_TRY(dalloc(h->d_p, J));
-    HIP_TRY(dalloc(h->d_off, J));
-    HIP_TRY(dalloc(h->d_cnt, J));
-    // y and e^2 transposed to [N][F], as mmg_diff_create holds them
-    std::vector<double> ty(FN), te(FN);
-    for (uint64_t f = 0; f < F; ++f)
-        for (uint64_t i = 0; i < N; ++i) {
-            ty[i * F + f] = y[f * N + i];
-            const double ei = e[f * N + i];
-            te[i * F + f] = ei * ei;
-        }
-    HIP_TRY(hipMemcpyAsync(h->d_y.get(), ty.data(), FN * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(h->d_esq.get(), te.data(), FN * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(h->dalloc(h->d_y, FN));
+    HIP_TRY(h->dalloc(h->d_esq, FN));
+    HIP_TRY(h->dalloc(h->d_M, (uint64_t)N * K));
+    HIP_TRY(h->dalloc(h->d_P0, (uint64_t)N * L0));
+    DiffStaged staged;                     // (this and hC: sources of asynchronous copies, alive until the synchronize below)
+    std::vector<std::vector<int>> hC(J);
+    if ((rc = df_upload_transposed(st, F, N, y, e, h->d_y.get(), h->d_esq.get(), staged))) return rc;
     HIP_TRY(hipMemcpyAsync(h->d_M.get(), M, (size_t)N * K * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(h->d_P0.get(), P0, (size_t)N * L0 * 8, hipMemcpyHostToDevice, st));
-    std::vector<std::vector<int>> hC(J);   // (sources of asynchronous copies: alive until the synchronize below)
     const double *P1c = P1;
     for (uint32_t c = 0; c < J; ++c) {
         mmg_diff_poly::Cmp &q = h->cmp[c];
         DiffParams &p = h->h_p[c];
-        q.L1 = L1[c];
-        p.F = (int)F; p.N = (int)N; p.K = (int)K;
-        p.Mnil = df_nil(M, N, K) ? 1 : 0;
-        p.fixalpha = fixalpha ? 1 : 0;
-        p.d = d; p.s = s; p.v_beta = fixalpha ? 25.0 : 4.0;
-        p.seed = seed;
-        p.m[0].Pnil = df_nil(P0, N, L0) ? 1 : 0;
-        p.m[1].Pnil = df_nil(P1c, N, q.L1) ? 1 : 0;
-        const uint32_t L[2] = {L0, q.L1};
+        p = df_params(F, N, K, M, L0, P0, L1[c], P1c, d, s, fixalpha, seed);
+        const uint32_t L[2] = {L0, L1[c]};
         const int nc[2] = {nc0, nc1[c]};
-        q.nslot = df_layout(p, L, nc);
-        HIP_TRY(dalloc(q.d_st, (uint64_t)q.nslot * F));
-        HIP_TRY(dalloc(q.d_P1, (uint64_t)N * q.L1));
-        HIP_TRY(dalloc(q.d_C, (uint64_t)N * 2));
-        HIP_TRY(dalloc(q.d_gam, (uint64_t)F));
-        HIP_TRY(dalloc(q.d_tuned, (uint64_t)F));
+        const size_t nslot = df_layout(p, L, nc);
+        HIP_TRY(h->dalloc(q.d_st, (uint64_t)nslot * F));
+        HIP_TRY(h->dalloc(q.d_P1, (uint64_t)N * L1[c]));
+        HIP_TRY(h->dalloc(q.d_C, (uint64_t)N * 2));
+        HIP_TRY(h->dalloc(q.d_gam, (uint64_t)F));
+        HIP_TRY(h->dalloc(q.d_tuned, (uint64_t)F));
         hC[c].resize((size_t)N * 2);
         for (uint32_t i = 0; i < N; ++i) { hC[c][i * 2] = C0[i]; hC[c][i * 2 + 1] = C1[(size_t)c * N + i]; }
-        HIP_TRY(hipMemcpyAsync(q.d_P1.get(), P1c, (size_t)N * q.L1 * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(q.d_P1.get(), P1c, (size_t)N * L1[c] * 8, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(q.d_C.get(), hC[c].data(), (size_t)N * 2 * 4, hipMemcpyHostToDevice, st));
         p.M = h->d_M.get(); p.m[0].P = h->d_P0.get(); p.m[1].P = q.d_P1.get(); p.Cl = q.d_C.get();
         p.y = h->d_y.get(); p.esq = h->d_esq.get(); p.st = q.d_st.get(); p.gam = q.d_gam.get(); p.tuned = q.d_tuned.get();
-        P1c += (size_t)N * q.L1;
+        P1c += (size_t)N * L1[c];
     }
-    HIP_TRY(hipMemcpyAsync(h->d_p.get(), h->h_p.data(), (size_t)J * sizeof(DiffParams), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(h->d_off.get(), 0, (size_t)J * 4, st));
+    if ((rc = h->upload_params())) return rc;
     const double logitp0 = std::log(pdash) - std::log(1.0 - pdash);
     hipLaunchKernelGGL(k_dfp_init, h->grid(), dim3(DF_BLOCK), 0, st, h->d_p.get(), logitp0);
     HIP_TRY(hipGetLastError());
@@ -713,223 +877,97 @@ extern "C" int mmg_diff_poly_create(int device, uint32_t F, uint32_t N, const do
     return MMG_OK;
 }
 
-extern "C" int mmg_diff_poly_burnin(mmg_diff_poly *h, uint32_t iters)
-{
-    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
-    if (h->burnt) return fail(MMG_ERR_STATE, "the burn-in has run already");
-    if (iters == 0 || iters % 1024) return fail(MMG_ERR_ARG, "burn-in iterations must be a positive multiple of 1024");
-    HIP_TRY(hipSetDevice(h->device));
-    for (uint32_t t = 0; t < iters; t += DF_CHUNK) {
-        const uint32_t n = iters - t < DF_CHUNK ? iters - t : DF_CHUNK;
-        hipLaunchKernelGGL(k_dfp_run, h->grid(), dim3(DF_BLOCK), 0, h->st.get(), h->d_p.get(), h->d_off.get(), t, (int)t, (int)n, 0, DF_REC_FROM);
-    }
-    hipLaunchKernelGGL(k_dfp_pseudo, h->grid(), dim3(DF_BLOCK), 0, h->st.get(), h->d_p.get(), (double)(iters - DF_REC_FROM));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(h->st.get()));
-    h->burnin = iters;
-    h->burnt = true;
-    return MMG_OK;
-}
+extern "C" int mmg_diff_poly_burnin(mmg_diff_poly *h, uint32_t iters) { return h ? h->run_burnin(iters) : df_null(); }
 
-extern "C" int mmg_diff_poly_tune_batch(mmg_diff_poly *h, uint32_t *untuned, int32_t *ended)
-{
-    if (!h || !untuned) return fail(MMG_ERR_ARG, "NULL argument");
-    if (!h->burnt) return fail(MMG_ERR_STATE, "mmg_diff_poly_tune_batch before mmg_diff_poly_burnin");
-    if (h->sampled) return fail(MMG_ERR_STATE, "mmg_diff_poly_tune_batch after sampling has started");
-    uint32_t active = 0;
-    for (uint32_t c = 0; c < h->J; ++c)
-        if (!h->cmp[c].ended) active |= 1u << c;
-    if (active) {
-        HIP_TRY(hipSetDevice(h->device));
-        HIP_TRY(hipMemsetAsync(h->d_cnt.get(), 0, (size_t)h->J * 4, h->st.get()));
-        const uint32_t it0 = h->burnin + h->batches * DF_BATCH;
-        hipLaunchKernelGGL(k_dfp_tune, h->grid(), dim3(DF_BLOCK), 0, h->st.get(), h->d_p.get(), active, it0, (int)h->batches, h->d_cnt.get());
-        HIP_TRY(hipGetLastError());
-        int cnt[DF_JMAX] = {0};
-        HIP_TRY(hipMemcpyAsync(cnt, h->d_cnt.get(), (size_t)h->J * 4, hipMemcpyDeviceToHost, h->st.get()));
-        HIP_TRY(hipStreamSynchronize(h->st.get()));
-        ++h->batches;
-        for (uint32_t c = 0; c < h->J; ++c) {
-            mmg_diff_poly::Cmp &q = h->cmp[c];
-            if (q.ended) { untuned[c] = 0; continue; }
-            q.batches = h->batches;
-            untuned[c] = (uint32_t)cnt[c];
-            if (cnt[c] == 0) q.ended = true;
-        }
-    } else {
-        for (uint32_t c = 0; c < h->J; ++c) untuned[c] = 0;
-    }
-    if (ended)
-        for (uint32_t c = 0; c < h->J; ++c) ended[c] = h->cmp[c].ended ? 1 : 0;
-    return MMG_OK;
-}
+extern "C" int mmg_diff_poly_tune_batch(mmg_diff_poly *h, uint32_t *untuned, int32_t *ended) { return h ? h->tune_batch(untuned, ended) : df_null(); }
 
-extern "C" int mmg_diff_poly_sample(mmg_diff_poly *h, uint32_t iters)
-{
-    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
-    if (!h->burnt) return fail(MMG_ERR_STATE, "mmg_diff_poly_sample before mmg_diff_poly_burnin");
-    if (iters == 0) return fail(MMG_ERR_ARG, "iters must be positive");
-    HIP_TRY(hipSetDevice(h->device));
-    if (!h->sampled) {
-        // comparison c's sampling starts at its own running index, burnin + 128 * (its batches)
-        for (uint32_t c = 0; c < h->J; ++c) h->h_off[c] = h->cmp[c].batches * DF_BATCH;
-        HIP_TRY(hipMemcpyAsync(h->d_off.get(), h->h_off.data(), (size_t)h->J * 4, hipMemcpyHostToDevice, h->st.get()));
-    }
-    for (uint32_t j = 0; j < iters; j += DF_CHUNK) {
-        const uint32_t n = iters - j < DF_CHUNK ? iters - j : DF_CHUNK;
-        hipLaunchKernelGGL(k_dfp_run, h->grid(), dim3(DF_BLOCK), 0, h->st.get(), h->d_p.get(), h->d_off.get(), h->burnin + h->sampled + j, 0, (int)n, 2, 0);
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(h->st.get()));
-    h->sampled += iters;
-    return MMG_OK;
-}
+extern "C" int mmg_diff_poly_sample(mmg_diff_poly *h, uint32_t iters) { return h ? h->sample(iters) : df_null(); }
 
 extern "C" int mmg_diff_poly_get_results(mmg_diff_poly *h, uint32_t j, double *gamma_mean, double *logitp, double *alpha, double *beta, double *eta)
 {
-    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
-    if (j >= h->J) return fail(MMG_ERR_ARG, "no such comparison");
-    if (!h->sampled) return fail(MMG_ERR_STATE, "mmg_diff_poly_get_results before mmg_diff_poly_sample");
-    HIP_TRY(hipSetDevice(h->device));
-    const uint32_t L[2] = {h->L0, h->cmp[j].L1};
-    return df_results(h->h_p[j], h->cmp[j].d_st.get(), h->F, h->K, L, h->sampled, gamma_mean, logitp, alpha, beta, eta);
+    return h ? h->results(j, gamma_mean, logitp, alpha, beta, eta) : df_null();
 }
 
 extern "C" int mmg_diff_poly_info(mmg_diff_poly *h, uint32_t j, int32_t *flags, uint32_t *n_classes, uint32_t *batches, int32_t *ended)
 {
-    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
-    if (j >= h->J) return fail(MMG_ERR_ARG, "no such comparison");
-    const DiffParams &p = h->h_p[j];
-    if (flags) { flags[0] = p.Mnil; flags[1] = p.m[0].Pnil; flags[2] = p.m[1].Pnil; }
-    if (n_classes) { n_classes[0] = (uint32_t)p.m[0].nc; n_classes[1] = (uint32_t)p.m[1].nc; }
-    if (batches) *batches = h->cmp[j].batches;
-    if (ended) *ended = h->cmp[j].ended ? 1 : 0;
-    return MMG_OK;
+    return h ? h->info(j, flags, n_classes, batches, ended) : df_null();
 }
 
-extern "C" int mmg_diff_poly_device_bytes(mmg_diff_poly *h, uint64_t *bytes)
-{
-    if (!h || !bytes) return fail(MMG_ERR_ARG, "NULL argument");
-    *bytes = h->device_bytes;
-    return MMG_OK;
-}
+extern "C" int mmg_diff_poly_device_bytes(mmg_diff_poly *h, uint64_t *bytes) { return df_device_bytes(h, bytes); }
 
 extern "C" void mmg_diff_poly_destroy(mmg_diff_poly *h) { delete h; }
 
 // ---- several chains of one comparison on one handle ---------------------------------------------------------------------------
 // y / e^2 / M / P0 / P1 and the class table once; per chain a DiffParams (chain c in the stream key), a state block of nslot + DF_NB slots
-// (the last DF_NB: the batch sums of gamma), gam / tuned.  The launches cover every chain (grid.y); a chain whose untuned count reached 0
-// leaves the tuning launches, as a comparison of mmg_diff_poly_* does.
-struct mmg_diff_chains {
-    DevStream st;
-    int device = 0;
-    uint32_t F = 0, N = 0, K = 0, L[2] = {0, 0}, C = 0, T = 0;
+// (the last DF_NB: the batch sums of gamma), gam / tuned.  The run launches are k_dfc_run, which fills the batch slots in sampling.
+struct mmg_diff_chains : DiffReplicas {
     size_t nslot = 0, npool = 0;   // slots per feature of one chain (without the batch slots) and of the pooled output
     DevBuf<double> d_y, d_esq, d_M, d_P0, d_P1, d_st, d_pool;
     DevBuf<int> d_C, d_gam, d_tuned;
-    std::vector<DiffParams> h_p;
-    std::vector<uint32_t> h_off, nb;   // per chain: 128 * (its batches); its batches
-    std::vector<char> ended;
-    DevBuf<DiffParams> d_p;
-    DevBuf<uint32_t> d_off;
-    DevBuf<int> d_cnt;
-    uint32_t burnin = 0, batches = 0, sampled = 0;
-    bool burnt = false, pooled = false;
-    uint64_t device_bytes = 0;
-    dim3 grid() const { return dim3(df_blocks(F), C); }
+    bool pooled = false;
+    mmg_diff_chains() : DiffReplicas("mmg_diff_chains", "chain") {}
+    ~mmg_diff_chains() { drain(); }
     int gb() const { return (int)nslot; }
-    ~mmg_diff_chains() { if (st) (void)hipStreamSynchronize(st.get()); }
+    // in sampling t is the sampling index of the launch's first iteration, the same for every chain
+    void launch_run(uint32_t it0, int t, int n, int mode, int rec_from) override
+    {
+        hipLaunchKernelGGL(k_dfc_run, grid(), dim3(DF_BLOCK), 0, st.get(), d_p.get(), d_off.get(), it0, t, n, mode, rec_from, gb(),
+                           (int)(sample_total / DF_NB));
+    }
 };
 
 extern "C" int mmg_diff_chains_create(int device, uint32_t F, uint32_t N, const double *y, const double *e, uint32_t K, const double *M,
                                       uint32_t L0, const double *P0, uint32_t L1, const double *P1, const int32_t *C, double d, double s,
                                       double pdash, int fixalpha, uint64_t seed, uint32_t n_chains, uint32_t sample_total, mmg_diff_chains **out)
 {
-    if (!out || !y || !e || !M || !P0 || !P1 || !C) return fail(MMG_ERR_ARG, "NULL argument");
+    if (!out || !y || !e || !M || !P0 || !P1 || !C) return df_null();
     *out = nullptr;
-    if (F == 0 || F > 0x7fffff00u / DF_BLOCK) return fail(MMG_ERR_ARG, "the number of features must be between 1 and 33554428");
-    if (N < 2 || N > (uint32_t)DF_NMAX) return fail(MMG_ERR_ARG, "the number of samples must be between 2 and 512");
-    if (K < 1 || K > (uint32_t)DF_KMAX) return fail(MMG_ERR_ARG, "M must have between 1 and 8 columns");
-    if (L0 < 1 || L0 > (uint32_t)DF_LMAX || L1 < 1 || L1 > (uint32_t)DF_LMAX) return fail(MMG_ERR_ARG, "P0 and P1 must have between 1 and 16 columns");
+    int nc[2] = {0, 0}, rc;
+    if ((rc = df_check_shape(F, N, K)) || (rc = df_check_cols(L0, 1, &L1))) return rc;
     if (n_chains < 1 || n_chains > (uint32_t)DF_CHAINS_MAX) return fail(MMG_ERR_ARG, "the number of chains must be between 1 and 16");
     if (sample_total == 0 || sample_total % DF_NB || sample_total > 0x7fffffffu)
         return fail(MMG_ERR_ARG, "the total sampling length must be a positive multiple of 16");
-    if (!(d > 0) || !(s > 0) || !std::isfinite(d) || !std::isfinite(s) || !(pdash >= 0 && pdash <= 1))
-        return fail(MMG_ERR_ARG, "d and s must be positive and finite and pdash in [0, 1]");
-    auto finite = [](const double *x, uint64_t n) { for (uint64_t i = 0; i < n; ++i) if (!std::isfinite(x[i])) return false; return true; };
-    if (!finite(y, (uint64_t)F * N) || !finite(e, (uint64_t)F * N)) return fail(MMG_ERR_ARG, "y and e must be finite");
-    if (!finite(M, (uint64_t)N * K) || !finite(P0, (uint64_t)N * L0) || !finite(P1, (uint64_t)N * L1)) return fail(MMG_ERR_ARG, "M, P0 and P1 must be finite");
-    int nc[2] = {0, 0};
-    int rc;
-    for (int mi = 0; mi < 2; ++mi)
-        if ((rc = df_classes(C + mi, 2, N, &nc[mi]))) return rc;
-    if ((rc = require_device(device))) return rc;
+    if ((rc = df_check_prior(d, s, pdash)) || (rc = df_check_finite(F, N, y, e, K, M, L0, P0, L1, P1)) || (rc = df_check_classes(C, N, nc))
+        || (rc = require_device(device)))
+        return rc;
 
     std::unique_ptr<mmg_diff_chains> h(new mmg_diff_chains());
-    h->device = device; h->F = F; h->N = N; h->K = K; h->L[0] = L0; h->L[1] = L1; h->C = n_chains; h->T = sample_total;
-    h->h_off.assign(n_chains, 0);
-    h->nb.assign(n_chains, 0);
-    h->ended.assign(n_chains, 0);
-    DiffParams p{};
-    p.F = (int)F; p.N = (int)N; p.K = (int)K;
-    p.Mnil = df_nil(M, N, K) ? 1 : 0;
-    p.fixalpha = fixalpha ? 1 : 0;
-    p.d = d; p.s = s; p.v_beta = fixalpha ? 25.0 : 4.0;
-    p.seed = seed;
-    p.m[0].Pnil = df_nil(P0, N, L0) ? 1 : 0;
-    p.m[1].Pnil = df_nil(P1, N, L1) ? 1 : 0;
-    h->nslot = df_layout(p, h->L, nc);
+    h->sample_total = sample_total;
+    DiffParams p = df_params(F, N, K, M, L0, P0, L1, P1, d, s, fixalpha, seed);
+    const uint32_t L[2] = {L0, L1};
+    h->nslot = df_layout(p, L, nc);
     h->npool = (size_t)DF_POOL_STATS + 2 * (size_t)(2 + 2 * K + L0 + L1);
     const uint64_t per_chain = (uint64_t)(h->nslot + DF_NB) * F;   // doubles of one chain's state block
 
-    auto dalloc = [&](auto &buf, uint64_t count) {
-        HIPE_TRY(buf.alloc(count));
-        h->device_bytes += count * sizeof(*buf.get());
-        return hipSuccess;
-    };
-    HIP_TRY(hipSetDevice(device));
-    HIP_TRY(h->st.create(hipStreamNonBlocking));
+    if ((rc = h->start(device, F, n_chains))) return rc;
     const hipStream_t st = h->st.get();
-    const uint64_t FN = (uint64_t)F * N;
-    HIP_TRY(dalloc(h->d_y, FN));
-    HIP_TRY(dalloc(h->d_esq, FN));
-    HIP_TRY(dalloc(h->d_M, (uint64_t)N * K));
-    HIP_TRY(dalloc(h->d_P0, (uint64_t)N * L0));
-    HIP_TRY(dalloc(h->d_P1, (uint64_t)N * L1));
-    HIP_TRY(dalloc(h->d_C, (uint64_t)N * 2));
-    HIP_TRY(dalloc(h->d_st, per_chain * n_chains));
-    HIP_TRY(dalloc(h->d_gam, (uint64_t)F * n_chains));
-    HIP_TRY(dalloc(h->d_tuned, (uint64_t)F * n_chains));
-    HIP_TRY(dalloc(h->d_pool, (uint64_t)h->npool * F));
-    HIP_TRY(dalloc(h->d_p, n_chains));
-    HIP_TRY(dalloc(h->d_off, n_chains));
-    HIP_TRY(dalloc(h->d_cnt, n_chains));
-    // y and e^2 transposed to [N][F], as mmg_diff_create holds them
-    std::vector<double> ty(FN), te(FN);
-    for (uint64_t f = 0; f < F; ++f)
-        for (uint64_t i = 0; i < N; ++i) {
-            ty[i * F + f] = y[f * N + i];
-            const double ei = e[f * N + i];
-            te[i * F + f] = ei * ei;
-        }
-    HIP_TRY(hipMemcpyAsync(h->d_y.get(), ty.data(), FN * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(h->d_esq.get(), te.data(), FN * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(h->dalloc(h->d_y, (uint64_t)F * N));
+    HIP_TRY(h->dalloc(h->d_esq, (uint64_t)F * N));
+    HIP_TRY(h->dalloc(h->d_M, (uint64_t)N * K));
+    HIP_TRY(h->dalloc(h->d_P0, (uint64_t)N * L0));
+    HIP_TRY(h->dalloc(h->d_P1, (uint64_t)N * L1));
+    HIP_TRY(h->dalloc(h->d_C, (uint64_t)N * 2));
+    HIP_TRY(h->dalloc(h->d_st, per_chain * n_chains));
+    HIP_TRY(h->dalloc(h->d_gam, (uint64_t)F * n_chains));
+    HIP_TRY(h->dalloc(h->d_tuned, (uint64_t)F * n_chains));
+    HIP_TRY(h->dalloc(h->d_pool, (uint64_t)h->npool * F));
+    DiffStaged staged;   // (sources of asynchronous copies: alive until the synchronize below)
+    if ((rc = df_upload_transposed(st, F, N, y, e, h->d_y.get(), h->d_esq.get(), staged))) return rc;
     HIP_TRY(hipMemcpyAsync(h->d_M.get(), M, (size_t)N * K * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(h->d_P0.get(), P0, (size_t)N * L0 * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(h->d_P1.get(), P1, (size_t)N * L1 * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(h->d_C.get(), C, (size_t)N * 2 * 4, hipMemcpyHostToDevice, st));
     p.M = h->d_M.get(); p.m[0].P = h->d_P0.get(); p.m[1].P = h->d_P1.get(); p.Cl = h->d_C.get();
     p.y = h->d_y.get(); p.esq = h->d_esq.get();
-    h->h_p.assign(n_chains, p);
     for (uint32_t c = 0; c < n_chains; ++c) {
         DiffParams &q = h->h_p[c];
+        q = p;
         q.chain = (int)c;
         q.st = h->d_st.get() + per_chain * c;
         q.gam = h->d_gam.get() + (size_t)F * c;
         q.tuned = h->d_tuned.get() + (size_t)F * c;
     }
-    HIP_TRY(hipMemcpyAsync(h->d_p.get(), h->h_p.data(), (size_t)n_chains * sizeof(DiffParams), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(h->d_off.get(), 0, (size_t)n_chains * 4, st));
+    if ((rc = h->upload_params())) return rc;
     const double logitp0 = std::log(pdash) - std::log(1.0 - pdash);
     hipLaunchKernelGGL(k_dfc_init, h->grid(), dim3(DF_BLOCK), 0, st, h->d_p.get(), logitp0, h->gb());
     HIP_TRY(hipGetLastError());
@@ -938,87 +976,25 @@ extern "C" int mmg_diff_chains_create(int device, uint32_t F, uint32_t N, const 
     return MMG_OK;
 }
 
-extern "C" int mmg_diff_chains_burnin(mmg_diff_chains *h, uint32_t iters)
-{
-    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
-    if (h->burnt) return fail(MMG_ERR_STATE, "the burn-in has run already");
-    if (iters == 0 || iters % 1024) return fail(MMG_ERR_ARG, "burn-in iterations must be a positive multiple of 1024");
-    HIP_TRY(hipSetDevice(h->device));
-    for (uint32_t t = 0; t < iters; t += DF_CHUNK) {
-        const uint32_t n = iters - t < DF_CHUNK ? iters - t : DF_CHUNK;
-        hipLaunchKernelGGL(k_dfc_run, h->grid(), dim3(DF_BLOCK), 0, h->st.get(), h->d_p.get(), h->d_off.get(), t, (int)t, (int)n, 0, DF_REC_FROM,
-                           h->gb(), (int)(h->T / DF_NB));
-    }
-    hipLaunchKernelGGL(k_dfc_pseudo, h->grid(), dim3(DF_BLOCK), 0, h->st.get(), h->d_p.get(), (double)(iters - DF_REC_FROM));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(h->st.get()));
-    h->burnin = iters;
-    h->burnt = true;
-    return MMG_OK;
-}
+extern "C" int mmg_diff_chains_burnin(mmg_diff_chains *h, uint32_t iters) { return h ? h->run_burnin(iters) : df_null(); }
 
-extern "C" int mmg_diff_chains_tune_batch(mmg_diff_chains *h, uint32_t *untuned, int32_t *ended)
-{
-    if (!h || !untuned) return fail(MMG_ERR_ARG, "NULL argument");
-    if (!h->burnt) return fail(MMG_ERR_STATE, "mmg_diff_chains_tune_batch before mmg_diff_chains_burnin");
-    if (h->sampled) return fail(MMG_ERR_STATE, "mmg_diff_chains_tune_batch after sampling has started");
-    uint32_t active = 0;
-    for (uint32_t c = 0; c < h->C; ++c)
-        if (!h->ended[c]) active |= 1u << c;
-    for (uint32_t c = 0; c < h->C; ++c) untuned[c] = 0;
-    if (active) {
-        HIP_TRY(hipSetDevice(h->device));
-        HIP_TRY(hipMemsetAsync(h->d_cnt.get(), 0, (size_t)h->C * 4, h->st.get()));
-        const uint32_t it0 = h->burnin + h->batches * DF_BATCH;
-        hipLaunchKernelGGL(k_dfc_tune, h->grid(), dim3(DF_BLOCK), 0, h->st.get(), h->d_p.get(), active, it0, (int)h->batches, h->d_cnt.get());
-        HIP_TRY(hipGetLastError());
-        int cnt[DF_CHAINS_MAX] = {0};
-        HIP_TRY(hipMemcpyAsync(cnt, h->d_cnt.get(), (size_t)h->C * 4, hipMemcpyDeviceToHost, h->st.get()));
-        HIP_TRY(hipStreamSynchronize(h->st.get()));
-        ++h->batches;
-        for (uint32_t c = 0; c < h->C; ++c) {
-            if (h->ended[c]) continue;
-            h->nb[c] = h->batches;
-            untuned[c] = (uint32_t)cnt[c];
-            if (cnt[c] == 0) h->ended[c] = 1;
-        }
-    }
-    if (ended)
-        for (uint32_t c = 0; c < h->C; ++c) ended[c] = h->ended[c] ? 1 : 0;
-    return MMG_OK;
-}
+extern "C" int mmg_diff_chains_tune_batch(mmg_diff_chains *h, uint32_t *untuned, int32_t *ended) { return h ? h->tune_batch(untuned, ended) : df_null(); }
 
 extern "C" int mmg_diff_chains_sample(mmg_diff_chains *h, uint32_t iters)
 {
-    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
-    if (!h->burnt) return fail(MMG_ERR_STATE, "mmg_diff_chains_sample before mmg_diff_chains_burnin");
-    if (iters == 0) return fail(MMG_ERR_ARG, "iters must be positive");
-    // the batch slot of sampling index t is t / (T / 16) < 16 only while t < T
-    if (iters > h->T - h->sampled) return fail(MMG_ERR_ARG, "sampling beyond the total sampling length the handle was created with");
-    HIP_TRY(hipSetDevice(h->device));
-    if (!h->sampled) {
-        // chain c's sampling starts at its own running index, burnin + 128 * (its batches)
-        for (uint32_t c = 0; c < h->C; ++c) h->h_off[c] = h->nb[c] * DF_BATCH;
-        HIP_TRY(hipMemcpyAsync(h->d_off.get(), h->h_off.data(), (size_t)h->C * 4, hipMemcpyHostToDevice, h->st.get()));
-    }
-    for (uint32_t j = 0; j < iters; j += DF_CHUNK) {
-        const uint32_t n = iters - j < DF_CHUNK ? iters - j : DF_CHUNK;
-        hipLaunchKernelGGL(k_dfc_run, h->grid(), dim3(DF_BLOCK), 0, h->st.get(), h->d_p.get(), h->d_off.get(), h->burnin + h->sampled + j,
-                           (int)(h->sampled + j), (int)n, 2, 0, h->gb(), (int)(h->T / DF_NB));
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(h->st.get()));
-    h->sampled += iters;
-    h->pooled = false;
-    return MMG_OK;
+    if (!h) return df_null();
+    const int rc = h->sample(iters);
+    if (!rc) h->pooled = false;
+    return rc;
 }
 
 extern "C" int mmg_diff_chains_pool(mmg_diff_chains *h)
 {
-    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
-    if (h->sampled != h->T) return fail(MMG_ERR_STATE, "mmg_diff_chains_pool before the total sampling length has been sampled");
+    if (!h) return df_null();
+    if (h->sampled != h->sample_total) return fail(MMG_ERR_STATE, "mmg_diff_chains_pool before the total sampling length has been sampled");
     HIP_TRY(hipSetDevice(h->device));
-    hipLaunchKernelGGL(k_dfc_pool, dim3(df_blocks(h->F)), dim3(DF_BLOCK), 0, h->st.get(), h->d_p.get(), (int)h->C, (int)h->T, h->gb(), h->d_pool.get());
+    hipLaunchKernelGGL(k_dfc_pool, dim3(df_blocks(h->F)), dim3(DF_BLOCK), 0, h->st.get(), h->d_p.get(), (int)h->R, (int)h->sample_total, h->gb(),
+                       h->d_pool.get());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(h->st.get()));
     h->pooled = true;
@@ -1027,17 +1003,13 @@ extern "C" int mmg_diff_chains_pool(mmg_diff_chains *h)
 
 extern "C" int mmg_diff_chains_get_results(mmg_diff_chains *h, uint32_t c, double *gamma_mean, double *logitp, double *alpha, double *beta, double *eta)
 {
-    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
-    if (c >= h->C) return fail(MMG_ERR_ARG, "no such chain");
-    if (!h->sampled) return fail(MMG_ERR_STATE, "mmg_diff_chains_get_results before mmg_diff_chains_sample");
-    HIP_TRY(hipSetDevice(h->device));
-    return df_results(h->h_p[c], h->h_p[c].st, h->F, h->K, h->L, h->sampled, gamma_mean, logitp, alpha, beta, eta);
+    return h ? h->results(c, gamma_mean, logitp, alpha, beta, eta) : df_null();
 }
 
 extern "C" int mmg_diff_chains_get_batch_sums(mmg_diff_chains *h, uint32_t c, double *sums)
 {
-    if (!h || !sums) return fail(MMG_ERR_ARG, "NULL argument");
-    if (c >= h->C) return fail(MMG_ERR_ARG, "no such chain");
+    if (!h || !sums) return df_null();
+    if (c >= h->R) return fail(MMG_ERR_ARG, "no such chain");
     if (!h->sampled) return fail(MMG_ERR_STATE, "mmg_diff_chains_get_batch_sums before mmg_diff_chains_sample");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipMemcpy(sums, h->h_p[c].st + h->nslot * h->F, (size_t)DF_NB * h->F * 8, hipMemcpyDeviceToHost));
@@ -1047,7 +1019,7 @@ extern "C" int mmg_diff_chains_get_batch_sums(mmg_diff_chains *h, uint32_t c, do
 extern "C" int mmg_diff_chains_get_pooled(mmg_diff_chains *h, double *log_bf, double *log_bf_sd, double *log_bf_mcse, uint32_t *chains_mixed,
                                           double *alpha, double *beta, double *eta)
 {
-    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
+    if (!h) return df_null();
     if (!h->pooled) return fail(MMG_ERR_STATE, "mmg_diff_chains_get_pooled before mmg_diff_chains_pool");
     HIP_TRY(hipSetDevice(h->device));
     const size_t F = h->F;
@@ -1060,7 +1032,8 @@ extern "C" int mmg_diff_chains_get_pooled(mmg_diff_chains *h, double *log_bf, do
         if (chains_mixed) chains_mixed[f] = (uint32_t)v[3 * F + f];
     }
     // the means: summed sums / summed counts, the quotient on the host as df_results takes it
-    const size_t nq[3] = {2, 2 * (size_t)h->K, (size_t)h->L[0] + h->L[1]};
+    const DiffParams &p = h->h_p[0];
+    const size_t nq[3] = {2, 2 * (size_t)p.K, (size_t)p.m[0].L + (size_t)p.m[1].L};
     double *dst[3] = {alpha, beta, eta};
     size_t q = 0;
     for (int a = 0; a < 3; ++a)
@@ -1074,125 +1047,66 @@ extern "C" int mmg_diff_chains_get_pooled(mmg_diff_chains *h, double *log_bf, do
 
 extern "C" int mmg_diff_chains_info(mmg_diff_chains *h, uint32_t c, int32_t *flags, uint32_t *n_classes, uint32_t *batches, int32_t *ended)
 {
-    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
-    if (c >= h->C) return fail(MMG_ERR_ARG, "no such chain");
-    const DiffParams &p = h->h_p[c];
-    if (flags) { flags[0] = p.Mnil; flags[1] = p.m[0].Pnil; flags[2] = p.m[1].Pnil; }
-    if (n_classes) { n_classes[0] = (uint32_t)p.m[0].nc; n_classes[1] = (uint32_t)p.m[1].nc; }
-    if (batches) *batches = h->nb[c];
-    if (ended) *ended = h->ended[c] ? 1 : 0;
-    return MMG_OK;
+    return h ? h->info(c, flags, n_classes, batches, ended) : df_null();
 }
 
-extern "C" int mmg_diff_chains_device_bytes(mmg_diff_chains *h, uint64_t *bytes)
-{
-    if (!h || !bytes) return fail(MMG_ERR_ARG, "NULL argument");
-    *bytes = h->device_bytes;
-    return MMG_OK;
-}
+extern "C" int mmg_diff_chains_device_bytes(mmg_diff_chains *h, uint64_t *bytes) { return df_device_bytes(h, bytes); }
 
 extern "C" void mmg_diff_chains_destroy(mmg_diff_chains *h) { delete h; }
 
 // ---- a permutation null: the data and B shuffled copies of it on one handle ----------------------------------------------------
 // M / P0 / P1 and the class table once; per replica its y / e^2 ([R][N][F]: replica 0 as given, replica b >= 1 shuffled by
-// k_dfq_shuffle), a DiffParams (replica b in the stream key), a state block, gam / tuned.  The launches are those of mmg_diff_poly_*,
-// grid.y the replica; a replica whose untuned count reached 0 leaves the tuning launches.  stat / null_ge / q: what
+// k_dfq_shuffle), a DiffParams (replica b in the stream key), a state block, gam / tuned.  stat / null_ge / q: what
 // mmg_diff_perm_qvalues leaves on the device.
-constexpr uint32_t DF_PERM_MAX = 31;   // k_dfp_tune's `active` mask has 32 bits: the data and 31 shuffles
+constexpr uint32_t DF_PERM_MAX = DF_RMAX - 1;   // the data and 31 shuffles
 
-struct mmg_diff_perm {
-    DevStream st;
-    int device = 0;
-    uint32_t F = 0, N = 0, K = 0, L[2] = {0, 0}, R = 0;
+struct mmg_diff_perm : DiffReplicas {
     size_t nslot = 0;
     DevBuf<double> d_y, d_esq, d_M, d_P0, d_P1, d_st, d_stat, d_q;
     DevBuf<uint64_t> d_null_ge;
     DevBuf<int> d_C, d_gam, d_tuned;
-    std::vector<DiffParams> h_p;
-    std::vector<uint32_t> h_off, nb;   // per replica: 128 * (its batches); its batches
-    std::vector<char> ended;
-    DevBuf<DiffParams> d_p;
-    DevBuf<uint32_t> d_off;
-    DevBuf<int> d_cnt;
-    uint32_t burnin = 0, batches = 0, sampled = 0;
-    bool burnt = false, have_q = false;
-    uint64_t device_bytes = 0;
-    dim3 grid() const { return dim3(df_blocks(F), R); }
-    ~mmg_diff_perm() { if (st) (void)hipStreamSynchronize(st.get()); }
+    bool have_q = false;
+    mmg_diff_perm() : DiffReplicas("mmg_diff_perm", "replica") {}
+    ~mmg_diff_perm() { drain(); }
 };
 
 extern "C" int mmg_diff_perm_create(int device, uint32_t F, uint32_t N, const double *y, const double *e, uint32_t K, const double *M,
                                     uint32_t L0, const double *P0, uint32_t L1, const double *P1, const int32_t *C, double d, double s,
                                     double pdash, int fixalpha, uint64_t seed, uint32_t n_perm, mmg_diff_perm **out)
 {
-    if (!out || !y || !e || !M || !P0 || !P1 || !C) return fail(MMG_ERR_ARG, "NULL argument");
+    if (!out || !y || !e || !M || !P0 || !P1 || !C) return df_null();
     *out = nullptr;
-    if (F == 0 || F > 0x7fffff00u / DF_BLOCK) return fail(MMG_ERR_ARG, "the number of features must be between 1 and 33554428");
-    if (N < 2 || N > (uint32_t)DF_NMAX) return fail(MMG_ERR_ARG, "the number of samples must be between 2 and 512");
-    if (K < 1 || K > (uint32_t)DF_KMAX) return fail(MMG_ERR_ARG, "M must have between 1 and 8 columns");
-    if (L0 < 1 || L0 > (uint32_t)DF_LMAX || L1 < 1 || L1 > (uint32_t)DF_LMAX) return fail(MMG_ERR_ARG, "P0 and P1 must have between 1 and 16 columns");
+    int nc[2] = {0, 0}, rc;
+    if ((rc = df_check_shape(F, N, K)) || (rc = df_check_cols(L0, 1, &L1))) return rc;
     if (n_perm < 1 || n_perm > DF_PERM_MAX) return fail(MMG_ERR_ARG, "the number of permutations must be between 1 and 31");
-    if (!(d > 0) || !(s > 0) || !std::isfinite(d) || !std::isfinite(s) || !(pdash >= 0 && pdash <= 1))
-        return fail(MMG_ERR_ARG, "d and s must be positive and finite and pdash in [0, 1]");
-    auto finite = [](const double *x, uint64_t n) { for (uint64_t i = 0; i < n; ++i) if (!std::isfinite(x[i])) return false; return true; };
-    if (!finite(y, (uint64_t)F * N) || !finite(e, (uint64_t)F * N)) return fail(MMG_ERR_ARG, "y and e must be finite");
-    if (!finite(M, (uint64_t)N * K) || !finite(P0, (uint64_t)N * L0) || !finite(P1, (uint64_t)N * L1)) return fail(MMG_ERR_ARG, "M, P0 and P1 must be finite");
-    int nc[2] = {0, 0};
-    int rc;
-    for (int mi = 0; mi < 2; ++mi)
-        if ((rc = df_classes(C + mi, 2, N, &nc[mi]))) return rc;
-    if ((rc = require_device(device))) return rc;
+    if ((rc = df_check_prior(d, s, pdash)) || (rc = df_check_finite(F, N, y, e, K, M, L0, P0, L1, P1)) || (rc = df_check_classes(C, N, nc))
+        || (rc = require_device(device)))
+        return rc;
 
     const uint32_t R = n_perm + 1;
     std::unique_ptr<mmg_diff_perm> h(new mmg_diff_perm());
-    h->device = device; h->F = F; h->N = N; h->K = K; h->L[0] = L0; h->L[1] = L1; h->R = R;
-    h->h_off.assign(R, 0);
-    h->nb.assign(R, 0);
-    h->ended.assign(R, 0);
-    DiffParams p{};
-    p.F = (int)F; p.N = (int)N; p.K = (int)K;
-    p.Mnil = df_nil(M, N, K) ? 1 : 0;
-    p.fixalpha = fixalpha ? 1 : 0;
-    p.d = d; p.s = s; p.v_beta = fixalpha ? 25.0 : 4.0;
-    p.seed = seed;
-    p.m[0].Pnil = df_nil(P0, N, L0) ? 1 : 0;
-    p.m[1].Pnil = df_nil(P1, N, L1) ? 1 : 0;
-    h->nslot = df_layout(p, h->L, nc);
+    DiffParams p = df_params(F, N, K, M, L0, P0, L1, P1, d, s, fixalpha, seed);
+    const uint32_t L[2] = {L0, L1};
+    h->nslot = df_layout(p, L, nc);
     const uint64_t FN = (uint64_t)F * N, per_replica = (uint64_t)h->nslot * F;
 
-    auto dalloc = [&](auto &buf, uint64_t count) {
-        HIPE_TRY(buf.alloc(count));
-        h->device_bytes += count * sizeof(*buf.get());
-        return hipSuccess;
-    };
-    HIP_TRY(hipSetDevice(device));
-    HIP_TRY(h->st.create(hipStreamNonBlocking));
+    if ((rc = h->start(device, F, R))) return rc;
     const hipStream_t st = h->st.get();
-    HIP_TRY(dalloc(h->d_y, FN * R));
-    HIP_TRY(dalloc(h->d_esq, FN * R));
-    HIP_TRY(dalloc(h->d_M, (uint64_t)N * K));
-    HIP_TRY(dalloc(h->d_P0, (uint64_t)N * L0));
-    HIP_TRY(dalloc(h->d_P1, (uint64_t)N * L1));
-    HIP_TRY(dalloc(h->d_C, (uint64_t)N * 2));
-    HIP_TRY(dalloc(h->d_st, per_replica * R));
-    HIP_TRY(dalloc(h->d_gam, (uint64_t)F * R));
-    HIP_TRY(dalloc(h->d_tuned, (uint64_t)F * R));
-    HIP_TRY(dalloc(h->d_stat, (uint64_t)F * R));
-    HIP_TRY(dalloc(h->d_q, (uint64_t)F));
-    HIP_TRY(dalloc(h->d_null_ge, (uint64_t)F));
-    HIP_TRY(dalloc(h->d_p, R));
-    HIP_TRY(dalloc(h->d_off, R));
-    HIP_TRY(dalloc(h->d_cnt, R));
-    // y and e^2 transposed to [N][F], as mmg_diff_create holds them: replica 0, copied on the device to every other replica and shuffled there
-    std::vector<double> ty(FN), te(FN);
-    for (uint64_t f = 0; f < F; ++f)
-        for (uint64_t i = 0; i < N; ++i) {
-            ty[i * F + f] = y[f * N + i];
-            const double ei = e[f * N + i];
-            te[i * F + f] = ei * ei;
-        }
-    HIP_TRY(hipMemcpyAsync(h->d_y.get(), ty.data(), FN * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(h->d_esq.get(), te.data(), FN * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(h->dalloc(h->d_y, FN * R));
+    HIP_TRY(h->dalloc(h->d_esq, FN * R));
+    HIP_TRY(h->dalloc(h->d_M, (uint64_t)N * K));
+    HIP_TRY(h->dalloc(h->d_P0, (uint64_t)N * L0));
+    HIP_TRY(h->dalloc(h->d_P1, (uint64_t)N * L1));
+    HIP_TRY(h->dalloc(h->d_C, (uint64_t)N * 2));
+    HIP_TRY(h->dalloc(h->d_st, per_replica * R));
+    HIP_TRY(h->dalloc(h->d_gam, (uint64_t)F * R));
+    HIP_TRY(h->dalloc(h->d_tuned, (uint64_t)F * R));
+    HIP_TRY(h->dalloc(h->d_stat, (uint64_t)F * R));
+    HIP_TRY(h->dalloc(h->d_q, (uint64_t)F));
+    HIP_TRY(h->dalloc(h->d_null_ge, (uint64_t)F));
+    // replica 0 as mmg_diff_create holds the data, copied on the device to every other replica and shuffled there
+    DiffStaged staged;   // (sources of asynchronous copies: alive until the synchronize below)
+    if ((rc = df_upload_transposed(st, F, N, y, e, h->d_y.get(), h->d_esq.get(), staged))) return rc;
     for (uint32_t b = 1; b < R; ++b) {
         HIP_TRY(hipMemcpyAsync(h->d_y.get() + FN * b, h->d_y.get(), FN * 8, hipMemcpyDeviceToDevice, st));
         HIP_TRY(hipMemcpyAsync(h->d_esq.get() + FN * b, h->d_esq.get(), FN * 8, hipMemcpyDeviceToDevice, st));
@@ -1204,9 +1118,9 @@ extern "C" int mmg_diff_perm_create(int device, uint32_t F, uint32_t N, const do
     HIP_TRY(hipMemcpyAsync(h->d_P1.get(), P1, (size_t)N * L1 * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(h->d_C.get(), C, (size_t)N * 2 * 4, hipMemcpyHostToDevice, st));
     p.M = h->d_M.get(); p.m[0].P = h->d_P0.get(); p.m[1].P = h->d_P1.get(); p.Cl = h->d_C.get();
-    h->h_p.assign(R, p);
     for (uint32_t b = 0; b < R; ++b) {
         DiffParams &q = h->h_p[b];
+        q = p;
         q.chain = (int)b;
         q.y = h->d_y.get() + FN * b;
         q.esq = h->d_esq.get() + FN * b;
@@ -1214,111 +1128,40 @@ extern "C" int mmg_diff_perm_create(int device, uint32_t F, uint32_t N, const do
         q.gam = h->d_gam.get() + (size_t)F * b;
         q.tuned = h->d_tuned.get() + (size_t)F * b;
     }
-    HIP_TRY(hipMemcpyAsync(h->d_p.get(), h->h_p.data(), (size_t)R * sizeof(DiffParams), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(h->d_off.get(), 0, (size_t)R * 4, st));
+    if ((rc = h->upload_params())) return rc;
     const double logitp0 = std::log(pdash) - std::log(1.0 - pdash);
     hipLaunchKernelGGL(k_dfp_init, h->grid(), dim3(DF_BLOCK), 0, st, h->d_p.get(), logitp0);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));   // (the host buffers were the sources of asynchronous copies)
+    HIP_TRY(hipStreamSynchronize(st));
     *out = h.release();
     return MMG_OK;
 }
 
-extern "C" int mmg_diff_perm_burnin(mmg_diff_perm *h, uint32_t iters)
-{
-    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
-    if (h->burnt) return fail(MMG_ERR_STATE, "the burn-in has run already");
-    if (iters == 0 || iters % 1024) return fail(MMG_ERR_ARG, "burn-in iterations must be a positive multiple of 1024");
-    HIP_TRY(hipSetDevice(h->device));
-    for (uint32_t t = 0; t < iters; t += DF_CHUNK) {
-        const uint32_t n = iters - t < DF_CHUNK ? iters - t : DF_CHUNK;
-        hipLaunchKernelGGL(k_dfp_run, h->grid(), dim3(DF_BLOCK), 0, h->st.get(), h->d_p.get(), h->d_off.get(), t, (int)t, (int)n, 0, DF_REC_FROM);
-    }
-    hipLaunchKernelGGL(k_dfp_pseudo, h->grid(), dim3(DF_BLOCK), 0, h->st.get(), h->d_p.get(), (double)(iters - DF_REC_FROM));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(h->st.get()));
-    h->burnin = iters;
-    h->burnt = true;
-    return MMG_OK;
-}
+extern "C" int mmg_diff_perm_burnin(mmg_diff_perm *h, uint32_t iters) { return h ? h->run_burnin(iters) : df_null(); }
 
-extern "C" int mmg_diff_perm_tune_batch(mmg_diff_perm *h, uint32_t *untuned, int32_t *ended)
-{
-    if (!h || !untuned) return fail(MMG_ERR_ARG, "NULL argument");
-    if (!h->burnt) return fail(MMG_ERR_STATE, "mmg_diff_perm_tune_batch before mmg_diff_perm_burnin");
-    if (h->sampled) return fail(MMG_ERR_STATE, "mmg_diff_perm_tune_batch after sampling has started");
-    uint32_t active = 0;
-    for (uint32_t b = 0; b < h->R; ++b)
-        if (!h->ended[b]) active |= 1u << b;
-    for (uint32_t b = 0; b < h->R; ++b) untuned[b] = 0;
-    if (active) {
-        HIP_TRY(hipSetDevice(h->device));
-        HIP_TRY(hipMemsetAsync(h->d_cnt.get(), 0, (size_t)h->R * 4, h->st.get()));
-        const uint32_t it0 = h->burnin + h->batches * DF_BATCH;
-        hipLaunchKernelGGL(k_dfp_tune, h->grid(), dim3(DF_BLOCK), 0, h->st.get(), h->d_p.get(), active, it0, (int)h->batches, h->d_cnt.get());
-        HIP_TRY(hipGetLastError());
-        int cnt[DF_PERM_MAX + 1] = {0};
-        HIP_TRY(hipMemcpyAsync(cnt, h->d_cnt.get(), (size_t)h->R * 4, hipMemcpyDeviceToHost, h->st.get()));
-        HIP_TRY(hipStreamSynchronize(h->st.get()));
-        ++h->batches;
-        for (uint32_t b = 0; b < h->R; ++b) {
-            if (h->ended[b]) continue;
-            h->nb[b] = h->batches;
-            untuned[b] = (uint32_t)cnt[b];
-            if (cnt[b] == 0) h->ended[b] = 1;
-        }
-    }
-    if (ended)
-        for (uint32_t b = 0; b < h->R; ++b) ended[b] = h->ended[b] ? 1 : 0;
-    return MMG_OK;
-}
+extern "C" int mmg_diff_perm_tune_batch(mmg_diff_perm *h, uint32_t *untuned, int32_t *ended) { return h ? h->tune_batch(untuned, ended) : df_null(); }
 
 extern "C" int mmg_diff_perm_sample(mmg_diff_perm *h, uint32_t iters)
 {
-    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
-    if (!h->burnt) return fail(MMG_ERR_STATE, "mmg_diff_perm_sample before mmg_diff_perm_burnin");
-    if (iters == 0) return fail(MMG_ERR_ARG, "iters must be positive");
-    HIP_TRY(hipSetDevice(h->device));
-    if (!h->sampled) {
-        // replica b's sampling starts at its own running index, burnin + 128 * (its batches)
-        for (uint32_t b = 0; b < h->R; ++b) h->h_off[b] = h->nb[b] * DF_BATCH;
-        HIP_TRY(hipMemcpyAsync(h->d_off.get(), h->h_off.data(), (size_t)h->R * 4, hipMemcpyHostToDevice, h->st.get()));
-    }
-    for (uint32_t j = 0; j < iters; j += DF_CHUNK) {
-        const uint32_t n = iters - j < DF_CHUNK ? iters - j : DF_CHUNK;
-        hipLaunchKernelGGL(k_dfp_run, h->grid(), dim3(DF_BLOCK), 0, h->st.get(), h->d_p.get(), h->d_off.get(), h->burnin + h->sampled + j, 0, (int)n, 2, 0);
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(h->st.get()));
-    h->sampled += iters;
-    h->have_q = false;
-    return MMG_OK;
+    if (!h) return df_null();
+    const int rc = h->sample(iters);
+    if (!rc) h->have_q = false;
+    return rc;
 }
 
 extern "C" int mmg_diff_perm_get_results(mmg_diff_perm *h, uint32_t b, double *gamma_mean, double *logitp, double *alpha, double *beta, double *eta)
 {
-    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
-    if (b >= h->R) return fail(MMG_ERR_ARG, "no such replica");
-    if (!h->sampled) return fail(MMG_ERR_STATE, "mmg_diff_perm_get_results before mmg_diff_perm_sample");
-    HIP_TRY(hipSetDevice(h->device));
-    return df_results(h->h_p[b], h->h_p[b].st, h->F, h->K, h->L, h->sampled, gamma_mean, logitp, alpha, beta, eta);
+    return h ? h->results(b, gamma_mean, logitp, alpha, beta, eta) : df_null();
 }
 
 extern "C" int mmg_diff_perm_info(mmg_diff_perm *h, uint32_t b, int32_t *flags, uint32_t *n_classes, uint32_t *batches, int32_t *ended)
 {
-    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
-    if (b >= h->R) return fail(MMG_ERR_ARG, "no such replica");
-    const DiffParams &p = h->h_p[b];
-    if (flags) { flags[0] = p.Mnil; flags[1] = p.m[0].Pnil; flags[2] = p.m[1].Pnil; }
-    if (n_classes) { n_classes[0] = (uint32_t)p.m[0].nc; n_classes[1] = (uint32_t)p.m[1].nc; }
-    if (batches) *batches = h->nb[b];
-    if (ended) *ended = h->ended[b] ? 1 : 0;
-    return MMG_OK;
+    return h ? h->info(b, flags, n_classes, batches, ended) : df_null();
 }
 
 extern "C" int mmg_diff_perm_qvalues(mmg_diff_perm *h)
 {
-    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
+    if (!h) return df_null();
     if (!h->sampled) return fail(MMG_ERR_STATE, "mmg_diff_perm_qvalues before mmg_diff_perm_sample");
     HIP_TRY(hipSetDevice(h->device));
     const DiffParams &p = h->h_p[0];
@@ -1333,7 +1176,7 @@ extern "C" int mmg_diff_perm_qvalues(mmg_diff_perm *h)
 
 extern "C" int mmg_diff_perm_get_qvalues(mmg_diff_perm *h, double *stat, uint64_t *null_ge, double *q)
 {
-    if (!h) return fail(MMG_ERR_ARG, "NULL argument");
+    if (!h) return df_null();
     if (!h->have_q) return fail(MMG_ERR_STATE, "mmg_diff_perm_get_qvalues before mmg_diff_perm_qvalues");
     HIP_TRY(hipSetDevice(h->device));
     const size_t F = h->F;
@@ -1343,11 +1186,6 @@ extern "C" int mmg_diff_perm_get_qvalues(mmg_diff_perm *h, double *stat, uint64_
     return MMG_OK;
 }
 
-extern "C" int mmg_diff_perm_device_bytes(mmg_diff_perm *h, uint64_t *bytes)
-{
-    if (!h || !bytes) return fail(MMG_ERR_ARG, "NULL argument");
-    *bytes = h->device_bytes;
-    return MMG_OK;
-}
+extern "C" int mmg_diff_perm_device_bytes(mmg_diff_perm *h, uint64_t *bytes) { return df_device_bytes(h, bytes); }
 
 extern "C" void mmg_diff_perm_destroy(mmg_diff_perm *h) { delete h; }

@@ -691,23 +691,7 @@ __global__ void __launch_bounds__(DF_BLOCK) k_dfc_run(const DiffParams *__restri
     }
 }
 
-// as k_dfp_tune, `active` the chains still tuning
-__global__ void __launch_bounds__(DF_BLOCK) k_dfc_tune(const DiffParams *__restrict__ ps, uint32_t active, uint32_t it0, int b,
-                                                       int *__restrict__ untuned)
-{
-    if (!((active >> blockIdx.y) & 1u)) return;
-    const DiffParams &p = ps[blockIdx.y];
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= p.F) return;
-    if (df_tune(p, f, it0, b)) atomicAdd(untuned + blockIdx.y, 1);
-}
-
-__global__ void k_dfc_pseudo(const DiffParams *__restrict__ ps, double runlen)
-{
-    const DiffParams &p = ps[blockIdx.y];
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f < p.F) df_pseudo(p, f, runlen);
-}
+// (tuning and the pseudopriors are k_dfp_tune and k_dfp_pseudo, `active` the chains still tuning)
 
 MMG_HD double df_sigmoid(double x) { return x > 0 ? 1.0 / (1.0 + dexp(-x)) : dexp(x) / (1.0 + dexp(x)); }
 

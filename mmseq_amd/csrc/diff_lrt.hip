@@ -30,18 +30,11 @@ namespace mmg {
 int lrt_check_args(int device, uint32_t F, uint32_t N, const double *y, const double *e, uint32_t K, const double *M, uint32_t L0, const double *P0,
                    uint32_t L1, const double *P1, const int32_t *C, int nc[2])
 {
-    if (F == 0 || F > 0x7fffff00u / LRT_BLOCK) return fail(MMG_ERR_ARG, "the number of features must be between 1 and 33554428");
-    if (N < 2 || N > (uint32_t)LRT_NMAX) return fail(MMG_ERR_ARG, "the number of samples must be between 2 and 512");
-    if (K < 1 || K > (uint32_t)LRT_KMAX) return fail(MMG_ERR_ARG, "M must have between 1 and 8 columns");
-    if (L0 < 1 || L0 > (uint32_t)LRT_LMAX || L1 < 1 || L1 > (uint32_t)LRT_LMAX) return fail(MMG_ERR_ARG, "P0 and P1 must have between 1 and 16 columns");
-    auto finite = [](const double *x, uint64_t n) { for (uint64_t i = 0; i < n; ++i) if (!std::isfinite(x[i])) return false; return true; };
-    if (!finite(y, (uint64_t)F * N) || !finite(e, (uint64_t)F * N)) return fail(MMG_ERR_ARG, "y and e must be finite");
-    if (!finite(M, (uint64_t)N * K) || !finite(P0, (uint64_t)N * L0) || !finite(P1, (uint64_t)N * L1)) return fail(MMG_ERR_ARG, "M, P0 and P1 must be finite");
-    nc[0] = nc[1] = 0;
-    for (int mi = 0; mi < 2; ++mi) {
-        const int rc = df_classes(C + mi, 2, N, &nc[mi]);
-        if (rc) return rc;
-    }
+    // (the caps are mmg_diff_create's: the static_assert of diff.hip)
+    int rc;
+    if ((rc = df_check_shape(F, N, K)) || (rc = df_check_cols(L0, 1, &L1)) || (rc = df_check_finite(F, N, y, e, K, M, L0, P0, L1, P1))
+        || (rc = df_check_classes(C, N, nc)))
+        return rc;
     return require_device(device);
 }
 
@@ -63,7 +56,7 @@ int lrt_observed(int device, uint32_t F, uint32_t N, const double *y, const doub
     // the device arrays are the caller's (D) and go when it lets them; the host sources of the asynchronous copies are locals, and
     // `drain`, the last local, waits for the stream before they go
     const uint64_t FN = (uint64_t)F * N;
-    std::vector<double> ty(FN), te(FN);
+    DiffStaged staged;
     std::vector<int> cls(2 * (size_t)N);
     DevStream &st = D.st;
     DevBuf<double> &d_y = D.d_y, &d_esq = D.d_esq, (&d_X)[2] = D.d_X, (&d_theta)[2] = D.d_theta, (&d_sig)[2] = D.d_sig, &d_ll = D.d_ll, &d_ws = D.d_ws;
@@ -91,15 +84,9 @@ int lrt_observed(int device, uint32_t F, uint32_t N, const double *y, const doub
     HIP_TRY(dalloc(d_iters, 2ull * F));
     HIP_TRY(dalloc(d_status, 2ull * F));
     // y and e^2 transposed to [N][F], as mmg_diff_create holds them; the classes as [2][N]
-    for (uint64_t f = 0; f < F; ++f)
-        for (uint64_t i = 0; i < N; ++i) {
-            ty[i * F + f] = y[f * N + i];
-            const double ei = e[f * N + i];
-            te[i * F + f] = ei * ei;
-        }
     for (uint32_t i = 0; i < N; ++i) { cls[i] = C[i * 2]; cls[N + i] = C[i * 2 + 1]; }
-    HIP_TRY(hipMemcpyAsync(d_y.get(), ty.data(), FN * 8, hipMemcpyHostToDevice, st.get()));
-    HIP_TRY(hipMemcpyAsync(d_esq.get(), te.data(), FN * 8, hipMemcpyHostToDevice, st.get()));
+    const int rc = df_upload_transposed(st.get(), F, N, y, e, d_y.get(), d_esq.get(), staged);
+    if (rc) return rc;
     for (int mi = 0; mi < 2; ++mi)
         if (h->p[mi]) HIP_TRY(hipMemcpyAsync(d_X[mi].get(), X[mi].data(), X[mi].size() * 8, hipMemcpyHostToDevice, st.get()));
     HIP_TRY(hipMemcpyAsync(d_cls.get(), cls.data(), cls.size() * 4, hipMemcpyHostToDevice, st.get()));

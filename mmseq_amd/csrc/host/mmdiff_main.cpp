@@ -15,6 +15,9 @@
 //
 // -effects FILE keeps thinned sampling rows on the device and writes their per-feature summaries (mean, sd, P(> 0), percentiles of
 // every parameter under its own model): write_effects below and DESIGN.md section 10.3.
+//
+// main() is a sequence of stages over Options, Inputs, Model and Mcmc: parse_args, check_combinations, the -polyclass shortcut,
+// load_inputs, the design, then run_poly, run_chains, run_perm (all three on run_replicas) or run_plain (with run_lrt).
 #include <algorithm>
 #include <atomic>
 #include <cfloat>
@@ -478,6 +481,27 @@ void validate_design(const Design &D, size_t S, bool fixalpha, bool &Mnil, bool 
     if (Pnil[1]) cerr << "Note: no etas in model 1\n";
 }
 
+// ---- what the stages of a run hand on ---------------------------------------------------------------------------------------------
+// the input tables: y and e as [feature][sample], normalised and permuted as the options ask
+struct Inputs {
+    vector<string> features, filenames;
+    Mat y, e;
+};
+
+// a validated comparison: the design and what of it is nil
+struct Model {
+    Design D;
+    bool Mnil = false, Pnil[2] = {false, false};
+};
+
+// -p, -d, -s, -pdash, -fixalpha, -notune, -burnin, -iter, -seed
+struct Mcmc {
+    double p = 0.1, d = 1.4, s = 2.0, pdash = 0.5;
+    bool fixalpha = false, tune = true;
+    int burnin = 8192, iters = 16384;
+    uint64_t seed = 1234;
+};
+
 struct DiffResults {
     vector<double> gm, logitp, alpha, beta, eta;
     DiffResults(size_t F, const Design &D) : gm(F), logitp(F), alpha(2 * F), beta(2 * D.K * F), eta((D.L0 + D.L1) * F) {}
@@ -497,13 +521,26 @@ struct PermCols {
     PermCols(size_t F) : null_ge(F), q(F) {}
 };
 
+// what a table has besides the plain one's columns.  warn_stuck: off for the tables of a run of several chains, which reports mixing per
+// feature itself.
+struct TableExtras {
+    bool warn_stuck = true;
+    const PooledCols *pool = nullptr;
+    const PermCols *perm = nullptr;
+};
+
 // The table of one comparison: to fp (if any) and appended to *keep (if any).  The Bayes factor is the chain's own, with the warning for
-// a gamma that did not mix -- or, with `pool` (the pooled table of several chains: its columns are appended), exp(log_bf).  warn_stuck:
-// off for the tables of a run of several chains, which reports mixing per feature itself.  With `perm` its two columns are appended.
-void write_table(FILE *fp, string *keep, const vector<string> &features, const vector<string> &filenames, const Design &D, bool fixalpha,
-                 bool Mnil, const bool Pnil[2], double p, const Mat &y, const Mat &e, const DiffResults &r, bool warn_stuck = true,
-                 const PooledCols *pool = nullptr, const PermCols *perm = nullptr)
+// a gamma that did not mix -- or, with x.pool (the pooled table of several chains: its columns are appended), exp(log_bf).  With x.perm
+// its two columns are appended.
+void write_table(FILE *fp, string *keep, const Inputs &in, const Model &model, const Mcmc &mc, const DiffResults &r, const TableExtras &x = {})
 {
+    const vector<string> &features = in.features, &filenames = in.filenames;
+    const Mat &y = in.y, &e = in.e;
+    const Design &D = model.D;
+    const bool fixalpha = mc.fixalpha, Mnil = model.Mnil, *Pnil = model.Pnil, warn_stuck = x.warn_stuck;
+    const double p = mc.p;
+    const PooledCols *pool = x.pool;
+    const PermCols *perm = x.perm;
     const size_t F = features.size(), S = filenames.size();
     const vector<double> &gm = r.gm, &logitp = r.logitp, &alpha = r.alpha, &beta = r.beta, &eta = r.eta;
     auto emit = [&](const string &t) {
@@ -639,6 +676,24 @@ void check_same_features(const PolyTable &A, const string &a, const PolyTable &B
             die("Error: features across tables do not match (" + to_string(i) + "," + B.features[i] + "," + A.features[i] + ")");
 }
 
+// a comma-separated list (-prior, -effects_percentiles): every item all of a finite number in [lo, hi], or die(msg)
+vector<double> parse_list(const string &text, double lo, double hi, const string &msg)
+{
+    vector<double> list;
+    size_t a = 0;
+    while (true) {
+        const size_t b = text.find(',', a);
+        const string tok = text.substr(a, b == string::npos ? string::npos : b - a);
+        char *end = NULL;
+        const double v = strtod(tok.c_str(), &end);
+        if (tok.empty() || *end != '\0' || !std::isfinite(v) || v < lo || v > hi) die(msg);
+        list.push_back(v);
+        if (b == string::npos) break;
+        a = b + 1;
+    }
+    return list;
+}
+
 // -prior: n finite values in [0, 1] adding up to 1 within 1.5e-8 (R's all.equal); without it the flat prior and R's warning
 vector<double> parse_prior(bool given, const string &text, size_t n)
 {
@@ -647,18 +702,7 @@ vector<double> parse_prior(bool given, const string &text, size_t n)
         return vector<double>(n, 1.0 / (double)n);
     }
     const string msg = "Error: -prior must list " + to_string(n) + " prior probabilities (one per model, model 0 first) in [0, 1] adding up to 1.";
-    vector<double> prior;
-    size_t a = 0;
-    while (true) {
-        const size_t b = text.find(',', a);
-        const string tok = text.substr(a, b == string::npos ? string::npos : b - a);
-        char *end = NULL;
-        const double v = strtod(tok.c_str(), &end);
-        if (tok.empty() || *end != '\0' || !std::isfinite(v) || v < 0 || v > 1) die(msg);
-        prior.push_back(v);
-        if (b == string::npos) break;
-        a = b + 1;
-    }
+    const vector<double> prior = parse_list(text, 0, 1, msg);
     double sum = 0;
     for (double v : prior) sum += v;
     if (prior.size() != n || !(fabs(sum - 1.0) <= 1.5e-8)) die(msg);
@@ -720,226 +764,6 @@ bool need(const vector<string> &a, size_t n)
 {
     if (a.size() < n) usage_error("Error: mandatory arguments missing.");
     return true;
-}
-
-// repeated -m: J alternatives against one model 0 on one device handle.  Table j (what `mmdiff <same options> -m alt_j <same tables>`
-// prints) goes to BASE.model<j>.mmdiff with -polyout; stdout gets polyclass of the tables, from the Bayes factors as the tables print
-// them (%g text parsed back), so that `mmdiff -polyclass` on the written tables reproduces it byte for byte.
-int run_poly(const vector<string> &mats, bool prior_given, const string &prior_text, bool polyout_given, const string &polyout,
-             const vector<string> &features, const vector<string> &filenames, const Mat &y, const Mat &e, double p, double d, double s,
-             double pdash, bool fixalpha, bool tune, int burnin, int mcmciters, uint64_t useed)
-{
-    const size_t J = mats.size(), S = filenames.size(), F = features.size();
-    vector<Design> Ds(J);
-    vector<char> Mnil(J), Pnil0(J), Pnil1(J);
-    for (size_t j = 0; j < J; ++j) {
-        cerr << "Alternative " << j + 1 << " (" << mats[j] << "):\n";
-        parse_matrices(mats[j], Ds[j], S);
-        bool mn = false, pn[2] = {false, false};
-        validate_design(Ds[j], S, fixalpha, mn, pn);
-        Mnil[j] = mn; Pnil0[j] = pn[0]; Pnil1[j] = pn[1];
-        bool same = Ds[j].K == Ds[0].K && Ds[j].L0 == Ds[0].L0 && Ds[j].M == Ds[0].M && Ds[j].P0 == Ds[0].P0;
-        for (size_t i = 0; same && i < S; ++i) same = Ds[j].C[i * 2] == Ds[0].C[i * 2];
-        if (!same) die("Error: model 0 differs between " + mats[0] + " and " + mats[j]);
-    }
-    const vector<double> prior = parse_prior(prior_given, prior_text, J + 1);
-    struct Closer { vector<FILE *> f; ~Closer() { for (FILE *x : f) if (x) fclose(x); } } files;
-    files.f.assign(J, nullptr);
-    if (polyout_given)
-        for (size_t j = 0; j < J; ++j) {
-            const string name = polyout + ".model" + to_string(j + 1) + ".mmdiff";
-            if (!(files.f[j] = fopen(name.c_str(), "w"))) die("Error: couldn't create " + name);
-        }
-
-    // every input is checked: now the device
-    int ndev = 0;
-    if (mmg_device_count(&ndev) != 0 || ndev < 1) die("Error: no HIP device available: mmdiff has no CPU fallback");
-    vector<uint32_t> L1(J);
-    Mat P1;
-    vector<int> C0(S), C1(J * S);
-    for (size_t i = 0; i < S; ++i) C0[i] = Ds[0].C[i * 2];
-    for (size_t j = 0; j < J; ++j) {
-        L1[j] = (uint32_t)Ds[j].L1;
-        P1.insert(P1.end(), Ds[j].P1.begin(), Ds[j].P1.end());
-        for (size_t i = 0; i < S; ++i) C1[j * S + i] = Ds[j].C[i * 2 + 1];
-    }
-    mmg_diff_poly *h = nullptr;
-    MMG_CHECK(mmg_diff_poly_create(0, (uint32_t)F, (uint32_t)S, y.data(), e.data(), (uint32_t)Ds[0].K, Ds[0].M.data(), (uint32_t)Ds[0].L0,
-                                   Ds[0].P0.data(), C0.data(), (uint32_t)J, L1.data(), P1.data(), C1.data(), d, s, pdash, fixalpha ? 1 : 0,
-                                   useed, &h));
-    cerr << "BURNIN (" << burnin << " iterations, " << J << " alternatives)...";
-    MMG_CHECK(mmg_diff_poly_burnin(h, (uint32_t)burnin));
-    cerr << "\nSetting pseudopriors...done.\n";
-    if (tune) {
-        // each comparison stops at the first batch after which none of its features is untuned, or with the others at MAXBATCHES
-        vector<uint32_t> untuned(J);
-        vector<int32_t> ended(J);
-        int numbatches = 0;
-        bool all_ended = false;
-        while (!all_ended && numbatches != MAXBATCHES) {
-            MMG_CHECK(mmg_diff_poly_tune_batch(h, untuned.data(), ended.data()));
-            numbatches++;
-            all_ended = true;
-            uint64_t left = 0;
-            for (size_t j = 0; j < J; ++j) { all_ended = all_ended && ended[j]; left += untuned[j]; }
-            if (numbatches % 64 == 0) cerr << "TUNING BATCH " << numbatches << " (" << left << " left)\r";
-        }
-    }
-    for (size_t j = 0; j < J; ++j) {
-        uint32_t nb = 0;
-        MMG_CHECK(mmg_diff_poly_info(h, (uint32_t)j, NULL, NULL, &nb, NULL));
-        cerr << "model " << j + 1 << ": sampling after " << nb << " tuning batches\n";
-    }
-    cerr << "TRACE (" << mcmciters << " iterations)";
-    MMG_CHECK(mmg_diff_poly_sample(h, (uint32_t)mcmciters));
-    cerr << "\nDONE MCMC\n";
-    vector<PolyTable> T(J);
-    for (size_t j = 0; j < J; ++j) {
-        DiffResults r(F, Ds[j]);
-        MMG_CHECK(mmg_diff_poly_get_results(h, (uint32_t)j, r.gm.data(), r.logitp.data(), r.alpha.data(), r.beta.data(), r.eta.data()));
-        string text;
-        const bool pn[2] = {(bool)Pnil0[j], (bool)Pnil1[j]};
-        write_table(files.f[j], &text, features, filenames, Ds[j], fixalpha, Mnil[j], pn, p, y, e, r);
-        if (files.f[j] && fflush(files.f[j]) != 0) die("Error: couldn't write " + polyout + ".model" + to_string(j + 1) + ".mmdiff");
-        istringstream in(text);
-        parse_poly_table(in, "the table of alternative " + to_string(j + 1), j == 0, T[j]);
-    }
-    mmg_diff_poly_destroy(h);
-    polyclass(T, prior, stdout);
-    return 0;
-}
-
-// -chains C, C >= 2: C chains of one comparison on one device handle, chain c keyed (seed, c).  Table c (what a single run prints for
-// that chain) goes to BASE.chain<c>.mmdiff with -chainout; stdout gets the pooled table.
-int run_chains(int C, bool chainout_given, const string &chainout, const Design &D, bool Mnil, const bool Pnil[2],
-               const vector<string> &features, const vector<string> &filenames, const Mat &y, const Mat &e, double p, double d, double s,
-               double pdash, bool fixalpha, bool tune, int burnin, int mcmciters, uint64_t useed)
-{
-    const size_t S = filenames.size(), F = features.size();
-    struct Closer { vector<FILE *> f; ~Closer() { for (FILE *x : f) if (x) fclose(x); } } files;
-    files.f.assign(C, nullptr);
-    auto name = [&](int c) { return chainout + ".chain" + to_string(c) + ".mmdiff"; };
-    if (chainout_given)
-        for (int c = 0; c < C; ++c)
-            if (!(files.f[c] = fopen(name(c).c_str(), "w"))) die("Error: couldn't create " + name(c));
-
-    // every input is checked: now the device
-    int ndev = 0;
-    if (mmg_device_count(&ndev) != 0 || ndev < 1) die("Error: no HIP device available: mmdiff has no CPU fallback");
-    mmg_diff_chains *h = nullptr;
-    MMG_CHECK(mmg_diff_chains_create(0, (uint32_t)F, (uint32_t)S, y.data(), e.data(), (uint32_t)D.K, D.M.data(), (uint32_t)D.L0, D.P0.data(),
-                                     (uint32_t)D.L1, D.P1.data(), D.C.data(), d, s, pdash, fixalpha ? 1 : 0, useed, (uint32_t)C,
-                                     (uint32_t)mcmciters, &h));
-    cerr << "BURNIN (" << burnin << " iterations, " << C << " chains)...";
-    MMG_CHECK(mmg_diff_chains_burnin(h, (uint32_t)burnin));
-    cerr << "\nSetting pseudopriors...done.\n";
-    if (tune) {
-        // each chain stops at the first batch after which none of its features is untuned, or with the others at MAXBATCHES
-        vector<uint32_t> untuned(C);
-        vector<int32_t> ended(C);
-        int numbatches = 0;
-        bool all_ended = false;
-        while (!all_ended && numbatches != MAXBATCHES) {
-            MMG_CHECK(mmg_diff_chains_tune_batch(h, untuned.data(), ended.data()));
-            numbatches++;
-            all_ended = true;
-            uint64_t left = 0;
-            for (int c = 0; c < C; ++c) { all_ended = all_ended && ended[c]; left += untuned[c]; }
-            if (numbatches % 64 == 0) cerr << "TUNING BATCH " << numbatches << " (" << left << " left)\r";
-        }
-    }
-    for (int c = 0; c < C; ++c) {
-        uint32_t nb = 0;
-        MMG_CHECK(mmg_diff_chains_info(h, (uint32_t)c, NULL, NULL, &nb, NULL));
-        cerr << "chain " << c << ": sampling after " << nb << " tuning batches\n";
-    }
-    cerr << "TRACE (" << mcmciters << " iterations)";
-    MMG_CHECK(mmg_diff_chains_sample(h, (uint32_t)mcmciters));
-    MMG_CHECK(mmg_diff_chains_pool(h));
-    cerr << "\nDONE MCMC\n";
-    DiffResults r(F, D);
-    for (int c = 0; c < C && chainout_given; ++c) {
-        MMG_CHECK(mmg_diff_chains_get_results(h, (uint32_t)c, r.gm.data(), r.logitp.data(), r.alpha.data(), r.beta.data(), r.eta.data()));
-        write_table(files.f[c], nullptr, features, filenames, D, fixalpha, Mnil, Pnil, p, y, e, r, false);
-        if (fflush(files.f[c]) != 0) die("Error: couldn't write " + name(c));
-    }
-    // the pooled table: chain 0's gamma mean and logit p' are not printed (the Bayes factor is exp(log_bf)), the means are the pooled ones
-    PooledCols pool(F);
-    MMG_CHECK(mmg_diff_chains_get_results(h, 0, r.gm.data(), r.logitp.data(), NULL, NULL, NULL));
-    MMG_CHECK(mmg_diff_chains_get_pooled(h, pool.log_bf.data(), pool.log_bf_sd.data(), pool.log_bf_mcse.data(), pool.chains_mixed.data(),
-                                         r.alpha.data(), r.beta.data(), r.eta.data()));
-    mmg_diff_chains_destroy(h);
-    for (size_t f = 0; f < F; ++f)
-        if (pool.chains_mixed[f] < (uint32_t)C)
-            cerr << "Warning: gamma mixed in " << pool.chains_mixed[f] << " of " << C << " chains for feature " << f << endl;
-    write_table(stdout, nullptr, features, filenames, D, fixalpha, Mnil, Pnil, p, y, e, r, false, &pool);
-    return 0;
-}
-
-// -permutations B: the data and B shuffled copies of it on one device handle (DESIGN.md section 10.4).  stdout gets the plain run's
-// table with perm_ge and q_value appended; the table of shuffled copy b (what -permute prints with the seed seed ^ (b << 32)) goes to
-// BASE.perm<b>.mmdiff with -permout.
-int run_perm(int B, bool permout_given, const string &permout, const Design &D, bool Mnil, const bool Pnil[2], const vector<string> &features,
-             const vector<string> &filenames, const Mat &y, const Mat &e, double p, double d, double s, double pdash, bool fixalpha, bool tune,
-             int burnin, int mcmciters, uint64_t useed)
-{
-    const size_t S = filenames.size(), F = features.size();
-    const int R = B + 1;
-    struct Closer { vector<FILE *> f; ~Closer() { for (FILE *x : f) if (x) fclose(x); } } files;
-    files.f.assign(R, nullptr);
-    auto name = [&](int b) { return permout + ".perm" + to_string(b) + ".mmdiff"; };
-    if (permout_given)
-        for (int b = 1; b < R; ++b)
-            if (!(files.f[b] = fopen(name(b).c_str(), "w"))) die("Error: couldn't create " + name(b));
-
-    // every input is checked: now the device
-    int ndev = 0;
-    if (mmg_device_count(&ndev) != 0 || ndev < 1) die("Error: no HIP device available: mmdiff has no CPU fallback");
-    mmg_diff_perm *h = nullptr;
-    MMG_CHECK(mmg_diff_perm_create(0, (uint32_t)F, (uint32_t)S, y.data(), e.data(), (uint32_t)D.K, D.M.data(), (uint32_t)D.L0, D.P0.data(),
-                                   (uint32_t)D.L1, D.P1.data(), D.C.data(), d, s, pdash, fixalpha ? 1 : 0, useed, (uint32_t)B, &h));
-    cerr << "BURNIN (" << burnin << " iterations, the data and " << B << " permutations)...";
-    MMG_CHECK(mmg_diff_perm_burnin(h, (uint32_t)burnin));
-    cerr << "\nSetting pseudopriors...done.\n";
-    if (tune) {
-        // each replica stops at the first batch after which none of its features is untuned, or with the others at MAXBATCHES
-        vector<uint32_t> untuned(R);
-        vector<int32_t> ended(R);
-        int numbatches = 0;
-        bool all_ended = false;
-        while (!all_ended && numbatches != MAXBATCHES) {
-            MMG_CHECK(mmg_diff_perm_tune_batch(h, untuned.data(), ended.data()));
-            numbatches++;
-            all_ended = true;
-            uint64_t left = 0;
-            for (int b = 0; b < R; ++b) { all_ended = all_ended && ended[b]; left += untuned[b]; }
-            if (numbatches % 64 == 0) cerr << "TUNING BATCH " << numbatches << " (" << left << " left)\r";
-        }
-    }
-    for (int b = 0; b < R; ++b) {
-        uint32_t nb = 0;
-        MMG_CHECK(mmg_diff_perm_info(h, (uint32_t)b, NULL, NULL, &nb, NULL));
-        cerr << "replica " << b << ": sampling after " << nb << " tuning batches\n";
-    }
-    cerr << "TRACE (" << mcmciters << " iterations)";
-    MMG_CHECK(mmg_diff_perm_sample(h, (uint32_t)mcmciters));
-    MMG_CHECK(mmg_diff_perm_qvalues(h));
-    cerr << "\nDONE MCMC\n";
-    DiffResults r(F, D);
-    for (int b = 1; b < R && permout_given; ++b) {
-        // the table's mu_ / sd_ columns: the shuffle the device applied to replica b, on the host
-        Mat yb = y, eb = e;
-        apply_permutation(yb, eb, F, S, useed ^ ((uint64_t)b << 32), true);
-        MMG_CHECK(mmg_diff_perm_get_results(h, (uint32_t)b, r.gm.data(), r.logitp.data(), r.alpha.data(), r.beta.data(), r.eta.data()));
-        write_table(files.f[b], nullptr, features, filenames, D, fixalpha, Mnil, Pnil, p, yb, eb, r, false);
-        if (fflush(files.f[b]) != 0) die("Error: couldn't write " + name(b));
-    }
-    PermCols cols(F);
-    MMG_CHECK(mmg_diff_perm_get_results(h, 0, r.gm.data(), r.logitp.data(), r.alpha.data(), r.beta.data(), r.eta.data()));
-    MMG_CHECK(mmg_diff_perm_get_qvalues(h, NULL, cols.null_ge.data(), cols.q.data()));
-    mmg_diff_perm_destroy(h);
-    write_table(stdout, nullptr, features, filenames, D, fixalpha, Mnil, Pnil, p, y, e, r, true, nullptr, &cols);
-    return 0;
 }
 
 // ---- -traces DIR: the files of the reference's -tracedir (BMS::initialise_streams, print, printtune, print_pseudo) ------------------
@@ -1141,18 +965,7 @@ private:
 vector<double> parse_percentiles(const string &text)
 {
     const string msg = "Error: -effects_percentiles takes a comma-separated list of 1 to " + to_string(MAXPERCENTILES) + " percentiles in [0, 100].";
-    vector<double> pct;
-    size_t a = 0;
-    while (true) {
-        const size_t b = text.find(',', a);
-        const string tok = text.substr(a, b == string::npos ? string::npos : b - a);
-        char *end = NULL;
-        const double v = strtod(tok.c_str(), &end);
-        if (tok.empty() || *end != '\0' || !std::isfinite(v) || v < 0 || v > 100) die(msg);
-        pct.push_back(v);
-        if (b == string::npos) break;
-        a = b + 1;
-    }
+    const vector<double> pct = parse_list(text, 0, 100, msg);
     if (pct.size() > MAXPERCENTILES) die(msg);
     return pct;
 }
@@ -1167,28 +980,36 @@ string fmt9(double x)
 }
 
 // whether the model of traced parameter `name` (alpha<m>, beta<m>_k, eta<m>_l, lambda<m>_l, sigmasq<m>_c, rho<m>) has it
-bool model_has(const string &name, bool fixalpha, bool Mnil, const bool Pnil[2])
+bool model_has(const string &name, bool fixalpha, const Model &model)
 {
     const string stem = name.substr(0, name.find('_'));
     const int m = stem.back() - '0';
     const string kind = stem.substr(0, stem.size() - 1);
     if (kind == "alpha") return !fixalpha;
-    if (kind == "beta") return !Mnil;
-    if (kind == "eta" || kind == "lambda") return !Pnil[m];
+    if (kind == "beta") return !model.Mnil;
+    if (kind == "eta" || kind == "lambda") return !model.Pnil[m];
     return true;
 }
 
-// The effects table: a line per feature, in the order of the stdout table.  names: the traced parameters without gamma.
-void write_effects(const string &file, const vector<string> &features, const vector<string> &names, const vector<double> &pct, bool fixalpha,
-                   bool Mnil, const bool Pnil[2], const vector<uint32_t> &n, const vector<double> &mean, const vector<double> &sd,
-                   const vector<uint32_t> &n_gt, const vector<double> &q)
+// what mmg_effects_get gives, and the traced parameters without gamma
+struct Effects {
+    vector<string> names;
+    vector<uint32_t> n, n_gt;
+    vector<double> mean, sd, q;
+};
+
+// The effects table: a line per feature, in the order of the stdout table.
+void write_effects(const string &file, const vector<string> &features, const vector<double> &pct, bool fixalpha, const Model &model, const Effects &fx)
 {
+    const vector<string> &names = fx.names;
+    const vector<uint32_t> &n = fx.n, &n_gt = fx.n_gt;
+    const vector<double> &mean = fx.mean, &sd = fx.sd, &q = fx.q;
     FILE *fp = fopen(file.c_str(), "w");
     if (!fp) die("Error: couldn't create " + file);
     const size_t F = features.size(), np = pct.size();
     vector<size_t> cols;
     for (size_t s = 0; s < names.size(); ++s)
-        if (model_has(names[s], fixalpha, Mnil, Pnil)) cols.push_back(s);
+        if (model_has(names[s], fixalpha, model)) cols.push_back(s);
     string out = "feature_id\tn0\tn1";
     for (size_t s : cols) {
         out += "\t" + names[s] + "_mean\t" + names[s] + "_sd\t" + names[s] + "_p_gt0";
@@ -1259,180 +1080,179 @@ void write_lrt(FILE *fp, const string &file, const vector<string> &features, con
     if (fflush(fp) != 0 || !ok) die("Error: couldn't write " + file);
 }
 
-} // namespace
-
-int main(int argc, char **argv)
-{
-    string matrices_file = "";
+// ---- options ------------------------------------------------------------------------------------------------------------------------
+struct Options {
     vector<string> matrices_files;   // every -m; more than one: the polytomous run
-    bool polyclass_mode = false, prior_given = false, polyout_given = false, chains_given = false, chainout_given = false, perms_given = false, permout_given = false;
+    vector<int> simple_de;           // -de
+    vector<string> files;            // what follows the options: the mmseq tables or, with -polyclass, mmdiff tables
+    bool polyclass_mode = false, prior_given = false, polyout_given = false, chains_given = false, chainout_given = false, perms_given = false,
+         permout_given = false, lrt_given = false, lrt_only = false, lrtperm_given = false, effects_every_given = false, effects_pct_given = false;
     string prior_text, polyout, chainout, permout, traces, effects, effects_pct_text = "2.5,50,97.5", lrt_file;
-    bool lrt_given = false, lrt_only = false, lrtperm_given = false;
-    long lrt_perms = 0;
-    bool effects_every_given = false, effects_pct_given = false;
-    long effects_every = 0;
-    int chains = 1, perms = 0;
-    double p = 0.1, d = 1.4, s = 2.0;
-    int burnin = 8192, mcmciters = 16384, seed = 1234, range_start = -1, range_end = -1;
-    bool useprops = false, fixalpha = false, normalise = true, customuhfrac = false, permute = false, tune = true;
-    double uhfrac = -1, pdash = 0.5;
-    vector<int> simple_de;
-    int ss = 0;
+    long lrt_perms = 0, effects_every = 0;
+    uint32_t effects_rows = 0;       // with -effects: the rows -iter and -effects_every give
+    vector<double> effects_pct;
+    int chains = 1, perms = 0, range_start = -1, range_end = -1;
+    bool useprops = false, normalise = true, customuhfrac = false, permute = false;
+    double uhfrac = -1;
+    Mcmc mc;
+    bool poly_run() const { return matrices_files.size() > 1; }
+};
 
+// the value of -chains, -permutations, -lrtperm or -effects_every: all of `v` a decimal number between lo and hi
+long int_option(const string &name, const string &v, long lo, long hi, bool usage = false)
+{
+    char *end = NULL;
+    const long n = strtol(v.c_str(), &end, 10);
+    if (v.empty() || *end != '\0' || n < lo || n > hi) {
+        const string msg = "Error: " + name + " takes an integer between " + to_string(lo) + " and " + to_string(hi) + ".";
+        if (usage) usage_error(msg);
+        die(msg);
+    }
+    return n;
+}
+
+// -m FILE [-m FILE ...] or -de n1 n2 ...: the last option, `arguments` what follows its name; the mmseq tables are left in `arguments`
+void parse_design_option(const string &a0, vector<string> &arguments, Options &opt)
+{
+    // -m FILE -m FILE ...: consecutive pairs are one polytomous run
+    size_t first_other = 0;
+    if (a0 == "-m")
+        for (first_other = arguments.empty() ? 0 : 1; first_other + 1 < arguments.size() && arguments[first_other] == "-m";) first_other += 2;
+    size_t n_m = a0 == "-m" ? 1 : 0;
+    bool de_too = a0 == "-de";
+    for (size_t i = 0; i < arguments.size(); i++) {
+        if (arguments[i] == "-m" && i + 1 < arguments.size()) n_m++;
+        if (arguments[i] == "-de") de_too = true;
+    }
+    if (de_too && n_m > 1) usage_error("Error: -de cannot be combined with more than one -m.");
+    if (opt.polyclass_mode) usage_error("Error: -polyclass takes mmdiff tables, not -de or -m.");
+    for (size_t i = first_other; i < arguments.size(); i++)
+        if (arguments[i].find("-") == 0) {
+            cerr << "Error: optional arguments must be specified before -de or -m." << endl << endl;
+            printUsage(cerr);
+            exit(1);
+        }
+    if (a0 == "-m") {
+        need(arguments, 1);
+        opt.matrices_files.push_back(arguments[0]);
+        arguments.erase(arguments.begin());
+        while (arguments.size() >= 2 && arguments[0] == "-m") {
+            opt.matrices_files.push_back(arguments[1]);
+            arguments.erase(arguments.begin(), arguments.begin() + 2);
+        }
+        if (opt.matrices_files.size() > MAXMODELS)
+            die("Error: this mmdiff handles at most " + to_string(MAXMODELS) + " alternative models (-m) in one run.");
+    } else {
+        int ss = 0;
+        cerr << "Number of samples in each group:";
+        while (ss < (int)arguments.size()) {
+            opt.simple_de.push_back(atoi(arguments[0].c_str()));
+            cerr << " " << opt.simple_de.back();
+            arguments.erase(arguments.begin());
+            if (opt.simple_de.back() < 1) die("\nError: each grouping must contain at least one sample");
+            ss += opt.simple_de.back();
+        }
+        cerr << endl;
+        if (ss != (int)arguments.size()) die("Error: total number of samples specified with -de must equal number of MMSEQ files");
+    }
+}
+
+Options parse_args(int argc, char **argv)
+{
+    Options opt;
+    Mcmc &mc = opt.mc;
     vector<string> arguments;
     for (int i = 1; i < argc; i++) arguments.push_back(string(argv[i]));
 
     while (true) {
         const string a0 = arguments.empty() ? string() : arguments[0];
+        auto flag = [&]() { arguments.erase(arguments.begin()); return true; };
         auto take = [&]() { arguments.erase(arguments.begin()); need(arguments, 1); string v = arguments[0]; arguments.erase(arguments.begin()); return v; };
         if (a0 == "-tracedir") {
             die("Error: -tracedir is not implemented in this version of mmdiff (MCMC traces are not written); use -traces DIR.");
         } else if (a0 == "-traces") {
-            traces = take();
-            if (traces.empty()) die("Error: -traces needs a directory.");
+            opt.traces = take();
+            if (opt.traces.empty()) die("Error: -traces needs a directory.");
         } else if (a0 == "-effects") {
-            effects = take();
-            if (effects.empty()) die("Error: -effects needs a file name.");
+            opt.effects = take();
+            if (opt.effects.empty()) die("Error: -effects needs a file name.");
         } else if (a0 == "-lrt") {
-            lrt_file = take();
-            if (lrt_file.empty()) die("Error: -lrt needs a file name.");
-            lrt_given = true;
+            opt.lrt_file = take();
+            if (opt.lrt_file.empty()) die("Error: -lrt needs a file name.");
+            opt.lrt_given = true;
         } else if (a0 == "-lrtonly") {
-            arguments.erase(arguments.begin());
-            lrt_only = true;
+            opt.lrt_only = flag();
         } else if (a0 == "-lrtperm") {
-            const string v = take();
-            char *end = NULL;
-            lrt_perms = strtol(v.c_str(), &end, 10);
-            if (v.empty() || *end != '\0' || lrt_perms < 1 || lrt_perms > MAXLRTPERMS)
-                usage_error("Error: -lrtperm takes an integer between 1 and " + to_string(MAXLRTPERMS) + ".");
-            lrtperm_given = true;
+            opt.lrt_perms = int_option(a0, take(), 1, MAXLRTPERMS, true);
+            opt.lrtperm_given = true;
         } else if (a0 == "-effects_every") {
-            const string v = take();
-            char *end = NULL;
-            effects_every = strtol(v.c_str(), &end, 10);
-            if (v.empty() || *end != '\0' || effects_every < 1 || effects_every > (1L << 30))
-                die("Error: -effects_every takes an integer between 1 and 1073741824.");
-            effects_every_given = true;
+            opt.effects_every = int_option(a0, take(), 1, 1L << 30);
+            opt.effects_every_given = true;
         } else if (a0 == "-effects_percentiles") {
-            effects_pct_text = take();
-            effects_pct_given = true;
+            opt.effects_pct_text = take();
+            opt.effects_pct_given = true;
         } else if (a0 == "-m" || a0 == "-de") {
             arguments.erase(arguments.begin());
-            // -m FILE -m FILE ...: consecutive pairs are one polytomous run
-            size_t first_other = 0;
-            if (a0 == "-m")
-                for (first_other = arguments.empty() ? 0 : 1; first_other + 1 < arguments.size() && arguments[first_other] == "-m";) first_other += 2;
-            size_t n_m = a0 == "-m" ? 1 : 0;
-            bool de_too = a0 == "-de";
-            for (size_t i = 0; i < arguments.size(); i++) {
-                if (arguments[i] == "-m" && i + 1 < arguments.size()) n_m++;
-                if (arguments[i] == "-de") de_too = true;
-            }
-            if (de_too && n_m > 1) usage_error("Error: -de cannot be combined with more than one -m.");
-            if (polyclass_mode) usage_error("Error: -polyclass takes mmdiff tables, not -de or -m.");
-            for (size_t i = first_other; i < arguments.size(); i++)
-                if (arguments[i].find("-") == 0) {
-                    cerr << "Error: optional arguments must be specified before -de or -m." << endl << endl;
-                    printUsage(cerr);
-                    exit(1);
-                }
-            if (a0 == "-m") {
-                need(arguments, 1);
-                matrices_file = arguments[0];
-                matrices_files.push_back(arguments[0]);
-                arguments.erase(arguments.begin());
-                while (arguments.size() >= 2 && arguments[0] == "-m") {
-                    matrices_files.push_back(arguments[1]);
-                    arguments.erase(arguments.begin(), arguments.begin() + 2);
-                }
-                if (matrices_files.size() > MAXMODELS)
-                    die("Error: this mmdiff handles at most " + to_string(MAXMODELS) + " alternative models (-m) in one run.");
-            } else {
-                cerr << "Number of samples in each group:";
-                while (ss < (int)arguments.size()) {
-                    simple_de.push_back(atoi(arguments[0].c_str()));
-                    cerr << " " << simple_de.back();
-                    arguments.erase(arguments.begin());
-                    if (simple_de.back() < 1) die("\nError: each grouping must contain at least one sample");
-                    ss += simple_de.back();
-                }
-                cerr << endl;
-                if (ss != (int)arguments.size()) die("Error: total number of samples specified with -de must equal number of MMSEQ files");
-            }
+            parse_design_option(a0, arguments, opt);
         } else if (a0 == "-useprops") {
-            arguments.erase(arguments.begin());
-            useprops = true;
+            opt.useprops = flag();
         } else if (a0 == "-p") {
-            p = strtod(take().c_str(), NULL);
-            if (!(p >= 0 && p <= 1)) die("Error: p must be between 0 and 1.");
+            mc.p = strtod(take().c_str(), NULL);
+            if (!(mc.p >= 0 && mc.p <= 1)) die("Error: p must be between 0 and 1.");
         } else if (a0 == "-s") {
-            s = strtod(take().c_str(), NULL);
-            if (!(s > 0) || !std::isfinite(s)) die("Error: s must be positive.");
+            mc.s = strtod(take().c_str(), NULL);
+            if (!(mc.s > 0) || !std::isfinite(mc.s)) die("Error: s must be positive.");
         } else if (a0 == "-d") {
-            d = strtod(take().c_str(), NULL);
-            if (!(d > 0) || !std::isfinite(d)) die("Error: d must be positive.");
+            mc.d = strtod(take().c_str(), NULL);
+            if (!(mc.d > 0) || !std::isfinite(mc.d)) die("Error: d must be positive.");
         } else if (a0 == "-pdash") {
-            pdash = strtod(take().c_str(), NULL);
-            if (!(pdash >= 0 && pdash <= 1)) die("Error: pdash must be between 0 and 1.");
+            mc.pdash = strtod(take().c_str(), NULL);
+            if (!(mc.pdash >= 0 && mc.pdash <= 1)) die("Error: pdash must be between 0 and 1.");
         } else if (a0 == "-fixalpha") {
-            arguments.erase(arguments.begin());
-            fixalpha = true;
+            mc.fixalpha = flag();
         } else if (a0 == "-l") {
             take();   // accepted for compatibility; the reference does not use it either
         } else if (a0 == "-burnin") {
-            burnin = atoi(take().c_str());
+            mc.burnin = atoi(take().c_str());
         } else if (a0 == "-iter") {
-            mcmciters = atoi(take().c_str());
+            mc.iters = atoi(take().c_str());
         } else if (a0 == "-seed") {
-            seed = atoi(take().c_str());
+            mc.seed = (uint64_t)(uint32_t)atoi(take().c_str());
         } else if (a0 == "-nonorm") {
-            arguments.erase(arguments.begin());
-            normalise = false;
+            opt.normalise = !flag();
         } else if (a0 == "-notune") {
-            arguments.erase(arguments.begin());
-            tune = false;
+            mc.tune = !flag();
         } else if (a0 == "-permute") {
-            arguments.erase(arguments.begin());
-            permute = true;
+            opt.permute = flag();
         } else if (a0 == "-uhfrac") {
-            customuhfrac = true;
-            uhfrac = atof(take().c_str());
+            opt.customuhfrac = true;
+            opt.uhfrac = atof(take().c_str());
         } else if (a0 == "-range") {
             arguments.erase(arguments.begin());
             need(arguments, 2);
-            range_start = atoi(arguments[0].c_str());
-            range_end = atoi(arguments[1].c_str());
+            opt.range_start = atoi(arguments[0].c_str());
+            opt.range_end = atoi(arguments[1].c_str());
             arguments.erase(arguments.begin(), arguments.begin() + 2);
         } else if (a0 == "-polyclass") {
-            arguments.erase(arguments.begin());
-            polyclass_mode = true;
+            opt.polyclass_mode = flag();
         } else if (a0 == "-prior") {
-            prior_text = take();
-            prior_given = true;
+            opt.prior_text = take();
+            opt.prior_given = true;
         } else if (a0 == "-polyout") {
-            polyout = take();
-            polyout_given = true;
+            opt.polyout = take();
+            opt.polyout_given = true;
         } else if (a0 == "-chains") {
-            const string v = take();
-            char *end = NULL;
-            const long n = strtol(v.c_str(), &end, 10);
-            if (v.empty() || *end != '\0' || n < 1 || n > MAXCHAINS) die("Error: -chains takes an integer between 1 and " + to_string(MAXCHAINS) + ".");
-            chains = (int)n;
-            chains_given = true;
+            opt.chains = (int)int_option(a0, take(), 1, MAXCHAINS);
+            opt.chains_given = true;
         } else if (a0 == "-chainout") {
-            chainout = take();
-            chainout_given = true;
+            opt.chainout = take();
+            opt.chainout_given = true;
         } else if (a0 == "-permutations") {
-            const string v = take();
-            char *end = NULL;
-            const long n = strtol(v.c_str(), &end, 10);
-            if (v.empty() || *end != '\0' || n < 1 || n > MAXPERMS) die("Error: -permutations takes an integer between 1 and " + to_string(MAXPERMS) + ".");
-            perms = (int)n;
-            perms_given = true;
+            opt.perms = (int)int_option(a0, take(), 1, MAXPERMS);
+            opt.perms_given = true;
         } else if (a0 == "-permout") {
-            permout = take();
-            permout_given = true;
+            opt.permout = take();
+            opt.permout_given = true;
         } else if (a0 == "-h" || a0 == "--help" || a0 == "-help") {
             cerr << "Bayesian model selection for RNA-seq expression estimates.\n";
             printUsage(cerr);
@@ -1441,179 +1261,439 @@ int main(int argc, char **argv)
             die("mmdiff-1.0.10-gfx950");
         } else {
             if (!a0.empty() && a0[0] == '-') usage_error("Error: unrecognised option " + a0 + ".");
-            else if (polyclass_mode && arguments.size() >= 2) break;
-            else if (polyclass_mode) usage_error("Error: -polyclass needs at least two mmdiff tables.");
+            else if (opt.polyclass_mode && arguments.size() >= 2) break;
+            else if (opt.polyclass_mode) usage_error("Error: -polyclass needs at least two mmdiff tables.");
             else if (arguments.size() <= 2) usage_error("Error: mandatory arguments missing.");
             else break;
         }
     }
+    opt.files = arguments;
+    return opt;
+}
 
-    const bool poly_run = matrices_files.size() > 1;
-    if ((prior_given || polyout_given) && !poly_run && !polyclass_mode)
+// the options that need or exclude each other; the percentiles of -effects
+void check_combinations(Options &opt)
+{
+    const bool poly_run = opt.poly_run(), polyclass_mode = opt.polyclass_mode, traces = !opt.traces.empty(), effects = !opt.effects.empty();
+    if ((opt.prior_given || opt.polyout_given) && !poly_run && !polyclass_mode)
         usage_error("Error: -prior and -polyout need more than one -m (or, -prior, -polyclass).");
-    if (polyout_given && !poly_run) usage_error("Error: -polyout needs more than one -m.");
-    if (chainout_given && !chains_given) usage_error("Error: -chainout needs -chains.");
-    if (chains_given && (poly_run || polyclass_mode))
+    if (opt.polyout_given && !poly_run) usage_error("Error: -polyout needs more than one -m.");
+    if (opt.chainout_given && !opt.chains_given) usage_error("Error: -chainout needs -chains.");
+    if (opt.chains_given && (poly_run || polyclass_mode))
         usage_error("Error: -chains cannot be combined with more than one -m or with -polyclass (chains of several alternatives are left for later).");
-    if (!traces.empty() && (chains_given || poly_run || polyclass_mode))
+    if (traces && (opt.chains_given || poly_run || polyclass_mode))
         usage_error("Error: -traces cannot be combined with -chains, more than one -m or -polyclass (traces of several chains or alternatives are left for later).");
-    if ((effects_every_given || effects_pct_given) && effects.empty())
+    if ((opt.effects_every_given || opt.effects_pct_given) && !effects)
         usage_error("Error: -effects_every and -effects_percentiles need -effects.");
-    if (!effects.empty() && !traces.empty())
+    if (effects && traces)
         usage_error("Error: -effects cannot be combined with -traces (the handle records rows for one of them).");
-    if (!effects.empty() && (chains_given || poly_run || polyclass_mode))
+    if (effects && (opt.chains_given || poly_run || polyclass_mode))
         usage_error("Error: -effects cannot be combined with -chains, more than one -m or -polyclass (effects of several chains or alternatives are left for later).");
-    if (permout_given && !perms_given) usage_error("Error: -permout needs -permutations.");
-    if (perms_given && (permute || chains > 1 || chainout_given || poly_run || polyclass_mode || !traces.empty() || !effects.empty()))
+    if (opt.permout_given && !opt.perms_given) usage_error("Error: -permout needs -permutations.");
+    if (opt.perms_given && (opt.permute || opt.chains > 1 || opt.chainout_given || poly_run || polyclass_mode || traces || effects))
         usage_error("Error: -permutations cannot be combined with -permute, -chains above 1 (or -chainout), more than one -m, -traces, -effects or -polyclass.");
-    if (lrt_only && !lrt_given) usage_error("Error: -lrtonly needs -lrt.");
-    if ((lrt_given || lrt_only) && (chains_given || poly_run || perms_given || polyclass_mode))
+    if (opt.lrt_only && !opt.lrt_given) usage_error("Error: -lrtonly needs -lrt.");
+    if ((opt.lrt_given || opt.lrt_only) && (opt.chains_given || poly_run || opt.perms_given || polyclass_mode))
         usage_error("Error: -lrt and -lrtonly cannot be combined with -chains, more than one -m, -permutations or -polyclass.");
-    if (lrtperm_given && !lrt_given) usage_error("Error: -lrtperm needs -lrt.");
-    if (lrtperm_given && permute) usage_error("Error: -lrtperm cannot be combined with -permute.");
-    vector<double> effects_pct;
-    if (!effects.empty()) effects_pct = parse_percentiles(effects_pct_text);
-    if (polyclass_mode) {
-        // host only: no device is looked for
-        const size_t J = arguments.size();
-        const vector<double> prior = parse_prior(prior_given, prior_text, J + 1);
-        vector<PolyTable> T(J);
-        for (size_t j = 0; j < J; ++j) {
-            ifstream ifs(arguments[j].c_str());
-            if (!ifs.good()) die("Error: couldn't open " + arguments[j]);
-            parse_poly_table(ifs, arguments[j], j == 0, T[j]);
-            if (j > 0) check_same_features(T[0], arguments[0], T[j], arguments[j]);
-        }
-        polyclass(T, prior, stdout);
-        return 0;
-    }
+    if (opt.lrtperm_given && !opt.lrt_given) usage_error("Error: -lrtperm needs -lrt.");
+    if (opt.lrtperm_given && opt.permute) usage_error("Error: -lrtperm cannot be combined with -permute.");
+    if (effects) opt.effects_pct = parse_percentiles(opt.effects_pct_text);
+}
 
-    if (burnin <= 0 || mcmciters <= 0) usage_error("Error: negative burnin and iter parameters.");
-    if (burnin % OUTLEN != 0 || mcmciters % OUTLEN != 0) usage_error("Error: burnin and iter parameters must be multiples of " + to_string(OUTLEN));
-    if (useprops) {
+// what a run on mmseq tables checks of its options before it reads them: the lengths, the rows of -effects, a design, the trace directory
+void check_run(Options &opt)
+{
+    const Mcmc &mc = opt.mc;
+    if (mc.burnin <= 0 || mc.iters <= 0) usage_error("Error: negative burnin and iter parameters.");
+    if (mc.burnin % OUTLEN != 0 || mc.iters % OUTLEN != 0) usage_error("Error: burnin and iter parameters must be multiples of " + to_string(OUTLEN));
+    if (opt.useprops) {
         cerr << "Using proportions, therefore disabling normalisation.\n";
-        normalise = false;
+        opt.normalise = false;
     }
-    uint32_t effects_rows = 0;
-    if (!effects.empty()) {
-        if (!effects_every_given) effects_every = max(1, mcmciters / 1024);
-        const long rows = ((long)mcmciters + effects_every - 1) / effects_every;
+    if (!opt.effects.empty()) {
+        if (!opt.effects_every_given) opt.effects_every = max(1, mc.iters / 1024);
+        const long rows = ((long)mc.iters + opt.effects_every - 1) / opt.effects_every;
         if (rows > MAXEFFECTROWS)
-            die("Error: -effects keeps at most " + to_string(MAXEFFECTROWS) + " rows: -iter " + to_string(mcmciters) + " with -effects_every "
-                + to_string(effects_every) + " needs " + to_string(rows) + ".");
-        effects_rows = (uint32_t)rows;
+            die("Error: -effects keeps at most " + to_string(MAXEFFECTROWS) + " rows: -iter " + to_string(mc.iters) + " with -effects_every "
+                + to_string(opt.effects_every) + " needs " + to_string(rows) + ".");
+        opt.effects_rows = (uint32_t)rows;
     }
-    if (matrices_file == "" && simple_de.size() == 0) die("Error: either -de or -m must be specified");
-    if (matrices_file == "" && simple_de.size() == 1) die("Error: -de requires at least two groupings");
-    if (!traces.empty()) {   // src/mmdiff.cpp:594-603
-        mkdir(traces.c_str(), 0755);
-        if (::access(traces.c_str(), F_OK | R_OK | W_OK | X_OK) == -1) die("Error: can't write to trace directory " + traces + ".");
+    if (opt.matrices_files.empty() && opt.simple_de.size() == 0) die("Error: either -de or -m must be specified");
+    if (opt.matrices_files.empty() && opt.simple_de.size() == 1) die("Error: -de requires at least two groupings");
+    if (!opt.traces.empty()) {   // src/mmdiff.cpp:594-603
+        mkdir(opt.traces.c_str(), 0755);
+        if (::access(opt.traces.c_str(), F_OK | R_OK | W_OK | X_OK) == -1) die("Error: can't write to trace directory " + opt.traces + ".");
     }
+}
 
-    vector<string> filenames(arguments.begin(), arguments.end());
-    const size_t S = filenames.size();
-    if (customuhfrac && (uhfrac > 1 || uhfrac < 1.0 / (double)S)) die("Error: uhfrac must be <= 1 and >= 1/N.");
-    if (!customuhfrac) uhfrac = max(0.2, (double)(S - S * S / 160) / (double)S);
-    if (normalise) cerr << "Min unique hits fraction for normalisation: " << uhfrac << endl;
+// ---- the stages of a run ------------------------------------------------------------------------------------------------------------
+// -polyclass: host only, no device is looked for
+int run_polyclass(const Options &opt)
+{
+    const vector<string> &tables = opt.files;
+    const size_t J = tables.size();
+    const vector<double> prior = parse_prior(opt.prior_given, opt.prior_text, J + 1);
+    vector<PolyTable> T(J);
+    for (size_t j = 0; j < J; ++j) {
+        ifstream ifs(tables[j].c_str());
+        if (!ifs.good()) die("Error: couldn't open " + tables[j]);
+        parse_poly_table(ifs, tables[j], j == 0, T[j]);
+        if (j > 0) check_same_features(T[0], tables[0], T[j], tables[j]);
+    }
+    polyclass(T, prior, stdout);
+    return 0;
+}
+
+// the mmseq tables, normalised and permuted as asked
+Inputs load_inputs(Options &opt)
+{
+    Inputs in;
+    in.filenames = opt.files;
+    const size_t S = in.filenames.size();
+    if (opt.customuhfrac && (opt.uhfrac > 1 || opt.uhfrac < 1.0 / (double)S)) die("Error: uhfrac must be <= 1 and >= 1/N.");
+    if (!opt.customuhfrac) opt.uhfrac = max(0.2, (double)(S - S * S / 160) / (double)S);
+    if (opt.normalise) cerr << "Min unique hits fraction for normalisation: " << opt.uhfrac << endl;
     if (S > 512) die("Error: this mmdiff handles at most 512 samples.");
-    const uint64_t useed = (uint64_t)(uint32_t)seed;
-
-    vector<string> features;
-    Mat y, e, uh;
-    parse_mmseq(filenames, features, y, e, uh, range_start, range_end, useprops);
-    const size_t F = features.size();
+    Mat uh;
+    parse_mmseq(in.filenames, in.features, in.y, in.e, uh, opt.range_start, opt.range_end, opt.useprops);
+    const size_t F = in.features.size();
     if (F == 0) die("Error: no features to analyse.");
-    if (normalise) apply_normalisation(filenames, y, uh, F, S, uhfrac);
-    if (permute) apply_permutation(y, e, F, S, useed);
+    if (opt.normalise) apply_normalisation(in.filenames, in.y, uh, F, S, opt.uhfrac);
+    if (opt.permute) apply_permutation(in.y, in.e, F, S, opt.mc.seed);
+    return in;
+}
 
+// -de n1 n2 ...: model 0 one mean and one variance class; model 1 a mean and a class per group (two groups: a contrast of +-0.5)
+Design de_design(const vector<int> &simple_de, size_t S)
+{
     Design D;
-    if (matrices_file == "") {
-        const size_t G = simple_de.size();
-        D.N = S; D.K = 1; D.L0 = 1; D.L1 = G > 2 ? G : 1; D.CC = 2;
-        D.M.assign(S, 0.0); D.P0.assign(S, 0.0); D.P1.assign(S * D.L1, 0.0); D.C.assign(S * 2, 0);
-        size_t k = 0;
-        for (size_t i = 0; i < G; i++)
-            for (int j = 0; j < simple_de[i]; j++) {
-                D.C[k * 2 + 1] = (int)i;
-                D.P0[k] = 1.0;
-                if (G > 2) D.P1[k * D.L1 + i] = 1.0;
-                else D.P1[k] = i == 0 ? .5 : -.5;
-                k++;
-            }
-    } else if (!poly_run) {
-        parse_matrices(matrices_file, D, S);
-    }
-    if (fixalpha) cerr << "Fixing alpha=0, so setting v_beta^2=25 instead of 4.\n";
-    bool Mnil = false, Pnil[2] = {false, false};
-    if (poly_run) return run_poly(matrices_files, prior_given, prior_text, polyout_given, polyout, features, filenames, y, e, p, d, s, pdash,
-                                  fixalpha, tune, burnin, mcmciters, useed);
-    validate_design(D, S, fixalpha, Mnil, Pnil);
-    if (chains > 1)
-        return run_chains(chains, chainout_given, chainout, D, Mnil, Pnil, features, filenames, y, e, p, d, s, pdash, fixalpha, tune, burnin,
-                          mcmciters, useed);
-    if (perms_given)
-        return run_perm(perms, permout_given, permout, D, Mnil, Pnil, features, filenames, y, e, p, d, s, pdash, fixalpha, tune, burnin, mcmciters,
-                        useed);
-    // -chains 1 -chainout BASE: the plain run, its table to BASE.chain0.mmdiff as well
-    struct Closer { FILE *f = nullptr; ~Closer() { if (f) fclose(f); } } chain0;
-    const string chain0_name = chainout + ".chain0.mmdiff";
-    if (chainout_given && !(chain0.f = fopen(chain0_name.c_str(), "w"))) die("Error: couldn't create " + chain0_name);
-    Closer lrt_out;
-    if (lrt_given && !(lrt_out.f = fopen(lrt_file.c_str(), "w"))) die("Error: couldn't create " + lrt_file);
+    const size_t G = simple_de.size();
+    D.N = S; D.K = 1; D.L0 = 1; D.L1 = G > 2 ? G : 1; D.CC = 2;
+    D.M.assign(S, 0.0); D.P0.assign(S, 0.0); D.P1.assign(S * D.L1, 0.0); D.C.assign(S * 2, 0);
+    size_t k = 0;
+    for (size_t i = 0; i < G; i++)
+        for (int j = 0; j < simple_de[i]; j++) {
+            D.C[k * 2 + 1] = (int)i;
+            D.P0[k] = 1.0;
+            if (G > 2) D.P1[k * D.L1 + i] = 1.0;
+            else D.P1[k] = i == 0 ? .5 : -.5;
+            k++;
+        }
+    return D;
+}
 
-    // every input is checked: now the device
+// The files of -polyout, -chainout, -permout and -lrt: created before the device is looked for, closed when the run ends.
+struct OutFiles {
+    vector<FILE *> f;
+    vector<string> names;
+    explicit OutFiles(size_t n) : f(n, nullptr), names(n) {}
+    ~OutFiles() { for (FILE *x : f) if (x) fclose(x); }
+    void open(size_t i, const string &name)
+    {
+        names[i] = name;
+        if (!(f[i] = fopen(name.c_str(), "w"))) die("Error: couldn't create " + name);
+    }
+    void flush(size_t i) { if (f[i] && fflush(f[i]) != 0) die("Error: couldn't write " + names[i]); }
+};
+
+template <typename H> using Owner = unique_ptr<H, void (*)(H *)>;   // a handle of the library and the entry that destroys it
+
+void require_device()
+{
     int ndev = 0;
     if (mmg_device_count(&ndev) != 0 || ndev < 1) die("Error: no HIP device available: mmdiff has no CPU fallback");
-    if (lrt_given) {
-        // the same y, e and design the chain gets
+}
+
+// The entries that the handles of several replicas (alternatives, chains, the data and its permutations) share apart from the handle
+// type, and their family in the entries' names.
+template <typename H> struct ReplicaApi {
+    const char *family;
+    int (*burnin)(H *, uint32_t);
+    int (*tune_batch)(H *, uint32_t *, int32_t *);
+    int (*info)(H *, uint32_t, int32_t *, uint32_t *, uint32_t *, int32_t *);
+    int (*sample)(H *, uint32_t);
+    void (*destroy)(H *);
+};
+const ReplicaApi<mmg_diff_poly> POLY = {"poly", mmg_diff_poly_burnin, mmg_diff_poly_tune_batch, mmg_diff_poly_info, mmg_diff_poly_sample,
+                                        mmg_diff_poly_destroy};
+const ReplicaApi<mmg_diff_chains> CHAINS = {"chains", mmg_diff_chains_burnin, mmg_diff_chains_tune_batch, mmg_diff_chains_info,
+                                            mmg_diff_chains_sample, mmg_diff_chains_destroy};
+const ReplicaApi<mmg_diff_perm> PERM = {"perm", mmg_diff_perm_burnin, mmg_diff_perm_tune_batch, mmg_diff_perm_info, mmg_diff_perm_sample,
+                                        mmg_diff_perm_destroy};
+
+// The MCMC of R replicas on the handle create() gives: the device check, the burn-in, tuning batches until every replica has ended (each
+// stops at the first batch after which none of its features is untuned, or with the others at MAXBATCHES), the batch count of each, the
+// sampling.  what: the replicas in the burn-in line; label(r): replica r in its own line.
+template <typename H, typename Create, typename Label>
+Owner<H> run_replicas(const ReplicaApi<H> &api, Create create, size_t R, const Mcmc &mc, const string &what, Label label)
+{
+    auto check = [&](int rc, const char *entry) {
+        if (rc != 0) die(string("Error: mmg_diff_") + api.family + "_" + entry + ": " + mmg_last_error());
+    };
+    // every input is checked: now the device
+    require_device();
+    Owner<H> h(create(), api.destroy);
+    cerr << "BURNIN (" << mc.burnin << " iterations, " << what << ")...";
+    check(api.burnin(h.get(), (uint32_t)mc.burnin), "burnin");
+    cerr << "\nSetting pseudopriors...done.\n";
+    if (mc.tune) {
+        vector<uint32_t> untuned(R);
+        vector<int32_t> ended(R);
+        int numbatches = 0;
+        bool all_ended = false;
+        while (!all_ended && numbatches != MAXBATCHES) {
+            check(api.tune_batch(h.get(), untuned.data(), ended.data()), "tune_batch");
+            numbatches++;
+            all_ended = true;
+            uint64_t left = 0;
+            for (size_t r = 0; r < R; ++r) { all_ended = all_ended && ended[r]; left += untuned[r]; }
+            if (numbatches % 64 == 0) cerr << "TUNING BATCH " << numbatches << " (" << left << " left)\r";
+        }
+    }
+    for (size_t r = 0; r < R; ++r) {
+        uint32_t nb = 0;
+        check(api.info(h.get(), (uint32_t)r, NULL, NULL, &nb, NULL), "info");
+        cerr << label(r) << ": sampling after " << nb << " tuning batches\n";
+    }
+    cerr << "TRACE (" << mc.iters << " iterations)";
+    check(api.sample(h.get(), (uint32_t)mc.iters), "sample");
+    return h;
+}
+
+// repeated -m: J alternatives against one model 0 on one device handle.  Table j (what `mmdiff <same options> -m alt_j <same tables>`
+// prints) goes to BASE.model<j>.mmdiff with -polyout; stdout gets polyclass of the tables, from the Bayes factors as the tables print
+// them (%g text parsed back), so that `mmdiff -polyclass` on the written tables reproduces it byte for byte.
+int run_poly(const Options &opt, const Inputs &in)
+{
+    const Mcmc &mc = opt.mc;
+    const vector<string> &mats = opt.matrices_files;
+    const size_t J = mats.size(), S = in.filenames.size(), F = in.features.size();
+    vector<Model> models(J);
+    const Design &D0 = models[0].D;
+    for (size_t j = 0; j < J; ++j) {
+        Design &D = models[j].D;
+        cerr << "Alternative " << j + 1 << " (" << mats[j] << "):\n";
+        parse_matrices(mats[j], D, S);
+        validate_design(D, S, mc.fixalpha, models[j].Mnil, models[j].Pnil);
+        bool same = D.K == D0.K && D.L0 == D0.L0 && D.M == D0.M && D.P0 == D0.P0;
+        for (size_t i = 0; same && i < S; ++i) same = D.C[i * 2] == D0.C[i * 2];
+        if (!same) die("Error: model 0 differs between " + mats[0] + " and " + mats[j]);
+    }
+    const vector<double> prior = parse_prior(opt.prior_given, opt.prior_text, J + 1);
+    OutFiles files(J);
+    if (opt.polyout_given)
+        for (size_t j = 0; j < J; ++j) files.open(j, opt.polyout + ".model" + to_string(j + 1) + ".mmdiff");
+
+    vector<uint32_t> L1(J);
+    Mat P1;
+    vector<int> C0(S), C1(J * S);
+    for (size_t i = 0; i < S; ++i) C0[i] = D0.C[i * 2];
+    for (size_t j = 0; j < J; ++j) {
+        const Design &D = models[j].D;
+        L1[j] = (uint32_t)D.L1;
+        P1.insert(P1.end(), D.P1.begin(), D.P1.end());
+        for (size_t i = 0; i < S; ++i) C1[j * S + i] = D.C[i * 2 + 1];
+    }
+    auto create = [&] {
+        mmg_diff_poly *h = nullptr;
+        MMG_CHECK(mmg_diff_poly_create(0, (uint32_t)F, (uint32_t)S, in.y.data(), in.e.data(), (uint32_t)D0.K, D0.M.data(), (uint32_t)D0.L0,
+                                       D0.P0.data(), C0.data(), (uint32_t)J, L1.data(), P1.data(), C1.data(), mc.d, mc.s, mc.pdash,
+                                       mc.fixalpha ? 1 : 0, mc.seed, &h));
+        return h;
+    };
+    Owner<mmg_diff_poly> h = run_replicas(POLY, create, J, mc, to_string(J) + " alternatives", [](size_t j) { return "model " + to_string(j + 1); });
+    cerr << "\nDONE MCMC\n";
+    vector<PolyTable> T(J);
+    for (size_t j = 0; j < J; ++j) {
+        DiffResults r(F, models[j].D);
+        MMG_CHECK(mmg_diff_poly_get_results(h.get(), (uint32_t)j, r.gm.data(), r.logitp.data(), r.alpha.data(), r.beta.data(), r.eta.data()));
+        string text;
+        write_table(files.f[j], &text, in, models[j], mc, r);
+        files.flush(j);
+        istringstream table(text);
+        parse_poly_table(table, "the table of alternative " + to_string(j + 1), j == 0, T[j]);
+    }
+    polyclass(T, prior, stdout);
+    return 0;
+}
+
+// -chains C, C >= 2: C chains of one comparison on one device handle, chain c keyed (seed, c).  Table c (what a single run prints for
+// that chain) goes to BASE.chain<c>.mmdiff with -chainout; stdout gets the pooled table.
+int run_chains(const Options &opt, const Inputs &in, const Model &model)
+{
+    const Mcmc &mc = opt.mc;
+    const Design &D = model.D;
+    const size_t C = (size_t)opt.chains, S = in.filenames.size(), F = in.features.size();
+    OutFiles files(C);
+    if (opt.chainout_given)
+        for (size_t c = 0; c < C; ++c) files.open(c, opt.chainout + ".chain" + to_string(c) + ".mmdiff");
+    auto create = [&] {
+        mmg_diff_chains *h = nullptr;
+        MMG_CHECK(mmg_diff_chains_create(0, (uint32_t)F, (uint32_t)S, in.y.data(), in.e.data(), (uint32_t)D.K, D.M.data(), (uint32_t)D.L0,
+                                         D.P0.data(), (uint32_t)D.L1, D.P1.data(), D.C.data(), mc.d, mc.s, mc.pdash, mc.fixalpha ? 1 : 0, mc.seed,
+                                         (uint32_t)C, (uint32_t)mc.iters, &h));
+        return h;
+    };
+    Owner<mmg_diff_chains> h = run_replicas(CHAINS, create, C, mc, to_string(C) + " chains", [](size_t c) { return "chain " + to_string(c); });
+    MMG_CHECK(mmg_diff_chains_pool(h.get()));
+    cerr << "\nDONE MCMC\n";
+    DiffResults r(F, D);
+    TableExtras extras;
+    extras.warn_stuck = false;
+    for (size_t c = 0; c < C && opt.chainout_given; ++c) {
+        MMG_CHECK(mmg_diff_chains_get_results(h.get(), (uint32_t)c, r.gm.data(), r.logitp.data(), r.alpha.data(), r.beta.data(), r.eta.data()));
+        write_table(files.f[c], nullptr, in, model, mc, r, extras);
+        files.flush(c);
+    }
+    // the pooled table: chain 0's gamma mean and logit p' are not printed (the Bayes factor is exp(log_bf)), the means are the pooled ones
+    PooledCols pool(F);
+    MMG_CHECK(mmg_diff_chains_get_results(h.get(), 0, r.gm.data(), r.logitp.data(), NULL, NULL, NULL));
+    MMG_CHECK(mmg_diff_chains_get_pooled(h.get(), pool.log_bf.data(), pool.log_bf_sd.data(), pool.log_bf_mcse.data(), pool.chains_mixed.data(),
+                                         r.alpha.data(), r.beta.data(), r.eta.data()));
+    for (size_t f = 0; f < F; ++f)
+        if (pool.chains_mixed[f] < (uint32_t)C)
+            cerr << "Warning: gamma mixed in " << pool.chains_mixed[f] << " of " << C << " chains for feature " << f << endl;
+    extras.pool = &pool;
+    write_table(stdout, nullptr, in, model, mc, r, extras);
+    return 0;
+}
+
+// -permutations B: the data and B shuffled copies of it on one device handle (DESIGN.md section 10.4).  stdout gets the plain run's
+// table with perm_ge and q_value appended; the table of shuffled copy b (what -permute prints with the seed seed ^ (b << 32)) goes to
+// BASE.perm<b>.mmdiff with -permout.
+int run_perm(const Options &opt, const Inputs &in, const Model &model)
+{
+    const Mcmc &mc = opt.mc;
+    const Design &D = model.D;
+    const size_t B = (size_t)opt.perms, R = B + 1, S = in.filenames.size(), F = in.features.size();
+    OutFiles files(R);
+    if (opt.permout_given)
+        for (size_t b = 1; b < R; ++b) files.open(b, opt.permout + ".perm" + to_string(b) + ".mmdiff");
+    auto create = [&] {
+        mmg_diff_perm *h = nullptr;
+        MMG_CHECK(mmg_diff_perm_create(0, (uint32_t)F, (uint32_t)S, in.y.data(), in.e.data(), (uint32_t)D.K, D.M.data(), (uint32_t)D.L0,
+                                       D.P0.data(), (uint32_t)D.L1, D.P1.data(), D.C.data(), mc.d, mc.s, mc.pdash, mc.fixalpha ? 1 : 0, mc.seed,
+                                       (uint32_t)B, &h));
+        return h;
+    };
+    Owner<mmg_diff_perm> h = run_replicas(PERM, create, R, mc, "the data and " + to_string(B) + " permutations",
+                                          [](size_t b) { return "replica " + to_string(b); });
+    MMG_CHECK(mmg_diff_perm_qvalues(h.get()));
+    cerr << "\nDONE MCMC\n";
+    DiffResults r(F, D);
+    TableExtras extras;
+    extras.warn_stuck = false;
+    Inputs shuffled = in;
+    for (size_t b = 1; b < R && opt.permout_given; ++b) {
+        // the table's mu_ / sd_ columns: the shuffle the device applied to replica b, on the host
+        shuffled.y = in.y;
+        shuffled.e = in.e;
+        apply_permutation(shuffled.y, shuffled.e, F, S, mc.seed ^ ((uint64_t)b << 32), true);
+        MMG_CHECK(mmg_diff_perm_get_results(h.get(), (uint32_t)b, r.gm.data(), r.logitp.data(), r.alpha.data(), r.beta.data(), r.eta.data()));
+        write_table(files.f[b], nullptr, shuffled, model, mc, r, extras);
+        files.flush(b);
+    }
+    PermCols cols(F);
+    MMG_CHECK(mmg_diff_perm_get_results(h.get(), 0, r.gm.data(), r.logitp.data(), r.alpha.data(), r.beta.data(), r.eta.data()));
+    MMG_CHECK(mmg_diff_perm_get_qvalues(h.get(), NULL, cols.null_ge.data(), cols.q.data()));
+    extras.warn_stuck = true;
+    extras.perm = &cols;
+    write_table(stdout, nullptr, in, model, mc, r, extras);
+    return 0;
+}
+
+// -lrt FILE: the likelihood-ratio test of the y, e and design the chain gets, with -lrtperm its permutation null; the table to `out`
+void run_lrt(const Options &opt, const Inputs &in, const Model &model, FILE *out)
+{
+    const Design &D = model.D;
+    const size_t S = in.filenames.size(), F = in.features.size();
+    const int fixalpha = opt.mc.fixalpha ? 1 : 0;
+    if (!opt.lrtperm_given) {
         mmg_diff_lrt *lh = nullptr;
+        MMG_CHECK(mmg_diff_lrt_create(0, (uint32_t)F, (uint32_t)S, in.y.data(), in.e.data(), (uint32_t)D.K, D.M.data(), (uint32_t)D.L0, D.P0.data(),
+                                      (uint32_t)D.L1, D.P1.data(), D.C.data(), fixalpha, 0, &lh));
+        const Owner<mmg_diff_lrt> owner(lh, mmg_diff_lrt_destroy);
+        write_lrt(out, opt.lrt_file, in.features, D, opt.mc.fixalpha, lh);
+    } else {
+        // copy b: the data of BASE.perm<b>.mmdiff of this command line with -permutations (the seed run_perm hands on)
         mmg_diff_lrt_perm *ph = nullptr;
-        if (lrtperm_given) {
-            // copy b: the data of BASE.perm<b>.mmdiff of this command line with -permutations (the seed run_perm hands on)
-            MMG_CHECK(mmg_diff_lrt_perm_create(0, (uint32_t)F, (uint32_t)S, y.data(), e.data(), (uint32_t)D.K, D.M.data(), (uint32_t)D.L0,
-                                               D.P0.data(), (uint32_t)D.L1, D.P1.data(), D.C.data(), fixalpha ? 1 : 0, 0, (uint32_t)lrt_perms, useed,
-                                               0, &ph));
-            lh = mmg_diff_lrt_perm_observed(ph);
-        } else {
-            MMG_CHECK(mmg_diff_lrt_create(0, (uint32_t)F, (uint32_t)S, y.data(), e.data(), (uint32_t)D.K, D.M.data(), (uint32_t)D.L0, D.P0.data(),
-                                          (uint32_t)D.L1, D.P1.data(), D.C.data(), fixalpha ? 1 : 0, 0, &lh));
-        }
-        write_lrt(lrt_out.f, lrt_file, features, D, fixalpha, lh, ph);
-        if (ph) {
-            vector<uint8_t> st((size_t)lrt_perms * F);
-            MMG_CHECK(mmg_diff_lrt_perm_get_null(ph, 0, (uint32_t)lrt_perms, NULL, st.data()));
-            uint64_t bits[3] = {0, 0, 0};
-            for (uint8_t v : st)
-                for (int k = 0; k < 3; ++k) bits[k] += ((v >> k) & 1) + ((v >> (4 + k)) & 1);
-            cerr << "Null of the likelihood-ratio test: " << 2 * st.size() << " fits on " << lrt_perms << " shuffled copies; status bit 1 (cap) on "
-                 << bits[0] << ", bit 2 (singular) on " << bits[1] << ", bit 4 (boundary) on " << bits[2] << "\n";
-            mmg_diff_lrt_perm_destroy(ph);
-        } else {
-            mmg_diff_lrt_destroy(lh);
-        }
-        cerr << "Wrote the likelihood-ratio tests of " << F << " features to " << lrt_file << "\n";
-        if (lrt_only) return 0;
+        MMG_CHECK(mmg_diff_lrt_perm_create(0, (uint32_t)F, (uint32_t)S, in.y.data(), in.e.data(), (uint32_t)D.K, D.M.data(), (uint32_t)D.L0,
+                                           D.P0.data(), (uint32_t)D.L1, D.P1.data(), D.C.data(), fixalpha, 0, (uint32_t)opt.lrt_perms, opt.mc.seed,
+                                           0, &ph));
+        const Owner<mmg_diff_lrt_perm> owner(ph, mmg_diff_lrt_perm_destroy);
+        write_lrt(out, opt.lrt_file, in.features, D, opt.mc.fixalpha, mmg_diff_lrt_perm_observed(ph), ph);
+        vector<uint8_t> st((size_t)opt.lrt_perms * F);
+        MMG_CHECK(mmg_diff_lrt_perm_get_null(ph, 0, (uint32_t)opt.lrt_perms, NULL, st.data()));
+        uint64_t bits[3] = {0, 0, 0};
+        for (uint8_t v : st)
+            for (int k = 0; k < 3; ++k) bits[k] += ((v >> k) & 1) + ((v >> (4 + k)) & 1);
+        cerr << "Null of the likelihood-ratio test: " << 2 * st.size() << " fits on " << opt.lrt_perms << " shuffled copies; status bit 1 (cap) on "
+             << bits[0] << ", bit 2 (singular) on " << bits[1] << ", bit 4 (boundary) on " << bits[2] << "\n";
+    }
+    cerr << "Wrote the likelihood-ratio tests of " << F << " features to " << opt.lrt_file << "\n";
+}
+
+// the names of the traced parameters in row order; gamma, the last one, only if asked for
+vector<string> traced_names(mmg_diff *h, bool with_gamma)
+{
+    uint32_t np = 0;
+    MMG_CHECK(mmg_diff_trace_layout(h, &np, NULL));
+    vector<string> names(with_gamma ? np : np - 1);
+    for (uint32_t i = 0; i < names.size(); ++i) {
+        char name[32];
+        MMG_CHECK(mmg_diff_trace_name(h, i, name, sizeof name));
+        names[i] = name;
+    }
+    return names;
+}
+
+// -effects FILE, after sampling: the summaries of the rows the handle kept
+void write_run_effects(mmg_diff *h, const Options &opt, const Inputs &in, const Model &model)
+{
+    const size_t F = in.features.size();
+    Effects fx;
+    fx.names = traced_names(h, false);   // gamma has no effects of its own
+    const size_t Q = fx.names.size(), np = opt.effects_pct.size();
+    mmg_effects *e = nullptr;
+    MMG_CHECK(mmg_diff_effects_summarize(h, (uint32_t)np, opt.effects_pct.data(), &e));
+    const Owner<mmg_effects> owner(e, mmg_effects_destroy);
+    fx.n.resize(2 * F); fx.n_gt.resize(Q * F);
+    fx.mean.resize(Q * F); fx.sd.resize(Q * F); fx.q.resize(Q * np * F);
+    MMG_CHECK(mmg_effects_get(e, fx.n.data(), fx.mean.data(), fx.sd.data(), fx.n_gt.data(), fx.q.data()));
+    write_effects(opt.effects, in.features, opt.effects_pct, opt.mc.fixalpha, model, fx);
+    cerr << "Wrote the effects of " << opt.effects_rows << " rows to " << opt.effects << "\n";
+}
+
+// One chain of one comparison, and what only it offers: -lrt ahead of it (or, with -lrtonly, alone), -traces, -effects, and with
+// -chains 1 -chainout BASE its table to BASE.chain0.mmdiff as well.
+int run_plain(const Options &opt, const Inputs &in, const Model &model)
+{
+    const Mcmc &mc = opt.mc;
+    const Design &D = model.D;
+    const size_t S = in.filenames.size(), F = in.features.size();
+    OutFiles chain0(1), lrt_out(1);
+    if (opt.chainout_given) chain0.open(0, opt.chainout + ".chain0.mmdiff");
+    if (opt.lrt_given) lrt_out.open(0, opt.lrt_file);
+
+    // every input is checked: now the device
+    require_device();
+    if (opt.lrt_given) {
+        run_lrt(opt, in, model, lrt_out.f[0]);
+        if (opt.lrt_only) return 0;
     }
     mmg_diff *h = nullptr;
-    MMG_CHECK(mmg_diff_create(0, (uint32_t)F, (uint32_t)S, y.data(), e.data(), (uint32_t)D.K, D.M.data(), (uint32_t)D.L0, D.P0.data(),
-                              (uint32_t)D.L1, D.P1.data(), D.C.data(), d, s, pdash, fixalpha ? 1 : 0, useed, &h));
+    MMG_CHECK(mmg_diff_create(0, (uint32_t)F, (uint32_t)S, in.y.data(), in.e.data(), (uint32_t)D.K, D.M.data(), (uint32_t)D.L0, D.P0.data(),
+                              (uint32_t)D.L1, D.P1.data(), D.C.data(), mc.d, mc.s, mc.pdash, mc.fixalpha ? 1 : 0, mc.seed, &h));
+    Owner<mmg_diff> owner(h, mmg_diff_destroy);
     unique_ptr<TraceWriter> tw;
-    if (!traces.empty()) {
-        uint32_t np = 0;
-        MMG_CHECK(mmg_diff_trace_layout(h, &np, NULL));
-        vector<string> names(np);
-        for (uint32_t i = 0; i < np; ++i) {
-            char name[32];
-            MMG_CHECK(mmg_diff_trace_name(h, i, name, sizeof name));
-            names[i] = name;
-        }
-        tw.reset(new TraceWriter(traces, names, F));
-        // a line per burnin / OUTLEN burn-in and per mcmciters / OUTLEN sampling iterations (src/mmdiff.cpp:733-734, 837)
-        MMG_CHECK(mmg_diff_trace_open(h, (uint32_t)(burnin / OUTLEN), (uint32_t)(mcmciters / OUTLEN), TraceWriter::sink, tw.get()));
+    if (!opt.traces.empty()) {
+        tw.reset(new TraceWriter(opt.traces, traced_names(h, true), F));
+        // a line per burnin / OUTLEN burn-in and per iters / OUTLEN sampling iterations (src/mmdiff.cpp:733-734, 837)
+        MMG_CHECK(mmg_diff_trace_open(h, (uint32_t)(mc.burnin / OUTLEN), (uint32_t)(mc.iters / OUTLEN), TraceWriter::sink, tw.get()));
     }
-    if (!effects.empty()) MMG_CHECK(mmg_diff_effects_open(h, (uint32_t)effects_every, effects_rows));
-    cerr << "BURNIN (" << burnin << " iterations)...";
-    MMG_CHECK(mmg_diff_burnin(h, (uint32_t)burnin));
+    if (!opt.effects.empty()) MMG_CHECK(mmg_diff_effects_open(h, (uint32_t)opt.effects_every, opt.effects_rows));
+    cerr << "BURNIN (" << mc.burnin << " iterations)...";
+    MMG_CHECK(mmg_diff_burnin(h, (uint32_t)mc.burnin));
     cerr << "\nSetting pseudopriors...done.\n";
     vector<double> mean_lo, tune_logitp;
     if (tw) {
@@ -1628,7 +1708,7 @@ int main(int argc, char **argv)
         tune_logitp.resize(F);
     }
     int numbatches = 0;
-    if (tune) {
+    if (mc.tune) {
         uint32_t untuned = 0;
         MMG_CHECK(mmg_diff_tune_batch(h, &untuned));
         numbatches = 1;
@@ -1642,37 +1722,42 @@ int main(int argc, char **argv)
             if (numbatches % 64 == 0) cerr << "TUNING BATCH " << numbatches << " (" << untuned << " left)\r";
         }
     }
-    cerr << "TRACE (" << mcmciters << " iterations, sampling after " << numbatches << " tuning batches)";
-    MMG_CHECK(mmg_diff_sample(h, (uint32_t)mcmciters));
+    cerr << "TRACE (" << mc.iters << " iterations, sampling after " << numbatches << " tuning batches)";
+    MMG_CHECK(mmg_diff_sample(h, (uint32_t)mc.iters));
     cerr << "\nDONE MCMC\n";
     DiffResults r(F, D);
     MMG_CHECK(mmg_diff_get_results(h, r.gm.data(), r.logitp.data(), r.alpha.data(), r.beta.data(), r.eta.data()));
-    if (!effects.empty()) {
-        uint32_t P = 0;
-        MMG_CHECK(mmg_diff_trace_layout(h, &P, NULL));
-        vector<string> names(P - 1);   // gamma, the last one, has no effects of its own
-        for (uint32_t i = 0; i + 1 < P; ++i) {
-            char name[32];
-            MMG_CHECK(mmg_diff_trace_name(h, i, name, sizeof name));
-            names[i] = name;
-        }
-        const size_t Q = P - 1, np = effects_pct.size();
-        mmg_effects *fx = nullptr;
-        MMG_CHECK(mmg_diff_effects_summarize(h, (uint32_t)np, effects_pct.data(), &fx));
-        vector<uint32_t> n(2 * F), n_gt(Q * F);
-        vector<double> mean(Q * F), sd(Q * F), q(Q * np * F);
-        MMG_CHECK(mmg_effects_get(fx, n.data(), mean.data(), sd.data(), n_gt.data(), q.data()));
-        mmg_effects_destroy(fx);
-        write_effects(effects, features, names, effects_pct, fixalpha, Mnil, Pnil, n, mean, sd, n_gt, q);
-        cerr << "Wrote the effects of " << effects_rows << " rows to " << effects << "\n";
-    }
-    mmg_diff_destroy(h);
+    if (!opt.effects.empty()) write_run_effects(h, opt, in, model);
+    owner.reset();
     if (tw) {
-        if (!tw->finish()) die("Error: couldn't write the trace files in " + traces);
-        cerr << "Wrote " << tw->bytes << " bytes of traces to " << traces << "\n";
+        if (!tw->finish()) die("Error: couldn't write the trace files in " + opt.traces);
+        cerr << "Wrote " << tw->bytes << " bytes of traces to " << opt.traces << "\n";
     }
     string text;
-    write_table(stdout, chain0.f ? &text : nullptr, features, filenames, D, fixalpha, Mnil, Pnil, p, y, e, r);
-    if (chain0.f && (fputs(text.c_str(), chain0.f) < 0 || fflush(chain0.f) != 0)) die("Error: couldn't write " + chain0_name);
+    write_table(stdout, chain0.f[0] ? &text : nullptr, in, model, mc, r);
+    if (chain0.f[0] && fputs(text.c_str(), chain0.f[0]) < 0) die("Error: couldn't write " + chain0.names[0]);
+    chain0.flush(0);
     return 0;
+}
+
+} // namespace
+
+int main(int argc, char **argv)
+{
+    Options opt = parse_args(argc, argv);
+    check_combinations(opt);
+    if (opt.polyclass_mode) return run_polyclass(opt);
+    check_run(opt);
+    const Inputs in = load_inputs(opt);
+    const size_t S = in.filenames.size();
+
+    Model model;
+    if (opt.matrices_files.empty()) model.D = de_design(opt.simple_de, S);
+    else if (!opt.poly_run()) parse_matrices(opt.matrices_files[0], model.D, S);
+    if (opt.mc.fixalpha) cerr << "Fixing alpha=0, so setting v_beta^2=25 instead of 4.\n";
+    if (opt.poly_run()) return run_poly(opt, in);
+    validate_design(model.D, S, opt.mc.fixalpha, model.Mnil, model.Pnil);
+    if (opt.chains > 1) return run_chains(opt, in, model);
+    if (opt.perms_given) return run_perm(opt, in, model);
+    return run_plain(opt, in, model);
 }

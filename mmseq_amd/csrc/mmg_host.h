@@ -317,6 +317,20 @@ int qvalues_on_device(hipStream_t st, uint32_t F, const double *d_obs, uint64_t 
 // df_classes: the classes of one model, C[i * stride]: labels 0 .. *nc - 1, every one of them used (MMG_ERR_ARG otherwise).
 bool df_nil(const double *X, uint32_t N, uint32_t cols);
 int df_classes(const int32_t *C, uint32_t stride, uint32_t N, int *nc);
+// The argument checks the create entries of mmg_diff_*, mmg_diff_poly / chains / perm_* and mmg_diff_lrt* share, each MMG_ERR_ARG with
+// the entries' message; an entry calls them in the order of its documented checks, its own counts in between.  df_check_shape: F, N and
+// the columns of M; df_check_cols: the columns of P0 and of J matrices P1; df_check_finite: y, e, M, P0 and P1 (N x L1 values);
+// df_check_classes: both models of a class table [N][2].
+int df_check_shape(uint32_t F, uint32_t N, uint32_t K);
+int df_check_cols(uint32_t L0, uint32_t J, const uint32_t *L1);
+int df_check_prior(double d, double s, double pdash);
+int df_check_finite(uint32_t F, uint32_t N, const double *y, const double *e, uint32_t K, const double *M, uint32_t L0, const double *P0,
+                    uint64_t L1, const double *P1);
+int df_check_classes(const int32_t *C, uint32_t N, int nc[2]);
+// y and e^2 transposed to [N][F] (the lanes of a wave read adjacent words), copied to d_y / d_esq in stream order.  `staged` holds the
+// sources of the asynchronous copies: it lives until the caller has waited for the stream.
+struct DiffStaged { std::vector<double> ty, te; };
+int df_upload_transposed(hipStream_t st, uint32_t F, uint32_t N, const double *y, const double *e, double *d_y, double *d_esq, DiffStaged &staged);
 
 int require_device(int device);
 void weighted_chunks(const std::vector<uint64_t> &cum, uint64_t grid, std::vector<uint64_t> &chunk);

@@ -21,26 +21,33 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _design(obj, y, e, M, P0, P1, classes):
+    """The arguments every two-model class takes, as the contiguous arrays of the create entries: (y, e, M, [P0, P1], classes) with
+    y, e (F, N), M (N, K), P0 (N, L0), P1 (N, L1), classes (N, 2); sets obj.F, N, K and L = (L0, L1)."""
+    y = np.ascontiguousarray(y, np.float64)
+    e = np.ascontiguousarray(e, np.float64)
+    M = np.ascontiguousarray(M, np.float64)
+    P = [np.ascontiguousarray(P0, np.float64), np.ascontiguousarray(P1, np.float64)]
+    Cl = np.ascontiguousarray(classes, np.int32)
+    F, N = y.shape
+    if e.shape != (F, N) or M.shape[0] != N or P[0].shape[0] != N or P[1].shape[0] != N or Cl.shape != (N, 2):
+        raise ValueError("inconsistent shapes")
+    obj.F, obj.N, obj.K = F, N, M.shape[1]
+    obj.L = (P[0].shape[1], P[1].shape[1])
+    return y, e, M, P, Cl
+
+
 class Diff:
     def __init__(self, y, e, M, P0, P1, classes, d=1.4, s=2.0, pdash=0.5, fixalpha=False, seed=1234, device=0):
         """y, e: (F, N) estimates and standard deviations; M (N, K), P0 (N, L0), P1 (N, L1); classes (N, 2) the variance class of each
         sample under models 0 and 1."""
         self._lib = _lib.load()
         self._h = None
-        self._y = np.ascontiguousarray(y, np.float64)
-        self._e = np.ascontiguousarray(e, np.float64)
-        self._M = np.ascontiguousarray(M, np.float64)
-        self._P = [np.ascontiguousarray(P0, np.float64), np.ascontiguousarray(P1, np.float64)]
-        self._C = np.ascontiguousarray(classes, np.int32)
-        F, N = self._y.shape
-        if self._e.shape != (F, N) or self._M.shape[0] != N or self._P[0].shape[0] != N or self._P[1].shape[0] != N or self._C.shape != (N, 2):
-            raise ValueError("inconsistent shapes")
-        self.F, self.N, self.K = F, N, self._M.shape[1]
-        self.L = (self._P[0].shape[1], self._P[1].shape[1])
+        y, e, M, P, Cl = _design(self, y, e, M, P0, P1, classes)
         h = C.c_void_p()
-        check(self._lib.mmg_diff_create(device, F, N, _ptr(self._y), _ptr(self._e), self.K, _ptr(self._M), self.L[0], _ptr(self._P[0]),
-                                        self.L[1], _ptr(self._P[1]), _ptr(self._C), float(d), float(s), float(pdash), int(bool(fixalpha)),
-                                        int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(h)))
+        check(self._lib.mmg_diff_create(device, self.F, self.N, _ptr(y), _ptr(e), self.K, _ptr(M), self.L[0], _ptr(P[0]), self.L[1], _ptr(P[1]),
+                                        _ptr(Cl), float(d), float(s), float(pdash), int(bool(fixalpha)), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                        C.byref(h)))
         self._h = h
 
     def burnin(self, iters):
@@ -201,10 +208,83 @@ def effects_of_rows(rows, model_of, percentiles=(2.5, 50.0, 97.5), names=None, d
     return _effects_out(lib, e, names if names is not None else ["param%d" % s for s in range(P - 1)], F, pct)
 
 
-class DiffPoly:
+class _DiffReplicas:
+    """What `DiffPoly`, `DiffChains` and `DiffPerm` share: a handle of `_n` replicas (comparisons, chains, data sets) driven through
+    the mmg_diff_<_prefix>_* entries, which differ in the handle type alone."""
+
+    _prefix = None
+    _h = None
+
+    def _fn(self, name):
+        return getattr(self._lib, "mmg_diff_%s_%s" % (self._prefix, name))
+
+    def _create(self, n, *args):
+        self._n = int(n)
+        h = C.c_void_p()
+        check(self._fn("create")(*args, C.byref(h)))
+        self._h = h
+
+    def burnin(self, iters):
+        check(self._fn("burnin")(self._h, int(iters)))
+
+    def tune_batch(self):
+        """One tuning batch for the replicas that have not ended; (untuned counts, ended flags), one entry per replica."""
+        n, ended = (C.c_uint32 * self._n)(), (C.c_int32 * self._n)()
+        check(self._fn("tune_batch")(self._h, n, ended))
+        return list(n), [bool(v) for v in ended]
+
+    def tune(self, max_batches=MAXBATCHES):
+        """Batches until every replica has ended or max_batches have run; the batch count of each replica."""
+        nb = 0
+        while nb != max_batches:
+            _, ended = self.tune_batch()
+            nb += 1
+            if all(ended):
+                break
+        return [self.info(r)["batches"] for r in range(self._n)]
+
+    def sample(self, iters):
+        check(self._fn("sample")(self._h, int(iters)))
+
+    def _eta_rows(self, r):
+        return self.L[0] + self.L[1]
+
+    def results(self, r):
+        F, K = self.F, self.K
+        out = dict(gamma_mean=np.empty(F), logitp=np.empty(F), alpha=np.empty((2, F)), beta=np.empty((2, K, F)),
+                   eta=np.empty((self._eta_rows(r), F)))
+        check(self._fn("get_results")(self._h, int(r), *(_ptr(out[k]) for k in ("gamma_mean", "logitp", "alpha", "beta", "eta"))))
+        return out
+
+    def info(self, r):
+        flags, nc, nb, ended = (C.c_int32 * 3)(), (C.c_uint32 * 2)(), C.c_uint32(), C.c_int32()
+        check(self._fn("info")(self._h, int(r), flags, nc, C.byref(nb), C.byref(ended)))
+        return dict(Mnil=bool(flags[0]), Pnil=(bool(flags[1]), bool(flags[2])), n_classes=(nc[0], nc[1]), batches=nb.value,
+                    ended=bool(ended.value))
+
+    def device_bytes(self):
+        b = C.c_uint64()
+        check(self._fn("device_bytes")(self._h, C.byref(b)))
+        return b.value
+
+    def close(self):
+        if self._h:
+            self._fn("destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DiffPoly(_DiffReplicas):
     """J alternatives against one model 0 on one handle (the mmg_diff_poly_* entries): y, e, M and P0 are held once and every launch
     covers all comparisons.  Comparison j's chain is bit for bit that of `Diff(y, e, M, P0, P1s[j], [classes0, classes1s[j]])` driven
     the same way; in tuning, a comparison whose untuned count reached 0 has ended and keeps its own batch count."""
+
+    _prefix = "poly"
 
     def __init__(self, y, e, M, P0, classes0, P1s, classes1s, d=1.4, s=2.0, pdash=0.5, fixalpha=False, seed=1234, device=0):
         """y, e: (F, N); M (N, K); P0 (N, L0); classes0 (N,) the variance classes under model 0; P1s: J matrices (N, L1_j);
@@ -228,64 +308,14 @@ class DiffPoly:
         self.L1 = tuple(P.shape[1] for P in P1s)
         L1 = np.array(self.L1, np.uint32)
         P1 = np.ascontiguousarray(np.concatenate([P.ravel() for P in P1s]))
-        h = C.c_void_p()
-        check(self._lib.mmg_diff_poly_create(device, F, N, _ptr(y), _ptr(e), self.K, _ptr(M), self.L0, _ptr(P0), _ptr(C0), J, _ptr(L1),
-                                             _ptr(P1), _ptr(C1), float(d), float(s), float(pdash), int(bool(fixalpha)),
-                                             int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(h)))
-        self._h = h
+        self._create(J, device, F, N, _ptr(y), _ptr(e), self.K, _ptr(M), self.L0, _ptr(P0), _ptr(C0), J, _ptr(L1), _ptr(P1), _ptr(C1),
+                     float(d), float(s), float(pdash), int(bool(fixalpha)), int(seed) & 0xFFFFFFFFFFFFFFFF)
 
-    def burnin(self, iters):
-        check(self._lib.mmg_diff_poly_burnin(self._h, int(iters)))
-
-    def tune_batch(self):
-        """One tuning batch for the comparisons that have not ended; (untuned counts, ended flags), one entry per comparison."""
-        n, ended = (C.c_uint32 * self.J)(), (C.c_int32 * self.J)()
-        check(self._lib.mmg_diff_poly_tune_batch(self._h, n, ended))
-        return list(n), [bool(v) for v in ended]
-
-    def tune(self, max_batches=MAXBATCHES):
-        """Batches until every comparison has ended or max_batches have run; the batch count of each comparison."""
-        nb = 0
-        while nb != max_batches:
-            _, ended = self.tune_batch()
-            nb += 1
-            if all(ended):
-                break
-        return [self.info(j)["batches"] for j in range(self.J)]
-
-    def sample(self, iters):
-        check(self._lib.mmg_diff_poly_sample(self._h, int(iters)))
-
-    def results(self, j):
-        F, K, L = self.F, self.K, self.L0 + self.L1[j]
-        out = dict(gamma_mean=np.empty(F), logitp=np.empty(F), alpha=np.empty((2, F)), beta=np.empty((2, K, F)), eta=np.empty((L, F)))
-        check(self._lib.mmg_diff_poly_get_results(self._h, int(j), *(_ptr(out[k]) for k in ("gamma_mean", "logitp", "alpha", "beta", "eta"))))
-        return out
-
-    def info(self, j):
-        flags, nc, nb, ended = (C.c_int32 * 3)(), (C.c_uint32 * 2)(), C.c_uint32(), C.c_int32()
-        check(self._lib.mmg_diff_poly_info(self._h, int(j), flags, nc, C.byref(nb), C.byref(ended)))
-        return dict(Mnil=bool(flags[0]), Pnil=(bool(flags[1]), bool(flags[2])), n_classes=(nc[0], nc[1]), batches=nb.value,
-                    ended=bool(ended.value))
-
-    def device_bytes(self):
-        b = C.c_uint64()
-        check(self._lib.mmg_diff_poly_device_bytes(self._h, C.byref(b)))
-        return b.value
-
-    def close(self):
-        if self._h:
-            self._lib.mmg_diff_poly_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _eta_rows(self, j):
+        return self.L0 + self.L1[j]
 
 
-class DiffChains:
+class DiffChains(_DiffReplicas):
     """C independent chains of one comparison on one handle (the mmg_diff_chains_* entries).  Chain c draws from the streams
     (seed, c, ...) and is bit for bit `Diff(..., seed=seed ^ (c << 32))` driven the same way; each chain tunes on its own and keeps
     its batch count.  `sample_total` (a positive multiple of 16) is the whole sampling length: `sample` may be called in pieces that
@@ -293,56 +323,18 @@ class DiffChains:
 
     NB = 16
 
+    _prefix = "chains"
+
     def __init__(self, y, e, M, P0, P1, classes, n_chains, sample_total, d=1.4, s=2.0, pdash=0.5, fixalpha=False, seed=1234, device=0):
         self._lib = _lib.load()
         self._h = None
-        y = np.ascontiguousarray(y, np.float64)
-        e = np.ascontiguousarray(e, np.float64)
-        M = np.ascontiguousarray(M, np.float64)
-        P = [np.ascontiguousarray(P0, np.float64), np.ascontiguousarray(P1, np.float64)]
-        Cl = np.ascontiguousarray(classes, np.int32)
-        F, N = y.shape
-        if e.shape != (F, N) or M.shape[0] != N or P[0].shape[0] != N or P[1].shape[0] != N or Cl.shape != (N, 2):
-            raise ValueError("inconsistent shapes")
-        self.F, self.N, self.K = F, N, M.shape[1]
-        self.L = (P[0].shape[1], P[1].shape[1])
+        y, e, M, P, Cl = _design(self, y, e, M, P0, P1, classes)
         self.C, self.T = int(n_chains), int(sample_total)
-        h = C.c_void_p()
-        check(self._lib.mmg_diff_chains_create(device, F, N, _ptr(y), _ptr(e), self.K, _ptr(M), self.L[0], _ptr(P[0]), self.L[1], _ptr(P[1]),
-                                               _ptr(Cl), float(d), float(s), float(pdash), int(bool(fixalpha)),
-                                               int(seed) & 0xFFFFFFFFFFFFFFFF, self.C, self.T, C.byref(h)))
-        self._h = h
-
-    def burnin(self, iters):
-        check(self._lib.mmg_diff_chains_burnin(self._h, int(iters)))
-
-    def tune_batch(self):
-        """One tuning batch for the chains that have not ended; (untuned counts, ended flags), one entry per chain."""
-        n, ended = (C.c_uint32 * self.C)(), (C.c_int32 * self.C)()
-        check(self._lib.mmg_diff_chains_tune_batch(self._h, n, ended))
-        return list(n), [bool(v) for v in ended]
-
-    def tune(self, max_batches=MAXBATCHES):
-        """Batches until every chain has ended or max_batches have run; the batch count of each chain."""
-        nb = 0
-        while nb != max_batches:
-            _, ended = self.tune_batch()
-            nb += 1
-            if all(ended):
-                break
-        return [self.info(c)["batches"] for c in range(self.C)]
-
-    def sample(self, iters):
-        check(self._lib.mmg_diff_chains_sample(self._h, int(iters)))
+        self._create(self.C, device, self.F, self.N, _ptr(y), _ptr(e), self.K, _ptr(M), self.L[0], _ptr(P[0]), self.L[1], _ptr(P[1]), _ptr(Cl),
+                     float(d), float(s), float(pdash), int(bool(fixalpha)), int(seed) & 0xFFFFFFFFFFFFFFFF, self.C, self.T)
 
     def pool(self):
         check(self._lib.mmg_diff_chains_pool(self._h))
-
-    def results(self, c):
-        F, K, L = self.F, self.K, self.L
-        out = dict(gamma_mean=np.empty(F), logitp=np.empty(F), alpha=np.empty((2, F)), beta=np.empty((2, K, F)), eta=np.empty((L[0] + L[1], F)))
-        check(self._lib.mmg_diff_chains_get_results(self._h, int(c), *(_ptr(out[k]) for k in ("gamma_mean", "logitp", "alpha", "beta", "eta"))))
-        return out
 
     def batch_sums(self, c):
         out = np.empty((self.NB, self.F))
@@ -357,90 +349,24 @@ class DiffChains:
                                                                                       "alpha", "beta", "eta"))))
         return out
 
-    def info(self, c):
-        flags, nc, nb, ended = (C.c_int32 * 3)(), (C.c_uint32 * 2)(), C.c_uint32(), C.c_int32()
-        check(self._lib.mmg_diff_chains_info(self._h, int(c), flags, nc, C.byref(nb), C.byref(ended)))
-        return dict(Mnil=bool(flags[0]), Pnil=(bool(flags[1]), bool(flags[2])), n_classes=(nc[0], nc[1]), batches=nb.value,
-                    ended=bool(ended.value))
 
-    def device_bytes(self):
-        b = C.c_uint64()
-        check(self._lib.mmg_diff_chains_device_bytes(self._h, C.byref(b)))
-        return b.value
-
-    def close(self):
-        if self._h:
-            self._lib.mmg_diff_chains_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DiffPerm:
+class DiffPerm(_DiffReplicas):
     """The data and B shuffled copies of it on one handle (the mmg_diff_perm_* entries): R = n_perm + 1 replicas, 1 <= n_perm <= 31.
     Replica 0 is the data as given; replica b >= 1 is the data with every feature's samples shuffled on the device, the shuffle
     `mmdiff -permute` applies with the seed seed ^ (b << 32).  Replica b is bit for bit `Diff(y_b, e_b, ..., seed=seed ^ (b << 32))`
     driven the same way; each replica tunes on its own and keeps its batch count.  After sampling, `qvalues` gives the log Bayes
     factors of every replica and the q-values of replica 0 against the pooled replicas 1 .. B."""
 
+    _prefix = "perm"
+
     def __init__(self, y, e, M, P0, P1, classes, n_perm, d=1.4, s=2.0, pdash=0.5, fixalpha=False, seed=1234, device=0):
         self._lib = _lib.load()
         self._h = None
-        y = np.ascontiguousarray(y, np.float64)
-        e = np.ascontiguousarray(e, np.float64)
-        M = np.ascontiguousarray(M, np.float64)
-        P = [np.ascontiguousarray(P0, np.float64), np.ascontiguousarray(P1, np.float64)]
-        Cl = np.ascontiguousarray(classes, np.int32)
-        F, N = y.shape
-        if e.shape != (F, N) or M.shape[0] != N or P[0].shape[0] != N or P[1].shape[0] != N or Cl.shape != (N, 2):
-            raise ValueError("inconsistent shapes")
-        self.F, self.N, self.K = F, N, M.shape[1]
-        self.L = (P[0].shape[1], P[1].shape[1])
+        y, e, M, P, Cl = _design(self, y, e, M, P0, P1, classes)
         self.B = int(n_perm)
         self.R = self.B + 1
-        h = C.c_void_p()
-        check(self._lib.mmg_diff_perm_create(device, F, N, _ptr(y), _ptr(e), self.K, _ptr(M), self.L[0], _ptr(P[0]), self.L[1], _ptr(P[1]),
-                                             _ptr(Cl), float(d), float(s), float(pdash), int(bool(fixalpha)),
-                                             int(seed) & 0xFFFFFFFFFFFFFFFF, self.B & 0xFFFFFFFF, C.byref(h)))
-        self._h = h
-
-    def burnin(self, iters):
-        check(self._lib.mmg_diff_perm_burnin(self._h, int(iters)))
-
-    def tune_batch(self):
-        """One tuning batch for the replicas that have not ended; (untuned counts, ended flags), one entry per replica."""
-        n, ended = (C.c_uint32 * self.R)(), (C.c_int32 * self.R)()
-        check(self._lib.mmg_diff_perm_tune_batch(self._h, n, ended))
-        return list(n), [bool(v) for v in ended]
-
-    def tune(self, max_batches=MAXBATCHES):
-        """Batches until every replica has ended or max_batches have run; the batch count of each replica."""
-        nb = 0
-        while nb != max_batches:
-            _, ended = self.tune_batch()
-            nb += 1
-            if all(ended):
-                break
-        return [self.info(b)["batches"] for b in range(self.R)]
-
-    def sample(self, iters):
-        check(self._lib.mmg_diff_perm_sample(self._h, int(iters)))
-
-    def results(self, b):
-        F, K, L = self.F, self.K, self.L
-        out = dict(gamma_mean=np.empty(F), logitp=np.empty(F), alpha=np.empty((2, F)), beta=np.empty((2, K, F)), eta=np.empty((L[0] + L[1], F)))
-        check(self._lib.mmg_diff_perm_get_results(self._h, int(b), *(_ptr(out[k]) for k in ("gamma_mean", "logitp", "alpha", "beta", "eta"))))
-        return out
-
-    def info(self, b):
-        flags, nc, nb, ended = (C.c_int32 * 3)(), (C.c_uint32 * 2)(), C.c_uint32(), C.c_int32()
-        check(self._lib.mmg_diff_perm_info(self._h, int(b), flags, nc, C.byref(nb), C.byref(ended)))
-        return dict(Mnil=bool(flags[0]), Pnil=(bool(flags[1]), bool(flags[2])), n_classes=(nc[0], nc[1]), batches=nb.value,
-                    ended=bool(ended.value))
+        self._create(self.R, device, self.F, self.N, _ptr(y), _ptr(e), self.K, _ptr(M), self.L[0], _ptr(P[0]), self.L[1], _ptr(P[1]), _ptr(Cl),
+                     float(d), float(s), float(pdash), int(bool(fixalpha)), int(seed) & 0xFFFFFFFFFFFFFFFF, self.B & 0xFFFFFFFF)
 
     def qvalues(self):
         """After sampling: `stat` (R, F) the log Bayes factor of every replica and feature, and of replica 0 against the pooled
@@ -449,22 +375,6 @@ class DiffPerm:
         check(self._lib.mmg_diff_perm_qvalues(self._h))
         check(self._lib.mmg_diff_perm_get_qvalues(self._h, _ptr(out["stat"]), _ptr(out["null_ge"]), _ptr(out["q"])))
         return out
-
-    def device_bytes(self):
-        b = C.c_uint64()
-        check(self._lib.mmg_diff_perm_device_bytes(self._h, C.byref(b)))
-        return b.value
-
-    def close(self):
-        if self._h:
-            self._lib.mmg_diff_perm_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class DiffLrt:
@@ -476,18 +386,9 @@ class DiffLrt:
         """y, e, M, P0, P1, classes as for `Diff`; max_iters: the cap on scoring iterations per model (0: the default, 200)."""
         self._lib = _lib.load()
         self._h = None
-        y = np.ascontiguousarray(y, np.float64)
-        e = np.ascontiguousarray(e, np.float64)
-        M = np.ascontiguousarray(M, np.float64)
-        P = [np.ascontiguousarray(P0, np.float64), np.ascontiguousarray(P1, np.float64)]
-        Cl = np.ascontiguousarray(classes, np.int32)
-        F, N = y.shape
-        if e.shape != (F, N) or M.shape[0] != N or P[0].shape[0] != N or P[1].shape[0] != N or Cl.shape != (N, 2):
-            raise ValueError("inconsistent shapes")
-        self.F, self.N, self.K = F, N, M.shape[1]
-        self.L = (P[0].shape[1], P[1].shape[1])
+        y, e, M, P, Cl = _design(self, y, e, M, P0, P1, classes)
         h = C.c_void_p()
-        check(self._lib.mmg_diff_lrt_create(device, F, N, _ptr(y), _ptr(e), self.K, _ptr(M), self.L[0], _ptr(P[0]), self.L[1], _ptr(P[1]),
+        check(self._lib.mmg_diff_lrt_create(device, self.F, self.N, _ptr(y), _ptr(e), self.K, _ptr(M), self.L[0], _ptr(P[0]), self.L[1], _ptr(P[1]),
                                             _ptr(Cl), int(bool(fixalpha)), int(max_iters), C.byref(h)))
         self._h = h
 
@@ -538,18 +439,11 @@ class DiffLrtPerm(DiffLrt):
         workspace under 1 GiB) -- no result depends on it."""
         self._lib = _lib.load()
         self._h = self._perm = None
-        y = np.ascontiguousarray(y, np.float64)
-        e = np.ascontiguousarray(e, np.float64)
-        M = np.ascontiguousarray(M, np.float64)
-        P = [np.ascontiguousarray(P0, np.float64), np.ascontiguousarray(P1, np.float64)]
-        Cl = np.ascontiguousarray(classes, np.int32)
-        F, N = y.shape
-        if e.shape != (F, N) or M.shape[0] != N or P[0].shape[0] != N or P[1].shape[0] != N or Cl.shape != (N, 2):
-            raise ValueError("inconsistent shapes")
+        y, e, M, P, Cl = _design(self, y, e, M, P0, P1, classes)
+        F, N = self.F, self.N
         if not 0 <= int(n_perm) < 2 ** 32 or not 0 <= int(slab_copies) < 2 ** 32:
             raise ValueError("n_perm and slab_copies must fit 32 bits")
-        self.F, self.N, self.K, self.B = F, N, M.shape[1], int(n_perm)
-        self.L = (P[0].shape[1], P[1].shape[1])
+        self.B = int(n_perm)
         h = C.c_void_p()
         check(self._lib.mmg_diff_lrt_perm_create(device, F, N, _ptr(y), _ptr(e), self.K, _ptr(M), self.L[0], _ptr(P[0]), self.L[1], _ptr(P[1]),
                                                  _ptr(Cl), int(bool(fixalpha)), int(max_iters), self.B, int(seed) & (2 ** 64 - 1), int(slab_copies),
