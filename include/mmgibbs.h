@@ -86,7 +86,8 @@ extern "C" {
  *      MMG_OPT_POOL_SLAB), and the posterior correlation of pairs of transcripts (mmg_pairs_*, MMG_OPT_PAIRS_SLAB), and mmdiff's
  *      effect summaries (mmg_diff_effects_*, mmg_effects_*), and mmdiff's permutation null with its q-values (mmg_diff_perm_*,
  *      mmg_qvalues), and the self test of the streams' key space and of the scalar functions (mmg_selftest_keyed), and mmdiff's
- *      likelihood-ratio test (mmg_diff_lrt_*) with its permutation null (mmg_diff_lrt_perm_*).
+ *      likelihood-ratio test (mmg_diff_lrt_*) with its permutation null (mmg_diff_lrt_perm_*), and the posterior fold change between
+ *      two samples from all pairs of their draws (mmg_fold_*, MMG_OPT_FOLD_SLAB).
  *      mmg_sampler_create refuses chains beyond 2^24: the Gamma stream's key holds 24 bits of the chain index (the row stream all 32), so
  *      chain 2^24 + c would redraw mu from chain c's uniforms.  No chain that ran before is changed by the check. */
 /* Layout.  The model does not care about the order of rows or the numbering of transcripts (src/mmseq.cpp:399-418 uses
@@ -499,7 +500,8 @@ enum {
     MMG_OPT_CONTRAST_SLAB = 16,    /* v >= 1: at most v contrasts per slab of mmg_contrast_create / _of_traces (slab edges on small inputs)      */
     MMG_OPT_POOL_SLAB = 17,        /* v >= 1: at most v series per slab of mmg_pooled_create / _of_traces (slab edges on small inputs)          */
     MMG_OPT_PAIRS_SLAB = 18,       /* v >= 1: at most v pairs per slab of mmg_pairs_create / _of_traces (slab edges on small inputs)             */
-    MMG_OPT_COUNT_ = 19
+    MMG_OPT_FOLD_SLAB = 19,        /* v >= 1: at most v features per slab of mmg_fold_create / _of_traces (slab edges on small inputs)           */
+    MMG_OPT_COUNT_ = 20
 };
 int mmg_selftest_option(int option, int value);
 /* What the library holds: counts[3] = device buffers, streams, events (tests: every call gives back what it acquired). */
@@ -702,6 +704,46 @@ int mmg_pairs_get(mmg_pairs *h, double *mean_a, double *mean_b, double *mean_sum
  * 60 Px of results; from a sampler also 8 S Mx of gathered traces, from host traces also 8 n_series S. */
 int mmg_pairs_device_bytes(mmg_pairs *h, uint64_t *bytes);
 void mmg_pairs_destroy(mmg_pairs *h);
+
+/* ---- the posterior fold change of a feature between two samples, from all pairs of their draws ---------------------------
+ * Two samples are independent given their reads, so every pair (draw i of A, draw j of B) is a draw from the joint posterior of the
+ * log fold change: Sa Sb draws per feature.  This is the posterior given the reads of these two libraries; it says nothing about
+ * biological variability -- for groups with replicates the tool is mmdiff.
+ * Feature f has the draws a[0 .. Sa) and b[0 .. Sb) on the mu scale and the offset `off` on the natural-log scale.  It is valid when
+ * every draw of both sides is finite and > 0; otherwise its status byte gets bit 0 (a draw of A) and / or bit 1 (a draw of B), all
+ * its outputs are NaN and its counts 0 (checked before anything else is done with the series).  For a valid feature, status 0 and:
+ *   x_i = log a_i (the library's log), y_j = log b_j + off, d_ij = x_i - y_j, each rounded once; -0.0 counts as +0.0.
+ *   n_gt = #{(i, j): x_i > y_j}, n_eq = #{(i, j): x_i == y_j}, exact, from x and y (never through d); the caller forms
+ *       p_gt = (n_gt + n_eq / 2) / (Sa Sb).
+ *   quantiles[f * n_ranks + r] = the ranks[r]-th smallest (zero-based) of the Sa Sb values d_ij, exactly: numpy's
+ *       np.sort(np.subtract.outer(x, y), axis=None)[k].  A rank >= Sa Sb gives NaN for that rank alone.
+ *   mean_a = sum x_i / Sa, mean_b = sum y_j / Sb (offset included), ss_a = sum (x_i - mean_a)^2, ss_b likewise (each square rounded,
+ *       then added).  Every sum runs over the series in the caller's sample order, as a wave with one lane per sample adds: lane l
+ *       adds its samples l, l + 64, ... ascending from 0.0, the 64 partial sums are folded by halving.  The caller derives
+ *       lfc = mean_a - mean_b and sd = sqrt(ss_a / (Sa - 1) + ss_b / (Sb - 1)).
+ * 1 <= Sa, Sb <= 4096 (they need not be equal, nor powers of two), n_features >= 1, n_ranks <= 64, off finite: MMG_ERR_ARG otherwise,
+ * with a message that names the argument; every argument is checked before any device work.  tests/fold_ref.py, DESIGN.md
+ * section 16; no floating-point atomics: reruns are bit-identical.  Additive in ABI version 8. */
+typedef struct mmg_fold mmg_fold;
+/* From host traces, series-major: a[f * Sa + s], b[f * Sb + s]. */
+int mmg_fold_of_traces(int device, uint32_t n_features, uint32_t Sa, const double *a, uint32_t Sb, const double *b, double off, uint32_t n_ranks,
+                       const uint32_t *ranks, mmg_fold **out);
+/* From the resident traces of two samplers on one device: feature f compares transcript ia[f] of chain chain_a of sampler sa with
+ * transcript ib[f] of chain chain_b of sampler sb (the caller's numbering; sa and sb may be the same sampler), over their trace_len
+ * kept samples (Sa, Sb).  Both samplers must hold a trace and be past their last kept sample (MMG_ERR_STATE otherwise).  MMG_ERR_ARG:
+ * a NULL sampler, array or output, a chain out of range, a member >= n (the message names the feature), samplers on different
+ * devices, and the rules above.  The same bits as mmg_fold_of_traces on the downloaded traces. */
+int mmg_fold_create(mmg_sampler *sa, int chain_a, mmg_sampler *sb, int chain_b, uint32_t n_features, const uint32_t *ia, const uint32_t *ib, double off,
+                    uint32_t n_ranks, const uint32_t *ranks, mmg_fold **out);
+/* mean_a, mean_b, ss_a, ss_b, n_gt, n_eq, status: [n_features]; quantiles: [n_features][n_ranks]; any pointer may be NULL.  The
+ * results are on the host from creation: no device work. */
+int mmg_fold_get(mmg_fold *h, double *mean_a, double *mean_b, double *ss_a, double *ss_b, uint32_t *n_gt, uint32_t *n_eq, double *quantiles,
+                 uint8_t *status);
+/* The handle holds nothing on the device once it exists; this is what its creation held at its peak.  The features are cut into
+ * slabs of cap = max(1, min(n_features, 256 MiB / (8 (Sa + Sb)), MMG_OPT_FOLD_SLAB if set)) consecutive features:
+ * 8 cap (Sa + Sb) of series + cap (41 + 8 n_ranks) of results + 4 n_ranks of ranks; from samplers also 8 cap of member lists. */
+int mmg_fold_device_bytes(mmg_fold *h, uint64_t *bytes);
+void mmg_fold_destroy(mmg_fold *h);
 
 /* ---- mmdiff: Bayesian model selection between two linear models per feature -------------------------------------------
  * src/bms.cpp driven as src/mmdiff.cpp:744-866: per feature an independent MCMC over both models with pseudopriors, the model

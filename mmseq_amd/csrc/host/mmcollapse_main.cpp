@@ -12,7 +12,6 @@
 // There is no CPU path: without a HIP device the program stops with an error once the inputs are checked.
 #include <omp.h>
 #include <sys/stat.h>
-#include <zlib.h>
 
 #include <algorithm>
 #include <cmath>
@@ -30,8 +29,14 @@
 
 #include "../../../include/mmgibbs.h"
 #include "stage_timer.hpp"
+#include "trace_io.hpp"
 
 using namespace std;
+using traceio::TableReader;
+using traceio::find_col;
+using traceio::num;
+using traceio::readable;
+using traceio::tokenise;
 
 static const int TRACELEN = 1024;
 static const double IACTTHRES = 1.1;
@@ -52,26 +57,6 @@ static void printUsage(ostream &out)
     exit(1);
 }
 
-static vector<string> tokenise(const string &str, const string &delim)
-{
-    vector<string> out;
-    string::size_type last = str.find_first_not_of(delim, 0), pos = str.find_first_of(delim, last);
-    while (pos != string::npos || last != string::npos) {
-        out.push_back(str.substr(last, pos - last));
-        last = str.find_first_not_of(delim, pos);
-        pos = str.find_first_of(delim, last);
-    }
-    return out;
-}
-
-static bool readable(const string &path)
-{
-    FILE *f = fopen(path.c_str(), "rb");
-    if (!f) return false;
-    fclose(f);
-    return true;
-}
-
 // what one sample's tables contribute (get_unidentifiable_transcripts, src/mmcollapse.cpp:117-396)
 struct Tables {
     vector<string> candidates, zeros, toremove;
@@ -79,24 +64,14 @@ struct Tables {
     long mapped = 0;
 };
 
-static int find_col(const vector<string> &hdr, const char *name)
-{
-    for (size_t i = 0; i < hdr.size(); ++i) if (hdr[i] == name) return (int)i;
-    return -1;
-}
-
-static double num(const string &s) { return atof(s.c_str()); }
-
 static void read_tables(const string &base, Tables &tb, vector<string> &all_features, bool want_all, map<string, bool> &isIdent)
 {
     vector<double> sd;
-    ifstream ifs((base + ".identical.mmseq").c_str());
-    if (!ifs.good()) die("Error: cannot open " + base + ".identical.mmseq");
-    string str;
-    getline(ifs, str);
-    while (ifs.good() && !str.empty() && str[0] == '#') getline(ifs, str);
-    if (!ifs.good()) die("Error: truncated *identical.mmseq file?");
-    vector<string> hdr = tokenise(str, "\t");
+    TableReader itab;
+    int rc = itab.open(base + ".identical.mmseq");
+    if (rc == TableReader::CANNOT_OPEN) die("Error: cannot open " + base + ".identical.mmseq");
+    if (rc == TableReader::TRUNCATED) die("Error: truncated *identical.mmseq file?");
+    const vector<string> &hdr = itab.hdr;
     const char *need[] = {"feature_id", "iact", "unique_hits", "observed", "sd", "log_mu", "effective_length"};
     int col[7];
     for (int i = 0; i < 7; ++i) {
@@ -105,10 +80,9 @@ static void read_tables(const string &base, Tables &tb, vector<string> &all_feat
     }
     int maxcol = *max_element(col, col + 7);
     const int ic = col[0], ac = col[1], ob = col[3], si = col[4], el = col[6];
-    while (getline(ifs, str)) {
-        vector<string> t = tokenise(str, "\t");
-        if (t.empty()) break;
-        if ((int)t.size() <= maxcol) die("Error: malformed line in " + base + ".identical.mmseq: " + str);
+    vector<string> t;
+    while (itab.row(t)) {
+        if ((int)t.size() <= maxcol) die("Error: malformed line in " + base + ".identical.mmseq: " + itab.line);
         tb.candidates.push_back(t[ic]);
         for (auto &m : tokenise(t[ic], "+")) isIdent[m] = true;
         if (want_all) all_features.push_back(t[ic]);
@@ -119,35 +93,28 @@ static void read_tables(const string &base, Tables &tb, vector<string> &all_feat
         } else sd.push_back(num(t[si]));
     }
     (void)ac;
-    ifs.close(); ifs.clear();
 
-    ifs.open((base + ".mmseq").c_str());
-    if (!ifs.good()) die("Error: cannot open " + base + ".mmseq");
-    getline(ifs, str);
+    TableReader table;
+    rc = table.open(base + ".mmseq");
+    if (rc == TableReader::CANNOT_OPEN) die("Error: cannot open " + base + ".mmseq");
     bool have_mapped = false;
-    while (ifs.good() && !str.empty() && str[0] == '#') {
+    for (const string &str : table.comments)
         if (str.find("Mapped fragments") != string::npos) {
-            vector<string> t = tokenise(str, " ");
-            tb.mapped = (long)num(t.back());
+            tb.mapped = (long)num(tokenise(str, " ").back());
             have_mapped = true;
         }
-        getline(ifs, str);
-    }
-    if (!ifs.good()) die("Error: truncated *mmseq file?");
+    if (rc == TableReader::TRUNCATED) die("Error: truncated *mmseq file?");
     if (!have_mapped) die("Error: " + base + ".mmseq has no \"# Mapped fragments\" line.");
-    hdr = tokenise(str, "\t");
     const char *need2[] = {"feature_id", "unique_hits", "iact", "observed", "sd", "log_mu", "effective_length"};
     for (int i = 0; i < 7; ++i) {
-        col[i] = find_col(hdr, need2[i]);
+        col[i] = find_col(table.hdr, need2[i]);
         if (col[i] < 0) die("Error: " + base + ".mmseq file does not contain \"" + need2[i] + "\" column.");
     }
     maxcol = *max_element(col, col + 7);
     const int ic2 = col[0], uc = col[1], ac2 = col[2], ob2 = col[3], si2 = col[4], el2 = col[6];
     double max_h1_sd = 0;
-    while (getline(ifs, str)) {
-        vector<string> t = tokenise(str, "\t");
-        if (t.empty()) break;
-        if ((int)t.size() <= maxcol) die("Error: malformed line in " + base + ".mmseq: " + str);
+    while (table.row(t)) {
+        if ((int)t.size() <= maxcol) die("Error: malformed line in " + base + ".mmseq: " + table.line);
         const bool ident = isIdent.count(t[ic2]) > 0;
         if (!ident && want_all) all_features.push_back(t[ic2]);
         if (t[uc] == "0" && !ident) {
@@ -168,60 +135,6 @@ static void read_tables(const string &base, Tables &tb, vector<string> &all_feat
             tb.toremove.push_back(tb.candidates[i]);
             tb.candidates.erase(tb.candidates.begin() + i);
         }
-}
-
-// whitespace-separated tokens of a gzip file
-struct GzTokens {
-    gzFile f = nullptr;
-    vector<char> buf = vector<char>(1 << 20);
-    size_t pos = 0, len = 0;
-    bool eof = false;
-    explicit GzTokens(const string &path) { f = gzopen(path.c_str(), "rb"); if (f) gzbuffer(f, 1 << 20); }
-    ~GzTokens() { if (f) gzclose(f); }
-    int get()
-    {
-        if (pos == len) {
-            if (eof) return -1;
-            const int r = gzread(f, buf.data(), (unsigned)buf.size());
-            if (r <= 0) { eof = true; return -1; }
-            len = (size_t)r; pos = 0;
-        }
-        return (unsigned char)buf[pos++];
-    }
-    bool line(string &out)
-    {
-        out.clear();
-        int c;
-        while ((c = get()) >= 0 && c != '\n') out.push_back((char)c);
-        return c >= 0 || !out.empty();
-    }
-    bool token(char *tmp, size_t cap)
-    {
-        int c;
-        while ((c = get()) >= 0 && (c == ' ' || c == '\n' || c == '\t' || c == '\r')) {}
-        if (c < 0) return false;
-        size_t n = 0;
-        while (c >= 0 && !(c == ' ' || c == '\n' || c == '\t' || c == '\r')) { if (n + 1 < cap) tmp[n++] = (char)c; c = get(); }
-        tmp[n] = 0;
-        return true;
-    }
-};
-
-// One trace file: the ids of its header line and the TRACELEN x ids values, row-major (values as atof reads them: "NA" is 0)
-static string read_trace(const string &path, vector<string> &ids, vector<double> &vals)
-{
-    GzTokens g(path);
-    if (!g.f) return "Error: couldn't open " + path + ".";
-    string head;
-    if (!g.line(head)) return "Error: " + path + " is empty.";
-    ids = tokenise(head, " ");
-    vals.assign((size_t)TRACELEN * ids.size(), 0.0);
-    char tmp[64];
-    for (size_t i = 0; i < vals.size(); ++i) {
-        if (!g.token(tmp, sizeof tmp)) return "Error: " + path + " is truncated (fewer than " + to_string(TRACELEN) + " rows).";
-        vals[i] = atof(tmp);
-    }
-    return string();
 }
 
 struct SampleTraces {
@@ -321,8 +234,8 @@ int main(int argc, char **argv)
                     SampleTraces &t = tr[s];
                     vector<string> ids1, ids2;
                     vector<double> m1, m2;
-                    t.err = read_trace(basenames[s] + ".trace_gibbs.gz", ids1, m1);
-                    if (t.err.empty()) t.err = read_trace(basenames[s] + ".identical.trace_gibbs.gz", ids2, m2);
+                    t.err = traceio::read_trace(basenames[s] + ".trace_gibbs.gz", TRACELEN, ids1, m1);
+                    if (t.err.empty()) t.err = traceio::read_trace(basenames[s] + ".identical.trace_gibbs.gz", TRACELEN, ids2, m2);
                     if (!t.err.empty()) continue;
                     vector<size_t> keep;   // the non-identical columns of the transcript trace (:838-849)
                     for (size_t c = 0; c < ids1.size(); ++c) if (!isIdent.count(ids1[c])) keep.push_back(c);
