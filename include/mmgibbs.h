@@ -87,7 +87,8 @@ extern "C" {
  *      effect summaries (mmg_diff_effects_*, mmg_effects_*), and mmdiff's permutation null with its q-values (mmg_diff_perm_*,
  *      mmg_qvalues), and the self test of the streams' key space and of the scalar functions (mmg_selftest_keyed), and mmdiff's
  *      likelihood-ratio test (mmg_diff_lrt_*) with its permutation null (mmg_diff_lrt_perm_*), and the posterior fold change between
- *      two samples from all pairs of their draws (mmg_fold_*, MMG_OPT_FOLD_SLAB).
+ *      two samples from all pairs of their draws (mmg_fold_*, MMG_OPT_FOLD_SLAB), and the posterior distances and correlations
+ *      between samples from their joint draws (mmg_sim_*, MMG_OPT_SIM_CHUNK).
  *      mmg_sampler_create refuses chains beyond 2^24: the Gamma stream's key holds 24 bits of the chain index (the row stream all 32), so
  *      chain 2^24 + c would redraw mu from chain c's uniforms.  No chain that ran before is changed by the check. */
 /* Layout.  The model does not care about the order of rows or the numbering of transcripts (src/mmseq.cpp:399-418 uses
@@ -501,7 +502,8 @@ enum {
     MMG_OPT_POOL_SLAB = 17,        /* v >= 1: at most v series per slab of mmg_pooled_create / _of_traces (slab edges on small inputs)          */
     MMG_OPT_PAIRS_SLAB = 18,       /* v >= 1: at most v pairs per slab of mmg_pairs_create / _of_traces (slab edges on small inputs)             */
     MMG_OPT_FOLD_SLAB = 19,        /* v >= 1: at most v features per slab of mmg_fold_create / _of_traces (slab edges on small inputs)           */
-    MMG_OPT_COUNT_ = 20
+    MMG_OPT_SIM_CHUNK = 20,        /* v >= 1: v features per chunk of mmg_sim_run's Gram kernel (chunk edges on small inputs; read by mmg_sim_create) */
+    MMG_OPT_COUNT_ = 21
 };
 int mmg_selftest_option(int option, int value);
 /* What the library holds: counts[3] = device buffers, streams, events (tests: every call gives back what it acquired). */
@@ -744,6 +746,59 @@ int mmg_fold_get(mmg_fold *h, double *mean_a, double *mean_b, double *ss_a, doub
  * 8 cap (Sa + Sb) of series + cap (41 + 8 n_ranks) of results + 4 n_ranks of ranks; from samplers also 8 cap of member lists. */
 int mmg_fold_device_bytes(mmg_fold *h, uint64_t *bytes);
 void mmg_fold_destroy(mmg_fold *h);
+
+/* ---- posterior distances and correlations between samples, from their joint draws ----------------------------------------
+ * Samples are independent given their reads, so draw t of every one of S samples together is one draw from the joint posterior of all
+ * S expression profiles, and a distance matrix computed per draw gives T posterior draws of that matrix.
+ * Sizes: 2 <= S <= 256 samples, 1 <= F < 2^31 features, 1 <= T <= 4096 joint draws; at most 64 zero-based ranks, a rank >= T gives
+ * NaN for that rank alone.
+ * Values: x = log v (the library's log), or x = v with MMG_SIM_LOGGED; z_s[t][f] = (x + off_s) - c[f], each operation rounded once,
+ * -0.0 stored as +0.0; c the handle's centre (NULL: zeros), off_s the sample's offset on the natural-log scale.
+ * Used features: mask[f] != 0 (NULL: all ones) and every one of the feature's S T values valid -- finite and > 0, or just finite with
+ * MMG_SIM_LOGGED; the check comes before the logarithm.  n is their number; the others contribute nothing anywhere (their z is 0.0
+ * once mmg_sim_run has run).  With n < 2 the status byte has bit 0, every summary is NaN and the counts are 0.
+ * Stage 1, per draw t: G[t][r][s] = sum over the used f of z_r[t][f] z_s[t][f] and m[t][r] = sum of z_r[t][f], in fp64 on the matrix
+ * cores.  The order of the sum is the kernel's own -- fixed for given inputs and settings, no floating-point atomics, so reruns give
+ * the same bits -- and not part of the specification.  G is symmetric.
+ * Stage 2, per draw and pair r < s, exactly these operations in this order, each rounded once, from the stage-1 numbers as stored:
+ *   D[t] = sqrt(max(0, (G_rr + G_ss) - 2 G_rs) / n): the root-mean-square log ratio over the used features (the centre cancels);
+ *   R[t] = (G_rs - m_r m_s / n) / sqrt((G_rr - m_r m_r / n) (G_ss - m_s m_s / n)): Pearson's correlation across the features.  A
+ *       variance term <= 0 or an R that is not finite in any draw gives the pair status bit 1 and NaN in every R output of the pair;
+ *   nn[a][b] = #{t: b = argmin over b' != a of (G_aa + G_b'b') - 2 G_ab'}, ties to the smallest b': integers, every row sums to T.
+ * Per pair (r < s, r-major) over the T draws: mean_D = sum D / T, ss_D = sum (D - mean_D)^2 and the same of R, every sum in the
+ * draws' order as a wave with one lane per draw adds (as mmg_fold_*); q_D, q_R [pair][n_ranks]: the order statistics at the ranks.
+ * The caller derives sd = sqrt(ss / (T - 1)) and p_nearest = nn / T.  tests/sim_ref.py, DESIGN.md section 17.  Additive in ABI
+ * version 8. */
+#define MMG_SIM_LOGGED 1u /* the traces are on the log scale already */
+typedef struct mmg_sim mmg_sim;
+/* Allocates everything the handle ever holds: S T F 8 bytes of draws plus the results (mmg_sim_device_bytes).  MMG_ERR_ARG, with a
+ * message that names the argument, before the device is touched: S, F or T outside the sizes above, flags with unknown bits, a
+ * centre that is not finite; and, with both numbers in the message, a need above the device's free memory. */
+int mmg_sim_create(int device, uint32_t S, uint32_t F, uint32_t T, const double *centre, const uint8_t *mask, uint32_t flags, mmg_sim **out);
+/* trace[t * F + f], the layout of the trace files (as mmg_collapse_set_sample takes it); off finite.  A sample may be set again before
+ * mmg_sim_run (MMG_ERR_STATE after it). */
+int mmg_sim_set_sample(mmg_sim *h, uint32_t s, const double *trace, double off);
+/* Both stages.  MMG_ERR_STATE while a sample is unset; MMG_ERR_ARG for n_ranks > 64 or NULL ranks with n_ranks > 0.  A later call
+ * summarises again (other ranks); the stage-1 numbers come out the same.  The calls out of sequence are MMG_ERR_STATE, as everywhere
+ * in this library, not MMG_ERR_ARG: no argument is wrong.  The getters of results (used, gram, get) serve the last run that
+ * succeeded: after a run that failed they are MMG_ERR_STATE again, as before the first. */
+int mmg_sim_run(mmg_sim *h, uint32_t n_ranks, const uint32_t *ranks);
+/* used[F] (0 / 1) and n of the last run; either may be NULL */
+int mmg_sim_get_used(mmg_sim *h, uint8_t *used, uint64_t *n);
+/* z of sample s, draws [first_draw, first_draw + n_draws): out[n_draws][F] as it stands on the device */
+int mmg_sim_get_z(mmg_sim *h, uint32_t s, uint32_t first_draw, uint32_t n_draws, double *out);
+/* G[n_draws][S][S] and m[n_draws][S] of the draws [first_draw, first_draw + n_draws); either may be NULL */
+int mmg_sim_get_gram(mmg_sim *h, uint32_t first_draw, uint32_t n_draws, double *G, double *m);
+/* mean_D, ss_D, mean_R, ss_R, pair_status: [S (S - 1) / 2]; q_D, q_R: [S (S - 1) / 2][n_ranks]; nn: [S][S], diagonal 0; status: one
+ * byte; any pointer may be NULL.  The results are on the host since the run: no device work. */
+int mmg_sim_get(mmg_sim *h, double *mean_D, double *ss_D, double *q_D, double *mean_R, double *ss_R, double *q_R, uint32_t *nn,
+                uint8_t *pair_status, uint8_t *status);
+/* What the handle holds from creation to destruction.  With NT = ceil((S + 1) / 16), U = NT (NT + 1) / 2 tiles,
+ * CH = min(F, max(MMG_OPT_SIM_CHUNK if set, else 4096, ceil(F / 65535)))
+ * features per chunk, C = ceil(F / CH) chunks and P = S (S - 1) / 2 pairs: 8 S T F of draws + F (S + 18) of centre, ones, mask, used
+ * and marks + 2048 T C U of partial tiles + 8 T (S S + S + 1) of G, m, n + 8 + 1057 P of summaries (64 ranks) + 4 S S + 256. */
+int mmg_sim_device_bytes(mmg_sim *h, uint64_t *bytes);
+void mmg_sim_destroy(mmg_sim *h);
 
 /* ---- mmdiff: Bayesian model selection between two linear models per feature -------------------------------------------
  * src/bms.cpp driven as src/mmdiff.cpp:744-866: per feature an independent MCMC over both models with pseudopriors, the model

@@ -39,7 +39,7 @@ class MMGError(RuntimeError):
 
 LAYOUT_CANONICAL, LAYOUT_KEEP_ROWS = 0, 1
 # mmg_selftest_option ids
-OPT_SAMPLE_KERNEL, OPT_FORCE_IDX64, OPT_SELL_WAVES_PER_CU, OPT_EM_KERNEL, OPT_EM_GRID, OPT_FUSE_CHAINS, OPT_CNT_REPLICAS, OPT_GROUP_FAIL, OPT_DERIVE_ORDER, OPT_WIRE_CHECK, OPT_BIGK_PER_WAVE, OPT_BIGK_SIDE_STREAM, OPT_FAIL_ALLOC, OPT_CONV_SLAB, OPT_DIFF_TRACE_ROWS, OPT_ASSIGN_WAVES, OPT_CONTRAST_SLAB, OPT_POOL_SLAB, OPT_PAIRS_SLAB, OPT_FOLD_SLAB = range(20)
+OPT_SAMPLE_KERNEL, OPT_FORCE_IDX64, OPT_SELL_WAVES_PER_CU, OPT_EM_KERNEL, OPT_EM_GRID, OPT_FUSE_CHAINS, OPT_CNT_REPLICAS, OPT_GROUP_FAIL, OPT_DERIVE_ORDER, OPT_WIRE_CHECK, OPT_BIGK_PER_WAVE, OPT_BIGK_SIDE_STREAM, OPT_FAIL_ALLOC, OPT_CONV_SLAB, OPT_DIFF_TRACE_ROWS, OPT_ASSIGN_WAVES, OPT_CONTRAST_SLAB, OPT_POOL_SLAB, OPT_PAIRS_SLAB, OPT_FOLD_SLAB, OPT_SIM_CHUNK = range(21)
 
 
 class ProblemDesc(C.Structure):
@@ -252,6 +252,15 @@ SYMBOLS = {
     "mmg_fold_get": (C.c_int, [C.c_void_p] * 9),
     "mmg_fold_device_bytes": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mmg_fold_destroy": (None, [C.c_void_p]),
+    "mmg_sim_create": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "mmg_sim_set_sample": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_double]),
+    "mmg_sim_run": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "mmg_sim_get_used": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "mmg_sim_get_z": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "mmg_sim_get_gram": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "mmg_sim_get": (C.c_int, [C.c_void_p] * 10),
+    "mmg_sim_device_bytes": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mmg_sim_destroy": (None, [C.c_void_p]),
     "mmg_convergence_create": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "mmg_convergence_get": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmg_convergence_destroy": (None, [C.c_void_p]),
