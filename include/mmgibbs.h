@@ -88,7 +88,8 @@ extern "C" {
  *      mmg_qvalues), and the self test of the streams' key space and of the scalar functions (mmg_selftest_keyed), and mmdiff's
  *      likelihood-ratio test (mmg_diff_lrt_*) with its permutation null (mmg_diff_lrt_perm_*), and the posterior fold change between
  *      two samples from all pairs of their draws (mmg_fold_*, MMG_OPT_FOLD_SLAB), and the posterior distances and correlations
- *      between samples from their joint draws (mmg_sim_*, MMG_OPT_SIM_CHUNK).
+ *      between samples from their joint draws (mmg_sim_*, MMG_OPT_SIM_CHUNK), and the pointwise self test of the binomial chain's
+ *      three shortcuts (mmg_selftest_bigk_points).
  *      mmg_sampler_create refuses chains beyond 2^24: the Gamma stream's key holds 24 bits of the chain index (the row stream all 32), so
  *      chain 2^24 + c would redraw mu from chain c's uniforms.  No chain that ran before is changed by the check. */
 /* Layout.  The model does not care about the order of rows or the numbering of transcripts (src/mmseq.cpp:399-418 uses
@@ -583,6 +584,41 @@ typedef struct mmg_keyed_io {
     double *out_u32, *out_u52, *out_target;
 } mmg_keyed_io;
 int mmg_selftest_keyed(int device, const mmg_keyed_io *io);
+
+/* The three shortcuts of the conditional-binomial chain's kernel (k_sample_bigk) on caller-given points (device >= 0: in kernels on that
+ * device; device == -1: the host instantiation of the same inline code, which has no fp32 tests).  Two independent parts; a part with
+ * count 0 is skipped, its pointers may be NULL.  Out-of-domain input is MMG_ERR_ARG.
+ *   inversion, element i: inv_n[i] >= 1, 0 < inv_p[i] <= 1/2 with n p < 10, 0 < inv_u[i] < 1; inv_slack > 0 scales the fp32 search's bound
+ *     out_inv_bound[i]  binv_zero_bound(n, n p): a uniform at or below it is x = 0 without the search (the kernel's STEP)
+ *     out_inv_x[i]      the x of the fp64 search on the uniform u, -1 where the sum of its terms fell short of u.  The search walks as
+ *                       far as u sends it: a caller keeps u away from 1 at large n
+ *     out_inv_pre[i]    the x of the fp32 search where its bound decides, -1 where it does not (always -1 on the host)
+ *   BTRS, element i: btrs_n[i] >= 21, btrs_p[i] <= 1/2 with n p >= 10, the attempt's two uniforms 0 < btrs_u[i], btrs_v[i] < 1; constants
+ *   and candidate formed as the kernel forms them
+ *     out_btrs_kf[i]     the candidate
+ *     out_btrs_reach[i]  0: the candidate is outside [0, n]; 1: the squeeze accepts it; 2: the exact test is reached, and then
+ *     out_btrs_exact[i]  1 / 0: the fp64 test accepts / rejects (-1 unless reach is 2);  out_btrs_diff[i]: its ub - v (0 unless reach is 2)
+ *     out_btrs_d32[i], out_btrs_e32[i]  the fp32 estimate of the difference and the bound on its error (0, 0 on the host or unless reach is 2)
+ *     out_btrs_pre[i]    +1 / -1: the fp32 test accepts / rejects, 0: undecided (0 on the host or unless reach is 2)
+ * Additive in version 8. */
+typedef struct mmg_bigk_points {
+    int64_t n_inv;
+    const uint32_t *inv_n;
+    const double *inv_p, *inv_u;
+    double inv_slack;
+    double *out_inv_bound;
+    int64_t *out_inv_x;
+    int32_t *out_inv_pre;
+    int64_t n_btrs;
+    const uint32_t *btrs_n;
+    const double *btrs_p, *btrs_u, *btrs_v;
+    double *out_btrs_kf;
+    int32_t *out_btrs_reach, *out_btrs_exact;
+    double *out_btrs_diff;
+    float *out_btrs_d32, *out_btrs_e32;
+    int32_t *out_btrs_pre;
+} mmg_bigk_points;
+int mmg_selftest_bigk_points(int device, const mmg_bigk_points *io);
 
 /* ---- mmcollapse: candidates collapsed by their mean posterior anti-correlation across samples ----------------------------
  * src/mmcollapse.cpp:483-561 (covariances of the candidates' traces per sample, mean correlations), :713-747 (row maxima for the

@@ -90,6 +90,14 @@ class KeyedIO(C.Structure):
                 ("out_u52", C.c_void_p), ("out_target", C.c_void_p)]
 
 
+class BigkPoints(C.Structure):
+    _fields_ = [("n_inv", C.c_int64), ("inv_n", C.c_void_p), ("inv_p", C.c_void_p), ("inv_u", C.c_void_p), ("inv_slack", C.c_double),
+                ("out_inv_bound", C.c_void_p), ("out_inv_x", C.c_void_p), ("out_inv_pre", C.c_void_p),
+                ("n_btrs", C.c_int64), ("btrs_n", C.c_void_p), ("btrs_p", C.c_void_p), ("btrs_u", C.c_void_p), ("btrs_v", C.c_void_p),
+                ("out_btrs_kf", C.c_void_p), ("out_btrs_reach", C.c_void_p), ("out_btrs_exact", C.c_void_p), ("out_btrs_diff", C.c_void_p),
+                ("out_btrs_d32", C.c_void_p), ("out_btrs_e32", C.c_void_p), ("out_btrs_pre", C.c_void_p)]
+
+
 class Timing(C.Structure):
     _fields_ = [("sample_ms", C.c_double), ("update_ms", C.c_double), ("sample_launches", C.c_uint64),
                 ("update_launches", C.c_uint64)]
@@ -295,6 +303,7 @@ SYMBOLS = {
     "mmg_selftest_btrs_pretest": (C.c_int, [C.c_int, C.c_uint64, C.c_int64, C.c_double, C.c_double, C.c_void_p]),
     "mmg_selftest_binv_pretest": (C.c_int, [C.c_int, C.c_uint64, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_void_p]),
     "mmg_selftest_keyed": (C.c_int, [C.c_int, C.POINTER(KeyedIO)]),
+    "mmg_selftest_bigk_points": (C.c_int, [C.c_int, C.POINTER(BigkPoints)]),
 }
 
 

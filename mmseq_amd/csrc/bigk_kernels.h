@@ -230,12 +230,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void
                             P = p;
                             const double np = dn * p;
                             if (np < 10.0) {
-                                // Inversion: x = 0 iff the uniform does not exceed r0 = exp(n log(1 - p)) as the sequential code computes it.  r0 is
-                                // at least 1 - n p - n 2^-54 - 2^-46 (Bernoulli's inequality; 1 - p rounds to within 2^-54, log and exp to an ulp,
-                                // |n log(1 - p)| < 20): a uniform below that bound less a margin settles x = 0 without the logarithm and the
+                                // Inversion: x = 0 iff the uniform does not exceed r0 = exp(n log(1 - p)) as the sequential code computes it: a uniform
+                                // at or below a lower bound of r0 (mmg_math.h: binv_zero_bound) settles x = 0 without the logarithm and the
                                 // exponential -- the common case for the hits of transcripts that carry (next to) nothing.  Same uniform consumed.
                                 const double u = next_unit();
-                                if (u <= 1.0 - np * (1.0 + 0x1p-10) - dn * 0x1p-49 - 0x1p-40) { x = 0; resolved = true; }
+                                if (u <= binv_zero_bound(dn, np)) { x = 0; resolved = true; }
                                 else { U = u; ph = BK_IFULL; }
                             } else ph = BK_BSET;
                         }

@@ -130,6 +130,18 @@ void host_keyed(const mmg_keyed_io &io)
     for (int64_t i = 0; i < io.n_words; ++i) keyed_words_one(io, i);
 }
 
+// mmg_selftest_bigk_points: the same convention
+void launch_selftest_bigk_points(const mmg_bigk_points &io, hipStream_t s)
+{
+    if (io.n_inv) hipLaunchKernelGGL(k_selftest_bigk_points_inv, dim3((unsigned)((io.n_inv + 255) / 256)), dim3(256), 0, s, io);
+    if (io.n_btrs) hipLaunchKernelGGL(k_selftest_bigk_points_btrs, dim3((unsigned)((io.n_btrs + 255) / 256)), dim3(256), 0, s, io);
+}
+void host_bigk_points(const mmg_bigk_points &io)
+{
+    for (int64_t i = 0; i < io.n_inv; ++i) bigk_points_inv_one(io, i);
+    for (int64_t i = 0; i < io.n_btrs; ++i) bigk_points_btrs_one(io, i);
+}
+
 // transcript tables of the synthetic generator
 void host_synth_tables(uint64_t seed, uint32_t T, double lambda, std::vector<double> &efflen, std::vector<double> &cdf,
                        std::vector<double> &len_cdf)

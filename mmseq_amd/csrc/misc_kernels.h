@@ -371,6 +371,60 @@ __global__ __launch_bounds__(256) void k_selftest_keyed_words(mmg_keyed_io a)
     if (i < a.n_words) keyed_words_one(a, i);
 }
 
+// mmg_selftest_bigk_points: the three shortcuts of k_sample_bigk (bigk_kernels.h) on caller-given points.  Host-and-device inline code like
+// the keyed self test above; the fp32 tests exist on the device only (the host instantiation reports them undecided).
+MMG_HD void bigk_points_inv_one(const mmg_bigk_points &a, int64_t i)
+{
+    const uint32_t n = a.inv_n[i];
+    const double dn = (double)n, p = a.inv_p[i], u = a.inv_u[i];
+    a.out_inv_bound[i] = binv_zero_bound(dn, dn * p);          // STEP: np = dn * p
+    uint32_t x = 0;
+    a.out_inv_x[i] = binv_exact(dn, p, u, n, x) ? (int64_t)x : -1;
+#if defined(__HIP_DEVICE_COMPILE__)
+    a.out_inv_pre[i] = binv_pretest(dn, p, u, (float)a.inv_slack);
+#else
+    a.out_inv_pre[i] = -1;
+#endif
+}
+MMG_HD void bigk_points_btrs_one(const mmg_bigk_points &a, int64_t i)
+{
+    // BSET and TRY of k_sample_bigk, the two uniforms given
+    const double dn = (double)a.btrs_n[i], p = a.btrs_p[i];
+    const double qq = 1.0 - p, spq = dsqrt(dn * p * qq);
+    const double bb = 1.15 + 2.53 * spq;
+    const double aa = -0.0873 + 0.0248 * bb + 0.01 * p;
+    const double cc = dn * p + 0.5;
+    const double vr = 0.92 - 4.2 / bb;
+    const double u = a.btrs_u[i] - 0.5;
+    const double v = a.btrs_v[i];
+    const double us = 0.5 - dabs(u);
+    const double kf = dfloor((2.0 * aa / us + bb) * u + cc);
+    int32_t reach = 2, exact = -1, pre = 0;
+    double diff = 0.0;
+    float d32 = 0.0f, e32 = 0.0f;
+    if (kf < 0.0 || kf > dn) reach = 0;
+    else if (us >= 0.07 && v <= vr) reach = 1;
+    else {
+        exact = btrs_exact_test(dn, p, kf, us, v, aa, bb, spq, &diff) ? 1 : 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+        btrs_estimate(dn, p, kf, us, v, aa, bb, spq, d32, e32);
+        pre = btrs_pretest(dn, p, kf, us, v, aa, bb, spq);
+#endif
+    }
+    a.out_btrs_kf[i] = kf; a.out_btrs_reach[i] = reach; a.out_btrs_exact[i] = exact; a.out_btrs_diff[i] = diff;
+    a.out_btrs_d32[i] = d32; a.out_btrs_e32[i] = e32; a.out_btrs_pre[i] = pre;
+}
+__global__ __launch_bounds__(256) void k_selftest_bigk_points_inv(mmg_bigk_points a)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < a.n_inv) bigk_points_inv_one(a, i);
+}
+__global__ __launch_bounds__(256) void k_selftest_bigk_points_btrs(mmg_bigk_points a)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < a.n_btrs) bigk_points_btrs_one(a, i);
+}
+
 // BTRS candidates over (n, p) drawn from the case index: n log-uniform in [n_lo, n_hi], p log-uniform in [10 / n, 1/2] (where binomial() takes
 // BTRS), one attempt each from the case's keyed stream.  counts[0] attempts that reach the exact test, [1] of them decided by btrs_pretest,
 // [2] decided AND different from the fp64 test (must stay 0), [3] accepted by the fp64 test, [4] max |estimate - fp64 difference| / bound, in millionths.

@@ -60,6 +60,8 @@ void launch_selftest_btrs_pretest(uint64_t seed, int64_t n_cases, double n_lo, d
 void launch_selftest_binv_pretest(uint64_t seed, int64_t n_cases, double n_lo, double n_hi, float slack, unsigned long long *counts /* [5], device */, hipStream_t s);
 void launch_selftest_keyed(const mmg_keyed_io &io /* its pointers: device memory */, hipStream_t s);
 void host_keyed(const mmg_keyed_io &io);
+void launch_selftest_bigk_points(const mmg_bigk_points &io /* its pointers: device memory */, hipStream_t s);
+void host_bigk_points(const mmg_bigk_points &io);
 // host instantiations of the same inline code (device == -1 paths of the self tests, synthetic transcript tables)
 void host_math(int64_t n, const double *x, double *ol, double *oe, double *os, double *orc);
 void host_philox(const uint32_t *ctr, const uint32_t *key, uint32_t *out);

@@ -559,7 +559,10 @@ MMG_HD uint32_t binomial(Src &q, uint32_t n, double p)
 //     E = sum_i c_i |x_i| / min(1, 1 + x_i) 2^-18 + (1 + |T0|) 2^-16 + 2^-14.
 // mmg_selftest_btrs_pretest runs candidates over the whole range of (n, p) through both and counts decided cases that disagree
 // with the fp64 test: none in 2.2 10^10 tests out of 6 10^10 attempts, the largest error 11 % of E (profiles/r06_btrs_pretest.txt;
-// tests/test_gpu_parity.py::test_btrs_pretest_never_contradicts_the_exact_test).  A NaN anywhere
+// tests/test_gpu_parity.py::test_btrs_pretest_never_contradicts_the_exact_test).  Pointwise, AT the threshold: with the second uniform on,
+// 1-3 ulps and 2^-1 ... 2^-40 around the largest value the fp64 test accepts (bisected), over a grid of n to 2^32 - 1, p to 1/2 and candidates
+// from the mode to six standard deviations out, 425 000 tests, 88 000 decided, none differently, the largest error 5.0 % of E below
+// n = 2^12, 4.3 % to 2^24, 4.7 % above (profiles/bigk_points.txt; tests/test_gpu_bigk_points.py).  A NaN anywhere
 // compares false twice: undecided.
 #if defined(__HIP_DEVICE_COMPILE__)
 __device__ __forceinline__ float mmg_rcpf(float x) { return __builtin_amdgcn_rcpf(x); }
@@ -642,7 +645,11 @@ MMG_HD bool btrs_exact_test(double dn, double p, double kf, double us, double vv
 // relative; every further term multiplies by s (n + 1 - x) / x with two v_rcp_f32 and four roundings: 4e-7 more per term; the sum adds an ulp of
 // itself per term; the uniform rounds to fp32 within 2^-25.  The bound takes six times that:  e_x = c~_x (2^-14 + x 2^-19) + 2^-22.
 // mmg_selftest_binv_pretest counts decided cases that differ from the fp64 search: none in 4 10^10, none with e_x at a sixteenth
-// (profiles/r06_binv_pretest.txt; tests/test_gpu_parity.py::test_binv_pretest_never_contradicts_the_fp64_search).
+// (profiles/r06_binv_pretest.txt; tests/test_gpu_parity.py::test_binv_pretest_never_contradicts_the_fp64_search).  Pointwise, AT the
+// boundaries: with the uniform on, 1-3 ulps and 2^-8 ... 2^-40 around each of the 10 315 boundaries of the fp64 search (bisected) over a grid
+// of n to 2^32 - 1 and n p from 1e-6 to 9.999, and on the two uniforms of the row stream next to it, 749 000 points: none decided differently
+// down to e_x at a sixteenth, 252 at a thirty-second (the first at n = 64, x = 5); every point with 8 e_x of room is decided
+// (profiles/bigk_points.txt; tests/test_gpu_bigk_points.py).
 #if defined(__HIP_DEVICE_COMPILE__)
 // (slack: the selftest's knob -- the bound scaled down until decided cases start to differ shows how much room it has; 1 in the sampler)
 __device__ __forceinline__ int binv_pretest(double dn, double p, double u, float slack = 1.0f)
@@ -665,6 +672,15 @@ __device__ __forceinline__ int binv_pretest(double dn, double p, double u, float
 #else
 __device__ __forceinline__ int binv_pretest(double, double, double, float = 1.0f) { return -1; }
 #endif
+// The inversion's x = 0 without the logarithm and the exponential (k_sample_bigk's STEP): x = 0 iff the uniform does not exceed
+// r0 = exp(n log(1 - p)) as binv_exact computes it, and r0 is at least 1 - n p - n 2^-54 - 2^-46 (Bernoulli's inequality; 1 - p rounds to
+// within 2^-54, log and exp to an ulp, |n log(1 - p)| < 20).  binv_zero_bound(n, n p) is that bound less a margin: a uniform at or below
+// it settles x = 0.  mmg_selftest_bigk_points returns it next to the search's outcome; tests/bigk_points_checks.py checks the claim and the
+// bound against (1 - p)^n at 80 digits over a grid of (n, p).
+MMG_HD double binv_zero_bound(double dn, double np)
+{
+    return 1.0 - np * (1.0 + 0x1p-10) - dn * 0x1p-49 - 0x1p-40;
+}
 // the fp64 search itself on one uniform (binomial()'s loop): false = the sum of the terms fell short of the uniform (binomial() starts over)
 MMG_HD bool binv_exact(double dn, double p, double u, uint32_t n, uint32_t &x_out)
 {

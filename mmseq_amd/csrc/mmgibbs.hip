@@ -1319,3 +1319,65 @@ extern "C" int mmg_selftest_keyed(int device, const mmg_keyed_io *io)
     if (e != hipSuccess) return fail(MMG_ERR_HIP, std::string("selftest_keyed: ") + hipGetErrorString(e));
     return MMG_OK;
 }
+
+extern "C" int mmg_selftest_bigk_points(int device, const mmg_bigk_points *io)
+{
+    if (!io || io->n_inv < 0 || io->n_btrs < 0 || io->n_inv > (int64_t)1 << 30 || io->n_btrs > (int64_t)1 << 30) return fail(MMG_ERR_ARG, "bad argument");
+    if (io->n_inv && (!io->inv_n || !io->inv_p || !io->inv_u || !io->out_inv_bound || !io->out_inv_x || !io->out_inv_pre))
+        return fail(MMG_ERR_ARG, "selftest_bigk_points: NULL inversion argument");
+    if (io->n_btrs && (!io->btrs_n || !io->btrs_p || !io->btrs_u || !io->btrs_v || !io->out_btrs_kf || !io->out_btrs_reach || !io->out_btrs_exact ||
+                       !io->out_btrs_diff || !io->out_btrs_d32 || !io->out_btrs_e32 || !io->out_btrs_pre))
+        return fail(MMG_ERR_ARG, "selftest_bigk_points: NULL BTRS argument");
+    // the domains on which the kernel takes each path (a NaN fails every comparison)
+    if (io->n_inv && !(io->inv_slack > 0.0 && io->inv_slack < __builtin_huge_val())) return fail(MMG_ERR_ARG, "selftest_bigk_points: inv_slack must be positive and finite");
+    for (int64_t i = 0; i < io->n_inv; ++i) {
+        const double dn = (double)io->inv_n[i], p = io->inv_p[i], u = io->inv_u[i];
+        if (!(io->inv_n[i] >= 1 && p > 0.0 && p <= 0.5 && dn * p < 10.0 && u > 0.0 && u < 1.0))
+            return fail(MMG_ERR_ARG, "selftest_bigk_points: inversion element " + std::to_string(i) + " needs n >= 1, 0 < p <= 1/2, n p < 10, 0 < u < 1");
+    }
+    for (int64_t i = 0; i < io->n_btrs; ++i) {
+        const double dn = (double)io->btrs_n[i], p = io->btrs_p[i], u = io->btrs_u[i], v = io->btrs_v[i];
+        if (!(io->btrs_n[i] >= 21 && p <= 0.5 && dn * p >= 10.0 && u > 0.0 && u < 1.0 && v > 0.0 && v < 1.0))
+            return fail(MMG_ERR_ARG, "selftest_bigk_points: BTRS element " + std::to_string(i) + " needs n >= 21, n p >= 10, p <= 1/2, 0 < u, v < 1");
+    }
+    if (device < 0) { host_bigk_points(*io); return MMG_OK; }
+    int rc = require_device(device);
+    if (rc) return rc;
+    // the descriptor again with every pointer replaced by a device buffer of the same extent (as mmg_selftest_keyed)
+    mmg_bigk_points d = *io;
+    struct Back { void *host; const void *dev; size_t bytes; };
+    std::vector<DevBuf<uint8_t>> bufs;
+    std::vector<Back> back;
+    bufs.reserve(20);
+    hipError_t e = hipSuccess;
+    auto in = [&](auto *&f, int64_t count) {
+        if (e != hipSuccess) return;
+        const void *h = f;
+        bufs.emplace_back();
+        e = bufs.back().alloc((size_t)count * sizeof(*f));
+        if (e == hipSuccess) e = hipMemcpy(bufs.back().get(), h, (size_t)count * sizeof(*f), hipMemcpyHostToDevice);
+        f = reinterpret_cast<std::remove_reference_t<decltype(f)>>(bufs.back().get());
+    };
+    auto out = [&](auto *&f, int64_t count) {
+        if (e != hipSuccess) return;
+        bufs.emplace_back();
+        e = bufs.back().alloc((size_t)count * sizeof(*f));
+        back.push_back(Back{f, bufs.back().get(), (size_t)count * sizeof(*f)});
+        f = reinterpret_cast<std::remove_reference_t<decltype(f)>>(bufs.back().get());
+    };
+    if (const int64_t n = d.n_inv) {
+        in(d.inv_n, n); in(d.inv_p, n); in(d.inv_u, n);
+        out(d.out_inv_bound, n); out(d.out_inv_x, n); out(d.out_inv_pre, n);
+    }
+    if (const int64_t n = d.n_btrs) {
+        in(d.btrs_n, n); in(d.btrs_p, n); in(d.btrs_u, n); in(d.btrs_v, n);
+        out(d.out_btrs_kf, n); out(d.out_btrs_reach, n); out(d.out_btrs_exact, n); out(d.out_btrs_diff, n);
+        out(d.out_btrs_d32, n); out(d.out_btrs_e32, n); out(d.out_btrs_pre, n);
+    }
+    if (e == hipSuccess) { launch_selftest_bigk_points(d, 0); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    for (const Back &b : back)
+        if (e == hipSuccess) e = hipMemcpy(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(MMG_ERR_HIP, std::string("selftest_bigk_points: ") + hipGetErrorString(e));
+    return MMG_OK;
+}

@@ -704,3 +704,32 @@ def selftest_keyed_words(w0, w1, t, device=-1):
                       out_target=_ptr(out["target"]))
     _keyed(device, io)
     return out
+
+
+def selftest_bigk_inversion(n, p, u, slack=1.0, device=-1):
+    """mmg_selftest_bigk_points, inversion: dict(bound: binv_zero_bound(n, n p), the STEP shortcut's threshold; x: the fp64 search's
+    outcome on the uniform u, -1 where it fell short; pre: the fp32 search's outcome, -1 where undecided and on the host) of element i
+    (scalars broadcast).  device -1: the host instantiation."""
+    n, p, u = np.broadcast_arrays(np.asarray(n, np.uint32), np.asarray(p, np.float64), np.asarray(u, np.float64))
+    n, p, u = [np.ascontiguousarray(a).ravel() for a in (n, p, u)]
+    out = dict(bound=np.empty(n.size), x=np.empty(n.size, np.int64), pre=np.empty(n.size, np.int32))
+    io = _lib.BigkPoints(n_inv=n.size, inv_n=_ptr(n), inv_p=_ptr(p), inv_u=_ptr(u), inv_slack=float(slack), out_inv_bound=_ptr(out["bound"]),
+                         out_inv_x=_ptr(out["x"]), out_inv_pre=_ptr(out["pre"]))
+    check(_lib.load().mmg_selftest_bigk_points(int(device), C.byref(io)))
+    return out
+
+
+def selftest_bigk_btrs(n, p, u, v, device=-1):
+    """mmg_selftest_bigk_points, BTRS: one attempt with the uniforms (u, v) at (n, p): dict(kf, reach: 0 outside [0, n] / 1 squeeze / 2
+    exact test; and where reach is 2: exact, diff: the fp64 test and its ub - v; d32, e32, pre: the fp32 estimate, its bound and its
+    verdict, 0 on the host) (include/mmgibbs.h)."""
+    n, p, u, v = np.broadcast_arrays(np.asarray(n, np.uint32), np.asarray(p, np.float64), np.asarray(u, np.float64), np.asarray(v, np.float64))
+    n, p, u, v = [np.ascontiguousarray(a).ravel() for a in (n, p, u, v)]
+    m = n.size
+    out = dict(kf=np.empty(m), reach=np.empty(m, np.int32), exact=np.empty(m, np.int32), diff=np.empty(m), d32=np.empty(m, np.float32),
+               e32=np.empty(m, np.float32), pre=np.empty(m, np.int32))
+    io = _lib.BigkPoints(n_btrs=m, btrs_n=_ptr(n), btrs_p=_ptr(p), btrs_u=_ptr(u), btrs_v=_ptr(v), out_btrs_kf=_ptr(out["kf"]),
+                         out_btrs_reach=_ptr(out["reach"]), out_btrs_exact=_ptr(out["exact"]), out_btrs_diff=_ptr(out["diff"]),
+                         out_btrs_d32=_ptr(out["d32"]), out_btrs_e32=_ptr(out["e32"]), out_btrs_pre=_ptr(out["pre"]))
+    check(_lib.load().mmg_selftest_bigk_points(int(device), C.byref(io)))
+    return out

@@ -36,6 +36,7 @@ def test_struct_layouts_match_header():
     assert C.sizeof(_lib.Timing) == 32
     assert C.sizeof(_lib.ProblemInfo) == 112
     assert C.sizeof(_lib.KeyedIO) == 208
+    assert C.sizeof(_lib.BigkPoints) == 160
 
 
 def test_no_cpu_fallback_without_device():
@@ -72,6 +73,21 @@ def test_argument_validation_happens_before_device_use():
         for io in (_lib.KeyedIO(n_math=3, x=x.ctypes.data), _lib.KeyedIO(n_streams=1), _lib.KeyedIO(n_words=-1)):
             assert lib.mmg_selftest_keyed(device, C.byref(io)) == 1, device
     assert lib.mmg_selftest_keyed(-1, C.byref(_lib.KeyedIO())) == 0          # nothing asked, nothing done
+    # mmg_selftest_bigk_points: the same rule, and every element inside the domain on which the kernel takes that path
+    for device in (-1, 0, 99):
+        assert lib.mmg_selftest_bigk_points(device, None) == 1
+        for io in (_lib.BigkPoints(n_inv=3, inv_p=x.ctypes.data), _lib.BigkPoints(n_btrs=1), _lib.BigkPoints(n_inv=-1)):
+            assert lib.mmg_selftest_bigk_points(device, C.byref(io)) == 1, device
+        for n, p, u, slack in ((0, .1, .5, 1), (5, 0., .5, 1), (5, .6, .5, 1), (100, .1, .5, 1), (5, .1, 0., 1), (5, .1, 1., 1), (5, .1, .5, 0),
+                               (5, float("nan"), .5, 1), (5, .1, float("nan"), 1)):
+            with pytest.raises(MMGError) as e:
+                gibbs.selftest_bigk_inversion(n, p, u, slack=slack, device=device)
+            assert e.value.code == 1 and "selftest_bigk_points" in str(e.value), (n, p, u, slack)
+        for n, p, u, v in ((20, .5, .5, .5), (100, .05, .5, .5), (100, .6, .5, .5), (100, .3, 0., .5), (100, .3, .5, 1.), (100, .3, .5, float("nan"))):
+            with pytest.raises(MMGError) as e:
+                gibbs.selftest_bigk_btrs(n, p, u, v, device=device)
+            assert e.value.code == 1 and "BTRS element 0" in str(e.value), (n, p, u, v)
+    assert lib.mmg_selftest_bigk_points(-1, C.byref(_lib.BigkPoints())) == 0
 
 
 def test_host_instantiation_of_library_math_equals_oracle(orc):
