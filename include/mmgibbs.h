@@ -89,7 +89,8 @@ extern "C" {
  *      likelihood-ratio test (mmg_diff_lrt_*) with its permutation null (mmg_diff_lrt_perm_*), and the posterior fold change between
  *      two samples from all pairs of their draws (mmg_fold_*, MMG_OPT_FOLD_SLAB), and the posterior distances and correlations
  *      between samples from their joint draws (mmg_sim_*, MMG_OPT_SIM_CHUNK), and the pointwise self test of the binomial chain's
- *      three shortcuts (mmg_selftest_bigk_points).
+ *      three shortcuts (mmg_selftest_bigk_points), and the posterior isoform usage within groups of transcripts -- dominant-isoform
+ *      probabilities and usage entropy (mmg_isoform_*, MMG_OPT_ISO_SLAB).
  *      mmg_sampler_create refuses chains beyond 2^24: the Gamma stream's key holds 24 bits of the chain index (the row stream all 32), so
  *      chain 2^24 + c would redraw mu from chain c's uniforms.  No chain that ran before is changed by the check. */
 /* Layout.  The model does not care about the order of rows or the numbering of transcripts (src/mmseq.cpp:399-418 uses
@@ -504,7 +505,8 @@ enum {
     MMG_OPT_PAIRS_SLAB = 18,       /* v >= 1: at most v pairs per slab of mmg_pairs_create / _of_traces (slab edges on small inputs)             */
     MMG_OPT_FOLD_SLAB = 19,        /* v >= 1: at most v features per slab of mmg_fold_create / _of_traces (slab edges on small inputs)           */
     MMG_OPT_SIM_CHUNK = 20,        /* v >= 1: v features per chunk of mmg_sim_run's Gram kernel (chunk edges on small inputs; read by mmg_sim_create) */
-    MMG_OPT_COUNT_ = 21
+    MMG_OPT_ISO_SLAB = 21,         /* v >= 1: at most v groups per slab of mmg_isoform_create / _of_traces (slab edges on small inputs)          */
+    MMG_OPT_COUNT_ = 22
 };
 int mmg_selftest_option(int option, int value);
 /* What the library holds: counts[3] = device buffers, streams, events (tests: every call gives back what it acquired). */
@@ -835,6 +837,70 @@ int mmg_sim_get(mmg_sim *h, double *mean_D, double *ss_D, double *q_D, double *m
  * and marks + 2048 T C U of partial tiles + 8 T (S S + S + 1) of G, m, n + 8 + 1057 P of summaries (64 ranks) + 4 S S + 256. */
 int mmg_sim_device_bytes(mmg_sim *h, uint64_t *bytes);
 void mmg_sim_destroy(mmg_sim *h);
+
+/* ---- isoform usage within groups of transcripts of one sample: dominant-isoform probabilities and usage entropy ----------
+ * Isoforms of a gene share their reads, so their draws are strongly anti-correlated, and which one is the major isoform, or whether
+ * the gene is spread over several, cannot be read off the marginal summaries: it needs the joint draws of the group's members.
+ * Group g is the ordered list member[ptr[g] .. ptr[g + 1]) of K >= 1 distinct members, laid out as mmg_summary_desc's genes are; a
+ * member < n is the caller's transcript, n + v isoform without hits v (its simulated trace).  A member may be in several groups, not
+ * twice in one.  Up to 8 thresholds theta_q, each finite in [0, 1); up to 64 zero-based ranks, a rank >= S gives NaN for that rank
+ * alone; 1 <= S <= 4096 kept samples of one chain; n_groups >= 1.
+ * Per sample s, with x_j = the trace of the member at position j, every operation one IEEE double operation rounded once, in this
+ * order:
+ *   valid: every x_j is finite and >= 0, and T_s is finite and > 0.  If any sample of a group is not valid the group's status byte
+ *       gets bit 0, every floating-point output of the group is NaN (rows included; its top / second rows are 0xffffffff) and every
+ *       count of the group and of its members is 0 (major is then position 0).  The check comes before the logarithms and the sort;
+ *       other groups are unaffected.
+ *   T_s = ((0.0 + x_0) + x_1) + ... in list order: the order of the summary's gene sums, so the bits of the gene's trace row.
+ *   top_s = the smallest j with x_j = the maximum (the draws are compared, never the proportions); second_s = the smallest j != top_s
+ *       with x_j = the maximum over j != top_s, 0xffffffff when K = 1.
+ *   p_j = x_j / T_s (the summary's proportion), P_s = x_top / T_s.
+ *   H_s: a = 0.0; for j ascending: if (p_j > 0) a = a + p_j * log(p_j) (the library's log); H_s = -a, -0.0 stored as +0.0.
+ *   above_s[j][q] = x_j > theta_q * T_s.
+ * Per member of a group, exact integers: n_top[j] = #{s: top_s = j}, n_second[j] alike, n_above[j][q].
+ * Per group: major = the smallest j with the largest n_top (a position in the list); n_distinct = #{j: n_top[j] > 0};
+ * mean_H = sum H / S, ss_H = sum (H - mean_H)^2, mean_P, ss_P alike, every sum in the samples' order as a wave with one lane per
+ * sample adds (lane l adds its samples l, l + 64, ... ascending from 0.0, the 64 partial sums are folded by halving, as mmg_pairs_*);
+ * q_H, q_P [group][n_ranks]: the order statistics of H and of P at the ranks.  The caller derives p_top = n_top / S,
+ * sd = sqrt(ss / (S - 1)) and the effective number of isoforms exp(mean_H).  For the same group in two samples A and B, which are
+ * independent given their reads, P(their major isoforms differ) = 1 - sum_j nA_top[j] nB_top[j] / (S_A S_B) over all pairs of draws:
+ * host arithmetic on the counts.  No floating-point atomics; counts are population counts of ballots: reruns and any slab cut give the
+ * same bits.  tests/isoforms_ref.py, DESIGN.md section 18.  Additive in ABI version 8. */
+typedef struct mmg_isoform mmg_isoform;
+typedef struct mmg_isoform_desc {
+    uint32_t n_groups;                                /* at least 1 */
+    const uint64_t *ptr; const uint32_t *member;      /* n_groups + 1 offsets from 0, increasing */
+    uint32_t n_thresholds; const double *threshold;   /* at most 8, each finite in [0, 1) */
+    uint32_t n_ranks; const uint32_t *rank;           /* at most 64, zero-based */
+} mmg_isoform_desc;
+/* After mmg_summary_finish (or _create) of a summary q of sampler s (MMG_ERR_STATE before): the chain is the summary's, and so are the
+ * isoforms without hits (their simulated traces are drawn again, the same bits).  MMG_ERR_ARG, with a message that names the
+ * argument, the group and the member, before the device is touched: a NULL pointer, n_groups == 0, an empty group, a member twice in
+ * a group, a member out of range, a threshold outside [0, 1) or not finite, more than 8 thresholds, more than 64 ranks, S outside
+ * [1, 4096].  The sampler must outlive the handle. */
+int mmg_isoform_create(mmg_sampler *s, mmg_summary *q, const mmg_isoform_desc *d, mmg_isoform **out);
+/* The same from host traces, series-major traces[member * S + s]; members < n_series only. */
+int mmg_isoform_of_traces(int device, uint32_t S, uint32_t n_series, const double *traces, const mmg_isoform_desc *d, mmg_isoform **out);
+/* n_top, n_second: one entry per entry of member[], in its flat order; n_above: [entry][n_thresholds].  Any output may be NULL; served
+ * from the host. */
+int mmg_isoform_get_members(mmg_isoform *h, uint32_t *n_top, uint32_t *n_second, uint32_t *n_above);
+/* status, major, n_distinct, mean_H, ss_H, mean_P, ss_P: [n_groups]; q_H, q_P: [n_groups][n_ranks].  Any output may be NULL; served
+ * from the host: no device work. */
+int mmg_isoform_get_groups(mmg_isoform *h, uint8_t *status, uint32_t *major, uint32_t *n_distinct, double *mean_H, double *ss_H, double *mean_P,
+                           double *ss_P, double *q_H, double *q_P);
+/* top, second, H, P of the groups [first, first + count), [(g - first) * S + s]: computed again on the device, the same bits as at
+ * creation.  Any output may be NULL. */
+int mmg_isoform_get_rows(mmg_isoform *h, uint32_t first, uint32_t count, uint32_t *top, uint32_t *second, double *H, double *P);
+/* What the handle holds between calls: 8 (n_groups + 1) + 4 (entries of member[]) bytes of lists; from a sampler also 4 bytes per
+ * distinct member of each slab (summed over the slabs) and 16 bytes per isoform without hits of the summary; from host traces also
+ * 8 n_series S.  The groups are cut into slabs of consecutive groups: a slab ends in front of the group that would bring its groups
+ * over gcap = max(1, min(n_groups, 256 MiB / (16 S), MMG_OPT_ISO_SLAB if set)) or, from a sampler, its distinct members over
+ * max(1, 256 MiB / (8 S)); a slab holds at least one group.  While creation or mmg_isoform_get_rows runs, with Gx the most groups and
+ * Mx the most distinct members of a slab, on top of that: 16 S Gx of H and P rows (get_rows: min(Gx, count) for Gx, and 4 S of that
+ * for each of top and second that is asked for), from a sampler 8 S Mx of gathered series, and at creation
+ * 4 (2 + n_thresholds) (entries of member[]) of counters + Gx (41 + 16 n_ranks) of results + 4 n_ranks. */
+int mmg_isoform_device_bytes(mmg_isoform *h, uint64_t *bytes);
+void mmg_isoform_destroy(mmg_isoform *h);
 
 /* ---- mmdiff: Bayesian model selection between two linear models per feature -------------------------------------------
  * src/bms.cpp driven as src/mmdiff.cpp:744-866: per feature an independent MCMC over both models with pseudopriors, the model

@@ -39,7 +39,7 @@ class MMGError(RuntimeError):
 
 LAYOUT_CANONICAL, LAYOUT_KEEP_ROWS = 0, 1
 # mmg_selftest_option ids
-OPT_SAMPLE_KERNEL, OPT_FORCE_IDX64, OPT_SELL_WAVES_PER_CU, OPT_EM_KERNEL, OPT_EM_GRID, OPT_FUSE_CHAINS, OPT_CNT_REPLICAS, OPT_GROUP_FAIL, OPT_DERIVE_ORDER, OPT_WIRE_CHECK, OPT_BIGK_PER_WAVE, OPT_BIGK_SIDE_STREAM, OPT_FAIL_ALLOC, OPT_CONV_SLAB, OPT_DIFF_TRACE_ROWS, OPT_ASSIGN_WAVES, OPT_CONTRAST_SLAB, OPT_POOL_SLAB, OPT_PAIRS_SLAB, OPT_FOLD_SLAB, OPT_SIM_CHUNK = range(21)
+OPT_SAMPLE_KERNEL, OPT_FORCE_IDX64, OPT_SELL_WAVES_PER_CU, OPT_EM_KERNEL, OPT_EM_GRID, OPT_FUSE_CHAINS, OPT_CNT_REPLICAS, OPT_GROUP_FAIL, OPT_DERIVE_ORDER, OPT_WIRE_CHECK, OPT_BIGK_PER_WAVE, OPT_BIGK_SIDE_STREAM, OPT_FAIL_ALLOC, OPT_CONV_SLAB, OPT_DIFF_TRACE_ROWS, OPT_ASSIGN_WAVES, OPT_CONTRAST_SLAB, OPT_POOL_SLAB, OPT_PAIRS_SLAB, OPT_FOLD_SLAB, OPT_SIM_CHUNK, OPT_ISO_SLAB = range(22)
 
 
 class ProblemDesc(C.Structure):
@@ -72,6 +72,11 @@ class SummaryDesc(C.Structure):
 class ContrastDesc(C.Structure):
     _fields_ = [("n_contrasts", C.c_uint32), ("num_ptr", C.c_void_p), ("num_member", C.c_void_p), ("den_ptr", C.c_void_p),
                 ("den_member", C.c_void_p), ("n_percentiles", C.c_uint32), ("percentile_index", C.c_void_p)]
+
+
+class IsoformDesc(C.Structure):
+    _fields_ = [("n_groups", C.c_uint32), ("ptr", C.c_void_p), ("member", C.c_void_p), ("n_thresholds", C.c_uint32), ("threshold", C.c_void_p),
+                ("n_ranks", C.c_uint32), ("rank", C.c_void_p)]
 
 
 class Config(C.Structure):
@@ -269,6 +274,13 @@ SYMBOLS = {
     "mmg_sim_get": (C.c_int, [C.c_void_p] * 10),
     "mmg_sim_device_bytes": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mmg_sim_destroy": (None, [C.c_void_p]),
+    "mmg_isoform_create": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(IsoformDesc), C.POINTER(C.c_void_p)]),
+    "mmg_isoform_of_traces": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(IsoformDesc), C.POINTER(C.c_void_p)]),
+    "mmg_isoform_get_members": (C.c_int, [C.c_void_p] * 4),
+    "mmg_isoform_get_groups": (C.c_int, [C.c_void_p] * 10),
+    "mmg_isoform_get_rows": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmg_isoform_device_bytes": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mmg_isoform_destroy": (None, [C.c_void_p]),
     "mmg_convergence_create": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "mmg_convergence_get": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmg_convergence_destroy": (None, [C.c_void_p]),

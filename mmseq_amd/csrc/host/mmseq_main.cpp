@@ -39,6 +39,7 @@
 
 #include "../../../include/mmgibbs.h"
 #include "contrasts_file.hpp"
+#include "iso_thresholds.hpp"
 #include "hitsio.hpp"
 #include "huffenc.hpp"
 #include "numerics.hpp"
@@ -92,6 +93,11 @@ static void printUsage(ostream &out)
         << "  -pairs             also write output_base.pairs: for every two transcripts that share a hit set the posterior correlation of" << endl
         << "                     their log mu, the sd of each and of the log of their sum, from chain 0's samples (one device only)" << endl
         << "  -pairs_maxset INT  with -pairs: hit sets of more transcripts than this contribute no pairs (default: 16)" << endl
+        << "  -isoforms          also write output_base.isoforms and output_base.gene.isoforms: per gene, from the joint draws of its isoforms" << endl
+        << "                     in chain 0's samples, the probability that each isoform is the major one, the entropy of the usage and the" << endl
+        << "                     share of the top isoform (one device only)" << endl
+        << "  -iso_thresholds STR  with -isoforms: comma-separated shares of the gene in [0, 1), at most 8; per isoform the probability that" << endl
+        << "                     it carries more than each (default: \"0.1,0.5\")" << endl
         << endl;
 }
 
@@ -143,6 +149,7 @@ using PooledSummary = Owned<mmg_pooled, mmg_pooled_destroy>;
 using Assign = Owned<mmg_assign, mmg_assign_destroy>;
 using Contrast = Owned<mmg_contrast, mmg_contrast_destroy>;
 using Pairs = Owned<mmg_pairs, mmg_pairs_destroy>;
+using Isoform = Owned<mmg_isoform, mmg_isoform_destroy>;
 // handles of one kind, one per device, destroyed together in order; reads as the array of raw handles the calls take
 template <class T, void (*Destroy)(T *)> struct HandleSet {
     vector<T *> h;
@@ -377,6 +384,8 @@ struct Options {
     string contrasts_file;
     bool pairs = false;
     int pairs_maxset = 16;
+    bool isoforms = false;
+    vector<double> iso_thresholds = {0.1, 0.5};
     string hits_file, output_base;
 };
 
@@ -385,6 +394,8 @@ static Options parse_options(int argc, char **argv)
 {
     Options o;
     vector<string> percentile_fields;
+    string iso_thresholds_text;
+    bool iso_thresholds_given = false;
     const CliOption options[] = {
         {"-alpha", CliOption::REAL, &o.alpha},        {"-beta", CliOption::REAL, &o.beta},
         {"-max_em_iter", CliOption::INT, &o.max_em_iter}, {"-epsilon", CliOption::REAL, &o.epsilon},
@@ -396,7 +407,8 @@ static Options parse_options(int argc, char **argv)
         {"-convergence", CliOption::FLAG, &o.convergence}, {"-assign", CliOption::FLAG, &o.assign},
         {"-contrasts", CliOption::TEXT, &o.contrasts_file}, {"-pool", CliOption::FLAG, &o.pool},
         {"-pairs", CliOption::FLAG, &o.pairs},        {"-pairs_maxset", CliOption::INT, &o.pairs_maxset},
-        {"-h", CliOption::HELP, nullptr},           {"-help", CliOption::HELP, nullptr},       {"--help", CliOption::HELP, nullptr},
+        {"-isoforms", CliOption::FLAG, &o.isoforms},  {"-iso_thresholds", CliOption::TEXT, &iso_thresholds_text},
+        {"-h", CliOption::HELP, nullptr},          {"-help", CliOption::HELP, nullptr},       {"--help", CliOption::HELP, nullptr},
         {"-v", CliOption::VERSION, nullptr},        {"-version", CliOption::VERSION, nullptr}, {"--version", CliOption::VERSION, nullptr},
     };
     auto usage_error = [&](const string &msg) { cerr << msg << "\n"; printUsage(cerr); exit(1); };
@@ -416,7 +428,7 @@ static Options parse_options(int argc, char **argv)
         const char *value = argv[pos + 1];
         if (opt->kind == CliOption::REAL) *(double *)opt->target = strtod(value, NULL);
         else if (opt->kind == CliOption::INT) *(int *)opt->target = atoi(value);
-        else if (opt->kind == CliOption::TEXT) *(string *)opt->target = value;
+        else if (opt->kind == CliOption::TEXT) { *(string *)opt->target = value; if (opt->target == &iso_thresholds_text) iso_thresholds_given = true; }
         else *(vector<string> *)opt->target = split_fields(value, ',');
         pos += 2;
     }
@@ -448,6 +460,15 @@ static Options parse_options(int argc, char **argv)
     check(!(!o.contrasts_file.empty() && o.gpus > 1), "Error: -contrasts reads the chain's trace on one device: it cannot be combined with -gpus > 1.\n");
     check(!(o.pairs && o.gpus > 1), "Error: -pairs reads the chain's trace on one device: it cannot be combined with -gpus > 1.\n");
     check(o.pairs_maxset >= 2, "Error: -pairs_maxset must be at least 2.\n");
+    // the pass reads chain 0's trace where one sampler holds it, a group's samples in the lanes of one wave and the LDS of one workgroup
+    check(!(o.isoforms && o.gpus > 1), "Error: -isoforms reads the chain's trace on one device: it cannot be combined with -gpus > 1.\n");
+    check(!(o.isoforms && trace_length > 4096), "Error: -isoforms takes traces of at most 4096 samples.\n");
+    check(!(iso_thresholds_given && !o.isoforms), "Error: -iso_thresholds needs -isoforms.\n");
+    if (iso_thresholds_given) {
+        string error;
+        const bool parsed = isocli::parse_thresholds(iso_thresholds_text, o.iso_thresholds, error);
+        check(parsed, "Error: " + error + "\n");
+    }
     check(is_power_of_two((unsigned)trace_length), "Error: gibbs_iter/gibbs_ss must be a power of 2.\n");
     return o;
 }
@@ -1760,6 +1781,104 @@ static void write_pairs(const Options &opt, const Header &hdr, const Hits &hits,
     if (!ofs) fatal("cannot write " + opt.output_base + ".pairs");
 }
 
+// ---- -isoforms: .isoforms and .gene.isoforms.  The groups are the genes of the summary (the hits header's, isoforms without hits as
+//      their simulated traces), the samples chain 0's trace_length kept samples -- the samples the .mmseq summaries are taken over --
+//      and everything per sample happens on the device (mmg_isoform_*).  From its counts and sums come, here: the shares count / S,
+//      sd = sqrt(ss / (S - 1)), the effective number of isoforms exp(mean entropy), and an isoform's rank in its gene by the number
+//      of samples it tops (the earlier of equals first).  A gene with a draw that is not valid prints NA and nan, and its status.
+static void write_isoforms(const Options &opt, const Header &hdr, const SeriesLayout &layout, const Chains &ch)
+{
+    const size_t G = layout.gptr.size() - 1, NM = layout.gmem.size(), nq = opt.iso_thresholds.size(), nP = opt.percentiles.size();
+    vector<uint32_t> n_top(NM), n_second(NM), n_above(max<size_t>(NM * nq, 1)), major(G), n_distinct(G);
+    vector<uint8_t> status(G);
+    vector<double> mean_H(G), ss_H(G), mean_P(G), ss_P(G), q_H(max<size_t>(G * nP, 1)), q_P(max<size_t>(G * nP, 1));
+    if (G) {
+        const vector<uint32_t> ranks(layout.pind.begin(), layout.pind.end());
+        mmg_isoform_desc d;
+        memset(&d, 0, sizeof d);
+        d.n_groups = (uint32_t)G; d.ptr = layout.gptr.data(); d.member = layout.gmem.data();
+        d.n_thresholds = (uint32_t)nq; d.threshold = opt.iso_thresholds.data();
+        d.n_ranks = (uint32_t)ranks.size(); d.rank = ranks.data();
+        mmg_isoform *raw = nullptr;
+        MMG_TRY(mmg_isoform_create(ch.smp(), ch.summ.get(), &d, &raw));
+        Isoform owned(raw);
+        MMG_TRY(mmg_isoform_get_members(raw, n_top.data(), n_second.data(), n_above.data()));
+        MMG_TRY(mmg_isoform_get_groups(raw, status.data(), major.data(), n_distinct.data(), mean_H.data(), ss_H.data(), mean_P.data(), ss_P.data(),
+                                       q_H.data(), q_P.data()));
+    }
+    const double S = (double)trace_length;
+    auto comment = [&](ostream &o) {
+        o << "# Isoform usage from the joint draws of a gene's isoforms: S = " << trace_length << " kept samples of chain 0; thresholds: ";
+        for (size_t q = 0; q < nq; ++q) o << opt.iso_thresholds[q] << (q + 1 < nq ? "," : "");
+        o << endl;
+    };
+    // where a transcript sits: its gene and its entry of the flat member list (the order series_layout built them in)
+    unordered_map<string, pair<uint32_t, uint64_t>> where;
+    where.reserve(NM);
+    vector<uint32_t> rank(NM, 0);
+    {
+        size_t g = 0;
+        uint64_t at = 0;
+        vector<uint32_t> order;
+        for (auto &gt : hdr.gene2transcripts) {
+            for (auto &name : gt.second) where[name] = {(uint32_t)g, at++};
+            const uint64_t b = layout.gptr[g], K = layout.gptr[g + 1] - b;
+            order.resize(K);
+            for (uint32_t j = 0; j < K; ++j) order[j] = j;
+            stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return n_top[b + x] > n_top[b + y]; });
+            for (uint32_t r = 0; r < K; ++r) rank[b + order[r]] = r + 1;
+            ++g;
+        }
+    }
+    ofstream ofs((opt.output_base + ".isoforms").c_str());
+    comment(ofs);
+    ofs << "feature_id\tgene_id\tn_isoforms\trank_in_gene\tp_major\tp_second";
+    for (size_t q = 0; q < nq; ++q) ofs << "\tp_above_" << opt.iso_thresholds[q];
+    ofs << "\n";
+    for (auto &name : hdr.transcriptList) {
+        auto it = where.find(name);
+        if (it == where.end()) {   // a transcript the header puts in no gene
+            ofs << name << "\tNA\t0\tNA\tnan\tnan";
+            for (size_t q = 0; q < nq; ++q) ofs << "\tnan";
+            ofs << "\n";
+            continue;
+        }
+        const uint32_t g = it->second.first;
+        const uint64_t j = it->second.second;
+        const bool ok = status[g] == 0;
+        ofs << name << "\t" << layout.gene_ids[g] << "\t" << layout.gptr[g + 1] - layout.gptr[g] << "\t";
+        if (ok) ofs << rank[j]; else ofs << "NA";
+        ofs << "\t" << (ok ? n_top[j] / S : NAN) << "\t" << (ok ? n_second[j] / S : NAN);
+        for (size_t q = 0; q < nq; ++q) ofs << "\t" << (ok ? n_above[j * nq + q] / S : NAN);
+        ofs << "\n";
+    }
+    ofs.close();
+    if (!ofs) fatal("cannot write " + opt.output_base + ".isoforms");
+
+    ofstream ofg((opt.output_base + ".gene.isoforms").c_str());
+    comment(ofg);
+    ofg << "gene_id\tn_isoforms\tmajor_id\tp_major\tn_distinct\tentropy\tentropy_sd\teff_isoforms\tmax_prop\tmax_prop_sd\t";
+    for (const char *what : {"percentiles_entropy", "percentiles_max_prop"}) {
+        ofg << what;
+        for (size_t i = 0; i < nP; i++) ofg << opt.percentiles[i] << (i == nP - 1 ? "\t" : ",");
+    }
+    ofg << "status\n";
+    size_t g = 0;
+    for (auto &gt : hdr.gene2transcripts) {
+        const bool ok = status[g] == 0;
+        const uint64_t b = layout.gptr[g];
+        ofg << gt.first << "\t" << gt.second.size() << "\t" << (ok ? gt.second[major[g]] : string("NA")) << "\t" << (ok ? n_top[b + major[g]] / S : NAN) << "\t"
+            << n_distinct[g] << "\t" << mean_H[g] << "\t" << sqrt(ss_H[g] / (S - 1.0)) << "\t" << exp(mean_H[g]) << "\t" << mean_P[g] << "\t"
+            << sqrt(ss_P[g] / (S - 1.0)) << "\t";
+        for (const vector<double> *qv : {&q_H, &q_P})
+            for (size_t i = 0; i < nP; i++) ofg << (*qv)[g * nP + i] << (i == nP - 1 ? "\t" : ",");
+        ofg << (int)status[g] << "\n";
+        ++g;
+    }
+    ofg.close();
+    if (!ofg) fatal("cannot write " + opt.output_base + ".gene.isoforms");
+}
+
 static void print_parameters(const Options &opt, int max_threads)
 {
     cout << "Running mmseq with parameters:\n"
@@ -1797,6 +1916,10 @@ static void print_output_files(const Options &opt)
              << endl;
     if (!opt.contrasts_file.empty()) cout << "  " << opt.output_base << ".contrasts.mmseq" << endl << endl;
     if (opt.pairs) cout << "  " << opt.output_base << ".pairs" << endl << endl;
+    if (opt.isoforms)
+        cout << "  " << opt.output_base << ".isoforms" << endl
+             << "  " << opt.output_base << ".gene.isoforms" << endl
+             << endl;
     if (opt.debug) {
         cout << endl
              << "  " << opt.output_base << ".trace_em.gz" << endl
@@ -1893,8 +2016,13 @@ static int run(int argc, char **argv)
             stage.mark(before_pairs);
             write_pairs(opt, hdr, hits, ch, pair_list);
         }
+        const char *before_isoforms = opt.pairs ? "pairs" : before_pairs;
+        if (opt.isoforms) {
+            stage.mark(before_isoforms);
+            write_isoforms(opt, hdr, layout, ch);
+        }
         print_output_files(opt);
-        stage.mark(opt.pairs ? "pairs" : before_pairs);
+        stage.mark(opt.isoforms ? "isoform usage" : before_isoforms);
         // (the writers fetch the last 1/64 of the rows behind the loop's last check: a failure there -- a HIP error in a row fetch --
         // would leave a valid but truncated trace file; it ends the run like any other)
         writers.finish();
