@@ -9,6 +9,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "mmg_series.h"   // lane_fold
 
 namespace mmg {
 
@@ -55,19 +56,6 @@ __device__ inline uint64_t asg_first_row_at(const uint64_t *row_ptr, uint64_t n_
         else hi = mid;
     }
     return lo;
-}
-
-// x[i] + x[i + 32], then 16, 8, 4, 2, 1: lane 0 ends with the sum in the halving order (the lanes above the live half read
-// themselves or dead lanes: their values are never used)
-__device__ inline double asg_fold(double x)
-{
-    x = x + __shfl_down(x, 32, 64);
-    x = x + __shfl_down(x, 16, 64);
-    x = x + __shfl_down(x, 8, 64);
-    x = x + __shfl_down(x, 4, 64);
-    x = x + __shfl_down(x, 2, 64);
-    x = x + __shfl_down(x, 1, 64);
-    return x;
 }
 
 __global__ __launch_bounds__(ASG_BLOCK) void k_assign(AsgArgs a)
@@ -121,7 +109,7 @@ __global__ __launch_bounds__(ASG_BLOCK) void k_assign(AsgArgs a)
 #pragma unroll
             for (uint32_t j = 0; j < ASG_REG_HITS; ++j) {
                 if (j < L) {                       // (L is the wave's: every lane takes part in the fold)
-                    const double sum = asg_fold(A[j]);
+                    const double sum = lane_fold(A[j]);
                     if (lane == 0) a.P[b + j] = sum / div;
                 }
             }
@@ -148,7 +136,7 @@ __global__ __launch_bounds__(ASG_BLOCK) void k_assign(AsgArgs a)
                         A = A + (rr < 0.0 ? flat : src[s] * rr);
                     }
                 }
-                const double sum = asg_fold(A);
+                const double sum = lane_fold(A);
                 if (lane == 0) a.P[j] = sum / div;
             }
         }

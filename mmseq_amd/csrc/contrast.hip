@@ -7,8 +7,10 @@
 // its series.  Per slab: the distinct members of its contrasts are gathered out of the chain's sample-major trace (isoforms without
 // hits: drawn) into a series-major matrix, a wave per contrast walks its two lists over that matrix, and the summary kernel takes
 // the slab's series one workgroup each.  From host traces the uploaded matrix is series-major already and nothing is gathered.
+// MemberSource (mmg_host.h), where those members come from, is defined here; iso.hip and pairs.hip use it as well.
 #include "mmg_host.h"
 #include "mmg_launch.h"
+#include "mmg_series.h"   // next_pow2
 
 #include <algorithm>
 #include <memory>
@@ -22,9 +24,7 @@ static constexpr uint32_t CONTRAST_WS_GROUPS = 1024;
 // Members are destroyed in reverse declaration order: the destructor waits for `st`, then the buffers go, and the stream last.
 struct mmg_contrast {
     DevStream st;
-    int device = 0;
-    uint32_t C = 0, S = 0, n = 0, nv = 0, np = 0, cap = 0;
-    bool from_traces = false;
+    uint32_t C = 0, np = 0, cap = 0;
     uint64_t n_num = 0, n_den = 0;
     // the descriptor on the device: the lists as slots of the slab's matrix (from host traces: the members themselves)
     DevBuf<uint64_t> d_num_ptr, d_den_ptr;
@@ -33,14 +33,7 @@ struct mmg_contrast {
     DevBuf<uint32_t> d_cols;
     std::vector<uint64_t> slab_col;
     uint64_t max_cols = 0;
-    DevBuf<uint64_t> d_vid;
-    DevBuf<double> d_vscale;
-    const double *trace = nullptr;        // the summary's chain [S][n], device numbering (the sampler's)
-    const uint32_t *int_of_ext = nullptr; // the problem's
-    uint64_t seed = 0;
-    double alpha = 0.0;
-    // from host traces: [n_series][S]
-    DevBuf<double> d_traces;
+    MemberSource src;
     // the results
     std::vector<double> log_ratio, var, tau, p_gt, pct;
     std::vector<int32_t> rc;
@@ -52,9 +45,7 @@ namespace {
 size_t workspace_elems(uint32_t S, uint32_t groups)
 {
     if (S <= 8192) return 0;
-    size_t sp = 1;
-    while (sp < S) sp <<= 1;
-    return (size_t)groups * 3 * sp;
+    return (size_t)groups * 3 * next_pow2<size_t>(S);
 }
 
 // the lists of a description: pointers, offsets, empty sides, member range, duplicates within a side -- before any device work
@@ -96,56 +87,42 @@ uint32_t slab_cap(uint32_t C, uint32_t S)
     return (uint32_t)cap;
 }
 
-template <typename T>
-hipError_t upload(DevBuf<T> &buf, const T *src, size_t count, hipStream_t st)
-{
-    HIPE_TRY(buf.alloc(count ? count : 1));
-    if (count) HIPE_TRY(hipMemcpyAsync(buf.get(), src, count * sizeof(T), hipMemcpyHostToDevice, st));
-    return hipSuccess;
-}
-
 // the series of the contrasts [c0, c0 + cnt) of slab k (all inside it) into R[cnt][S]; gt: their counts of N_s > D_s, or null
 void launch_rows(const mmg_contrast *h, uint32_t k, uint32_t c0, uint32_t cnt, double *M, double *R, uint32_t *gt, hipStream_t st)
 {
-    const double *src = h->d_traces.get();
-    if (!h->from_traces) {
-        launch_contrast_gather((uint32_t)(h->slab_col[k + 1] - h->slab_col[k]), h->S, h->n, h->d_cols.get() + h->slab_col[k], h->int_of_ext, h->trace, h->seed,
-                               h->alpha, h->d_vid.get(), h->d_vscale.get(), M, st);
-        src = M;
-    }
-    launch_contrast_series(c0, cnt, h->S, h->d_num_ptr.get(), h->d_num_slot.get(), h->d_den_ptr.get(), h->d_den_slot.get(), src, R, gt, st);
+    const uint32_t *cols = nullptr;   // from host traces the members are the uploaded rows: no columns
+    uint32_t nm = 0;
+    if (!h->src.from_traces) { cols = h->d_cols.get() + h->slab_col[k]; nm = (uint32_t)(h->slab_col[k + 1] - h->slab_col[k]); }
+    const double *X = h->src.rows(cols, nm, M, st);
+    launch_contrast_series(c0, cnt, h->src.S, h->d_num_ptr.get(), h->d_num_slot.get(), h->d_den_ptr.get(), h->d_den_slot.get(), X, R, gt, st);
 }
 
-// The lists become slots, the descriptor goes to the device, every slab is summarised: what both create calls share.  h->device, S, n,
-// nv, from_traces and the source pointers are set; the current device is h->device.
+// The lists become slots, the descriptor goes to the device, every slab is summarised: what both create calls share.  h->src is set;
+// the current device is its device.
 int build(mmg_contrast *h, const mmg_contrast_desc *d)
 {
-    const uint32_t C = d->n_contrasts, S = h->S, np = d->n_percentiles;
+    const bool from_traces = h->src.from_traces;
+    const uint32_t C = d->n_contrasts, S = h->src.S, np = d->n_percentiles;
     h->C = C; h->np = np; h->cap = slab_cap(C, S);
     h->n_num = d->num_ptr[C]; h->n_den = d->den_ptr[C];
     const uint32_t cap = h->cap, n_slabs = (C + cap - 1) / cap;
     std::vector<uint32_t> num_slot(d->num_member, d->num_member + h->n_num), den_slot(d->den_member, d->den_member + h->n_den), cols;
-    if (!h->from_traces) {
-        // per slab: its distinct members, ascending (neighbours in the caller's numbering are mostly neighbours on the device); slot = rank
-        std::vector<uint32_t> slot_of((size_t)h->n + h->nv, 0xffffffffu);
+    if (!from_traces) {
         h->slab_col.assign(1, 0);
+        // a fixed number of contrasts per slab: the distinct members of their two sides
+        SlabColumns sc((size_t)h->src.n + h->src.nv);
         for (uint32_t k = 0; k < n_slabs; ++k) {
             const uint32_t c0 = k * cap, c1 = std::min<uint64_t>((uint64_t)c0 + cap, C);
-            const size_t base = cols.size();
-            auto collect = [&](const uint64_t *ptr, const uint32_t *mem) {
-                for (uint64_t j = ptr[c0]; j < ptr[c1]; ++j)
-                    if (slot_of[mem[j]] == 0xffffffffu) { slot_of[mem[j]] = 0; cols.push_back(mem[j]); }
-            };
-            collect(d->num_ptr, d->num_member);
-            collect(d->den_ptr, d->den_member);
-            std::sort(cols.begin() + (ptrdiff_t)base, cols.end());
-            for (size_t i = base; i < cols.size(); ++i) slot_of[cols[i]] = (uint32_t)(i - base);
-            for (uint64_t j = d->num_ptr[c0]; j < d->num_ptr[c1]; ++j) num_slot[j] = slot_of[d->num_member[j]];
-            for (uint64_t j = d->den_ptr[c0]; j < d->den_ptr[c1]; ++j) den_slot[j] = slot_of[d->den_member[j]];
-            for (size_t i = base; i < cols.size(); ++i) slot_of[cols[i]] = 0xffffffffu;
-            h->slab_col.push_back(cols.size());
-            h->max_cols = std::max<uint64_t>(h->max_cols, cols.size() - base);
+            for (uint64_t j = d->num_ptr[c0]; j < d->num_ptr[c1]; ++j) sc.add(d->num_member[j]);
+            for (uint64_t j = d->den_ptr[c0]; j < d->den_ptr[c1]; ++j) sc.add(d->den_member[j]);
+            h->max_cols = std::max<uint64_t>(h->max_cols, sc.count());
+            sc.close([&](auto slot) {
+                for (uint64_t j = d->num_ptr[c0]; j < d->num_ptr[c1]; ++j) num_slot[j] = slot(d->num_member[j]);
+                for (uint64_t j = d->den_ptr[c0]; j < d->den_ptr[c1]; ++j) den_slot[j] = slot(d->den_member[j]);
+            });
+            h->slab_col.push_back(sc.cols.size());
         }
+        cols = std::move(sc.cols);
     }
     HIP_TRY(h->st.create(hipStreamNonBlocking));
     hipStream_t st = h->st.get();
@@ -153,7 +130,7 @@ int build(mmg_contrast *h, const mmg_contrast_desc *d)
     HIP_TRY(upload(h->d_den_ptr, d->den_ptr, (size_t)C + 1, st));
     HIP_TRY(upload(h->d_num_slot, num_slot.data(), num_slot.size(), st));
     HIP_TRY(upload(h->d_den_slot, den_slot.data(), den_slot.size(), st));
-    if (!h->from_traces) HIP_TRY(upload(h->d_cols, cols.data(), cols.size(), st));
+    if (!from_traces) HIP_TRY(upload(h->d_cols, cols.data(), cols.size(), st));
     // the scratch of creation: a slab of series, the gathered members, the tables, a slab's results, the workspace
     DevBuf<double> d_R, d_M, d_tw, d_res;
     DevBuf<int32_t> d_pind, d_rc;
@@ -163,7 +140,7 @@ int build(mmg_contrast *h, const mmg_contrast_desc *d)
     HIP_TRY(upload(d_tw, tw.data(), tw.size(), st));
     HIP_TRY(upload(d_pind, d->percentile_index, (size_t)np, st));
     HIP_TRY(d_R.alloc((size_t)cap * S));
-    if (!h->from_traces) HIP_TRY(d_M.alloc((size_t)h->max_cols * S));
+    if (!from_traces) HIP_TRY(d_M.alloc((size_t)h->max_cols * S));
     HIP_TRY(d_res.alloc((size_t)cap * (3 + (np ? np : 0)) + 1));
     HIP_TRY(d_rc.alloc(cap));
     HIP_TRY(d_gt.alloc(cap));
@@ -192,10 +169,8 @@ int build(mmg_contrast *h, const mmg_contrast_desc *d)
 
 } // namespace
 
-extern "C" int mmg_contrast_create(mmg_sampler *s, mmg_summary *q, const mmg_contrast_desc *d, mmg_contrast **out)
+int MemberSource::view_summary(mmg_sampler *s, mmg_summary *q, const char *not_finished)
 {
-    if (!s || !q || !d || !out) return fail(MMG_ERR_ARG, "NULL argument");
-    *out = nullptr;
     SamplerView v;
     int rc = sampler_view(s, &v);
     if (rc) return rc;
@@ -203,21 +178,60 @@ extern "C" int mmg_contrast_create(mmg_sampler *s, mmg_summary *q, const mmg_con
     rc = summary_view(q, &sv);
     if (rc) return rc;
     if (sv.p != v.p || !v.d_trace) return fail(MMG_ERR_ARG, "the summary is not one of this sampler");
-    if (!sv.finished) return fail(MMG_ERR_STATE, "contrasts are taken after mmg_summary_finish");
-    rc = check_desc(d, (uint64_t)sv.n + sv.nv);
+    if (!sv.finished) return fail(MMG_ERR_STATE, not_finished);
+    device = sv.device; S = sv.S; n = sv.n; nv = sv.nv;
+    trace = sv.trace; int_of_ext = sv.p->d_int_of_ext.get(); seed = sv.seed; alpha = sv.alpha;
+    h_vid_ = sv.vid; h_vscale_ = sv.vscale;
+    return MMG_OK;
+}
+
+int MemberSource::acquire(mmg_sampler *s)
+{
+    int rc = mmg_sampler_sync(s);   // every sample is final; nothing of the sampler is touched below
     if (rc) return rc;
-    rc = mmg_sampler_sync(s);   // every sample is final; nothing of the sampler is touched below
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(sv.device));
-    std::unique_ptr<mmg_contrast> h(new mmg_contrast());
-    h->device = sv.device; h->S = sv.S; h->n = sv.n; h->nv = sv.nv;
-    h->trace = sv.trace; h->int_of_ext = sv.p->d_int_of_ext.get(); h->seed = sv.seed; h->alpha = sv.alpha;
-    if (sv.nv) {
-        HIP_TRY(h->d_vid.alloc(sv.nv));
-        HIP_TRY(h->d_vscale.alloc(sv.nv));
-        HIP_TRY(hipMemcpy(h->d_vid.get(), sv.vid, (size_t)sv.nv * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(h->d_vscale.get(), sv.vscale, (size_t)sv.nv * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipSetDevice(device));
+    if (nv) {
+        HIP_TRY(d_vid.alloc(nv));
+        HIP_TRY(d_vscale.alloc(nv));
+        HIP_TRY(hipMemcpy(d_vid.get(), h_vid_, (size_t)nv * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_vscale.get(), h_vscale_, (size_t)nv * 8, hipMemcpyHostToDevice));
     }
+    return MMG_OK;
+}
+
+void MemberSource::from_chain(const SamplerView &v, int chain)
+{
+    device = v.p->device; S = (uint32_t)v.cfg.trace_len; n = v.p->n;
+    trace = v.d_trace + (uint64_t)chain * (uint64_t)v.cfg.trace_len * v.p->n;
+    int_of_ext = v.p->d_int_of_ext.get();
+}
+
+int MemberSource::from_host(int device_, uint32_t S_, uint32_t n_series, const double *traces)
+{
+    device = device_; S = S_; n = n_series; from_traces = true;
+    HIP_TRY(d_traces.alloc((size_t)n * S));
+    HIP_TRY(hipMemcpy(d_traces.get(), traces, (size_t)n * S * 8, hipMemcpyHostToDevice));
+    return MMG_OK;
+}
+
+const double *MemberSource::rows(const uint32_t *d_cols, uint32_t nm, double *M, hipStream_t st) const
+{
+    if (from_traces) return d_traces.get();
+    launch_contrast_gather(nm, S, n, d_cols, int_of_ext, trace, seed, alpha, d_vid.get(), d_vscale.get(), M, st);
+    return M;
+}
+
+extern "C" int mmg_contrast_create(mmg_sampler *s, mmg_summary *q, const mmg_contrast_desc *d, mmg_contrast **out)
+{
+    if (!s || !q || !d || !out) return fail(MMG_ERR_ARG, "NULL argument");
+    *out = nullptr;
+    std::unique_ptr<mmg_contrast> h(new mmg_contrast());
+    int rc = h->src.view_summary(s, q, "contrasts are taken after mmg_summary_finish");
+    if (rc) return rc;
+    rc = check_desc(d, (uint64_t)h->src.n + h->src.nv);
+    if (rc) return rc;
+    rc = h->src.acquire(s);
+    if (rc) return rc;
     rc = build(h.get(), d);
     if (rc) return rc;
     *out = h.release();
@@ -234,9 +248,8 @@ extern "C" int mmg_contrast_of_traces(int device, uint32_t S, uint32_t n_series,
     rc = require_device(device);
     if (rc) return rc;
     std::unique_ptr<mmg_contrast> h(new mmg_contrast());
-    h->device = device; h->S = S; h->n = n_series; h->from_traces = true;
-    HIP_TRY(h->d_traces.alloc((size_t)n_series * S));
-    HIP_TRY(hipMemcpy(h->d_traces.get(), traces, (size_t)n_series * S * 8, hipMemcpyHostToDevice));
+    rc = h->src.from_host(device, S, n_series, traces);
+    if (rc) return rc;
     rc = build(h.get(), d);
     if (rc) return rc;
     *out = h.release();
@@ -261,16 +274,17 @@ extern "C" int mmg_contrast_get_rows(mmg_contrast *h, uint32_t first, uint32_t c
     if (!h || (count && !R)) return fail(MMG_ERR_ARG, "NULL argument");
     if (first > h->C || count > h->C - first) return fail(MMG_ERR_ARG, "contrast range out of bounds");
     if (!count) return MMG_OK;
-    HIP_TRY(hipSetDevice(h->device));
+    const uint32_t S = h->src.S;
+    HIP_TRY(hipSetDevice(h->src.device));
     hipStream_t st = h->st.get();
     DevBuf<double> d_R, d_M;
-    HIP_TRY(d_R.alloc((size_t)std::min(h->cap, count) * h->S));
-    if (!h->from_traces) HIP_TRY(d_M.alloc((size_t)h->max_cols * h->S));
+    HIP_TRY(d_R.alloc((size_t)std::min(h->cap, count) * S));
+    if (!h->src.from_traces) HIP_TRY(d_M.alloc((size_t)h->max_cols * S));
     for (uint32_t c = first; c < first + count;) {   // the piece of [first, first + count) in each slab it touches
         const uint32_t k = c / h->cap, end = std::min<uint64_t>((uint64_t)(k + 1) * h->cap, (uint64_t)first + count), cnt = end - c;
         launch_rows(h, k, c, cnt, d_M.get(), d_R.get(), nullptr, st);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(R + (size_t)(c - first) * h->S, d_R.get(), (size_t)cnt * h->S * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(R + (size_t)(c - first) * S, d_R.get(), (size_t)cnt * S * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         c = end;
     }
@@ -281,8 +295,8 @@ extern "C" int mmg_contrast_device_bytes(mmg_contrast *h, uint64_t *bytes)
 {
     if (!h || !bytes) return fail(MMG_ERR_ARG, "NULL argument");
     uint64_t b = 16 * ((uint64_t)h->C + 1) + 4 * (h->n_num + h->n_den);
-    if (h->from_traces) b += 8 * (uint64_t)h->n * h->S;
-    else b += 4 * h->slab_col.back() + 16 * (uint64_t)h->nv;
+    if (h->src.from_traces) b += 8 * (uint64_t)h->src.n * h->src.S;
+    else b += 4 * h->slab_col.back() + 16 * (uint64_t)h->src.nv;
     *bytes = b;
     return MMG_OK;
 }

@@ -9,7 +9,8 @@
 //                       the simulated traces, into a series-major matrix M[slot][S]
 //   k_contrast_series   one wave per contrast, lane = sample: walks the two slot lists over M, writes R[contrast][S] and the count of gt_s
 //   k_contrast_summary  one workgroup per series of R at a time: the steps of k_series_summary<SMAX, true> (post_kernels.h) on y = R
-//                       itself instead of on log x -- a copy, not shared code: that kernel's output bits are a contract
+//                       itself instead of on log x -- the same two device functions, so the same operations in the same order: that
+//                       order is the contract behind both kernels' output bits
 // No floating-point atomics; every sum runs in a fixed order: reruns are bit-identical.
 #pragma once
 #include "post_kernels.h"
@@ -85,8 +86,8 @@ struct ContrastOut {
 };
 
 // One workgroup per series of S samples at a time (series-major input R[series * S + s]); workgroup b takes the series b, b + gridDim.x, ...
-// The order statistics at pind (bitonic sort on sort_key, NaN last); the mean of y = R (sequential, sample order); Sokal's var / tau
-// of y with the bit-reversed radix-2 transform, twiddle table and window loop of k_series_summary.
+// k_series_summary<SMAX, true> (post_kernels.h) on y = R itself instead of on log x: the same buffers, series_order_stats for the order
+// statistics at pind, series_sokal<SMAX, false> for the mean and Sokal's var / tau.
 // SMAX > 0: in LDS (S <= SMAX).  SMAX == 0: any S, in the workgroup's slice of ws (3 * SP * 8 bytes, SP = S rounded up to a power of two).
 // S a power of two in [4, 2^21] for the Sokal part, else rc = 201 / 200 / 100.
 template <int SMAX>
@@ -98,9 +99,7 @@ __global__ __launch_bounds__(256) void k_contrast_summary(uint32_t count, uint32
     constexpr bool IN_LDS = SMAX > 0;
     __shared__ uint64_t l_key[IN_LDS ? SMAX : 1];
     __shared__ double l_im[IN_LDS ? SMAX : 1];
-    const uint32_t tid = threadIdx.x;
-    uint32_t SP = 1;
-    while (SP < S) SP <<= 1;
+    const uint32_t SP = next_pow2(S);
     uint64_t *s_key;
     double *s_re, *s_im, *s_pw;
     uint32_t cap;
@@ -115,89 +114,8 @@ __global__ __launch_bounds__(256) void k_contrast_summary(uint32_t count, uint32
     for (uint32_t ser = blockIdx.x; ser < count; ser += gridDim.x) {
         __syncthreads();   // the previous series of this workgroup is done with the buffers
         const double *x = X + (uint64_t)ser * S;
-        for (uint32_t i = tid; i < S; i += 256) s_key[i] = sort_key(x[i]);
-        for (uint32_t i = S + tid; i < cap; i += 256) s_key[i] = ~0ull; // padding sorts last
-        __syncthreads();
-        // bitonic sort of SP = next power of two >= S keys
-        for (uint32_t k = 2; k <= SP; k <<= 1)
-            for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-                for (uint32_t i = tid; i < SP; i += 256) {
-                    const uint32_t l = i ^ j;
-                    if (l > i) {
-                        const uint64_t a = s_key[i], b = s_key[l];
-                        const bool up = (i & k) == 0;
-                        if ((a > b) == up) { s_key[i] = b; s_key[l] = a; }
-                    }
-                }
-                __syncthreads();
-            }
-        for (uint32_t q = tid; q < np; q += 256) {
-            const int32_t idx = pind[q];
-            o.pct[(uint64_t)ser * np + q] = (idx >= 0 && (uint32_t)idx < S) ? sort_unkey(s_key[idx]) : __builtin_nan("");
-        }
-        __syncthreads();   // the order statistics are out: the keys' storage becomes the real parts
-        int rc = 0;
-        if (S > (2u << 20)) rc = 100;
-        else if (S < 4) rc = 200;
-        else if (S & (S - 1)) rc = 201;
-        for (uint32_t i = tid; i < S; i += 256) s_im[i] = x[i]; // natural order, for the mean
-        __syncthreads();
-        if (tid == 0) {
-            double acc = 0.0;
-            for (uint32_t i = 0; i < S; ++i) acc += s_im[i];
-            o.log_ratio[ser] = acc / (double)S;
-        }
-        if (rc != 0) {
-            if (tid == 0) { o.rc[ser] = rc; o.var[ser] = 0.0; o.tau[ser] = 0.0; }
-            continue;
-        }
-        // y into the transform buffers in bit-reversed order
-        for (uint32_t i = tid; i < S; i += 256) s_re[__brev(i) >> (32 - lg)] = s_im[i];
-        __syncthreads();
-        for (uint32_t i = tid; i < S; i += 256) s_im[i] = 0.0;
-        __syncthreads();
-        auto fft = [&]() { // in-place radix-2 DIT on bit-reversed input: the butterflies of host/numerics.hpp:fft_pow2
-            for (uint32_t len = 2; len <= S; len <<= 1) {
-                const uint32_t half = len >> 1;
-                for (uint32_t b = tid; b < (S >> 1); b += 256) {
-                    const uint32_t j = b & (half - 1), i = ((b / half) * len) + j, q = i + half;
-                    const double wr = tw[2 * (half + j)], wi = tw[2 * (half + j) + 1];
-                    const double xr = s_re[q] * wr - s_im[q] * wi, xi = s_re[q] * wi + s_im[q] * wr;
-                    const double ar = s_re[i], ai = s_im[i];
-                    s_re[q] = ar - xr; s_im[q] = ai - xi;
-                    s_re[i] = ar + xr; s_im[i] = ai + xi;
-                }
-                __syncthreads();
-            }
-        };
-        fft();
-        // power spectrum, mean removed, back into bit-reversed order for the second transform
-        if constexpr (IN_LDS) {
-            double pw[(SMAX + 255) / 256];
-            for (uint32_t i = tid, c = 0; i < S; i += 256, ++c) pw[c] = i == 0 ? 0.0 : s_re[i] * s_re[i] + s_im[i] * s_im[i];
-            __syncthreads();
-            for (uint32_t i = tid, c = 0; i < S; i += 256, ++c) { s_re[__brev(i) >> (32 - lg)] = pw[c]; s_im[i] = 0.0; }
-        } else {
-            for (uint32_t i = tid; i < S; i += 256) s_pw[i] = i == 0 ? 0.0 : s_re[i] * s_re[i] + s_im[i] * s_im[i];
-            __syncthreads();
-            for (uint32_t i = tid; i < S; i += 256) { s_re[__brev(i) >> (32 - lg)] = s_pw[i]; s_im[i] = 0.0; }
-        }
-        __syncthreads();
-        fft();
-        if (tid == 0) {
-            const double n = (double)S;
-            const double r0 = s_re[0];
-            o.var[ser] = r0 / (n * (n - 1.0));
-            const double c = 1.0 / r0;
-            double sum = -0.333333333333333333333;
-            int m = (int)S + 1;
-            for (uint32_t i = 0; i < S; ++i) {
-                sum += s_re[i] * c - 0.166666666666666666666;
-                if (sum < 0) { m = (int)i + 1; break; }
-            }
-            o.tau[ser] = 2 * (sum + ((double)m - 1.0) / 6.0);
-            o.rc[ser] = 0;
-        }
+        series_order_stats<256>(x, S, SP, cap, s_key, np, pind, o.pct + (uint64_t)ser * np);
+        series_sokal<SMAX, false>(x, S, lg, s_re, s_im, s_pw, tw, ser, o.log_ratio, o.var, o.tau, o.rc);
     }
 }
 

@@ -4,7 +4,7 @@
 //
 // One workgroup per series of C chains x S draws (series-major input X[series][C][S]).  N = S / 2 draws per split chain (for odd S the
 // middle draw is dropped), M = 2C split chains, P = M N pooled draws; split chain j = 2c + h is chain c's first (h = 0) or last half.
-// Per series the workgroup sorts the pooled draws (bitonic, keys of post_kernels.h: sort_key), reads the median and the 5 % / 95 %
+// Per series the workgroup sorts the pooled draws (block_sort on order_key: mmg_series.h), reads the median and the 5 % / 95 %
 // quantiles off the sorted keys, ranks every draw by a lower / upper-bound search of its own key (ties get their average rank) and
 // maps the rank to a normal score with dprobit; then the same for the draws folded about the median.  Sums over a split chain and over
 // the lags of the autocovariances run in a fixed order (lanes strided, then a butterfly over the wave), so reruns are bit-identical.
@@ -14,7 +14,8 @@
 
 namespace mmg {
 
-// the sum of v over the 64 lanes; every lane holds the same bits (each step adds two partial sums, a + b == b + a)
+// the sum of v over the 64 lanes; every lane holds the same bits (each step adds two partial sums, a + b == b + a).  An xor butterfly,
+// not the halving order of lane_sum (mmg_series.h): it associates the 64 values differently, and its bits are R-hat's and ESS's contract
 __device__ __forceinline__ double conv_wave_sum(double v)
 {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
@@ -26,22 +27,6 @@ __device__ __forceinline__ double conv_draw(const double *__restrict__ x, uint32
 {
     const uint32_t j = i / N, n = i - j * N;
     return x[(uint64_t)(j >> 1) * S + ((j & 1) ? S - N + n : n)];
-}
-
-// bitonic sort of PP (a power of two) keys by the whole workgroup; ends synchronised
-__device__ void conv_sort(uint64_t *k, uint32_t PP)
-{
-    for (uint32_t w = 2; w <= PP; w <<= 1)
-        for (uint32_t j = w >> 1; j > 0; j >>= 1) {
-            for (uint32_t i = threadIdx.x; i < PP; i += 256) {
-                const uint32_t l = i ^ j;
-                if (l > i) {
-                    const uint64_t a = k[i], b = k[l];
-                    if ((a > b) == ((i & w) == 0)) { k[i] = b; k[l] = a; }
-                }
-            }
-            __syncthreads();
-        }
 }
 
 // normal score of the draw with key `key` among the P sorted keys: z = probit((r - 3/8) / (P + 1/4)), r its average 1-based rank
@@ -60,10 +45,10 @@ __device__ __forceinline__ double conv_z(const uint64_t *k, uint32_t P, uint64_t
 __device__ __forceinline__ double conv_quantile(const uint64_t *k, uint32_t P, double p)
 {
     const double vi = (double)(P - 1) * p;
-    if (vi >= (double)(P - 1)) return sort_unkey(k[P - 1]);
+    if (vi >= (double)(P - 1)) return order_unkey(k[P - 1]);
     const double fl = __builtin_floor(vi);
     const uint32_t lo = (uint32_t)fl;
-    const double g = vi - fl, a = sort_unkey(k[lo]), b = sort_unkey(k[lo + 1]);
+    const double g = vi - fl, a = order_unkey(k[lo]), b = order_unkey(k[lo + 1]);
     const double d = b - a;
     return g >= 0.5 ? b - d * (1.0 - g) : a + d * g;
 }
@@ -181,8 +166,7 @@ __global__ __launch_bounds__(256) void k_convergence(uint32_t count, uint32_t C,
     __shared__ double sh[9];
     __shared__ int flag;
     const uint32_t tid = threadIdx.x, N = S / 2, M = 2 * C, P = M * N;
-    uint32_t PP = 1;
-    while (PP < P) PP <<= 1;
+    const uint32_t PP = next_pow2(P);
     uint64_t *key;
     double *y;
     if constexpr (IN_LDS) {
@@ -194,25 +178,25 @@ __global__ __launch_bounds__(256) void k_convergence(uint32_t count, uint32_t C,
     for (uint32_t ser = blockIdx.x; ser < count; ser += gridDim.x) {
         __syncthreads();   // the previous series of this workgroup is done with the buffers
         const double *x = X + (uint64_t)ser * C * S;
-        for (uint32_t i = tid; i < PP; i += 256) key[i] = i < P ? sort_key(conv_draw(x, i, N, S) + 0.0) : ~0ull; // (+ 0.0: -0 ties +0)
+        for (uint32_t i = tid; i < PP; i += 256) key[i] = i < P ? order_key(conv_draw(x, i, N, S) + 0.0) : ~0ull; // (+ 0.0: -0 ties +0)
         __syncthreads();
-        conv_sort(key, PP);
+        block_sort<256>(key, PP);
         if (key[0] == key[P - 1]) {   // a constant series (the same answer in every thread: the keys are sorted and synchronised)
             if (tid == 0) { rhat_o[ser] = __builtin_nan(""); ess_bulk_o[ser] = __builtin_nan(""); ess_tail_o[ser] = __builtin_nan(""); }
             continue;
         }
-        const double med = (sort_unkey(key[P / 2 - 1]) + sort_unkey(key[P / 2])) / 2.0;
+        const double med = (order_unkey(key[P / 2 - 1]) + order_unkey(key[P / 2])) / 2.0;
         const double q05 = conv_quantile(key, P, 0.05), q95 = conv_quantile(key, P, 0.95);
         // bulk: normal scores of the ranks
-        for (uint32_t i = tid; i < P; i += 256) y[i] = conv_z(key, P, sort_key(conv_draw(x, i, N, S) + 0.0));
+        for (uint32_t i = tid; i < P; i += 256) y[i] = conv_z(key, P, order_key(conv_draw(x, i, N, S) + 0.0));
         __syncthreads();
         double rhat_bulk = 0.0, ess_bulk = 0.0, rhat_tail = 0.0, ess_lo = 0.0, ess_hi = 0.0, unused = 0.0;
         conv_split_stats(y, wk, N, M, true, inv_log10_p, sh, &flag, rhat_bulk, ess_bulk);
         // folded about the median
-        for (uint32_t i = tid; i < PP; i += 256) key[i] = i < P ? sort_key(dabs(conv_draw(x, i, N, S) - med)) : ~0ull;
+        for (uint32_t i = tid; i < PP; i += 256) key[i] = i < P ? order_key(dabs(conv_draw(x, i, N, S) - med)) : ~0ull;
         __syncthreads();
-        conv_sort(key, PP);
-        for (uint32_t i = tid; i < P; i += 256) y[i] = conv_z(key, P, sort_key(dabs(conv_draw(x, i, N, S) - med)));
+        block_sort<256>(key, PP);
+        for (uint32_t i = tid; i < P; i += 256) y[i] = conv_z(key, P, order_key(dabs(conv_draw(x, i, N, S) - med)));
         __syncthreads();
         conv_split_stats(y, wk, N, M, false, inv_log10_p, sh, &flag, rhat_tail, unused);
         // tails: indicators of the 5 % and 95 % quantiles

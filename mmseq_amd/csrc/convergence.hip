@@ -10,6 +10,7 @@
 //   the simulated traces of every chain, C S n_virtual doubles (the group sums of any slab may read any of them).
 #include "mmg_host.h"
 #include "mmg_launch.h"
+#include "mmg_series.h"   // next_pow2
 #include "mmg_math.h"   // (TAG_SIMU)
 
 #include <cmath>
@@ -63,10 +64,7 @@ struct ConvWork {
     }
     uint64_t pooled_pow2() const
     {
-        const uint64_t p = (uint64_t)2 * C * (S / 2);
-        uint64_t pp = 1;
-        while (pp < p) pp <<= 1;
-        return pp;
+        return next_pow2((uint64_t)2 * C * (S / 2));
     }
     // the diagnostic of the cnt series in `slab`; results into host rhat[t0 + i], ...
     int run(uint32_t cnt, hipStream_t st, double *rhat, double *essb, double *esst)

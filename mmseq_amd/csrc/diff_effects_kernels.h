@@ -12,7 +12,7 @@
 //                is a bijection of the bits.  The same ballots count the draws > 0 and (parameter 0's workgroups) the rows of model 1.
 //   3. moments   one lane per series walks its draws in row order: sum / n, then the squared deviations from that mean (two passes)
 //   4. sort      the keys are padded with ~0 to a power of two and sorted by the whole workgroup: the bitonic network and the keys
-//                of k_series_summary (post_kernels.h), all series of the workgroup side by side
+//                of mmg_series.h (block_sort, order_key), all series of the workgroup side by side
 //   5. pick      q[j] = the sorted draw at floor(percentiles[j] / 100 * (n - 1) + 0.5)
 // KEYS is the power of two of keys a series has room for in LDS (S <= KEYS), NSER the series a workgroup sorts: 8 up to 2048 keys.  At
 // 4096 keys eight series would take 256 KiB, more than a CU has, so NSER = 4 and the tile is shared by two workgroups (blockIdx.z),
@@ -20,7 +20,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "mmg_math.h"
+#include "mmg_series.h"
 
 namespace mmg {
 
@@ -29,17 +29,6 @@ constexpr uint32_t FX_BLOCK = 256;
 constexpr uint32_t FX_CHUNK = 128;     // rows staged at a time (with 1024 keys a series, two workgroups fit a CU)
 constexpr uint32_t FX_SMAX = 4096;     // keys per series at most
 constexpr uint32_t FX_NPMAX = 32;
-
-// the order-preserving keys of post_kernels.h: sort_key / sort_unkey (that header defines kernels, so it belongs to post.hip alone)
-__device__ __forceinline__ uint64_t fx_key(double x)
-{
-    const uint64_t b = bits_of(x);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double fx_unkey(uint64_t k)
-{
-    return double_of((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k);
-}
 
 struct EffectsOut {
     uint32_t *n;       // [2][F]
@@ -97,7 +86,7 @@ __global__ __launch_bounds__(FX_BLOCK) void k_df_effects(uint32_t S, uint32_t P,
                 const uint32_t g = s_g[j][i];
                 const bool keep = live && g == m;
                 const uint64_t mask = __ballot(keep);
-                if (keep) s_key[jl][cnt[u] + (uint32_t)__popcll(mask & below)] = fx_key(x);   // cnt + prefix < n <= S <= KEYS
+                if (keep) s_key[jl][cnt[u] + (uint32_t)__popcll(mask & below)] = order_key(x);   // cnt + prefix < n <= S <= KEYS
                 cnt[u] += (uint32_t)__popcll(mask);
                 gt[u] += (uint32_t)__popcll(__ballot(keep && x > 0.0));
                 ones[u] += (uint32_t)__popcll(__ballot(live && g == 1));
@@ -116,11 +105,11 @@ __global__ __launch_bounds__(FX_BLOCK) void k_df_effects(uint32_t S, uint32_t P,
         if (f < F) {
             const uint64_t *k = s_key[jl];
             double sum = 0.0;
-            for (uint32_t i = 0; i < n; ++i) sum += fx_unkey(k[i]);
+            for (uint32_t i = 0; i < n; ++i) sum += order_unkey(k[i]);
             const double mean = sum / (double)n;   // 0 / 0 for n = 0: NaN
             double ss = 0.0;
             for (uint32_t i = 0; i < n; ++i) {
-                const double dx = fx_unkey(k[i]) - mean;
+                const double dx = order_unkey(k[i]) - mean;
                 ss += dx * dx;
             }
             const size_t at = (size_t)s * F + f;
@@ -164,7 +153,7 @@ __global__ __launch_bounds__(FX_BLOCK) void k_df_effects(uint32_t S, uint32_t P,
         if (n) {
             uint32_t idx = (uint32_t)__builtin_floor(pct[jq] / 100.0 * (double)(n - 1) + 0.5);
             idx = idx < n ? idx : n - 1;
-            v = fx_unkey(s_key[jl][idx]);
+            v = order_unkey(s_key[jl][idx]);
         }
         o.q[((size_t)s * np + jq) * F + f] = v;
     }

@@ -61,17 +61,10 @@ uint64_t slab_cap(uint64_t F, uint32_t Sa, uint32_t Sb)
     return std::max<uint64_t>(cap, 1);
 }
 
-uint32_t pow2_at_least(uint32_t v)
-{
-    uint32_t p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
-
 // what both create calls share; the current device is the sources'
 int build(mmg_fold *h, const Side &sa, const Side &sb, uint64_t F, double off, uint32_t nr, const uint32_t *ranks)
 {
-    const uint32_t Sa = sa.S, Sb = sb.S, PA = pow2_at_least(Sa), PB = pow2_at_least(Sb);
+    const uint32_t Sa = sa.S, Sb = sb.S, PA = next_pow2(Sa), PB = next_pow2(Sb);
     const uint64_t cap = slab_cap(F, Sa, Sb);
     const bool from_traces = sa.host != nullptr;
     const size_t lds = 8 * ((size_t)PA + PB);

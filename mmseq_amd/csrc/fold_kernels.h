@@ -8,7 +8,7 @@
 //             zero counts, and the workgroup leaves -- no logarithm, no sort and no search ever sees such a series
 //   moments   wave 0 takes x, wave 1 takes y, in the caller's sample order: lane l adds its samples l, l + 64, ... ascending from 0.0,
 //             the 64 partial sums are folded by halving; mean = sum / S, then ss = the same sum over (v - mean) * (v - mean)
-//   sort      the words become order-preserving keys (fold_key), padded with ~0 above every finite key, and are sorted (bitonic, the
+//   sort      the words become order-preserving keys (order_key), padded with ~0 above every finite key, and are sorted (bitonic, the
 //             whole workgroup); then they are turned back into doubles in place
 //   counts    per x_i a lower- and an upper-bound search in y: n_gt += #{y_j < x_i}, n_eq += #{y_j == x_i}; x and y are compared, never d
 //   ranks     per requested rank k a bisection over the key space of d for the smallest key c with #{d_ij <= c} >= k + 1, at most 64
@@ -19,7 +19,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "mmg_math.h"
+#include "mmg_series.h"
 
 namespace mmg {
 
@@ -28,29 +28,6 @@ constexpr uint32_t FOLD_MAX_S = 4096;      // draws per side at most: 2 x 4096 w
 constexpr uint32_t FOLD_MAX_RANKS = 64;
 enum : uint8_t { FOLD_BAD_A = 1, FOLD_BAD_B = 2 };
 
-// order-preserving map of doubles onto unsigned integers (the sort_key of post_kernels.h)
-__device__ __forceinline__ uint64_t fold_key(double x)
-{
-    const uint64_t b = bits_of(x);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double fold_unkey(uint64_t k)
-{
-    return double_of((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k);
-}
-
-// x[i] + x[i + 32], then 16, 8, 4, 2, 1, and the sum of lane 0 to every lane (the pair_fold of pair_kernels.h)
-__device__ __forceinline__ double fold_sum(double x)
-{
-    x = x + __shfl_down(x, 32, 64);
-    x = x + __shfl_down(x, 16, 64);
-    x = x + __shfl_down(x, 8, 64);
-    x = x + __shfl_down(x, 4, 64);
-    x = x + __shfl_down(x, 2, 64);
-    x = x + __shfl_down(x, 1, 64);
-    return __shfl(x, 0, 64);
-}
-
 // the sum of v over the workgroup, in every thread; sh: 4 words that no thread is still reading (the callers alternate two sets)
 __device__ __forceinline__ uint32_t fold_block_add(uint32_t v, uint32_t *sh)
 {
@@ -58,22 +35,6 @@ __device__ __forceinline__ uint32_t fold_block_add(uint32_t v, uint32_t *sh)
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
     __syncthreads();
     return sh[0] + sh[1] + sh[2] + sh[3];
-}
-
-// bitonic sort of PP (a power of two) keys by the whole workgroup; ends synchronised (the conv_sort of conv_kernels.h)
-__device__ __forceinline__ void fold_sort(uint64_t *k, uint32_t PP)
-{
-    for (uint32_t w = 2; w <= PP; w <<= 1)
-        for (uint32_t j = w >> 1; j > 0; j >>= 1) {
-            for (uint32_t i = threadIdx.x; i < PP; i += FOLD_BLOCK) {
-                const uint32_t l = i ^ j;
-                if (l > i) {
-                    const uint64_t a = k[i], b = k[l];
-                    if ((a > b) == ((i & w) == 0)) { k[i] = b; k[l] = a; }
-                }
-            }
-            __syncthreads();
-        }
 }
 
 struct FoldOut {
@@ -132,10 +93,10 @@ __global__ __launch_bounds__(FOLD_BLOCK) void k_fold(uint32_t Sa, uint32_t Sb, u
         const uint32_t S = w ? Sb : Sa;
         double s = 0.0;
         for (uint32_t i = lane; i < S; i += 64) s = s + double_of(z[i]);
-        const double m = fold_sum(s) / (double)S;
+        const double m = lane_sum(s) / (double)S;
         double q = 0.0;
         for (uint32_t i = lane; i < S; i += 64) { const double d = double_of(z[i]) - m; q = q + d * d; }
-        q = fold_sum(q);
+        q = lane_sum(q);
         if (lane == 0) {
             if (w) { o.mean_b[f] = m; o.ss_b[f] = q; }
             else { o.mean_a[f] = m; o.ss_a[f] = q; o.status[f] = 0; }
@@ -144,13 +105,13 @@ __global__ __launch_bounds__(FOLD_BLOCK) void k_fold(uint32_t Sa, uint32_t Sb, u
     __syncthreads();
 
     // ---- sort both sides by key; the padding sorts above every finite key
-    for (uint32_t i = tid; i < PA; i += FOLD_BLOCK) kx[i] = i < Sa ? fold_key(double_of(kx[i])) : ~0ull;
-    for (uint32_t j = tid; j < PB; j += FOLD_BLOCK) ky[j] = j < Sb ? fold_key(double_of(ky[j])) : ~0ull;
+    for (uint32_t i = tid; i < PA; i += FOLD_BLOCK) kx[i] = i < Sa ? order_key(double_of(kx[i])) : ~0ull;
+    for (uint32_t j = tid; j < PB; j += FOLD_BLOCK) ky[j] = j < Sb ? order_key(double_of(ky[j])) : ~0ull;
     __syncthreads();
-    fold_sort(kx, PA);
-    fold_sort(ky, PB);
-    for (uint32_t i = tid; i < Sa; i += FOLD_BLOCK) kx[i] = bits_of(fold_unkey(kx[i]));
-    for (uint32_t j = tid; j < Sb; j += FOLD_BLOCK) ky[j] = bits_of(fold_unkey(ky[j]));
+    block_sort<FOLD_BLOCK>(kx, PA);
+    block_sort<FOLD_BLOCK>(ky, PB);
+    for (uint32_t i = tid; i < Sa; i += FOLD_BLOCK) kx[i] = bits_of(order_unkey(kx[i]));
+    for (uint32_t j = tid; j < Sb; j += FOLD_BLOCK) ky[j] = bits_of(order_unkey(ky[j]));
     __syncthreads();
 
     // ---- counts: x against y
@@ -170,8 +131,8 @@ __global__ __launch_bounds__(FOLD_BLOCK) void k_fold(uint32_t Sa, uint32_t Sb, u
     if (tid == 0) { o.n_gt[f] = gt; o.n_eq[f] = eq; }
 
     // ---- order statistics of d: bisection over its key space
-    const uint64_t key_min = fold_key((double_of(kx[0]) - double_of(ky[Sb - 1])) + 0.0);
-    const uint64_t key_max = fold_key((double_of(kx[Sa - 1]) - double_of(ky[0])) + 0.0);
+    const uint64_t key_min = order_key((double_of(kx[0]) - double_of(ky[Sb - 1])) + 0.0);
+    const uint64_t key_max = order_key((double_of(kx[Sa - 1]) - double_of(ky[0])) + 0.0);
     const uint32_t pairs = Sa * Sb;   // at most 2^24
     uint32_t par = 0;
     for (uint32_t r = 0; r < nr; ++r) {
@@ -183,7 +144,7 @@ __global__ __launch_bounds__(FOLD_BLOCK) void k_fold(uint32_t Sa, uint32_t Sb, u
         uint64_t lo = key_min, hi = key_max;   // the same in every thread: the counts are
         while (lo < hi) {
             const uint64_t mid = lo + ((hi - lo) >> 1);
-            const double c = fold_unkey(mid);
+            const double c = order_unkey(mid);
             uint32_t cnt = 0;
             for (uint32_t i = tid; i < Sa; i += FOLD_BLOCK) {
                 const double xi = double_of(kx[i]);
@@ -195,7 +156,7 @@ __global__ __launch_bounds__(FOLD_BLOCK) void k_fold(uint32_t Sa, uint32_t Sb, u
             par ^= 1;
             if (cnt >= k + 1) hi = mid; else lo = mid + 1;
         }
-        if (tid == 0) o.q[(uint64_t)f * nr + r] = fold_unkey(lo) + 0.0;
+        if (tid == 0) o.q[(uint64_t)f * nr + r] = order_unkey(lo) + 0.0;
     }
 }
 

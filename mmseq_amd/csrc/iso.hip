@@ -31,9 +31,7 @@ struct IsoSlab {
 // Members are destroyed in reverse declaration order: the destructor waits for `st`, then the buffers go, and the stream last.
 struct mmg_isoform {
     DevStream st;
-    int device = 0;
-    uint32_t G = 0, S = 0, n = 0, nv = 0, nq = 0, nr = 0;
-    bool from_traces = false;
+    uint32_t G = 0, nq = 0, nr = 0;
     uint64_t n_members = 0;
     // the description on the device: the lists as slots of their slab's matrix (from host traces: the members themselves)
     DevBuf<uint64_t> d_ptr;
@@ -42,13 +40,7 @@ struct mmg_isoform {
     std::vector<IsoSlab> slabs;
     uint64_t max_cols = 0, n_cols = 0;
     uint32_t max_groups = 0;
-    DevBuf<uint64_t> d_vid;
-    DevBuf<double> d_vscale;
-    const double *trace = nullptr;        // the summary's chain [S][n], device numbering (the sampler's)
-    const uint32_t *int_of_ext = nullptr; // the problem's
-    uint64_t seed = 0;
-    double alpha = 0.0;
-    DevBuf<double> d_traces;              // from host traces: [n_series][S]
+    MemberSource src;
     // the results
     std::vector<uint32_t> n_top, n_second, n_above, major, n_distinct;
     std::vector<uint8_t> status;
@@ -98,48 +90,36 @@ uint32_t group_cap(uint32_t G, uint32_t S)
     return (uint32_t)cap;
 }
 
-template <typename T>
-hipError_t upload(DevBuf<T> &buf, const T *src, size_t count, hipStream_t st)
-{
-    HIPE_TRY(buf.alloc(count ? count : 1));
-    if (count) HIPE_TRY(hipMemcpyAsync(buf.get(), src, count * sizeof(T), hipMemcpyHostToDevice, st));
-    return hipSuccess;
-}
-
 // consecutive groups, greedily; from a sampler also the slabs' member lists one after the other (cols) and every list entry as the
 // slot of its member in its slab's list
 void cut_slabs(mmg_isoform *h, const mmg_isoform_desc *d, std::vector<uint32_t> &cols, std::vector<uint32_t> &slot)
 {
-    const uint32_t G = h->G, gcap = group_cap(G, h->S);
-    const uint64_t mcap = std::max<uint64_t>(1, ISO_SLAB_BYTES / (8ull * h->S));
-    std::vector<uint32_t> slot_of;
-    if (!h->from_traces) slot_of.assign((size_t)h->n + h->nv, 0xffffffffu);
+    const bool from_traces = h->src.from_traces;
+    const uint32_t G = h->G, S = h->src.S, gcap = group_cap(G, S);
+    const uint64_t mcap = std::max<uint64_t>(1, ISO_SLAB_BYTES / (8ull * S));
+    SlabColumns sc(from_traces ? 0 : (size_t)h->src.n + h->src.nv);
     for (uint32_t g0 = 0; g0 < G;) {
         IsoSlab sl;
-        sl.g0 = g0; sl.c0 = cols.size();
+        sl.g0 = g0; sl.c0 = sc.first();
         uint32_t g = g0;
         for (; g < G && g - g0 < gcap; ++g) {
-            if (h->from_traces) continue;
+            if (from_traces) continue;
             uint64_t fresh = 0;
-            for (uint64_t j = d->ptr[g]; j < d->ptr[g + 1]; ++j) fresh += slot_of[d->member[j]] == 0xffffffffu;
-            if (g > g0 && cols.size() - sl.c0 + fresh > mcap) break;
-            for (uint64_t j = d->ptr[g]; j < d->ptr[g + 1]; ++j)
-                if (slot_of[d->member[j]] == 0xffffffffu) { slot_of[d->member[j]] = 0; cols.push_back(d->member[j]); }
+            for (uint64_t j = d->ptr[g]; j < d->ptr[g + 1]; ++j) fresh += sc.fresh(d->member[j]);
+            if (g > g0 && sc.count() + fresh > mcap) break;
+            for (uint64_t j = d->ptr[g]; j < d->ptr[g + 1]; ++j) sc.add(d->member[j]);
         }
         sl.ng = g - g0;
-        if (!h->from_traces) {
-            sl.nm = cols.size() - sl.c0;
-            // ascending: neighbours in the caller's numbering are mostly neighbours on the device; slot = rank
-            std::sort(cols.begin() + (ptrdiff_t)sl.c0, cols.end());
-            for (uint64_t i = 0; i < sl.nm; ++i) slot_of[cols[sl.c0 + i]] = (uint32_t)i;
-            for (uint64_t j = d->ptr[g0]; j < d->ptr[g]; ++j) slot[j] = slot_of[d->member[j]];
-            for (uint64_t i = 0; i < sl.nm; ++i) slot_of[cols[sl.c0 + i]] = 0xffffffffu;
+        if (!from_traces) {
+            sl.nm = sc.count();
+            sc.close([&](auto slot_of) { for (uint64_t j = d->ptr[g0]; j < d->ptr[g]; ++j) slot[j] = slot_of(d->member[j]); });
             h->max_cols = std::max(h->max_cols, sl.nm);
         }
         h->max_groups = std::max(h->max_groups, sl.ng);
         h->slabs.push_back(sl);
         g0 = g;
     }
+    cols = std::move(sc.cols);
     h->n_cols = cols.size();
 }
 
@@ -147,22 +127,18 @@ void cut_slabs(mmg_isoform *h, const mmg_isoform_desc *d, std::vector<uint32_t> 
 void launch_rows(const mmg_isoform *h, const IsoSlab &sl, uint32_t g, uint32_t cnt, uint32_t nq, const IsoTheta &theta, double *M, uint32_t *top,
                  uint32_t *second, double *H, double *P, uint8_t *bad, uint32_t *cnt_words, hipStream_t st)
 {
-    const double *src = h->d_traces.get();
-    if (!h->from_traces) {
-        launch_contrast_gather((uint32_t)sl.nm, h->S, h->n, h->d_cols.get() + sl.c0, h->int_of_ext, h->trace, h->seed, h->alpha, h->d_vid.get(),
-                               h->d_vscale.get(), M, st);
-        src = M;
-    }
+    const double *src = h->src.rows(h->src.from_traces ? nullptr : h->d_cols.get() + sl.c0, (uint32_t)sl.nm, M, st);
     constexpr unsigned per = ISO_BLOCK / ISO_LANES;
-    hipLaunchKernelGGL(k_iso_series, dim3((cnt + per - 1) / per), dim3(ISO_BLOCK), 0, st, g, cnt, h->S, nq, theta, (const uint64_t *)h->d_ptr.get(),
+    hipLaunchKernelGGL(k_iso_series, dim3((cnt + per - 1) / per), dim3(ISO_BLOCK), 0, st, g, cnt, h->src.S, nq, theta, (const uint64_t *)h->d_ptr.get(),
                        (const uint32_t *)h->d_slot.get(), src, top, second, H, P, bad, cnt_words);
 }
 
-// The lists become slots, the description goes to the device, every slab is summarised: what both create calls share.  h->device, S, n,
-// nv, from_traces and the source pointers are set; the current device is h->device.
+// The lists become slots, the description goes to the device, every slab is summarised: what both create calls share.  h->src is set;
+// the current device is its device.
 int build(mmg_isoform *h, const mmg_isoform_desc *d)
 {
-    const uint32_t G = d->n_groups, S = h->S, nq = d->n_thresholds, nr = d->n_ranks, stride = 2 + nq;
+    const bool from_traces = h->src.from_traces;
+    const uint32_t G = d->n_groups, S = h->src.S, nq = d->n_thresholds, nr = d->n_ranks, stride = 2 + nq;
     h->G = G; h->nq = nq; h->nr = nr; h->n_members = d->ptr[G];
     const uint64_t NM = h->n_members;
     if (NM * stride >= (1ull << 40)) return fail(MMG_ERR_ARG, "member: too many list entries");
@@ -171,20 +147,19 @@ int build(mmg_isoform *h, const mmg_isoform_desc *d)
     const uint32_t gx = h->max_groups;
     IsoTheta theta{};
     for (uint32_t q = 0; q < nq; ++q) theta.v[q] = d->threshold[q];
-    uint32_t PP = 1;
-    while (PP < S) PP <<= 1;
+    const uint32_t PP = next_pow2(S);
     const size_t lds = 16 * (size_t)PP;
 
     HIP_TRY(h->st.create(hipStreamNonBlocking));
     hipStream_t st = h->st.get();
     HIP_TRY(upload(h->d_ptr, d->ptr, (size_t)G + 1, st));
     HIP_TRY(upload(h->d_slot, slot.data(), slot.size(), st));
-    if (!h->from_traces) HIP_TRY(upload(h->d_cols, cols.data(), cols.size(), st));
+    if (!from_traces) HIP_TRY(upload(h->d_cols, cols.data(), cols.size(), st));
     // the scratch of creation: the gathered members, a slab's rows and results, the counters of every list entry, the ranks
     DevBuf<double> d_M, d_H, d_P, d_res;
     DevBuf<uint32_t> d_cnt, d_ranks, d_gi;
     DevBuf<uint8_t> d_bad;
-    if (!h->from_traces) HIP_TRY(d_M.alloc((size_t)h->max_cols * S));
+    if (!from_traces) HIP_TRY(d_M.alloc((size_t)h->max_cols * S));
     HIP_TRY(d_H.alloc((size_t)gx * S));
     HIP_TRY(d_P.alloc((size_t)gx * S));
     HIP_TRY(d_res.alloc((size_t)gx * (4 + 2 * (size_t)nr)));
@@ -238,28 +213,13 @@ extern "C" int mmg_isoform_create(mmg_sampler *s, mmg_summary *q, const mmg_isof
 {
     if (!s || !q || !d || !out) return fail(MMG_ERR_ARG, "NULL argument");
     *out = nullptr;
-    SamplerView v;
-    int rc = sampler_view(s, &v);
-    if (rc) return rc;
-    SummaryView sv;
-    rc = summary_view(q, &sv);
-    if (rc) return rc;
-    if (sv.p != v.p || !v.d_trace) return fail(MMG_ERR_ARG, "the summary is not one of this sampler");
-    if (!sv.finished) return fail(MMG_ERR_STATE, "isoform usage is taken after mmg_summary_finish");
-    rc = check_desc(d, (uint64_t)sv.n + sv.nv, sv.S);
-    if (rc) return rc;
-    rc = mmg_sampler_sync(s);   // every sample is final; nothing of the sampler is touched below
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(sv.device));
     std::unique_ptr<mmg_isoform> h(new mmg_isoform());
-    h->device = sv.device; h->S = sv.S; h->n = sv.n; h->nv = sv.nv;
-    h->trace = sv.trace; h->int_of_ext = sv.p->d_int_of_ext.get(); h->seed = sv.seed; h->alpha = sv.alpha;
-    if (sv.nv) {
-        HIP_TRY(h->d_vid.alloc(sv.nv));
-        HIP_TRY(h->d_vscale.alloc(sv.nv));
-        HIP_TRY(hipMemcpy(h->d_vid.get(), sv.vid, (size_t)sv.nv * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(h->d_vscale.get(), sv.vscale, (size_t)sv.nv * 8, hipMemcpyHostToDevice));
-    }
+    int rc = h->src.view_summary(s, q, "isoform usage is taken after mmg_summary_finish");
+    if (rc) return rc;
+    rc = check_desc(d, (uint64_t)h->src.n + h->src.nv, h->src.S);
+    if (rc) return rc;
+    rc = h->src.acquire(s);
+    if (rc) return rc;
     rc = build(h.get(), d);
     if (rc) return rc;
     *out = h.release();
@@ -276,9 +236,8 @@ extern "C" int mmg_isoform_of_traces(int device, uint32_t S, uint32_t n_series, 
     rc = require_device(device);
     if (rc) return rc;
     std::unique_ptr<mmg_isoform> h(new mmg_isoform());
-    h->device = device; h->S = S; h->n = n_series; h->from_traces = true;
-    HIP_TRY(h->d_traces.alloc((size_t)n_series * S));
-    HIP_TRY(hipMemcpy(h->d_traces.get(), traces, (size_t)n_series * S * 8, hipMemcpyHostToDevice));
+    rc = h->src.from_host(device, S, n_series, traces);
+    if (rc) return rc;
     rc = build(h.get(), d);
     if (rc) return rc;
     *out = h.release();
@@ -316,12 +275,12 @@ extern "C" int mmg_isoform_get_rows(mmg_isoform *h, uint32_t first, uint32_t cou
     if (!h) return fail(MMG_ERR_ARG, "NULL isoform handle");
     if (first > h->G || count > h->G - first) return fail(MMG_ERR_ARG, "group range out of bounds");
     if (!count) return MMG_OK;
-    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipSetDevice(h->src.device));
     hipStream_t st = h->st.get();
-    const uint32_t S = h->S, rows = std::min(h->max_groups, count);
+    const uint32_t S = h->src.S, rows = std::min(h->max_groups, count);
     DevBuf<double> d_M, d_H, d_P;
     DevBuf<uint32_t> d_top, d_second;
-    if (!h->from_traces) HIP_TRY(d_M.alloc((size_t)h->max_cols * S));
+    if (!h->src.from_traces) HIP_TRY(d_M.alloc((size_t)h->max_cols * S));
     HIP_TRY(d_H.alloc((size_t)rows * S));
     HIP_TRY(d_P.alloc((size_t)rows * S));
     if (top) HIP_TRY(d_top.alloc((size_t)rows * S));
@@ -349,8 +308,8 @@ extern "C" int mmg_isoform_device_bytes(mmg_isoform *h, uint64_t *bytes)
 {
     if (!h || !bytes) return fail(MMG_ERR_ARG, "NULL argument");
     uint64_t b = 8 * ((uint64_t)h->G + 1) + 4 * h->n_members;
-    if (h->from_traces) b += 8 * (uint64_t)h->n * h->S;
-    else b += 4 * h->n_cols + 16 * (uint64_t)h->nv;
+    if (h->src.from_traces) b += 8 * (uint64_t)h->src.n * h->src.S;
+    else b += 4 * h->n_cols + 16 * (uint64_t)h->src.nv;
     *bytes = b;
     return MMG_OK;
 }

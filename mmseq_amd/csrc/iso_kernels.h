@@ -11,13 +11,13 @@
 //                  are zeroed before the launch; one wave owns a group's counters).  A group with a sample that is not valid does no
 //                  logarithm from that block on, and ends with NaN rows, 0xffffffff tops and zero counters.
 //   k_iso_summary  one workgroup of four waves per group: the H and P series as 64-bit words in LDS, the moments in the fixed lane
-//                  order of pair_kernels.h (pairs_ref.lsum) by waves 0 and 1, major and n_distinct from the counters by wave 2, then
+//                  order of lane_sum (pairs_ref.lsum) by waves 0 and 1, major and n_distinct from the counters by wave 2, then
 //                  both series as order-preserving keys, sorted bitonically and picked at the ranks: the shape of k_sim_pair.
 // No floating-point atomics, no atomics at all; every sum runs in a fixed order: reruns and any slab cut give the same bits.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "mmg_math.h"
+#include "mmg_series.h"
 
 namespace mmg {
 
@@ -28,45 +28,6 @@ constexpr uint32_t ISO_BLOCK = 256, ISO_LANES = 64;   // four waves: a group eac
 constexpr uint32_t ISO_NONE = 0xffffffffu;
 
 struct IsoTheta { double v[ISO_MAX_THRESHOLDS]; };
-
-// order-preserving map of doubles onto unsigned integers, and back (the sim_key of sim_kernels.h)
-__device__ __forceinline__ uint64_t iso_key(double x)
-{
-    const uint64_t b = bits_of(x);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double iso_unkey(uint64_t k)
-{
-    return double_of((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k);
-}
-
-// x[i] + x[i + 32], then 16, 8, 4, 2, 1, and the sum of lane 0 to every lane (the pair_fold of pair_kernels.h)
-__device__ __forceinline__ double iso_sum(double x)
-{
-    x = x + __shfl_down(x, 32, 64);
-    x = x + __shfl_down(x, 16, 64);
-    x = x + __shfl_down(x, 8, 64);
-    x = x + __shfl_down(x, 4, 64);
-    x = x + __shfl_down(x, 2, 64);
-    x = x + __shfl_down(x, 1, 64);
-    return __shfl(x, 0, 64);
-}
-
-// bitonic sort of PP (a power of two) keys by the whole workgroup; ends synchronised
-__device__ __forceinline__ void iso_sort(uint64_t *k, uint32_t PP)
-{
-    for (uint32_t w = 2; w <= PP; w <<= 1)
-        for (uint32_t j = w >> 1; j > 0; j >>= 1) {
-            for (uint32_t i = threadIdx.x; i < PP; i += ISO_BLOCK) {
-                const uint32_t l = i ^ j;
-                if (l > i) {
-                    const uint64_t a = k[i], b = k[l];
-                    if ((a > b) == ((i & w) == 0)) { k[i] = b; k[l] = a; }
-                }
-            }
-            __syncthreads();
-        }
-}
 
 // Group g = g0 + w of wave w < cnt, its members the slots slot[ptr[g] .. ptr[g + 1]) of M[slot][S] (ptr and slot are the whole
 // description's: flat positions).  Rows w of top / second / H / P [cnt][S] (top and second may be null: not wanted), bad[w] = 1 when a
@@ -186,10 +147,10 @@ __global__ __launch_bounds__(ISO_BLOCK) void k_iso_summary(uint32_t g0, uint32_t
         if (!bad) {
             double a = 0.0;
             for (uint32_t s = lane; s < S; s += 64) a = a + double_of(x[s]);
-            mean = iso_sum(a) / (double)S;
+            mean = lane_sum(a) / (double)S;
             double q = 0.0;
             for (uint32_t s = lane; s < S; s += 64) { const double d = double_of(x[s]) - mean; q = q + d * d; }
-            ss = iso_sum(q);
+            ss = lane_sum(q);
         }
         if (lane == 0) {
             if (w) { o.mean_P[b] = mean; o.ss_P[b] = ss; }
@@ -216,17 +177,17 @@ __global__ __launch_bounds__(ISO_BLOCK) void k_iso_summary(uint32_t g0, uint32_t
     // ---- order statistics: both series sorted by key, the padding above every key
     if (!bad) {   // (uniform over the workgroup)
         for (uint32_t s = tid; s < PP; s += ISO_BLOCK) {
-            kh[s] = s < S ? iso_key(double_of(kh[s])) : ~0ull;
-            kp[s] = s < S ? iso_key(double_of(kp[s])) : ~0ull;
+            kh[s] = s < S ? order_key(double_of(kh[s])) : ~0ull;
+            kp[s] = s < S ? order_key(double_of(kp[s])) : ~0ull;
         }
         __syncthreads();
-        iso_sort(kh, PP);
-        iso_sort(kp, PP);
+        block_sort<ISO_BLOCK>(kh, PP);
+        block_sort<ISO_BLOCK>(kp, PP);
     }
     for (uint32_t k = tid; k < nr; k += ISO_BLOCK) {
         const uint32_t rk = ranks[k];
-        o.q_H[(uint64_t)b * nr + k] = rk < S && !bad ? iso_unkey(kh[rk]) : nan;
-        o.q_P[(uint64_t)b * nr + k] = rk < S && !bad ? iso_unkey(kp[rk]) : nan;
+        o.q_H[(uint64_t)b * nr + k] = rk < S && !bad ? order_unkey(kh[rk]) : nan;
+        o.q_P[(uint64_t)b * nr + k] = rk < S && !bad ? order_unkey(kp[rk]) : nan;
     }
 }
 

@@ -2,6 +2,7 @@
 // the problem handle, error plumbing, caller <-> device transcript numbering.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstring>
 #include <functional>
 #include <string>
@@ -290,6 +291,78 @@ struct SummaryView {
 };
 int summary_view(mmg_summary *q, SummaryView *v);
 std::vector<double> series_twiddles(uint32_t S);   // the twiddle table of k_series_summary (post.hip)
+
+// a host array as a device buffer of its own (one word for an empty array), copied in stream order
+template <typename T>
+inline hipError_t upload(DevBuf<T> &buf, const T *src, size_t count, hipStream_t st)
+{
+    HIPE_TRY(buf.alloc(count ? count : 1));
+    if (count) HIPE_TRY(hipMemcpyAsync(buf.get(), src, count * sizeof(T), hipMemcpyHostToDevice, st));
+    return hipSuccess;
+}
+
+// Where the member traces of the contrasts, the isoform groups and the pairs come from (contrast.hip): a chain of a sampler, [S][n]
+// sample-major in device numbering, with the nv isoforms without hits drawn on demand (member n + v: Gamma(alpha) * vscale[v] keyed
+// (seed, chain 0, TAG_SIMU, vid[v], sample)) -- or the caller's host traces [n][S], uploaded.  A handle that answers row queries after
+// its creation keeps it as a member: the owned buffers go with the handle.
+struct MemberSource {
+    int device = 0;
+    uint32_t S = 0, n = 0, nv = 0;
+    bool from_traces = false;
+    const double *trace = nullptr;        // the chain (the sampler's memory)
+    const uint32_t *int_of_ext = nullptr; // the problem's; null: the identity
+    uint64_t seed = 0;
+    double alpha = 0.0;
+    DevBuf<uint64_t> d_vid;               // [nv]
+    DevBuf<double> d_vscale;
+    DevBuf<double> d_traces;              // from host traces: [n][S]
+    // The chain of summary q of sampler s, its simulated isoforms included, in two steps with the caller's own argument checks in
+    // between (members < n + nv, S samples: known after the first, and checked before any device work).  view_summary: the views and
+    // what can be wrong with them; not_finished: the message when the summary is not finished.  acquire: waits for the sampler,
+    // leaves the summary's device current and copies the isoforms' ids and scales to it.
+    int view_summary(mmg_sampler *s, mmg_summary *q, const char *not_finished);
+    int acquire(mmg_sampler *s);
+    // chain `chain` of a sampler's kept trace, no simulated isoforms; no device work
+    void from_chain(const SamplerView &v, int chain);
+    // host traces [n_series][S] to the current device, which is `device`
+    int from_host(int device_, uint32_t S_, uint32_t n_series, const double *traces);
+    // the series-major rows of the nm members d_cols[0 .. nm): gathered into M[nm][S] in stream order and M returned -- or, from host
+    // traces, the uploaded matrix itself (the members are its rows: nothing is gathered)
+    const double *rows(const uint32_t *d_cols, uint32_t nm, double *M, hipStream_t st) const;
+
+private:
+    const uint64_t *h_vid_ = nullptr;     // the summary's host arrays, between view_summary and acquire
+    const double *h_vscale_ = nullptr;
+};
+
+// The distinct members of consecutive slabs of member lists: per slab its columns in ascending order (neighbours in the caller's
+// numbering are mostly neighbours on the device) and every member's slot, its rank among them.  The cut rule is the caller's: it asks
+// fresh(), adds the members of what it takes into the open slab, and closes the slab.
+class SlabColumns {
+public:
+    std::vector<uint32_t> cols;   // the closed slabs' columns one after the other, then the open slab's in the order they came
+    explicit SlabColumns(size_t limit) : slot_of_(limit, NONE) {}
+    bool fresh(uint32_t member) const { return slot_of_[member] == NONE; }   // not in the open slab yet
+    void add(uint32_t member) { if (fresh(member)) { slot_of_[member] = 0; cols.push_back(member); } }
+    uint64_t first() const { return base_; }                 // the open slab is cols[first() .. first() + count())
+    uint64_t count() const { return cols.size() - base_; }
+    // Ends the open slab: sorts its columns, calls lists(slot), in which slot(member) is the member's slot and the caller rewrites the
+    // slab's lists, and opens the next slab.
+    template <typename F>
+    void close(F &&lists)
+    {
+        std::sort(cols.begin() + (ptrdiff_t)base_, cols.end());
+        for (size_t i = base_; i < cols.size(); ++i) slot_of_[cols[i]] = (uint32_t)(i - base_);
+        lists([this](uint32_t member) { return slot_of_[member]; });
+        for (size_t i = base_; i < cols.size(); ++i) slot_of_[cols[i]] = NONE;
+        base_ = cols.size();
+    }
+
+private:
+    static constexpr uint32_t NONE = 0xffffffffu;
+    std::vector<uint32_t> slot_of_;
+    size_t base_ = 0;
+};
 
 // read shards of one problem as one EM (em_host.hip): make_reduce(members, ctx) returns the exchange called between the phases with
 // what = 0 (xe: max, int32), 1 (accumulators + log-likelihood limbs: sum, uint64), 2 (column counts: sum, uint64); the buffers of a

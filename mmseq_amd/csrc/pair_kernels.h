@@ -14,7 +14,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "mmg_math.h"
+#include "mmg_series.h"
 
 namespace mmg {
 
@@ -22,19 +22,6 @@ constexpr uint32_t PAIR_LANES = 64;
 constexpr uint32_t PAIR_BLOCK = 256;                              // four waves per workgroup, a member or a pair each
 constexpr uint32_t PAIR_REG_BLOCKS = 16;                          // sample blocks of 64 a lane keeps in registers
 constexpr uint32_t PAIR_REG_SAMPLES = PAIR_REG_BLOCKS * PAIR_LANES;   // 1024
-
-// x[i] + x[i + 32], then 16, 8, 4, 2, 1, and the sum of lane 0 to every lane (the lanes above the live half read themselves or dead
-// lanes: their values are never used)
-__device__ inline double pair_fold(double x)
-{
-    x = x + __shfl_down(x, 32, 64);
-    x = x + __shfl_down(x, 16, 64);
-    x = x + __shfl_down(x, 8, 64);
-    x = x + __shfl_down(x, 4, 64);
-    x = x + __shfl_down(x, 2, 64);
-    x = x + __shfl_down(x, 1, 64);
-    return __shfl(x, 0, 64);
-}
 
 // Member j < nm of wave j: x = X[(row ? row[j] : j) * S + s]; mean[j] = lsum(dlog x) / S, Cn[j * S + s] = dlog(x) - mean[j],
 // saa[j] = lsum of the squares of that row.  REG: S <= PAIR_REG_SAMPLES.
@@ -57,7 +44,7 @@ __global__ __launch_bounds__(PAIR_BLOCK) void k_pair_members(uint32_t nm, uint32
             u[b] = 0.0;
             if (s < S) { u[b] = dlog(x[s]); A = A + u[b]; }
         }
-        const double m = pair_fold(A) / div;
+        const double m = lane_sum(A) / div;
 #pragma unroll
         for (uint32_t b = 0; b < PAIR_REG_BLOCKS; ++b) {
             const uint32_t s = b * PAIR_LANES + lane;
@@ -67,17 +54,17 @@ __global__ __launch_bounds__(PAIR_BLOCK) void k_pair_members(uint32_t nm, uint32
                 Q = Q + d * d;
             }
         }
-        const double q = pair_fold(Q);
+        const double q = lane_sum(Q);
         if (lane == 0) { mean[j] = m; saa[j] = q; }
     } else {
         for (uint32_t s = lane; s < S; s += PAIR_LANES) A = A + dlog(x[s]);
-        const double m = pair_fold(A) / div;
+        const double m = lane_sum(A) / div;
         for (uint32_t s = lane; s < S; s += PAIR_LANES) {
             const double d = dlog(x[s]) - m;
             c[s] = d;
             Q = Q + d * d;
         }
-        const double q = pair_fold(Q);
+        const double q = lane_sum(Q);
         if (lane == 0) { mean[j] = m; saa[j] = q; }
     }
 }
@@ -116,7 +103,7 @@ __global__ __launch_bounds__(PAIR_BLOCK) void k_pair_stats(uint32_t np, uint32_t
             if (in) { va = xa[s]; vb = xb[s]; w[b] = dlog(va + vb); A = A + w[b]; }
             count += (uint32_t)__popcll(__ballot(in && va > vb));
         }
-        const double m = pair_fold(A) / div;
+        const double m = lane_sum(A) / div;
 #pragma unroll
         for (uint32_t b = 0; b < PAIR_REG_BLOCKS; ++b) {
             const uint32_t s = b * PAIR_LANES + lane;
@@ -126,7 +113,7 @@ __global__ __launch_bounds__(PAIR_BLOCK) void k_pair_stats(uint32_t np, uint32_t
                 AB = AB + ca[s] * cb[s];
             }
         }
-        const double q = pair_fold(Q), ab = pair_fold(AB);
+        const double q = lane_sum(Q), ab = lane_sum(AB);
         if (lane == 0) {
             o.mean_a[p] = mean[ja]; o.mean_b[p] = mean[jb]; o.mean_sum[p] = m;
             o.saa[p] = saa[ja]; o.sbb[p] = saa[jb]; o.sab[p] = ab; o.sss[p] = q; o.n_gt[p] = count;
@@ -139,13 +126,13 @@ __global__ __launch_bounds__(PAIR_BLOCK) void k_pair_stats(uint32_t np, uint32_t
             if (in) { va = xa[s]; vb = xb[s]; A = A + dlog(va + vb); }
             count += (uint32_t)__popcll(__ballot(in && va > vb));
         }
-        const double m = pair_fold(A) / div;
+        const double m = lane_sum(A) / div;
         for (uint32_t s = lane; s < S; s += PAIR_LANES) {
             const double d = dlog(xa[s] + xb[s]) - m;
             Q = Q + d * d;
             AB = AB + ca[s] * cb[s];
         }
-        const double q = pair_fold(Q), ab = pair_fold(AB);
+        const double q = lane_sum(Q), ab = lane_sum(AB);
         if (lane == 0) {
             o.mean_a[p] = mean[ja]; o.mean_b[p] = mean[jb]; o.mean_sum[p] = m;
             o.saa[p] = saa[ja]; o.sbb[p] = saa[jb]; o.sab[p] = ab; o.sss[p] = q; o.n_gt[p] = count;

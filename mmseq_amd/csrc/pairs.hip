@@ -9,7 +9,6 @@
 // A member's numbers depend on the member alone, so the results do not depend on the cut.
 #include "pair_kernels.h"
 #include "mmg_host.h"
-#include "mmg_launch.h"
 
 #include <algorithm>
 #include <memory>
@@ -29,15 +28,6 @@ struct mmg_pairs {
 };
 
 namespace {
-
-struct Source {
-    uint32_t S = 0, n = 0;
-    // from a sampler: the chain [S][n] sample-major, device numbering
-    const double *trace = nullptr;
-    const uint32_t *int_of_ext = nullptr;
-    // from host traces: [n][S]
-    const double *host = nullptr;
-};
 
 int check_pairs(uint64_t n_pairs, const uint32_t *a, const uint32_t *b, uint32_t n)
 {
@@ -74,31 +64,28 @@ void cut_slabs(uint64_t P, const uint32_t *a, const uint32_t *b, uint32_t n, uin
                std::vector<uint32_t> &sa, std::vector<uint32_t> &sb)
 {
     const uint64_t mcap = member_cap(S), pcap = pair_cap();
-    std::vector<uint32_t> slot_of(n, 0xffffffffu);
+    SlabColumns sc(n);
     sa.resize(P); sb.resize(P);
     for (uint64_t p0 = 0; p0 < P;) {
         Slab sl;
-        sl.p0 = p0; sl.c0 = cols.size();
+        sl.p0 = p0; sl.c0 = sc.first();
         uint64_t p = p0;
         for (; p < P && p - p0 < pcap; ++p) {
-            const uint64_t fresh = (slot_of[a[p]] == 0xffffffffu) + (slot_of[b[p]] == 0xffffffffu);
-            if (p > p0 && cols.size() - sl.c0 + fresh > mcap) break;
-            if (slot_of[a[p]] == 0xffffffffu) { slot_of[a[p]] = 0; cols.push_back(a[p]); }
-            if (slot_of[b[p]] == 0xffffffffu) { slot_of[b[p]] = 0; cols.push_back(b[p]); }
+            const uint64_t fresh = (uint64_t)sc.fresh(a[p]) + sc.fresh(b[p]);
+            if (p > p0 && sc.count() + fresh > mcap) break;
+            sc.add(a[p]);
+            sc.add(b[p]);
         }
-        sl.np = p - p0; sl.nm = cols.size() - sl.c0;
-        // ascending: neighbours in the caller's numbering are mostly neighbours on the device; slot = rank
-        std::sort(cols.begin() + (ptrdiff_t)sl.c0, cols.end());
-        for (uint64_t i = 0; i < sl.nm; ++i) slot_of[cols[sl.c0 + i]] = (uint32_t)i;
-        for (uint64_t q = p0; q < p; ++q) { sa[q] = slot_of[a[q]]; sb[q] = slot_of[b[q]]; }
-        for (uint64_t i = 0; i < sl.nm; ++i) slot_of[cols[sl.c0 + i]] = 0xffffffffu;
+        sl.np = p - p0; sl.nm = sc.count();
+        sc.close([&](auto slot) { for (uint64_t q = p0; q < p; ++q) { sa[q] = slot(a[q]); sb[q] = slot(b[q]); } });
         slabs.push_back(sl);
         p0 = p;
     }
+    cols = std::move(sc.cols);
 }
 
-// what both create calls share; the current device is the source's
-int build(mmg_pairs *h, const Source &src, uint64_t P, const uint32_t *a, const uint32_t *b)
+// what both create calls share; the current device is the source's, st a stream of it that outlives the call
+int build(mmg_pairs *h, const MemberSource &src, hipStream_t st, uint64_t P, const uint32_t *a, const uint32_t *b)
 {
     const uint32_t S = src.S;
     std::vector<Slab> slabs;
@@ -106,19 +93,11 @@ int build(mmg_pairs *h, const Source &src, uint64_t P, const uint32_t *a, const 
     cut_slabs(P, a, b, src.n, S, slabs, cols, sa, sb);
     uint64_t Mx = 0, Px = 0;
     for (const Slab &sl : slabs) { Mx = std::max(Mx, sl.nm); Px = std::max(Px, sl.np); }
-    const bool from_traces = src.host != nullptr;
-    // everything on the device is scratch of this call, released with these owners (the stream last)
-    DevStream stream;
-    DevBuf<double> d_traces, d_M, d_C, d_mstat, d_res;
+    const bool from_traces = src.from_traces;
+    // everything on the device is scratch of this call, released with these owners, the caller's source and its stream
+    DevBuf<double> d_M, d_C, d_mstat, d_res;
     DevBuf<uint32_t> d_cols, d_slots, d_gt;
-    HIP_TRY(stream.create(hipStreamNonBlocking));
-    hipStream_t st = stream.get();
-    if (from_traces) {
-        HIP_TRY(d_traces.alloc((size_t)src.n * S));
-        HIP_TRY(hipMemcpyAsync(d_traces.get(), src.host, (size_t)src.n * S * 8, hipMemcpyHostToDevice, st));
-    } else {
-        HIP_TRY(d_M.alloc((size_t)Mx * S));
-    }
+    if (!from_traces) HIP_TRY(d_M.alloc((size_t)Mx * S));
     HIP_TRY(d_cols.alloc(Mx));
     HIP_TRY(d_C.alloc((size_t)Mx * S));
     HIP_TRY(d_mstat.alloc(2 * Mx));
@@ -137,13 +116,9 @@ int build(mmg_pairs *h, const Source &src, uint64_t P, const uint32_t *a, const 
         HIP_TRY(hipMemcpyAsync(d_cols.get(), cols.data() + sl.c0, (size_t)nm * 4, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_slots.get(), sa.data() + sl.p0, (size_t)np * 4, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_slots.get() + Px, sb.data() + sl.p0, (size_t)np * 4, hipMemcpyHostToDevice, st));
-        const double *X;
-        const uint32_t *row;
-        if (from_traces) { X = d_traces.get(); row = d_cols.get(); }
-        else {
-            launch_contrast_gather(nm, S, src.n, d_cols.get(), src.int_of_ext, src.trace, 0, 0.0, nullptr, nullptr, d_M.get(), st);
-            X = d_M.get(); row = nullptr;
-        }
+        // gathered: member j is row j of X; from host traces: row d_cols[j] of the uploaded matrix
+        const double *X = src.rows(d_cols.get(), nm, d_M.get(), st);
+        const uint32_t *row = from_traces ? d_cols.get() : nullptr;
         double *mean = d_mstat.get(), *saa = d_mstat.get() + Mx;
         PairOut o;
         double *r = d_res.get();
@@ -183,11 +158,11 @@ extern "C" int mmg_pairs_create(mmg_sampler *s, int chain, uint64_t n_pairs, con
     if (rc) return rc;
     HIP_TRY(hipSetDevice(v.p->device));
     std::unique_ptr<mmg_pairs> h(new mmg_pairs());
-    Source src;
-    src.S = (uint32_t)v.cfg.trace_len; src.n = v.p->n;
-    src.trace = v.d_trace + (uint64_t)chain * (uint64_t)v.cfg.trace_len * v.p->n;
-    src.int_of_ext = v.p->d_int_of_ext.get();
-    rc = build(h.get(), src, n_pairs, a, b);
+    DevStream stream;   // (declared first: destroyed after the source's buffers)
+    MemberSource src;
+    src.from_chain(v, chain);
+    HIP_TRY(stream.create(hipStreamNonBlocking));
+    rc = build(h.get(), src, stream.get(), n_pairs, a, b);
     if (rc) return rc;
     *out = h.release();
     return MMG_OK;
@@ -204,9 +179,12 @@ extern "C" int mmg_pairs_of_traces(int device, uint32_t S, uint32_t n_series, co
     rc = require_device(device);
     if (rc) return rc;
     std::unique_ptr<mmg_pairs> h(new mmg_pairs());
-    Source src;
-    src.S = S; src.n = n_series; src.host = traces;
-    rc = build(h.get(), src, n_pairs, a, b);
+    DevStream stream;   // (declared first: destroyed after the source's buffers)
+    MemberSource src;
+    HIP_TRY(stream.create(hipStreamNonBlocking));
+    rc = src.from_host(device, S, n_series, traces);
+    if (rc) return rc;
+    rc = build(h.get(), src, stream.get(), n_pairs, a, b);
     if (rc) return rc;
     *out = h.release();
     return MMG_OK;

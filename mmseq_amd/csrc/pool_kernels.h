@@ -4,12 +4,11 @@
 // Input as for the convergence diagnostics: series-major slabs X[series][chain][sample] of C chains x S draws, N = C S pooled draws.
 // The per-chain columns of the logged draws (mean, Sokal's var / tau / rc) are NOT computed here: a slab is count * C series of
 // length S to k_series_summary<., true> (post_kernels.h, unchanged), whose results this kernel combines.  What is new here are the
-// order statistics of the N pooled draws (bitonic sort of the keys of post_kernels.h: sort_key, padded to a power of two), the
+// order statistics of the N pooled draws (block_sort of their order_key, padded to a power of two: mmg_series.h), the
 // combination rule of the log columns, and the pooled proportion summaries (per chain the three sequential sums of
 // k_series_summary<., false>, then summed over the chains in ascending order).  Every sum runs in a fixed order: reruns are bit-identical.
 #pragma once
 #include "post_kernels.h"
-#include "conv_kernels.h"   // conv_sort
 
 namespace mmg {
 
@@ -34,8 +33,7 @@ __global__ __launch_bounds__(256) void k_pooled_summary(uint32_t count, uint32_t
     constexpr bool IN_LDS = PMAX > 0;
     __shared__ uint64_t l_key[IN_LDS ? PMAX : 1];
     const uint32_t tid = threadIdx.x, N = C * S;
-    uint32_t PP = 1;
-    while (PP < N) PP <<= 1;
+    const uint32_t PP = next_pow2(N);
     uint64_t *key;
     if constexpr (IN_LDS) key = l_key;
     else key = ws + (uint64_t)blockIdx.x * PP;
@@ -43,12 +41,12 @@ __global__ __launch_bounds__(256) void k_pooled_summary(uint32_t count, uint32_t
     for (uint32_t ser = blockIdx.x; ser < count; ser += gridDim.x) {
         __syncthreads();   // the previous series of this workgroup is done with the keys
         const double *x = X + (uint64_t)ser * N;
-        for (uint32_t i = tid; i < PP; i += 256) key[i] = i < N ? sort_key(x[i]) : ~0ull;   // padding sorts last
+        for (uint32_t i = tid; i < PP; i += 256) key[i] = i < N ? order_key(x[i]) : ~0ull;   // padding sorts last
         __syncthreads();
-        conv_sort(key, PP);
+        block_sort<256>(key, PP);
         for (uint32_t q = tid; q < np; q += 256) {
             const int32_t idx = pind[q];
-            o.pct[(uint64_t)ser * np + q] = (idx >= 0 && (uint32_t)idx < N) ? sort_unkey(key[idx]) : __builtin_nan("");
+            o.pct[(uint64_t)ser * np + q] = (idx >= 0 && (uint32_t)idx < N) ? order_unkey(key[idx]) : __builtin_nan("");
         }
         const uint64_t c0 = (uint64_t)ser * C;
         if constexpr (LOG_MODE) {

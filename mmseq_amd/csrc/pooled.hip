@@ -10,6 +10,7 @@
 // Every device buffer exists from the start of the call to its end: mmg_pooled_device_bytes is their sum.
 #include "mmg_host.h"
 #include "mmg_launch.h"
+#include "mmg_series.h"   // next_pow2
 #include "mmg_math.h"   // (TAG_SIMU)
 
 #include <memory>
@@ -68,9 +69,7 @@ struct PoolWork {
     }
     uint64_t pooled_pow2() const
     {
-        uint64_t pp = 1;
-        while (pp < (uint64_t)C * S) pp <<= 1;
-        return pp;
+        return next_pow2((uint64_t)C * S);
     }
     // need_groups: the sums of a slab of groups are staged; max_local > 0: proportions, whose slabs list at most max_local gene members
     hipError_t alloc(uint32_t c_, uint32_t s_, uint32_t max_count, uint32_t np_, const int32_t *h_pind, const std::vector<double> &h_tw, bool need_groups,

@@ -76,9 +76,7 @@ static constexpr uint32_t SERIES_WS_GROUPS = 1024;
 static size_t series_workspace_bytes(uint32_t S)
 {
     if (S <= 8192) return 0;
-    size_t sp = 1;
-    while (sp < S) sp <<= 1;
-    return (size_t)SERIES_WS_GROUPS * 3 * sp * 8;
+    return (size_t)SERIES_WS_GROUPS * 3 * next_pow2<size_t>(S) * 8;
 }
 template <bool LOG_MODE>
 static int launch_series(uint32_t count, uint32_t S, const double *X, uint32_t np, const int32_t *pind, const uint8_t *multi, const double *tw,

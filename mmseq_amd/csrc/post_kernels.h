@@ -10,7 +10,7 @@
 // log() alone.
 #pragma once
 #include "mmg_types.h"
-#include "mmg_math.h"
+#include "mmg_series.h"
 
 namespace mmg {
 
@@ -59,23 +59,111 @@ __global__ __launch_bounds__(256) void k_proportions(uint32_t cnt, uint32_t S, u
 
 // (dprobit, the inverse standard normal CDF of the proportion summaries: mmg_math.h)
 
-// order-preserving map of doubles onto unsigned integers (NaNs sort last): the sort below compares these
-__device__ __forceinline__ uint64_t sort_key(double x)
-{
-    const uint64_t b = bits_of(x);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double sort_unkey(uint64_t k)
-{
-    return double_of((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k);
-}
-
 struct SeriesOut {
     double *log_mean, *var, *tau;   // [count]      (log mode)
     int32_t *rc;                    // [count]      Sokal return code (src/sokal.cc:36-39)
     double *pct;                    // [count][np]  percentiles of the series itself (both modes)
     double *mean, *probit_mean, *probit_sd; // [count]  (proportion mode)
 };
+
+// The order statistics of the series x[0 .. S) by the whole workgroup of BLOCK threads: pct[q] = the pind[q]-th smallest value (NaNs
+// sort last; NaN for a position outside [0, S)).  s_key: cap >= SP words, SP = next_pow2(S); the words [SP, cap) are padded as well.
+// The caller synchronises before (the buffer is free) and, when it reuses the keys' storage, after (the picks are out).
+template <uint32_t BLOCK>
+__device__ __forceinline__ void series_order_stats(const double *x, uint32_t S, uint32_t SP, uint32_t cap, uint64_t *s_key, uint32_t np,
+                                                   const int32_t *__restrict__ pind, double *pct)
+{
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t i = tid; i < S; i += BLOCK) s_key[i] = order_key(x[i]);
+    for (uint32_t i = S + tid; i < cap; i += BLOCK) s_key[i] = ~0ull; // padding sorts last
+    __syncthreads();
+    block_sort<BLOCK>(s_key, SP);
+    for (uint32_t q = tid; q < np; q += BLOCK) {
+        const int32_t idx = pind[q];
+        pct[q] = (idx >= 0 && (uint32_t)idx < S) ? order_unkey(s_key[idx]) : __builtin_nan("");
+    }
+}
+
+// The mean and Sokal's var / tau of y = log x (TAKE_LOG) or y = x (:1195-1227, :1307-1363; src/sokal.cc:33-87) by a workgroup of 256
+// threads: the return code, y in natural order into s_im, its sequential mean, the bit-reversed radix-2 transform of y, the power
+// spectrum with the mean removed, its transform, and the window loop.  Thread 0 stores the results of series `ser` at mean[ser],
+// var[ser], tau[ser] and rc_out[ser] (the arrays and the index, not four addresses: those would each hold a pair of scalar registers
+// across the whole body).  s_re / s_im: S words each; s_pw: S words when SMAX == 0 (they may be the caller's sort keys), unused otherwise (the
+// spectrum waits in registers).  Returns where there is nothing more to do for this series: rc != 0 after the mean, or the end.
+// Every floating-point expression and its order is the contract here: k_series_summary, k_contrast_summary and the host
+// implementation (host/numerics.hpp) give the same bits because they run the same operations in the same order.
+template <int SMAX, bool TAKE_LOG>
+__device__ __forceinline__ void series_sokal(const double *x, uint32_t S, uint32_t lg, double *s_re, double *s_im, double *s_pw,
+                                             const double *__restrict__ tw, uint32_t ser, double *mean, double *var, double *tau, int32_t *rc_out)
+{
+    const uint32_t tid = threadIdx.x;
+    __syncthreads();   // the order statistics are out: the keys' storage becomes the real parts
+    int rc = 0;
+    if (S > (2u << 20)) rc = 100;
+    else if (S < 4) rc = 200;
+    else if (S & (S - 1)) rc = 201;
+    for (uint32_t i = tid; i < S; i += 256) { // natural order, for the mean
+        if constexpr (TAKE_LOG) s_im[i] = dlog(x[i]);
+        else s_im[i] = x[i];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double acc = 0.0;
+        for (uint32_t i = 0; i < S; ++i) acc += s_im[i];
+        mean[ser] = acc / (double)S;
+    }
+    if (rc != 0) {
+        if (tid == 0) { rc_out[ser] = rc; var[ser] = 0.0; tau[ser] = 0.0; }
+        return;
+    }
+    // y into the transform buffers in bit-reversed order (the host permutes after loading; same values)
+    for (uint32_t i = tid; i < S; i += 256) s_re[__brev(i) >> (32 - lg)] = s_im[i];
+    __syncthreads();
+    for (uint32_t i = tid; i < S; i += 256) s_im[i] = 0.0;
+    __syncthreads();
+    auto fft = [&]() { // in-place radix-2 DIT on bit-reversed input: the butterflies of host/numerics.hpp:fft_pow2
+        for (uint32_t len = 2; len <= S; len <<= 1) {
+            const uint32_t half = len >> 1;
+            for (uint32_t b = tid; b < (S >> 1); b += 256) {
+                const uint32_t j = b & (half - 1), i = ((b / half) * len) + j, q = i + half;
+                const double wr = tw[2 * (half + j)], wi = tw[2 * (half + j) + 1];
+                const double xr = s_re[q] * wr - s_im[q] * wi, xi = s_re[q] * wi + s_im[q] * wr;
+                const double ar = s_re[i], ai = s_im[i];
+                s_re[q] = ar - xr; s_im[q] = ai - xi;
+                s_re[i] = ar + xr; s_im[i] = ai + xi;
+            }
+            __syncthreads();
+        }
+    };
+    fft();
+    // power spectrum, mean removed, back into bit-reversed order for the second transform
+    if constexpr (SMAX > 0) {
+        double pw[(SMAX + 255) / 256];
+        for (uint32_t i = tid, c = 0; i < S; i += 256, ++c) pw[c] = i == 0 ? 0.0 : s_re[i] * s_re[i] + s_im[i] * s_im[i];
+        __syncthreads();
+        for (uint32_t i = tid, c = 0; i < S; i += 256, ++c) { s_re[__brev(i) >> (32 - lg)] = pw[c]; s_im[i] = 0.0; }
+    } else {
+        for (uint32_t i = tid; i < S; i += 256) s_pw[i] = i == 0 ? 0.0 : s_re[i] * s_re[i] + s_im[i] * s_im[i];
+        __syncthreads();
+        for (uint32_t i = tid; i < S; i += 256) { s_re[__brev(i) >> (32 - lg)] = s_pw[i]; s_im[i] = 0.0; }
+    }
+    __syncthreads();
+    fft();
+    if (tid == 0) {
+        const double n = (double)S;
+        const double r0 = s_re[0];
+        var[ser] = r0 / (n * (n - 1.0));
+        const double c = 1.0 / r0;
+        double sum = -0.333333333333333333333;
+        int m = (int)S + 1;
+        for (uint32_t i = 0; i < S; ++i) {
+            sum += s_re[i] * c - 0.166666666666666666666;
+            if (sum < 0) { m = (int)i + 1; break; }
+        }
+        tau[ser] = 2 * (sum + ((double)m - 1.0) / 6.0);
+        rc_out[ser] = 0;
+    }
+}
 
 // One workgroup per series of S samples at a time (series-major input X[series * S + s]); workgroup b takes the series b, b + gridDim.x, ...
 //   LOG_MODE:  percentiles of x (:1110-1192); y = log x; mean of y (:1195-1227); Sokal var / tau of y (:1307-1363)
@@ -94,8 +182,7 @@ __global__ __launch_bounds__(256) void k_series_summary(uint32_t count, uint32_t
     __shared__ uint64_t l_key[IN_LDS ? SMAX : 1];
     __shared__ double l_im[(IN_LDS && LOG_MODE) ? SMAX : 1];
     const uint32_t tid = threadIdx.x;
-    uint32_t SP = 1;
-    while (SP < S) SP <<= 1;
+    const uint32_t SP = next_pow2(S);
     uint64_t *s_key;
     double *s_re, *s_im, *s_pw;
     uint32_t cap;
@@ -110,27 +197,10 @@ __global__ __launch_bounds__(256) void k_series_summary(uint32_t count, uint32_t
     for (uint32_t ser = blockIdx.x; ser < count; ser += gridDim.x) {
         __syncthreads();   // the previous series of this workgroup is done with the buffers
         const double *x = X + (uint64_t)ser * S;
-        for (uint32_t i = tid; i < S; i += 256) s_key[i] = sort_key(x[i]);
-        for (uint32_t i = S + tid; i < cap; i += 256) s_key[i] = ~0ull; // padding sorts last
-        __syncthreads();
-        // bitonic sort of SP = next power of two >= S keys
-        for (uint32_t k = 2; k <= SP; k <<= 1)
-            for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-                for (uint32_t i = tid; i < SP; i += 256) {
-                    const uint32_t l = i ^ j;
-                    if (l > i) {
-                        const uint64_t a = s_key[i], b = s_key[l];
-                        const bool up = (i & k) == 0;
-                        if ((a > b) == up) { s_key[i] = b; s_key[l] = a; }
-                    }
-                }
-                __syncthreads();
-            }
-        for (uint32_t q = tid; q < np; q += 256) {
-            const int32_t idx = pind[q];
-            o.pct[(uint64_t)ser * np + q] = (idx >= 0 && (uint32_t)idx < S) ? sort_unkey(s_key[idx]) : __builtin_nan("");
-        }
-        if constexpr (!LOG_MODE) {
+        series_order_stats<256>(x, S, SP, cap, s_key, np, pind, o.pct + (uint64_t)ser * np);
+        if constexpr (LOG_MODE) {
+            series_sokal<SMAX, true>(x, S, lg, s_re, s_im, s_pw, tw, ser, o.log_mean, o.var, o.tau, o.rc);
+        } else {
             // sequential sums in sample order, as the reference (:1237-1262)
             if (tid == 0) {
                 double sp = 0.0;
@@ -153,71 +223,6 @@ __global__ __launch_bounds__(256) void k_series_summary(uint32_t count, uint32_t
                 }
                 o.probit_mean[ser] = s1 / (double)S;
                 o.probit_sd[ser] = dsqrt((s2 - s1 * s1 / (double)S) / ((double)S - 1.0));
-            }
-        } else {
-            // ---- log mode
-            __syncthreads();   // the percentiles are out: the keys' storage becomes the real parts
-            int rc = 0;
-            if (S > (2u << 20)) rc = 100;
-            else if (S < 4) rc = 200;
-            else if (S & (S - 1)) rc = 201;
-            for (uint32_t i = tid; i < S; i += 256) s_im[i] = dlog(x[i]); // natural order, for the mean
-            __syncthreads();
-            if (tid == 0) {
-                double acc = 0.0;
-                for (uint32_t i = 0; i < S; ++i) acc += s_im[i];
-                o.log_mean[ser] = acc / (double)S;
-            }
-            if (rc != 0) {
-                if (tid == 0) { o.rc[ser] = rc; o.var[ser] = 0.0; o.tau[ser] = 0.0; }
-                continue;
-            }
-            // y into the transform buffers in bit-reversed order (the host permutes after loading; same values)
-            for (uint32_t i = tid; i < S; i += 256) s_re[__brev(i) >> (32 - lg)] = s_im[i];
-            __syncthreads();
-            for (uint32_t i = tid; i < S; i += 256) s_im[i] = 0.0;
-            __syncthreads();
-            auto fft = [&]() { // in-place radix-2 DIT on bit-reversed input: the butterflies of host/numerics.hpp:fft_pow2
-                for (uint32_t len = 2; len <= S; len <<= 1) {
-                    const uint32_t half = len >> 1;
-                    for (uint32_t b = tid; b < (S >> 1); b += 256) {
-                        const uint32_t j = b & (half - 1), i = ((b / half) * len) + j, q = i + half;
-                        const double wr = tw[2 * (half + j)], wi = tw[2 * (half + j) + 1];
-                        const double xr = s_re[q] * wr - s_im[q] * wi, xi = s_re[q] * wi + s_im[q] * wr;
-                        const double ar = s_re[i], ai = s_im[i];
-                        s_re[q] = ar - xr; s_im[q] = ai - xi;
-                        s_re[i] = ar + xr; s_im[i] = ai + xi;
-                    }
-                    __syncthreads();
-                }
-            };
-            fft();
-            // power spectrum, mean removed, back into bit-reversed order for the second transform
-            if constexpr (IN_LDS) {
-                double pw[(SMAX + 255) / 256];
-                for (uint32_t i = tid, c = 0; i < S; i += 256, ++c) pw[c] = i == 0 ? 0.0 : s_re[i] * s_re[i] + s_im[i] * s_im[i];
-                __syncthreads();
-                for (uint32_t i = tid, c = 0; i < S; i += 256, ++c) { s_re[__brev(i) >> (32 - lg)] = pw[c]; s_im[i] = 0.0; }
-            } else {
-                for (uint32_t i = tid; i < S; i += 256) s_pw[i] = i == 0 ? 0.0 : s_re[i] * s_re[i] + s_im[i] * s_im[i];
-                __syncthreads();
-                for (uint32_t i = tid; i < S; i += 256) { s_re[__brev(i) >> (32 - lg)] = s_pw[i]; s_im[i] = 0.0; }
-            }
-            __syncthreads();
-            fft();
-            if (tid == 0) {
-                const double n = (double)S;
-                const double r0 = s_re[0];
-                o.var[ser] = r0 / (n * (n - 1.0));
-                const double c = 1.0 / r0;
-                double sum = -0.333333333333333333333;
-                int m = (int)S + 1;
-                for (uint32_t i = 0; i < S; ++i) {
-                    sum += s_re[i] * c - 0.166666666666666666666;
-                    if (sum < 0) { m = (int)i + 1; break; }
-                }
-                o.tau[ser] = 2 * (sum + ((double)m - 1.0) / 6.0);
-                o.rc[ser] = 0;
             }
         }
     }

@@ -7,7 +7,7 @@
 // that count are the heads of the two sorted arrays.
 #pragma once
 #include <hip/hip_runtime.h>
-#include "mmg_math.h"
+#include "mmg_series.h"
 
 namespace mmg {
 
@@ -16,8 +16,7 @@ constexpr int QV_BLOCK = 256;
 __device__ inline uint64_t qv_key(double x, uint64_t nan_key)
 {
     if (x != x) return nan_key;
-    const uint64_t b = bits_of(x == 0.0 ? 0.0 : x);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+    return order_key(x == 0.0 ? 0.0 : x);
 }
 
 // T = log(g) - log(1 - g) - logit p' per (replica, feature): g = (sum of gamma) / sampled as mmg_diff_*_get_results forms it.  st: the

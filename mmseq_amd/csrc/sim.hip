@@ -59,13 +59,6 @@ uint32_t chunk_features(uint32_t F)
     return (uint32_t)std::min<uint64_t>(ch, F);
 }
 
-uint32_t pow2_at_least(uint32_t v)
-{
-    uint32_t p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
-
 } // namespace
 
 extern "C" int mmg_sim_create(int device, uint32_t S, uint32_t F, uint32_t T, const double *centre, const uint8_t *mask, uint32_t flags, mmg_sim **out)
@@ -202,7 +195,7 @@ extern "C" int mmg_sim_run(mmg_sim *h, uint32_t n_ranks, const uint32_t *ranks)
     h->status = count < 2 ? SIM_FEW_FEATURES : 0;
     if (h->status) { h->ran = true; return MMG_OK; }
     if (n_ranks) HIP_TRY(hipMemcpyAsync(h->d_ranks.get(), ranks, 4 * (size_t)n_ranks, hipMemcpyHostToDevice, st));
-    const uint32_t PT = pow2_at_least(T);
+    const uint32_t PT = next_pow2(T);
     const size_t lds = 16 * (size_t)PT;
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sim_pair), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     SimOut o;

@@ -18,13 +18,13 @@
 //                  registers, 256 doubles per tile
 //   k_sim_reduce   adds the chunks of a tile in ascending order from 0.0 and writes G (both triangles), m and n
 //   k_sim_pair     one workgroup per pair r < s: D[t] and R[t] of the T draws in LDS, the moments in the fixed lane order of
-//                  fold_kernels.h (pairs_ref.lsum), a bitonic sort of each, the order statistics at the ranks
+//                  lane_sum (pairs_ref.lsum), a bitonic sort of each, the order statistics at the ranks
 //   k_sim_nn       one thread per (a, t): the nearest other sample by the D^2 numerator, ties to the smallest index; integer adds
 // No floating-point atomics, no private memory: reruns are bit-identical.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "mmg_math.h"
+#include "mmg_series.h"
 
 namespace mmg {
 
@@ -39,45 +39,6 @@ enum : uint8_t { SIM_FEW_FEATURES = 1, SIM_PAIR_NO_R = 2 };
 constexpr uint32_t SIM_PAIR_BLOCK = 256;
 
 typedef double sim_acc __attribute__((ext_vector_type(4)));
-
-// order-preserving map of doubles onto unsigned integers, and back (the fold_key of fold_kernels.h)
-__device__ __forceinline__ uint64_t sim_key(double x)
-{
-    const uint64_t b = bits_of(x);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double sim_unkey(uint64_t k)
-{
-    return double_of((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k);
-}
-
-// x[i] + x[i + 32], then 16, 8, 4, 2, 1, and the sum of lane 0 to every lane (the fold_sum of fold_kernels.h)
-__device__ __forceinline__ double sim_sum(double x)
-{
-    x = x + __shfl_down(x, 32, 64);
-    x = x + __shfl_down(x, 16, 64);
-    x = x + __shfl_down(x, 8, 64);
-    x = x + __shfl_down(x, 4, 64);
-    x = x + __shfl_down(x, 2, 64);
-    x = x + __shfl_down(x, 1, 64);
-    return __shfl(x, 0, 64);
-}
-
-// bitonic sort of PP (a power of two) keys by the whole workgroup; ends synchronised (the fold_sort of fold_kernels.h)
-__device__ __forceinline__ void sim_sort(uint64_t *k, uint32_t PP)
-{
-    for (uint32_t w = 2; w <= PP; w <<= 1)
-        for (uint32_t j = w >> 1; j > 0; j >>= 1) {
-            for (uint32_t i = threadIdx.x; i < PP; i += SIM_PAIR_BLOCK) {
-                const uint32_t l = i ^ j;
-                if (l > i) {
-                    const uint64_t a = k[i], b = k[l];
-                    if ((a > b) == ((i & w) == 0)) { k[i] = b; k[l] = a; }
-                }
-            }
-            __syncthreads();
-        }
-}
 
 // tiles (ti <= tj) of an NT x NT upper triangle in row-major order: the index of (ti, tj), and back
 __host__ __device__ __forceinline__ uint32_t sim_ut_index(uint32_t NT, uint32_t ti, uint32_t tj)
@@ -255,10 +216,10 @@ __global__ __launch_bounds__(SIM_PAIR_BLOCK) void k_sim_pair(uint32_t S, uint32_
         if (!(w && bad)) {
             double a = 0.0;
             for (uint32_t t = lane; t < T; t += 64) a = a + double_of(x[t]);
-            mean = sim_sum(a) / (double)T;
+            mean = lane_sum(a) / (double)T;
             double q = 0.0;
             for (uint32_t t = lane; t < T; t += 64) { const double d = double_of(x[t]) - mean; q = q + d * d; }
-            ss = sim_sum(q);
+            ss = lane_sum(q);
         }
         if (lane == 0) {
             if (w) { o.mean_R[p] = mean; o.ss_R[p] = ss; }
@@ -269,16 +230,16 @@ __global__ __launch_bounds__(SIM_PAIR_BLOCK) void k_sim_pair(uint32_t S, uint32_
 
     // ---- order statistics: both series sorted by key, the padding above every key
     for (uint32_t t = tid; t < P; t += SIM_PAIR_BLOCK) {
-        kd[t] = t < T ? sim_key(double_of(kd[t])) : ~0ull;
-        kr[t] = t < T ? sim_key(double_of(kr[t])) : ~0ull;
+        kd[t] = t < T ? order_key(double_of(kd[t])) : ~0ull;
+        kr[t] = t < T ? order_key(double_of(kr[t])) : ~0ull;
     }
     __syncthreads();
-    sim_sort(kd, P);
-    if (!bad) sim_sort(kr, P);
+    block_sort<SIM_PAIR_BLOCK>(kd, P);
+    if (!bad) block_sort<SIM_PAIR_BLOCK>(kr, P);
     for (uint32_t k = tid; k < nr; k += SIM_PAIR_BLOCK) {
         const uint32_t rk = ranks[k];
-        o.q_D[(uint64_t)p * nr + k] = rk < T ? sim_unkey(kd[rk]) : nan;
-        o.q_R[(uint64_t)p * nr + k] = rk < T && !bad ? sim_unkey(kr[rk]) : nan;
+        o.q_D[(uint64_t)p * nr + k] = rk < T ? order_unkey(kd[rk]) : nan;
+        o.q_R[(uint64_t)p * nr + k] = rk < T && !bad ? order_unkey(kr[rk]) : nan;
     }
 }
 

@@ -48,7 +48,7 @@ def series(traces, contrasts, log=np.log):
 
 
 def sort_key(x):
-    """the library's order-preserving map of doubles onto unsigned integers (post_kernels.h: sort_key): NaN of either sign bit set... sorts
+    """the library's order-preserving map of doubles onto unsigned integers (mmg_series.h: order_key): NaN of either sign bit set... sorts
     by its bits; the positive NaNs come last"""
     b = np.ascontiguousarray(x, np.float64).view(np.uint64)
     return np.where(b >> np.uint64(63) != 0, ~b, b | np.uint64(1 << 63))

@@ -12,7 +12,7 @@ Log mode (transcripts, isoforms without hits, identical sets, genes), y = log x:
               tau      = (sum tau_c var_c) / (sum var_c)                                   so that mcse2 = tau W / N, W the mean within-chain variance
               rc       = the first non-zero rc_c, else 0;  rc != 0: tau = mcse2 = 0 (var: the formula on the zeros it was given)
   C = 1       the chain's own columns, copied: no arithmetic but mcse2 = tau_0 var_0 / S
-  percentiles the order statistics of the N pooled draws of x itself at the caller's positions, in sort_key order (NaNs last);
+  percentiles the order statistics of the N pooled draws of x itself at the caller's positions, in order_key order (NaNs last);
               a position outside [0, N) gives NaN
 Non-finite values propagate; nothing is clamped.
 

@@ -91,6 +91,25 @@ def test_trace_lengths_sokal_refuses_and_the_global_workspace(gpu, orc, S):
     _check_summary(got, ref, S, pidx, orc)
 
 
+@pytest.mark.parametrize("S", [4, 6, 8, 1024])
+def test_contrast_summary_and_log_summary_share_their_bits(gpu, S):
+    """k_contrast_summary on y = R and k_series_summary<., true> on y = log x run the same device functions: with R = dlog(x) - dlog(1)
+    = dlog(x) the mean, Sokal's var and tau and the return code (6 samples: 201) are the same bits, not merely close"""
+    from mmseq_amd import Contrast
+    from mmseq_amd.collapse import summarize
+    rng = np.random.default_rng(900 + S)
+    n = 5
+    x = _traces(rng, n, S)
+    tr = np.vstack([x, np.ones((1, S))])
+    with Contrast.from_traces(tr, [([j], [n]) for j in range(n)]) as h:
+        got = h.summary()
+    log_mean, var, tau, rc = summarize(np.ascontiguousarray(x.T), [[j] for j in range(n)])
+    assert (rc == (201 if S == 6 else 0)).all() and np.array_equal(got["rc"], rc)
+    assert np.array_equal(got["log_ratio"], log_mean)
+    assert np.array_equal(got["var"], var) and np.array_equal(got["tau"], tau)
+    assert S == 6 or (var > 0.0).all()                             # (not equal because both are zero)
+
+
 def test_slab_edges_and_reruns_give_the_same_bits(gpu, slab_option):
     from mmseq_amd import Contrast
     rng = np.random.default_rng(3)
