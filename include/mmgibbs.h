@@ -90,7 +90,8 @@ extern "C" {
  *      two samples from all pairs of their draws (mmg_fold_*, MMG_OPT_FOLD_SLAB), and the posterior distances and correlations
  *      between samples from their joint draws (mmg_sim_*, MMG_OPT_SIM_CHUNK), and the pointwise self test of the binomial chain's
  *      three shortcuts (mmg_selftest_bigk_points), and the posterior isoform usage within groups of transcripts -- dominant-isoform
- *      probabilities and usage entropy (mmg_isoform_*, MMG_OPT_ISO_SLAB).
+ *      probabilities and usage entropy (mmg_isoform_*, MMG_OPT_ISO_SLAB), and the extension of a finished run to twice its length
+ *      (mmg_sampler_extend).
  *      mmg_sampler_create refuses chains beyond 2^24: the Gamma stream's key holds 24 bits of the chain index (the row stream all 32), so
  *      chain 2^24 + c would redraw mu from chain c's uniforms.  No chain that ran before is changed by the check. */
 /* Layout.  The model does not care about the order of rows or the numbering of transcripts (src/mmseq.cpp:399-418 uses
@@ -292,6 +293,24 @@ int mmg_sampler_set_stream(mmg_sampler *s, void *hip_stream);
 /* n_iter full Gibbs iterations = src/mmseq.cpp:851-918 (sample+scatter, gamma redraw,
  * trace capture), enqueued asynchronously. */
 int mmg_sampler_run(mmg_sampler *s, int n_iter);
+/* Turns a run that has reached its planned end into the first half of a run of twice the length.  A chain is a function of (problem,
+ * seed, chain, iteration) alone and gibbs_iter enters only the thinning gibbs_iter / trace_len, so the samples a run of 2 gibbs_iter
+ * keeps from its first half are every second sample of this run: for every chain, trace row j becomes row 2 j (j < trace_len / 2),
+ * rows trace_len / 2 .. trace_len - 1 become +0.0 as in a new sampler, the moment sums are added up again from the kept rows in sample
+ * order, the configuration's gibbs_iter doubles and the number of kept samples becomes trace_len / 2.  The iteration, mu, the counts
+ * and the timing sums stay; mmg_sampler_run continues and the next kept sample is row trace_len / 2.
+ * IDENTITY: after mmg_sampler_extend and gibbs_iter more iterations (the value before the call), the trace, the moments, mu, the counts
+ * and the iteration equal, bit for bit, those of a sampler created with 2 gibbs_iter and run to its end -- and so at every iteration
+ * in between.
+ * MMG_ERR_ARG: trace_len odd; gibbs_iter >= 2^30 (twice its value must fit the configuration's int32).  MMG_ERR_STATE: created with
+ * keep_trace == 0; between mmg_sampler_sample and mmg_sampler_update; the planned run is not complete (iteration == gibbs_iter and all
+ * trace_len samples kept).  The argument rules are checked first.  The call waits for the sampler's stream, allocates a scratch buffer
+ * of 8 n trace_len / 2 bytes (a failure leaves the sampler untouched) and has completed on the device when it returns.
+ * A summary begun (mmg_summary_begin) before the call holds rows of samples that no longer exist: its mmg_summary_advance / _finish /
+ * _get_rows return MMG_ERR_STATE from then on.  The handles made from a full trace (mmg_fold_*, mmg_pairs_*, mmg_assign_*) refuse the
+ * sampler until its trace is full again.  The samplers of a group must be extended alike (the group calls compare gibbs_iter and the
+ * kept samples). */
+int mmg_sampler_extend(mmg_sampler *s);
 /* The two halves of one iteration, for read-shard mode where the caller all-reduces the
  * counts in between:  sample = :857-891 (+ :887 column sums), update = :905-917. */
 int mmg_sampler_sample(mmg_sampler *s);

@@ -16,3 +16,4 @@ from .pairs import Pairs  # noqa: F401
 from .fold import Fold  # noqa: F401
 from .similarity import Similarity  # noqa: F401
 from .gibbs import Problem, Sampler, device_count  # noqa: F401
+from .autolength import run_auto  # noqa: F401

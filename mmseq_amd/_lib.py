@@ -135,6 +135,7 @@ SYMBOLS = {
     "mmg_sampler_create": (C.c_int, [C.c_void_p, C.POINTER(Config), C.c_void_p, C.POINTER(C.c_void_p)]),
     "mmg_sampler_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mmg_sampler_run": (C.c_int, [C.c_void_p, C.c_int]),
+    "mmg_sampler_extend": (C.c_int, [C.c_void_p]),
     "mmg_sampler_sample": (C.c_int, [C.c_void_p]),
     "mmg_sampler_update": (C.c_int, [C.c_void_p]),
     "mmg_sampler_counts_devptr": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),

@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "../../../include/mmgibbs.h"
+#include "auto_rule.hpp"
 #include "contrasts_file.hpp"
 #include "iso_thresholds.hpp"
 #include "hitsio.hpp"
@@ -98,6 +99,13 @@ static void printUsage(ostream &out)
         << "                     share of the top isoform (one device only)" << endl
         << "  -iso_thresholds STR  with -isoforms: comma-separated shares of the gene in [0, 1), at most 8; per isoform the probability that" << endl
         << "                     it carries more than each (default: \"0.1,0.5\")" << endl
+        << "  -gibbs_auto MAX    run gibbs_iter iterations, judge the transcripts' R-hat and effective sample sizes across the chains, and" << endl
+        << "                     double the run (bit for bit the run planned that long) until -auto_frac of them meet the targets or twice" << endl
+        << "                     the length would pass MAX (gibbs_iter times a power of 2, at most 2^30).  Also writes output_base.autolength;" << endl
+        << "                     every other output is that of -gibbs_iter L for the length L it stopped at (one device only)" << endl
+        << "  -auto_ess FLOAT    with -gibbs_auto: least bulk and tail effective sample size of a transcript that passes (default: 400)" << endl
+        << "  -auto_rhat FLOAT   with -gibbs_auto: largest R-hat of a transcript that passes (default: 1.01)" << endl
+        << "  -auto_frac FLOAT   with -gibbs_auto: share of the judged transcripts that must pass, in (0, 1] (default: 0.99)" << endl
         << endl;
 }
 
@@ -386,6 +394,10 @@ struct Options {
     int pairs_maxset = 16;
     bool isoforms = false;
     vector<double> iso_thresholds = {0.1, 0.5};
+    // -gibbs_auto: the run is doubled from gibbs_iter until the rule of host/auto_rule.hpp holds or twice the length would pass gibbs_auto
+    bool auto_on = false;
+    int gibbs_auto = 0;
+    autolen::Targets auto_targets;
     string hits_file, output_base;
 };
 
@@ -395,7 +407,7 @@ static Options parse_options(int argc, char **argv)
     Options o;
     vector<string> percentile_fields;
     string iso_thresholds_text;
-    bool iso_thresholds_given = false;
+    bool iso_thresholds_given = false, auto_target_given = false;
     const CliOption options[] = {
         {"-alpha", CliOption::REAL, &o.alpha},        {"-beta", CliOption::REAL, &o.beta},
         {"-max_em_iter", CliOption::INT, &o.max_em_iter}, {"-epsilon", CliOption::REAL, &o.epsilon},
@@ -408,6 +420,8 @@ static Options parse_options(int argc, char **argv)
         {"-contrasts", CliOption::TEXT, &o.contrasts_file}, {"-pool", CliOption::FLAG, &o.pool},
         {"-pairs", CliOption::FLAG, &o.pairs},        {"-pairs_maxset", CliOption::INT, &o.pairs_maxset},
         {"-isoforms", CliOption::FLAG, &o.isoforms},  {"-iso_thresholds", CliOption::TEXT, &iso_thresholds_text},
+        {"-gibbs_auto", CliOption::INT, &o.gibbs_auto},   {"-auto_ess", CliOption::REAL, &o.auto_targets.ess},
+        {"-auto_rhat", CliOption::REAL, &o.auto_targets.rhat}, {"-auto_frac", CliOption::REAL, &o.auto_targets.frac},
         {"-h", CliOption::HELP, nullptr},          {"-help", CliOption::HELP, nullptr},       {"--help", CliOption::HELP, nullptr},
         {"-v", CliOption::VERSION, nullptr},        {"-version", CliOption::VERSION, nullptr}, {"--version", CliOption::VERSION, nullptr},
     };
@@ -426,6 +440,13 @@ static Options parse_options(int argc, char **argv)
         if (opt->kind == CliOption::FLAG) { *(bool *)opt->target = true; pos += 1; continue; }
         if (pos + 1 >= argc) usage_error("Error: mandatory arguments missing.");
         const char *value = argv[pos + 1];
+        if (opt->target == &o.gibbs_auto) o.auto_on = true;
+        if (strncmp(opt->name, "-auto_", 6) == 0) { // (a value that is no number is NaN: refused by the checks below)
+            auto_target_given = true;
+            char *end = nullptr;
+            const double v = strtod(value, &end);
+            *(double *)opt->target = end == value || *end != '\0' ? NAN : v;
+        } else
         if (opt->kind == CliOption::REAL) *(double *)opt->target = strtod(value, NULL);
         else if (opt->kind == CliOption::INT) *(int *)opt->target = atoi(value);
         else if (opt->kind == CliOption::TEXT) { *(string *)opt->target = value; if (opt->target == &iso_thresholds_text) iso_thresholds_given = true; }
@@ -470,6 +491,17 @@ static Options parse_options(int argc, char **argv)
         check(parsed, "Error: " + error + "\n");
     }
     check(is_power_of_two((unsigned)trace_length), "Error: gibbs_iter/gibbs_ss must be a power of 2.\n");
+    check(!(auto_target_given && !o.auto_on), "Error: -auto_ess, -auto_rhat and -auto_frac need -gibbs_auto.\n");
+    if (o.auto_on) {
+        // the run is extended on the one sampler that holds every chain
+        check(o.gpus == 1, "Error: -gibbs_auto extends the chains on one device: it cannot be combined with -gpus > 1.\n");
+        check(o.gibbs_auto <= (1 << 30), "Error: -gibbs_auto must be at most 2^30 = 1073741824.\n");
+        check(o.gibbs_auto >= o.gibbs_iter && o.gibbs_auto % o.gibbs_iter == 0 && is_power_of_two((unsigned)(o.gibbs_auto / o.gibbs_iter)),
+              "Error: -gibbs_auto must be gibbs_iter times a power of 2 (gibbs_iter, 2 gibbs_iter, 4 gibbs_iter, ...).\n");
+        check(o.auto_targets.ess > 0.0, "Error: -auto_ess must be a number > 0.\n");
+        check(o.auto_targets.rhat > 1.0, "Error: -auto_rhat must be a number > 1.\n");
+        check(o.auto_targets.frac > 0.0 && o.auto_targets.frac <= 1.0, "Error: -auto_frac must be a number in (0, 1].\n");
+    }
     return o;
 }
 
@@ -1158,6 +1190,7 @@ struct Chains {
 //      one device: `chains` chains in one sampler.  several devices, one chain: the stored rows are cut into contiguous shards
 //      (mmg_shard_bounds), one per device, counts all-reduced over RCCL every iteration -- bit-identical to the one-device run.
 //      several devices, chains >= devices: the stored problem is replicated, every device runs chains / gpus chains.
+static void begin_summary(Chains &ch, const SeriesLayout &layout);
 static Chains start_chains(const Options &opt, const Device &dev, const vector<double> &mu_em, const SeriesLayout &layout)
 {
     Chains ch;
@@ -1181,6 +1214,13 @@ static Chains start_chains(const Options &opt, const Device &dev, const vector<d
     //      loop; :927-1108 derives the other traces after it): sample s is final after iteration s * gibbs_ss, so the four trace files
     //      are formatted, compressed and written by background threads while the device runs on -- rows come off the device on
     //      streams of their own (mmg_sampler_get_trace_rows_done, mmg_summary_get_rows), nothing waits for the chain.
+    //      (-gibbs_auto: begun behind the last stage -- an extension replaces the samples a summary was begun on)
+    if (!opt.auto_on) begin_summary(ch, layout);
+    return ch;
+}
+
+static void begin_summary(Chains &ch, const SeriesLayout &layout)
+{
     mmg_summary_desc sd = layout.desc();
     sd.chain = 0;
     sd.n_percentiles = (uint32_t)layout.pind.size(); sd.percentile_index = layout.pind.data();
@@ -1188,7 +1228,6 @@ static Chains start_chains(const Options &opt, const Device &dev, const vector<d
     mmg_summary *summ = nullptr;
     MMG_TRY(mmg_summary_begin(smp, &sd, &summ));
     ch.summ.reset(summ);
-    return ch;
 }
 
 // One trace file, written by a worker thread: the ids of the series kept, then trace_length rows fetched as they become final.  With
@@ -1217,17 +1256,13 @@ static void start_trace_file(TraceWriters &w, const string &path, const vector<s
     });
 }
 
-// the Gibbs loop; the four trace files are written alongside by `w` (whose threads outlive it: they are joined after the tables are
-// written -- the tail of their work runs next to the summary columns and the tables instead of in front of them)
-static void run_gibbs(const Options &opt, const Observed &obs, const SeriesLayout &layout, const Device &dev, const Chains &ch,
-                      TraceWriters &w, StageTimer &stage)
+// the writers of the four trace files, each waiting for the samples `w` publishes
+static void start_trace_writers(const Options &opt, const Observed &obs, const SeriesLayout &layout, const Chains &ch, TraceWriters &w)
 {
     const int writer_threads = max(1, omp_get_max_threads());
     const int t_big = max(1, (writer_threads - 1) * 9 / 20), t_gene = max(1, writer_threads / 10);
     mmg_sampler *smp = ch.smp();
     mmg_summary *summ = ch.summ.get();
-    mmg_group *grp = dev.grp.get();
-    const Samplers &smps = ch.smps;
     auto rows = [summ](int kind) { return [summ, kind](int first, int count, double *out) { return mmg_summary_get_rows(summ, kind, first, count, out); }; };
     const string &base = opt.output_base;
     w.threads.reserve(4);
@@ -1242,6 +1277,17 @@ static void run_gibbs(const Options &opt, const Observed &obs, const SeriesLayou
                      "mmg_summary_get_rows(summ, MMG_SERIES_GENE, first, count, out)", t_gene);
     start_trace_file(w, base + ".prop.trace_gibbs.gz", obs.names, nullptr, rows(MMG_SERIES_TRANSCRIPT),
                      "mmg_summary_get_rows(summ, MMG_SERIES_TRANSCRIPT, first, count, out)", t_big);
+}
+
+// the Gibbs loop; the four trace files are written alongside by `w` (whose threads outlive it: they are joined after the tables are
+// written -- the tail of their work runs next to the summary columns and the tables instead of in front of them)
+static void run_gibbs(const Options &opt, const Observed &obs, const SeriesLayout &layout, const Device &dev, const Chains &ch,
+                      TraceWriters &w, StageTimer &stage)
+{
+    mmg_summary *summ = ch.summ.get();
+    mmg_group *grp = dev.grp.get();
+    const Samplers &smps = ch.smps;
+    start_trace_writers(opt, obs, layout, ch, w);
     // chunks of 1/64 of the run: the writers start on a chunk's samples when it ends, so what is left of their work after the last
     // iteration is 1/64 of the files
     const int gibbs_iter = opt.gibbs_iter, gibbs_ss = opt.gibbs_ss;
@@ -1277,6 +1323,71 @@ static void run_gibbs(const Options &opt, const Observed &obs, const SeriesLayou
     cout << "Gibbs iteration " << gibbs_iter - 1 << "       \r" << endl;
     if (stage.on) fprintf(stderr, "[timing] Gibbs loop: enqueue %.3f s, wait for the device %.3f s, derived rows %.3f s\n", t_enqueue, t_sync, t_advance);
     stage.mark("Gibbs (trace files written alongside)");
+}
+
+// ostream's default formatting of a double (%g, 6 digits), NaN as "nan": the numbers of output_base.autolength, as mmdiff prints its own
+static string fmt_auto(double x)
+{
+    if (std::isnan(x)) return std::signbit(x) ? "-nan" : "nan";
+    char buf[64];
+    snprintf(buf, sizeof buf, "%g", x);
+    return buf;
+}
+
+// -gibbs_auto: the run in stages.  Each stage runs the sampler to its planned end and judges the transcripts' R-hat and bulk / tail
+// ESS across the chains (host/auto_rule.hpp); while the rule says no and twice the length stays within gibbs_auto the sampler is
+// extended (mmg_sampler_extend: bit for bit the run planned at twice the length) and the next stage runs the second half.  No sample
+// is final before the last stage ends, so the summary is begun and advanced to trace_length in one step behind it, and the four
+// trace writers start with every sample published: their whole work follows the chain.  On return opt.gibbs_iter / gibbs_ss are the
+// length the run stopped at, and everything downstream is what `mmseq -gibbs_iter L` does.
+static void run_gibbs_auto(Options &opt, const Observed &obs, const SeriesLayout &layout, Chains &ch, uint32_t n, TraceWriters &w, StageTimer &stage)
+{
+    mmg_sampler *smp = ch.smp();
+    const string path = opt.output_base + ".autolength";
+    ofstream out(path.c_str());
+    if (!out) fatal("cannot open " + path + " for writing.");
+    const autolen::Targets &tg = opt.auto_targets;
+    out << "# auto_ess " << fmt_auto(tg.ess) << " auto_rhat " << fmt_auto(tg.rhat) << " auto_frac " << fmt_auto(tg.frac) << " chains " << opt.chains << "\n";
+    mmg_summary_desc cd;   // transcripts only: no isoforms without hits, no identical sets, no genes
+    memset(&cd, 0, sizeof cd);
+    vector<double> rhat(max<uint32_t>(n, 1), NAN), ess_bulk(rhat.size(), NAN), ess_tail(rhat.size(), NAN);
+    double t_chain = 0.0, t_diag = 0.0, t_extend = 0.0;
+    int done = 0;
+    for (;;) {
+        const double c0 = omp_get_wtime();
+        MMG_TRY(mmg_sampler_run(smp, opt.gibbs_iter - done));
+        MMG_TRY(mmg_sampler_sync(smp));
+        done = opt.gibbs_iter;
+        const double c1 = omp_get_wtime();
+        {
+            mmg_convergence *conv = nullptr;
+            MMG_TRY(mmg_convergence_create(smp, &cd, &conv));
+            const Convergence owned(conv);
+            MMG_TRY(mmg_convergence_get(conv, MMG_SERIES_TRANSCRIPT, rhat.data(), ess_bulk.data(), ess_tail.data()));
+        }
+        const autolen::Verdict v = autolen::judge(n, rhat.data(), ess_bulk.data(), ess_tail.data(), tg);
+        const double c2 = omp_get_wtime();
+        t_chain += c1 - c0; t_diag += c2 - c1;
+        const char *decision = v.stop ? "stop" : (opt.gibbs_iter <= opt.gibbs_auto / 2 ? "extend" : "max");
+        out << opt.gibbs_iter << "\t" << opt.gibbs_iter / trace_length << "\t" << v.judged << "\t" << v.passes << "\t" << fmt_auto(v.min_ess) << "\t"
+            << fmt_auto(v.max_rhat) << "\t" << decision << "\n";
+        cout << "Gibbs auto: length " << opt.gibbs_iter << ", judged " << v.judged << ", passes " << v.passes << ", worst ESS " << fmt_auto(v.min_ess)
+             << ", worst R-hat " << fmt_auto(v.max_rhat) << ": " << decision << endl;
+        if (decision[0] != 'e') break;
+        MMG_TRY(mmg_sampler_extend(smp));
+        opt.gibbs_iter *= 2;
+        t_extend += omp_get_wtime() - c2;
+    }
+    opt.gibbs_ss = opt.gibbs_iter / trace_length;
+    out.close();
+    if (!out) fatal("cannot write " + path + ".");
+    if (stage.on) fprintf(stderr, "[timing] Gibbs auto: chain %.3f s, diagnostics %.3f s, extensions %.3f s\n", t_chain, t_diag, t_extend);
+    stage.mark("Gibbs (auto length)");
+    begin_summary(ch, layout);
+    MMG_TRY(mmg_summary_advance(ch.summ.get(), trace_length));
+    start_trace_writers(opt, obs, layout, ch, w);
+    w.publish(trace_length);
+    stage.mark("derived rows, writers started");
 }
 
 // moments of log mu pooled over all chains and devices (one fp64 all-reduce): log_mu, sd and mcse of multi-chain runs
@@ -1920,6 +2031,7 @@ static void print_output_files(const Options &opt)
         cout << "  " << opt.output_base << ".isoforms" << endl
              << "  " << opt.output_base << ".gene.isoforms" << endl
              << endl;
+    if (opt.auto_on) cout << "  " << opt.output_base << ".autolength" << endl << endl;
     if (opt.debug) {
         cout << endl
              << "  " << opt.output_base << ".trace_em.gz" << endl
@@ -1940,7 +2052,7 @@ static int run(int argc, char **argv)
         if (q > 0 && q < omp_get_max_threads()) omp_set_num_threads(q);
     }
     const int max_threads = omp_get_max_threads();
-    const Options opt = parse_options(argc, argv);
+    Options opt = parse_options(argc, argv);   // (-gibbs_auto: gibbs_iter and gibbs_ss become the length the run stopped at)
     HitsfileReader hitsfileReader(opt.hits_file);
     print_parameters(opt, max_threads);
 
@@ -1978,9 +2090,10 @@ static int run(int argc, char **argv)
         const vector<double> mu_em = run_em(opt, obs, dev, std::move(mu), stage);
         stage.mark("EM");
         const SeriesLayout layout = series_layout(opt, hdr, hits, obs);
-        const Chains ch = start_chains(opt, dev, mu_em, layout);
+        Chains ch = start_chains(opt, dev, mu_em, layout);
         TraceWriters writers;   // (stopped and joined before the summary and samplers they read are released)
-        run_gibbs(opt, obs, layout, dev, ch, writers, stage);
+        if (opt.auto_on) run_gibbs_auto(opt, obs, layout, ch, (uint32_t)hits.n(), writers, stage);
+        else run_gibbs(opt, obs, layout, dev, ch, writers, stage);
         const Pooled pooled = pool_moments(opt, dev, ch, hits.n());
         cout << "Amalgamating transcripts and calculating summary statistics..." << flush;
         // ---- posterior summary on the device (src/mmseq.cpp:927-1363): the derived traces were computed while the chain ran; what is

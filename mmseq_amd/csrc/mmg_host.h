@@ -3,8 +3,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <atomic>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <string>
 #include <type_traits>
 #include <utility>
@@ -274,6 +276,9 @@ struct SamplerView {
     hipStream_t stream;
     int iter;
     int64_t n_kept;          // samples kept so far
+    // how often mmg_sampler_extend has rewritten the trace: a handle that keeps rows derived from it compares the value at its
+    // creation with the current one (shared: the counter outlives the sampler while such a handle exists)
+    std::shared_ptr<const std::atomic<uint64_t>> extensions;
 };
 int sampler_view(mmg_sampler *s, SamplerView *v);
 

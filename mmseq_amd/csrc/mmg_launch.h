@@ -72,6 +72,12 @@ void host_synth_tables(uint64_t seed, uint32_t T, double lambda, std::vector<dou
 // exact start-value share limbs (host side of k_start_values)
 double host_start_value(uint64_t a0, uint64_t a1, uint64_t a2, double l);
 
+// ---- extend.hip: mmg_sampler_extend (extend_kernels.h)
+// one chain's trace[S][n] (S even): row j becomes row 2 j for j < S / 2, rows S / 2 .. S - 1 become +0.0; scratch: n * S / 2 doubles
+void launch_trace_halve(double *trace, double *scratch, uint32_t n, uint32_t S, hipStream_t s);
+// sum_log / sum_log2 [n_chains][n] from the first `rows` rows of every chain of trace[n_chains][S][n], in sample order as k_update adds them
+void launch_moments_rebuild(const double *trace, double *sum_log, double *sum_log2, uint32_t n, uint32_t n_chains, uint32_t S, uint32_t rows, hipStream_t s);
+
 // ---- order.hip: a transcript order from the hit graph when the caller passes none
 // sorted, duplicate-free directed edges u << 32 | v (both directions) of the co-occurrence graph of a content-hash sample of the rows
 hipError_t order_cooccurrence_edges(bool idx64, uint64_t m, uint64_t nnz, const void *d_rp, const uint32_t *d_col, std::vector<uint64_t> &edges, hipStream_t s,

@@ -44,6 +44,10 @@ struct mmg_summary {
     std::vector<uint64_t> h_vid;
     std::vector<double> h_vscale;
     uint32_t done = 0;             // samples whose derived rows exist
+    // the sampler's count of mmg_sampler_extend calls and its value at _begin: an extend in between replaced the samples the rows
+    // were derived from
+    std::shared_ptr<const std::atomic<uint64_t>> extensions;
+    uint64_t extensions_at_begin = 0;
     bool finished = false;
     std::vector<DevBuf<uint8_t>> scratch; // device buffers that live until _finish (the pointers below point into them)
     uint64_t *d_iptr = nullptr, *d_gptr = nullptr;
@@ -69,6 +73,13 @@ static hipError_t scratch_alloc(std::vector<DevBuf<uint8_t>> &list, void **ptr, 
 }
 
 static inline unsigned blocks_of(uint64_t n) { return (unsigned)((n + 255) / 256); }
+
+static int check_not_extended(const mmg_summary *q)
+{
+    if (q->extensions && q->extensions->load() != q->extensions_at_begin)
+        return fail(MMG_ERR_STATE, "the sampler was extended after mmg_summary_begin: the samples this summary was begun on no longer exist");
+    return MMG_OK;
+}
 
 // The per-series summary kernel sorts and transforms in LDS up to 8192 samples (128 KB of the 160 KB a workgroup may hold); longer
 // traces take the same steps in a global workspace, SERIES_WS_GROUPS workgroups striding over the series.
@@ -148,6 +159,8 @@ extern "C" int mmg_summary_begin(mmg_sampler *smp, const mmg_summary_desc *d, mm
     q->p = p;
     q->trace = v.d_trace + (size_t)d->chain * S * n;
     q->seed = v.cfg.seed; q->alpha = v.cfg.alpha;
+    q->extensions = v.extensions;
+    q->extensions_at_begin = v.extensions ? v.extensions->load() : 0;
     if (nv) { q->h_vid.assign(d->virtual_id, d->virtual_id + nv); q->h_vscale.assign(d->virtual_scale, d->virtual_scale + nv); }
     HIP_TRY(q->st.create(hipStreamNonBlocking));
     hipStream_t st = q->st.get();
@@ -190,6 +203,7 @@ extern "C" int mmg_summary_begin(mmg_sampler *smp, const mmg_summary_desc *d, mm
 extern "C" int mmg_summary_advance(mmg_summary *q, int samples_done)
 {
     if (!q) return fail(MMG_ERR_ARG, "NULL summary");
+    if (int rc = check_not_extended(q)) return rc;
     if (q->finished) return fail(MMG_ERR_STATE, "the summary is finished");
     if (samples_done < (int)q->done || samples_done > (int)q->S) return fail(MMG_ERR_ARG, "samples_done out of range");
     if ((uint32_t)samples_done == q->done) return MMG_OK;
@@ -213,6 +227,7 @@ extern "C" int mmg_summary_advance(mmg_summary *q, int samples_done)
 extern "C" int mmg_summary_finish(mmg_summary *q)
 {
     if (!q) return fail(MMG_ERR_ARG, "NULL summary");
+    if (int rc = check_not_extended(q)) return rc;
     if (q->finished) return MMG_OK;
     if (q->done != q->S) return fail(MMG_ERR_STATE, "mmg_summary_finish before every sample was handed to mmg_summary_advance");
     HIP_TRY(hipSetDevice(q->device));
@@ -324,6 +339,7 @@ extern "C" int mmg_summary_get_proportions(mmg_summary *q, int kind, double *mea
 extern "C" int mmg_summary_get_rows(mmg_summary *q, int kind, int first_sample, int n_samples, double *out)
 {
     if (!q || !out) return fail(MMG_ERR_ARG, "NULL argument");
+    if (int rc = check_not_extended(q)) return rc;
     const double *src = nullptr;
     size_t width = 0;
     switch (kind) {

@@ -31,6 +31,7 @@ struct mmg_sampler {
     int iter = 0;          // completed iterations
     bool sampled = false;  // sample() issued for the current iteration, update() pending
     int64_t n_kept = 0;
+    std::shared_ptr<std::atomic<uint64_t>> extensions = std::make_shared<std::atomic<uint64_t>>(0); // mmg_sampler_extend calls (SamplerView)
     // timing
     // HIP-event pairs around timed launches: a pair is harvested (its time added to the sums, its events back on the free list) as soon
     // as it has completed, so the pool stays as large as the launches in flight however long the chain
@@ -66,6 +67,7 @@ int mmg::sampler_view(mmg_sampler *s, SamplerView *v)
 {
     if (!s || !v) return fail(MMG_ERR_ARG, "NULL argument");
     v->p = s->p; v->cfg = s->cfg; v->d_trace = s->d_trace.get(); v->stream = s->cur; v->iter = s->iter; v->n_kept = s->n_kept;
+    v->extensions = s->extensions;
     return MMG_OK;
 }
 
@@ -380,6 +382,41 @@ extern "C" int mmg_sampler_run(mmg_sampler *s, int n_iter)
         rc = mmg_sampler_update(s);
         if (rc) return rc;
     }
+    return MMG_OK;
+}
+
+// A finished run of length L becomes the first half of a run of length 2 L (include/mmgibbs.h).  A chain is a pure
+// function of (problem, seed, chain, iteration) and gibbs_iter enters nowhere but the thinning of mmg_sampler_update, so what a run
+// planned at 2 L holds after L iterations is: the even samples of this run in rows 0 .. S / 2 - 1, zeros behind them, the moment sums
+// of those samples, and everything else as it is here.
+extern "C" int mmg_sampler_extend(mmg_sampler *s)
+{
+    if (!s) return fail(MMG_ERR_ARG, "NULL sampler");
+    // what the configuration rules out first (no run length changes these), then the state of the run
+    if (s->cfg.trace_len % 2 != 0) return fail(MMG_ERR_ARG, "extend: trace_len must be even (every second sample is kept)");
+    if (s->cfg.gibbs_iter >= (1 << 30)) return fail(MMG_ERR_ARG, "extend: gibbs_iter must be below 2^30 (twice its value is the new length)");
+    if (!s->cfg.keep_trace || !s->d_trace.get()) return fail(MMG_ERR_STATE, "extend: sampler was created with keep_trace == 0 (the kept samples are rebuilt from the trace)");
+    if (s->sampled) return fail(MMG_ERR_STATE, "extend: between sample() and update(); call update()");
+    if (s->iter != s->cfg.gibbs_iter || s->n_kept != (int64_t)s->cfg.trace_len)
+        return fail(MMG_ERR_STATE, "extend: the planned run is not complete (iteration == gibbs_iter with all trace_len samples kept)");
+    const mmg_problem *p = s->p;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->cur));
+    const size_t C = (size_t)s->cfg.n_chains, n = p->n, S = (size_t)s->cfg.trace_len;
+    // everything the call acquires, before the first kernel: a failure here leaves the sampler as it was
+    DevBuf<double> d_scratch;
+    HIP_TRY(d_scratch.alloc(n * (S / 2)));
+    for (size_t c = 0; c < C; ++c) launch_trace_halve(s->d_trace.get() + c * S * n, d_scratch.get(), (uint32_t)n, (uint32_t)S, s->cur);
+    launch_moments_rebuild(s->d_trace.get(), s->d_mom.get(), s->d_mom.get() + C * n, (uint32_t)n, (uint32_t)C, (uint32_t)S, (uint32_t)(S / 2), s->cur);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s->cur)); // (the scratch goes at return)
+    s->cfg.gibbs_iter *= 2;
+    s->n_kept = (int64_t)(S / 2);
+    // the pending marks stand for samples that have completed: back to their pool
+    for (const auto &mk : s->marks) s->mark_free.push_back(mk.second);
+    s->marks.clear();
+    s->fired_upto = s->iter;
+    s->extensions->fetch_add(1);
     return MMG_OK;
 }
 

@@ -197,6 +197,7 @@ class Sampler:
         self.n = problem.info.n
         self.n_chains = n_chains
         self.trace_len = trace_len
+        self.gibbs_iter = gibbs_iter
         mu0 = np.ascontiguousarray(mu0, np.float64)
         if mu0.size != self.n:
             raise ValueError("mu0 must have n entries")
@@ -210,6 +211,12 @@ class Sampler:
 
     def run(self, n_iter):
         check(self._lib.mmg_sampler_run(self._h, n_iter))
+
+    def extend(self):
+        """mmg_sampler_extend: a run at its planned end becomes the first half of a run of twice the length (every second sample kept,
+        the moments rebuilt); run(gibbs_iter) more iterations then give what a sampler planned at 2 * gibbs_iter holds at its end."""
+        check(self._lib.mmg_sampler_extend(self._h))
+        self.gibbs_iter *= 2
 
     def sample(self):
         check(self._lib.mmg_sampler_sample(self._h))
