@@ -232,6 +232,25 @@ int mmg_device_count(int *count);
 int mmg_problem_create(const mmg_problem_desc *desc, int device, mmg_problem **out);
 int mmg_problem_create_synthetic(const mmg_synth_desc *desc, int device, mmg_problem **out);
 int mmg_problem_info_get(const mmg_problem *p, mmg_problem_info *info);
+/* The single-chain sample launch of a sliced-ELL problem (mmg_problem_info stays as ABI 8 laid it out; this is what it would have
+ * gained): which instantiation of k_sample_sell runs, and how the launch's ranges are balanced by the cost model that cut them. */
+typedef struct mmg_k1_info {
+    int32_t lean;            /* 0: the general kernel; 1: the instantiation for lists of register-path and empty tiles only */
+    int32_t fixed_walk;      /* straight-line walks for every group count up to 8 (fewer than 5 groups per tile on average) */
+    int32_t range_tile_cost; /* v >= 1: the ranges price a register-path tile v + 1 per group of its block; 0: a constant (MMG_OPT_K1_RANGE_COST = 0) */
+    int32_t reserved;
+    uint64_t n_ranges;       /* ranges of the launch that hold work */
+    uint64_t range_cost_max; /* the dearest range, in the model's units */
+    double range_cost_mean;  /* over the n_ranges ranges (a launch of several generations ends in ranges of half the cost) */
+    uint64_t range_tiles_max;/* tiles of the longest range */
+    uint64_t n_list;         /* entries of the tile list the launch walks */
+    uint64_t list_cost;      /* their modelled cost */
+} mmg_k1_info;
+int mmg_problem_k1_info_get(const mmg_problem *p, mmg_k1_info *info);
+/* The ranges themselves: bound[0 .. n] (n = mmg_problem_info.sample_grid) are list entries, range c holds entries [bound[c], bound[c + 1]);
+ * cum_cost[c] is the modelled cost of the entries in front of bound[c], cum_groups[c] the 256-byte groups of their blocks (whatever the
+ * model).  Any may be NULL.  MMG_ERR_STATE without a sliced-ELL stream. */
+int mmg_problem_k1_ranges(const mmg_problem *p, uint64_t *bound, uint64_t *cum_cost, uint64_t *cum_groups);
 /* Copies the device CSR back in STORED order (row_ptr m+1 u64, col_idx nnz u32 in the caller's transcript numbering,
  * k m u32; any may be NULL): what a checker needs to replay the chain row by row -- stored row i walks its hits in the
  * returned order and draws from random stream row_id_base + i. */
@@ -525,7 +544,13 @@ enum {
     MMG_OPT_FOLD_SLAB = 19,        /* v >= 1: at most v features per slab of mmg_fold_create / _of_traces (slab edges on small inputs)           */
     MMG_OPT_SIM_CHUNK = 20,        /* v >= 1: v features per chunk of mmg_sim_run's Gram kernel (chunk edges on small inputs; read by mmg_sim_create) */
     MMG_OPT_ISO_SLAB = 21,         /* v >= 1: at most v groups per slab of mmg_isoform_create / _of_traces (slab edges on small inputs)          */
-    MMG_OPT_COUNT_ = 22
+    MMG_OPT_K1_LEAN = 22,          /* k_sample_sell's instantiation for lists of register-path and empty tiles only, read by mmg_problem_create*: 0 never,
+                                      1 forced -- refused with MMG_ERR_ARG for a problem
+                                      that has far, CSR-walked or multiplicity tiles; default: wherever the list allows it */
+    MMG_OPT_K1_RANGE_COST = 23,    /* 0: the ranges of the k = 1 launches cut by a constant per tile, as before the tiles were priced by their groups;
+                                      v >= 1: a register-path tile priced v + 1 per group of its block (the A/B of the ratio; default 6) */
+    MMG_OPT_K1_RANGES = 24,        /* v >= 1: at most v ranges (workgroups) per k = 1 launch, one generation, no tapered end (long ranges on small inputs) */
+    MMG_OPT_COUNT_ = 25
 };
 int mmg_selftest_option(int option, int value);
 /* What the library holds: counts[3] = device buffers, streams, events (tests: every call gives back what it acquired). */
@@ -546,6 +571,9 @@ int mmg_selftest_gibbs_shards(mmg_sampler *const *samplers, int n_shards, int n_
 /* What the HIP runtime reports about the k == NULL sliced-ELL sample kernel on `device`: registers, LDS and scratch bytes per
  * thread, and resident 64-thread workgroups per CU (hipOccupancyMaxActiveBlocksPerMultiprocessor). */
 int mmg_selftest_kernel_info(int device, int *vgprs, int *lds_bytes, int *scratch_bytes, int *resident_per_cu);
+/* The same about the instantiation the single-chain launch of a problem with 32-bit offsets runs for (lean, fixed_walk) as
+ * mmg_k1_info reports them. */
+int mmg_selftest_k1_kernel_info(int device, int lean, int fixed_walk, int *vgprs, int *lds_bytes, int *scratch_bytes, int *resident_per_cu);
 /* Evaluates the library's own log / exp / sqrt / 1/x on x[0..n) (device >= 0: in a kernel
  * on that device; device == -1: the host instantiation of the same inline code). */
 int mmg_selftest_math(int device, int64_t n, const double *x, double *out_log, double *out_exp,

@@ -39,7 +39,7 @@ class MMGError(RuntimeError):
 
 LAYOUT_CANONICAL, LAYOUT_KEEP_ROWS = 0, 1
 # mmg_selftest_option ids
-OPT_SAMPLE_KERNEL, OPT_FORCE_IDX64, OPT_SELL_WAVES_PER_CU, OPT_EM_KERNEL, OPT_EM_GRID, OPT_FUSE_CHAINS, OPT_CNT_REPLICAS, OPT_GROUP_FAIL, OPT_DERIVE_ORDER, OPT_WIRE_CHECK, OPT_BIGK_PER_WAVE, OPT_BIGK_SIDE_STREAM, OPT_FAIL_ALLOC, OPT_CONV_SLAB, OPT_DIFF_TRACE_ROWS, OPT_ASSIGN_WAVES, OPT_CONTRAST_SLAB, OPT_POOL_SLAB, OPT_PAIRS_SLAB, OPT_FOLD_SLAB, OPT_SIM_CHUNK, OPT_ISO_SLAB = range(22)
+OPT_SAMPLE_KERNEL, OPT_FORCE_IDX64, OPT_SELL_WAVES_PER_CU, OPT_EM_KERNEL, OPT_EM_GRID, OPT_FUSE_CHAINS, OPT_CNT_REPLICAS, OPT_GROUP_FAIL, OPT_DERIVE_ORDER, OPT_WIRE_CHECK, OPT_BIGK_PER_WAVE, OPT_BIGK_SIDE_STREAM, OPT_FAIL_ALLOC, OPT_CONV_SLAB, OPT_DIFF_TRACE_ROWS, OPT_ASSIGN_WAVES, OPT_CONTRAST_SLAB, OPT_POOL_SLAB, OPT_PAIRS_SLAB, OPT_FOLD_SLAB, OPT_SIM_CHUNK, OPT_ISO_SLAB, OPT_K1_LEAN, OPT_K1_RANGE_COST, OPT_K1_RANGES = range(25)
 
 
 class ProblemDesc(C.Structure):
@@ -60,6 +60,12 @@ class ProblemInfo(C.Structure):
                 ("device_bytes", C.c_uint64), ("index_bits", C.c_int32), ("sample_kernel", C.c_int32),
                 ("stream_bytes", C.c_uint64), ("fast_tiles", C.c_uint64), ("far_tiles", C.c_uint64), ("padded_slots", C.c_uint64),
                 ("layout", C.c_int32), ("tx_renumbered", C.c_int32), ("sample_grid", C.c_int32), ("cu_count", C.c_int32)]
+
+
+class K1Info(C.Structure):
+    _fields_ = [("lean", C.c_int32), ("fixed_walk", C.c_int32), ("range_tile_cost", C.c_int32), ("reserved", C.c_int32),
+                ("n_ranges", C.c_uint64), ("range_cost_max", C.c_uint64), ("range_cost_mean", C.c_double),
+                ("range_tiles_max", C.c_uint64), ("n_list", C.c_uint64), ("list_cost", C.c_uint64)]
 
 
 class SummaryDesc(C.Structure):
@@ -116,6 +122,9 @@ SYMBOLS = {
     "mmg_problem_create": (C.c_int, [C.POINTER(ProblemDesc), C.c_int, C.POINTER(C.c_void_p)]),
     "mmg_problem_create_synthetic": (C.c_int, [C.POINTER(SynthDesc), C.c_int, C.POINTER(C.c_void_p)]),
     "mmg_problem_info_get": (C.c_int, [C.c_void_p, C.POINTER(ProblemInfo)]),
+    "mmg_problem_k1_info_get": (C.c_int, [C.c_void_p, C.POINTER(K1Info)]),
+    "mmg_problem_k1_ranges": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mmg_selftest_k1_kernel_info": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mmg_problem_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmg_problem_tx_perm": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mmg_selftest_option": (C.c_int, [C.c_int, C.c_int]),

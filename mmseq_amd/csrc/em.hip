@@ -1,5 +1,6 @@
 // em.hip -- device TU: EM sweeps (src/mmseq.cpp:741-811), kernels in em_kernels.h
 #include "gibbs_kernels.h"
+#undef MMG_K1_STAMPS // (a diagnostics build's stamp buffer belongs to k1.hip, which instantiates the kernel that writes it)
 #include "sell_kernels.h"
 #include "em_kernels.h"
 #include "mmg_launch.h"

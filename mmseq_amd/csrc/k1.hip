@@ -7,8 +7,10 @@
 
 namespace mmg {
 
-const void *k1_sell_kernel(bool idx64, bool has_k, bool fixed_walk)
+const void *k1_sell_kernel(bool idx64, bool has_k, bool fixed_walk, bool lean)
 {
+    if (!has_k && lean && fixed_walk) return idx64 ? (const void *)k_sample_sell<uint64_t, false, 8, 1, false, true, true> : (const void *)k_sample_sell<uint32_t, false, 8, 1, false, true, true>;
+    if (!has_k && lean) return idx64 ? (const void *)k_sample_sell<uint64_t, false, 8, 1, false, false, true> : (const void *)k_sample_sell<uint32_t, false, 8, 1, false, false, true>;
     if (!has_k && fixed_walk) return idx64 ? (const void *)k_sample_sell<uint64_t, false, 8, 1, false, true> : (const void *)k_sample_sell<uint32_t, false, 8, 1, false, true>;
     if (idx64) return has_k ? (const void *)k_sample_sell<uint64_t, true, 8> : (const void *)k_sample_sell<uint64_t, false, 8>;
     return has_k ? (const void *)k_sample_sell<uint32_t, true, 8> : (const void *)k_sample_sell<uint32_t, false, 8>;
@@ -34,6 +36,19 @@ extern "C" int mmg_selftest_bigk_stats(unsigned long long *out) // reads and cle
     unsigned long long zero[16] = {0};
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bigk_stats), sizeof(zero)) != hipSuccess) return 1;
     return hipMemcpyToSymbol(HIP_SYMBOL(g_bigk_stats), zero, sizeof(zero)) == hipSuccess ? 0 : 1;
+}
+#endif
+
+#if defined(MMG_K1_STAMPS)
+// hands back and clears the stamps of the first n_workgroups workgroups (diagnostics build only; sell_kernels.h, tools/k1_timeline.py)
+extern "C" int mmg_selftest_k1_stamps(unsigned long long *out, unsigned long long n_workgroups)
+{
+    if (!out || n_workgroups > K1_STAMP_CAP) return 1;
+    const size_t bytes = (size_t)n_workgroups * K1_STAMP_WORDS * sizeof(unsigned long long);
+    void *sym = nullptr;
+    if (hipDeviceSynchronize() != hipSuccess || hipGetSymbolAddress(&sym, HIP_SYMBOL(g_k1_stamps)) != hipSuccess) return 1;
+    if (hipMemcpy(out, sym, bytes, hipMemcpyDeviceToHost) != hipSuccess) return 1;
+    return hipMemset(sym, 0, bytes) == hipSuccess ? 0 : 1;
 }
 #endif
 

@@ -222,6 +222,16 @@ struct mmg_problem {
     mmg::DevBuf<uint64_t> d_colcnt;             // hits per transcript, for the EM scale words (lazy)
     bool order_derived = false;                 // the renumbering came from the hit graph (order.hip), not from the caller's tx_order
     bool k1_fixed_walk = false;    // the k = 1 sample kernel's straight-line instantiation (fewer than 5 groups per register-path tile on average)
+    // the single-chain launch runs k_sample_sell's lean instantiation (sell_kernels.h: LEAN): its list holds nothing but
+    // register-path and empty tiles
+    bool k1_lean = false;
+    // what the constant model of the kernel choice and of the order derivation makes of a sweep (2 per register-path tile): those
+    // thresholds were fitted in its units; the ranges are cut by h_sell_cum / h_cum1, which price a tile by its groups
+    uint64_t sweep_cost_const = 0;
+    uint64_t range_tile_cost = 0;  // the ranges price a register-path tile this + 1 per group of its block (0: the constant model, MMG_OPT_K1_RANGE_COST = 0)
+    uint64_t range_cost_max = 0, range_cost_sum = 0, range_count = 0; // modelled cost of the single-chain launch's non-empty ranges
+    uint64_t range_tiles_max = 0;                                     // tiles of its longest range
+    std::vector<uint64_t> h_chunk1, h_chunk1_groups;                  // its ranges: entries of the list h_cum1 prices; groups in front of every bound
     bool groups_reordered = false; // tx_order given and the library reordered its groups (spec version 7)
     bool order_skipped = false;    // an order from the hit graph was called for but not tried (device memory) or could not be built: the caller's order stands
     bool renumbered() const { return !h_int_of_ext.empty(); }

@@ -29,7 +29,8 @@ extern "C" const char *mmg_last_error(void) { return g_err.c_str(); }
 extern "C" int mmg_abi_version(void) { return MMG_ABI_VERSION; }
 
 // self-test overrides (mmg_selftest_option): -1 = the library decides
-static std::atomic<int> g_opt[MMG_OPT_COUNT_] = {{-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}};
+static std::atomic<int> g_opt[MMG_OPT_COUNT_] = {{-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}};
+static_assert(MMG_OPT_COUNT_ == 25, "one initialiser per option above");
 static std::atomic<int64_t> g_acquired{0}; // acquisitions through the owners since MMG_OPT_FAIL_ALLOC was last set
 static std::atomic<int64_t> g_live[3] = {{0}, {0}, {0}};
 int mmg::opt(int o) { return g_opt[o].load(std::memory_order_relaxed); }
@@ -114,6 +115,22 @@ constexpr uint64_t SELL_FAST_TILE_COST = 2;
 constexpr uint64_t SELL_FAR_TILE_COST = 2;   // plus SELL_FAR_ENTRY_COST per entry of the far list
 constexpr uint64_t SELL_FAR_ENTRY_COST = 4;
 constexpr uint64_t SELL_SLOW_TILE_COST = 48; // a CSR-walked tile
+// (the four above: the constant model -- the kernel choice, the order derivation and the ranges of the multiplicity launch are fitted in
+// its units, mmg_problem::sweep_cost_const; MMG_OPT_K1_RANGE_COST = 0 cuts every launch's ranges by it, as they were)
+// The ranges of the k = 1 launches (single chain, pairs, EM) are cut by what a tile costs: RANGE_TILE_COST + 1 per group of its block.
+// Rows are stored by band, then by length, so the tiles of a band run from short to long, and ranges of equal tile COUNT differ by
+// their groups (the headline, 1 + Poisson(19) hits: 4 ... 7 groups) -- the last generation's spread is the launch's tail.  The ratio
+// is fitted to the timeline of a launch (tools/k1_timeline.py, profiles/k1_timeline_before.txt: the duration of a range against its
+// tiles and its groups, all ranges of a launch competing for the device): 50 M x 20 hits 1.30 us per tile + 0.111 us per group with
+// the ranges cut by tile count, 1.04 + 0.157 with the tile counts spread; 5 M x 8 hits 0.73 + 0.060 and 0.46 + 0.048 -- a group costs
+// a tenth to a sixth of a tile, NOT the two tiles per group of the shard model below: that one prices whole devices, where the bytes
+// of the stream bound the time; inside a launch a range shares the stream with 7 000 others and its own time is the latency of its
+// tiles' dependent steps.  Same-box K1 with v per tile + 1 per group (profiles/k1_fixed_cost_ab.md), 50 M x 20 hits / 5 M x 8 hits:
+// constant 0.2021 / 0.0203 ms, v = 2 0.2015 / 0.0207, 4 0.2009 / 0.0200, 6 0.2003 / 0.0198, 12 0.2013 / 0.0198; with one tile per
+// two groups (the shard model's ratio) 5 M x 8 hits LOST 11 %: the ranges at the long end of a band got too few tiles.
+// Far and CSR-walked tiles keep the constant model's ratios to a register-path tile of 5.4 groups: an entry of the far list two of
+// them, a CSR-walked tile 24.  MMG_OPT_K1_RANGE_COST = v >= 1 prices a tile v + 1 per group (the A/B of the ratio).
+constexpr uint64_t RANGE_TILE_COST = 6;
 // the cut into read shards (h_shard_cum): a register-path tile of 5.4 groups (config 3) costs 1 + 2 * 5.4 = 11.8 of these units
 constexpr uint64_t SHARD_TILE_COST = 1, SHARD_GROUP_COST = 2;
 constexpr uint64_t SHARD_FAR_ENTRY_COST = 24;  // measured (tools/shard_balance.py): a far tile with one entry per lane takes 3 x a register-path tile
@@ -230,9 +247,31 @@ static int problem_build_sell(mmg_problem *p, const std::vector<uint64_t> &seg_s
     auto is_far = [&](uint64_t t) { return far_nf[t] <= 255u; };
     d_tile_row.reset();
     d_td.reset();
-    auto resident_raw = [&](bool has_k) { // workgroups of the kernel the device holds at once
+    auto has_k_rows = [&](uint64_t t) { return p->d_k.get() != nullptr && td[t].knot1 > 0; };
+    // The lean instantiation of the k = 1 kernel (sell_kernels.h: LEAN) when no tile needs anything else: every tile with hits on the
+    // register path in its band's own window (then the loop below stores it as SELL_FAST whatever window is in force), none with
+    // multiplicities.  MMG_OPT_K1_LEAN: 0 never, 1 forced -- refused where a tile needs the general kernel.
+    {
+        bool only_fast = true;
+        uint64_t groups = 0, n_blocks = 0;
+        for (uint64_t t = 0; t < nt && only_fast; ++t) {
+            if (td[t].nnz == 0) continue;
+            only_fast = qualifies(td[t]) && !has_k_rows(t);
+            groups += (td[t].maxlen + 3) / 4;
+            ++n_blocks;
+        }
+        const int want = opt(MMG_OPT_K1_LEAN);
+        if (want >= 1 && !only_fast) return fail(MMG_ERR_ARG, "MMG_OPT_K1_LEAN forced on a problem with far, CSR-walked or multiplicity tiles");
+        p->k1_lean = only_fast && want != 0;
+        if (p->k1_lean) p->k1_fixed_walk = n_blocks > 0 && groups < 5 * n_blocks; // (as below: known here because every block is a register-path tile's)
+    }
+    // workgroups of the kernel the device holds at once.  A lean problem: of the instantiation its launch runs.  Otherwise of the general
+    // kernel with the generic walk: whether the launch takes the straight-line walk is known only once the tiles are laid out, which
+    // needs the ranges, which need this number (both instantiations report 7 waves per SIMD).
+    auto resident_raw = [&](bool has_k) {
         int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k1_sell_kernel(p->idx64, has_k, false), 64, 0) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 16; }
+        const void *fn = has_k ? k1_sell_kernel(p->idx64, true) : k1_sell_kernel(p->idx64, false, p->k1_lean && p->k1_fixed_walk, p->k1_lean);
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64, 0) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 16; }
         if (per_cu > 32) per_cu = 32;
         if (opt(MMG_OPT_SELL_WAVES_PER_CU) >= 1 && opt(MMG_OPT_SELL_WAVES_PER_CU) < per_cu) per_cu = opt(MMG_OPT_SELL_WAVES_PER_CU);
         return (uint64_t)p->cu_count * per_cu;
@@ -244,7 +283,11 @@ static int problem_build_sell(mmg_problem *p, const std::vector<uint64_t> &seg_s
     // (config 3: 109 tiles per range in one generation -> 27 in four, -2 to -4 %).  K1 is bound by HBM traffic now, and every range
     // costs a window load and a flush of its counts (0.14 GB written per launch in five generations): 36 tiles per range (three
     // generations at config 3) 0.2387 ms against 0.2467 at 24 and 0.2400 at 48; the pair kernel 1.617 / 1.630 / 1.617 ms.
+    // Rerun with the ranges cut by groups and the lean kernel (same box, K1 at 50 M x 20 hits; profiles/k1_fixed_cost_ab.md): 24 tiles per range
+    // 0.2087 ms, 36 0.2091, 48 0.2091 -- no difference left to choose by; 36 stays.
+    const bool plain_ranges = opt(MMG_OPT_SELL_WAVES_PER_CU) >= 1 || opt(MMG_OPT_K1_RANGES) >= 1; // one generation, no tapered end
     auto generations = [&](uint64_t resident) {
+        if (opt(MMG_OPT_K1_RANGES) >= 1) return std::max<uint64_t>(1, std::min<uint64_t>(nt, (uint64_t)opt(MMG_OPT_K1_RANGES)));
         if (opt(MMG_OPT_SELL_WAVES_PER_CU) >= 1) return resident;
         const uint64_t g = (nt + resident * (SELL_TILES_PER_RANGE / 2)) / (resident * SELL_TILES_PER_RANGE); // nearest
         return std::min<uint64_t>(nt, resident * std::min<uint64_t>(16, std::max<uint64_t>(1, g)));
@@ -254,23 +297,33 @@ static int problem_build_sell(mmg_problem *p, const std::vector<uint64_t> &seg_s
     // ranges of the two sample launches of a problem with multiplicities -- tiles whose rows all have k = 1, and the others, where a
     // row draws k times (k <= K_SMALL) or runs a binomial per hit.  Identical reads pile up on few hit sets of few abundant
     // transcripts: without their cost in the ranges one workgroup ends up with most of them (20 x the kernel time at config 3).
-    auto has_k_rows = [&](uint64_t t) { return p->d_k.get() != nullptr && td[t].knot1 > 0; };
+    // A tile's block in groups, and its price for the ranges (the constants' comment: RANGE_*); cumk stays in the constant model's units
+    // (a launch and ranges of its own, dominated by the draws).
+    auto tile_groups = [&](uint64_t t) -> uint64_t { return qualifies(td[t]) ? (td[t].maxlen + 3) / 4 : is_far(t) ? (far_nn[t] + 3) / 4 : 0; };
+    const bool by_groups = opt(MMG_OPT_K1_RANGE_COST) != 0;
+    const uint64_t tile_cost = opt(MMG_OPT_K1_RANGE_COST) >= 1 ? (uint64_t)opt(MMG_OPT_K1_RANGE_COST) : RANGE_TILE_COST;
+    const uint64_t far_entry_cost = 2 * tile_cost + 11, slow_tile_cost = 24 * tile_cost + 130; // (2 and 24 tiles of 5.4 groups)
     p->h_sell_cum.assign(nt + 1, 0);
     std::vector<uint64_t> cum1(nt + 1, 0), cumk(nt + 1, 0);
     uint64_t n_hask = 0;
+    p->sweep_cost_const = 0;
+    p->range_tile_cost = by_groups ? tile_cost : 0;
     for (uint64_t t = 0; t < nt; ++t) {
         const uint64_t c = td[t].nnz == 0 ? 0 : qualifies(td[t]) ? SELL_FAST_TILE_COST : is_far(t) ? SELL_FAR_TILE_COST + SELL_FAR_ENTRY_COST * far_nf[t] : SELL_SLOW_TILE_COST;
-        p->h_sell_cum[t + 1] = p->h_sell_cum[t] + c;
+        const uint64_t cg = !by_groups ? c : td[t].nnz == 0 ? 0 : qualifies(td[t]) ? tile_cost + tile_groups(t)
+                                  : is_far(t) ? tile_cost + tile_groups(t) + far_entry_cost * far_nf[t] : slow_tile_cost;
+        p->sweep_cost_const += c;
+        p->h_sell_cum[t + 1] = p->h_sell_cum[t] + cg;
         const bool hk = has_k_rows(t);
         n_hask += hk;
-        cum1[t + 1] = cum1[t] + (hk ? 0 : c);
+        cum1[t + 1] = cum1[t] + (hk ? 0 : cg);
         // a draw costs about as much as a register-path tile per 64 rows (2)
         // (the tile's rows on the binomial chain are skipped here -- the list kernel draws them: what is left draws at most K_SMALL times)
         cumk[t + 1] = cumk[t] + (!hk ? 0 : 2 * c + 2 * (uint64_t)std::min<uint32_t>(td[t].kmax, K_SMALL));
     }
-    // What a sweep over the tiles [0, t) costs, for the cut into read shards (mmg_problem_shard_bounds).  The ranges of ONE launch get by
-    // with "2 per register-path tile": several generations of short ranges even out what the model misses.  A shard is one range per
-    // device and the slowest device sets the pace, so here a register-path tile is priced by what bounds it -- the bytes of its block,
+    // What a sweep over the tiles [0, t) costs, for the cut into read shards (mmg_problem_shard_bounds).  A shard is one range per
+    // device and the slowest device sets the pace, so a register-path tile is priced by what bounds it (as in the ranges of one launch,
+    // above; here with the multiplicities' draws) -- the bytes of its block,
     // ng groups of 256 (K1's time per tile at 2.4 and 5.4 groups per tile: 2.0 and 4.7 us per million rows, i.e. proportional) -- a far
     // tile by its block plus SHARD_FAR_ENTRY_COST per entry of the far list (64 gathers from L2), a CSR-walked tile by the model above.
     p->h_shard_cum.assign(nt + 1, 0);
@@ -288,7 +341,7 @@ static int problem_build_sell(mmg_problem *p, const std::vector<uint64_t> &seg_s
     p->h_tile_row = tile_row;
     std::vector<uint64_t> chunk;
     if (n_hask) weighted_chunks(p->h_sell_cum, grid, chunk); // (with SELL_HASK tiles: only the windows below follow these ranges)
-    else weighted_chunks_tapered(cum1, grid, opt(MMG_OPT_SELL_WAVES_PER_CU) >= 1 ? 0 : resident_grid(false), chunk);
+    else weighted_chunks_tapered(cum1, grid, plain_ranges ? 0 : resident_grid(false), chunk);
     const uint64_t n_ranges = chunk.size() - 1;
     std::vector<SellTile> st(nt);
     uint64_t n_fast = 0, n_far = 0, pos = 0, slots = 0;
@@ -332,14 +385,14 @@ static int problem_build_sell(mmg_problem *p, const std::vector<uint64_t> &seg_s
     }
     // tiles that do not qualify are walked from their far lists or from the CSR inside the same kernel (far rows are sorted last:
     // a contiguous tail); a problem whose tiles cost more than the CSR kernel's on average -- hits uniform over all transcripts -- runs there
-    p->use_sell = p->h_sell_cum[nt] <= p->nnz * 7 / 160 || opt(MMG_OPT_SAMPLE_KERNEL) == 2;
-    if (!p->use_sell) { p->h_sell_cum.clear(); p->h_shard_cum.clear(); p->h_tile_row.clear(); return MMG_OK; }
+    p->use_sell = p->sweep_cost_const <= p->nnz * 7 / 160 || opt(MMG_OPT_SAMPLE_KERNEL) == 2;
+    if (!p->use_sell) { p->k1_lean = false; p->h_sell_cum.clear(); p->h_shard_cum.clear(); p->h_tile_row.clear(); return MMG_OK; }
     p->sell_bytes = pos * 16;
     p->n_sell_tiles = nt;
     p->n_fast_tiles = n_fast;
     p->n_far_tiles = n_far;
     p->padded_slots = slots;
-    p->k1_fixed_walk = n_fast > 0 && slots < 5 * 256 * n_fast; // fewer than 5 groups per register-path tile on average (sell_kernels.h: FIXW)
+    p->k1_fixed_walk = n_fast > 0 && slots < 5 * 256 * n_fast; // (a lean problem: as decided above) fewer than 5 groups per register-path tile on average (sell_kernels.h: FIXW)
     const size_t alloc = p->sell_bytes + 64 + 8 * 256; // head room: tiles without a block prefetch the head of the stream
     HIP_TRY(p->d_sell.alloc(alloc));
     HIP_TRY(hipMemset(p->d_sell.get(), 0, alloc));
@@ -375,6 +428,23 @@ static int problem_build_sell(mmg_problem *p, const std::vector<uint64_t> &seg_s
         p->device_bytes += (s1.size() + sk.size()) * sizeof(SellTile);
     }
     if (!n_hask) p->h_cum1 = cum1;
+    p->h_chunk1 = chunk; // (with SELL_HASK tiles: r1, over the list without them)
+    p->range_cost_max = p->range_cost_sum = p->range_count = p->range_tiles_max = 0;
+    p->h_chunk1_groups.assign(chunk.size(), 0); // groups of the blocks in front of every bound: what the timeline sets durations against
+    for (size_t c = 0; c + 1 < chunk.size(); ++c) {
+        uint64_t g = 0;
+        for (uint64_t e = chunk[c]; e < chunk[c + 1]; ++e) {
+            if (n_hask && e >= p->h_list1_tile.size()) break; // (no tile without multiplicities: the list is one empty entry)
+            g += st[n_hask ? p->h_list1_tile[e] : e].ng();
+        }
+        p->h_chunk1_groups[c + 1] = p->h_chunk1_groups[c] + g;
+        const uint64_t rc = p->h_cum1[chunk[c + 1]] - p->h_cum1[chunk[c]];
+        if (!rc) continue;
+        p->range_cost_max = std::max(p->range_cost_max, rc);
+        p->range_cost_sum += rc;
+        p->range_tiles_max = std::max(p->range_tiles_max, chunk[c + 1] - chunk[c]);
+        ++p->range_count;
+    }
     p->resident1 = resident_raw(false); p->residentk = resident_raw(true);
     if (!n_hask) HIP_TRY(upload_ranges(chunk, st, p->d_sell_chunk)); // (with SELL_HASK tiles: uploaded above, over the list without them)
     { // chains in pairs (k_sample_sell_multi): the register-path tiles without multiplicities in their own ranges, the rest apart
@@ -403,9 +473,9 @@ static int problem_build_sell(mmg_problem *p, const std::vector<uint64_t> &seg_s
                 if (pc > 32) pc = 32;
                 if (opt(MMG_OPT_SELL_WAVES_PER_CU) >= 1 && opt(MMG_OPT_SELL_WAVES_PER_CU) < pc) pc = opt(MMG_OPT_SELL_WAVES_PER_CU);
                 const uint64_t rq = std::max<uint64_t>(1, std::min<uint64_t>(nf, (uint64_t)p->cu_count * pc));
-                const uint64_t gen = opt(MMG_OPT_SELL_WAVES_PER_CU) >= 1 ? rq : std::min<uint64_t>(nf, rq * std::min<uint64_t>(16, std::max<uint64_t>(1, (nf + rq * (SELL_TILES_PER_RANGE / 2)) / (rq * SELL_TILES_PER_RANGE))));
+                const uint64_t gen = opt(MMG_OPT_K1_RANGES) >= 1 ? std::min<uint64_t>(nf, (uint64_t)opt(MMG_OPT_K1_RANGES)) : opt(MMG_OPT_SELL_WAVES_PER_CU) >= 1 ? rq : std::min<uint64_t>(nf, rq * std::min<uint64_t>(16, std::max<uint64_t>(1, (nf + rq * (SELL_TILES_PER_RANGE / 2)) / (rq * SELL_TILES_PER_RANGE))));
                 std::vector<uint64_t> cq;
-                weighted_chunks_tapered(cf, gen, opt(MMG_OPT_SELL_WAVES_PER_CU) >= 1 ? 0 : rq, cq);
+                weighted_chunks_tapered(cf, gen, plain_ranges ? 0 : rq, cq);
                 HIP_TRY(upload_ranges(cq, sf, p->d_sell_chunk_m[q]));
                 p->grid_sell_m[q] = (int)(cq.size() - 1);
             }
@@ -536,7 +606,7 @@ static int problem_build(mmg_problem *p, DevBuf<uint64_t> d_rp64)
 static int problem_create_checked(const mmg_problem_desc *d, int device, const uint64_t *tx_order, ProblemPtr &out);
 
 // what a sweep over the problem costs in the units of the tile ranges (2 per register-path tile; the CSR-tile kernel 2.8 per 64 hits)
-static uint64_t modelled_sweep_cost(const mmg_problem *p) { return p->use_sell && !p->h_sell_cum.empty() ? p->h_sell_cum.back() : p->nnz * 7 / 160; }
+static uint64_t modelled_sweep_cost(const mmg_problem *p) { return p->use_sell && !p->h_sell_cum.empty() ? p->sweep_cost_const : p->nnz * 7 / 160; }
 
 extern "C" int mmg_problem_create(const mmg_problem_desc *d, int device, mmg_problem **out)
 {
@@ -896,7 +966,7 @@ extern "C" int mmg_problem_shard_bounds_timed(const mmg_problem *p, const double
         if (g1) {
             const SellTile *ts = d_t1;
             void *kargs[] = {(void *)&rp, (void *)&ci, (void *)&kk, (void *)&ts, (void *)&hdr1, (void *)&mup, (void *)&ss, (void *)&cnt, (void *)&a};
-            e = hipLaunchKernel(k1_sell_kernel(p->idx64, false, p->k1_fixed_walk), dim3(g1), dim3(64), kargs, 0, 0);
+            e = hipLaunchKernel(k1_sell_kernel(p->idx64, false, p->k1_fixed_walk, p->k1_lean), dim3(g1), dim3(64), kargs, 0, 0);
         }
         if (e == hipSuccess && gk) {
             const SellTile *ts = p->d_sell_tiles_k.get();
@@ -1075,6 +1145,35 @@ extern "C" int mmg_problem_info_get(const mmg_problem *p, mmg_problem_info *info
     return MMG_OK;
 }
 
+extern "C" int mmg_problem_k1_info_get(const mmg_problem *p, mmg_k1_info *info)
+{
+    if (!p || !info) return fail(MMG_ERR_ARG, "NULL argument");
+    std::memset(info, 0, sizeof(*info));
+    if (!p->use_sell) return MMG_OK;
+    info->lean = p->k1_lean ? 1 : 0;
+    info->fixed_walk = p->k1_fixed_walk ? 1 : 0;
+    info->range_tile_cost = (int32_t)p->range_tile_cost;
+    info->n_ranges = p->range_count;
+    info->range_cost_max = p->range_cost_max;
+    info->range_cost_mean = p->range_count ? (double)p->range_cost_sum / (double)p->range_count : 0.0;
+    info->range_tiles_max = p->range_tiles_max;
+    info->n_list = p->h_cum1.empty() ? 0 : p->h_cum1.size() - 1;
+    info->list_cost = p->h_cum1.empty() ? 0 : p->h_cum1.back();
+    return MMG_OK;
+}
+
+extern "C" int mmg_problem_k1_ranges(const mmg_problem *p, uint64_t *bound, uint64_t *cum_cost, uint64_t *cum_groups)
+{
+    if (!p) return fail(MMG_ERR_ARG, "NULL problem");
+    if (!p->use_sell || p->h_chunk1.empty()) return fail(MMG_ERR_STATE, "the problem has no sliced-ELL stream");
+    for (size_t c = 0; c < p->h_chunk1.size(); ++c) {
+        if (bound) bound[c] = p->h_chunk1[c];
+        if (cum_cost) cum_cost[c] = p->h_cum1[p->h_chunk1[c]];
+        if (cum_groups) cum_groups[c] = p->h_chunk1_groups[c];
+    }
+    return MMG_OK;
+}
+
 extern "C" int mmg_problem_download(const mmg_problem *p, uint64_t *row_ptr, uint32_t *col_idx, uint32_t *k)
 {
     if (!p) return fail(MMG_ERR_ARG, "NULL problem");
@@ -1159,6 +1258,23 @@ extern "C" int mmg_selftest_kernel_info(int device, int *vgprs, int *lds_bytes, 
     HIP_TRY(hipFuncGetAttributes(&fa, k1_sell_kernel(false, false)));
     int per_cu = 0;
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k1_sell_kernel(false, false), 64, 0));
+    if (vgprs) *vgprs = fa.numRegs;
+    if (lds_bytes) *lds_bytes = (int)fa.sharedSizeBytes;
+    if (scratch_bytes) *scratch_bytes = (int)fa.localSizeBytes;
+    if (resident_per_cu) *resident_per_cu = per_cu;
+    return MMG_OK;
+}
+
+extern "C" int mmg_selftest_k1_kernel_info(int device, int lean, int fixed_walk, int *vgprs, int *lds_bytes, int *scratch_bytes, int *resident_per_cu)
+{
+    if (lean < 0 || lean > 1) return fail(MMG_ERR_ARG, "no such instantiation");
+    int rc = require_device(device);
+    if (rc) return rc;
+    const void *fn = k1_sell_kernel(false, false, fixed_walk != 0, lean != 0);
+    hipFuncAttributes fa;
+    HIP_TRY(hipFuncGetAttributes(&fa, fn));
+    int per_cu = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64, 0));
     if (vgprs) *vgprs = fa.numRegs;
     if (lds_bytes) *lds_bytes = (int)fa.sharedSizeBytes;
     if (scratch_bytes) *scratch_bytes = (int)fa.localSizeBytes;

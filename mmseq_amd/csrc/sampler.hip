@@ -218,7 +218,8 @@ static int sampler_sample(mmg_sampler *s, bool fold)
             const double *mu = s->d_mu.get() + (size_t)c0 * p->n;
             int32_t *cnt = s->d_cnt.get() + (size_t)c0 * p->n;
             void *kargs[] = {(void *)&rp, (void *)&ci, (void *)&kk, (void *)&ts, (void *)&cs, (void *)&mu, (void *)&ss, (void *)&cnt, (void *)&a};
-            const void *fn = kind == 2 ? k1_sell_far_kernel(p->idx64) : k1_sell_kernel(p->idx64, kind == 1, kind == 0 && p->k1_fixed_walk);
+            // (kind 0 is launched over the problem's main list only: the one mmg_problem::k1_lean speaks of)
+            const void *fn = kind == 2 ? k1_sell_far_kernel(p->idx64) : k1_sell_kernel(p->idx64, kind == 1, kind == 0 && p->k1_fixed_walk, kind == 0 && p->k1_lean);
             HIP_TRY(launch(fn, dim3(grid, nc), dim3(64), kargs));
             return MMG_OK;
         };

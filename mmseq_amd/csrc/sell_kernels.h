@@ -163,6 +163,16 @@ struct RowViewFarTile {
     }
 };
 
+#if defined(MMG_K1_STAMPS)
+// diagnostics build (tools/k1_timeline.py): the timeline of the LAST k_sample_sell launch -- every workgroup of its first chain leaves
+// K1_STAMP_WORDS words: s_memtime at entry, with its first window in LDS, behind its last walk and at exit (the wave's own clock: for
+// the phases of one workgroup), s_memrealtime at entry and at exit (one constant-rate clock for the device: for placing workgroups
+// against each other), blockIdx.x | tiles << 32, and where it ran (HW_ID | XCC_ID << 32, as tools/issue_bench.hip reads them).  Lane 0
+// writes them with ordinary stores.  The stamps cost time themselves: the files are for the shape of a launch, not for its duration.
+constexpr uint32_t K1_STAMP_CAP = 1u << 16, K1_STAMP_WORDS = 8;
+__device__ unsigned long long g_k1_stamps[(size_t)K1_STAMP_CAP * K1_STAMP_WORDS];
+#endif
+
 // FARPF: the instantiation that walks the list of far (and CSR-walked) tiles: the far count and the first far transcript of every lane
 // travel with the block's prefetch, and the first far weight is gathered while the window part is walked.  Without it a far tile is
 // three dependent memory round trips in the middle of its walk (count -> transcript id -> weight): 10 x a register-path tile.
@@ -171,13 +181,21 @@ struct RowViewFarTile {
 // 0.0258 -> 0.0246 ms; 20 M x 12 hits 0.0792 -> 0.0762; 50 M x 16 hits 0.1859 -> 0.1816; at 50 M x 20 hits (5.4 groups per tile: the
 // headline) the stream bounds the kernel and the generic walk is 0.4-0.7 % ahead (0.2254 vs 0.2264): the host picks per problem
 // (mmg_problem::k1_fixed_walk)
-template <typename IdxT, bool HAS_K, int NGC, int REP = 1, bool FARPF = false, bool FIXW = false>
+// LEAN: the instantiation for tile lists that hold nothing but register-path and empty tiles (no far list, no CSR-walked tile, no
+// multiplicity: mmg_problem::k1_lean) -- what the single chain of a problem without far rows runs.  The CSR row walks, the far-tile walk,
+// the far table with its initialisation and flush and every HAS_K / FARPF branch are compiled out: the image is a third of the general
+// kernel's, nothing spills, no wave gets a scratch slot, and a workgroup's prologue and epilogue touch 4 KB of LDS instead of 5
+// (profiles/k1_fixed_cost_ab.md).  The walk is the one FIXW selects.  Same additions, comparisons and draws: bit-identical.
+// (Tried inside it: straight-line bodies for 4 ... 7 groups only, the generic walk for the rest -- K1 at the headline 0.2066 against
+// 0.2084 ms, -0.9 %, but 2 spilled VGPRs and 12 bytes of scratch per lane: it misses what this instantiation is for, and is not kept.)
+template <typename IdxT, bool HAS_K, int NGC, int REP = 1, bool FARPF = false, bool FIXW = false, bool LEAN = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HAS_K ? 5 : (FARPF ? 6 : 7), HAS_K ? 5 : (FARPF ? 6 : 7)))) void k_sample_sell(const IdxT *__restrict__ row_ptr, const uint32_t *__restrict__ col_idx,
                                                     const uint32_t *__restrict__ kmult, const SellTile *__restrict__ tiles, const uint64_t *__restrict__ chunk_tile,
                                                     const double *__restrict__ gmu /* [grid.y][n] */, const uint8_t *__restrict__ stream,
                                                     int32_t *gcnt /* [grid.y][n] */, SampleArgs a)
 {
     constexpr int WIN = (int)SELL_WIN;
+    static_assert(!LEAN || (!HAS_K && !FARPF && REP == 1), "the lean instantiation is the k = 1 kernel without far lists");
     __shared__ __attribute__((aligned(16))) double s_mu[WIN + 1]; // [WIN] stays 0.0: what pad slots read
     // REP replicas of the counts (lane l adds to replica l % REP) were tried against same-address serialisation of the LDS
     // atomics: with one atomic per ROW they only cost (0.433 ms with 1, 0.445 / 0.455 / 0.473 with 2 / 4 / 8 at cfg 3)
@@ -194,6 +212,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HAS_K ? 5 : 
     __shared__ uint32_t s_fkey[FAR_SLOTS];
     __shared__ int32_t s_fcnt[FAR_SLOTS];
     const uint32_t lane = threadIdx.x;
+#if defined(MMG_K1_STAMPS)
+    const uint64_t st_entry = __builtin_amdgcn_s_memtime(), st_entry_rt = __builtin_amdgcn_s_memrealtime();
+#endif
     // grid.y = chain: the tile lists that only some rows are on (multiplicities, far rows) are walked for every chain of a sampler
     // in one launch -- their launches are bound by a few long rows, eight of them side by side fill the GPU eight times better
     gmu += (size_t)blockIdx.y * a.n;
@@ -212,7 +233,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HAS_K ? 5 : 
     const SellTile *__restrict__ T = tiles + t_begin;
 
     for (int i = lane; i < REP * 2 * (WIN + 1); i += 64) s_cnt[i] = 0;
-    for (uint32_t i = lane; i < FAR_SLOTS; i += 64) { s_fkey[i] = FAR_EMPTY; s_fcnt[i] = 0; }
+    if constexpr (!LEAN)
+        for (uint32_t i = lane; i < FAR_SLOTS; i += 64) { s_fkey[i] = FAR_EMPTY; s_fcnt[i] = 0; }
     auto far_add = [&](uint32_t col, int32_t x) {
         // two candidate slots per key (the cold far targets of paralogue rows come first and sit in the table too: with one slot per key a
         // sixth of the hot ones found theirs taken)
@@ -273,7 +295,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HAS_K ? 5 : 
     // number issued per tile must not depend on the path -- otherwise the compiler has to assume the fewest, and every walk
     // waits for the prefetch issued just before it.  Groups beyond the tile's ng fail the descriptor's range check: no memory access.
     auto issue = [&](const SellTile &d, Buf &bf) {
-        const bool fast = d.flags() & (SELL_FAST | SELL_FAR); // uniform: the tile has a block (a far tile's window part is a fast tile's)
+        const bool fast = d.flags() & (LEAN ? SELL_FAST : (SELL_FAST | SELL_FAR)); // uniform: the tile has a block (a far tile's window part is a fast tile's)
         const bool farb = FARPF && (d.flags() & SELL_FAR);
         const SellBlock blk(stream + (fast ? d.off16 * 16 : 0), d.meta, farb ? 64u + d.nf() * 256u : 0u);
         if (FARPF) { // two more loads, whatever the tile (a tile without a far list reads its own head again)
@@ -713,6 +735,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HAS_K ? 5 : 
                 }
             } else walk(d, bf, which, BoolTag<false>());
         }
+        else if constexpr (LEAN) {} // (the host launches this instantiation over lists without any other tile)
         else if (!HAS_K && (d.flags() & SELL_FAR)) walk(d, bf, which, BoolTag<true>());
         else if (d.flags() & SELL_FAR) far_tile(d); // with multiplicities: the generic row walk over the tile's block
         else slow_tile(d);
@@ -731,6 +754,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HAS_K ? 5 : 
     load_window(dA.wbase);
     uint32_t cur_base = dA.wbase;
     __syncthreads();
+#if defined(MMG_K1_STAMPS)
+    const uint64_t st_window = __builtin_amdgcn_s_memtime();
+#endif
     issue(dA, bufA);
     __builtin_amdgcn_sched_barrier(0); // A's block is requested before B's, here as in the loop (sell_multi_kernels.h): the waits are by count
     issue(dB, bufB);
@@ -742,12 +768,31 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(HAS_K ? 5 : 
         dA = nA;
         dB = nB;
     }
+#if defined(MMG_K1_STAMPS)
+    const uint64_t st_walked = __builtin_amdgcn_s_memtime();
+#endif
     __syncthreads();
     flush_window(cur_base);
-    for (uint32_t i = lane; i < FAR_SLOTS; i += 64) {
-        const int32_t v = s_fcnt[i];
-        if (v) global_count_add(gcnt, s_fkey[i], v);
+    if constexpr (!LEAN)
+        for (uint32_t i = lane; i < FAR_SLOTS; i += 64) {
+            const int32_t v = s_fcnt[i];
+            if (v) global_count_add(gcnt, s_fkey[i], v);
+        }
+#if defined(MMG_K1_STAMPS)
+    if (blockIdx.y == 0 && blockIdx.x < K1_STAMP_CAP) {
+        __builtin_amdgcn_s_waitcnt(0); // the flush's atomics have left the wave: "exit" is behind them
+        uint32_t hw, xcc;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+        const uint64_t st_exit = __builtin_amdgcn_s_memtime(), st_exit_rt = __builtin_amdgcn_s_memrealtime();
+        if (lane == 0) {
+            unsigned long long *o = g_k1_stamps + (size_t)blockIdx.x * K1_STAMP_WORDS;
+            o[0] = st_entry; o[1] = st_window; o[2] = st_walked; o[3] = st_exit; o[4] = st_entry_rt; o[5] = st_exit_rt;
+            o[6] = (uint64_t)blockIdx.x | ((uint64_t)nt << 32);
+            o[7] = (uint64_t)hw | ((uint64_t)xcc << 32);
+        }
     }
+#endif
 }
 
 } // namespace mmg

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import Config, ProblemDesc, ProblemInfo, SynthDesc, Timing, check
+from ._lib import Config, K1Info, ProblemDesc, ProblemInfo, SynthDesc, Timing, check
 
 
 def device_count():
@@ -67,6 +67,22 @@ class Problem:
         inf = ProblemInfo()
         check(self._lib.mmg_problem_info_get(self._h, C.byref(inf)))
         return inf
+
+    @property
+    def k1_info(self):
+        """The single-chain sample launch: which instantiation of the kernel runs, and the modelled cost of its ranges."""
+        inf = K1Info()
+        check(self._lib.mmg_problem_k1_info_get(self._h, C.byref(inf)))
+        return inf
+
+    def k1_ranges(self):
+        """(bound, cum_cost, cum_groups): range c of the single-chain launch holds list entries [bound[c], bound[c + 1]), costs
+        cum_cost[c + 1] - cum_cost[c] in the units of the model that cut the ranges, and its blocks hold
+        cum_groups[c + 1] - cum_groups[c] groups of 256 bytes."""
+        n = self.info.sample_grid + 1
+        bound, cum, grp = np.zeros(n, np.uint64), np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+        check(self._lib.mmg_problem_k1_ranges(self._h, _ptr(bound), _ptr(cum), _ptr(grp)))
+        return bound, cum, grp
 
     def download(self, with_k=False):
         """The CSR in STORED order (caller's transcript numbering): what a checker replays row by row."""
@@ -606,7 +622,8 @@ def selftest_option(option, value):
 OPT = dict(sample_kernel=_lib.OPT_SAMPLE_KERNEL, force_idx64=_lib.OPT_FORCE_IDX64, sell_waves_per_cu=_lib.OPT_SELL_WAVES_PER_CU,
            em_kernel=_lib.OPT_EM_KERNEL, em_grid=_lib.OPT_EM_GRID, fuse_chains=_lib.OPT_FUSE_CHAINS, cnt_replicas=_lib.OPT_CNT_REPLICAS, group_fail=_lib.OPT_GROUP_FAIL, derive_order=_lib.OPT_DERIVE_ORDER,
            wire_check=_lib.OPT_WIRE_CHECK, bigk_per_wave=_lib.OPT_BIGK_PER_WAVE, bigk_side_stream=_lib.OPT_BIGK_SIDE_STREAM,
-           conv_slab=_lib.OPT_CONV_SLAB, contrast_slab=_lib.OPT_CONTRAST_SLAB, pool_slab=_lib.OPT_POOL_SLAB, pairs_slab=_lib.OPT_PAIRS_SLAB, fold_slab=_lib.OPT_FOLD_SLAB, sim_chunk=_lib.OPT_SIM_CHUNK, iso_slab=_lib.OPT_ISO_SLAB)
+           conv_slab=_lib.OPT_CONV_SLAB, contrast_slab=_lib.OPT_CONTRAST_SLAB, pool_slab=_lib.OPT_POOL_SLAB, pairs_slab=_lib.OPT_PAIRS_SLAB, fold_slab=_lib.OPT_FOLD_SLAB, sim_chunk=_lib.OPT_SIM_CHUNK, iso_slab=_lib.OPT_ISO_SLAB,
+           k1_lean=_lib.OPT_K1_LEAN, k1_range_cost=_lib.OPT_K1_RANGE_COST, k1_ranges=_lib.OPT_K1_RANGES)
 
 
 class options:
