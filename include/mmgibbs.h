@@ -249,7 +249,10 @@ typedef struct mmg_k1_info {
 int mmg_problem_k1_info_get(const mmg_problem *p, mmg_k1_info *info);
 /* The ranges themselves: bound[0 .. n] (n = mmg_problem_info.sample_grid) are list entries, range c holds entries [bound[c], bound[c + 1]);
  * cum_cost[c] is the modelled cost of the entries in front of bound[c], cum_groups[c] the 256-byte groups of their blocks (whatever the
- * model).  Any may be NULL.  MMG_ERR_STATE without a sliced-ELL stream. */
+ * model).  The list is every tile in stored order -- unless the problem has tiles with multiplicities: then it is the list WITHOUT
+ * them (they have a launch and ranges of their own), entry e is the e-th tile without multiplicities and bound[n] = mmg_k1_info.n_list
+ * is their number, not the number of tiles; a problem whose every tile has multiplicities has the single empty entry (n_list = 1, cost 0).
+ * Any may be NULL.  MMG_ERR_STATE without a sliced-ELL stream. */
 int mmg_problem_k1_ranges(const mmg_problem *p, uint64_t *bound, uint64_t *cum_cost, uint64_t *cum_groups);
 /* Copies the device CSR back in STORED order (row_ptr m+1 u64, col_idx nnz u32 in the caller's transcript numbering,
  * k m u32; any may be NULL): what a checker needs to replay the chain row by row -- stored row i walks its hits in the
@@ -549,7 +552,8 @@ enum {
                                       that has far, CSR-walked or multiplicity tiles; default: wherever the list allows it */
     MMG_OPT_K1_RANGE_COST = 23,    /* 0: the ranges of the k = 1 launches cut by a constant per tile, as before the tiles were priced by their groups;
                                       v >= 1: a register-path tile priced v + 1 per group of its block (the A/B of the ratio; default 6) */
-    MMG_OPT_K1_RANGES = 24,        /* v >= 1: at most v ranges (workgroups) per k = 1 launch, one generation, no tapered end (long ranges on small inputs) */
+    MMG_OPT_K1_RANGES = 24,        /* v >= 1: at most v ranges (workgroups) per launch over a tile list (mmg_selftest_k1_lists names the five), one generation,
+                                      no tapered end (long ranges on small inputs) */
     MMG_OPT_COUNT_ = 25
 };
 int mmg_selftest_option(int option, int value);
@@ -574,6 +578,11 @@ int mmg_selftest_kernel_info(int device, int *vgprs, int *lds_bytes, int *scratc
 /* The same about the instantiation the single-chain launch of a problem with 32-bit offsets runs for (lean, fixed_walk) as
  * mmg_k1_info reports them. */
 int mmg_selftest_k1_kernel_info(int device, int lean, int fixed_walk, int *vgprs, int *lds_bytes, int *scratch_bytes, int *resident_per_cu);
+/* The five tile lists a sample call of the problem can launch over -- 0: the main list (with multiplicity tiles: the list without them,
+ * as mmg_problem_k1_ranges), 1: the tiles with multiplicities, 2 / 3: the register-path tiles of chains in pairs / in fours, 4: the far
+ * and CSR-walked tiles of paired chains -- out[3 * i + 0 .. 2] = entries of list i, its ranges, the entries of its longest range; all 0
+ * for a list the problem does not have (and without a sliced-ELL stream).  MMG_OPT_K1_RANGES = v caps the ranges of every one at v. */
+int mmg_selftest_k1_lists(const mmg_problem *p, uint64_t *out);
 /* Evaluates the library's own log / exp / sqrt / 1/x on x[0..n) (device >= 0: in a kernel
  * on that device; device == -1: the host instantiation of the same inline code). */
 int mmg_selftest_math(int device, int64_t n, const double *x, double *out_log, double *out_exp,

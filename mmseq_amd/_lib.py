@@ -125,6 +125,7 @@ SYMBOLS = {
     "mmg_problem_k1_info_get": (C.c_int, [C.c_void_p, C.POINTER(K1Info)]),
     "mmg_problem_k1_ranges": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmg_selftest_k1_kernel_info": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "mmg_selftest_k1_lists": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mmg_problem_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mmg_problem_tx_perm": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mmg_selftest_option": (C.c_int, [C.c_int, C.c_int]),

@@ -232,6 +232,9 @@ struct mmg_problem {
     uint64_t range_cost_max = 0, range_cost_sum = 0, range_count = 0; // modelled cost of the single-chain launch's non-empty ranges
     uint64_t range_tiles_max = 0;                                     // tiles of its longest range
     std::vector<uint64_t> h_chunk1, h_chunk1_groups;                  // its ranges: entries of the list h_cum1 prices; groups in front of every bound
+    // the five tile lists a sample call can launch over (main or list 1, multiplicity, pairs, fours, far / CSR of the paired chains):
+    // entries, ranges, entries of the longest range (mmg_selftest_k1_lists); all 0 for a list the problem does not have
+    uint64_t k1_lists[5][3] = {};
     bool groups_reordered = false; // tx_order given and the library reordered its groups (spec version 7)
     bool order_skipped = false;    // an order from the hit graph was called for but not tried (device memory) or could not be built: the caller's order stands
     bool renumbered() const { return !h_int_of_ext.empty(); }

@@ -181,6 +181,13 @@ static hipError_t upload_ranges(const std::vector<uint64_t> &chunk, const std::v
     return hipMemcpy(d_out.get(), h.data(), h.size() * sizeof(uint64_t), hipMemcpyHostToDevice);
 }
 
+// what mmg_selftest_k1_lists reports about a list: its entries, its ranges, the entries of its longest range
+static void note_list(uint64_t (&out)[3], uint64_t entries, const std::vector<uint64_t> &chunk)
+{
+    out[0] = entries; out[1] = chunk.size() - 1; out[2] = 0;
+    for (size_t c = 0; c + 1 < chunk.size(); ++c) out[2] = std::max(out[2], chunk[c + 1] - chunk[c]);
+}
+
 // List entries per workgroup of k_sample_bigk (one wave): 64 -- a row per lane, no second helping.  Measured (profiles/r06_bigk_ab.md):
 // longer pieces, whose lanes fetch the next row when they finish one, lose to it at every list length (2 M rows: 1.17 ms at 64, 1.18 /
 // 1.21 / 1.36 at 128 / 256 / 512; 262 k rows: 0.33 ms at 64, 0.36 / 0.40 / 0.47 at 96 / 128 / 192) -- the canonical order already puts rows
@@ -410,7 +417,9 @@ static int problem_build_sell(mmg_problem *p, const std::vector<uint64_t> &seg_s
             if (st[t].flags() & SELL_HASK) { sk.push_back(st[t]); ck.push_back(ck.back() + (cumk[t + 1] - cumk[t])); p->h_listk_tile.push_back((uint32_t)t); }
             else { s1.push_back(st[t]); c1.push_back(c1.back() + (cum1[t + 1] - cum1[t])); p->h_list1_tile.push_back((uint32_t)t); }
         }
-        const uint64_t g1 = std::max<uint64_t>(1, std::min<uint64_t>(s1.size(), grid)), gk = std::max<uint64_t>(1, std::min<uint64_t>(sk.size(), 4 * resident_grid(true))); // (a multiplicity tile costs tens of register-path tiles: short ranges, several generations, even out the tail)
+        // (a multiplicity tile costs tens of register-path tiles: short ranges, several generations, even out the tail; MMG_OPT_K1_RANGES caps them)
+        const uint64_t capk = opt(MMG_OPT_K1_RANGES) >= 1 ? (uint64_t)opt(MMG_OPT_K1_RANGES) : 4 * resident_grid(true);
+        const uint64_t g1 = std::max<uint64_t>(1, std::min<uint64_t>(s1.size(), grid)), gk = std::max<uint64_t>(1, std::min<uint64_t>(sk.size(), capk));
         if (s1.empty()) { SellTile e; e.off16 = 0; e.r0 = 0; e.wbase = 0; e.meta = sell_meta(0, 0, SELL_EMPTY); s1.push_back(e); c1.push_back(0); }
         std::vector<uint64_t> r1, rk;
         weighted_chunks(c1, g1, r1);
@@ -421,6 +430,7 @@ static int problem_build_sell(mmg_problem *p, const std::vector<uint64_t> &seg_s
         HIP_TRY(p->d_sell_tiles_k.alloc(sk.size()));
         HIP_TRY(hipMemcpy(p->d_sell_tiles_k.get(), sk.data(), sk.size() * sizeof(SellTile), hipMemcpyHostToDevice));
         HIP_TRY(upload_ranges(rk, sk, p->d_sell_chunk_k));
+        note_list(p->k1_lists[1], sk.size(), rk);
         HIP_TRY(upload_ranges(r1, s1, p->d_sell_chunk));
         p->h_cum1 = c1; p->h_cumk = ck;
         p->grid_sell_k = (int)gk;
@@ -429,6 +439,7 @@ static int problem_build_sell(mmg_problem *p, const std::vector<uint64_t> &seg_s
     }
     if (!n_hask) p->h_cum1 = cum1;
     p->h_chunk1 = chunk; // (with SELL_HASK tiles: r1, over the list without them)
+    note_list(p->k1_lists[0], p->h_cum1.size() - 1, chunk); // (as mmg_k1_info.n_list: a list without a tile is its one empty entry)
     p->range_cost_max = p->range_cost_sum = p->range_count = p->range_tiles_max = 0;
     p->h_chunk1_groups.assign(chunk.size(), 0); // groups of the blocks in front of every bound: what the timeline sets durations against
     for (size_t c = 0; c + 1 < chunk.size(); ++c) {
@@ -478,14 +489,17 @@ static int problem_build_sell(mmg_problem *p, const std::vector<uint64_t> &seg_s
                 weighted_chunks_tapered(cf, gen, plain_ranges ? 0 : rq, cq);
                 HIP_TRY(upload_ranges(cq, sf, p->d_sell_chunk_m[q]));
                 p->grid_sell_m[q] = (int)(cq.size() - 1);
+                note_list(p->k1_lists[2 + q], nf, cq);
             }
         }
         if (!sx.empty()) {
             HIP_TRY(p->d_sell_tiles_x.alloc(sx.size()));
             HIP_TRY(hipMemcpy(p->d_sell_tiles_x.get(), sx.data(), sx.size() * sizeof(SellTile), hipMemcpyHostToDevice));
             std::vector<uint64_t> rx;
-            weighted_chunks(cx, std::max<uint64_t>(1, std::min<uint64_t>(sx.size(), resident_grid(false))), rx);
+            const uint64_t capx = opt(MMG_OPT_K1_RANGES) >= 1 ? (uint64_t)opt(MMG_OPT_K1_RANGES) : resident_grid(false);
+            weighted_chunks(cx, std::max<uint64_t>(1, std::min<uint64_t>(sx.size(), capx)), rx);
             HIP_TRY(upload_ranges(rx, sx, p->d_sell_chunk_x));
+            note_list(p->k1_lists[4], sx.size(), rx);
             p->grid_sell_x = (int)(rx.size() - 1);
             p->device_bytes += sx.size() * sizeof(SellTile);
         }
@@ -1171,6 +1185,14 @@ extern "C" int mmg_problem_k1_ranges(const mmg_problem *p, uint64_t *bound, uint
         if (cum_cost) cum_cost[c] = p->h_cum1[p->h_chunk1[c]];
         if (cum_groups) cum_groups[c] = p->h_chunk1_groups[c];
     }
+    return MMG_OK;
+}
+
+extern "C" int mmg_selftest_k1_lists(const mmg_problem *p, uint64_t *out)
+{
+    if (!p || !out) return fail(MMG_ERR_ARG, "NULL argument");
+    for (int i = 0; i < 5; ++i)
+        for (int j = 0; j < 3; ++j) out[3 * i + j] = p->use_sell ? p->k1_lists[i][j] : 0;
     return MMG_OK;
 }
 

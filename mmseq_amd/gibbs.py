@@ -76,13 +76,24 @@ class Problem:
         return inf
 
     def k1_ranges(self):
-        """(bound, cum_cost, cum_groups): range c of the single-chain launch holds list entries [bound[c], bound[c + 1]), costs
+        """(bound, cum_cost, cum_groups): range c of the single-chain launch holds list entries [bound[c], bound[c + 1]) -- tiles, or
+        with multiplicity tiles entries of the list without them -- costs
         cum_cost[c + 1] - cum_cost[c] in the units of the model that cut the ranges, and its blocks hold
         cum_groups[c + 1] - cum_groups[c] groups of 256 bytes."""
         n = self.info.sample_grid + 1
         bound, cum, grp = np.zeros(n, np.uint64), np.zeros(n, np.uint64), np.zeros(n, np.uint64)
         check(self._lib.mmg_problem_k1_ranges(self._h, _ptr(bound), _ptr(cum), _ptr(grp)))
         return bound, cum, grp
+
+    K1_LISTS = ("main", "multiplicity", "pairs", "fours", "far_csr")
+
+    def k1_lists(self):
+        """{list: (entries, ranges, entries of the longest range)} of the five tile lists a sample call can launch over: the main list
+        (with multiplicity tiles: the list without them), the tiles with multiplicities, the register-path tiles of chains in pairs and
+        in fours, the far and CSR-walked tiles of paired chains.  (0, 0, 0): the problem has no such list."""
+        out = np.zeros(15, np.uint64)
+        check(self._lib.mmg_selftest_k1_lists(self._h, _ptr(out)))
+        return {name: tuple(int(v) for v in out[3 * i:3 * i + 3]) for i, name in enumerate(self.K1_LISTS)}
 
     def download(self, with_k=False):
         """The CSR in STORED order (caller's transcript numbering): what a checker replays row by row."""

@@ -172,13 +172,31 @@ def ladder(periods, variant, seed=0):
 
 
 # ---- the tile cut and the window rule, restated (mmgibbs.hip: problem_build_sell) ---------------------------------------------
-def tile_table(row_ptr, col_idx, k, seg_key, row_id_base=0):
-    """The tiles of a STORED problem (rows in canonical order, none empty).  seg_key: a row's (near, band), i.e. its layout key >> 18.
-    Returns a dict of per-tile arrays: r0, nrows, maxlen, ng, call, cmax, far, hask, odd (the tile starts on an odd row id), wbase
-    and slid (the window moved in front of the tile) as ONE range over all tiles gives them, fast."""
+def tile_table(row_ptr, col_idx, k, seg_key, row_id_base=0, max_seg=None):
+    """The tiles of a STORED problem.  seg_key: a row's (near, band), i.e. its layout key >> 18 (an empty row's is ignored: it belongs
+    to the run around it).  max_seg: the most runs of equal (near, band) the library cuts tiles by -- with more, the whole problem is
+    one run (rows kept in the caller's order); None: no limit.
+    Returns a dict of per-tile arrays: r0, nrows, nnz, maxlen, ng, call, cmax, far (the key's far bit), hask, knot1, kmax, odd (the tile
+    starts on an odd row id); wbase and slid (the window moved in front of the tile) as ONE range over all tiles gives them, fast;
+    and what the library derives before it lays the stream out (mmgibbs.hip: problem_build_sell; sell_kernels.h: k_tile_far):
+      qual      the tile is on the register path: hits, no row above 255 hits, all hits inside the window of its smallest hit's band
+      far_wbase, far_nn, far_nf   of a tile that has hits, does not qualify and has no row above 255 hits: the window base its rows
+                were sorted for (the band field of its first non-empty row's key), the most hits a row has inside that window and the
+                most it has outside -- far_nf = -1 where a row has a window hit behind a hit outside (not stored window-hits-first)
+      far_tile  such a tile with 0 <= far_nf <= 255: a block for the window hits plus a far list of far_nf entries
+      slow      a tile with hits that is neither: walked from the CSR
+      blk_ng    the groups of the tile's block in the stream: ng for qual, ceil(far_nn / 4) for far_tile, else 0."""
     rp = np.asarray(row_ptr).astype(np.int64)
+    col = np.asarray(col_idx)
     m = rp.size - 1
-    seg = np.flatnonzero(np.concatenate([[True], seg_key[1:] != seg_key[:-1]])).tolist() + [m]
+    L = np.diff(rp)
+    seg_key = np.asarray(seg_key, np.uint64)
+    ne = np.flatnonzero(L > 0)                                           # k_segment_starts: row 0, and a non-empty row whose key differs
+    starts = ne[1:][seg_key[ne[1:]] != seg_key[ne[:-1]]]                 # from the last non-empty row's in front of it
+    seg = sorted(set([0] + starts.tolist()))
+    if max_seg is not None and len(seg) > max_seg:
+        seg = [0]
+    seg = seg + [m]
     r0 = []
     for s, e in zip(seg[:-1], seg[1:]):
         r = s
@@ -186,21 +204,29 @@ def tile_table(row_ptr, col_idx, k, seg_key, row_id_base=0):
             r0.append(r)
             r += 64 - ((int(row_id_base) + r) & 1)                      # a tile spans at most 32 Philox blocks
     r0 = np.asarray(r0, np.int64)
-    seg_end = np.asarray(seg[1:], np.int64)[np.searchsorted(np.asarray(seg[1:]), r0, side="right")]
-    r1 = np.minimum(np.concatenate([r0[1:], [m]]), seg_end)
-    L = np.diff(rp)
-    t = dict(r0=r0, nrows=r1 - r0, maxlen=np.maximum.reduceat(L, r0), call=np.minimum.reduceat(col_idx, rp[r0]).astype(np.int64),
-             cmax=np.maximum.reduceat(col_idx, rp[r0]).astype(np.int64), odd=((int(row_id_base) + r0) & 1).astype(bool),
-             far=(seg_key[r0] >> np.uint64(45)).astype(bool))
-    kk = np.ones(m, np.int64) if k is None else np.asarray(k).astype(np.int64)
-    t["hask"] = np.add.reduceat((kk != 1).astype(np.int64), r0) > 0
-    t["ng"] = (t["maxlen"] + 3) // 4
     nt = r0.size
+    r1 = np.concatenate([r0[1:], [m]])
+    nnz = rp[r1] - rp[r0]
+    has = np.flatnonzero(nnz > 0)                                        # (reduceat over the tiles with hits: their first hits ascend strictly)
+    call, cmax = np.zeros(nt, np.int64), np.zeros(nt, np.int64)
+    if has.size:
+        call[has] = np.minimum.reduceat(col, rp[r0[has]]).astype(np.int64)
+        cmax[has] = np.maximum.reduceat(col, rp[r0[has]]).astype(np.int64)
+    t = dict(r0=r0, nrows=r1 - r0, nnz=nnz, maxlen=np.maximum.reduceat(L, r0), call=call, cmax=cmax,
+             odd=((int(row_id_base) + r0) & 1).astype(bool))
+    first = np.minimum(np.searchsorted(ne, r0), max(ne.size - 1, 0))     # the tile's first non-empty row (a tile with hits has one)
+    first = ne[first] if ne.size else np.zeros(nt, np.int64)
+    t["far"] = (seg_key[first] >> np.uint64(45)).astype(bool) & (nnz > 0) if m else np.zeros(nt, bool)
+    kk = np.ones(m, np.int64) if k is None else np.asarray(k).astype(np.int64)
+    t["knot1"] = np.add.reduceat((kk != 1).astype(np.int64), r0)
+    t["kmax"] = np.maximum.reduceat(kk, r0)
+    t["hask"] = t["knot1"] > 0
+    t["ng"] = (t["maxlen"] + 3) // 4
     wbase, slid, fast = np.zeros(nt, np.int64), np.zeros(nt, bool), np.zeros(nt, bool)
     have, cur = False, 0
     for i in range(nt):
         if t["far"][i]:                                                  # its own window: the home band's
-            cur, have = int(seg_key[r0[i]] & np.uint64((1 << 45) - 1)) * BAND, True
+            cur, have = int(seg_key[first[i]] & np.uint64((1 << 45) - 1)) * BAND, True
             wbase[i], slid[i] = cur, True
             continue
         # keep the window in force when the whole tile lies inside it; otherwise slide to the band start of its smallest id
@@ -210,6 +236,30 @@ def tile_table(row_ptr, col_idx, k, seg_key, row_id_base=0):
         wbase[i], slid[i] = cur, not inside
         fast[i] = t["maxlen"][i] <= 255 and t["nrows"][i] <= 64 and t["cmax"][i] < cur + WIN
     t.update(wbase=wbase, slid=slid, fast=fast)
+    # the register path, and k_tile_far's answers for the tiles that miss it
+    short = (nnz > 0) & (t["maxlen"] <= 255) & (t["nrows"] <= 64)
+    t["qual"] = short & (cmax < (call & ~(BAND - 1)) + WIN)
+    cand = short & ~t["qual"]
+    far_wbase = np.where(cand, (seg_key[first] & np.uint64((1 << 45) - 1)).astype(np.int64) * BAND, 0) if m else np.zeros(nt, np.int64)
+    far_nn, far_nf = np.zeros(nt, np.int64), np.full(nt, -1, np.int64)
+    if cand.any():
+        rid = np.repeat(np.arange(m, dtype=np.int64), L)
+        tid = np.searchsorted(r0, rid, side="right") - 1
+        sel = cand[tid]
+        rid, tid, c = rid[sel], tid[sel], col[sel].astype(np.int64)
+        pos = np.flatnonzero(sel) - rp[rid]                              # the hit's place in its row
+        inw = ((c - far_wbase[tid]) & 0xffffffff) < WIN                  # (u32 wrap-around: a hit below the window is outside)
+        n_in = np.bincount(rid, weights=inw, minlength=m).astype(np.int64)
+        lead = np.bincount(rid, weights=inw & (pos < n_in[rid]), minlength=m).astype(np.int64)
+        n_out = np.where(lead == n_in, L - n_in, 1 << 32)               # a window hit behind a far one: not stored window-hits-first
+        ct = np.flatnonzero(cand)
+        far_nn[ct] = np.maximum.reduceat(n_in, r0)[ct]
+        nf = np.maximum.reduceat(n_out, r0)[ct]
+        far_nf[ct] = np.where(nf <= 255, nf, -1)
+    t["far_wbase"], t["far_nn"], t["far_nf"] = far_wbase, far_nn, far_nf
+    t["far_tile"] = cand & (far_nf >= 0)
+    t["slow"] = (nnz > 0) & ~t["qual"] & ~t["far_tile"]
+    t["blk_ng"] = np.where(t["qual"], t["ng"], np.where(t["far_tile"], (far_nn + 3) // 4, 0))
     return t
 
 

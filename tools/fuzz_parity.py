@@ -5,10 +5,14 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 
 
-def one_case(seed, gpu, orc, verbose=True):
+def generate(seed, orc, max_rows=60000):
+    """The random problem of a case and the options fuzz_parity runs it under: everything up to the upload.  Returns the generator (the
+    caller's further draws continue its stream) and a dict: pk (the oracle's Problem in the caller's row order), k, T, opts, keep_rows,
+    tx_order, mu0, uh (the oracle's start values, with dead and rescaled entries drawn in), row_id_base, and the drawn shape.  max_rows: the
+    bound of the row count (a tool whose cases cost more per row lowers it; the number of draws stays)."""
     rng = np.random.default_rng(seed)
     T = int(rng.choice([40, 300, 2000, 20000]))
-    R = int(rng.integers(200, 60000))
+    R = int(rng.integers(200, max_rows))
     avg = float(rng.choice([1.5, 3, 8, 20, 45]))
     sort = bool(rng.integers(0, 4) != 0)
     far = float(rng.choice([0.0, 0.0, 0.03, 0.5]))      # rows with a hit anywhere in the transcriptome: far tiles
@@ -56,11 +60,19 @@ def one_case(seed, gpu, orc, verbose=True):
         tx_order = (rng.permutation(T).astype(np.uint64) // np.uint64(int(rng.integers(1, 9)))) << np.uint64(32)
     elif genes:                                          # the CLI's keys for the generator's genes: gene << 32 | transcript (spec 7: the genes may be reordered)
         tx_order = ((np.arange(T, dtype=np.uint64) // np.uint64(genes)) << np.uint64(32)) | np.arange(T, dtype=np.uint64)
+    mu0, uh = orc.start_values(pk)
+    if rng.integers(0, 3) == 0: mu0[rng.integers(0, T, size=max(1, T // 20))] = 0.0
+    if rng.integers(0, 4) == 0: mu0 *= 10.0 ** rng.uniform(-120, 120, size=T)
+    rid0 = int(rng.choice([0, 0, 12345, (1 << 32) - 100, (1 << 33) - 40, (1 << 40) + 7]))    # shard offset: crosses 2^32 / 2^33 (the row stream's key changes) in the middle of a problem
+    return rng, dict(pk=pk, k=k, T=T, opts=opts, keep_rows=keep_rows, tx_order=tx_order, mu0=mu0, uh=uh, row_id_base=rid0,
+                     avg=avg, far=far, sort=sort, dups=dups, uniform=uni, genes=genes)
+
+
+def one_case(seed, gpu, orc, verbose=True):
+    rng, g = generate(seed, orc)
+    pk, k, T, opts, keep_rows, tx_order, mu0, uh, rid0 = (g[x] for x in ("pk", "k", "T", "opts", "keep_rows", "tx_order", "mu0", "uh", "row_id_base"))
+    avg, far, sort, dups = g["avg"], g["far"], g["sort"], g["dups"]
     with gpu.options(**opts):
-        mu0, uh = orc.start_values(pk)
-        if rng.integers(0, 3) == 0: mu0[rng.integers(0, T, size=max(1, T // 20))] = 0.0
-        if rng.integers(0, 4) == 0: mu0 *= 10.0 ** rng.uniform(-120, 120, size=T)
-        rid0 = int(rng.choice([0, 0, 12345, (1 << 32) - 100, (1 << 33) - 40, (1 << 40) + 7]))    # shard offset: crosses 2^32 / 2^33 (the row stream's key changes) in the middle of a problem
         prob = gpu.Problem.from_csr(pk.row_ptr, pk.col_idx, pk.l, k=pk.k, row_id_base=rid0, keep_rows=keep_rows, tx_order=tx_order)
         d_rp, d_ci, d_k = prob.download(with_k=True)     # stored order: what the oracle replays
         pk = orc.Problem(d_rp, d_ci, pk.l, k=(d_k if k is not None else None))
