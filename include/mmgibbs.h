@@ -554,9 +554,18 @@ enum {
                                       v >= 1: a register-path tile priced v + 1 per group of its block (the A/B of the ratio; default 6) */
     MMG_OPT_K1_RANGES = 24,        /* v >= 1: at most v ranges (workgroups) per launch over a tile list (mmg_selftest_k1_lists names the five), one generation,
                                       no tapered end (long ranges on small inputs) */
-    MMG_OPT_COUNT_ = 25
+    MMG_OPT_SERIES_GROUPS = 25,    /* v >= 1: at most v workgroups per launch of a workspace instantiation of k_series_summary, k_convergence,
+                                      k_pooled_summary and k_contrast_summary (a workgroup walks several series on small inputs).  The workspaces
+                                      keep their size: every *_device_bytes formula holds as stated.  Under the option such a launch also
+                                      starts from result columns of 0xFF bytes: a series no workgroup reached reads NaN, return code -1 */
+    MMG_OPT_COUNT_ = 26
 };
 int mmg_selftest_option(int option, int value);
+/* The last launch in this process of a workspace instantiation (the series too long for LDS: S > 8192, or C S > 8192) of kernel 0:
+ * k_series_summary (mmg_summary_finish, mmg_collapse_summarize, the chains' columns of mmg_pooled_*), 1: k_convergence, 2: k_pooled_summary,
+ * 3: k_contrast_summary -- *grid workgroups walked *count series.  Recorded on the host where the launch is made; zeros before any such
+ * launch.  MMG_ERR_ARG for another kernel or a NULL pointer.  (Tests: MMG_OPT_SERIES_GROUPS reached the launch.) */
+int mmg_selftest_series_launch(int kernel, uint32_t *grid, uint32_t *count);
 /* What the library holds: counts[3] = device buffers, streams, events (tests: every call gives back what it acquired). */
 int mmg_selftest_live(int64_t *counts);
 /* A sampler's pool of timing events: *pool events, *free_idx of them on the free list, *pending_idx in pairs not yet harvested

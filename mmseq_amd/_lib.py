@@ -39,7 +39,7 @@ class MMGError(RuntimeError):
 
 LAYOUT_CANONICAL, LAYOUT_KEEP_ROWS = 0, 1
 # mmg_selftest_option ids
-OPT_SAMPLE_KERNEL, OPT_FORCE_IDX64, OPT_SELL_WAVES_PER_CU, OPT_EM_KERNEL, OPT_EM_GRID, OPT_FUSE_CHAINS, OPT_CNT_REPLICAS, OPT_GROUP_FAIL, OPT_DERIVE_ORDER, OPT_WIRE_CHECK, OPT_BIGK_PER_WAVE, OPT_BIGK_SIDE_STREAM, OPT_FAIL_ALLOC, OPT_CONV_SLAB, OPT_DIFF_TRACE_ROWS, OPT_ASSIGN_WAVES, OPT_CONTRAST_SLAB, OPT_POOL_SLAB, OPT_PAIRS_SLAB, OPT_FOLD_SLAB, OPT_SIM_CHUNK, OPT_ISO_SLAB, OPT_K1_LEAN, OPT_K1_RANGE_COST, OPT_K1_RANGES = range(25)
+OPT_SAMPLE_KERNEL, OPT_FORCE_IDX64, OPT_SELL_WAVES_PER_CU, OPT_EM_KERNEL, OPT_EM_GRID, OPT_FUSE_CHAINS, OPT_CNT_REPLICAS, OPT_GROUP_FAIL, OPT_DERIVE_ORDER, OPT_WIRE_CHECK, OPT_BIGK_PER_WAVE, OPT_BIGK_SIDE_STREAM, OPT_FAIL_ALLOC, OPT_CONV_SLAB, OPT_DIFF_TRACE_ROWS, OPT_ASSIGN_WAVES, OPT_CONTRAST_SLAB, OPT_POOL_SLAB, OPT_PAIRS_SLAB, OPT_FOLD_SLAB, OPT_SIM_CHUNK, OPT_ISO_SLAB, OPT_K1_LEAN, OPT_K1_RANGE_COST, OPT_K1_RANGES, OPT_SERIES_GROUPS = range(26)
 
 
 class ProblemDesc(C.Structure):
@@ -130,6 +130,7 @@ SYMBOLS = {
     "mmg_problem_tx_perm": (C.c_int, [C.c_void_p, C.c_void_p]),
     "mmg_selftest_option": (C.c_int, [C.c_int, C.c_int]),
     "mmg_selftest_live": (C.c_int, [C.c_void_p]),
+    "mmg_selftest_series_launch": (C.c_int, [C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "mmg_selftest_sampler_events": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mmg_selftest_kernel_info": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mmg_problem_get_l": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -144,8 +144,10 @@ int build(mmg_contrast *h, const mmg_contrast_desc *d)
     HIP_TRY(d_res.alloc((size_t)cap * (3 + (np ? np : 0)) + 1));
     HIP_TRY(d_rc.alloc(cap));
     HIP_TRY(d_gt.alloc(cap));
-    const uint32_t ws_groups = cap < CONTRAST_WS_GROUPS ? cap : CONTRAST_WS_GROUPS;
+    uint32_t ws_groups = cap < CONTRAST_WS_GROUPS ? cap : CONTRAST_WS_GROUPS;
     if (workspace_elems(S, ws_groups)) HIP_TRY(d_ws.alloc(workspace_elems(S, ws_groups)));
+    const int og = opt(MMG_OPT_SERIES_GROUPS);   // (fewer workgroups in the workspace of the size above)
+    if (og > 0 && (uint32_t)og < ws_groups) ws_groups = (uint32_t)og;
     h->log_ratio.resize(C); h->var.resize(C); h->tau.resize(C); h->p_gt.resize(C); h->rc.resize(C); h->pct.resize((size_t)C * np);
     std::vector<uint32_t> gt(cap);
     struct { double *log_ratio, *var, *tau; int32_t *rc; double *pct; } o{d_res.get(), d_res.get() + cap, d_res.get() + 2 * (size_t)cap, d_rc.get(),

@@ -57,8 +57,10 @@ struct ConvWork {
             if (g < 1) g = 1;
             if (g > CONV_WS_GROUPS) g = CONV_WS_GROUPS;
             if (g > cap) g = cap;
-            ws_groups = (uint32_t)g;
             HIPE_TRY(ws.alloc((size_t)2 * pp * g));
+            const int og = opt(MMG_OPT_SERIES_GROUPS);   // (fewer workgroups in the workspace of the size above)
+            if (og > 0 && (uint64_t)og < g) g = (uint64_t)og;
+            ws_groups = (uint32_t)g;
         }
         return hipSuccess;
     }

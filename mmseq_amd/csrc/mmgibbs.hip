@@ -29,8 +29,8 @@ extern "C" const char *mmg_last_error(void) { return g_err.c_str(); }
 extern "C" int mmg_abi_version(void) { return MMG_ABI_VERSION; }
 
 // self-test overrides (mmg_selftest_option): -1 = the library decides
-static std::atomic<int> g_opt[MMG_OPT_COUNT_] = {{-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}};
-static_assert(MMG_OPT_COUNT_ == 25, "one initialiser per option above");
+static std::atomic<int> g_opt[MMG_OPT_COUNT_] = {{-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}, {-1}};
+static_assert(MMG_OPT_COUNT_ == 26, "one initialiser per option above");
 static std::atomic<int64_t> g_acquired{0}; // acquisitions through the owners since MMG_OPT_FAIL_ALLOC was last set
 static std::atomic<int64_t> g_live[3] = {{0}, {0}, {0}};
 int mmg::opt(int o) { return g_opt[o].load(std::memory_order_relaxed); }

@@ -104,8 +104,10 @@ struct PoolWork {
             if (g < 1) g = 1;
             if (g > POOL_WS_GROUPS) g = POOL_WS_GROUPS;
             if (g > cap) g = cap;
-            ws_groups = (uint32_t)g;
             HIPE_TRY(get(ws, (size_t)pp * g));
+            const int og = opt(MMG_OPT_SERIES_GROUPS);   // (fewer workgroups in the workspace of the size above)
+            if (og > 0 && (uint64_t)og < g) g = (uint64_t)og;
+            ws_groups = (uint32_t)g;
         }
         return hipSuccess;
     }

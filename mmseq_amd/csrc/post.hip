@@ -7,6 +7,7 @@
 #include "mmg_host.h"
 #include "mmg_launch.h"
 
+#include <atomic>
 #include <cmath>
 #include <memory>
 #include <mutex>
@@ -89,6 +90,31 @@ static size_t series_workspace_bytes(uint32_t S)
     if (S <= 8192) return 0;
     return (size_t)SERIES_WS_GROUPS * 3 * next_pow2<size_t>(S) * 8;
 }
+
+// What the workspace instantiations were last launched with, by kernel (mmg_selftest_series_launch): grid << 32 | series.  Written on the
+// host by the launchers below, nothing of it is on the device.
+static std::atomic<uint64_t> g_series_launch[4] = {{0}, {0}, {0}, {0}};
+static inline unsigned walked(int kernel, uint32_t count, uint32_t groups)
+{
+    const uint32_t grid = count < groups ? count : groups;
+    g_series_launch[kernel].store((uint64_t)grid << 32 | count, std::memory_order_relaxed);
+    return grid;
+}
+// Under MMG_OPT_SERIES_GROUPS the result columns of such a launch start as 0xFF bytes (NaN, return code -1): a series that no workgroup
+// reached shows as that, not as what the allocator left in a fresh buffer -- which may be an earlier call's correct numbers.
+template <typename T> static void unreached(T *col, size_t count, hipStream_t st)
+{
+    if (col && count && opt(MMG_OPT_SERIES_GROUPS) > 0) (void)hipMemsetAsync(col, 0xFF, count * sizeof(T), st);
+}
+extern "C" int mmg_selftest_series_launch(int kernel, uint32_t *grid, uint32_t *count)
+{
+    if (kernel < 0 || kernel > 3) return fail(MMG_ERR_ARG, "kernel: 0 series summary, 1 convergence, 2 pooled summary, 3 contrast summary");
+    if (!grid || !count) return fail(MMG_ERR_ARG, "NULL argument");
+    const uint64_t v = g_series_launch[kernel].load(std::memory_order_relaxed);
+    *grid = (uint32_t)(v >> 32); *count = (uint32_t)v;
+    return MMG_OK;
+}
+
 template <bool LOG_MODE>
 static int launch_series(uint32_t count, uint32_t S, const double *X, uint32_t np, const int32_t *pind, const uint8_t *multi, const double *tw,
                          SeriesOut o, uint64_t *ws, hipStream_t st)
@@ -101,8 +127,13 @@ static int launch_series(uint32_t count, uint32_t S, const double *X, uint32_t n
     else if (S <= 8192) SERIES_IN_LDS(8192);
     else {
         if (!ws) return fail(MMG_ERR_STATE, "no workspace for the summary of a long trace");
-        hipLaunchKernelGGL((k_series_summary<0, LOG_MODE>), dim3(count < SERIES_WS_GROUPS ? count : SERIES_WS_GROUPS), dim3(256), 0, st, count, S, X, np, pind,
-                           multi, tw, o, ws);
+        uint32_t groups = SERIES_WS_GROUPS;   // (the workspace holds that many slices whatever the option says)
+        const int og = opt(MMG_OPT_SERIES_GROUPS);
+        if (og > 0 && (uint32_t)og < groups) groups = (uint32_t)og;
+        for (double *col : {o.log_mean, o.var, o.tau, o.mean, o.probit_mean, o.probit_sd}) unreached(col, count, st);
+        unreached(o.rc, count, st);
+        unreached(o.pct, (size_t)count * np, st);
+        hipLaunchKernelGGL((k_series_summary<0, LOG_MODE>), dim3(walked(0, count, groups)), dim3(256), 0, st, count, S, X, np, pind, multi, tw, o, ws);
     }
 #undef SERIES_IN_LDS
     HIP_TRY(hipGetLastError());
@@ -467,7 +498,10 @@ void mmg::launch_convergence(uint32_t cnt, uint32_t C, uint32_t S, const double 
     else if (cs <= 2048) CONV_IN_LDS(2048);
     else if (cs <= 4096) CONV_IN_LDS(4096);
     else if (cs <= 8192) CONV_IN_LDS(8192);
-    else hipLaunchKernelGGL((k_convergence<0>), dim3(cnt < ws_groups ? cnt : ws_groups), dim3(256), 0, st, cnt, C, S, X, inv_log10_p, rhat, ess_bulk, ess_tail, ws);
+    else {
+        for (double *col : {rhat, ess_bulk, ess_tail}) unreached(col, cnt, st);
+        hipLaunchKernelGGL((k_convergence<0>), dim3(walked(1, cnt, ws_groups)), dim3(256), 0, st, cnt, C, S, X, inv_log10_p, rhat, ess_bulk, ess_tail, ws);
+    }
 #undef CONV_IN_LDS
 }
 
@@ -495,7 +529,12 @@ void mmg::launch_contrast_summary(uint32_t cnt, uint32_t S, const double *R, uin
     else if (S <= 2048) CONTRAST_IN_LDS(2048);
     else if (S <= 4096) CONTRAST_IN_LDS(4096);
     else if (S <= 8192) CONTRAST_IN_LDS(8192);
-    else hipLaunchKernelGGL((k_contrast_summary<0>), dim3(cnt < ws_groups ? cnt : ws_groups), dim3(256), 0, st, cnt, S, R, np, pind, tw, o, ws);
+    else {
+        for (double *col : {log_ratio, var, tau}) unreached(col, cnt, st);
+        unreached(rc, cnt, st);
+        unreached(pct, (size_t)cnt * np, st);
+        hipLaunchKernelGGL((k_contrast_summary<0>), dim3(walked(3, cnt, ws_groups)), dim3(256), 0, st, cnt, S, R, np, pind, tw, o, ws);
+    }
 #undef CONTRAST_IN_LDS
 }
 
@@ -531,7 +570,12 @@ void mmg::launch_pooled_summary(bool log_mode, uint32_t cnt, uint32_t C, uint32_
     else if (cs <= 2048) POOLED_IN_LDS(2048);
     else if (cs <= 4096) POOLED_IN_LDS(4096);
     else if (cs <= 8192) POOLED_IN_LDS(8192);
-    else if (log_mode) hipLaunchKernelGGL((k_pooled_summary<0, true>), dim3(cnt < ws_groups ? cnt : ws_groups), dim3(256), 0, st, cnt, C, S, X, np, pind, cm, cv, ct, crc, multi, o, ws);
-    else hipLaunchKernelGGL((k_pooled_summary<0, false>), dim3(cnt < ws_groups ? cnt : ws_groups), dim3(256), 0, st, cnt, C, S, X, np, pind, cm, cv, ct, crc, multi, o, ws);
+    else {
+        for (double *col : {a, b, c, mcse2}) unreached(col, cnt, st);
+        unreached(rc, cnt, st);
+        unreached(pct, (size_t)cnt * np, st);
+        if (log_mode) hipLaunchKernelGGL((k_pooled_summary<0, true>), dim3(walked(2, cnt, ws_groups)), dim3(256), 0, st, cnt, C, S, X, np, pind, cm, cv, ct, crc, multi, o, ws);
+        else hipLaunchKernelGGL((k_pooled_summary<0, false>), dim3(walked(2, cnt, ws_groups)), dim3(256), 0, st, cnt, C, S, X, np, pind, cm, cv, ct, crc, multi, o, ws);
+    }
 #undef POOLED_IN_LDS
 }

@@ -634,7 +634,8 @@ OPT = dict(sample_kernel=_lib.OPT_SAMPLE_KERNEL, force_idx64=_lib.OPT_FORCE_IDX6
            em_kernel=_lib.OPT_EM_KERNEL, em_grid=_lib.OPT_EM_GRID, fuse_chains=_lib.OPT_FUSE_CHAINS, cnt_replicas=_lib.OPT_CNT_REPLICAS, group_fail=_lib.OPT_GROUP_FAIL, derive_order=_lib.OPT_DERIVE_ORDER,
            wire_check=_lib.OPT_WIRE_CHECK, bigk_per_wave=_lib.OPT_BIGK_PER_WAVE, bigk_side_stream=_lib.OPT_BIGK_SIDE_STREAM,
            conv_slab=_lib.OPT_CONV_SLAB, contrast_slab=_lib.OPT_CONTRAST_SLAB, pool_slab=_lib.OPT_POOL_SLAB, pairs_slab=_lib.OPT_PAIRS_SLAB, fold_slab=_lib.OPT_FOLD_SLAB, sim_chunk=_lib.OPT_SIM_CHUNK, iso_slab=_lib.OPT_ISO_SLAB,
-           k1_lean=_lib.OPT_K1_LEAN, k1_range_cost=_lib.OPT_K1_RANGE_COST, k1_ranges=_lib.OPT_K1_RANGES)
+           k1_lean=_lib.OPT_K1_LEAN, k1_range_cost=_lib.OPT_K1_RANGE_COST, k1_ranges=_lib.OPT_K1_RANGES,
+           series_groups=_lib.OPT_SERIES_GROUPS)
 
 
 class options:
@@ -653,6 +654,16 @@ class options:
             selftest_option(OPT[k], -1)
         return False
 
+
+SERIES_KERNELS = dict(series=0, convergence=1, pooled=2, contrast=3)
+
+
+def selftest_series_launch(kernel):
+    """mmg_selftest_series_launch: (workgroups, series) of the last launch in this process of the workspace instantiation of `kernel`
+    (a name of SERIES_KERNELS or its number); (0, 0) before any."""
+    g, c = C.c_uint32(0), C.c_uint32(0)
+    check(_lib.load().mmg_selftest_series_launch(int(SERIES_KERNELS.get(kernel, kernel)), C.byref(g), C.byref(c)))
+    return g.value, c.value
 
 
 def selftest_math(x, device):

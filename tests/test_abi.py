@@ -28,6 +28,30 @@ def test_library_exports_every_declared_symbol():
     assert lib.mmg_abi_version() == 8
 
 
+def test_selftest_options_and_the_series_launch_record():
+    """the option table of the binding is the header's, MMG_OPT_SERIES_GROUPS is its last entry, and mmg_selftest_series_launch answers
+    for its four kernels on the host alone: zeros while no workspace instantiation was launched (no device here), MMG_ERR_ARG otherwise"""
+    from mmseq_amd import _lib, gibbs
+    lib = _lib.load()
+    txt = open(os.path.join(ROOT, "include", "mmgibbs.h")).read()
+    ids = {name: int(v) for name, v in re.findall(r"\bMMG_(OPT_[A-Z0-9_]+?)_? = (\d+)", txt)}
+    count = ids.pop("OPT_COUNT")
+    assert count == 26 and sorted(ids.values()) == list(range(count))
+    assert {k: v for k, v in vars(_lib).items() if k.startswith("OPT_")} == ids
+    assert _lib.OPT_SERIES_GROUPS == 25 and gibbs.OPT["series_groups"] == 25 and sorted(gibbs.OPT.values()) == sorted(set(gibbs.OPT.values()))
+    assert lib.mmg_selftest_option(_lib.OPT_SERIES_GROUPS, 2) == 0 and lib.mmg_selftest_option(_lib.OPT_SERIES_GROUPS, -1) == 0
+    assert lib.mmg_selftest_option(count, 1) == 1
+    g, c = C.c_uint32(7), C.c_uint32(7)
+    if gibbs.device_count() == 0:
+        for kernel in range(4):
+            assert lib.mmg_selftest_series_launch(kernel, C.byref(g), C.byref(c)) == 0 and (g.value, c.value) == (0, 0)
+            assert gibbs.selftest_series_launch(kernel) == (0, 0)
+        assert gibbs.selftest_series_launch("contrast") == (0, 0)
+    for kernel in (-1, 4):
+        assert lib.mmg_selftest_series_launch(kernel, C.byref(g), C.byref(c)) == 1 and b"kernel" in lib.mmg_last_error()
+    assert lib.mmg_selftest_series_launch(0, None, C.byref(c)) == 1 and lib.mmg_selftest_series_launch(0, C.byref(g), None) == 1
+
+
 def test_struct_layouts_match_header():
     from mmseq_amd import _lib
     assert C.sizeof(_lib.ProblemDesc) == 72

@@ -10,6 +10,52 @@ from key_space_checks import probit_as241
 pytestmark = pytest.mark.gpu
 
 
+def order_stats(tr, pidx):
+    """the order statistics of every row of tr at the positions pidx (NaNs sort last, as on the device); NaN for a position outside"""
+    srt, S = np.sort(tr, axis=1), tr.shape[1]
+    if not len(pidx):
+        return np.empty((tr.shape[0], 0))
+    return np.stack([srt[:, i] if 0 <= i < S else np.full(tr.shape[0], np.nan) for i in pidx], axis=1)
+
+
+def check_log_series(r, tr, pidx, orc, rows):
+    """the log columns r (Summary.series) of the series tr [count, S]: percentiles bit for bit, the mean of the logged trace to the
+    rounding of log(), Sokal's var and tau of the series in `rows` against the oracle (pinned to the reference's compiled sokal.cc:
+    test_oracle_sokal.py), return code 201 and nothing else for a length that is no power of two"""
+    S = tr.shape[1]
+    pow2 = S & (S - 1) == 0
+    assert np.array_equal(r["percentiles"], order_stats(tr, pidx), equal_nan=True)
+    with np.errstate(divide="ignore"):
+        lt = np.log(tr)
+    np.testing.assert_allclose(r["log_mean"], lt.mean(axis=1), rtol=1e-12, atol=1e-12)
+    assert (r["rc"] == (0 if pow2 else 201)).all()
+    for i in rows:
+        rc, var, tau, m = orc.sokal(lt[i])
+        assert rc == (0 if pow2 else 201)
+        if pow2:
+            np.testing.assert_allclose([r["var"][i], r["tau"][i]], [var, tau], rtol=1e-9)
+
+
+def check_proportions(gpu, r, pr, mu, pidx):
+    """the proportion columns r (Summary.proportions) of the proportion series pr [count, S]; mu: the series whose gene has company"""
+    from scipy.special import ndtri
+    S = pr.shape[1]
+    assert np.array_equal(r["percentiles"], order_stats(pr, pidx), equal_nan=True)
+    np.testing.assert_allclose(r["mean"], pr.mean(axis=1), rtol=1e-12)
+    # bit for bit: AS 241 transcribed on the device's own logarithm, the sums one addition after the other in sample order (:1237-1262)
+    z = probit_as241(np.clip(pr[mu], 1e-9, 1 - 1e-9), lambda x: gpu.selftest_math(x, 0)["log"])
+    s1, s2 = np.add.accumulate(z, axis=1)[:, -1], np.add.accumulate(z * z, axis=1)[:, -1]
+    assert np.array_equal(r["probit_mean"][mu], s1 / S)
+    with np.errstate(invalid="ignore"):                        # (genes of one transcript, not compared: a constant series whose variance may round below 0)
+        assert np.array_equal(r["probit_sd"][mu], np.sqrt((s2 - s1 * s1 / S) / (S - 1.0)))
+    # ... and to the accuracy of AS 241 against scipy's ndtri, as before
+    z = ndtri(np.clip(pr[mu], 1e-9, 1 - 1e-9))
+    s1, s2 = z.sum(axis=1), (z * z).sum(axis=1)
+    np.testing.assert_allclose(r["probit_mean"][mu], s1 / S, rtol=1e-9, atol=1e-12)
+    np.testing.assert_allclose(r["probit_sd"][mu], np.sqrt((s2 - s1 * s1 / S) / (S - 1.0)), rtol=1e-7)
+    assert np.isinf(r["probit_mean"][~mu]).all() and np.isnan(r["probit_sd"][~mu]).all()   # :1243-1262 with a single-transcript gene
+
+
 def _setup(gpu, orc, trace_len, tx_order=False, seed=5):
     p, _ = orc.synth_problem(R=30000, T=900, avg_hits=5, seed=seed, sort=False)
     n = p.n
@@ -65,41 +111,17 @@ def test_device_summary_matches_numpy_and_the_pinned_sokal(gpu, orc, tx_order):
     assert np.array_equal(q.rows(gpu.SERIES_GENE, 17, 5), t_gene[:, 17:22].T)
 
     def check_series(kind, tr):
-        r = q.series(kind)
-        assert np.array_equal(r["percentiles"], np.sort(tr, axis=1)[:, pidx])
-        with np.errstate(divide="ignore"):
-            lt = np.log(tr)
-        np.testing.assert_allclose(r["log_mean"], lt.mean(axis=1), rtol=1e-12, atol=1e-12)
-        assert (r["rc"] == 0).all()
-        for i in range(0, tr.shape[0], max(1, tr.shape[0] // 150)):
-            rc, var, tau, m = orc.sokal(lt[i])                   # pinned to the reference's compiled sokal.cc (test_oracle_sokal.py)
-            assert rc == 0
-            np.testing.assert_allclose([r["var"][i], r["tau"][i]], [var, tau], rtol=1e-9)
+        check_log_series(q.series(kind), tr, pidx, orc, range(0, tr.shape[0], max(1, tr.shape[0] // 150)))
 
     check_series(gpu.SERIES_TRANSCRIPT, trace)
     check_series(gpu.SERIES_VIRTUAL, V)
     check_series(gpu.SERIES_IDENTICAL, t_ident)
     check_series(gpu.SERIES_GENE, t_gene)
 
-    from scipy.special import ndtri
     multi = np.array([len(genes[g]) > 1 for g in gene_of])
     for kind, pr, mu in ((gpu.SERIES_TRANSCRIPT, prop[:n], multi[:n]), (gpu.SERIES_VIRTUAL, prop[n:], multi[n:])):
-        r = q.proportions(kind)
-        assert np.array_equal(r["percentiles"], np.sort(pr, axis=1)[:, pidx])
-        np.testing.assert_allclose(r["mean"], pr.mean(axis=1), rtol=1e-12)
-        # bit for bit: AS 241 transcribed on the device's own logarithm, the sums one addition after the other in sample order (:1237-1262)
-        z = probit_as241(np.clip(pr, 1e-9, 1 - 1e-9), lambda x: gpu.selftest_math(x, 0)["log"])
-        s1, s2 = np.add.accumulate(z, axis=1)[:, -1], np.add.accumulate(z * z, axis=1)[:, -1]
         assert mu.sum() > 20
-        assert np.array_equal(r["probit_mean"][mu], (s1 / S)[mu])
-        with np.errstate(invalid="ignore"):                        # (genes of one transcript, not compared: a constant series whose variance may round below 0)
-            assert np.array_equal(r["probit_sd"][mu], np.sqrt((s2 - s1 * s1 / S) / (S - 1.0))[mu])
-        # ... and to the accuracy of AS 241 against scipy's ndtri, as before
-        z = ndtri(np.clip(pr, 1e-9, 1 - 1e-9))
-        s1, s2 = z.sum(axis=1), (z * z).sum(axis=1)
-        np.testing.assert_allclose(r["probit_mean"][mu], (s1 / S)[mu], rtol=1e-9, atol=1e-12)
-        np.testing.assert_allclose(r["probit_sd"][mu], np.sqrt((s2 - s1 * s1 / S) / (S - 1.0))[mu], rtol=1e-7)
-        assert np.isinf(r["probit_mean"][~mu]).all() and np.isnan(r["probit_sd"][~mu]).all()   # :1243-1262 with a single-transcript gene
+        check_proportions(gpu, q.proportions(kind), pr, mu, pidx)
     q.close()
 
 
@@ -146,19 +168,8 @@ def test_summary_of_long_traces(gpu, orc, S):
         for m in ms:
             t_gene[g] += trace[m]
     assert np.array_equal(q.rows(gpu.SERIES_GENE).T, t_gene)
-    pow2 = S & (S - 1) == 0
     for kind, tr in ((gpu.SERIES_TRANSCRIPT, trace), (gpu.SERIES_GENE, t_gene), (gpu.SERIES_VIRTUAL, V)):
-        r = q.series(kind)
-        assert np.array_equal(r["percentiles"], np.sort(tr, axis=1)[:, pidx])
-        with np.errstate(divide="ignore"):
-            lt = np.log(tr)
-        np.testing.assert_allclose(r["log_mean"], lt.mean(axis=1), rtol=1e-12, atol=1e-12)
-        assert (r["rc"] == (0 if pow2 else 201)).all()
-        for i in range(0, tr.shape[0], 7):
-            rc, var, tau, m = orc.sokal(lt[i])
-            assert rc == (0 if pow2 else 201)
-            if pow2:
-                np.testing.assert_allclose([r["var"][i], r["tau"][i]], [var, tau], rtol=1e-9)
+        check_log_series(q.series(kind), tr, pidx, orc, range(0, tr.shape[0], 7))
     gene_of = np.empty(n, np.int64)
     for g, ms in enumerate(genes):
         gene_of[ms] = g
